@@ -11,12 +11,17 @@ N > 1  : SNP-row shards, one rank per GPU, weak scaling: every rank holds config
          taken as given.  No torch in either case: genomic_pca_amd/launch.py carries the unique id, the barriers and the max.
 
 One JSON line on rank 0.  `value` is the configuration BASELINE.json names -- int8 genotypes resident in HBM -- on the engine's default
-GEMM path for them: exact-integer GEMMs, HBM-bound.  The same job with the genotypes resident as 2-bit codes (what both command lines
-choose for >= 1 024 samples: less HBM, faster kernels) is `packed_2bit_residency`; `f32_mfma_path` is the same job on
-v_mfma_f32_32x32x2_f32 (north_star's MFMA-fp32 roofline).  `roofline` is for the
-dominant kernel, from HIP events recorded on the engine's own stream inside the timed region; `parity` is
-max|dPC| against the oracle on a small seeded case; `cpu_baseline` is the oracle's f32 restatement ("port")
-timed on this box's host cores on a bounded sample (N = 1 only).
+GEMM path for them: exact-integer GEMMs, HBM-bound.  `roofline` is for the dominant kernel, from HIP events recorded on the engine's
+own stream inside the timed region.  A plain run times that headline path only: set-up, --warmup steps, --steps timed steps, the line.
+
+--full adds everything else the line has carried (N = 1 only; --no-second-path, --no-extras and --no-cpu-baseline drop parts of it):
+the same job with the genotypes resident as 2-bit codes (what both command lines choose for >= 1 024 samples: less HBM, faster
+kernels) is `packed_2bit_residency`; `f32_mfma_path` is the same job on v_mfma_f32_32x32x2_f32 (north_star's MFMA-fp32 roofline);
+the other BASELINE.json workloads at their own sizes (default shape only); `parity` is max|dPC| against the oracle on a small seeded
+case; `cpu_baseline` is the oracle's f32 restatement ("port") timed on the host's cores on a bounded sample.
+
+--dump-outputs DIR writes what the headline path returned after its last timed step as DIR/<name>.npy (dump_outputs), so that two
+builds can be compared output for output: the inputs are seeded, identical from run to run for the same arguments.
 """
 import argparse
 import json
@@ -164,6 +169,26 @@ TIMING_EVERY = 4
 
 def sampled_steps(steps):
     return -(-steps // TIMING_EVERY)
+
+
+DUMP_CAP_BYTES = {"scores": 16 << 20, "loadings": 32 << 20}   # --dump-outputs: 48 MB at most for the two large arrays
+DUMP_SAMPLE_SEED = 2025
+
+
+def dump_outputs(eng, out_dir):
+    """--dump-outputs: the arrays a caller of the timed path receives after its last step -- eigenvalues (k, f64), singular values
+    (k + oversample, f64), scores (samples x k, f64) and loadings (PCA SNPs x k, f32) -- as <out_dir>/<name>.npy.  An array over its
+    share of DUMP_CAP_BYTES is written as a seeded sample of its rows, in row order: the same rows for the same shape in every run."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"eigenvalues": eng.eigenvalues(), "singular_values": eng.singular_values()}
+    for name, fetch in (("scores", lambda: eng.scores(f64=True)), ("loadings", eng.loadings)):
+        x = fetch()
+        if x.nbytes > DUMP_CAP_BYTES[name]:
+            rows = DUMP_CAP_BYTES[name] // (x.shape[1] * x.itemsize)
+            x = x[np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(x.shape[0], size=rows, replace=False))]
+        arrays[name] = x
+    for name, x in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), x)
 
 
 def timed_run(eng, a, k, barrier, rdzv, min_warm_s=0.0):
@@ -374,7 +399,8 @@ def extra_config2_line(g, a, device):
                 "top_eigenvalues": [float(x) for x in e.eigenvalues()[:3]]}
 
 
-def streamed_run(g, a, M, N, k, storage, device, snp_offset, rdzv, uid_fn=None, steps=None, warmup=None, cache_gb=0.0, bench_hold=False):
+def streamed_run(g, a, M, N, k, storage, device, snp_offset, rdzv, uid_fn=None, steps=None, warmup=None, cache_gb=0.0, bench_hold=False,
+                 dump_dir=None):
     """One out-of-core job: stats sweep + `steps` timed gpca_rsvd calls over panels that are regenerated on every sweep."""
     steps = a.steps if steps is None else steps
     warmup = a.warmup if warmup is None else warmup
@@ -433,6 +459,8 @@ def streamed_run(g, a, M, N, k, storage, device, snp_offset, rdzv, uid_fn=None, 
                          "note": "the solo reference streams without the panel cache; allreduce spans include the wait for the slowest rank"}
         tim["_ranks"].update(weak_scaling_fields(dt / steps * 1e3, tim["_ranks"]["same_shard_without_exchange_ms_per_step_per_rank"] or []))
     ev = eng.eigenvalues()
+    if dump_dir:
+        dump_outputs(eng, dump_dir)
     eng.close()
     tim["_panels_cached"] = n_cached
     tim["_memory"] = mem
@@ -466,7 +494,8 @@ def streamed_main(a, g, rank, world, local_rank, rdzv):
     if rdzv is not None:
         def uid_fn(eng):
             connect(g, a, eng, rdzv, rank, world, snp_offset)
-    dt, tim, ev, t_stats = streamed_run(g, a, M_local, N, k, a.storage, local_rank, snp_offset, rdzv, uid_fn, cache_gb=a.cache_gb, bench_hold=a.bench_hold)
+    dt, tim, ev, t_stats = streamed_run(g, a, M_local, N, k, a.storage, local_rank, snp_offset, rdzv, uid_fn, cache_gb=a.cache_gb, bench_hold=a.bench_hold,
+                                        dump_dir=a.dump_outputs if rank == 0 else None)
     n_cached = tim.pop("_panels_cached")
     mem = tim.pop("_memory", None)
     rank_info = tim.pop("_ranks", None)
@@ -539,10 +568,15 @@ def main():
     ap.add_argument("--oversample", type=int, default=10)
     ap.add_argument("--power-iters", type=int, default=2)
     ap.add_argument("--rfit-seed", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-second-path", action="store_true", help="skip the extra f32-MFMA measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="one GPU: after the headline, also time the other GEMM paths and residencies, the other BASELINE.json workloads "
+                         "(default shape), parity against the oracle and the CPU baseline (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline path returned after its last timed step to DIR/<name>.npy (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip parity and the CPU baseline")
+    ap.add_argument("--no-second-path", action="store_true", help="--full: skip the extra paths (f32-MFMA, 2-bit residency)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the extra BASELINE.json workloads of the default one-GPU run (configs[3]'s per-GPU shard 1.25M x 100k int8 and "
+                    help="--full: skip the extra BASELINE.json workloads of the default one-GPU run (configs[3]'s per-GPU shard 1.25M x 100k int8 and "
                          "north_star's literal 10M x 100k MFMA-fp32 job on 2-bit rows, configs[4]'s per-GPU shard streamed out of core): use it under rocprofv3, whose per-kernel averages "
                          "would otherwise mix three shapes")
     ap.add_argument("--storage", default="int8", choices=["int8", "2bit"],
@@ -624,8 +658,8 @@ def main():
             rdzv.barrier()
 
     results = {}
-    # the extra measurements (f32-MFMA path, 2-bit residency) are single-GPU information: multi-rank runs time the headline only
-    extras = not a.no_second_path and world == 1
+    # the extra measurements (f32-MFMA path, 2-bit residency) are single-GPU information of --full: other runs time the headline only
+    extras = a.full and not a.no_second_path and world == 1
     order = [a.precision] + ([] if (not extras or a.precision == "f32" or l > 32) else ["f32"])
     if a.precision == "i8" and a.storage == "int8" and extras:
         order.append("i8_2bit")
@@ -684,6 +718,8 @@ def main():
             results[prec] = (dt, timings, eng.eigenvalues())
             if prec == a.precision:
                 head_rank_info = rank_info
+                if a.dump_outputs and rank == 0:
+                    dump_outputs(eng, a.dump_outputs)
         finally:
             engines[:] = []
             eng.close()
@@ -760,7 +796,7 @@ def main():
                                               "device generator (GPCA_PANEL_SYNTH16; a different synthetic draw than the resident matrix)",
                                       "value": M_local * N / (dts / min(a.steps, 3)), "unit": "SNPs*samples/s",
                                       "ms_per_step": dts / min(a.steps, 3) * 1e3, **streamed_summary(tims, min(a.steps, 3), M_local, N, l, a.storage)}
-        if world == 1 and DEFAULT_SHAPE and not a.no_extras and not a.no_second_path and a.precision == "i8" and a.storage == "int8":
+        if a.full and world == 1 and DEFAULT_SHAPE and not a.no_extras and not a.no_second_path and a.precision == "i8" and a.storage == "int8":
             # the other single-GPU workloads BASELINE.json names, timed inside this (the driver's) run.  Each is an extra: one that
             # cannot run here (a device that is not all ours, say: the 10M x 100k matrix takes 251 of the 288 GB) is reported as an
             # error under its key and never costs the headline line
@@ -820,7 +856,7 @@ def main():
         }.items() if os.path.exists(os.path.join(ROOT, v_))}
         if extra_errors:
             out["extra_path_errors"] = extra_errors
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             try:
                 out["parity"] = parity_check(g, PREC[a.precision], a.rfit_seed)
             except Exception as ex:       # noqa: BLE001

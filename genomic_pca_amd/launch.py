@@ -141,7 +141,9 @@ class Hub:
                         else:                      # rank 0 closed between rounds: the normal end (everybody closes after the last round)
                             self.lost = None
                         raise EOFError
-                for c in conns:
+                # rank 0 is answered last: under torch.distributed.run it hosts this hub in a daemon thread of its own process, and
+                # once released it may exit (ending the thread) before a later send; what is sent before that stays readable
+                for c in conns[1:] + conns[:1]:
                     c.send(msgs)
                 self.rounds += 1
         except EOFError:

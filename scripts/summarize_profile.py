@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Condense the rocprofv3 outputs of scripts/gpu_profile.sh into profiles/<tag>_*.{csv,md} (tracked)."""
+"""Condense the rocprofv3 outputs of scripts/gpu_profile.sh into profiles/<tag>_*.{csv,md} (tracked).  usage: summarize_profile.py <tag> [<output dir>]"""
 import collections
 import csv
 import glob
@@ -8,7 +8,7 @@ import os
 import sys
 
 tag = sys.argv[1]
-out = "gpurun_out"
+out = sys.argv[2] if len(sys.argv) > 2 else "profile_out"     # raw outputs of gpu_profile.sh
 os.makedirs("profiles", exist_ok=True)
 
 
@@ -41,7 +41,7 @@ if ks:
     rows = list(csv.DictReader(open(ks[0])))
     with open(f"profiles/{tag}_kernel_stats.csv", "w") as f:
         f.write(open(ks[0]).read())
-    lines += ["## `rocprofv3 --kernel-trace --stats -- python bench.py --no-cpu-baseline` (20 timed + 2 warm-up steps per path; default = exact-integer path, then the f32-MFMA path, 2-bit residency, three planes)", "",
+    lines += ["## `rocprofv3 --kernel-trace --stats -- python bench.py --full --no-cpu-baseline --no-extras` (20 timed + 2 warm-up steps per path; default = exact-integer path, then the f32-MFMA path, 2-bit residency, three planes)", "",
               "| kernel | calls | total ms | avg us | % |", "|---|---|---|---|---|"]
     for r in rows[:22]:
         lines.append(f"| `{short(r['Name'])}` | {r['Calls']} | {float(r['TotalDurationNs']) / 1e6:.3f} | {float(r['AverageNs']) / 1e3:.1f} | {float(r['Percentage']):.2f} |")

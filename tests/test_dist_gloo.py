@@ -7,6 +7,7 @@ gpca_set_allreduce_hook) summing the N x l sketch and the l x l Gram, and replic
 The sharded result must equal the unsharded oracle run.  (On a GPU the same exchange is exercised by
 test_allreduce_hook_two_shards_one_gpu and test_rccl_world1.)"""
 import os
+import subprocess
 import sys
 
 import numpy as np
@@ -51,10 +52,19 @@ def _worker(rank, world, port, M, N, P, k, seed, out_dir):
 
 @pytest.mark.timeout(300)
 def test_two_rank_gloo_sharded_equals_unsharded(tmp_path, oracle, gpca):
-    import torch.multiprocessing as mp
     M, N, P, k, seed, world = 3000, 256, 8, 6, 17, 2
     port = 29500 + (os.getpid() % 2000)
-    mp.spawn(_worker, args=(world, port, M, N, P, k, seed, str(tmp_path)), nprocs=world, join=True)
+    # the ranks are plain child processes: torch never loads into the test process, whose HIP runtime and RCCL must stay the ones
+    # libgpca.so links (torch bundles its own librccl, which a later dlopen of librccl.so.1 in this process would bind to)
+    code = ("import sys; sys.path.insert(0, %r); import test_dist_gloo as t; t._worker(int(sys.argv[1]), %d, %d, %d, %d, %d, %d, %d, %r)"
+            % (os.path.dirname(os.path.abspath(__file__)), world, port, M, N, P, k, seed, str(tmp_path)))
+    procs = [subprocess.Popen([sys.executable, "-c", code, str(r)]) for r in range(world)]
+    try:
+        assert [p.wait(timeout=240) for p in procs] == [0] * world
+    finally:
+        for p in procs:
+            if p.poll() is None:
+                p.kill()
     th = gpca.synth_thresholds(M, P, seed=seed, fst=0.25)
     G = oracle.synth_genotypes(M, N, seed, th)
     st = oracle.snp_stats(G, N, 0.0, 0.0, 1.0)
