@@ -76,6 +76,13 @@ def build_parser() -> argparse.ArgumentParser:
                    help="EigenSNP workflow: run the multi-stage algorithm the --eigensnp-* local / refine flags parameterise (per-block "
                         "local bases on a sample subset, condensed features, global PCA, refinement) instead of one global randomized "
                         "PCA over all blocks (the default: fewer passes, more accurate); needs a resident matrix")
+    # projection onto a fitted model (extensions)
+    p.add_argument("--gpca-save-model", action="store_true",
+                   help="EigenSNP workflow: also write P.eigensnp.model.tsv (per PCA SNP: alleles, mean, s.d., loadings) for "
+                        "--gpca-project-model")
+    p.add_argument("--gpca-project-model", default=None, metavar="MODEL",
+                   help="project the samples of --bed-file onto the PCs of MODEL (a P.eigensnp.model.tsv), matched by variant ID "
+                        "with allele flips handled; missing calls mean-imputed -> P.projected.pca.tsv")
     return p
 
 
@@ -220,13 +227,50 @@ def run_eigensnp_workflow(a) -> int:
     gio.write_eigenvalues(a.output_prefix, out.final_principal_component_eigenvalues)
     gio.write_loadings(a.output_prefix, [fs.variant_ids[r] for r in rows], [fs.chromosomes[r] for r in rows],
                        [int(fs.positions[r]) for r in rows], out.final_snp_principal_component_loadings)
+    if a.gpca_save_model:
+        stz = eng.get_standardization()
+        gio.write_model(a.output_prefix, gio.ProjectionModel(
+            [fs.variant_ids[r] for r in rows], [fs.chromosomes[r] for r in rows], [int(fs.positions[r]) for r in rows],
+            [fs.allele1[r] for r in rows], [fs.allele2[r] for r in rows], stz["mu"][rows], stz["sigma"][rows],
+            np.asarray(out.final_snp_principal_component_loadings, np.float32), np.asarray(out.final_principal_component_eigenvalues, np.float64),
+            len(sample_ids)))
     eng.close()
     _log(f"EigenSNP workflow done in {time.time() - t0:.2f}s")
     return 0
 
 
+def run_project_workflow(a) -> int:
+    """--gpca-project-model MODEL --bed-file TARGET --out Q: the target's samples on the model's PCs (gpca_project)."""
+    if not a.bed_file:
+        raise SystemExit("error: --bed-file is required with --gpca-project-model")
+    if a.eigensnp or a.vcf_dir:
+        raise SystemExit("error: --gpca-project-model takes a --bed-file target, not --eigensnp or --vcf-dir")
+    if a.gpca_precision != "i8":
+        raise SystemExit("error: --gpca-project-model needs --gpca-precision i8")
+    t0 = time.time()
+    model = gio.read_model(a.gpca_project_model)
+    fs = gio.read_plink(a.bed_file)
+    al = gio.align_model(model, fs.variant_ids, fs.allele1, fs.allele2)
+    _log(f"model of {len(model.variant_ids)} SNPs, k = {model.k}: {al.matched} matched ({al.flipped} with swapped alleles), "
+         f"{al.allele_mismatch} allele mismatches dropped, {al.absent} absent from the target")
+    if al.matched == 0:
+        raise SystemExit(f"error: no SNP of {a.gpca_project_model} matches a variant of {a.bed_file} (by ID and alleles)")
+    prec, store = _engine_modes(a, fs.n_samples)
+    with GpcaEngine(device=a.device, precision=prec, storage=store) as eng:
+        _load_bed(eng, a, fs, None)
+        scores, used = eng.project(al.mean, al.sd, al.loadings)
+    _ensure_parent(a.output_prefix)
+    gio.write_projected(a.output_prefix, fs.sample_ids, scores, used)
+    _log(f"projection of {fs.n_samples} samples done in {time.time() - t0:.2f}s")
+    return 0
+
+
 def main(argv=None) -> int:
     a = build_parser().parse_args(argv)
+    if a.gpca_project_model:
+        return run_project_workflow(a)
+    if a.gpca_save_model and not a.eigensnp:
+        raise SystemExit("error: --gpca-save-model needs the --eigensnp workflow")
     return run_eigensnp_workflow(a) if a.eigensnp else run_vcf_workflow(a)
 
 

@@ -282,4 +282,23 @@ int launch_gq_d(hipStream_t st, const int8_t* G, int64_t ldg, const GqPlan& plan
 void launch_gtt_2bit(hipStream_t st, const uint8_t* G2, int64_t ld2, int64_t Mpad, int64_t Npad, const int8_t* Td,
                      double* Ypart, const Gtt8Plan& plan, int nd = 4);
 
+
+// ---- projection onto a fitted model, missing calls mean-imputed (project.hip) ------------------------------------------------------
+// Per 32-column half: Ypa / Ypb [W][Npad][32] = exact integer sums of g' (missing -> 0) against the digit planes Ta of r o W and of the
+// missing indicator against the planes Tb of b o W (both in layout 0), one read of the genotypes; cnt[n] += missing calls of sample n in
+// the rows whose bit is set in rmask [rows_pad / 32] (atomic, zeroed by the caller; cnt = NULL: not counted); *bad |= 1 when such a row holds a value outside
+// {0, 1, 2, missing} (int8 rows).  lazy_b: the Tb planes are loaded only for blocks that hold a missing code (else with every
+// block, in the register ring).  G: int8 rows (packed = 0) or 2-bit codes (packed = 1) of pitch ldr bytes.
+struct PrjPlan { int64_t ngroups; int W; int64_t rows_per_wave; int64_t grid; };
+PrjPlan prj_plan(int64_t Mpad, int64_t Npad, int target_waves);
+void launch_project(hipStream_t st, const void* G, int packed, int64_t ldr, int64_t Mpad, int64_t Npad, const int8_t* Ta, const int8_t* Tb,
+                    const uint32_t* rmask, double* Ypa, double* Ypb, unsigned* cnt, unsigned* bad, const PrjPlan& plan, int nd, int lazy_b);
+// Y[n][j] = fma(-tscale_b[j], Yint_b[n][j], Y[n][j])  (one 32-column half, pitch ldy); 0 for a sample with cnt[n] == n_model
+void launch_project_correct(hipStream_t st, const double* Yint_b, int64_t N, const double* tscale_b, const unsigned* cnt, int64_t n_model,
+                            double* Y, int64_t ldy);
+// out[j] = max(out[j], max_i |X[i][j]|), X [rows][L] f32, out: the bits of non-negative doubles (zeroed by the caller)
+void launch_project_colmax(hipStream_t st, const float* X, int64_t rows, int L, unsigned long long* out);
+// used[n] = n_model - cnt[n]
+void launch_project_used(hipStream_t st, const unsigned* cnt, int64_t N, double n_model, double* used);
+
 }  // namespace gpca

@@ -349,6 +349,22 @@ class GpcaEngine:
         self._chk(self._lib.gpca_transform(self._h, _vp(out)))
         return out
 
+    def project(self, mu: np.ndarray, sigma: np.ndarray, W: np.ndarray):
+        """Scores of this engine's genotypes on a fitted model (gpca_project): mu, sigma [M], W [M][k] in this engine's row order,
+        zero rows = not in the model.  Missing calls are mean-imputed.  Returns (scores f64 [N][k], n_used int32 [N])."""
+        M, N = self.dims()
+        mu = np.ascontiguousarray(mu, np.float32); sigma = np.ascontiguousarray(sigma, np.float32)
+        W = np.ascontiguousarray(W, np.float32)
+        if W.ndim == 1:
+            W = W.reshape(-1, 1)
+        if mu.shape != (M,) or sigma.shape != (M,) or W.ndim != 2 or W.shape[0] != M:
+            raise ValueError(f"project: mu and sigma must be [{M}] and W [{M}][k]")
+        k = W.shape[1]
+        scores = np.empty((N, k), np.float64)
+        used = np.empty(N, np.int32)
+        self._chk(self._lib.gpca_project(self._h, _vp(mu), _vp(sigma), _vp(W), k, _vp(scores), _vp(used)))
+        return scores, used
+
     # -- f3: the stages of EigenSNPCoreAlgorithm (gpca.h)
     def copy_rows_from(self, src: "GpcaEngine", row0: int, rows: int):
         """This engine receives rows [row0, row0 + rows) of src's resident matrix (device to device)."""
@@ -427,6 +443,33 @@ class GpcaEngine:
         self._chk(self._lib.gpca_synchronize(self._h))
 
 
+def _digest_i8(g: np.ndarray) -> bytes:
+    """Identity of an int8 genotype matrix (PCA.transform(x) recognises the fitted matrix by it)."""
+    import hashlib
+    h = hashlib.blake2b(digest_size=32)
+    h.update(np.asarray(g.shape, np.int64).tobytes())
+    h.update(np.ascontiguousarray(g).data)
+    return h.digest()
+
+
+def _dosages_snp_major(x: np.ndarray, where: str) -> np.ndarray:
+    """samples x variants dosages (0/1/2; NaN = missing) -> int8 SNP-major rows with -127 for a missing call."""
+    n_samples, n_features = x.shape
+    if x.dtype == np.int8:
+        return np.ascontiguousarray(x.T)
+    g = np.empty((n_features, n_samples), np.int8)
+    step = max(1, (1 << 24) // max(n_features, 1))
+    for s0 in range(0, n_samples, step):
+        blk = np.asarray(x[s0:s0 + step], np.float64)
+        miss = np.isnan(blk)
+        r = np.rint(np.where(miss, 0.0, blk))
+        if not (np.all(np.abs(r) <= 127) and np.array_equal(r[~miss], blk[~miss])):
+            raise ValueError(f"{where}: x must hold genotype dosages 0/1/2 or NaN (found a value that is not a whole number)")
+        r[miss] = -127
+        g[:, s0:s0 + step] = r.T.astype(np.int8)
+    return g
+
+
 # ------------------------------------------------------------------------------------------------
 # efficient_pca::PCA as called at main.rs:602, 648-660
 # ------------------------------------------------------------------------------------------------
@@ -471,6 +514,8 @@ class PCA:
                     raise ValueError("PCA.rfit: x must hold genotype dosages 0/1/2 (found a value that is not a whole number)")
                 g[:, s0:s0 + step] = r.T.astype(np.int8)
         self._eng.upload_genotypes_i8(g)
+        self._fit_digest = _digest_i8(g)
+        self._n_features = n_features
         self._eng.snp_stats(QcConfig.none(), fetch=False)
         # zero-variance rows leave the PCA even without QC thresholds: the reference's clamp (main.rs:621-628), applied to what is left
         if self._eng.num_pca_snps() == 0:
@@ -483,10 +528,25 @@ class PCA:
         return self
 
     def transform(self, x: Optional[np.ndarray] = None) -> np.ndarray:
-        """Scores of the fitted matrix (the reference passes the clone of the same x, main.rs:640,659)."""
+        """Scores of samples x variants ``x`` on the fitted axes.  No ``x``, or the fitted matrix itself: the fitted matrix's scores (the
+        reference passes the clone of the same x, main.rs:640,659).  Any other ``x`` with the fitted variant count (NaN = missing call)
+        is projected with the fitted mean, s.d. and loadings through a second engine (gpca_project; missing calls mean-imputed)."""
         if not self._fitted:
             raise RuntimeError("PCA.transform before rfit")
-        return self._eng.transform()
+        if x is None:
+            return self._eng.transform()
+        x = np.asarray(x)
+        if x.ndim != 2 or x.shape[1] != self._n_features:
+            raise ValueError(f"PCA.transform: x must be samples x {self._n_features} variants, got shape {x.shape}")
+        g = _dosages_snp_major(x, "PCA.transform")
+        if _digest_i8(g) == self._fit_digest:
+            return self._eng.transform()
+        st = self._eng.get_standardization()
+        W = np.zeros((self._n_features, self.k), np.float32)
+        W[self._eng.pca_snp_rows()] = self._eng.loadings()
+        with GpcaEngine(device=self._eng._device, precision=_lib.PREC_I8_EXACT, storage=self._eng.storage) as e:
+            e.upload_genotypes_i8(g)
+            return e.project(st["mu"], st["sigma"], W)[0]
 
     def explained_variance(self) -> np.ndarray:
         return self._eng.eigenvalues()

@@ -57,6 +57,7 @@ struct PlinkFileset {
     int64_t n_snps = 0, n_samples = 0, bytes_per_row = 0;
     std::vector<std::string> sample_ids, variant_ids, chromosomes;
     std::vector<int64_t> positions;
+    std::vector<std::string> allele1, allele2;   // .bim columns 5 / 6: A1 (the allele the dosages count), A2
     void* map_base = nullptr; size_t map_len = 0;
     PlinkFileset() = default;
     PlinkFileset(const PlinkFileset&) = delete;
@@ -85,7 +86,10 @@ inline void read_plink(const std::string& bed_path, PlinkFileset& fs) {
         if (!f) throw std::runtime_error("cannot open " + prefix + ".bim");
         while (std::getline(f, line)) {
             const auto p = split_ws(line);
-            if (p.size() >= 4) { fs.chromosomes.push_back(p[0]); fs.variant_ids.push_back(p[1]); fs.positions.push_back(std::stoll(p[3])); }
+            if (p.size() >= 4) {
+                fs.chromosomes.push_back(p[0]); fs.variant_ids.push_back(p[1]); fs.positions.push_back(std::stoll(p[3]));
+                fs.allele1.push_back(p.size() > 4 ? p[4] : "."); fs.allele2.push_back(p.size() > 5 ? p[5] : ".");
+            }
         }
     }
     fs.n_samples = (int64_t)fs.sample_ids.size(); fs.n_snps = (int64_t)fs.variant_ids.size();
@@ -370,6 +374,136 @@ inline void write_loadings(const std::string& prefix, const std::vector<std::str
         std::fprintf(o.f, "%s\t%s\t%lld", variant_ids[i].c_str(), chroms[i].c_str(), (long long)positions[i]);
         for (int c = 0; c < k; ++c) std::fprintf(o.f, "\t%.6f", (double)loadings[i * (size_t)k + (size_t)c]);
         std::fputc('\n', o.f);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- projection model (io.py's twin)
+// P.eigensnp.model.tsv: "#gpca-model v1\tk=K\tfit_samples=N", "#eigenvalues\t%.17g ...", the header, then one row per PCA SNP with
+// its f32 mean / s.d. / loadings in %.9g (reads back to the same f32)
+struct ProjectionModel {
+    std::vector<std::string> variant_ids, chromosomes, allele1, allele2;
+    std::vector<int64_t> positions;
+    std::vector<float> mean, sd, loadings;   // loadings [S][k]
+    std::vector<double> eigenvalues;
+    int k = 0;
+    int64_t n_samples = 0;
+};
+
+inline void write_model(const std::string& prefix, const ProjectionModel& m) {
+    OutFile o(prefix + ".eigensnp.model.tsv");
+    std::fprintf(o.f, "#gpca-model v1\tk=%d\tfit_samples=%lld\n", m.k, (long long)m.n_samples);
+    std::fputs("#eigenvalues", o.f);
+    for (double v : m.eigenvalues) std::fprintf(o.f, "\t%.17g", v);
+    std::fputs("\nVariantID\tChrom\tPos\tA1\tA2\tMean\tSD", o.f);
+    for (int c = 1; c <= m.k; ++c) std::fprintf(o.f, "\tPC%d_loading", c);
+    std::fputc('\n', o.f);
+    for (size_t i = 0; i < m.variant_ids.size(); ++i) {
+        std::fprintf(o.f, "%s\t%s\t%lld\t%s\t%s\t%.9g\t%.9g", m.variant_ids[i].c_str(), m.chromosomes[i].c_str(), (long long)m.positions[i],
+                     m.allele1[i].c_str(), m.allele2[i].c_str(), (double)m.mean[i], (double)m.sd[i]);
+        for (int c = 0; c < m.k; ++c) std::fprintf(o.f, "\t%.9g", (double)m.loadings[i * (size_t)m.k + (size_t)c]);
+        std::fputc('\n', o.f);
+    }
+}
+
+inline std::vector<std::string> split_tabs(const std::string& line) {
+    std::vector<std::string> out;
+    size_t a = 0;
+    for (;;) {
+        const size_t b = line.find('\t', a);
+        out.push_back(line.substr(a, b == std::string::npos ? std::string::npos : b - a));
+        if (b == std::string::npos) return out;
+        a = b + 1;
+    }
+}
+
+inline ProjectionModel read_model(const std::string& path) {
+    std::ifstream f(path);
+    if (!f) throw std::runtime_error("cannot open " + path);
+    ProjectionModel m;
+    std::string line;
+    auto bad = [&](const std::string& why) { return std::runtime_error(path + ": " + why); };
+    if (!std::getline(f, line)) throw bad("empty file");
+    auto head = split_tabs(line);
+    if (head.empty() || head[0] != "#gpca-model v1") throw bad("not a projection model (first line must start with '#gpca-model v1')");
+    bool have_k = false, have_n = false;
+    for (size_t i = 1; i < head.size(); ++i) {
+        const size_t eq = head[i].find('=');
+        if (eq == std::string::npos) continue;
+        const std::string key = head[i].substr(0, eq), v = head[i].substr(eq + 1);
+        try {
+            if (key == "k") { m.k = std::stoi(v); have_k = true; }
+            else if (key == "fit_samples") { m.n_samples = std::stoll(v); have_n = true; }
+        } catch (...) { throw bad("the first line must carry k=<int> and fit_samples=<int>"); }
+    }
+    if (!have_k || !have_n || m.k < 1) throw bad("the first line must carry k=<int> and fit_samples=<int>");
+    if (!std::getline(f, line)) throw bad("second line must be '#eigenvalues ...'");
+    auto ev = split_tabs(line);
+    if (ev.empty() || ev[0] != "#eigenvalues") throw bad("second line must be '#eigenvalues ...'");
+    for (size_t i = 1; i < ev.size(); ++i) m.eigenvalues.push_back(std::stod(ev[i]));
+    if (!std::getline(f, line)) throw bad("no header line");
+    auto cols = split_tabs(line);
+    const std::vector<std::string> want = {"VariantID", "Chrom", "Pos", "A1", "A2", "Mean", "SD"};
+    if (cols.size() != 7 + (size_t)m.k || !std::equal(want.begin(), want.end(), cols.begin()))
+        throw bad("bad header line (VariantID Chrom Pos A1 A2 Mean SD and " + std::to_string(m.k) + " loading columns expected)");
+    int64_t ln = 3;
+    while (std::getline(f, line)) {
+        ++ln;
+        if (line.empty()) continue;
+        auto p = split_tabs(line);
+        if (p.size() != 7 + (size_t)m.k)
+            throw bad(std::to_string(ln) + ": " + std::to_string(p.size()) + " columns, " + std::to_string(7 + m.k) + " expected");
+        m.variant_ids.push_back(p[0]); m.chromosomes.push_back(p[1]); m.positions.push_back(std::stoll(p[2]));
+        m.allele1.push_back(p[3]); m.allele2.push_back(p[4]);
+        m.mean.push_back((float)std::stod(p[5])); m.sd.push_back((float)std::stod(p[6]));
+        for (int c = 0; c < m.k; ++c) m.loadings.push_back((float)std::stod(p[7 + c]));
+    }
+    return m;
+}
+
+// The model's rows per target row, matched by variant ID ('.' never matches; the first target row of a duplicated ID is the one used).
+// Same (A1, A2): as is; swapped: mean -> 2 - mean, loadings -> -loadings; any other pair: dropped.
+struct Alignment {
+    std::vector<float> mean, sd, loadings;   // [M_target], [M_target], [M_target][k]; zero loading rows = outside the model
+    int64_t matched = 0, flipped = 0, allele_mismatch = 0, absent = 0;
+};
+inline Alignment align_model(const ProjectionModel& m, const std::vector<std::string>& ids, const std::vector<std::string>& a1,
+                             const std::vector<std::string>& a2) {
+    const size_t M = ids.size(), k = (size_t)m.k;
+    std::map<std::string, size_t> first;
+    for (size_t i = 0; i < M; ++i) if (ids[i] != ".") first.emplace(ids[i], i);
+    Alignment al;
+    al.mean.assign(M, 0.f); al.sd.assign(M, 1.f); al.loadings.assign(M * k, 0.f);
+    std::vector<char> seen(M, 0);
+    for (size_t s = 0; s < m.variant_ids.size(); ++s) {
+        const auto it = m.variant_ids[s] == "." ? first.end() : first.find(m.variant_ids[s]);
+        if (it == first.end() || seen[it->second]) { al.absent++; continue; }
+        const size_t i = it->second;
+        const float* w = &m.loadings[s * k];
+        if (a1[i] == m.allele1[s] && a2[i] == m.allele2[s]) {
+            al.mean[i] = m.mean[s]; al.sd[i] = m.sd[s];
+            for (size_t c = 0; c < k; ++c) al.loadings[i * k + c] = w[c];
+        } else if (a1[i] == m.allele2[s] && a2[i] == m.allele1[s]) {
+            al.mean[i] = 2.0f - m.mean[s]; al.sd[i] = m.sd[s];
+            for (size_t c = 0; c < k; ++c) al.loadings[i * k + c] = -w[c];
+            al.flipped++;
+        } else { al.allele_mismatch++; continue; }
+        seen[i] = 1;
+        al.matched++;
+    }
+    return al;
+}
+
+// Q.projected.pca.tsv: SampleID, PC1..PCk ("{:.6}" as the other PC files), SNPsUsed
+inline void write_projected(const std::string& prefix, const std::vector<std::string>& sample_names, const double* scores, int k,
+                            const std::vector<int32_t>& used) {
+    OutFile o(prefix + ".projected.pca.tsv");
+    std::fputs("SampleID", o.f);
+    for (int c = 1; c <= k; ++c) std::fprintf(o.f, "\tPC%d", c);
+    std::fputs("\tSNPsUsed\n", o.f);
+    for (size_t i = 0; i < sample_names.size(); ++i) {
+        std::fputs(sample_names[i].c_str(), o.f);
+        for (int c = 0; c < k; ++c) std::fprintf(o.f, "\t%.6f", scores[i * (size_t)k + (size_t)c]);
+        std::fprintf(o.f, "\t%d\n", (int)used[i]);
     }
 }
 

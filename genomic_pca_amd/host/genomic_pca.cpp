@@ -40,6 +40,8 @@ struct Args {
     std::string precision = "i8", storage = "auto", stream = "auto";
     int64_t panel_rows = 0;
     bool local_stage = false;
+    bool save_model = false;          // --gpca-save-model: also write P.eigensnp.model.tsv
+    std::string project_model;        // --gpca-project-model MODEL: project --bed-file's samples onto it
 };
 
 [[noreturn]] void usage_error(const std::string& msg) {
@@ -91,6 +93,10 @@ void print_help() {
         "      --gpca-rfit-power-iters <N>      VCF workflow: power iterations of the randomized PCA [default: 2]\n"
         "      --gpca-eigensnp-local-stage      run the multi-stage algorithm of the --eigensnp-* local / refine flags instead of\n"
         "                                       one global randomized PCA over all blocks (the default)\n"
+        "      --gpca-save-model                EigenSNP workflow: also write P.eigensnp.model.tsv (per PCA SNP: alleles, mean, s.d.,\n"
+        "                                       loadings) for --gpca-project-model\n"
+        "      --gpca-project-model <MODEL>     project the samples of --bed-file onto the PCs of MODEL (matched by variant ID, allele\n"
+        "                                       flips handled, missing calls mean-imputed) -> P.projected.pca.tsv\n"
         "  -h, --help                           Print help");
 }
 
@@ -154,6 +160,8 @@ Args parse(int argc, char** argv) {
         else if (f == "--gpca-panel-rows") a.panel_rows = to_i64(f, val());
         else if (f == "--gpca-rfit-power-iters") a.rfit_power_iters = to_i64(f, val());
         else if (f == "--gpca-eigensnp-local-stage") a.local_stage = true;
+        else if (f == "--gpca-save-model") a.save_model = true;
+        else if (f == "--gpca-project-model") a.project_model = val();
         else usage_error("unexpected argument '" + f + "' found");
     }
     if (a.output_prefix.empty()) usage_error("the following required arguments were not provided:\n  --out <OUTPUT_PREFIX>");
@@ -333,7 +341,50 @@ int run_eigensnp_workflow(Args a) {
     vids.reserve(rows.size()); chroms.reserve(rows.size()); pos.reserve(rows.size());
     for (int64_t r : rows) { vids.push_back(fs.variant_ids[(size_t)r]); chroms.push_back(fs.chromosomes[(size_t)r]); pos.push_back(fs.positions[(size_t)r]); }
     gpca_host::write_loadings(a.output_prefix, vids, chroms, pos, out.final_snp_principal_component_loadings.data(), (int64_t)rows.size(), kc);
+    if (a.save_model) {
+        gpca_host::ProjectionModel m;
+        m.variant_ids = vids; m.chromosomes = chroms; m.positions = pos; m.k = kc; m.n_samples = (int64_t)sample_ids.size();
+        for (int64_t r : rows) {
+            m.allele1.push_back(fs.allele1[(size_t)r]); m.allele2.push_back(fs.allele2[(size_t)r]);
+            m.mean.push_back(st.mu[(size_t)r]); m.sd.push_back(st.sigma[(size_t)r]);
+        }
+        m.loadings.assign(out.final_snp_principal_component_loadings.begin(), out.final_snp_principal_component_loadings.begin() + rows.size() * (size_t)kc);
+        m.eigenvalues = out.final_principal_component_eigenvalues;
+        gpca_host::write_model(a.output_prefix, m);
+    }
     std::snprintf(buf, sizeof buf, "EigenSNP workflow done in %.2fs", seconds_since(t0));
+    logmsg(buf);
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ projection onto a fitted model
+// --gpca-project-model MODEL --bed-file TARGET --out Q: the target's samples on the model's PCs (gpca_project; cli.py:run_project_workflow)
+int run_project_workflow(Args a) {
+    auto refuse = [](const char* m) { std::fprintf(stderr, "error: %s\n", m); return 2; };
+    if (a.bed_file.empty()) return refuse("--bed-file is required with --gpca-project-model");
+    if (a.eigensnp || !a.vcf_dir.empty()) return refuse("--gpca-project-model takes a --bed-file target, not --eigensnp or --vcf-dir");
+    if (a.precision != "i8") return refuse("--gpca-project-model needs --gpca-precision i8");
+    const auto t0 = std::chrono::steady_clock::now();
+    const gpca_host::ProjectionModel model = gpca_host::read_model(a.project_model);
+    gpca_host::PlinkFileset fs;
+    gpca_host::read_plink(a.bed_file, fs);
+    const gpca_host::Alignment al = gpca_host::align_model(model, fs.variant_ids, fs.allele1, fs.allele2);
+    char buf[512];
+    std::snprintf(buf, sizeof buf, "model of %zu SNPs, k = %d: %lld matched (%lld with swapped alleles), %lld allele mismatches dropped, %lld absent from the target",
+                  model.variant_ids.size(), model.k, (long long)al.matched, (long long)al.flipped, (long long)al.allele_mismatch, (long long)al.absent);
+    logmsg(buf);
+    if (al.matched == 0) {
+        std::fprintf(stderr, "error: no SNP of %s matches a variant of %s (by ID and alleles)\n", a.project_model.c_str(), a.bed_file.c_str());
+        return 1;
+    }
+    const int store = engine_storage(a, fs.n_samples);
+    gpca::Engine eng(a.device, engine_precision(a), store);
+    load_bed(eng, a, fs, nullptr);
+    std::vector<int32_t> used;
+    const std::vector<double> scores = eng.project(al.mean.data(), al.sd.data(), al.loadings.data(), model.k, &used);
+    gpca_host::ensure_parent(a.output_prefix);
+    gpca_host::write_projected(a.output_prefix, fs.sample_ids, scores.data(), model.k, used);
+    std::snprintf(buf, sizeof buf, "projection of %lld samples done in %.2fs", (long long)fs.n_samples, seconds_since(t0));
     logmsg(buf);
     return 0;
 }
@@ -343,6 +394,8 @@ int run_eigensnp_workflow(Args a) {
 int main(int argc, char** argv) {
     const Args a = parse(argc, argv);
     try {
+        if (!a.project_model.empty()) return run_project_workflow(a);
+        if (a.save_model && !a.eigensnp) { std::fprintf(stderr, "error: --gpca-save-model needs the --eigensnp workflow\n"); return 2; }
         return a.eigensnp ? run_eigensnp_workflow(a) : run_vcf_workflow(a);
     } catch (const gpca::Error& e) {
         std::fprintf(stderr, "Error: %s\n", e.what());

@@ -32,6 +32,8 @@ class PlinkFileset:
     variant_ids: List[str]        # .bim sid
     chromosomes: List[str]        # .bim chrom
     positions: np.ndarray         # .bim bp (int64)
+    allele1: List[str] = None     # .bim column 5: A1, the allele the dosages count
+    allele2: List[str] = None     # .bim column 6: A2
 
 
 def _strip_ext(path: str) -> str:
@@ -49,12 +51,13 @@ def read_plink(bed_path: str) -> PlinkFileset:
             p = line.split()
             if p:
                 iids.append(p[1] if len(p) > 1 else p[0])
-    sids, chroms, pos = [], [], []
+    sids, chroms, pos, a1, a2 = [], [], [], [], []
     with open(prefix + ".bim") as f:
         for line in f:
             p = line.split()
             if len(p) >= 4:
                 chroms.append(p[0]); sids.append(p[1]); pos.append(int(p[3]))
+                a1.append(p[4] if len(p) > 4 else "."); a2.append(p[5] if len(p) > 5 else ".")
     n, m = len(iids), len(sids)
     bpr = (n + 3) // 4
     with open(prefix + ".bed", "rb") as f:
@@ -65,11 +68,11 @@ def read_plink(bed_path: str) -> PlinkFileset:
     if size != 3 + m * bpr:
         raise ValueError(f"{prefix}.bed: size {size} does not match {m} SNPs x {n} samples")
     rows = np.memmap(prefix + ".bed", dtype=np.uint8, mode="r", offset=3, shape=(m, bpr))
-    return PlinkFileset(rows, n, iids, sids, chroms, np.asarray(pos, np.int64))
+    return PlinkFileset(rows, n, iids, sids, chroms, np.asarray(pos, np.int64), a1, a2)
 
 
 def write_plink(prefix: str, dosage_count_a1: np.ndarray, sample_ids: Sequence[str], variant_ids: Sequence[str],
-                chromosomes: Sequence[str], positions: Sequence[int]) -> None:
+                chromosomes: Sequence[str], positions: Sequence[int], alleles: Optional[Sequence[Tuple[str, str]]] = None) -> None:
     """Test/fixture helper: int8 [M, N] count-A1 dosages (-127 missing) -> .bed/.bim/.fam."""
     g = np.asarray(dosage_count_a1, np.int8)
     m, n = g.shape
@@ -83,8 +86,9 @@ def write_plink(prefix: str, dosage_count_a1: np.ndarray, sample_ids: Sequence[s
     with open(prefix + ".bed", "wb") as f:
         f.write(BED_MAGIC); f.write(rows.tobytes())
     with open(prefix + ".bim", "w") as f:
-        for c, s, p in zip(chromosomes, variant_ids, positions):
-            f.write(f"{c}\t{s}\t0\t{p}\tA\tG\n")
+        for i, (c, s, p) in enumerate(zip(chromosomes, variant_ids, positions)):
+            x1, x2 = alleles[i] if alleles is not None else ("A", "G")
+            f.write(f"{c}\t{s}\t0\t{p}\t{x1}\t{x2}\n")
     with open(prefix + ".fam", "w") as f:
         for s in sample_ids:
             f.write(f"{s}\t{s}\t0\t0\t0\t-9\n")
@@ -277,4 +281,127 @@ def write_loadings(prefix: str, variant_ids: Sequence[str], chromosomes: Sequenc
         f.write("VariantID\tChrom\tPos" + "".join(f"\tPC{i}_loading" for i in range(1, loadings.shape[1] + 1)) + "\n")
         for i in range(len(variant_ids)):
             f.write(f"{variant_ids[i]}\t{chromosomes[i]}\t{positions[i]}" + "".join("\t" + _fmt6(v) for v in loadings[i]) + "\n")
+    return path
+
+
+# ------------------------------------------------------------------------------------------------ projection model
+# P.eigensnp.model.tsv: what a projection of other samples onto fitted PCs needs (gpca_project): per PCA SNP its id, position,
+# alleles (A1 = the counted allele), the f32 mean / s.d. of the standardisation and the f32 loadings, each written with %.9g so that
+# it reads back to the same f32; the eigenvalues (%.17g) and the fitting sample count ride in the header lines.
+MODEL_MAGIC = "#gpca-model v1"
+
+
+@dataclass
+class ProjectionModel:
+    variant_ids: List[str]
+    chromosomes: List[str]
+    positions: List[int]
+    allele1: List[str]
+    allele2: List[str]
+    mean: np.ndarray              # f32 [S]
+    sd: np.ndarray                # f32 [S]
+    loadings: np.ndarray          # f32 [S][k]
+    eigenvalues: np.ndarray       # f64 [k]
+    n_samples: int                # samples the model was fitted on
+
+    @property
+    def k(self) -> int:
+        return self.loadings.shape[1]
+
+
+def _g9(x) -> str:
+    return "%.9g" % float(np.float32(x))
+
+
+def write_model(prefix: str, model: ProjectionModel) -> str:
+    path = f"{prefix}.eigensnp.model.tsv"
+    k = model.k
+    with open(path, "w") as f:
+        f.write(f"{MODEL_MAGIC}\tk={k}\tfit_samples={int(model.n_samples)}\n")
+        f.write("#eigenvalues" + "".join("\t%.17g" % float(v) for v in model.eigenvalues) + "\n")
+        f.write("VariantID\tChrom\tPos\tA1\tA2\tMean\tSD" + "".join(f"\tPC{i}_loading" for i in range(1, k + 1)) + "\n")
+        for i in range(len(model.variant_ids)):
+            f.write(f"{model.variant_ids[i]}\t{model.chromosomes[i]}\t{int(model.positions[i])}\t{model.allele1[i]}\t{model.allele2[i]}\t"
+                    f"{_g9(model.mean[i])}\t{_g9(model.sd[i])}" + "".join("\t" + _g9(v) for v in model.loadings[i]) + "\n")
+    return path
+
+
+def read_model(path: str) -> ProjectionModel:
+    with open(path) as f:
+        head = f.readline().rstrip("\n").split("\t")
+        if not head or head[0] != MODEL_MAGIC:
+            raise ValueError(f"{path}: not a projection model (first line must start with '{MODEL_MAGIC}')")
+        kv = dict(t.split("=", 1) for t in head[1:] if "=" in t)
+        try:
+            k, n_fit = int(kv["k"]), int(kv["fit_samples"])
+        except (KeyError, ValueError):
+            raise ValueError(f"{path}: the first line must carry k=<int> and fit_samples=<int>")
+        ev_line = f.readline().rstrip("\n").split("\t")
+        if not ev_line or ev_line[0] != "#eigenvalues":
+            raise ValueError(f"{path}: second line must be '#eigenvalues ...'")
+        ev = np.array([float(v) for v in ev_line[1:]], np.float64)
+        cols = f.readline().rstrip("\n").split("\t")
+        if cols[:7] != ["VariantID", "Chrom", "Pos", "A1", "A2", "Mean", "SD"] or len(cols) != 7 + k:
+            raise ValueError(f"{path}: bad header line (VariantID Chrom Pos A1 A2 Mean SD and {k} loading columns expected)")
+        ids, chroms, pos, a1, a2, rows = [], [], [], [], [], []
+        for ln, line in enumerate(f, start=4):
+            p = line.rstrip("\n").split("\t")
+            if p == [""]:
+                continue
+            if len(p) != 7 + k:
+                raise ValueError(f"{path}:{ln}: {len(p)} columns, {7 + k} expected")
+            ids.append(p[0]); chroms.append(p[1]); pos.append(int(p[2])); a1.append(p[3]); a2.append(p[4])
+            rows.append([float(v) for v in p[5:]])
+    vals = np.array(rows, np.float64).reshape(len(rows), 2 + k).astype(np.float32)
+    return ProjectionModel(ids, chroms, pos, a1, a2, vals[:, 0].copy(), vals[:, 1].copy(), np.ascontiguousarray(vals[:, 2:]), ev, n_fit)
+
+
+@dataclass
+class Alignment:
+    mean: np.ndarray              # f32 [M_target]: the model's mean on the target's counted allele (2 - mean where flipped)
+    sd: np.ndarray                # f32 [M_target]
+    loadings: np.ndarray          # f32 [M_target][k]: zero rows = target variants outside the model
+    matched: int                  # model SNPs used (same or swapped alleles)
+    flipped: int                  # ... of them with A1 / A2 swapped
+    allele_mismatch: int          # model SNPs whose ID matched but whose allele pair differs: dropped
+    absent: int                   # model SNPs with no target variant of that ID
+
+
+def align_model(model: ProjectionModel, variant_ids: Sequence[str], allele1: Sequence[str], allele2: Sequence[str]) -> Alignment:
+    """The model's rows per target row, matched by variant ID ('.' never matches; the first target row of a duplicated ID is the
+    one used).  Same (A1, A2): as is; swapped: mean -> 2 - mean, loadings -> -loadings; any other pair: dropped."""
+    M = len(variant_ids)
+    first = {}
+    for i, v in enumerate(variant_ids):
+        if v != "." and v not in first:
+            first[v] = i
+    mean = np.zeros(M, np.float32); sd = np.ones(M, np.float32)
+    W = np.zeros((M, model.k), np.float32)
+    matched = flipped = mismatch = absent = 0
+    seen = set()
+    for s, v in enumerate(model.variant_ids):
+        i = first.get(v) if v != "." else None
+        if i is None or i in seen:
+            absent += 1
+            continue
+        if (allele1[i], allele2[i]) == (model.allele1[s], model.allele2[s]):
+            mean[i], sd[i], W[i] = model.mean[s], model.sd[s], model.loadings[s]
+        elif (allele1[i], allele2[i]) == (model.allele2[s], model.allele1[s]):
+            mean[i], sd[i], W[i] = np.float32(2.0) - model.mean[s], model.sd[s], -model.loadings[s]
+            flipped += 1
+        else:
+            mismatch += 1
+            continue
+        seen.add(i)
+        matched += 1
+    return Alignment(mean, sd, W, matched, flipped, mismatch, absent)
+
+
+def write_projected(prefix: str, sample_names: Sequence[str], scores: np.ndarray, used: Sequence[int]) -> str:
+    """Q.projected.pca.tsv: SampleID, PC1..PCk ('{:.6}' as the other PC files), SNPsUsed (model SNPs with an observed call)."""
+    path = f"{prefix}.projected.pca.tsv"
+    with open(path, "w") as f:
+        f.write("SampleID" + "".join(f"\tPC{i}" for i in range(1, scores.shape[1] + 1)) + "\tSNPsUsed\n")
+        for i, name in enumerate(sample_names):
+            f.write(name + "".join("\t" + _fmt6(v) for v in scores[i]) + f"\t{int(used[i])}\n")
     return path

@@ -276,6 +276,18 @@ GPCA_API int gpca_get_singular_values(gpca_handle* h, double* out /* [k+oversamp
 GPCA_API int gpca_get_loadings(gpca_handle* h, float* out /* [num_pca_snps][k] */); /* main.rs:407 */
 /* PCA::transform (main.rs:659) on the resident matrix: scores = A^T * loadings, f64 [N][k]. */
 GPCA_API int gpca_transform(gpca_handle* h, double* out);
+/* ---- a7: projection of this handle's genotypes onto a fitted model (PCA::transform(x) of efficient_pca on new samples, main.rs:659):
+ * mu, sigma: f32 [M]; W: f32 [M][k] row-major in THIS handle's row order, zero rows = not in the model; scores: f64 [N][k];
+ * n_used: int32 [N] or NULL (model rows with an observed call).  Missing calls are mean-imputed: their standardised value is 0.
+ * Needs genotypes only (no gpca_snp_stats / gpca_rsvd) and leaves every fitted result of the handle as it was.  1 <= k <= 128.
+ * A model row with a non-finite mu / sigma / W entry or sigma <= 0 is GPCA_ERR_BAD_ARG (the message names the row); a model row
+ * holding a value outside {0, 1, 2, missing} is GPCA_ERR_INVALID_GENOTYPE.  GPCA_PREC_F32_MFMA handles return GPCA_ERR_STATE.
+ * With the handle's own model (loadings scattered to gpca_get_pca_snp_rows, mu / sigma of gpca_get_standardization) and no missing
+ * call in a model row, the scores equal gpca_transform's bit for bit -- as long as gpca_rsvd ran on the handle's own rows.  When QC
+ * dropped so many rows that gpca_rsvd ran on a compacted copy of the kept rows (at least 32 Ki rows and 8 MiB dropped, at most half
+ * of the rows kept), gpca_transform sums c = b^T W over other 64-row groups and the two may differ in the last bits.  Row-sharded handles: every rank passes its own rows' model;
+ * scores and counts are summed in one exchange that also carries the status word, so a rank-local failure comes back from every rank. */
+GPCA_API int gpca_project(gpca_handle* h, const float* mu, const float* sigma, const float* W, int32_t k, double* scores, int32_t* n_used);
 
 /* ---- f3: the stages of EigenSNPCoreAlgorithm::compute_pca (main.rs:311-327, 359-366) ------------------------------------------
  * The algorithm lives in the un-vendored efficient_pca crate (Cargo.toml:30, branch "main", no pinned revision): what follows is

@@ -145,6 +145,13 @@ public:
     std::vector<float> loadings() const { std::vector<float> l((size_t)num_pca_snps() * (size_t)k_); check(gpca_get_loadings(h_, l.data())); return l; }
     std::vector<double> scores_f64() const { std::vector<double> s((size_t)num_qc_samples() * (size_t)k_); check(gpca_get_scores_f64(h_, s.data())); return s; }
     std::vector<double> transform() const { std::vector<double> s((size_t)num_qc_samples() * (size_t)k_); check(gpca_transform(h_, s.data())); return s; }
+    // scores [N][k] of this handle's genotypes on a model (mu, sigma [M], W [M][k]); used (may be null) receives n_used [N]
+    std::vector<double> project(const float* mu, const float* sigma, const float* W, int k, std::vector<int32_t>* used = nullptr) const {
+        std::vector<double> s((size_t)num_qc_samples() * (size_t)k);
+        if (used) used->assign((size_t)num_qc_samples(), 0);
+        check(gpca_project(h_, mu, sigma, W, k, s.data(), used ? used->data() : nullptr));
+        return s;
+    }
 
 private:
     gpca_handle* h_ = nullptr;
