@@ -27,6 +27,8 @@ PREC_F32_MFMA = 2
 STORE_AUTO = 0         # 2-bit codes from 1 024 samples on, int8 below (decided when the genotypes arrive)
 STORE_2BIT = 1
 STORE_INT8 = 2
+GRM_STANDARDIZED = 0      # gpca_grm scalings (include/gpca.h)
+GRM_CENTRED = 1
 CFG_SIMPLE_KERNELS = 1     # gpca_config.reserved[0] flags (include/gpca.h)
 CFG_NO_COMPACT = 2
 CFG_NO_NARROW = 4
@@ -125,6 +127,7 @@ PROTOTYPES = {
     "gpca_get_loadings": (C.c_int, [_H, C.c_void_p]),
     "gpca_transform": (C.c_int, [_H, C.c_void_p]),
     "gpca_project": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "gpca_grm": (C.c_int, [_H, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "gpca_comm_get_unique_id": (C.c_int, [C.c_void_p]),
     "gpca_comm_init": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, C.c_int64]),
     "gpca_set_allreduce_hook": (C.c_int, [_H, ALLREDUCE_FN, C.c_void_p, C.c_int32, C.c_int32, C.c_int64]),

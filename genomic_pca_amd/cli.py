@@ -83,7 +83,25 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--gpca-project-model", default=None, metavar="MODEL",
                    help="project the samples of --bed-file onto the PCs of MODEL (a P.eigensnp.model.tsv), matched by variant ID "
                         "with allele flips handled; missing calls mean-imputed -> P.projected.pca.tsv")
+    p.add_argument("--gpca-make-grm", action="store_true",
+                   help="EigenSNP workflow: also write the genetic relationship matrix of the kept SNPs in GCTA's binary layout "
+                        "(P.grm.bin, P.grm.N.bin, P.grm.id).  Each entry is (1/K) sum of Z_j Z_k over the K kept SNPs, missing calls at "
+                        "0: the divisor is K for every pair, not GCTA's per-pair count, and GCTA's GRM formula is not claimed; "
+                        "P.grm.N.bin holds the SNPs where both samples are observed")
+    p.add_argument("--gpca-grm-scaling", choices=("standardized", "centred"), default="standardized",
+                   help="--gpca-make-grm: Z = (g - mean) / s.d. (standardized, the matrix the PCA factorises) or g - mean (centred)")
     return p
+
+
+def grm_bands(n: int, max_entries: int = 1 << 26):
+    """Consecutive row bands [row0, row1) of an n-sample lower triangle, each of at most max_entries entries (at least one row)."""
+    r0 = 0
+    while r0 < n:
+        r1 = r0 + 1
+        while r1 < n and (r1 + 1) * (r1 + 2) // 2 - r0 * (r0 + 1) // 2 <= max_entries:
+            r1 += 1
+        yield r0, r1
+        r0 = r1
 
 
 def _engine_modes(a, bed_samples: int = 0):
@@ -203,6 +221,12 @@ def run_eigensnp_workflow(a) -> int:
         _log("No samples or SNPs available for EigenSNP PCA after preparation.")     # main.rs:349-352
         return 0
     eng.set_standardization(st["mu"], st["sigma"], keep)
+    if a.gpca_make_grm:
+        _ensure_parent(a.output_prefix)
+        fids = fs.family_ids if cols is None else [fs.family_ids[i] for i in cols]
+        gio.write_grm(a.output_prefix, fids, sample_ids,
+                      (eng.grm(a.gpca_grm_scaling, rows=b, npairs=True) for b in grm_bands(len(sample_ids))))
+        _log(f"GRM of {len(sample_ids)} samples over {int(keep.sum())} SNPs written to {a.output_prefix}.grm.bin")
     acc = MicroarrayGenotypeAccessor(eng)
     rows = acc.original_indices_of_pca_snps()
     row_to_id = {int(r): i for i, r in enumerate(rows)}
@@ -267,6 +291,8 @@ def run_project_workflow(a) -> int:
 
 def main(argv=None) -> int:
     a = build_parser().parse_args(argv)
+    if a.gpca_make_grm and not a.eigensnp:
+        raise SystemExit("error: --gpca-make-grm needs the --eigensnp workflow")
     if a.gpca_project_model:
         return run_project_workflow(a)
     if a.gpca_save_model and not a.eigensnp:

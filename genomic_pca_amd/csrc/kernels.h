@@ -301,4 +301,23 @@ void launch_project_colmax(hipStream_t st, const float* X, int64_t rows, int L, 
 // used[n] = n_model - cnt[n]
 void launch_project_used(hipStream_t st, const unsigned* cnt, int64_t N, double n_model, double* used);
 
+// ---- genetic relationship matrix: lower-triangular SYRK over the kept rows (grm.hip) ---------------------------------------------------
+// Tables of one 32-row block, kGrmTabBytes bytes: [4][kGrmDigits][32] base-128 digits (plane 0 least significant, each in [0, 127]) of
+// w, 2w, c = -r b and e = b^2 on the call's common power-of-two scale (0 on rows that are not kept).  Integer partials are flushed to f64
+// once per kGrmFlushRows rows, counted from the first row of the launch.
+constexpr int kGrmDigits = 6;
+constexpr int kGrmFlushRows = 4096;
+constexpr int kGrmTabBytes = 4 * kGrmDigits * 32;
+// tiles: (tile row, tile column) pairs of 64 x 64 output tiles, tile row >= tile column; R, Q: running sums of the band (first: from 0)
+void launch_grm(hipStream_t st, const void* G, int packed, int64_t ldr, int64_t rows_pad, const int8_t* tab, const uint32_t* kmask,
+                const int2* tiles, int64_t ntiles, int64_t row0, int64_t row1, int64_t N, double* R, int* Q, int first);
+// Up, Vp [ceil(rows / kGrmFlushRows)][Npad]: per flush group, sum of qc g' and of qe m over kept rows; cnt += kept rows missing;
+// *bad |= 1 on a kept row with a value outside {0, 1, 2, missing}
+void launch_grm_vec(hipStream_t st, const void* G, int packed, int64_t ldr, int64_t rows, int64_t Npad, const uint8_t* keep,
+                    const int64_t* qc, const int64_t* qe, double* Up, double* Vp, unsigned* cnt, unsigned* bad);
+void launch_grm_vec_fold(hipStream_t st, const double* Up, const double* Vp, int64_t rows, int64_t Npad, double* u, double* v);
+// out = S (R - u_a - u_b + beta - v_a - v_b), npairs (may be NULL) = K - cnt_a - cnt_b + Q, band rows [row0, row1)
+void launch_grm_finish(hipStream_t st, const double* R, const int* Q, const double* u, const double* v, const unsigned* cnt, double S,
+                       double beta, double K, int64_t row0, int64_t row1, double* out, double* npairs);
+
 }  // namespace gpca

@@ -20,7 +20,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass, field
-from typing import Optional, Sequence
+from typing import Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -364,6 +364,36 @@ class GpcaEngine:
         used = np.empty(N, np.int32)
         self._chk(self._lib.gpca_project(self._h, _vp(mu), _vp(sigma), _vp(W), k, _vp(scores), _vp(used)))
         return scores, used
+
+    def grm(self, scaling: str = "standardized", rows: Optional[Tuple[int, int]] = None, npairs: bool = False):
+        """Genetic relationship matrix of the kept rows (gpca_grm): (1 / K) Z^T Z with missing calls at 0, K = kept rows.
+        scaling: "standardized" (Z = r g + b, the matrix gpca_rsvd factorises) or "centred" (Z = g - mu).  rows = (row0, row1): rows
+        [row0, row1) of the lower triangle packed row-major (GCTA .grm.bin order), f64; rows = None: the full symmetric [N][N] f64 array.
+        npairs=True also returns the number of kept rows where both samples are observed (f32, same shape)."""
+        if scaling not in ("standardized", "centred"):
+            raise ValueError('scaling must be "standardized" or "centred"')
+        sc = _lib.GRM_STANDARDIZED if scaling == "standardized" else _lib.GRM_CENTRED
+        N = self.dims()[1]
+        r0, r1 = (0, N) if rows is None else (int(rows[0]), int(rows[1]))
+        n0 = r0 * (r0 + 1) // 2
+        E = max(r1 * (r1 + 1) // 2 - n0, 0)
+        g = np.empty(max(E, 1), np.float64)
+        npv = np.empty(max(E, 1), np.float32) if npairs else None
+        self._chk(self._lib.gpca_grm(self._h, sc, r0, r1, _vp(g), _vp(npv)))
+        g = g[:E]
+        npv = npv[:E] if npairs else None
+        if rows is not None:
+            return (g, npv) if npairs else g
+        il = np.tril_indices(N)
+        full = np.zeros((N, N), np.float64)
+        full[il] = g
+        full.T[il] = g
+        if not npairs:
+            return full
+        fp = np.zeros((N, N), np.float32)
+        fp[il] = npv
+        fp.T[il] = npv
+        return full, fp
 
     # -- f3: the stages of EigenSNPCoreAlgorithm (gpca.h)
     def copy_rows_from(self, src: "GpcaEngine", row0: int, rows: int):

@@ -58,6 +58,7 @@ struct PlinkFileset {
     std::vector<std::string> sample_ids, variant_ids, chromosomes;
     std::vector<int64_t> positions;
     std::vector<std::string> allele1, allele2;   // .bim columns 5 / 6: A1 (the allele the dosages count), A2
+    std::vector<std::string> family_ids;         // .fam FID
     void* map_base = nullptr; size_t map_len = 0;
     PlinkFileset() = default;
     PlinkFileset(const PlinkFileset&) = delete;
@@ -78,7 +79,7 @@ inline void read_plink(const std::string& bed_path, PlinkFileset& fs) {
         if (!f) throw std::runtime_error("cannot open " + prefix + ".fam");
         while (std::getline(f, line)) {
             const auto p = split_ws(line);
-            if (!p.empty()) fs.sample_ids.push_back(p.size() > 1 ? p[1] : p[0]);
+            if (!p.empty()) { fs.sample_ids.push_back(p.size() > 1 ? p[1] : p[0]); fs.family_ids.push_back(p[0]); }
         }
     }
     {
@@ -506,6 +507,38 @@ inline void write_projected(const std::string& prefix, const std::vector<std::st
         std::fprintf(o.f, "\t%d\n", (int)used[i]);
     }
 }
+
+// GCTA's binary GRM layout, written band by band: P.grm.bin (f32 little-endian, lower triangle with the diagonal, packed row-major),
+// P.grm.N.bin (f32, the number of SNPs behind each entry), P.grm.id (FID<TAB>IID per sample).  Bands come in row order, packed the same
+// way (gpca_grm's output); close() checks that they covered the n (n + 1) / 2 entries and writes the ids.
+class GrmWriter {
+public:
+    GrmWriter(const std::string& prefix, const std::vector<std::string>& family_ids, const std::vector<std::string>& sample_ids)
+        : prefix_(prefix), fids_(family_ids), iids_(sample_ids), g_(prefix + ".grm.bin"), n_(prefix + ".grm.N.bin") {
+        if (fids_.size() != iids_.size()) throw std::runtime_error("write_grm: one family ID per sample");
+    }
+    void add_band(const double* grm, const float* npairs, size_t entries) {
+        std::vector<float> v(entries);
+        for (size_t i = 0; i < entries; ++i) v[i] = (float)grm[i];
+        if (std::fwrite(v.data(), 4, entries, g_.f) != entries || std::fwrite(npairs, 4, entries, n_.f) != entries)
+            throw std::runtime_error("cannot write " + prefix_ + ".grm.bin / .grm.N.bin");
+        total_ += entries;
+    }
+    void close() {
+        const size_t n = iids_.size();
+        if (total_ != n * (n + 1) / 2)
+            throw std::runtime_error("write_grm: the bands hold " + std::to_string(total_) + " entries, " + std::to_string(n) + " samples need " +
+                                     std::to_string(n * (n + 1) / 2));
+        OutFile o(prefix_ + ".grm.id");
+        for (size_t i = 0; i < n; ++i) std::fprintf(o.f, "%s\t%s\n", fids_[i].c_str(), iids_[i].c_str());
+    }
+
+private:
+    std::string prefix_;
+    std::vector<std::string> fids_, iids_;
+    OutFile g_, n_;
+    size_t total_ = 0;
+};
 
 }  // namespace gpca_host
 

@@ -42,6 +42,8 @@ struct Args {
     bool local_stage = false;
     bool save_model = false;          // --gpca-save-model: also write P.eigensnp.model.tsv
     std::string project_model;        // --gpca-project-model MODEL: project --bed-file's samples onto it
+    bool make_grm = false;            // --gpca-make-grm: also write P.grm.bin / P.grm.N.bin / P.grm.id
+    std::string grm_scaling = "standardized";
 };
 
 [[noreturn]] void usage_error(const std::string& msg) {
@@ -97,6 +99,13 @@ void print_help() {
         "                                       loadings) for --gpca-project-model\n"
         "      --gpca-project-model <MODEL>     project the samples of --bed-file onto the PCs of MODEL (matched by variant ID, allele\n"
         "                                       flips handled, missing calls mean-imputed) -> P.projected.pca.tsv\n"
+        "      --gpca-make-grm                  EigenSNP workflow: also write the genetic relationship matrix of the kept SNPs in\n"
+        "                                       GCTA's binary layout (P.grm.bin, P.grm.N.bin, P.grm.id).  Each entry is (1/K) sum of\n"
+        "                                       Z_j Z_k over the K kept SNPs, missing calls at 0: the divisor is K for every pair, not\n"
+        "                                       GCTA's per-pair count, and GCTA's GRM formula is not claimed; P.grm.N.bin holds the\n"
+        "                                       SNPs where both samples are observed\n"
+        "      --gpca-grm-scaling <S>           --gpca-make-grm: standardized ((g - mean) / s.d., the matrix the PCA factorises) or\n"
+        "                                       centred (g - mean) [default: standardized]\n"
         "  -h, --help                           Print help");
 }
 
@@ -162,6 +171,8 @@ Args parse(int argc, char** argv) {
         else if (f == "--gpca-eigensnp-local-stage") a.local_stage = true;
         else if (f == "--gpca-save-model") a.save_model = true;
         else if (f == "--gpca-project-model") a.project_model = val();
+        else if (f == "--gpca-make-grm") a.make_grm = true;
+        else if (f == "--gpca-grm-scaling") { a.grm_scaling = val(); if (a.grm_scaling != "standardized" && a.grm_scaling != "centred") usage_error("invalid value '" + a.grm_scaling + "' for '--gpca-grm-scaling' (standardized, centred)"); }
         else usage_error("unexpected argument '" + f + "' found");
     }
     if (a.output_prefix.empty()) usage_error("the following required arguments were not provided:\n  --out <OUTPUT_PREFIX>");
@@ -307,6 +318,25 @@ int run_eigensnp_workflow(Args a) {
     logmsg(buf);
     if (sample_ids.empty() || n_in == 0) { logmsg("No samples or SNPs available for EigenSNP PCA after preparation."); return 0; }   // main.rs:349-352
     eng.set_standardization(st.mu, st.sigma, keep);
+    if (a.make_grm) {
+        gpca_host::ensure_parent(a.output_prefix);
+        std::vector<std::string> fids = fs.family_ids;
+        if (use_kept) { fids.clear(); for (int64_t c : kept.cols) fids.push_back(fs.family_ids[(size_t)c]); }
+        gpca_host::GrmWriter w(a.output_prefix, fids, sample_ids);
+        const int scaling = a.grm_scaling == "centred" ? GPCA_GRM_CENTRED : GPCA_GRM_STANDARDIZED;
+        const int64_t n = (int64_t)sample_ids.size();
+        for (int64_t r0 = 0; r0 < n;) {      // row bands of at most 2^26 entries (at least one row), as the Python command line cuts them
+            int64_t r1 = r0 + 1;
+            while (r1 < n && (r1 + 1) * (r1 + 2) / 2 - r0 * (r0 + 1) / 2 <= ((int64_t)1 << 26)) ++r1;
+            std::vector<float> np;
+            const std::vector<double> g = eng.grm(scaling, r0, r1, &np);
+            w.add_band(g.data(), np.data(), g.size());
+            r0 = r1;
+        }
+        w.close();
+        std::snprintf(buf, sizeof buf, "GRM of %lld samples over %lld SNPs written to %s.grm.bin", (long long)n, (long long)n_in, a.output_prefix.c_str());
+        logmsg(buf);
+    }
     gpca::MicroarrayGenotypeAccessor acc(eng);
     const std::vector<int64_t> rows = acc.original_indices_of_pca_snps();
     std::unordered_map<int64_t, int64_t> row_to_id;
@@ -394,6 +424,7 @@ int run_project_workflow(Args a) {
 int main(int argc, char** argv) {
     const Args a = parse(argc, argv);
     try {
+        if (a.make_grm && !a.eigensnp) { std::fprintf(stderr, "error: --gpca-make-grm needs the --eigensnp workflow\n"); return 2; }
         if (!a.project_model.empty()) return run_project_workflow(a);
         if (a.save_model && !a.eigensnp) { std::fprintf(stderr, "error: --gpca-save-model needs the --eigensnp workflow\n"); return 2; }
         return a.eigensnp ? run_eigensnp_workflow(a) : run_vcf_workflow(a);

@@ -34,6 +34,7 @@ class PlinkFileset:
     positions: np.ndarray         # .bim bp (int64)
     allele1: List[str] = None     # .bim column 5: A1, the allele the dosages count
     allele2: List[str] = None     # .bim column 6: A2
+    family_ids: List[str] = None  # .fam FID
 
 
 def _strip_ext(path: str) -> str:
@@ -45,12 +46,13 @@ def _strip_ext(path: str) -> str:
 
 def read_plink(bed_path: str) -> PlinkFileset:
     prefix = _strip_ext(bed_path)
-    iids = []
+    iids, fids = [], []
     with open(prefix + ".fam") as f:
         for line in f:
             p = line.split()
             if p:
                 iids.append(p[1] if len(p) > 1 else p[0])
+                fids.append(p[0])
     sids, chroms, pos, a1, a2 = [], [], [], [], []
     with open(prefix + ".bim") as f:
         for line in f:
@@ -68,7 +70,7 @@ def read_plink(bed_path: str) -> PlinkFileset:
     if size != 3 + m * bpr:
         raise ValueError(f"{prefix}.bed: size {size} does not match {m} SNPs x {n} samples")
     rows = np.memmap(prefix + ".bed", dtype=np.uint8, mode="r", offset=3, shape=(m, bpr))
-    return PlinkFileset(rows, n, iids, sids, chroms, np.asarray(pos, np.int64), a1, a2)
+    return PlinkFileset(rows, n, iids, sids, chroms, np.asarray(pos, np.int64), a1, a2, fids)
 
 
 def write_plink(prefix: str, dosage_count_a1: np.ndarray, sample_ids: Sequence[str], variant_ids: Sequence[str],
@@ -405,3 +407,29 @@ def write_projected(prefix: str, sample_names: Sequence[str], scores: np.ndarray
         for i, name in enumerate(sample_names):
             f.write(name + "".join("\t" + _fmt6(v) for v in scores[i]) + f"\t{int(used[i])}\n")
     return path
+
+
+def write_grm(prefix: str, family_ids: Sequence[str], sample_ids: Sequence[str], bands) -> Tuple[str, str, str]:
+    """GCTA's binary GRM layout: P.grm.bin (f32 little-endian, lower triangle with the diagonal, packed row-major), P.grm.N.bin (f32,
+    the number of SNPs behind each entry) and P.grm.id (FID<TAB>IID per sample).  bands: (grm, npairs) pairs of consecutive row bands
+    in row order, each packed the same way (gpca_grm's output), written as they come: the whole matrix is never held."""
+    n = len(sample_ids)
+    if len(family_ids) != n:
+        raise ValueError("write_grm: one family ID per sample")
+    paths = (f"{prefix}.grm.bin", f"{prefix}.grm.N.bin", f"{prefix}.grm.id")
+    total = 0
+    with open(paths[0], "wb") as fg, open(paths[1], "wb") as fn:
+        for g, npairs in bands:
+            g = np.asarray(g).ravel()
+            npairs = np.asarray(npairs).ravel()
+            if g.shape != npairs.shape:
+                raise ValueError("write_grm: a band's grm and npairs differ in length")
+            fg.write(g.astype("<f4").tobytes())
+            fn.write(npairs.astype("<f4").tobytes())
+            total += g.size
+    if total != n * (n + 1) // 2:
+        raise ValueError(f"write_grm: the bands hold {total} entries, {n} samples need {n * (n + 1) // 2}")
+    with open(paths[2], "w") as f:
+        for fid, iid in zip(family_ids, sample_ids):
+            f.write(f"{fid}\t{iid}\n")
+    return paths

@@ -289,6 +289,20 @@ GPCA_API int gpca_transform(gpca_handle* h, double* out);
  * scores and counts are summed in one exchange that also carries the status word, so a rank-local failure comes back from every rank. */
 GPCA_API int gpca_project(gpca_handle* h, const float* mu, const float* sigma, const float* W, int32_t k, double* scores, int32_t* n_used);
 
+/* ---- a8: genetic relationship matrix of this handle's kept rows (the reference's exact-PCA check, tests/pca.py: GRM = X X^T / kept).
+ * Z[i][n] = r_i g + b_i for an observed call (GPCA_GRM_STANDARDIZED: the matrix gpca_rsvd factorises, r = 1 / sigma, b = -mu r in f32 as
+ * gpca_set_standardization makes them) or g - mu_i (GPCA_GRM_CENTRED), and 0 for a missing call.  Over the kept rows, K of them summed
+ * over all ranks:  grm[j][k] = (1 / K) sum_i Z[i][j] Z[i][k];  npairs[j][k] = kept rows where both j and k are observed (exact).
+ * Writes rows row0 <= j < row1 of the lower triangle, diagonal included, packed row-major: element (j, k <= j) at
+ * j (j + 1) / 2 - row0 (row0 + 1) / 2 + k (GCTA's .grm.bin order), so a band is bit-identical to the same rows of the full call.
+ * npairs may be NULL.  Works on every handle (int8 or 2-bit, resident or streamed, either precision, sharded); the sample mask is
+ * ignored and no fitted result of the handle is touched.  Sharded handles: every rank passes the same band; bands and status go
+ * through the exchange, so a rank-local failure comes back from every rank.  Errors: GPCA_ERR_BAD_ARG (scaling, row range, a kept
+ * row with a negative or non-finite mean), GPCA_ERR_STATE (no standardisation, or K = 0), GPCA_ERR_INVALID_GENOTYPE (a kept row holds
+ * a value outside {0, 1, 2, missing}), GPCA_ERR_OOM (the band does not fit in device memory: checked before any allocation). */
+enum { GPCA_GRM_STANDARDIZED = 0, GPCA_GRM_CENTRED = 1 };
+GPCA_API int gpca_grm(gpca_handle* h, int32_t scaling, int64_t row0, int64_t row1, double* grm, float* npairs /* may be NULL */);
+
 /* ---- f3: the stages of EigenSNPCoreAlgorithm::compute_pca (main.rs:311-327, 359-366) ------------------------------------------
  * The algorithm lives in the un-vendored efficient_pca crate (Cargo.toml:30, branch "main", no pinned revision): what follows is
  * the stage structure of its published description -- per-LD-block local bases learnt on a sample subset, condensed features of

@@ -152,6 +152,17 @@ public:
         check(gpca_project(h_, mu, sigma, W, k, s.data(), used ? used->data() : nullptr));
         return s;
     }
+    // rows [row0, row1) of the lower triangle of the GRM of the kept rows, packed row-major (gpca_grm); npairs (may be null) receives
+    // the number of kept rows where both samples are observed
+    std::vector<double> grm(int scaling, int64_t row0, int64_t row1, std::vector<float>* npairs = nullptr) const {
+        const size_t e = row1 > row0 ? (size_t)(row1 * (row1 + 1) / 2 - row0 * (row0 + 1) / 2) : 0;
+        std::vector<double> g(std::max<size_t>(e, 1));
+        if (npairs) npairs->assign(std::max<size_t>(e, 1), 0.f);
+        check(gpca_grm(h_, scaling, row0, row1, g.data(), npairs ? npairs->data() : nullptr));
+        g.resize(e);
+        if (npairs) npairs->resize(e);
+        return g;
+    }
 
 private:
     gpca_handle* h_ = nullptr;
