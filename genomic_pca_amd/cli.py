@@ -90,6 +90,16 @@ def build_parser() -> argparse.ArgumentParser:
                         "P.grm.N.bin holds the SNPs where both samples are observed")
     p.add_argument("--gpca-grm-scaling", choices=("standardized", "centred"), default="standardized",
                    help="--gpca-make-grm: Z = (g - mean) / s.d. (standardized, the matrix the PCA factorises) or g - mean (centred)")
+    p.add_argument("--gpca-make-king", action="store_true",
+                   help="EigenSNP workflow: also write the KING-robust kinship of every sample pair over the kept SNPs to P.kin0 "
+                        "(#FID1 IID1 FID2 IID2 NSNP HETHET IBS0 KINSHIP, ID1 the earlier sample in .fam order)")
+    p.add_argument("--gpca-king-table-filter", type=float, default=None, metavar="X",
+                   help="--gpca-make-king: write only the pairs with kinship >= X")
+    p.add_argument("--gpca-king-cutoff", type=float, default=None, metavar="X",
+                   help="EigenSNP workflow: drop related samples before the PCA (0 < X < 0.5; 0.0884 = second degree).  While a pair with "
+                        "KING-robust kinship > X remains, the sample with the most such partners leaves (ties: the later one in .fam "
+                        "order) -> P.king.cutoff.in.id / .out.id.  The PCs are fitted on the in-set and every sample is projected onto "
+                        "them; SNP QC, means and s.d. stay over all samples")
     return p
 
 
@@ -227,6 +237,9 @@ def run_eigensnp_workflow(a) -> int:
         gio.write_grm(a.output_prefix, fids, sample_ids,
                       (eng.grm(a.gpca_grm_scaling, rows=b, npairs=True) for b in grm_bands(len(sample_ids))))
         _log(f"GRM of {len(sample_ids)} samples over {int(keep.sum())} SNPs written to {a.output_prefix}.grm.bin")
+    inset = None
+    if a.gpca_make_king or a.gpca_king_cutoff is not None:
+        inset = _king(eng, a, fs, cols, sample_ids, int(keep.sum()))
     acc = MicroarrayGenotypeAccessor(eng)
     rows = acc.original_indices_of_pca_snps()
     row_to_id = {int(r): i for i, r in enumerate(rows)}
@@ -242,12 +255,17 @@ def run_eigensnp_workflow(a) -> int:
         local_rsvd_num_power_iterations=a.eigensnp_local_power_iter, random_seed=a.eigensnp_seed,
         snp_processing_strip_size=a.eigensnp_snp_strip_size, refine_pass_count=a.eigensnp_refine_passes,
         collect_diagnostics=a.eigensnp_collect_diagnostics)
-    k = min(cfg.target_num_global_pcs, len(sample_ids), len(rows))
+    n_fit = len(sample_ids) if inset is None else int(inset.sum())
+    k = min(cfg.target_num_global_pcs, n_fit, len(rows))
     cfg.target_num_global_pcs = k
-    cfg.global_pca_sketch_oversampling = max(0, min(cfg.global_pca_sketch_oversampling, min(len(sample_ids), len(rows)) - k))
-    out, _ = EigenSNPCoreAlgorithm(cfg).compute_pca(acc, specs, local_stage=a.gpca_eigensnp_local_stage)
+    cfg.global_pca_sketch_oversampling = max(0, min(cfg.global_pca_sketch_oversampling, min(n_fit, len(rows)) - k))
+    if inset is not None and not inset.all():
+        eng.set_sample_mask(inset.astype(np.uint8))                                # the fit sees the in-set only
+    out, _ = EigenSNPCoreAlgorithm(cfg).compute_pca(acc, specs, local_stage=a.gpca_eigensnp_local_stage, project_all=inset is not None)
+    # with the cutoff: every sample projected onto the in-set's fit, the relatives included
+    scores = out.final_sample_principal_component_scores if inset is None else out.projected_sample_scores
     _ensure_parent(a.output_prefix)
-    gio.write_principal_components(a.output_prefix, "eigensnp.pca.tsv", sample_ids, out.final_sample_principal_component_scores)
+    gio.write_principal_components(a.output_prefix, "eigensnp.pca.tsv", sample_ids, scores)
     gio.write_eigenvalues(a.output_prefix, out.final_principal_component_eigenvalues)
     gio.write_loadings(a.output_prefix, [fs.variant_ids[r] for r in rows], [fs.chromosomes[r] for r in rows],
                        [int(fs.positions[r]) for r in rows], out.final_snp_principal_component_loadings)
@@ -257,10 +275,43 @@ def run_eigensnp_workflow(a) -> int:
             [fs.variant_ids[r] for r in rows], [fs.chromosomes[r] for r in rows], [int(fs.positions[r]) for r in rows],
             [fs.allele1[r] for r in rows], [fs.allele2[r] for r in rows], stz["mu"][rows], stz["sigma"][rows],
             np.asarray(out.final_snp_principal_component_loadings, np.float32), np.asarray(out.final_principal_component_eigenvalues, np.float64),
-            len(sample_ids)))
+            n_fit))
     eng.close()
     _log(f"EigenSNP workflow done in {time.time() - t0:.2f}s")
     return 0
+
+
+def _king(eng, a, fs, cols, sample_ids, n_snps):
+    """--gpca-make-king / --gpca-king-cutoff: one pass over the bands of the kinship triangle (gpca_king) that writes P.kin0 and / or
+    collects the pairs above the cutoff; with the cutoff, the greedy in-set (io.king_unrelated) and its id files.  Returns the in-set
+    mask, or None without the cutoff."""
+    _ensure_parent(a.output_prefix)
+    fids = fs.family_ids if cols is None else [fs.family_ids[i] for i in cols]
+    n = len(sample_ids)
+    related = []
+
+    def bands():
+        for b in gio.king_bands(n):
+            kin, cnt = eng.king(rows=b, counts=True)
+            if a.gpca_king_cutoff is not None:
+                j, k = gio.band_pairs(*b)
+                hit = np.flatnonzero(kin > a.gpca_king_cutoff)
+                related.extend(zip(k[hit].tolist(), j[hit].tolist()))
+            yield b, kin, cnt
+    if a.gpca_make_king:
+        gio.write_kin0(a.output_prefix, fids, sample_ids, bands(), a.gpca_king_table_filter)
+        _log(f"KING-robust kinship of {n} samples over {n_snps} SNPs written to {a.output_prefix}.kin0")
+    else:
+        for _ in bands():
+            pass
+    if a.gpca_king_cutoff is None:
+        return None
+    inset = gio.king_unrelated(n, related)
+    gio.write_king_cutoff_ids(a.output_prefix, fids, sample_ids, inset)
+    _log(f"KING cutoff {a.gpca_king_cutoff:g}: {len(related)} related pairs, {n - int(inset.sum())} of {n} samples left out of the fit")
+    if int(inset.sum()) < 2:
+        raise SystemExit("error: --gpca-king-cutoff leaves fewer than 2 samples to fit the PCA on")
+    return inset
 
 
 def run_project_workflow(a) -> int:
@@ -293,6 +344,14 @@ def main(argv=None) -> int:
     a = build_parser().parse_args(argv)
     if a.gpca_make_grm and not a.eigensnp:
         raise SystemExit("error: --gpca-make-grm needs the --eigensnp workflow")
+    if (a.gpca_make_king or a.gpca_king_cutoff is not None) and not a.eigensnp:
+        raise SystemExit("error: --gpca-make-king and --gpca-king-cutoff need the --eigensnp workflow")
+    if a.gpca_king_table_filter is not None and not a.gpca_make_king:
+        raise SystemExit("error: --gpca-king-table-filter needs --gpca-make-king")
+    if a.gpca_king_cutoff is not None and not 0.0 < a.gpca_king_cutoff < 0.5:
+        raise SystemExit("error: --gpca-king-cutoff must lie in (0, 0.5)")
+    if a.gpca_king_cutoff is not None and a.gpca_eigensnp_local_stage:
+        raise SystemExit("error: --gpca-king-cutoff cannot be combined with --gpca-eigensnp-local-stage (that stage owns the sample mask)")
     if a.gpca_project_model:
         return run_project_workflow(a)
     if a.gpca_save_model and not a.eigensnp:

@@ -1,0 +1,171 @@
+// gpca_king (include/gpca.h section a9): KING-robust kinship of every pair of one row band of the strictly lower triangle, from the
+// handle's kept rows.  One sweep over the resident matrix or the streamed panels (king.hip); the call has its own workspace, allocated
+// and freed per call, and reads nothing of the handle's state but the keep mask of its standardisation.
+#include "gpca_internal.h"
+
+using namespace gpca;
+
+namespace {
+struct KingWs {
+    double* kin = nullptr;
+    int* counts = nullptr;
+    uint32_t* kmask = nullptr;
+    uint8_t* keep = nullptr;
+    int2* tiles = nullptr;
+    unsigned *het = nullptr, *miss = nullptr, *bad = nullptr;    // (device memory: the per-sample counts take atomics)
+    ~KingWs() { dfree(kin); dfree(counts); dfree(kmask); dfree(keep); dfree(tiles); dfree(het); dfree(miss); dfree(bad); }
+};
+template <typename T>
+hipError_t dalloc(T*& p, size_t elems) { return hipMalloc((void**)&p, std::max<size_t>(elems, 1) * sizeof(T)); }
+// the exchange buffer: device memory, or pinned host memory the device can address when the device has none left (gpca_grm's rule)
+struct XBuf {
+    double* p = nullptr; bool pinned = false;
+    hipError_t alloc(size_t n) {
+        if (hipMalloc((void**)&p, std::max<size_t>(n, 1) * 8) == hipSuccess) return hipSuccess;
+        (void)hipGetLastError();
+        p = nullptr; pinned = true;
+        return hipHostMalloc((void**)&p, std::max<size_t>(n, 1) * 8, hipHostMallocDefault);
+    }
+    ~XBuf() { if (p) { if (pinned) (void)hipHostFree(p); else (void)hipFree(p); } }
+};
+constexpr int kKingTileSamples = 128;   // (king.hip: kKingTile)
+}  // namespace
+
+extern "C" int gpca_king(gpca_handle* h, int64_t row0, int64_t row1, double* kinship, int32_t* counts) {
+    if (!h) return GPCA_ERR_BAD_ARG;
+    if (!kinship) return fail(h, GPCA_ERR_BAD_ARG, "gpca_king: kinship is required");
+    LOCK(h);
+    if (!have_genotypes(h)) return fail(h, GPCA_ERR_STATE, "gpca_king: no genotypes resident and no panel stream open");
+    const int64_t M = h->M, N = h->N, Mpad = h->Mpad, Npad = h->ldg;
+    if (row0 < 0 || row1 <= row0 || row1 > N)
+        return fail(h, GPCA_ERR_BAD_ARG, "gpca_king: rows must satisfy 0 <= row0 < row1 <= N (N = " + std::to_string(N) + ")");
+    if (!h->have_stats) return fail(h, GPCA_ERR_STATE, "gpca_king: no standardisation: run gpca_snp_stats or gpca_set_standardization first");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->st));
+    const bool mr = multi_rank(h);
+    const bool packed = h->storage == GPCA_STORE_2BIT;
+    const int64_t E = row1 * (row1 - 1) / 2 - row0 * (row0 - 1) / 2;      // strictly lower: row j holds j entries
+    int lrc = GPCA_OK;
+    // A rank-local failure does not return before the exchange on a sharded handle: every rank must reach it (gpca_grm's rule).
+#define LOCAL(x) do { if (lrc == GPCA_OK) lrc = (x); if (lrc != GPCA_OK && !mr) return lrc; } while (0)
+
+    // 1. the kept rows: their bit mask per 32-row block and their count
+    std::vector<uint8_t> keep((size_t)M);
+    HIPCHK(hipMemcpy(keep.data(), h->d_keep, (size_t)M, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> kmask((size_t)(Mpad / 32), 0u);
+    int64_t K_local = 0;
+    for (int64_t i = 0; i < M; ++i)
+        if (keep[(size_t)i]) { kmask[(size_t)(i >> 5)] |= 1u << (i & 31); ++K_local; }
+    constexpr int64_t kMaxK = (int64_t)1 << 31;
+    if (!mr && K_local == 0) return fail(h, GPCA_ERR_STATE, "gpca_king: no kept row (the keep mask is empty)");
+    if (K_local >= kMaxK) LOCAL(fail(h, GPCA_ERR_BAD_ARG, "gpca_king: 2^31 or more kept rows (the counts are 32-bit)"));
+
+    // 2. preflight: everything the call allocates on the device, before any allocation
+    const int64_t t0 = row0 / kKingTileSamples, t1 = (row1 + kKingTileSamples - 1) / kKingTileSamples;
+    const int64_t ntiles = t1 * (t1 + 1) / 2 - t0 * (t0 + 1) / 2;
+    const size_t outn = (size_t)E * 5 + 2 * (size_t)Npad + 1 + 16;     // XX HH HM MH MM | het | miss | K | status slots: one exchange
+    const double need = 8.0 * (double)outn + (counts ? 20.0 : 8.0) * (double)E + 8.0 * (double)Npad + (double)(Mpad / 32) * 4 + (double)M + 8.0 * (double)ntiles +
+                        (64 << 20);
+    auto preflight = [&]() -> int {
+        size_t fr = 0, tot = 0;
+        HIPCHK(hipMemGetInfo(&fr, &tot));
+        if (need > (double)fr) {
+            char buf[256];
+            snprintf(buf, sizeof buf, "gpca_king: the band needs %.3g GB of device memory, %.3g GB are free: ask for fewer rows", need * 1e-9, (double)fr * 1e-9);
+            return fail(h, GPCA_ERR_OOM, buf);
+        }
+        return GPCA_OK;
+    };
+    LOCAL(preflight());
+
+    KingWs ws;
+    XBuf xb;
+    HIPCHK(xb.alloc(outn));
+    HIPCHK(hipMemsetAsync(xb.p, 0, outn * 8, h->st));
+    double* const R = xb.p;
+    double* const het = R + 5 * (size_t)E;
+    double* const miss = het + Npad;
+    std::vector<int2> tiles;
+    auto prep = [&]() -> int {
+        tiles.reserve((size_t)ntiles);
+        for (int64_t ta = t0; ta < t1; ++ta)
+            for (int64_t tb = 0; tb <= ta; ++tb) tiles.push_back(make_int2((int)ta, (int)tb));
+        HIPCHK(dalloc(ws.kmask, kmask.size())); HIPCHK(dalloc(ws.keep, M)); HIPCHK(dalloc(ws.tiles, tiles.size())); HIPCHK(dalloc(ws.bad, 1));
+        HIPCHK(dalloc(ws.het, Npad)); HIPCHK(dalloc(ws.miss, Npad));
+        HIPCHK(dalloc(ws.kin, E));
+        if (counts) HIPCHK(dalloc(ws.counts, 3 * (size_t)E));
+        hipStream_t st = h->st;
+        HIPCHK(hipMemcpyAsync(ws.kmask, kmask.data(), kmask.size() * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(ws.keep, keep.data(), (size_t)M, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(ws.tiles, tiles.data(), tiles.size() * sizeof(int2), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemsetAsync(ws.bad, 0, 4, st));
+        HIPCHK(hipMemsetAsync(ws.het, 0, (size_t)Npad * 4, st)); HIPCHK(hipMemsetAsync(ws.miss, 0, (size_t)Npad * 4, st));
+        HIPCHK(hipStreamSynchronize(st));
+        return GPCA_OK;
+    };
+    LOCAL(prep());
+
+    // 3. one sweep: per panel (or the resident matrix) the per-sample counts and the dosage check, then the triangle's tiles of the band
+    auto sweep = [&]() -> int {
+        const double elems = (double)M * (double)N;
+        ScopedTimer t(h, "king", 2.0 * 2.0 * 32768.0 * (double)(Mpad / 32) * 16.0 * (double)ntiles, (packed ? elems / 4 : elems));
+        CHK(for_each_panel(h, [&](const PanelView& pv) -> int {
+            const void* G = packed ? (const void*)pv.g2 : (const void*)pv.g8;
+            const int64_t ldr = packed ? h->ld2 : h->ld8;
+            launch_king_vec(h->st, G, packed, ldr, pv.rows, Npad, ws.keep + pv.row0, ws.het, ws.miss, ws.bad);
+            launch_king(h->st, G, packed, ldr, pv.rows_pad, ws.kmask + (pv.row0 >> 5), ws.tiles, ntiles, row0, row1, N, R, E,
+                        pv.index == 0 ? 1 : 0);
+            HIPCHK(hipGetLastError());
+            return GPCA_OK;
+        }));
+        launch_king_vec_f64(h->st, ws.het, ws.miss, Npad, het, miss);
+        HIPCHK(hipGetLastError());
+        return GPCA_OK;
+    };
+    LOCAL(sweep());
+    auto check = [&]() -> int {
+        unsigned bad = 0;
+        HIPCHK(hipMemcpyAsync(&bad, ws.bad, 4, hipMemcpyDeviceToHost, h->st));
+        HIPCHK(hipStreamSynchronize(h->st));
+        if (bad) return fail(h, GPCA_ERR_INVALID_GENOTYPE, "gpca_king: a kept row holds a genotype outside {0, 1, 2, missing}");
+        return GPCA_OK;
+    };
+    LOCAL(check());
+
+    // 4. sharded handles: one exchange of the integer counts (exact in f64 below 2^53), the kept-row count and the status word; the
+    //    kinship is computed after the sum, so every rank gets the one-rank bits
+    double K_total = (double)K_local;
+    if (mr) {
+        double* slot = xb.p + outn - 17;
+        const double kl = lrc == GPCA_OK ? (double)K_local : 0.0;
+        h->status_own = h->err;
+        status_histogram(h->h_status, lrc);
+        if ((hipMemcpyAsync(slot, &kl, 8, hipMemcpyHostToDevice, h->st) != hipSuccess ||
+             hipMemcpyAsync(slot + 1, h->h_status, 16 * sizeof(double), hipMemcpyHostToDevice, h->st) != hipSuccess ||
+             hipStreamSynchronize(h->st) != hipSuccess) && lrc == GPCA_OK)
+            lrc = fail(h, GPCA_ERR_HIP, "gpca_king: status copy failed");
+        { const int xrc = allreduce_f64(h, xb.p, (int64_t)outn); if (xrc != GPCA_OK) return xrc; }
+        double slots[17];
+        HIPCHK(hipMemcpyAsync(slots, slot, 17 * sizeof(double), hipMemcpyDeviceToHost, h->st));
+        HIPCHK(hipStreamSynchronize(h->st));
+        const int own_rc = lrc;
+        lrc = status_verdict(h, slots + 1, own_rc, h->status_own, "gpca_king");
+        if (lrc == GPCA_OK) lrc = own_rc;
+        if (lrc != GPCA_OK) return lrc;
+        K_total = slots[0];
+        if (K_total < 0.5) return fail(h, GPCA_ERR_STATE, "gpca_king: no kept row on any rank (the keep masks are empty)");
+        if (K_total >= (double)kMaxK) return fail(h, GPCA_ERR_BAD_ARG, "gpca_king: 2^31 or more kept rows over the ranks (the counts are 32-bit)");
+    }
+    if (lrc != GPCA_OK) return lrc;
+#undef LOCAL
+
+    // 5. the kinship of the band from the summed counts
+    launch_king_finish(h->st, R, E, het, miss, K_total, row0, row1, ws.kin, ws.counts);
+    HIPCHK(hipGetLastError());
+    if (E > 0) {
+        HIPCHK(hipMemcpyAsync(kinship, ws.kin, (size_t)E * 8, hipMemcpyDeviceToHost, h->st));
+        if (counts) HIPCHK(hipMemcpyAsync(counts, ws.counts, (size_t)E * 12, hipMemcpyDeviceToHost, h->st));
+    }
+    HIPCHK(hipStreamSynchronize(h->st));
+    return GPCA_OK;
+}

@@ -320,4 +320,18 @@ void launch_grm_vec_fold(hipStream_t st, const double* Up, const double* Vp, int
 void launch_grm_finish(hipStream_t st, const double* R, const int* Q, const double* u, const double* v, const unsigned* cnt, double S,
                        double beta, double K, int64_t row0, int64_t row1, double* out, double* npairs);
 
+// ---- KING-robust kinship: lower-triangular SYRK of the het / missing / homozygous indicators over the kept rows (king.hip) ----------
+// tiles: (tile row, tile column) pairs of 128 x 128 output tiles, tile row >= tile column; kmask: one bit per row (kept), per 32-row
+// block of the launch; R [5][E]: running f64 sums XX, HH, HM, MH, MM of the band's strictly-lower entries (first: from 0)
+void launch_king(hipStream_t st, const void* G, int packed, int64_t ldr, int64_t rows_pad, const uint32_t* kmask, const int2* tiles,
+                 int64_t ntiles, int64_t row0, int64_t row1, int64_t N, double* R, int64_t E, int first);
+// het[n], miss[n] += kept rows with a het / missing call (device u32); *bad |= 1 on a kept row with a value outside {0, 1, 2, missing}
+void launch_king_vec(hipStream_t st, const void* G, int packed, int64_t ldr, int64_t rows, int64_t Npad, const uint8_t* keep,
+                     unsigned* het, unsigned* miss, unsigned* bad);
+// het_f, miss_f [Npad] = het, miss as f64 (the exchange buffer's slots)
+void launch_king_vec_f64(hipStream_t st, const unsigned* het, const unsigned* miss, int64_t Npad, double* het_f, double* miss_f);
+// kin [E] = the kinship of the band's pairs, counts (may be NULL) [E][3] = NSNP, HETHET, IBS0; band rows [row0, row1)
+void launch_king_finish(hipStream_t st, const double* R, int64_t E, const double* het, const double* miss, double K, int64_t row0,
+                        int64_t row1, double* kin, int* counts);
+
 }  // namespace gpca

@@ -395,6 +395,32 @@ class GpcaEngine:
         fp.T[il] = npv
         return full, fp
 
+    def king(self, rows: Optional[Tuple[int, int]] = None, counts: bool = False):
+        """KING-robust kinship of the kept rows (gpca_king).  rows = (row0, row1): rows [row0, row1) of the STRICTLY lower triangle packed
+        row-major (pair (j, k < j) at j (j - 1) / 2 - row0 (row0 - 1) / 2 + k), f64; rows = None: the full symmetric [N][N] f64 array with
+        0.5 on the diagonal.  NaN where a pair has no het call on the rows both samples are called on.  counts=True also returns the
+        int32 counts NSNP, HETHET, IBS0 per pair ([pairs][3], or [N][N][3] with zeros on the diagonal)."""
+        N = self.dims()[1]
+        r0, r1 = (0, N) if rows is None else (int(rows[0]), int(rows[1]))
+        E = max(r1 * (r1 - 1) // 2 - r0 * (r0 - 1) // 2, 0)
+        k = np.empty(max(E, 1), np.float64)
+        cnt = np.empty((max(E, 1), 3), np.int32) if counts else None
+        self._chk(self._lib.gpca_king(self._h, r0, r1, _vp(k), _vp(cnt)))
+        k = k[:E]
+        cnt = cnt[:E] if counts else None
+        if rows is not None:
+            return (k, cnt) if counts else k
+        il = np.tril_indices(N, -1)
+        full = np.full((N, N), 0.5, np.float64)
+        full[il] = k
+        full.T[il] = k
+        if not counts:
+            return full
+        fc = np.zeros((N, N, 3), np.int32)
+        fc[il] = cnt
+        fc.transpose(1, 0, 2)[il] = cnt
+        return full, fc
+
     # -- f3: the stages of EigenSNPCoreAlgorithm (gpca.h)
     def copy_rows_from(self, src: "GpcaEngine", row0: int, rows: int):
         """This engine receives rows [row0, row0 + rows) of src's resident matrix (device to device)."""
@@ -641,6 +667,9 @@ class EigenSNPCoreOutput:
     num_qc_samples_used: int = 0
     num_pca_snps_used: int = 0
     num_principal_components_computed: int = 0
+    # compute_pca(..., project_all=True): every sample projected onto the fit (gpca_transform, [N, K] f64), taken while the fit is
+    # valid -- before the keep mask of the blocks' union is restored (which drops the fit)
+    projected_sample_scores: Optional[np.ndarray] = None
 
 
 class EigenSNPCoreAlgorithm:
@@ -678,7 +707,8 @@ class EigenSNPCoreAlgorithm:
             raise ValueError(f"compute_pca: PcaSnpId {int(ids[0] if ids[0] < 0 else ids[-1])} out of range [0, {n_pca})")
         return ids
 
-    def compute_pca(self, accessor: MicroarrayGenotypeAccessor, ld_blocks: Sequence[LdBlockSpecification], local_stage: bool = False):
+    def compute_pca(self, accessor: MicroarrayGenotypeAccessor, ld_blocks: Sequence[LdBlockSpecification], local_stage: bool = False,
+                    project_all: bool = False):
         eng = accessor.engine
         cfg = self.config
         n_pca = accessor.num_pca_snps()
@@ -703,7 +733,7 @@ class EigenSNPCoreAlgorithm:
                          cfg.random_seed)
             sc = eng.scores()     # (the local stage may leave fewer components than target_num_global_pcs: min(K, condensed features))
             out = EigenSNPCoreOutput(sc, eng.eigenvalues(), eng.loadings(), accessor.num_qc_samples(),
-                                     int(ids.size), int(sc.shape[1]))
+                                     int(ids.size), int(sc.shape[1]), eng.transform() if project_all else None)
         finally:
             if restore is not None:
                 eng.set_standardization(restore["mu"], restore["sigma"], restore["keep"])

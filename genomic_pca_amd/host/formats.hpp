@@ -29,6 +29,7 @@
 #include <map>
 #include <sstream>
 #include <stdexcept>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -539,6 +540,77 @@ private:
     OutFile g_, n_;
     size_t total_ = 0;
 };
+
+// P.kin0 (KING-robust kinship), written band by band: `#FID1 IID1 FID2 IID2 NSNP HETHET IBS0 KINSHIP`, tab-separated, one line per
+// pair of gpca_king's band order (ID1 the earlier sample in .fam order), the kinship as %.6f or nan; min_kinship (if set): only pairs
+// with kinship >= it (io.write_kin0).
+class Kin0Writer {
+public:
+    Kin0Writer(const std::string& prefix, const std::vector<std::string>& family_ids, const std::vector<std::string>& sample_ids,
+               bool filter, double min_kinship)
+        : prefix_(prefix), fids_(family_ids), iids_(sample_ids), f_(prefix + ".kin0"), filter_(filter), min_(min_kinship) {
+        if (fids_.size() != iids_.size()) throw std::runtime_error("write_kin0: one family ID per sample");
+        std::fputs("#FID1\tIID1\tFID2\tIID2\tNSNP\tHETHET\tIBS0\tKINSHIP\n", f_.f);
+    }
+    void add_band(int64_t row0, int64_t row1, const double* kin, const int32_t* counts) {
+        if (row0 != next_) throw std::runtime_error("write_kin0: band [" + std::to_string(row0) + ", " + std::to_string(row1) + ") does not follow row " + std::to_string(next_));
+        next_ = row1;
+        size_t i = 0;
+        for (int64_t j = row0; j < row1; ++j)
+            for (int64_t k = 0; k < j; ++k, ++i) {
+                const double v = kin[i];
+                if (filter_ && !(v >= min_)) continue;
+                char num[64];
+                if (v != v) std::snprintf(num, sizeof num, "nan"); else std::snprintf(num, sizeof num, "%.6f", v);
+                std::fprintf(f_.f, "%s\t%s\t%s\t%s\t%d\t%d\t%d\t%s\n", fids_[(size_t)k].c_str(), iids_[(size_t)k].c_str(), fids_[(size_t)j].c_str(),
+                             iids_[(size_t)j].c_str(), counts[3 * i], counts[3 * i + 1], counts[3 * i + 2], num);
+            }
+    }
+    void close() {
+        if (!iids_.empty() && next_ != (int64_t)iids_.size())
+            throw std::runtime_error("write_kin0: the bands end at row " + std::to_string(next_) + ", " + std::to_string(iids_.size()) + " samples need " + std::to_string(iids_.size()));
+    }
+
+private:
+    std::string prefix_;
+    std::vector<std::string> fids_, iids_;
+    OutFile f_;
+    bool filter_;
+    double min_;
+    int64_t next_ = 0;
+};
+
+// The greedy pruning rule of --gpca-king-cutoff (io.king_unrelated): while a related pair remains, the sample with the most remaining
+// partners leaves, ties going to the later sample.  pairs: (i, j) sample indices.  Returns keep[n] (1 = in the fit).
+inline std::vector<uint8_t> king_unrelated(int64_t n, const std::vector<std::pair<int64_t, int64_t>>& pairs) {
+    std::vector<std::set<int64_t>> adj((size_t)n);
+    for (const auto& p : pairs) {
+        if (p.first == p.second || p.first < 0 || p.second < 0 || p.first >= n || p.second >= n) throw std::runtime_error("king_unrelated: bad pair");
+        adj[(size_t)p.first].insert(p.second); adj[(size_t)p.second].insert(p.first);
+    }
+    std::vector<uint8_t> keep((size_t)n, 1);
+    for (;;) {
+        int64_t s = -1; size_t top = 0;
+        for (int64_t i = 0; i < n; ++i)
+            if (adj[(size_t)i].size() >= top && adj[(size_t)i].size() > 0) { top = adj[(size_t)i].size(); s = i; }
+        if (s < 0) break;
+        keep[(size_t)s] = 0;
+        for (int64_t t : adj[(size_t)s]) adj[(size_t)t].erase(s);
+        adj[(size_t)s].clear();
+    }
+    return keep;
+}
+
+// P.king.cutoff.in.id / P.king.cutoff.out.id: `#FID<TAB>IID`, then the samples of each set in .fam order
+inline void write_king_cutoff_ids(const std::string& prefix, const std::vector<std::string>& family_ids, const std::vector<std::string>& sample_ids,
+                                  const std::vector<uint8_t>& keep) {
+    for (int want = 1; want >= 0; --want) {
+        OutFile o(prefix + (want ? ".king.cutoff.in.id" : ".king.cutoff.out.id"));
+        std::fputs("#FID\tIID\n", o.f);
+        for (size_t i = 0; i < sample_ids.size(); ++i)
+            if ((keep[i] != 0) == (want == 1)) std::fprintf(o.f, "%s\t%s\n", family_ids[i].c_str(), sample_ids[i].c_str());
+    }
+}
 
 }  // namespace gpca_host
 

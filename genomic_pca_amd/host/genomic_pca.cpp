@@ -14,6 +14,7 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <memory>
 #include <set>
 #include <string>
 #include <unordered_map>
@@ -44,6 +45,9 @@ struct Args {
     std::string project_model;        // --gpca-project-model MODEL: project --bed-file's samples onto it
     bool make_grm = false;            // --gpca-make-grm: also write P.grm.bin / P.grm.N.bin / P.grm.id
     std::string grm_scaling = "standardized";
+    bool make_king = false;           // --gpca-make-king: also write P.kin0
+    bool have_king_filter = false, have_king_cutoff = false;
+    double king_filter = 0.0, king_cutoff = 0.0;   // --gpca-king-table-filter X, --gpca-king-cutoff X
 };
 
 [[noreturn]] void usage_error(const std::string& msg) {
@@ -106,6 +110,15 @@ void print_help() {
         "                                       SNPs where both samples are observed\n"
         "      --gpca-grm-scaling <S>           --gpca-make-grm: standardized ((g - mean) / s.d., the matrix the PCA factorises) or\n"
         "                                       centred (g - mean) [default: standardized]\n"
+        "      --gpca-make-king                 EigenSNP workflow: also write the KING-robust kinship of every sample pair over the\n"
+        "                                       kept SNPs to P.kin0 (#FID1 IID1 FID2 IID2 NSNP HETHET IBS0 KINSHIP, ID1 the earlier\n"
+        "                                       sample in .fam order)\n"
+        "      --gpca-king-table-filter <X>     --gpca-make-king: write only the pairs with kinship >= X\n"
+        "      --gpca-king-cutoff <X>           EigenSNP workflow: drop related samples before the PCA (0 < X < 0.5; 0.0884 = second\n"
+        "                                       degree).  While a pair with KING-robust kinship > X remains, the sample with the most\n"
+        "                                       such partners leaves (ties: the later one in .fam order) -> P.king.cutoff.in.id / .out.id.\n"
+        "                                       The PCs are fitted on the in-set and every sample is projected onto them; SNP QC, means\n"
+        "                                       and s.d. stay over all samples\n"
         "  -h, --help                           Print help");
 }
 
@@ -173,6 +186,9 @@ Args parse(int argc, char** argv) {
         else if (f == "--gpca-project-model") a.project_model = val();
         else if (f == "--gpca-make-grm") a.make_grm = true;
         else if (f == "--gpca-grm-scaling") { a.grm_scaling = val(); if (a.grm_scaling != "standardized" && a.grm_scaling != "centred") usage_error("invalid value '" + a.grm_scaling + "' for '--gpca-grm-scaling' (standardized, centred)"); }
+        else if (f == "--gpca-make-king") a.make_king = true;
+        else if (f == "--gpca-king-table-filter") { a.king_filter = to_f64(f, val()); a.have_king_filter = true; }
+        else if (f == "--gpca-king-cutoff") { a.king_cutoff = to_f64(f, val()); a.have_king_cutoff = true; }
         else usage_error("unexpected argument '" + f + "' found");
     }
     if (a.output_prefix.empty()) usage_error("the following required arguments were not provided:\n  --out <OUTPUT_PREFIX>");
@@ -337,6 +353,48 @@ int run_eigensnp_workflow(Args a) {
         std::snprintf(buf, sizeof buf, "GRM of %lld samples over %lld SNPs written to %s.grm.bin", (long long)n, (long long)n_in, a.output_prefix.c_str());
         logmsg(buf);
     }
+    std::vector<uint8_t> inset;
+    if (a.make_king || a.have_king_cutoff) {
+        // one pass over the bands of the kinship triangle: P.kin0 and / or the pairs above the cutoff (cli.py:_king)
+        gpca_host::ensure_parent(a.output_prefix);
+        std::vector<std::string> fids = fs.family_ids;
+        if (use_kept) { fids.clear(); for (int64_t c : kept.cols) fids.push_back(fs.family_ids[(size_t)c]); }
+        const int64_t n = (int64_t)sample_ids.size();
+        std::unique_ptr<gpca_host::Kin0Writer> w;
+        if (a.make_king) w.reset(new gpca_host::Kin0Writer(a.output_prefix, fids, sample_ids, a.have_king_filter, a.king_filter));
+        std::vector<std::pair<int64_t, int64_t>> related;
+        for (int64_t r0 = 0; r0 < n;) {      // row bands of at most 2^26 pairs (at least one row), as io.king_bands cuts them
+            int64_t r1 = r0 + 1;
+            while (r1 < n && (r1 + 1) * r1 / 2 - r0 * (r0 - 1) / 2 <= ((int64_t)1 << 26)) ++r1;
+            std::vector<int32_t> cnt;
+            const std::vector<double> kin = eng.king(r0, r1, &cnt);
+            if (w) w->add_band(r0, r1, kin.data(), cnt.data());
+            if (a.have_king_cutoff) {
+                size_t i = 0;
+                for (int64_t j = r0; j < r1; ++j)
+                    for (int64_t k = 0; k < j; ++k, ++i)
+                        if (kin[i] > a.king_cutoff) related.emplace_back(k, j);
+            }
+            r0 = r1;
+        }
+        if (w) {
+            w->close(); w.reset();
+            std::snprintf(buf, sizeof buf, "KING-robust kinship of %lld samples over %lld SNPs written to %s.kin0", (long long)n, (long long)n_in, a.output_prefix.c_str());
+            logmsg(buf);
+        }
+        if (a.have_king_cutoff) {
+            inset = gpca_host::king_unrelated(n, related);
+            gpca_host::write_king_cutoff_ids(a.output_prefix, fids, sample_ids, inset);
+            int64_t n_fit = 0;
+            for (uint8_t v : inset) n_fit += v;
+            std::snprintf(buf, sizeof buf, "KING cutoff %g: %zu related pairs, %lld of %lld samples left out of the fit", a.king_cutoff, related.size(),
+                          (long long)(n - n_fit), (long long)n);
+            logmsg(buf);
+            if (n_fit < 2) { std::fprintf(stderr, "error: --gpca-king-cutoff leaves fewer than 2 samples to fit the PCA on\n"); return 1; }
+        }
+    }
+    int64_t n_fit = (int64_t)sample_ids.size();
+    if (!inset.empty()) { n_fit = 0; for (uint8_t v : inset) n_fit += v; }
     gpca::MicroarrayGenotypeAccessor acc(eng);
     const std::vector<int64_t> rows = acc.original_indices_of_pca_snps();
     std::unordered_map<int64_t, int64_t> row_to_id;
@@ -349,7 +407,7 @@ int run_eigensnp_workflow(Args a) {
         specs.push_back(std::move(s));
     }
     gpca::EigenSNPCoreAlgorithmConfig cfg;
-    const int64_t lim = std::min<int64_t>((int64_t)sample_ids.size(), (int64_t)rows.size());
+    const int64_t lim = std::min<int64_t>(n_fit, (int64_t)rows.size());
     const int64_t k = std::min<int64_t>(a.k_global, lim);
     cfg.target_num_global_pcs = (int)k;
     cfg.components_per_ld_block = (int)a.components_per_block;
@@ -360,12 +418,18 @@ int run_eigensnp_workflow(Args a) {
     cfg.local_rsvd_sketch_oversampling = (int)a.local_oversampling; cfg.local_rsvd_num_power_iterations = (int)a.local_power_iter;
     cfg.random_seed = a.seed; cfg.snp_processing_strip_size = a.strip_size; cfg.refine_pass_count = (int)a.refine_passes;
     cfg.collect_diagnostics = a.collect_diagnostics;
-    const gpca::EigenSNPCoreOutput out = gpca::EigenSNPCoreAlgorithm(cfg).compute_pca(acc, specs, a.local_stage);
+    if (!inset.empty() && n_fit < (int64_t)inset.size()) eng.set_sample_mask(&inset);      // the fit sees the in-set only
+    // with the cutoff every sample is projected onto the in-set's PCs (the relatives included), inside compute_pca while the fit is valid
+    const gpca::EigenSNPCoreOutput out = gpca::EigenSNPCoreAlgorithm(cfg).compute_pca(acc, specs, a.local_stage, !inset.empty());
+    const std::vector<double>& projected = out.projected_sample_scores;
     // the column count comes from the result: the local stage may leave fewer than k components (min(k, condensed features))
     const int kc = (int)out.num_principal_components_computed;
     gpca_host::ensure_parent(a.output_prefix);
-    gpca_host::write_principal_components(a.output_prefix, "eigensnp.pca.tsv", sample_ids, out.final_sample_principal_component_scores.data(),
-                                          out.num_qc_samples_used, kc);
+    if (inset.empty())
+        gpca_host::write_principal_components(a.output_prefix, "eigensnp.pca.tsv", sample_ids, out.final_sample_principal_component_scores.data(),
+                                              out.num_qc_samples_used, kc);
+    else
+        gpca_host::write_principal_components(a.output_prefix, "eigensnp.pca.tsv", sample_ids, projected.data(), (int64_t)sample_ids.size(), kc);
     gpca_host::write_eigenvalues(a.output_prefix, out.final_principal_component_eigenvalues);
     std::vector<std::string> vids, chroms; std::vector<int64_t> pos;
     vids.reserve(rows.size()); chroms.reserve(rows.size()); pos.reserve(rows.size());
@@ -373,7 +437,7 @@ int run_eigensnp_workflow(Args a) {
     gpca_host::write_loadings(a.output_prefix, vids, chroms, pos, out.final_snp_principal_component_loadings.data(), (int64_t)rows.size(), kc);
     if (a.save_model) {
         gpca_host::ProjectionModel m;
-        m.variant_ids = vids; m.chromosomes = chroms; m.positions = pos; m.k = kc; m.n_samples = (int64_t)sample_ids.size();
+        m.variant_ids = vids; m.chromosomes = chroms; m.positions = pos; m.k = kc; m.n_samples = n_fit;
         for (int64_t r : rows) {
             m.allele1.push_back(fs.allele1[(size_t)r]); m.allele2.push_back(fs.allele2[(size_t)r]);
             m.mean.push_back(st.mu[(size_t)r]); m.sd.push_back(st.sigma[(size_t)r]);
@@ -425,6 +489,13 @@ int main(int argc, char** argv) {
     const Args a = parse(argc, argv);
     try {
         if (a.make_grm && !a.eigensnp) { std::fprintf(stderr, "error: --gpca-make-grm needs the --eigensnp workflow\n"); return 2; }
+        if ((a.make_king || a.have_king_cutoff) && !a.eigensnp) { std::fprintf(stderr, "error: --gpca-make-king and --gpca-king-cutoff need the --eigensnp workflow\n"); return 2; }
+        if (a.have_king_filter && !a.make_king) { std::fprintf(stderr, "error: --gpca-king-table-filter needs --gpca-make-king\n"); return 2; }
+        if (a.have_king_cutoff && !(a.king_cutoff > 0.0 && a.king_cutoff < 0.5)) { std::fprintf(stderr, "error: --gpca-king-cutoff must lie in (0, 0.5)\n"); return 2; }
+        if (a.have_king_cutoff && a.local_stage) {
+            std::fprintf(stderr, "error: --gpca-king-cutoff cannot be combined with --gpca-eigensnp-local-stage (that stage owns the sample mask)\n");
+            return 2;
+        }
         if (!a.project_model.empty()) return run_project_workflow(a);
         if (a.save_model && !a.eigensnp) { std::fprintf(stderr, "error: --gpca-save-model needs the --eigensnp workflow\n"); return 2; }
         return a.eigensnp ? run_eigensnp_workflow(a) : run_vcf_workflow(a);

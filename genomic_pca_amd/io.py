@@ -433,3 +433,92 @@ def write_grm(prefix: str, family_ids: Sequence[str], sample_ids: Sequence[str],
         for fid, iid in zip(family_ids, sample_ids):
             f.write(f"{fid}\t{iid}\n")
     return paths
+
+
+# ------------------------------------------------------------------------------------------------ KING-robust kinship
+KIN0_HEADER = "#FID1\tIID1\tFID2\tIID2\tNSNP\tHETHET\tIBS0\tKINSHIP\n"
+
+
+def king_bands(n: int, max_pairs: int = 1 << 26):
+    """Consecutive row bands [row0, row1) of an n-sample STRICTLY lower triangle (row j holds j pairs), each of at most max_pairs
+    pairs (at least one row): the bands gpca_king is asked for, one at a time."""
+    r0 = 0
+    while r0 < n:
+        r1 = r0 + 1
+        while r1 < n and (r1 + 1) * r1 // 2 - r0 * (r0 - 1) // 2 <= max_pairs:
+            r1 += 1
+        yield r0, r1
+        r0 = r1
+
+
+def band_pairs(row0: int, row1: int) -> Tuple[np.ndarray, np.ndarray]:
+    """(j, k) sample indices of the pairs of a band, in gpca_king's order: j = row0 .. row1 - 1, k = 0 .. j - 1 (k < j)."""
+    js = np.arange(row0, row1, dtype=np.int64)
+    j = np.repeat(js, js)
+    starts = np.repeat(np.cumsum(js) - js, js)
+    k = np.arange(j.size, dtype=np.int64) - starts
+    return j, k
+
+
+def _fmt_kin(v: float) -> str:
+    return "nan" if v != v else f"{v:.6f}"
+
+
+def write_kin0(prefix: str, family_ids: Sequence[str], sample_ids: Sequence[str], bands, min_kinship: Optional[float] = None) -> str:
+    """P.kin0: one tab-separated line per pair, `FID1 IID1 FID2 IID2 NSNP HETHET IBS0 KINSHIP`, ID1 the earlier sample in .fam order,
+    the kinship as %.6f (or nan).  bands: ((row0, row1), kinship, counts) in row order (gpca_king's output, counts [pairs][3]), written
+    as they come: the whole matrix is never held.  min_kinship: only pairs with kinship >= it (NaN never passes)."""
+    n = len(sample_ids)
+    if len(family_ids) != n:
+        raise ValueError("write_kin0: one family ID per sample")
+    path = f"{prefix}.kin0"
+    nxt = 0
+    with open(path, "w") as f:
+        f.write(KIN0_HEADER)
+        for (r0, r1), kin, cnt in bands:
+            if r0 != nxt:
+                raise ValueError(f"write_kin0: band [{r0}, {r1}) does not follow row {nxt}")
+            nxt = r1
+            kin = np.asarray(kin, np.float64).ravel()
+            cnt = np.asarray(cnt).reshape(-1, 3)
+            j, k = band_pairs(r0, r1)
+            if kin.size != j.size or cnt.shape[0] != j.size:
+                raise ValueError(f"write_kin0: band [{r0}, {r1}) needs {j.size} pairs")
+            sel = np.flatnonzero(kin >= min_kinship) if min_kinship is not None else range(j.size)
+            f.writelines(f"{family_ids[k[i]]}\t{sample_ids[k[i]]}\t{family_ids[j[i]]}\t{sample_ids[j[i]]}\t{cnt[i, 0]}\t{cnt[i, 1]}\t"
+                         f"{cnt[i, 2]}\t{_fmt_kin(kin[i])}\n" for i in sel)
+    if nxt != n and n > 0:
+        raise ValueError(f"write_kin0: the bands end at row {nxt}, {n} samples need {n}")
+    return path
+
+
+def king_unrelated(n: int, pairs) -> np.ndarray:
+    """The greedy pruning rule of --gpca-king-cutoff: pairs = (i, j) sample indices of the related pairs (kinship above the cutoff; NaN
+    never counts).  While any pair remains, the sample with the most remaining partners leaves, ties going to the later sample in .fam
+    order.  Returns the in-set as a bool mask [n] (True = kept for the fit)."""
+    adj = [set() for _ in range(n)]
+    for i, j in pairs:
+        i, j = int(i), int(j)
+        if i == j or not (0 <= i < n and 0 <= j < n):
+            raise ValueError(f"king_unrelated: bad pair ({i}, {j}) for {n} samples")
+        adj[i].add(j); adj[j].add(i)
+    deg = np.array([len(a) for a in adj], np.int64)
+    keep = np.ones(n, bool)
+    while n and deg.max() > 0:
+        top = int(deg.max())
+        s = int(np.flatnonzero(deg == top)[-1])                  # the later sample of the tie
+        keep[s] = False
+        for t in adj[s]:
+            adj[t].discard(s); deg[t] -= 1
+        adj[s].clear(); deg[s] = 0
+    return keep
+
+
+def write_king_cutoff_ids(prefix: str, family_ids: Sequence[str], sample_ids: Sequence[str], keep: np.ndarray) -> Tuple[str, str]:
+    """P.king.cutoff.in.id and P.king.cutoff.out.id: `#FID<TAB>IID`, then one line per sample in .fam order."""
+    paths = (f"{prefix}.king.cutoff.in.id", f"{prefix}.king.cutoff.out.id")
+    for path, want in zip(paths, (True, False)):
+        with open(path, "w") as f:
+            f.write("#FID\tIID\n")
+            f.writelines(f"{family_ids[i]}\t{sample_ids[i]}\n" for i in range(len(sample_ids)) if bool(keep[i]) == want)
+    return paths

@@ -303,6 +303,21 @@ GPCA_API int gpca_project(gpca_handle* h, const float* mu, const float* sigma, c
 enum { GPCA_GRM_STANDARDIZED = 0, GPCA_GRM_CENTRED = 1 };
 GPCA_API int gpca_grm(gpca_handle* h, int32_t scaling, int64_t row0, int64_t row1, double* grm, float* npairs /* may be NULL */);
 
+/* ---- a9: KING-robust kinship of this handle's kept rows (relatedness that needs no allele frequencies: plink2 --make-king).
+ * Per sample and kept row: H = [g == 1], M = [missing], X = g - 1 for g in {0, 2} (0 otherwise).  Over the K kept rows (all ranks):
+ *   HETHET = sum H_a H_b;  NSNP = K - miss_a - miss_b + sum M_a M_b;  het_ab = het_a - sum H_a M_b;  het_ba = het_b - sum M_a H_b
+ *   (het_x, miss_x: the sample's het and missing counts);  homhom = NSNP - het_ab - het_ba + HETHET;  IBS0 = (homhom - sum X_a X_b) / 2
+ *   kinship = 0.5 - (4 IBS0 + het_ab + het_ba - 2 HETHET) / (4 min(het_ab, het_ba)),  NaN when min(het_ab, het_ba) = 0.
+ * Every count is an exact integer; the kinship is computed in f64 from them, so only the division and the last subtraction round.
+ * Writes rows row0 <= j < row1 of the STRICTLY lower triangle packed row-major: pair (j, k < j) at j (j - 1) / 2 - row0 (row0 - 1) / 2 + k,
+ * so a band is bit-identical to the same rows of the full call.  counts (may be NULL): [pairs][3] = NSNP, HETHET, IBS0.  Works on every
+ * handle (int8 or 2-bit, resident or streamed, either precision, sharded); the sample mask is ignored and no fitted result is touched.
+ * Sharded handles: every rank passes the same band; the integer counts, K and the status word are summed in one exchange and the
+ * kinship is computed after it, so a rank-local failure comes back from every rank and two ranks give the one-rank bits.
+ * Errors: GPCA_ERR_STATE (no standardisation, or K = 0), GPCA_ERR_BAD_ARG (row range, or K >= 2^31), GPCA_ERR_INVALID_GENOTYPE (a kept
+ * row holds a value outside {0, 1, 2, missing}), GPCA_ERR_OOM (the band does not fit in device memory: checked before any allocation). */
+GPCA_API int gpca_king(gpca_handle* h, int64_t row0, int64_t row1, double* kinship, int32_t* counts /* [pairs][3]; may be NULL */);
+
 /* ---- f3: the stages of EigenSNPCoreAlgorithm::compute_pca (main.rs:311-327, 359-366) ------------------------------------------
  * The algorithm lives in the un-vendored efficient_pca crate (Cargo.toml:30, branch "main", no pinned revision): what follows is
  * the stage structure of its published description -- per-LD-block local bases learnt on a sample subset, condensed features of

@@ -163,6 +163,17 @@ public:
         if (npairs) npairs->resize(e);
         return g;
     }
+    // rows [row0, row1) of the strictly lower triangle of the KING-robust kinship of the kept rows, packed row-major (gpca_king); counts
+    // (may be null) receives NSNP, HETHET, IBS0 per pair
+    std::vector<double> king(int64_t row0, int64_t row1, std::vector<int32_t>* counts = nullptr) const {
+        const size_t e = row1 > row0 ? (size_t)(row1 * (row1 - 1) / 2 - row0 * (row0 - 1) / 2) : 0;
+        std::vector<double> k(std::max<size_t>(e, 1));
+        if (counts) counts->assign(3 * std::max<size_t>(e, 1), 0);
+        check(gpca_king(h_, row0, row1, k.data(), counts ? counts->data() : nullptr));
+        k.resize(e);
+        if (counts) counts->resize(3 * e);
+        return k;
+    }
 
 private:
     gpca_handle* h_ = nullptr;
@@ -217,6 +228,9 @@ struct EigenSNPCoreOutput {
     std::vector<float> final_snp_principal_component_loadings;     // [D][K]  main.rs:407
     int64_t num_qc_samples_used = 0, num_pca_snps_used = 0;
     int num_principal_components_computed = 0;
+    // compute_pca(..., project_all = true): every sample projected onto the fit (gpca_transform, [N][K]), taken while the fit is valid --
+    // before the keep mask of the blocks' union is restored (which drops the fit)
+    std::vector<double> projected_sample_scores;
 };
 
 /* EigenSNPCoreAlgorithm::new(cfg).compute_pca(&accessor, &blocks) (main.rs:359-365): top-K PCA of the standardised matrix
@@ -258,7 +272,7 @@ public:
     }
 
     EigenSNPCoreOutput compute_pca(const MicroarrayGenotypeAccessor& accessor, const std::vector<LdBlockSpecification>& ld_blocks,
-                                   bool local_stage = false) const {
+                                   bool local_stage = false, bool project_all = false) const {
         Engine& eng = accessor.engine();
         const int64_t n_pca = accessor.num_pca_snps();
         if (ld_blocks.empty()) throw std::invalid_argument("compute_pca: ld_block_specifications is empty");
@@ -289,6 +303,7 @@ public:
             out.num_qc_samples_used = accessor.num_qc_samples();
             out.num_pca_snps_used = (int64_t)ids.size();
             out.num_principal_components_computed = eng.components();   // (the local stage may leave fewer: min(K, condensed features))
+            if (project_all) out.projected_sample_scores = eng.transform();
         } catch (...) {
             if (restrict_rows) eng.set_standardization(saved.mu, saved.sigma, saved.keep);
             throw;
