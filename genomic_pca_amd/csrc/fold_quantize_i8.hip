@@ -133,8 +133,7 @@ void launch_absmax_fold(hipStream_t st, const double* apart, int64_t P, double* 
 // Quantisation of the skinny operand: column abs-max -> scale; X[rows][32] -> digit planes
 // blocked [block = row/32][d][lane = 32*((row%32)/16) + col][j = row%16] (16 B per lane per plane).
 // ------------------------------------------------------------------------------------------------
-constexpr int kAbsmaxRowsPerBlock = 1024;
-int64_t absmax_num_parts(int64_t rows) { return (rows + kAbsmaxRowsPerBlock - 1) / kAbsmaxRowsPerBlock; }
+// (kAbsmaxRowsPerBlock rows per workgroup of the abs-max pass: plan_math.h)
 
 template <typename T>
 __global__ __launch_bounds__(256) void k_col_absmax(const T* __restrict__ X, int64_t rows, double* __restrict__ part, int64_t ldx) {
@@ -293,7 +292,6 @@ __global__ __launch_bounds__(256) void k_post_k1(const float* __restrict__ cpart
     scale[cc] = a > 0.0 ? a / DS : 0.0;
     inv[cc] = a > 0.0 ? DS / a : 0.0;
 }
-int post_k1_slices(int64_t units) { return sum_slices(units, 32); }
 void launch_post_k1(hipStream_t st, const float* cpart, int64_t units, double* cscratch, const double* apart, int64_t P, double* scale, double* inv, int nd) {
     const int S = post_k1_slices(units);
     hipLaunchKernelGGL(k_post_k1, dim3((unsigned)(S + 1)), dim3(256), 0, st, cpart, units, cscratch, S, apart, P, scale, inv, digit_scale(nd));

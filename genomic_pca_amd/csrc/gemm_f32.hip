@@ -49,15 +49,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p) {
 // in chunks of 32: lane (c, h) loads the 16 bytes [s0+16h, s0+16h+16) of row c of each tile; byte u is the A
 // operand of k-step u; the lane's 16 Q values of the chunk (one 64-byte run of Qb) are the B operands.
 // ------------------------------------------------------------------------------------------------
-GqPlan gq_plan(int64_t Mpad, int waves_target) {
-    GqPlan p;
-    p.units = Mpad / 32;
-    int64_t w = waves_target < 4 ? 4 : waves_target;
-    if (w > p.units) w = p.units;
-    w = (w + 3) / 4 * 4;
-    p.waves = w;
-    return p;
-}
+// (the plan: gq_plan, plan_math.h)
 
 // One 128-sample super-chunk of a group's R row tiles.  int8 rows: the four 32-byte pieces of a row's 128-byte line are
 // requested back to back by the same lanes (one L1 miss + three hits); requested one piece per 32-sample chunk -- 8 192
@@ -238,23 +230,7 @@ void launch_gq_f32(hipStream_t st, const void* G, int packed, int64_t ldr, const
 // contiguous range of SNP rows (groups of 16 = 8 k-steps; the lane's 8 T' values of a group are one 32-byte
 // run of Tb); partial Y^T tiles go to Ypart and are summed in f64 by k_reduce_y (deterministic, no atomics).
 // ------------------------------------------------------------------------------------------------
-GttPlan gtt_plan(int64_t Mpad, int64_t Npad, int L, int target_waves) {
-    GttPlan p;
-    p.nblocks_n = Npad / kSamplePad;
-    int64_t W = target_waves / p.nblocks_n;
-    if (W < 1) W = 1;
-    const int64_t maxW = Mpad / 32;
-    if (W > maxW) W = maxW;
-    int64_t rpw = (Mpad + W - 1) / W;
-    rpw = (rpw + 31) / 32 * 32;          // even number of 16-row groups per wave (Mpad is a multiple of 128)
-    W = (Mpad + rpw - 1) / rpw;
-    p.W = (int)W;
-    p.rows_per_wave = rpw;
-    const int64_t ngroups = (p.nblocks_n + 3) / 4;
-    p.grid = ngroups * W;
-    (void)L;
-    return p;
-}
+// (the plan: gtt_plan, plan_math.h)
 
 template <int LT>
 struct GttBuf { i32x2 g[8]; i32x4 t0[LT], t1[LT]; };

@@ -127,60 +127,8 @@ int launch_gq_n(hipStream_t st, const int8_t* G, int64_t ldg, const GqPlan& plan
 // ------------------------------------------------------------------------------------------------
 // K2
 // ------------------------------------------------------------------------------------------------
-Gtt8Plan gtt8_plan(int64_t Mpad, int64_t Npad, int target_waves) {
-    Gtt8Plan p{};
-    p.nblocks_n = Npad / 128;
-    int64_t W = target_waves / p.nblocks_n;
-    if (W < 1) W = 1;
-    // a slice's digit-plane sums live in i32 accumulators: |g| <= 2 times |digit| <= 128 per row keeps 2^22 rows a factor 2 inside
-    // 2^31 (only a resident matrix of > 4M rows AND > 260k samples would get there: more than one GPU holds)
-    const int64_t minW = (Mpad + ((int64_t)1 << 22) - 1) >> 22;
-    if (W < minW) W = minW;
-    const int64_t maxW = Mpad / 128;
-    if (W > maxW) W = maxW;
-    int64_t rpw = (Mpad + W - 1) / W;
-    rpw = (rpw + 127) / 128 * 128;       // k-blocks per wave: multiple of 4 (Mpad is a multiple of 128)
-    W = (Mpad + rpw - 1) / rpw;
-    p.W = (int)W;
-    p.rows_per_wave = rpw;
-    p.grid = ((p.nblocks_n + 3) / 4) * W;
-    return p;
-}
+// (the plans gtt8_plan, gtt8_plan_batched and gtt8_plan_narrow: plan_math.h)
 
-// several consecutive (row chunk, n-group) tasks per workgroup (kernels.h): W row chunks such that one batch of `grid0` workgroups
-// covers the tasks evenly.  Cost model per candidate W, relative to the bytes of one sweep: batch fill (tasks rounded up to whole
-// workgroup loads), ~3 stages of prologue / drain / tile store per task, the fold's read of W partial tiles, and 2 % when a row chunk's
-// T' planes (16 KiB per stage) outgrow the share of an XCD's L2 they can expect to keep.
-Gtt8Plan gtt8_plan_batched(int64_t Mpad, int64_t Npad, int target_waves) {
-    Gtt8Plan p{};
-    p.nblocks_n = Npad / 128;
-    p.ngroups = (p.nblocks_n + 3) / 4;
-    p.S = Mpad / 128;
-    int64_t grid0 = target_waves / 8;                // the default target (2 048) = 256 workgroups = one per CU of an MI355X
-    if (grid0 < 1) grid0 = 1;
-    // a task's digit-plane sums live in i32 accumulators: at most 2^22 rows (32 768 stages) per task
-    const int64_t wmin = std::max<int64_t>(1, (p.S + 32767) / 32768), wmax = std::min<int64_t>(p.S, 1024);
-    double best = 1e300;
-    int64_t bestW = wmin;
-    for (int64_t W = wmin; W <= std::max(wmin, wmax); ++W) {
-        const int64_t T = W * p.ngroups, k = (T + grid0 - 1) / grid0;
-        double f = (double)(k * grid0) / (double)T;                                      // batch fill: k tasks per workgroup against T / grid0
-        f *= 1.0 + 3.0 * (double)W / (double)p.S;                                        // per-task prologue / drain / store
-        f += (double)W * 256.0 / (double)Mpad;                                           // the fold reads W x Npad x 256 B against Mpad x Npad
-        if ((double)p.S / (double)W * 16384.0 > 3.0 * 1048576.0) f += 0.02;               // T' planes of a row chunk vs L2
-        if (f < best - 1e-12) { best = f; bestW = W; }
-    }
-    p.C = (p.S + bestW - 1) / bestW;                  // stages per row chunk (the last chunk may be shorter)
-    p.W = (int)((p.S + p.C - 1) / p.C);
-    const int64_t T = (int64_t)p.W * p.ngroups;
-    p.tasks_per_wg = (int)((T + grid0 - 1) / grid0);
-    p.grid = (T + p.tasks_per_wg - 1) / p.tasks_per_wg;
-    p.strided = 1;
-    p.rows_per_wave = p.C * 128;                      // rows of a full task
-    return p;
-}
-
-// (the slice-form plan of the narrow K2, gtt8_plan_narrow, lives with that kernel in gemm_i8_simple.hip)
 
 // ================================================================================================
 // 2-bit resident genotypes (GPCA_STORE_2BIT): the same two products with the dosage codes decoded in the prologue.

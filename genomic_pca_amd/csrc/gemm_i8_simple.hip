@@ -241,21 +241,6 @@ __global__ __launch_bounds__(256, 1) void k_gtt_i8(const int8_t* __restrict__ G,
 }
 
 // K2 for at most 256 samples (int8 rows): plan = gtt8_plan_narrow; every wave owns a row chunk of its own
-Gtt8Plan gtt8_plan_narrow(int64_t Mpad, int64_t N, int target_waves) {
-    Gtt8Plan p{};
-    p.nblocks_n = (N + 127) / 128;                      // 128-sample blocks that hold samples: 1 or 2
-    int64_t W = target_waves / p.nblocks_n;
-    if (W < 1) W = 1;
-    const int64_t maxW = Mpad / 128;
-    if (W > maxW) W = maxW;
-    int64_t rpw = (Mpad + W - 1) / W;
-    rpw = (rpw + 127) / 128 * 128;
-    W = (Mpad + rpw - 1) / rpw;
-    p.W = (int)W;
-    p.rows_per_wave = rpw;
-    p.grid = (W * p.nblocks_n + 3) / 4;
-    return p;
-}
 void launch_gtt_n(hipStream_t st, const int8_t* G, int64_t ldg, int64_t Mpad, int64_t Npad, const int8_t* Td,
                   double* Ypart, const Gtt8Plan& plan) {
     hipLaunchKernelGGL((k_gtt_i8<2, true>), dim3((unsigned)plan.grid), dim3(256), 0, st, G, ldg, Mpad, Npad, Td, Ypart, plan.nblocks_n, plan.rows_per_wave);

@@ -243,7 +243,6 @@ struct gpca_handle {
     std::vector<gpca_kernel_timing> agg;
 };
 constexpr size_t kMaxTimingRecs = 32768;
-constexpr size_t kPostK1Scratch = 256 * 32;     // doubles of d_scratch64 per 32-column block of the sketch (<= 256 slices x 32 columns; kSumScratchElems holds 32 of them)
 // every entry point: take the handle's lock and make its device the calling thread's current one (a host thread that drives
 // several handles on different GPUs, or that last touched another device, would otherwise launch on the wrong one)
 #define LOCK(h) std::lock_guard<std::recursive_mutex> lock_guard_(h->mu); (void)hipSetDevice(h->device); drain_pulls(h)

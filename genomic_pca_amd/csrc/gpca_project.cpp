@@ -100,9 +100,9 @@ extern "C" int gpca_project(gpca_handle* h, const float* mu, const float* sigma,
         HIPCHK(dalloc(ws.mu, M)); HIPCHK(dalloc(ws.sigma, M)); HIPCHK(dalloc(ws.keep, M));
         HIPCHK(dalloc(ws.r, Mpad)); HIPCHK(dalloc(ws.b, Mpad)); HIPCHK(dalloc(ws.rmask, Mpad / 32));
         HIPCHK(dalloc(ws.Wa, (size_t)Mpad * Lp)); HIPCHK(dalloc(ws.Wb, (size_t)Mpad * Lp));
-        HIPCHK(dalloc(ws.cpart, (size_t)omega_num_parts(Mpad) * Lp)); HIPCHK(dalloc(ws.cpart_b, (size_t)omega_num_parts(Mpad) * Lp));
+        HIPCHK(dalloc(ws.cpart, (size_t)project_cpart_capacity(Mpad, Lp))); HIPCHK(dalloc(ws.cpart_b, (size_t)project_cpart_capacity(Mpad, Lp)));
         HIPCHK(dalloc(ws.Ta, td_half * halves)); HIPCHK(dalloc(ws.Tb, td_half * halves));
-        HIPCHK(dalloc(ws.c, Lp)); HIPCHK(dalloc(ws.scratch, kSumScratchElems)); HIPCHK(dalloc(ws.part, std::max<size_t>((size_t)absmax_num_parts(Mpad) * 32, 2 * (size_t)Lp)));
+        HIPCHK(dalloc(ws.c, Lp)); HIPCHK(dalloc(ws.scratch, (size_t)project_scratch_capacity(Lp))); HIPCHK(dalloc(ws.part, (size_t)project_part_capacity(Mpad, Lp)));
         HIPCHK(dalloc(ws.tsa, Lp)); HIPCHK(dalloc(ws.tia, Lp)); HIPCHK(dalloc(ws.tsb, Lp)); HIPCHK(dalloc(ws.tib, Lp));
         HIPCHK(dalloc(ws.Ypa, (size_t)max_W * Npad * 32)); HIPCHK(dalloc(ws.Ypb, (size_t)max_W * Npad * 32));
         HIPCHK(dalloc(ws.Yia, (size_t)N * Lp)); HIPCHK(dalloc(ws.Yib, (size_t)N * Lp));

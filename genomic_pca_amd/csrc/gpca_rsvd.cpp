@@ -442,10 +442,10 @@ static int ensure_workspace(gpca_handle* h) {
     if (h->Mpad > M) HIPCHK(hipMemsetAsync(h->dT + (size_t)M * L, 0, (size_t)(h->Mpad - M) * L * 4, h->st));
     if (h->precision == GPCA_PREC_F32_MFMA) CHK(ensure(h, h->dYpart, h->cap_Ypart, (size_t)h->plan.W * (size_t)Npad * L));
     // c partials: per wave x L (f32 path, Omega: 64-row groups), or per 32-row unit x 32 per column half (exact path)
-    const int64_t cparts = std::max({h->gqplan.waves * (int64_t)L, omega_num_parts(h->Mpad) * (int64_t)L, h->Mpad * (int64_t)(L / 32)});
+    const int64_t cparts = cpart_capacity(h->gqplan.waves, h->Mpad, L);
     CHK(ensure(h, h->d_cpart, h->cap_cpart, (size_t)cparts));
     CHK(ensure(h, h->dY, h->cap_Y, (size_t)N * L + 16));   // (+ 16 status slots: gpca_transform's agreement rides its exchange)
-    const int64_t p64 = std::max({gram_num_parts(N) * (int64_t)L * L, gram_num_parts(M) * (int64_t)L * L, colsum_num_parts(Npad) * (int64_t)L, absmax_num_parts(h->Mpad) * (int64_t)32, 2 * tail_num_parts(Npad) * (int64_t)L});
+    const int64_t p64 = part64_capacity(M, h->Mpad, N, Npad, L);
     CHK(ensure(h, h->d_part64, h->cap_part64, (size_t)p64));
     if (!h->d_c) {
         constexpr size_t LL = (size_t)kMaxSketch * kMaxSketch;
@@ -453,9 +453,9 @@ static int ensure_workspace(gpca_handle* h) {
         HIPCHK(hipMalloc((void**)&h->d_s32, kMaxSketch * 4)); HIPCHK(hipMalloc((void**)&h->dW, (LL + 16) * 8));   // (+ the 16 status slots that ride the Gram's exchange)
         HIPCHK(hipMalloc((void**)&h->dZ, 2 * LL * 8));
         HIPCHK(hipHostMalloc((void**)&h->h_pin, (3 * LL + 16) * 8, hipHostMallocDefault)); HIPCHK(hipMalloc((void**)&h->d_sign, kMaxSketch * 4));
-        HIPCHK(hipMalloc((void**)&h->d_scratch64, kSumScratchElems * 8));
+        HIPCHK(hipMalloc((void**)&h->d_scratch64, (size_t)sum_scratch_capacity(kMaxSketch) * 8));      // (allocated once: sized for the widest sketch)
         HIPCHK(hipMalloc((void**)&h->d_eigres, kEigResCount * 8));
-        HIPCHK(hipMalloc((void**)&h->d_cand_val, (size_t)64 * kMaxSketch * 8)); HIPCHK(hipMalloc((void**)&h->d_cand_idx, (size_t)64 * kMaxSketch * 8));      // (scores_num_parts <= 48)
+        HIPCHK(hipMalloc((void**)&h->d_cand_val, (size_t)scores_cand_capacity() * 8)); HIPCHK(hipMalloc((void**)&h->d_cand_idx, (size_t)scores_cand_capacity() * 8));
         HIPCHK(hipMalloc((void**)&h->d_cholflag, 4));
     }
     if (h->precision == GPCA_PREC_I8_EXACT) {

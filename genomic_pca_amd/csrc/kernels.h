@@ -3,12 +3,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "plan_math.h"   // part counts, GEMM plans, workspace capacities: plain host arithmetic, audited by tests/cpp/plan_audit.cpp
 
 namespace gpca {
-
-// Row pitch of the int8 genotype matrix and row count of Q/Y buffers: multiple of this many samples.
-constexpr int64_t kSamplePad = 256;   // = samples covered by one wave tile of the G^T T kernel
-constexpr int kGQRowsPerWave = 128;   // SNP rows per wave in the G Q kernel (R = 4 tiles of 32)
 
 struct QcParams { double min_call_rate, min_maf, max_hwe_p; };
 
@@ -26,7 +23,6 @@ int init_device_kernels_common();
 int init_device_kernels_eig();
 
 // ---- the small dense step on the device (small_eig.hip) ----------------------------------------------------------------------
-constexpr int kMaxSketchCols = 128;                  // = kMaxSketch (gpca_internal.h)
 // layout of the result block `res` of launch_small_eigh (doubles): what the host reads back ONCE, at the end of the call
 constexpr int kEigResSv = 0;                         // [128] singular values sqrt(max(w, 0)), descending
 constexpr int kEigResEig = kMaxSketchCols;           // [128] w_c / denom for c < k
@@ -75,7 +71,7 @@ void launch_standardize_block(hipStream_t st, const int8_t* G, int64_t ld, const
                               int64_t nj, float* out, unsigned long long* err_idx);
 
 // sketch operand: Tb (blocked, all Mpad rows) = r_i * Omega[i][j] (j < l, else 0); cpart[wave][j] = sum_i b_i Omega[i][j]
-int64_t omega_num_parts(int64_t Mpad);
+//   (omega_num_parts(Mpad) waves: plan_math.h)
 // row_ids (may be NULL): global index of every row (a matrix of gathered rows draws the normals its rows would draw in place)
 void launch_omega(hipStream_t st, int64_t M, int64_t Mpad, int l, int L, int64_t snp_offset, uint64_t seed,
                   const float* r, const float* b, float* Tb, float* cpart, double* apart, int blocked = 1, const int64_t* row_ids = nullptr);
@@ -91,14 +87,12 @@ void launch_max_f32(hipStream_t st, const float* r, int64_t n, float* out);
 
 // K1: T = r o (G Q) + b s^T.  Tb != NULL: write r o T blocked into Tb and cpart[wave][j] = sum_i b_i T_ij
 // (power iteration); Tb == NULL: write T row-major into Tout (projection B = A Q).  Qb is the blocked basis.
-struct GqPlan { int64_t units; int64_t waves; };   // 32-row units of the padded matrix; resident waves (multiple of 4)
-GqPlan gq_plan(int64_t Mpad, int waves_target);
+// (GqPlan / gq_plan: plan_math.h)
 // G: int8 rows (packed = 0) or 2-bit dosage codes (packed = 1) of row pitch ldr bytes; Npad = padded sample count (multiple of 256)
 void launch_gq_f32(hipStream_t st, const void* G, int packed, int64_t ldr, const GqPlan& plan, int64_t Npad, const float* Qb,
                    int L, const float* r, const float* b, const float* s, float* Tout, float* Tb, float* cpart);
 // K2: Ypart[w][n][j] = 2^-9 * sum over the wave's SNP rows of G[i][n] * T'[i][j]   (T' blocked in Tb)
-struct GttPlan { int64_t nblocks_n; int W; int64_t rows_per_wave; int64_t grid; };
-GttPlan gtt_plan(int64_t Mpad, int64_t Npad, int L, int target_waves);
+// (GttPlan / gtt_plan: plan_math.h)
 void launch_gtt_f32(hipStream_t st, const void* G, int packed, int64_t ldr, int64_t Mpad, int64_t Npad, const float* Tb,
                     int L, float* Ypart, const GttPlan& plan);
 // Y[n][j] = c[j] + 2^9 * sum_w Ypart[w][n][j]   (f64 sum), n < N
@@ -106,12 +100,11 @@ void launch_reduce_y(hipStream_t st, const float* Ypart, int W, int64_t Npad, in
                      double* Y);
 
 // generic tall-skinny helpers
-// scratch: >= S * E doubles, S <= 64 slices (<= 256 when E <= 64): kSumScratchElems covers E <= 4096
-constexpr int64_t kSumScratchElems = 64 * 4096;
+// scratch: >= S * E doubles, S = sum_slices(P, E) <= 64 slices (<= 256 when E <= 64): sum_scratch_need(E) holds any part count
 void launch_sum_partials_f32(hipStream_t st, const float* part, int64_t P, int64_t E, double* out, double* scratch);
 void launch_sum_partials_f64(hipStream_t st, const double* part, int64_t P, int64_t E, double* out, double* scratch);
-// slices of the part axis the first stage uses (a function of (P, E) only: the summation tree is the same for every run and partition)
-int sum_slices(int64_t P, int64_t E);
+// slices of the part axis the first stage uses: sum_slices(P, E) (plan_math.h; a function of (P, E) only: the summation tree is the
+// same for every run and partition)
 #ifdef __HIPCC__
 // The body of the two-stage sum (one workgroup of 256 threads = columns 64 bx .. + 63, slice by of S): out[by][e] = sum over the slice's
 // parts in a fixed tree.  Shared by k_sum_partials and by the kernels that carry one of its stages along (k_post_k1, k_quantize).
@@ -139,7 +132,7 @@ __device__ __forceinline__ void sum_partials_body(const T* __restrict__ part, in
 // first stage only: *slices partial sums of [E] doubles at *src, for a consumer that folds the (<= 64, or <= 256 for E <= 64) slices
 // itself (launch_small_eigh, k_chol_inv); P <= 64 parts are their own slices and nothing is launched
 void launch_sum_partials_f64_stage1(hipStream_t st, const double* part, int64_t P, int64_t E, double* scratch, const double** src, int* slices);
-int64_t gram_num_parts(int64_t rows);
+// part [gram_num_parts(rows)][L * L]
 void launch_gram_f64(hipStream_t st, const double* X, int64_t rows, int L, double* part);
 void launch_gram_f32(hipStream_t st, const float* X, int64_t rows, int L, double* part);
 // X[n][:] <- X[n][:] * Z  (Z: [L][L] f64, in place); optionally also the blocked f32 basis Qb (rows_pad rows, pad rows zeroed)
@@ -149,7 +142,7 @@ constexpr double kDigitScale = 0.49 * 268435456.0;
 constexpr double kDigitScale3 = 0.49 * 16777216.0;
 inline double digit_scale(int nd) { return nd == 3 ? kDigitScale3 : kDigitScale; }
 // last right-multiplication of CholeskyQR2 + partials of Q^T 1 and of the column abs-max; k_finish_q reduces them
-int64_t tail_num_parts(int64_t rows_pad);
+// csum_part, amax_part [tail_num_parts(rows_pad)][L]
 void launch_apply_right_tail(hipStream_t st, double* X, int64_t rows, int L, const double* Z, float* Qout, int64_t rows_pad,
                              double* csum_part, double* amax_part);
 void launch_finish_q(hipStream_t st, const double* csum_part, const double* amax_part, int64_t P, int L, double* s64, float* s32,
@@ -170,11 +163,10 @@ void launch_rightmul_gather_f32(hipStream_t st, const float* X, const int64_t* r
 // column, the first row with maximal |score| (value + row: scores_num_parts(rows) candidates); launch_scores_sign folds the candidates
 // (every workgroup for itself: they are few), flips the columns whose winner is negative (in place, plus the f32 copy) and leaves
 // sign[c] = +-1 for the loadings.
-int64_t scores_num_parts(int64_t rows);
 void launch_scores(hipStream_t st, const double* X, int64_t rows, int L, const double* Z, int K, double* out64, double* cand_val, int64_t* cand_idx);
 void launch_scores_sign(hipStream_t st, double* out64, float* out32, int64_t rows, int K, const double* cand_val, const int64_t* cand_idx,
                         int64_t parts, int* sign);
-int64_t colsum_num_parts(int64_t rows);
+// part [colsum_num_parts(rows)][L]
 void launch_colsum_f64(hipStream_t st, const double* X, int64_t rows, int L, double* part);
 // sign[c] = sign of the first element of column c with maximal |x|
 void launch_col_sign(hipStream_t st, const double* X, int64_t rows, int K, int* sign);
@@ -210,15 +202,11 @@ void launch_gq_i8(hipStream_t st, const int8_t* G, int64_t ldg, const GqPlan& pl
 // workgroup ran 500 workgroups on 256 CUs at configs[1] and 392 at configs[3]'s shard -- a second, part-empty batch, 6 % and 14 % of
 // the launch.  gtt8_plan_batched picks W (stages per task against per-task prologues, the fold's traffic and the L2 footprint of a
 // row chunk's T' planes, which the workgroups of an XCD share).
-struct Gtt8Plan { int64_t nblocks_n; int W; int64_t rows_per_wave; int64_t grid; int tasks_per_wg; int64_t S; int64_t ngroups; int strided; int64_t C; };
-Gtt8Plan gtt8_plan(int64_t Mpad, int64_t Npad, int target_waves);
-Gtt8Plan gtt8_plan_batched(int64_t Mpad, int64_t Npad, int target_waves);
+// (Gtt8Plan and its three planners gtt8_plan, gtt8_plan_batched, gtt8_plan_narrow: plan_math.h)
 void launch_gtt_i8(hipStream_t st, const int8_t* G, int64_t ldg, int64_t Mpad, int64_t Npad, const int8_t* Td,
                    double* Ypart, const Gtt8Plan& plan, const KernelOpts& ko = KernelOpts());
 // narrow matrices (N <= 256 samples, int8 rows): every wave owns its own row range, Q's digit planes stay in registers (K1) /
 // the four waves of a workgroup take four row chunks instead of four sample blocks (K2).  launch_gq_n returns a hipError_t value.
-constexpr int64_t kNarrowSamples = 256;
-Gtt8Plan gtt8_plan_narrow(int64_t Mpad, int64_t N, int target_waves);
 void launch_gtt_n(hipStream_t st, const int8_t* G, int64_t ldg, int64_t Mpad, int64_t Npad, const int8_t* Td, double* Ypart,
                   const Gtt8Plan& plan);
 int launch_gq_n(hipStream_t st, const int8_t* G, int64_t ldg, const GqPlan& plan, int64_t N, const int8_t* Qd,
@@ -231,7 +219,6 @@ void launch_finish_y_i8(hipStream_t st, const double* Yint, int64_t N, const dou
 void launch_absmax_fold(hipStream_t st, const double* apart, int64_t P, double* run);
 void launch_accum_y_scaled(hipStream_t st, const double* Ypart, int W, int64_t Npad, int64_t N, const double* tscale, double* Yacc, int first);
 void launch_finish_y_sum(hipStream_t st, const double* Yacc, int64_t N, const double* c, double* Y, int64_t ldy = 32);
-int64_t absmax_num_parts(int64_t rows);
 // X [rows][32] row-major -> digit planes Xd [rows_pad/32][kDigits][64][16 B]; scale[j] = colmax_j / S, inv = 1/scale
 // layout 0: 32 consecutive rows per block; layout 1: the MFMA-step order of the packed (2-bit) G Q kernel
 void launch_quantize_f32(hipStream_t st, const float* X, int64_t rows, int64_t rows_pad, double* part, double* scale,
@@ -254,7 +241,6 @@ void launch_gq_2bit(hipStream_t st, const uint8_t* G2, int64_t ld2, const GqPlan
                     double* apart, int scale_out, int nd = 4, int64_t ldt = 32);
 void launch_quantize_f64_prescaled(hipStream_t st, const double* X, int64_t rows, int64_t rows_pad, const double* inv, int8_t* Xd, int layout, int nd = 4, int64_t ldx = 32);
 // the same with launch_finish_q folded in for these 32 columns (every workgroup folds the P abs-max partials itself: for P <= kFinishQFoldMax)
-constexpr int64_t kFinishQFoldMax = 512;
 void launch_quantize_f64_finishq(hipStream_t st, const double* X, int64_t rows, int64_t rows_pad, int8_t* Xd, int layout, int nd, int64_t ldx,
                                  const double* csum_part, const double* amax_part, int64_t P, int ldp, double* s64, float* s32, double* scale, double* inv);
 // quantise X whose column abs-max partials [P][32] were already produced by the kernel that wrote it (K1 epilogue)
@@ -265,7 +251,6 @@ void launch_quantize_f32_premax(hipStream_t st, const float* X, int64_t rows, in
 //                             cscratch) BESIDE the fold of the waves' column abs-max apart [P][32] into the digit scale (one more workgroup);
 //   launch_quantize_f32_cfold: the digit planes of T' as launch_quantize_f32_premax's second half, and -- its first workgroup -- the
 //                             second stage of c (cscratch -> c[32]).  Same summation tree as launch_sum_partials_f32: the same bits.
-int post_k1_slices(int64_t units);
 void launch_post_k1(hipStream_t st, const float* cpart, int64_t units, double* cscratch, const double* apart, int64_t P, double* scale, double* inv, int nd);
 void launch_quantize_f32_cfold(hipStream_t st, const float* X, int64_t rows, int64_t rows_pad, const double* inv, int8_t* Xd, int layout, int nd,
                                int64_t ldx, const double* cscratch, int cslices, double* c);
@@ -289,8 +274,7 @@ void launch_gtt_2bit(hipStream_t st, const uint8_t* G2, int64_t ld2, int64_t Mpa
 // the rows whose bit is set in rmask [rows_pad / 32] (atomic, zeroed by the caller; cnt = NULL: not counted); *bad |= 1 when such a row holds a value outside
 // {0, 1, 2, missing} (int8 rows).  lazy_b: the Tb planes are loaded only for blocks that hold a missing code (else with every
 // block, in the register ring).  G: int8 rows (packed = 0) or 2-bit codes (packed = 1) of pitch ldr bytes.
-struct PrjPlan { int64_t ngroups; int W; int64_t rows_per_wave; int64_t grid; };
-PrjPlan prj_plan(int64_t Mpad, int64_t Npad, int target_waves);
+// (PrjPlan / prj_plan: plan_math.h)
 void launch_project(hipStream_t st, const void* G, int packed, int64_t ldr, int64_t Mpad, int64_t Npad, const int8_t* Ta, const int8_t* Tb,
                     const uint32_t* rmask, double* Ypa, double* Ypb, unsigned* cnt, unsigned* bad, const PrjPlan& plan, int nd, int lazy_b);
 // Y[n][j] = fma(-tscale_b[j], Yint_b[n][j], Y[n][j])  (one 32-column half, pitch ldy); 0 for a sample with cnt[n] == n_model

@@ -363,7 +363,6 @@ void launch_standardize_block(hipStream_t st, const int8_t* G, int64_t ld, const
 // Box-Muller pairs in f64 (bit-compatible recipe with oracle/gpca_oracle.c:omega4).
 // One wave = 64 rows; writes Tp = r o Omega and the wave's partial of c = b^T Omega.
 // ------------------------------------------------------------------------------------------------
-int64_t omega_num_parts(int64_t Mpad) { return (Mpad + 63) / 64; }
 // sketches wider than 64 columns: the plain any-L kernels of wide_sketch.hip
 void launch_gram_any_f64(hipStream_t st, const double* X, int64_t rows, int64_t rpb, int64_t parts, int L, double* part);
 void launch_gram_any_f32(hipStream_t st, const float* X, int64_t rows, int64_t rpb, int64_t parts, int L, double* part);
@@ -597,14 +596,7 @@ __global__ __launch_bounds__(256) void k_sum_partials(const T* __restrict__ part
     __shared__ double red[4][64];
     sum_partials_body<T>(part, P, E, out, S, blockIdx.x, blockIdx.y, red);
 }
-// slices of the part axis in stage 1.  Few elements per part (E <= 64: the c = b^T T partials, one per 32-row unit, 31 250 of them at
-// a million SNPs) put a single column of workgroups on the grid: up to 256 slices there instead of 64 (14 us -> ~5 us for 4 MB).
-// S depends on (P, E) only, so the summation tree -- and with it every bit of the result -- is the same for every run and partition.
-int sum_slices(int64_t P, int64_t E) {
-    const int64_t cap = E <= 64 ? 256 : 64;
-    int64_t s = (P + 63) / 64;
-    return (int)(s < 1 ? 1 : (s > cap ? cap : s));
-}
+// (slices of the part axis in stage 1: sum_slices, plan_math.h)
 template <typename T>
 static void launch_sum_partials_t(hipStream_t st, const T* part, int64_t P, int64_t E, double* out, double* scratch) {
     const int S = sum_slices(P, E);
@@ -631,22 +623,7 @@ void launch_sum_partials_f64_stage1(hipStream_t st, const double* part, int64_t 
 }
 
 // Gram: part[blk][a][c] = sum over the block's rows of X[n][a] X[n][c]  (f64 accumulate, k_gram_mfma below).
-// Rows per block adapt to the problem so that ~1024 blocks are in flight (N = 10^4 used to get 20 blocks).
-static int64_t gram_rows_per_block(int64_t rows) {
-    // The sample-side Grams of CholeskyQR (N rows, four per call) sit on the critical path between two GEMM passes, and their partial
-    // sums are folded by the ONE workgroup that factors the result (k_chol_inv_fold32): 32 parts up to 8k rows, rising to at most 64, which
-    // one k_sum_partials launch still finishes (the matrix-core Gram of 10 000 x 32 takes 5 us with 63 workgroups, 11 with 16).
-    if (rows <= 262144) {
-        int64_t parts = rows / 256;
-        parts = parts < 32 ? 32 : (parts > 64 ? 64 : parts);
-        const int64_t q = (rows + parts - 1) / parts;
-        return q < 32 ? 32 : (q + 31) / 32 * 32;
-    }
-    int64_t r = (rows + 1023) / 1024;
-    r = (r + 31) / 32 * 32;
-    return r < 32 ? 32 : (r > 2048 ? 2048 : r);
-}
-int64_t gram_num_parts(int64_t rows) { const int64_t rpb = gram_rows_per_block(rows); return (rows + rpb - 1) / rpb; }
+// Rows per block adapt to the problem so that ~1024 blocks are in flight: gram_rows_per_block / gram_num_parts (plan_math.h).
 
 // Gram of a tall factor (f32: B = A Q, M rows; f64: the sample-side sketch, N rows) on the f64 matrix cores: W = X^T X as 16x16x4 MFMAs.  Lane (i = lane & 15,
 // k = lane >> 4) converts X[n + k][16 g + i] once and uses it both as the A element (X^T tile g) and as the B element
@@ -759,8 +736,6 @@ __global__ __launch_bounds__(256) void k_apply_right(double* __restrict__ X, int
 // (s = Q^T 1, the centring term of A Q) and of the column abs-max (digit scale of the exact-integer path).  A workgroup
 // walks kTailRows rows so that Z is staged once per 64 rows and the partial arrays stay small; k_finish_q reduces them
 // in a fixed order.  Replaces k_colsum + 2 x k_sum_partials + k_f64_to_f32 + k_col_absmax + k_finish_scale.
-constexpr int kTailRows = 64;
-int64_t tail_num_parts(int64_t rows_pad) { return (rows_pad + kTailRows - 1) / kTailRows; }
 template <int L>
 __global__ __launch_bounds__(256) void k_apply_right_tail(double* __restrict__ X, int64_t rows, const double* __restrict__ Z,
                                                           float* __restrict__ Qout, int64_t rows_pad,
@@ -1092,8 +1067,7 @@ void launch_rightmul_gather_f32(hipStream_t st, const float* X, const int64_t* r
 // sample count; k_scores_sign folds the candidates in workgroup order (ascending rows within a workgroup's chunks, so "first row"
 // needs the row index, not the fold order), applies the sign in place and writes the f32 copy.  Replaces k_rightmul + k_col_sign
 // (one workgroup per column walking all rows: 17 us) + 2 x k_scale_cols.
-constexpr int kScoreParts = 48;                       // (x 64 columns x 16 B of candidates = 48 KiB of LDS in k_scores_sign)
-int64_t scores_num_parts(int64_t rows) { const int64_t c = (rows + 255) / 256; return c < kScoreParts ? (c < 1 ? 1 : c) : kScoreParts; }
+// (kScoreParts, scores_num_parts: plan_math.h)
 template <int L>
 __global__ __launch_bounds__(256) void k_scores(const double* __restrict__ X, int64_t nrows, const double* __restrict__ Z, int K,
                                                 double* __restrict__ out64, double* __restrict__ cand_val, int64_t* __restrict__ cand_idx) {
@@ -1197,8 +1171,6 @@ void launch_scores_sign(hipStream_t st, double* out64, float* out32, int64_t row
     hipLaunchKernelGGL(k_scores_sign, dim3((unsigned)blocks), dim3(256), lds, st, out64, out32, total, K, cand_val, cand_idx, (int)parts, sign);
 }
 
-constexpr int kColsumRowsPerBlock = 256;
-int64_t colsum_num_parts(int64_t rows) { return (rows + kColsumRowsPerBlock - 1) / kColsumRowsPerBlock; }
 __global__ __launch_bounds__(256) void k_colsum(const double* __restrict__ X, int64_t rows, int L, double* __restrict__ part) {
     __shared__ double red[256];
     const int cc = threadIdx.x % L, rg = threadIdx.x / L, nrg = 256 / L;

@@ -1,0 +1,221 @@
+// Host arithmetic that sizes launches and workspaces: part counts, slice counts, GEMM plans, and the capacity of every buffer they
+// write.  Plain C++ (no HIP type): kernels.h includes it for the engine, tests/cpp/plan_audit.cpp includes it under a host compiler
+// and checks every writer's extent against the capacity of the buffer it writes.  A buffer's size is stated here ONCE, as a function
+// that its allocation site and the audit both call.
+#pragma once
+#include <stdint.h>
+#include <algorithm>
+
+namespace gpca {
+
+// Row pitch of the int8 genotype matrix and row count of Q/Y buffers: multiple of this many samples.
+constexpr int64_t kSamplePad = 256;   // = samples covered by one wave tile of the G^T T kernel
+constexpr int kGQRowsPerWave = 128;   // SNP rows per wave in the G Q kernel (R = 4 tiles of 32)
+constexpr int kMaxSketchCols = 128;   // = kMaxSketch (gpca_internal.h)
+
+// ---- part counts of the tall-skinny helpers (kernels.hip, fold_quantize_i8.hip) --------------------------------------------------
+// sketch operand: cpart[wave][j], one wave per 64 rows
+inline int64_t omega_num_parts(int64_t Mpad) { return (Mpad + 63) / 64; }
+
+// slices of the part axis in stage 1 of the two-stage sum.  Few elements per part (E <= 64: the c = b^T T partials, one per 32-row unit,
+// 31 250 of them at a million SNPs) put a single column of workgroups on the grid: up to 256 slices there instead of 64 (14 us -> ~5 us
+// for 4 MB).  S depends on (P, E) only, so the summation tree -- and with it every bit of the result -- is the same for every run and partition.
+constexpr int kSumSlicesMax = 64, kSumSlicesMaxNarrow = 256;      // what a consumer that folds the slices itself must hold (narrow: E <= 64)
+inline int sum_slices(int64_t P, int64_t E) {
+    const int64_t cap = E <= 64 ? kSumSlicesMaxNarrow : kSumSlicesMax;
+    int64_t s = (P + 63) / 64;
+    return (int)(s < 1 ? 1 : (s > cap ? cap : s));
+}
+// doubles the first stage of a sum of parts of [E] writes at most, whatever the part count
+inline int64_t sum_scratch_need(int64_t E) { return (E <= 64 ? (int64_t)kSumSlicesMaxNarrow : (int64_t)kSumSlicesMax) * E; }
+// doubles of scratch per 32-column block of the sketch that launch_post_k1 / launch_quantize_f32_cfold use (<= 256 slices x 32 columns)
+constexpr int64_t kPostK1Scratch = 256 * 32;
+inline int post_k1_slices(int64_t units) { return sum_slices(units, 32); }
+// Capacity (doubles) of the scratch of a handle whose sums have at most Lmax * Lmax elements per part (the l x l Grams) and whose
+// launch_post_k1 takes one kPostK1Scratch block per 32 columns: every slice count sum_slices can return fits, at any part count.
+inline int64_t sum_scratch_capacity(int Lmax) {
+    const int64_t E = (int64_t)Lmax * Lmax;
+    const int64_t need = std::max(sum_scratch_need(64), sum_scratch_need(E));      // (64 E grows with E above 64; 256 E tops at E = 64)
+    return std::max<int64_t>(need, (int64_t)(Lmax / 32) * kPostK1Scratch);
+}
+
+// Gram: rows per block adapt to the problem so that ~1024 blocks are in flight (N = 10^4 used to get 20 blocks).
+inline int64_t gram_rows_per_block(int64_t rows) {
+    // The sample-side Grams of CholeskyQR (N rows, four per call) sit on the critical path between two GEMM passes, and their partial
+    // sums are folded by the ONE workgroup that factors the result (k_chol_inv_fold32): 32 parts up to 8k rows, rising to at most 64, which
+    // one k_sum_partials launch still finishes (the matrix-core Gram of 10 000 x 32 takes 5 us with 63 workgroups, 11 with 16).
+    if (rows <= 262144) {
+        int64_t parts = rows / 256;
+        parts = parts < 32 ? 32 : (parts > 64 ? 64 : parts);
+        const int64_t q = (rows + parts - 1) / parts;
+        return q < 32 ? 32 : (q + 31) / 32 * 32;
+    }
+    int64_t r = (rows + 1023) / 1024;
+    r = (r + 31) / 32 * 32;
+    return r < 32 ? 32 : (r > 2048 ? 2048 : r);
+}
+inline int64_t gram_num_parts(int64_t rows) { const int64_t rpb = gram_rows_per_block(rows); return (rows + rpb - 1) / rpb; }
+// An upper bound of gram_num_parts over EVERY row count up to `rows` (the part count is not monotone in the rows: 294 912 rows make
+// 1 024 parts, 294 913 make 922): what a buffer must hold when the same handle also folds Grams of fewer rows (the condensed features
+// of gpca_rsvd_condensed, R <= M).
+inline int64_t gram_max_parts(int64_t rows) {
+    if (rows <= 262144) return 64;
+    return std::max<int64_t>(1024, (rows + 2047) / 2048);
+}
+
+constexpr int kTailRows = 64;                       // rows per workgroup of the last right-multiplication of CholeskyQR2
+inline int64_t tail_num_parts(int64_t rows_pad) { return (rows_pad + kTailRows - 1) / kTailRows; }
+constexpr int64_t kFinishQFoldMax = 512;            // most tail partials that k_quantize<double> folds by itself
+
+constexpr int kScoreParts = 48;                     // (x 64 columns x 16 B of candidates = 48 KiB of LDS in k_scores_sign)
+inline int64_t scores_num_parts(int64_t rows) { const int64_t c = (rows + 255) / 256; return c < kScoreParts ? (c < 1 ? 1 : c) : kScoreParts; }
+constexpr int kColsumRowsPerBlock = 256;
+inline int64_t colsum_num_parts(int64_t rows) { return (rows + kColsumRowsPerBlock - 1) / kColsumRowsPerBlock; }
+constexpr int kAbsmaxRowsPerBlock = 1024;
+inline int64_t absmax_num_parts(int64_t rows) { return (rows + kAbsmaxRowsPerBlock - 1) / kAbsmaxRowsPerBlock; }
+
+// ---- GEMM plans ------------------------------------------------------------------------------------------------------------------
+// K1: 32-row units of the padded matrix; resident waves (multiple of 4), wave w owns a contiguous, balanced range of units
+struct GqPlan { int64_t units; int64_t waves; };
+inline GqPlan gq_plan(int64_t Mpad, int waves_target) {
+    GqPlan p;
+    p.units = Mpad / 32;
+    int64_t w = waves_target < 4 ? 4 : waves_target;
+    if (w > p.units) w = p.units;
+    w = (w + 3) / 4 * 4;
+    p.waves = w;
+    return p;
+}
+// K2 (f32): a wave owns one 256-sample block and a contiguous range of SNP rows
+struct GttPlan { int64_t nblocks_n; int W; int64_t rows_per_wave; int64_t grid; };
+inline GttPlan gtt_plan(int64_t Mpad, int64_t Npad, int L, int target_waves) {
+    GttPlan p;
+    p.nblocks_n = Npad / kSamplePad;
+    int64_t W = target_waves / p.nblocks_n;
+    if (W < 1) W = 1;
+    const int64_t maxW = Mpad / 32;
+    if (W > maxW) W = maxW;
+    int64_t rpw = (Mpad + W - 1) / W;
+    rpw = (rpw + 31) / 32 * 32;          // even number of 16-row groups per wave (Mpad is a multiple of 128)
+    W = (Mpad + rpw - 1) / rpw;
+    p.W = (int)W;
+    p.rows_per_wave = rpw;
+    const int64_t ngroups = (p.nblocks_n + 3) / 4;
+    p.grid = ngroups * W;
+    (void)L;
+    return p;
+}
+// K2 (exact path) work decomposition: see kernels.h
+struct Gtt8Plan { int64_t nblocks_n; int W; int64_t rows_per_wave; int64_t grid; int tasks_per_wg; int64_t S; int64_t ngroups; int strided; int64_t C; };
+inline Gtt8Plan gtt8_plan(int64_t Mpad, int64_t Npad, int target_waves) {
+    Gtt8Plan p{};
+    p.nblocks_n = Npad / 128;
+    int64_t W = target_waves / p.nblocks_n;
+    if (W < 1) W = 1;
+    // a slice's digit-plane sums live in i32 accumulators: |g| <= 2 times |digit| <= 128 per row keeps 2^22 rows a factor 2 inside
+    // 2^31 (only a resident matrix of > 4M rows AND > 260k samples would get there: more than one GPU holds)
+    const int64_t minW = (Mpad + ((int64_t)1 << 22) - 1) >> 22;
+    if (W < minW) W = minW;
+    const int64_t maxW = Mpad / 128;
+    if (W > maxW) W = maxW;
+    int64_t rpw = (Mpad + W - 1) / W;
+    rpw = (rpw + 127) / 128 * 128;       // k-blocks per wave: multiple of 4 (Mpad is a multiple of 128)
+    W = (Mpad + rpw - 1) / rpw;
+    p.W = (int)W;
+    p.rows_per_wave = rpw;
+    p.grid = ((p.nblocks_n + 3) / 4) * W;
+    return p;
+}
+// several consecutive (row chunk, n-group) tasks per workgroup (kernels.h): W row chunks such that one batch of `grid0` workgroups
+// covers the tasks evenly.  Cost model per candidate W, relative to the bytes of one sweep: batch fill (tasks rounded up to whole
+// workgroup loads), ~3 stages of prologue / drain / tile store per task, the fold's read of W partial tiles, and 2 % when a row chunk's
+// T' planes (16 KiB per stage) outgrow the share of an XCD's L2 they can expect to keep.
+inline Gtt8Plan gtt8_plan_batched(int64_t Mpad, int64_t Npad, int target_waves) {
+    Gtt8Plan p{};
+    p.nblocks_n = Npad / 128;
+    p.ngroups = (p.nblocks_n + 3) / 4;
+    p.S = Mpad / 128;
+    int64_t grid0 = target_waves / 8;                // the default target (2 048) = 256 workgroups = one per CU of an MI355X
+    if (grid0 < 1) grid0 = 1;
+    // a task's digit-plane sums live in i32 accumulators: at most 2^22 rows (32 768 stages) per task
+    const int64_t wmin = std::max<int64_t>(1, (p.S + 32767) / 32768), wmax = std::min<int64_t>(p.S, 1024);
+    double best = 1e300;
+    int64_t bestW = wmin;
+    for (int64_t W = wmin; W <= std::max(wmin, wmax); ++W) {
+        const int64_t T = W * p.ngroups, k = (T + grid0 - 1) / grid0;
+        double f = (double)(k * grid0) / (double)T;                                      // batch fill: k tasks per workgroup against T / grid0
+        f *= 1.0 + 3.0 * (double)W / (double)p.S;                                        // per-task prologue / drain / store
+        f += (double)W * 256.0 / (double)Mpad;                                           // the fold reads W x Npad x 256 B against Mpad x Npad
+        if ((double)p.S / (double)W * 16384.0 > 3.0 * 1048576.0) f += 0.02;               // T' planes of a row chunk vs L2
+        if (f < best - 1e-12) { best = f; bestW = W; }
+    }
+    p.C = (p.S + bestW - 1) / bestW;                  // stages per row chunk (the last chunk may be shorter)
+    p.W = (int)((p.S + p.C - 1) / p.C);
+    const int64_t T = (int64_t)p.W * p.ngroups;
+    p.tasks_per_wg = (int)((T + grid0 - 1) / grid0);
+    p.grid = (T + p.tasks_per_wg - 1) / p.tasks_per_wg;
+    p.strided = 1;
+    p.rows_per_wave = p.C * 128;                      // rows of a full task
+    return p;
+}
+// K2 for at most 256 samples (int8 rows): every wave owns a row chunk of its own
+constexpr int64_t kNarrowSamples = 256;
+inline Gtt8Plan gtt8_plan_narrow(int64_t Mpad, int64_t N, int target_waves) {
+    Gtt8Plan p{};
+    p.nblocks_n = (N + 127) / 128;                      // 128-sample blocks that hold samples: 1 or 2
+    int64_t W = target_waves / p.nblocks_n;
+    if (W < 1) W = 1;
+    const int64_t maxW = Mpad / 128;
+    if (W > maxW) W = maxW;
+    int64_t rpw = (Mpad + W - 1) / W;
+    rpw = (rpw + 127) / 128 * 128;
+    W = (Mpad + rpw - 1) / rpw;
+    p.W = (int)W;
+    p.rows_per_wave = rpw;
+    p.grid = (W * p.nblocks_n + 3) / 4;
+    return p;
+}
+// projection sweep (project.hip): n-groups of 4 x 64 samples, W row chunks
+struct PrjPlan { int64_t ngroups; int W; int64_t rows_per_wave; int64_t grid; };
+inline PrjPlan prj_plan(int64_t Mpad, int64_t Npad, int target_waves) {
+    PrjPlan p{};
+    const int64_t nblocks = Npad / 64;
+    p.ngroups = (nblocks + 3) / 4;
+    int64_t W = target_waves / nblocks;
+    if (W < 1) W = 1;
+    const int64_t minW = (Mpad + ((int64_t)1 << 22) - 1) >> 22;    // i32 accumulators: |g| |digit| <= 128 per row, 2^22 rows per wave at most
+    if (W < minW) W = minW;
+    const int64_t maxW = Mpad / 128;
+    if (W > maxW) W = maxW;
+    if (W < 1) W = 1;
+    int64_t rpw = (Mpad + W - 1) / W;
+    rpw = (rpw + 127) / 128 * 128;
+    W = (Mpad + rpw - 1) / rpw;
+    p.W = (int)W;
+    p.rows_per_wave = rpw;
+    p.grid = p.ngroups * W;
+    return p;
+}
+
+// ---- workspace capacities (elements) ---------------------------------------------------------------------------------------------
+// d_part64 (doubles) of a handle with M rows (Mpad padded) and N samples (Npad padded) at sketch width L: the partial Grams of the
+// sample side, of B = A Q and of any factor of fewer rows, the column sums, the abs-max partials of a 32-column block, and the two
+// partial arrays of the orthonormalisation's tail
+inline int64_t part64_capacity(int64_t M, int64_t Mpad, int64_t N, int64_t Npad, int L) {
+    return std::max({std::max(gram_num_parts(N), gram_max_parts(std::max(M, N))) * (int64_t)L * L, colsum_num_parts(Npad) * (int64_t)L,
+                     absmax_num_parts(Mpad) * (int64_t)32, 2 * tail_num_parts(Npad) * (int64_t)L});
+}
+// d_cpart (floats): c partials per K1 wave x L (f32 path), per 64-row group x L (Omega, launch_scale_rows), or per 32-row unit x 32 per
+// 32-column block (exact path)
+inline int64_t cpart_capacity(int64_t gq_waves, int64_t Mpad, int L) {
+    return std::max({gq_waves * (int64_t)L, omega_num_parts(Mpad) * (int64_t)L, Mpad * (int64_t)(L / 32)});
+}
+// d_cand_val / d_cand_idx (elements): one candidate per workgroup of launch_scores and column
+inline int64_t scores_cand_capacity() { return (int64_t)kScoreParts * kMaxSketchCols; }
+// the workspace of one gpca_project call (Lp = columns rounded up to 32): scratch of the sum of c (doubles), the abs-max partials of a
+// 32-column block or the 2 * Lp gathered column maxima of a sharded model (doubles), the c partials of one side (floats)
+inline int64_t project_scratch_capacity(int Lp) { return sum_scratch_need(Lp); }
+inline int64_t project_part_capacity(int64_t Mpad, int Lp) { return std::max<int64_t>(absmax_num_parts(Mpad) * 32, 2 * (int64_t)Lp); }
+inline int64_t project_cpart_capacity(int64_t Mpad, int Lp) { return omega_num_parts(Mpad) * (int64_t)Lp; }
+
+}  // namespace gpca

@@ -177,25 +177,7 @@ __global__ __launch_bounds__(256, 1) void k_project(const void* __restrict__ G, 
     if (bad) atomicOr(bad_out, 1u);
 }
 
-PrjPlan prj_plan(int64_t Mpad, int64_t Npad, int target_waves) {
-    PrjPlan p{};
-    const int64_t nblocks = Npad / 64;
-    p.ngroups = (nblocks + 3) / 4;
-    int64_t W = target_waves / nblocks;
-    if (W < 1) W = 1;
-    const int64_t minW = (Mpad + ((int64_t)1 << 22) - 1) >> 22;    // i32 accumulators: |g| |digit| <= 128 per row, 2^22 rows per wave at most
-    if (W < minW) W = minW;
-    const int64_t maxW = Mpad / 128;
-    if (W > maxW) W = maxW;
-    if (W < 1) W = 1;
-    int64_t rpw = (Mpad + W - 1) / W;
-    rpw = (rpw + 127) / 128 * 128;
-    W = (Mpad + rpw - 1) / rpw;
-    p.W = (int)W;
-    p.rows_per_wave = rpw;
-    p.grid = p.ngroups * W;
-    return p;
-}
+// (the plan: prj_plan, plan_math.h)
 
 void launch_project(hipStream_t st, const void* G, int packed, int64_t ldr, int64_t Mpad, int64_t Npad, const int8_t* Ta, const int8_t* Tb,
                     const uint32_t* rmask, double* Ypa, double* Ypb, unsigned* cnt, unsigned* bad, const PrjPlan& plan, int nd, int lazy_b) {

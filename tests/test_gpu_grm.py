@@ -12,6 +12,7 @@ import pytest
 import genomic_pca_amd as gpca
 from genomic_pca_amd import _lib
 from genomic_pca_amd._lib import GpcaError
+from _edges import edge_keeps, edge_shapes
 
 pytestmark = pytest.mark.gpu
 
@@ -284,3 +285,55 @@ def test_errors():
         assert "device memory" in lib.gpca_last_error(e._h).decode()
     with gpca.GpcaEngine() as e:                                  # no genotypes
         assert lib.gpca_grm(e._h, 0, 0, 1, out.ctypes.data, None) == _lib.GPCA_ERR_STATE
+
+
+# 9. tile edges: sample counts at and around the 64 x 64 output tile, kSamplePad (256) and kSamplePad2bit (1 024), down to one sample; row
+#    counts at and around the 32-row block and the flush group (4 096), down to one row.  mu / sigma come from the population frequencies,
+#    not from the data, so that every row of every shape -- one sample included -- is a usable model row.
+def edge_case(M, N, seed, miss=0.02):
+    rng = np.random.default_rng(seed)
+    p = rng.uniform(0.05, 0.5, size=(M, 1))
+    G = (rng.random((M, N)) < p).astype(np.int8) + (rng.random((M, N)) < p).astype(np.int8)
+    G[rng.random((M, N)) < miss] = -127
+    mu = (2 * p[:, 0]).astype(np.float32)
+    sigma = np.sqrt(2 * p[:, 0] * (1 - p[:, 0])).astype(np.float32)
+    return G, mu, sigma
+
+
+@pytest.mark.parametrize("store", ["int8", "2bit"])
+@pytest.mark.parametrize("M,N", edge_shapes((65, 1025)))
+def test_tile_edges(store, M, N):
+    G, mu, sigma = edge_case(M, N, seed=1000 * N + M)
+    with gpca.GpcaEngine(storage=STORES[store]) as e:
+        e.upload_genotypes_i8(G)
+        e.snp_stats(gpca.QcConfig.none())
+        for name, keep in edge_keeps(M):
+            e.set_standardization(mu, sigma, keep)
+            st = e.get_standardization()
+            assert np.array_equal(st["keep"].astype(np.uint8), keep), name
+            for scaling in ("standardized", "centred"):
+                g, npairs = e.grm(scaling, npairs=True)
+                ref, ref_np = ref_grm(G, st, scaling)
+                assert g.shape == (N, N) and npairs.shape == (N, N) and np.array_equal(g, g.T), (name, scaling)
+                assert np.max(np.abs(g - ref)) <= 1e-8 * np.max(np.diag(ref)), (name, scaling)
+                assert np.array_equal(npairs, ref_np.astype(np.float32)), (name, scaling)
+                tri = e.grm(scaling, rows=(0, N))
+                assert tri.shape == (N * (N + 1) // 2,) and np.array_equal(tri, g[np.tril_indices(N)]), (name, scaling)
+
+
+@pytest.mark.parametrize("store", ["int8", "2bit"])
+def test_bands_cut_at_every_tile_edge(store):
+    """[0, N) cut at every multiple of the 64-row output tile, and one below and one above it: the bands, concatenated, are the full call"""
+    M, N = 2000, 330
+    G, mu, sigma = edge_case(M, N, seed=21)
+    cuts = sorted({0, N} | {c for t in range(64, N, 64) for c in (t - 1, t, t + 1)})
+    with gpca.GpcaEngine(storage=STORES[store]) as e:
+        e.upload_genotypes_i8(G)
+        e.snp_stats(gpca.QcConfig.none())
+        e.set_standardization(mu, sigma, np.ones(M, np.uint8))
+        for s in ("standardized", "centred"):
+            full, fnp = e.grm(s, rows=(0, N), npairs=True)
+            parts = [e.grm(s, rows=(a, b), npairs=True) for a, b in zip(cuts[:-1], cuts[1:])]
+            assert [p[0].size for p in parts] == [b * (b + 1) // 2 - a * (a + 1) // 2 for a, b in zip(cuts[:-1], cuts[1:])]
+            assert np.array_equal(np.concatenate([p[0] for p in parts]), full)
+            assert np.array_equal(np.concatenate([p[1] for p in parts]), fnp)

@@ -14,6 +14,7 @@ import pytest
 import genomic_pca_amd as gpca
 from genomic_pca_amd import _lib
 from genomic_pca_amd._lib import GpcaError
+from _edges import edge_keeps, edge_shapes
 
 pytestmark = pytest.mark.gpu
 
@@ -358,3 +359,42 @@ def test_compute_pca_project_all_with_blocks_leaving_snps_out():
         acc = gpca.MicroarrayGenotypeAccessor(e)
         out, _ = gpca.EigenSNPCoreAlgorithm(cfg).compute_pca(acc, [gpca.LdBlockSpecification("b", ids)])
         assert out.projected_sample_scores is None
+
+
+# 9. tile edges: sample counts at and around the 128 x 128 output tile, kSamplePad (256) and kSamplePad2bit (1 024), down to one sample
+#    (an empty triangle); row counts at and around the 32-row block, down to one row; three keep masks per shape.
+@pytest.mark.parametrize("store", ["int8", "2bit"])
+@pytest.mark.parametrize("M,N", edge_shapes((129, 1025)))
+def test_tile_edges(store, M, N):
+    G = genotypes(M, N, seed=1000 * N + M, miss=0.02)
+    mu, sigma = np.ones(M, np.float32), np.ones(M, np.float32)      # (the kinship reads only the genotypes and the keep mask)
+    with gpca.GpcaEngine(storage=STORES[store]) as e:
+        e.upload_genotypes_i8(G)
+        e.snp_stats(gpca.QcConfig.none())
+        for name, keep in edge_keeps(M):
+            e.set_standardization(mu, sigma, keep)
+            assert np.array_equal(e.get_standardization()["keep"].astype(np.uint8), keep), name
+            kin, cnt = e.king(rows=(0, N), counts=True)
+            full = e.king()
+            ref, rcnt = ref_king(G, keep)
+            assert kin.shape == (N * (N - 1) // 2,) and cnt.shape == (N * (N - 1) // 2, 3), name
+            assert full.shape == (N, N) and np.all(np.diag(full) == 0.5), name
+            assert np.array_equal(cnt, lower(rcnt)), name
+            assert np.array_equal(kin, lower(ref), equal_nan=True), name
+            assert np.array_equal(lower(full), kin, equal_nan=True) and np.array_equal(full, full.T, equal_nan=True), name
+
+
+@pytest.mark.parametrize("store", ["int8", "2bit"])
+def test_bands_cut_at_every_tile_edge(store):
+    """[0, N) cut at every multiple of the 128-row output tile, and one below and one above it: the bands, concatenated, are the full call"""
+    M, N = 2000, 530
+    G = genotypes(M, N, seed=23, miss=0.02)
+    cuts = sorted({0, N} | {c for t in range(128, N, 128) for c in (t - 1, t, t + 1)})
+    with gpca.GpcaEngine(storage=STORES[store]) as e:
+        e.upload_genotypes_i8(G)
+        keep_some(e, seed=24)
+        full, fc = e.king(rows=(0, N), counts=True)
+        parts = [e.king(rows=(a, b), counts=True) for a, b in zip(cuts[:-1], cuts[1:])]
+        assert [p[0].size for p in parts] == [b * (b - 1) // 2 - a * (a - 1) // 2 for a, b in zip(cuts[:-1], cuts[1:])]
+        assert np.array_equal(np.concatenate([p[0] for p in parts]), full, equal_nan=True)
+        assert np.array_equal(np.concatenate([p[1] for p in parts]), fc)

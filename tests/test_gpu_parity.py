@@ -216,6 +216,40 @@ def test_rsvd_wide_sketch(gpca, oracle, store, M, N, P, k):
             e.rsvd(120, 10, 2, seed=7)
 
 
+@pytest.mark.timeout(240)      # (first measured run: 48 s, most of it the oracle's plain-loop products over 2.2 M rows; five times that)
+def test_rsvd_wide_sketch_above_two_million_rows(gpca, oracle):
+    """A sketch wider than 64 columns (k = 60 -> l = 70 -> L = 128) on more than 2 097 152 rows: gram_num_parts(M) = 1 075 parts of the
+    Gram of B = A Q, folded in sum_slices = 17 slices of 128 x 128 doubles -- 278 528 doubles of scratch, where the handle used to hold
+    262 144 (tests/test_plan_audit.py names the pair).  int8 rows from the on-device generator, a short sample axis (the row count is the
+    point), against the oracle on the same int8 rows at the suite's bars; then the suite's usual properties."""
+    from genomic_pca_amd import _lib
+    M, N, P, k = 2200000, 128, 6, 60
+    th = gpca.synth_thresholds(M, P, seed=5, fst=0.3)
+    with gpca.GpcaEngine(precision=_lib.PREC_I8_EXACT, storage=_lib.STORE_INT8) as e:
+        e.synth_genotypes(M, N, 5, th)
+        G = e.download_genotypes_i8()
+        st = oracle.snp_stats(G, N, 0.0, 0.0, 1.0)
+        dst = e.snp_stats(gpca.QcConfig.none())
+        assert np.array_equal(dst["keep"], st["keep"]) and np.array_equal(dst["mu"], st["mu"])
+        e.rsvd(k, 10, 2, seed=5)
+        ev, sc, ld, sv = e.eigenvalues(), e.scores(f64=True), e.loadings().astype(np.float64), e.singular_values()
+        e.rsvd(k, 10, 2, seed=5)
+        assert np.array_equal(e.eigenvalues(), ev) and np.array_equal(e.scores(f64=True), sc), "a second call gave other bits"
+    r, b = oracle.scale_shift(st["mu"], st["sigma"], st["keep"])
+    R = oracle.rsvd(G, N, r, b, k, 10, 2, seed=5)
+    kept = st["keep"].astype(bool)                                   # (a handful of the rows are monomorphic in 128 samples: no loading)
+    assert ev.shape == (k,) and sc.shape == (N, k) and ld.shape == (int(kept.sum()), k) and sv.shape == (k + 10,)
+    dev = float(np.max(np.abs(ev - R["eigenvalues"]) / R["eigenvalues"]))
+    ns = P - 1                                                       # the population PCs; the rest sit in the noise bulk
+    dsc, dld = oracle.max_abs_dpc(sc[:, :ns], R["scores"][:, :ns]), oracle.max_abs_dpc(ld[:, :ns], R["loadings"][kept][:, :ns])
+    print(f"wide sketch, M={M} N={N} k={k}: max rel d(eigenvalue) = {dev:.3e}, max|dPC| scores = {dsc:.3e}, loadings = {dld:.3e}")
+    assert dev < TOL_EV and dsc < TOL_PC and dld < TOL_PC
+    gram = sc.T @ sc
+    assert np.max(np.abs(gram - np.diag(np.diag(gram)))) < 1e-8 * gram[0, 0]          # scores orthogonal, norms = singular values
+    assert np.max(np.abs(np.sqrt(np.diag(gram)) - sv[:k]) / sv[:k]) < 1e-8
+    assert np.max(np.abs(ld.T @ ld - np.eye(k))) < 1e-5                                # loadings orthonormal (f32 storage)
+
+
 @pytest.mark.parametrize("planes", [3, 4])
 def test_three_planes_under_a_wide_maf_spectrum(gpca, oracle, planes):
     """three digit planes are the default on 2-bit rows, and the sketch's planes are scaled by the analytic bound 6.67 max r over

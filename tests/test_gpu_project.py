@@ -12,6 +12,8 @@ import pytest
 import genomic_pca_amd as gpca
 from genomic_pca_amd import _lib
 from genomic_pca_amd._lib import GpcaError
+from _edges import edge_keeps, edge_shapes
+from test_gpu_exact_pass import check_against_bars
 
 pytestmark = pytest.mark.gpu
 
@@ -281,3 +283,25 @@ def test_pca_transform_new_samples():
     assert got.shape == (N2, model.k) and close(got, ref)
     with pytest.raises(ValueError):
         model.transform(x2[:, :-1])
+
+
+# 9. tile edges: sample counts at and around the 64-sample block of the sweep, kSamplePad (256) and kSamplePad2bit (1 024), down to one
+#    sample; row counts at and around the 32-row block and the 128-row stage, down to one row; 2 % missing calls; three models per shape.
+@pytest.mark.parametrize("store", ["int8", "2bit"])
+@pytest.mark.parametrize("M,N", edge_shapes((65, 1025)))
+def test_tile_edges(store, M, N):
+    k = 33                                                          # two 32-column blocks, the second with one live column
+    G = genotypes(M, N, seed=1000 * N + M, miss=0.02)
+    G[:, N // 2] = -127                                              # a sample with every call missing
+    mu, sigma, W0 = random_model(M, k, seed=M + N, frac_model=1.0)
+    with gpca.GpcaEngine(storage=STORES[store]) as e:
+        e.upload_genotypes_i8(G)
+        for name, model in edge_keeps(M):
+            W = np.where(model.astype(bool)[:, None], W0, np.float32(0))
+            sc, used = e.project(mu, sigma, W)
+            ref, ref_used = ref_project(G, mu, sigma, W)
+            assert sc.shape == (N, k) and used.shape == (N,), name
+            assert np.array_equal(used, ref_used), name
+            # the derived bars of one exact pass (tests/test_gpu_exact_pass.py), every sample and column: not close()'s 1e-4
+            check_against_bars(sc, G, mu, sigma, W, 4 if store == "int8" else 3, True, f"project {store} M={M} N={N} {name}")
+            assert np.all(sc[N // 2] == 0.0) and used[N // 2] == 0, name
