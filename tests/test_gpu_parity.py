@@ -571,6 +571,7 @@ def test_bed2bit_decode_reference_fixture(gpca, oracle, engine):
 # BASELINE.json configs[1] at full size (1M SNPs x 10k samples): size-independent properties
 # ------------------------------------------------------------------------------------------------
 _FULL = {}
+_FULL_K1 = {}        # the rows of check (7) and their bytes from the oracle: the same for every path
 
 
 def _full_size_case(gpca, oracle, prec, store):
@@ -628,6 +629,24 @@ def _full_size_case(gpca, oracle, prec, store):
             g_row = oracle.synth_genotypes(1, N, seed, th[i:i + 1], snp_offset=int(i)).astype(np.float64)[0]
             a_i = (g_row - float(st["mu"][i])) / float(st["sigma"][i])
             assert np.max(np.abs(a_i @ V / sv[:2] - ld[i, :2].astype(np.float64))) < 1e-5
+        # (7) the same identity for a few thousand rows and ALL k columns under the bar derived in test_gpu_k1_pass.py (one K1 sweep between
+        #     the scores and the loadings): the first and last 64 rows, the rows around every 2^16 boundary, a seeded sample of the rest
+        import test_gpu_k1_pass as K1
+        if "rows" not in _FULL_K1:
+            edge = np.concatenate([np.arange(64), np.arange(M - 64, M)] + [np.arange(b - 2, b + 2) for b in range(1 << 16, M, 1 << 16)])
+            pick = np.unique(np.concatenate([edge, np.random.default_rng(7).choice(M, 2000, replace=False)]))
+            _FULL_K1["rows"] = pick
+            _FULL_K1["G"] = np.concatenate([oracle.synth_genotypes(1, N, seed, th[i:i + 1], snp_offset=int(i)) for i in pick])
+        pick, Gp = _FULL_K1["rows"], _FULL_K1["G"]
+        op = oracle.snp_stats(Gp, N, 0.0, 0.0, 1.0)
+        assert np.array_equal(st["mu"][pick], op["mu"])
+        ulps = np.abs(st["sigma"][pick].astype(np.float64) - op["sigma"].astype(np.float64)) / np.spacing(op["sigma"]).astype(np.float64)
+        assert np.all(ulps <= 1)
+        at = np.arange(len(pick))
+        truth = K1.k1_truth(Gp, op["mu"], op["sigma"], at, sc, sv)
+        nd = 0 if prec == "f32" else (3 if store == "2bit" else 4)
+        bar = K1.k1_bar(Gp, op["mu"], op["sigma"], at, sc, sv, k + 10, nd, truth, None, ulps)
+        K1.check(ld[pick], truth, bar, f"full size {prec} {store}: {len(pick)} rows x {k} columns")
     _FULL[(prec, store)] = (ev, sc[:, :2].copy(), ld[:, :2].astype(np.float64))
     return _FULL[(prec, store)]
 
