@@ -100,6 +100,12 @@ def build_parser() -> argparse.ArgumentParser:
                         "KING-robust kinship > X remains, the sample with the most such partners leaves (ties: the later one in .fam "
                         "order) -> P.king.cutoff.in.id / .out.id.  The PCs are fitted on the in-set and every sample is projected onto "
                         "them; SNP QC, means and s.d. stay over all samples")
+    p.add_argument("--gpca-indep-pairwise", nargs=2, default=None, metavar=("WINDOW", "R2"),
+                   help="EigenSNP workflow: prune SNPs in linkage disequilibrium before the GRM, KING and the PCA (plink's "
+                        "--indep-pairwise with step 1).  WINDOW = a variant count such as 50 (each kept SNP against the next 49 of its "
+                        "chromosome) or a span such as 250kb; 0 < R2 < 1.  Of a pair of kept SNPs with unphased r^2 > R2 the one with the "
+                        "smaller minor-allele frequency leaves (ties: the later one) -> P.prune.in / P.prune.out.  Needs the matrix "
+                        "resident on the device; plink's exact output is not claimed")
     return p
 
 
@@ -231,6 +237,8 @@ def run_eigensnp_workflow(a) -> int:
         _log("No samples or SNPs available for EigenSNP PCA after preparation.")     # main.rs:349-352
         return 0
     eng.set_standardization(st["mu"], st["sigma"], keep)
+    if a.gpca_indep_pairwise:
+        keep, by_tag = _indep_pairwise(eng, a, fs, st, keep, by_tag)
     if a.gpca_make_grm:
         _ensure_parent(a.output_prefix)
         fids = fs.family_ids if cols is None else [fs.family_ids[i] for i in cols]
@@ -314,6 +322,41 @@ def _king(eng, a, fs, cols, sample_ids, n_snps):
     return inset
 
 
+def _indep_pairwise(eng, a, fs, st, keep, by_tag):
+    """--gpca-indep-pairwise WINDOW R2: the threshold bits of the windowed r^2 (gpca_ld_window, in row bands), the pruning rule
+    (io.ld_prune) and P.prune.in / P.prune.out; the in-set narrows the keep mask (mu, sigma unchanged) and the block lists.  Returns
+    the new (keep, by_tag)."""
+    from . import _lib
+    window, r2max = a.gpca_indep_pairwise[0], float(a.gpca_indep_pairwise[1])
+    rows = np.flatnonzero(keep)
+    try:
+        win_end = gio.ld_windows([fs.chromosomes[r] for r in rows], np.asarray(fs.positions, np.int64)[rows], window)
+    except ValueError as e:
+        raise SystemExit(f"error: --gpca-indep-pairwise: {e} (variant indices count the SNPs kept by QC and the LD blocks)") from None
+    counts, _ = eng.snp_qc_detail()
+    counts = counts[rows]
+    maf = gio.maf_from_qc_detail(counts[:, 0], counts[:, 2], counts[:, 3])
+
+    def bands():
+        for r0, r1, wm in gio.ld_bands(win_end):
+            yield (r0, r1), eng.ld_window(win_end[r0:r1], wmax=wm, rows=(r0, r1), threshold=r2max, r2=False)["above"]
+    try:
+        inset = gio.ld_prune(win_end, bands(), maf)
+    except _lib.GpcaError as e:
+        if e.status == _lib.GPCA_ERR_STATE:
+            raise SystemExit("error: --gpca-indep-pairwise needs the genotype matrix resident on the device: with the matrix walked out "
+                             "of core a window crosses the panels, and the halo of rows that needs is not implemented") from None
+        raise
+    _ensure_parent(a.output_prefix)
+    gio.write_prune_ids(a.output_prefix, [fs.variant_ids[r] for r in rows], inset)
+    _log(f"LD pruning (window {window}, r^2 > {r2max:g}): {int(inset.sum())} SNPs kept, {len(rows) - int(inset.sum())} removed")
+    keep2 = np.zeros_like(keep)
+    keep2[rows[inset]] = 1
+    eng.set_standardization(st["mu"], st["sigma"], keep2)
+    by_tag = [(t, [r for r in rs if keep2[r]]) for t, rs in by_tag]
+    return keep2, [(t, rs) for t, rs in by_tag if rs]
+
+
 def run_project_workflow(a) -> int:
     """--gpca-project-model MODEL --bed-file TARGET --out Q: the target's samples on the model's PCs (gpca_project)."""
     if not a.bed_file:
@@ -352,6 +395,19 @@ def main(argv=None) -> int:
         raise SystemExit("error: --gpca-king-cutoff must lie in (0, 0.5)")
     if a.gpca_king_cutoff is not None and a.gpca_eigensnp_local_stage:
         raise SystemExit("error: --gpca-king-cutoff cannot be combined with --gpca-eigensnp-local-stage (that stage owns the sample mask)")
+    if a.gpca_indep_pairwise:
+        if not a.eigensnp:
+            raise SystemExit("error: --gpca-indep-pairwise needs the --eigensnp workflow")
+        try:
+            gio.parse_ld_window(a.gpca_indep_pairwise[0])
+        except ValueError as e:
+            raise SystemExit(f"error: --gpca-indep-pairwise: {e}") from None
+        try:
+            r2max = float(a.gpca_indep_pairwise[1])
+        except ValueError:
+            r2max = float("nan")
+        if not 0.0 < r2max < 1.0:
+            raise SystemExit("error: --gpca-indep-pairwise R2 must lie in (0, 1)")
     if a.gpca_project_model:
         return run_project_workflow(a)
     if a.gpca_save_model and not a.eigensnp:

@@ -318,4 +318,17 @@ void launch_king_vec_f64(hipStream_t st, const unsigned* het, const unsigned* mi
 void launch_king_finish(hipStream_t st, const double* R, int64_t E, const double* het, const double* miss, double K, int64_t row0,
                         int64_t row1, double* kin, int* counts);
 
+// ---- windowed LD: banded SYRK of the kept rows with themselves over the samples (ld.hip) ---------------------------------------------
+// krows [K]: original row of every kept row; W [kLdProducts][(row1 - row0) * wmax] i32 product planes, zeroed by the caller; weff: the
+// widest window of the band in slots (tiles beyond it are not multiplied)
+void launch_ld(hipStream_t st, const void* G, int packed, int64_t ldr, const int64_t* krows, int64_t K, int64_t N, int64_t row0,
+               int64_t row1, const int64_t* win_end, int wmax, int weff, int* W);
+// stat [hi - row0][3] = sum g', sum g'^2, missing calls of kept rows [row0, hi); *bad = min original row with a value outside
+// {0, 1, 2, missing} (left as it is when there is none)
+void launch_ld_vec(hipStream_t st, const void* G, int packed, int64_t ldr, const int64_t* krows, int64_t N, int64_t row0, int64_t hi,
+                   unsigned* stat, unsigned long long* bad);
+// r2 [rows][wmax], counts [rows][wmax][6], above [rows][ld_above_words(wmax)] (each may be NULL) from the planes and the per-row sums
+void launch_ld_finish(hipStream_t st, const int* W, const unsigned* stat, int64_t N, int64_t row0, int64_t row1, const int64_t* win_end,
+                      int wmax, double threshold, double* r2, int* counts, unsigned long long* above);
+
 }  // namespace gpca

@@ -218,4 +218,31 @@ inline int64_t project_scratch_capacity(int Lp) { return sum_scratch_need(Lp); }
 inline int64_t project_part_capacity(int64_t Mpad, int Lp) { return std::max<int64_t>(absmax_num_parts(Mpad) * 32, 2 * (int64_t)Lp); }
 inline int64_t project_cpart_capacity(int64_t Mpad, int Lp) { return omega_num_parts(Mpad) * (int64_t)Lp; }
 
+// ---- windowed LD (ld.hip, gpca_ld.cpp) -------------------------------------------------------------------------------------------
+// A workgroup owns kLdRows consecutive kept rows of the band (two 32-row tiles, first row i0) and one chunk of kLdCols columns (four
+// 32-column tiles, one per wave) of the span that starts at i0; it walks the samples in stages of kLdStage.
+constexpr int kLdRows = 64, kLdCols = 128, kLdStage = 128, kLdThreads = 256;
+constexpr int kLdProducts = 6;                       // sum g'g', g'm, mg', g'^2 m, m g'^2, mm: i32 planes of the call's workspace
+inline int64_t ld_row_blocks(int64_t rows) { return (rows + kLdRows - 1) / kLdRows; }
+// 32-column tiles from i0 that a row block's widest window (weff slots) reaches: its last column is i0 + kLdRows - 1 + weff
+inline int64_t ld_col_tiles(int64_t weff) { return (kLdRows - 1 + weff) / 32 + 1; }
+inline int64_t ld_col_chunks(int64_t weff) { return (ld_col_tiles(weff) + kLdCols / 32 - 1) / (kLdCols / 32); }
+inline int64_t ld_stages(int64_t N) { return (N + kLdStage - 1) / kLdStage; }
+// stages per workgroup when the sample axis is split so that about 1 024 workgroups exist (the partial sums meet in i32 atomics)
+inline int64_t ld_stages_per_split(int64_t nblocks, int64_t nst) {
+    int64_t S = nblocks >= 1024 ? 1 : (1024 + nblocks - 1) / std::max<int64_t>(nblocks, 1);
+    if (S > nst) S = nst;
+    if (S < 1) S = 1;
+    return (nst + S - 1) / S;
+}
+inline int64_t ld_splits(int64_t nblocks, int64_t nst) { const int64_t per = ld_stages_per_split(nblocks, nst); return (nst + per - 1) / per; }
+constexpr int64_t ld_above_words(int64_t wmax) { return (wmax + 63) / 64; }
+// elements of the call's buffers: the product planes (i32), one plane after the other; the per-row sums of rows [row0, hi) (u32:
+// sum g', sum g'^2, missing); r2 / counts / above of the band
+inline int64_t ld_ws_capacity(int64_t rows, int64_t wmax) { return (int64_t)kLdProducts * rows * wmax; }
+inline int64_t ld_stat_capacity(int64_t row0, int64_t hi) { return 3 * (hi - row0); }
+inline int64_t ld_r2_capacity(int64_t rows, int64_t wmax) { return rows * wmax; }
+inline int64_t ld_counts_capacity(int64_t rows, int64_t wmax) { return 6 * rows * wmax; }
+inline int64_t ld_above_capacity(int64_t rows, int64_t wmax) { return rows * ld_above_words(wmax); }
+
 }  // namespace gpca

@@ -421,6 +421,38 @@ class GpcaEngine:
         fc.transpose(1, 0, 2)[il] = cnt
         return full, fc
 
+    def ld_window(self, win_end, wmax: Optional[int] = None, rows: Optional[Tuple[int, int]] = None, threshold: Optional[float] = None,
+                  r2: bool = True, counts: bool = False):
+        """Windowed LD of the kept rows (gpca_ld_window), rows in PCA-SNP order.  win_end[t]: row row0 + t is paired with every later
+        kept row below win_end[t]; slot d = j - i - 1.  rows = (row0, row1), default every kept row; wmax: slots per row, default the
+        widest window of win_end (at least 1).  Returns a dict with the outputs asked for: "r2" [rows][wmax] f64 (NaN where a row of the
+        pair has no variance over the jointly observed samples), "counts" [rows][wmax][6] int32 = n, sx, sy, sxx, syy, sxy, and, when a
+        threshold is given, "above" [rows][ceil(wmax / 64)] uint64 (bit d % 64 of word d / 64 = r2 > threshold).  Slots outside a row's
+        window are 0."""
+        K = int(self._lib.gpca_num_pca_snps(self._h))
+        r0, r1 = (0, K) if rows is None else (int(rows[0]), int(rows[1]))
+        we = np.ascontiguousarray(win_end, np.int64)
+        n = max(r1 - r0, 0)
+        if we.shape != (n,):
+            raise ValueError("win_end must have one entry per row of the band")
+        if wmax is None:
+            wmax = max(int(np.max(we - np.arange(r0, r1) - 1)) if n else 1, 1)
+        wmax = int(wmax)
+        w1 = max(wmax, 1)
+        out_r2 = np.zeros((max(n, 1), w1), np.float64) if r2 else None
+        out_cnt = np.zeros((max(n, 1), w1, 6), np.int32) if counts else None
+        out_ab = np.zeros((max(n, 1), (w1 + 63) // 64), np.uint64) if threshold is not None else None
+        self._chk(self._lib.gpca_ld_window(self._h, r0, r1, _vp(we), wmax, float(0.0 if threshold is None else threshold),
+                                           _vp(out_r2), _vp(out_cnt), _vp(out_ab)))
+        res = {}
+        if r2:
+            res["r2"] = out_r2[:n]
+        if counts:
+            res["counts"] = out_cnt[:n]
+        if threshold is not None:
+            res["above"] = out_ab[:n]
+        return res
+
     # -- f3: the stages of EigenSNPCoreAlgorithm (gpca.h)
     def copy_rows_from(self, src: "GpcaEngine", row0: int, rows: int):
         """This engine receives rows [row0, row0 + rows) of src's resident matrix (device to device)."""

@@ -22,6 +22,8 @@
 
 #include <algorithm>
 #include <cctype>
+#include <cmath>
+#include <cstdlib>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -609,6 +611,111 @@ inline void write_king_cutoff_ids(const std::string& prefix, const std::vector<s
         std::fputs("#FID\tIID\n", o.f);
         for (size_t i = 0; i < sample_ids.size(); ++i)
             if ((keep[i] != 0) == (want == 1)) std::fprintf(o.f, "%s\t%s\n", family_ids[i].c_str(), sample_ids[i].c_str());
+    }
+}
+
+// ---- windowed LD and LD pruning: the twins of io.parse_ld_window, io.ld_windows, io.ld_bands, io.ld_prune, io.maf_from_qc_detail and
+// io.write_prune_ids (same rules, same error texts, byte-identical files) --------------------------------------------------------
+struct LdWindow { bool bp; int64_t w; };   // bp: a span in base pairs; otherwise a count of variants (the SNP itself included)
+inline LdWindow parse_ld_window(const std::string& text) {
+    auto strip = [](std::string t) {
+        size_t a = 0, b = t.size();
+        while (a < b && std::isspace((unsigned char)t[a])) ++a;
+        while (b > a && std::isspace((unsigned char)t[b - 1])) --b;
+        return t.substr(a, b - a);
+    };
+    std::string t = strip(text);
+    std::transform(t.begin(), t.end(), t.begin(), [](unsigned char c) { return (char)std::tolower(c); });
+    const bool kb = t.size() >= 2 && t.compare(t.size() - 2, 2, "kb") == 0;
+    const std::string num = kb ? strip(t.substr(0, t.size() - 2)) : t;
+    const std::string bad = "bad LD window '" + text + "': ";
+    char* end = nullptr;
+    if (num.empty() || std::isspace((unsigned char)num[0])) throw std::runtime_error(bad + "expected a variant count such as 50 or a span such as 250kb");
+    if (kb) {
+        const double v = std::strtod(num.c_str(), &end);
+        if (*end) throw std::runtime_error(bad + "expected a variant count such as 50 or a span such as 250kb");
+        if (!(v > 0.0) || !std::isfinite(v)) throw std::runtime_error(bad + "the span must be positive");
+        return LdWindow{true, (int64_t)std::nearbyint(v * 1000.0)};
+    }
+    const long long v = std::strtoll(num.c_str(), &end, 10);
+    if (*end) throw std::runtime_error(bad + "expected a variant count such as 50 or a span such as 250kb");
+    if (v < 2) throw std::runtime_error(bad + "a window in variants holds at least 2");
+    return LdWindow{false, (int64_t)v};
+}
+
+// win_end [K] over the kept SNPs, in their order: SNP i is paired with the later SNPs j < win_end[i] of its chromosome run
+inline std::vector<int64_t> ld_windows(const std::vector<std::string>& chromosomes, const std::vector<int64_t>& positions, const std::string& window) {
+    const LdWindow lw = parse_ld_window(window);
+    const int64_t K = (int64_t)chromosomes.size();
+    if ((int64_t)positions.size() != K) throw std::runtime_error("ld_windows: one position per chromosome entry");
+    std::vector<int64_t> win_end((size_t)K);
+    std::set<std::string> seen;
+    for (int64_t s = 0; s < K;) {
+        const std::string c = normalize_chromosome_name(chromosomes[(size_t)s]);
+        if (!seen.insert(c).second)
+            throw std::runtime_error("ld_windows: chromosome '" + chromosomes[(size_t)s] + "' reappears at variant " + std::to_string(s) +
+                                     " after another chromosome: sort the variants");
+        int64_t e = s + 1;
+        while (e < K && normalize_chromosome_name(chromosomes[(size_t)e]) == c) {
+            if (positions[(size_t)e] < positions[(size_t)e - 1])
+                throw std::runtime_error("ld_windows: the position of variant " + std::to_string(e) + " (" + std::to_string(positions[(size_t)e]) +
+                                         ") is below that of the variant before it on chromosome '" + chromosomes[(size_t)e] + "': sort the variants");
+            ++e;
+        }
+        int64_t hi = s;                                  // first SNP of the run beyond the window of i (positions are sorted: it only moves on)
+        for (int64_t i = s; i < e; ++i) {
+            if (!lw.bp) { win_end[(size_t)i] = std::min(i + lw.w, e); continue; }
+            if (hi < i + 1) hi = i + 1;
+            while (hi < e && positions[(size_t)hi] <= positions[(size_t)i] + lw.w) ++hi;
+            win_end[(size_t)i] = hi;
+        }
+        s = e;
+    }
+    return win_end;
+}
+
+// the next row band [r0, r1) with (r1 - r0) * wmax <= max_slots (at least one row), wmax = its widest window (at least 1)
+inline void ld_next_band(const std::vector<int64_t>& win_end, int64_t r0, int64_t max_slots, int64_t& r1, int64_t& wmax) {
+    const int64_t K = (int64_t)win_end.size();
+    auto width = [&](int64_t i) { return win_end[(size_t)i] - i - 1; };
+    r1 = r0 + 1; wmax = std::max<int64_t>(width(r0), 1);
+    while (r1 < K) {
+        const int64_t w2 = std::max(wmax, width(r1));
+        if ((r1 + 1 - r0) * w2 > max_slots) break;
+        wmax = w2; ++r1;
+    }
+}
+
+// one band of the pruning rule (io.ld_prune): above [r1 - r0][words] as gpca_ld_window writes it; bands come in row order
+inline void ld_prune_band(const std::vector<int64_t>& win_end, int64_t r0, int64_t r1, const std::vector<uint64_t>& above, int64_t words,
+                          const std::vector<double>& maf, std::vector<uint8_t>& inset) {
+    for (int64_t i = r0; i < r1; ++i) {
+        if (!inset[(size_t)i]) continue;
+        const uint64_t* row = above.data() + (size_t)(i - r0) * (size_t)words;
+        const int64_t n = win_end[(size_t)i] - i - 1;
+        for (int64_t d = 0; d < n; ++d) {
+            if (!((row[d >> 6] >> (d & 63)) & 1u)) continue;
+            const int64_t j = i + 1 + d;
+            if (!inset[(size_t)j]) continue;
+            if (maf[(size_t)j] > maf[(size_t)i]) { inset[(size_t)i] = 0; break; }
+            inset[(size_t)j] = 0;
+        }
+    }
+}
+
+inline double maf_from_counts(uint32_t n_valid, uint32_t n_het, uint32_t n_hom2) {
+    if (n_valid == 0) return 0.0;
+    const double p = ((double)n_het + 2.0 * (double)n_hom2) / (2.0 * (double)n_valid);
+    return std::min(p, 1.0 - p);
+}
+
+// P.prune.in / P.prune.out: one variant ID per line, in the order given
+inline void write_prune_ids(const std::string& prefix, const std::vector<std::string>& variant_ids, const std::vector<uint8_t>& inset) {
+    if (variant_ids.size() != inset.size()) throw std::runtime_error("write_prune_ids: one in-set flag per variant ID");
+    for (int want = 1; want >= 0; --want) {
+        OutFile o(prefix + (want ? ".prune.in" : ".prune.out"));
+        for (size_t i = 0; i < variant_ids.size(); ++i)
+            if ((inset[i] != 0) == (want == 1)) std::fprintf(o.f, "%s\n", variant_ids[i].c_str());
     }
 }
 

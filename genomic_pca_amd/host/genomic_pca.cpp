@@ -48,6 +48,9 @@ struct Args {
     bool make_king = false;           // --gpca-make-king: also write P.kin0
     bool have_king_filter = false, have_king_cutoff = false;
     double king_filter = 0.0, king_cutoff = 0.0;   // --gpca-king-table-filter X, --gpca-king-cutoff X
+    bool have_indep = false;          // --gpca-indep-pairwise WINDOW R2: LD pruning of the kept SNPs before the GRM, KING and the PCA
+    std::string indep_window, indep_r2_text;
+    double indep_r2 = 0.0;
 };
 
 [[noreturn]] void usage_error(const std::string& msg) {
@@ -110,6 +113,11 @@ void print_help() {
         "                                       SNPs where both samples are observed\n"
         "      --gpca-grm-scaling <S>           --gpca-make-grm: standardized ((g - mean) / s.d., the matrix the PCA factorises) or\n"
         "                                       centred (g - mean) [default: standardized]\n"
+        "      --gpca-indep-pairwise <WINDOW> <R2>  EigenSNP workflow: prune SNPs in linkage disequilibrium before the GRM, KING and the PCA\n"
+        "                                       (plink's --indep-pairwise, step 1).  WINDOW = a variant count such as 50 or a span such as\n"
+        "                                       250kb; 0 < R2 < 1.  Of a pair of kept SNPs with unphased r^2 > R2 the one with the smaller\n"
+        "                                       minor-allele frequency leaves (ties: the later one) -> P.prune.in / P.prune.out.  Needs the\n"
+        "                                       matrix resident on the device\n"
         "      --gpca-make-king                 EigenSNP workflow: also write the KING-robust kinship of every sample pair over the\n"
         "                                       kept SNPs to P.kin0 (#FID1 IID1 FID2 IID2 NSNP HETHET IBS0 KINSHIP, ID1 the earlier\n"
         "                                       sample in .fam order)\n"
@@ -189,6 +197,11 @@ Args parse(int argc, char** argv) {
         else if (f == "--gpca-make-king") a.make_king = true;
         else if (f == "--gpca-king-table-filter") { a.king_filter = to_f64(f, val()); a.have_king_filter = true; }
         else if (f == "--gpca-king-cutoff") { a.king_cutoff = to_f64(f, val()); a.have_king_cutoff = true; }
+        else if (f == "--gpca-indep-pairwise") {
+            a.indep_window = val();
+            if (i + 1 >= argc) usage_error("two values (WINDOW R2) are required for '" + f + "'");
+            a.indep_r2_text = argv[++i]; a.have_indep = true;
+        }
         else usage_error("unexpected argument '" + f + "' found");
     }
     if (a.output_prefix.empty()) usage_error("the following required arguments were not provided:\n  --out <OUTPUT_PREFIX>");
@@ -325,7 +338,7 @@ int run_eigensnp_workflow(Args a) {
     const gpca::SnpStats st = eng.snp_stats(gpca::QcConfig{a.min_call_rate, a.min_maf, a.max_hwe_p});
     const auto blocks = gpca_host::parse_ld_block_file(a.ld_block_file);
     std::vector<uint8_t> keep;
-    const auto by_tag = gpca_host::map_snps_to_ld_blocks(blocks, fs.chromosomes, fs.positions, st.keep, keep);
+    auto by_tag = gpca_host::map_snps_to_ld_blocks(blocks, fs.chromosomes, fs.positions, st.keep, keep);
     int64_t n_qc = 0, n_in = 0;
     for (uint8_t k : st.keep) n_qc += k;
     for (uint8_t k : keep) n_in += k;
@@ -334,6 +347,58 @@ int run_eigensnp_workflow(Args a) {
     logmsg(buf);
     if (sample_ids.empty() || n_in == 0) { logmsg("No samples or SNPs available for EigenSNP PCA after preparation."); return 0; }   // main.rs:349-352
     eng.set_standardization(st.mu, st.sigma, keep);
+    if (a.have_indep) {
+        // the threshold bits of the windowed r^2 in row bands, the pruning rule, P.prune.in / .out; the in-set narrows the keep mask
+        // (mu, sigma unchanged) and the block lists (cli.py:_indep_pairwise)
+        std::vector<int64_t> rows, pos;
+        std::vector<std::string> chrom, ids;
+        for (size_t i = 0; i < keep.size(); ++i)
+            if (keep[i]) { rows.push_back((int64_t)i); chrom.push_back(fs.chromosomes[i]); pos.push_back(fs.positions[i]); ids.push_back(fs.variant_ids[i]); }
+        std::vector<int64_t> win_end;
+        try { win_end = gpca_host::ld_windows(chrom, pos, a.indep_window); }
+        catch (const std::runtime_error& e) {
+            std::fprintf(stderr, "error: --gpca-indep-pairwise: %s (variant indices count the SNPs kept by QC and the LD blocks)\n", e.what());
+            return 1;
+        }
+        const std::vector<uint32_t> counts = eng.snp_qc_counts();
+        std::vector<double> maf(rows.size());
+        for (size_t t = 0; t < rows.size(); ++t) {
+            const uint32_t* c = counts.data() + 4 * (size_t)rows[t];
+            maf[t] = gpca_host::maf_from_counts(c[0], c[2], c[3]);
+        }
+        std::vector<uint8_t> in_ld(rows.size(), 1);
+        for (int64_t r0 = 0; r0 < (int64_t)rows.size();) {
+            int64_t r1 = 0, wm = 1;
+            gpca_host::ld_next_band(win_end, r0, (int64_t)1 << 26, r1, wm);
+            const std::vector<int64_t> we(win_end.begin() + r0, win_end.begin() + r1);
+            std::vector<uint64_t> above;
+            try { eng.ld_window(r0, r1, we, (int32_t)wm, a.indep_r2, nullptr, nullptr, &above); }
+            catch (const gpca::Error& e) {
+                if (e.status() != GPCA_ERR_STATE) throw;
+                std::fprintf(stderr, "error: --gpca-indep-pairwise needs the genotype matrix resident on the device: with the matrix walked out "
+                                     "of core a window crosses the panels, and the halo of rows that needs is not implemented\n");
+                return 1;
+            }
+            gpca_host::ld_prune_band(win_end, r0, r1, above, (wm + 63) / 64, maf, in_ld);
+            r0 = r1;
+        }
+        gpca_host::ensure_parent(a.output_prefix);
+        gpca_host::write_prune_ids(a.output_prefix, ids, in_ld);
+        int64_t n_ld = 0;
+        for (uint8_t v : in_ld) n_ld += v;
+        std::snprintf(buf, sizeof buf, "LD pruning (window %s, r^2 > %g): %lld SNPs kept, %lld removed", a.indep_window.c_str(), a.indep_r2, (long long)n_ld,
+                      (long long)((int64_t)rows.size() - n_ld));
+        logmsg(buf);
+        std::fill(keep.begin(), keep.end(), (uint8_t)0);
+        for (size_t t = 0; t < rows.size(); ++t) if (in_ld[t]) keep[(size_t)rows[t]] = 1;
+        eng.set_standardization(st.mu, st.sigma, keep);
+        for (auto& tr : by_tag) {
+            auto& rs = tr.second;
+            rs.erase(std::remove_if(rs.begin(), rs.end(), [&](int64_t r) { return !keep[(size_t)r]; }), rs.end());
+        }
+        by_tag.erase(std::remove_if(by_tag.begin(), by_tag.end(), [](const auto& tr) { return tr.second.empty(); }), by_tag.end());
+        n_in = n_ld;
+    }
     if (a.make_grm) {
         gpca_host::ensure_parent(a.output_prefix);
         std::vector<std::string> fids = fs.family_ids;
@@ -486,8 +551,16 @@ int run_project_workflow(Args a) {
 }  // namespace
 
 int main(int argc, char** argv) {
-    const Args a = parse(argc, argv);
+    Args a = parse(argc, argv);
     try {
+        if (a.have_indep) {
+            if (!a.eigensnp) { std::fprintf(stderr, "error: --gpca-indep-pairwise needs the --eigensnp workflow\n"); return 2; }
+            try { gpca_host::parse_ld_window(a.indep_window); }
+            catch (const std::runtime_error& e) { std::fprintf(stderr, "error: --gpca-indep-pairwise: %s\n", e.what()); return 2; }
+            char* end = nullptr;
+            a.indep_r2 = a.indep_r2_text.empty() ? std::nan("") : std::strtod(a.indep_r2_text.c_str(), &end);
+            if ((end && *end) || !(a.indep_r2 > 0.0 && a.indep_r2 < 1.0)) { std::fprintf(stderr, "error: --gpca-indep-pairwise R2 must lie in (0, 1)\n"); return 2; }
+        }
         if (a.make_grm && !a.eigensnp) { std::fprintf(stderr, "error: --gpca-make-grm needs the --eigensnp workflow\n"); return 2; }
         if ((a.make_king || a.have_king_cutoff) && !a.eigensnp) { std::fprintf(stderr, "error: --gpca-make-king and --gpca-king-cutoff need the --eigensnp workflow\n"); return 2; }
         if (a.have_king_filter && !a.make_king) { std::fprintf(stderr, "error: --gpca-king-table-filter needs --gpca-make-king\n"); return 2; }

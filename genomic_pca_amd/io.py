@@ -522,3 +522,133 @@ def write_king_cutoff_ids(prefix: str, family_ids: Sequence[str], sample_ids: Se
             f.write("#FID\tIID\n")
             f.writelines(f"{family_ids[i]}\t{sample_ids[i]}\n" for i in range(len(sample_ids)) if bool(keep[i]) == want)
     return paths
+
+
+# ------------------------------------------------------------------------------------------------ windowed LD and LD pruning
+def parse_ld_window(text: str) -> Tuple[str, int]:
+    """The WINDOW of --gpca-indep-pairwise: "50" -> ("variants", 50): each SNP against the next 49 kept SNPs of its chromosome run
+    (plink's window of 50 variants, step 1); "250kb" -> ("bp", 250000): later kept SNPs of the run at most 250 000 bp further on."""
+    t = str(text).strip().lower()
+    kb = t.endswith("kb")
+    num = t[:-2].strip() if kb else t
+    try:
+        v = float(num) if kb else int(num)
+    except ValueError:
+        raise ValueError(f"bad LD window '{text}': expected a variant count such as 50 or a span such as 250kb") from None
+    if kb:
+        if not (v > 0 and np.isfinite(v)):
+            raise ValueError(f"bad LD window '{text}': the span must be positive")
+        return "bp", int(round(v * 1000))
+    if v < 2:
+        raise ValueError(f"bad LD window '{text}': a window in variants holds at least 2")
+    return "variants", v
+
+
+def ld_windows(chromosomes: Sequence[str], positions: Sequence[int], window: str) -> np.ndarray:
+    """win_end [K] (int64) over the kept SNPs, in their order, for gpca_ld_window: SNP i is paired with the later SNPs j < win_end[i]
+    of its chromosome run.  A chromosome that reappears after another, or positions that decrease inside a run, is an error that
+    names the variant (by its index among the SNPs given)."""
+    kind, w = parse_ld_window(window)
+    K = len(chromosomes)
+    pos = np.asarray(positions, np.int64)
+    if pos.shape != (K,):
+        raise ValueError("ld_windows: one position per chromosome entry")
+    win_end = np.empty(K, np.int64)
+    seen = set()
+    s = 0
+    while s < K:
+        c = normalize_chromosome_name(chromosomes[s])
+        if c in seen:
+            raise ValueError(f"ld_windows: chromosome '{chromosomes[s]}' reappears at variant {s} after another chromosome: sort the variants")
+        seen.add(c)
+        e = s + 1
+        while e < K and normalize_chromosome_name(chromosomes[e]) == c:
+            if pos[e] < pos[e - 1]:
+                raise ValueError(f"ld_windows: the position of variant {e} ({int(pos[e])}) is below that of the variant before it on chromosome "
+                                 f"'{chromosomes[e]}': sort the variants")
+            e += 1
+        idx = np.arange(s, e, dtype=np.int64)
+        if kind == "variants":
+            win_end[s:e] = np.minimum(idx + w, e)
+        else:
+            win_end[s:e] = np.maximum(s + np.searchsorted(pos[s:e], pos[s:e] + w, side="right"), idx + 1)
+        s = e
+    return win_end
+
+
+def ld_bands(win_end: np.ndarray, max_slots: int = 1 << 26):
+    """Consecutive row bands (row0, row1, wmax) over the rows of win_end with (row1 - row0) * wmax <= max_slots (at least one row),
+    wmax = the widest window of the band (at least 1): the bands gpca_ld_window is asked for, so that a kb window over a dense region
+    stays bounded."""
+    we = np.asarray(win_end, np.int64)
+    K = we.size
+    width = we - np.arange(K, dtype=np.int64) - 1
+    r0 = 0
+    while r0 < K:
+        r1, wm = r0 + 1, max(int(width[r0]), 1)
+        while r1 < K:
+            w2 = max(wm, int(width[r1]))
+            if (r1 + 1 - r0) * w2 > max_slots:
+                break
+            wm, r1 = w2, r1 + 1
+        yield r0, r1, wm
+        r0 = r1
+
+
+def ld_prune(win_end: np.ndarray, above_bands, maf: np.ndarray) -> np.ndarray:
+    """The pruning rule of --gpca-indep-pairwise.  above_bands: ((row0, row1), above) in row order, above [rows][words] uint64 as
+    gpca_ld_window writes it (or one such array for all rows).  Walk i ascending; skip i if it is out; J = the in-window j still in with
+    above(i, j), ascending; j* = the first of them with maf[j] > maf[i]; every member of J before j* (all of J if there is none) goes
+    out; if j* exists, i goes out.  So of a pair above the threshold the SNP with the smaller MAF leaves, ties the later one, and once i
+    has left its window is not looked at further.  Returns the in-set as a bool mask [K]."""
+    we = np.asarray(win_end, np.int64)
+    maf = np.asarray(maf, np.float64)
+    K = we.size
+    if maf.shape != (K,):
+        raise ValueError("ld_prune: one MAF per row of win_end")
+    if isinstance(above_bands, np.ndarray):
+        above_bands = [((0, K), above_bands)]
+    inset = np.ones(K, bool)
+    nxt = 0
+    for (r0, r1), above in above_bands:
+        if r0 != nxt:
+            raise ValueError(f"ld_prune: band [{r0}, {r1}) does not follow row {nxt}")
+        nxt = r1
+        above = np.ascontiguousarray(above, np.uint64).reshape(r1 - r0, -1) if r1 > r0 else np.zeros((0, 1), np.uint64)
+        hot = np.flatnonzero(above.any(axis=1))
+        for t in hot:
+            i = r0 + int(t)
+            if not inset[i]:
+                continue
+            bits = np.unpackbits(above[t].view(np.uint8), bitorder="little")[: max(int(we[i]) - i - 1, 0)]
+            for d in np.flatnonzero(bits):
+                j = i + 1 + int(d)
+                if not inset[j]:
+                    continue
+                if maf[j] > maf[i]:
+                    inset[i] = False
+                    break
+                inset[j] = False
+    if nxt != K:
+        raise ValueError(f"ld_prune: the bands end at row {nxt}, {K} rows need {K}")
+    return inset
+
+
+def maf_from_qc_detail(n_valid, n_het, n_hom2) -> np.ndarray:
+    """maf = min(p, 1 - p), p = (n_het + 2 n_hom2) / (2 n_valid) in f64 (0 where nothing is observed)"""
+    nv = np.asarray(n_valid, np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        p = (np.asarray(n_het, np.float64) + 2.0 * np.asarray(n_hom2, np.float64)) / (2.0 * nv)
+    p = np.where(nv > 0, p, 0.0)
+    return np.minimum(p, 1.0 - p)
+
+
+def write_prune_ids(prefix: str, variant_ids: Sequence[str], inset: np.ndarray) -> Tuple[str, str]:
+    """P.prune.in and P.prune.out: one variant ID per line, in the order given (.bim order)."""
+    if len(variant_ids) != len(inset):
+        raise ValueError("write_prune_ids: one in-set flag per variant ID")
+    paths = (f"{prefix}.prune.in", f"{prefix}.prune.out")
+    for path, want in zip(paths, (True, False)):
+        with open(path, "w") as f:
+            f.writelines(f"{variant_ids[i]}\n" for i in range(len(variant_ids)) if bool(inset[i]) == want)
+    return paths

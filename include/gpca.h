@@ -318,6 +318,33 @@ GPCA_API int gpca_grm(gpca_handle* h, int32_t scaling, int64_t row0, int64_t row
  * row holds a value outside {0, 1, 2, missing}), GPCA_ERR_OOM (the band does not fit in device memory: checked before any allocation). */
 GPCA_API int gpca_king(gpca_handle* h, int64_t row0, int64_t row1, double* kinship, int32_t* counts /* [pairs][3]; may be NULL */);
 
+/* ---- a10: windowed LD of this handle's kept rows: the unphased r^2 of plink's --indep-pairwise, SNP against the SNPs after it.
+ * Rows are addressed in PCA-SNP order (i = rank among the kept rows, the ids of gpca_standardize_block / gpca_get_pca_snp_rows;
+ * K = gpca_num_pca_snps), so windows are counted over the SNPs the run keeps.  Row i = row0 + t is paired with every j,
+ * i < j < win_end[t]; the pair's slot is d = j - i - 1.  Required: 0 <= row0 <= row1 <= K, wmax >= 1,
+ * i + 1 <= win_end[t] <= min(K, i + 1 + wmax): one primitive serves windows of a variant count, windows in kb (ragged) and chromosome
+ * boundaries (the last row of a chromosome has an empty window).  Per pair and sample, with o = [call observed] and g' = g on an
+ * observed call, 0 on a missing one:
+ *   n = sum o_i o_j,  sx = sum g'_i o_j,  sy = sum o_i g'_j,  sxx = sum g'_i^2 o_j,  syy = sum o_i g'_j^2,  sxy = sum g'_i g'_j
+ *   cov = n sxy - sx sy,  vx = n sxx - sx sx,  vy = n syy - sy sy   (exact integers in f64)
+ *   r2 = (cov cov) / (vx vy) in f64: exactly these two products and one division;  NaN when vx <= 0 or vy <= 0
+ * -- the squared Pearson correlation of the two dosage vectors over the samples observed at both SNPs.
+ * r2 [rows][wmax];  counts [rows][wmax][6] = n, sx, sy, sxx, syy, sxy;  above [rows][ceil(wmax / 64)]: bit d % 64 of word d / 64 =
+ * (r2 > threshold), NaN is not above, from the same f64 value r2 receives.  Slots outside a row's window are 0 in all three, padding
+ * bits included.  Any of the three may be NULL, not all; threshold is read only with above and must be finite then.
+ * A row band is bit-identical to the same rows of a wider call, int8 and 2-bit residency give the same bits, and so does a
+ * GPCA_PREC_F32_MFMA handle (the call reads only the genotypes and the keep mask); the sample mask is ignored and no fitted result
+ * of the handle is touched.
+ * Out of scope: streamed and row-sharded handles (a window crosses panel and shard boundaries and needs a halo of wmax rows): they
+ * return GPCA_ERR_STATE.  No r^2 table file, no phased r^2 / D'.
+ * Errors: GPCA_ERR_STATE (no standardisation, K = 0, a streamed handle, a row-sharded handle), GPCA_ERR_BAD_ARG (ranges, win_end,
+ * wmax, all outputs NULL, a non-finite threshold, 4 N >= 2^31), GPCA_ERR_INVALID_GENOTYPE (a row the call reads holds a value outside
+ * {0, 1, 2, missing}; the message names the row), GPCA_ERR_OOM (the band's buffers do not fit in device memory: checked before any
+ * allocation). */
+GPCA_API int gpca_ld_window(gpca_handle* h, int64_t row0, int64_t row1, const int64_t* win_end /* [row1 - row0] */, int32_t wmax,
+                            double threshold, double* r2 /* [rows][wmax] */, int32_t* counts /* [rows][wmax][6] */,
+                            uint64_t* above /* [rows][ceil(wmax / 64)] */);
+
 /* ---- f3: the stages of EigenSNPCoreAlgorithm::compute_pca (main.rs:311-327, 359-366) ------------------------------------------
  * The algorithm lives in the un-vendored efficient_pca crate (Cargo.toml:30, branch "main", no pinned revision): what follows is
  * the stage structure of its published description -- per-LD-block local bases learnt on a sample subset, condensed features of

@@ -101,6 +101,12 @@ public:
         if (mu.size() != M || sigma.size() != M || keep.size() != M) throw std::invalid_argument("set_standardization: need one entry per SNP row");
         check(gpca_set_standardization(h_, mu.data(), sigma.data(), keep.data()));
     }
+    // counts [M][4] = n_valid, n_hom0, n_het, n_hom2 of the last QC pass (gpca_get_snp_qc_detail)
+    std::vector<uint32_t> snp_qc_counts() const {
+        std::vector<uint32_t> c(4 * (size_t)dims().first);
+        check(gpca_get_snp_qc_detail(h_, c.data(), nullptr));
+        return c;
+    }
     int64_t num_pca_snps() const { return gpca_num_pca_snps(h_); }
     int64_t num_qc_samples() const { return gpca_num_qc_samples(h_); }
     std::vector<int64_t> pca_snp_rows() const {
@@ -173,6 +179,21 @@ public:
         k.resize(e);
         if (counts) counts->resize(3 * e);
         return k;
+    }
+    // windowed LD of kept rows [row0, row1) (gpca_ld_window): win_end has one entry per row of the band.  Each output that is not null
+    // is resized: r2 [rows][wmax], counts [rows][wmax][6], above [rows][(wmax + 63) / 64] (r2 > threshold); not all three may be null
+    void ld_window(int64_t row0, int64_t row1, const std::vector<int64_t>& win_end, int32_t wmax, double threshold, std::vector<double>* r2,
+                   std::vector<int32_t>* counts = nullptr, std::vector<uint64_t>* above = nullptr) const {
+        const size_t rows = row1 > row0 ? (size_t)(row1 - row0) : 0, w = (size_t)std::max<int32_t>(wmax, 1);
+        if (win_end.size() != rows) throw std::invalid_argument("gpca::Engine::ld_window: win_end needs one entry per row of the band");
+        if (r2) r2->assign(std::max<size_t>(rows * w, 1), 0.0);
+        if (counts) counts->assign(std::max<size_t>(6 * rows * w, 1), 0);
+        if (above) above->assign(std::max<size_t>(rows * ((w + 63) / 64), 1), 0);
+        check(gpca_ld_window(h_, row0, row1, win_end.data(), wmax, threshold, r2 ? r2->data() : nullptr, counts ? counts->data() : nullptr,
+                             above ? above->data() : nullptr));
+        if (r2) r2->resize(rows * w);
+        if (counts) counts->resize(6 * rows * w);
+        if (above) above->resize(rows * ((w + 63) / 64));
     }
 
 private:
