@@ -100,6 +100,17 @@ def build_parser() -> argparse.ArgumentParser:
                         "KING-robust kinship > X remains, the sample with the most such partners leaves (ties: the later one in .fam "
                         "order) -> P.king.cutoff.in.id / .out.id.  The PCs are fitted on the in-set and every sample is projected onto "
                         "them; SNP QC, means and s.d. stay over all samples")
+    p.add_argument("--gpca-make-pcrelate", type=int, default=None, metavar="P",
+                   help="EigenSNP workflow: also write the PC-Relate kinship of every sample pair over the kept SNPs, adjusted for the first "
+                        "P PCs of the scores this run writes (0 <= P <= --eigensnp-k-global, at most 32; 0 = the homogeneous estimator), to "
+                        "P.pcrelate.kin (#FID1 IID1 FID2 IID2 NSNP KINSHIP, ID1 the earlier sample in .fam order) and the inbreeding "
+                        "coefficients to P.pcrelate.inbreed (#FID IID NSNP F).  With --gpca-king-cutoff the regression is fitted on the "
+                        "in-set, otherwise on every sample.  Needs the matrix resident on the device")
+    p.add_argument("--gpca-pcrelate-maf-bound", type=float, default=None, metavar="T",
+                   help="--gpca-make-pcrelate: an entry counts when its individual-specific allele frequency lies in (T, 1 - T); "
+                        "0 <= T < 0.5 [default: 0.01]")
+    p.add_argument("--gpca-pcrelate-table-filter", type=float, default=None, metavar="X",
+                   help="--gpca-make-pcrelate: write only the pairs with kinship >= X (P.pcrelate.inbreed stays whole)")
     p.add_argument("--gpca-indep-pairwise", nargs=2, default=None, metavar=("WINDOW", "R2"),
                    help="EigenSNP workflow: prune SNPs in linkage disequilibrium before the GRM, KING and the PCA (plink's "
                         "--indep-pairwise with step 1).  WINDOW = a variant count such as 50 (each kept SNP against the next 49 of its "
@@ -173,11 +184,12 @@ def run_vcf_workflow(a) -> int:
     return 0
 
 
-def _load_bed(eng, a, fs, cols):
+def _load_bed(eng, a, fs, cols) -> bool:
     """The .bed payload into the engine: resident (decoded on the GPU from 256 MiB row chunks of the memory map), or -- when
     it does not fit the device, or on request -- out of core: every pass walks the memory map panel by panel through a ring
     of HBM buffers, and the HBM that is left keeps the leading panels (gpca_stream_set_cache).  The reference's solver pulls
-    strips through the accessor on every pass in the same way (prepare.rs:1839-2022, main.rs:322)."""
+    strips through the accessor on every pass in the same way (prepare.rs:1839-2022, main.rs:322).  Returns True when the matrix is
+    walked out of core."""
     from . import _lib
     from .engine import PanelSource
     rows = fs.bed_rows
@@ -203,7 +215,7 @@ def _load_bed(eng, a, fs, cols):
                 eng.upload_bed2bit(rows, fs.n_samples)
             else:
                 eng.load_from_source(PanelSource.host_i8(subset), rows.shape[0], n_samples)
-            return
+            return False
         except _lib.GpcaError as e:
             if a.gpca_stream == "off" or e.status != _lib.GPCA_ERR_OOM:
                 raise
@@ -211,6 +223,7 @@ def _load_bed(eng, a, fs, cols):
     # the memory-mapped payload itself is the source (GPCA_PANEL_MAPPED_BED): the library's copy threads stage its panels, no callback
     src = PanelSource.mapped_bed(rows) if cols is None else PanelSource.host_i8(subset)
     eng.stream_open(src, rows.shape[0], n_samples, panel_rows=a.gpca_panel_rows, cache_bytes=-1)
+    return True
 
 
 def run_eigensnp_workflow(a) -> int:
@@ -228,7 +241,8 @@ def run_eigensnp_workflow(a) -> int:
         if len(cols) == 0:
             _log("No samples available after sample QC."); return 0
         sample_ids = [fs.sample_ids[i] for i in cols]
-    _load_bed(eng, a, fs, cols)
+    if _load_bed(eng, a, fs, cols) and a.gpca_make_pcrelate is not None:
+        raise SystemExit(PCRELATE_NEEDS_RESIDENT)
     st = eng.snp_stats(QcConfig(a.eigensnp_min_call_rate, a.eigensnp_min_maf, a.eigensnp_max_hwe_p))
     blocks = gio.parse_ld_block_file(a.ld_block_file)
     keep, by_tag = gio.map_snps_to_ld_blocks(blocks, fs.chromosomes, fs.positions, st["keep"])
@@ -267,6 +281,8 @@ def run_eigensnp_workflow(a) -> int:
     k = min(cfg.target_num_global_pcs, n_fit, len(rows))
     cfg.target_num_global_pcs = k
     cfg.global_pca_sketch_oversampling = max(0, min(cfg.global_pca_sketch_oversampling, min(n_fit, len(rows)) - k))
+    if a.gpca_make_pcrelate is not None and a.gpca_make_pcrelate > k:
+        raise SystemExit(f"error: --gpca-make-pcrelate {a.gpca_make_pcrelate} asks for more PCs than the {k} this run computes")
     if inset is not None and not inset.all():
         eng.set_sample_mask(inset.astype(np.uint8))                                # the fit sees the in-set only
     out, _ = EigenSNPCoreAlgorithm(cfg).compute_pca(acc, specs, local_stage=a.gpca_eigensnp_local_stage, project_all=inset is not None)
@@ -284,6 +300,8 @@ def run_eigensnp_workflow(a) -> int:
             [fs.allele1[r] for r in rows], [fs.allele2[r] for r in rows], stz["mu"][rows], stz["sigma"][rows],
             np.asarray(out.final_snp_principal_component_loadings, np.float32), np.asarray(out.final_principal_component_eigenvalues, np.float64),
             n_fit))
+    if a.gpca_make_pcrelate is not None:
+        _pcrelate(eng, a, fs, cols, sample_ids, np.asarray(scores, np.float64)[:, :a.gpca_make_pcrelate], inset, len(rows))
     eng.close()
     _log(f"EigenSNP workflow done in {time.time() - t0:.2f}s")
     return 0
@@ -320,6 +338,32 @@ def _king(eng, a, fs, cols, sample_ids, n_snps):
     if int(inset.sum()) < 2:
         raise SystemExit("error: --gpca-king-cutoff leaves fewer than 2 samples to fit the PCA on")
     return inset
+
+
+PCRELATE_NEEDS_RESIDENT = ("error: --gpca-make-pcrelate needs the genotype matrix resident on the device: the f32 sums are not "
+                           "associative across the panels of a matrix walked out of core")
+
+
+def _pcrelate(eng, a, fs, cols, sample_ids, V, inset, n_snps):
+    """--gpca-make-pcrelate P: the bands of the PC-Relate triangle (gpca_pcrelate) into P.pcrelate.kin / P.pcrelate.inbreed.  V = the
+    first P columns of the scores the run wrote; the regression is fitted on the KING in-set when there is one, else on everyone."""
+    from . import _lib
+    fids = fs.family_ids if cols is None else [fs.family_ids[i] for i in cols]
+    n = len(sample_ids)
+    tau = 0.01 if a.gpca_pcrelate_maf_bound is None else a.gpca_pcrelate_maf_bound
+    train = None if inset is None else np.asarray(inset, bool)
+
+    def bands():
+        for b in gio.pcrelate_bands(n):
+            kin, cnt = eng.pcrelate(V, train, tau, rows=b, nsnp=True)
+            yield b, kin, cnt
+    try:
+        gio.write_pcrelate(a.output_prefix, fids, sample_ids, bands(), a.gpca_pcrelate_table_filter)
+    except _lib.GpcaError as e:
+        if e.status == _lib.GPCA_ERR_STATE:
+            raise SystemExit(PCRELATE_NEEDS_RESIDENT) from None
+        raise
+    _log(f"PC-Relate kinship of {n} samples over {n_snps} SNPs, adjusted for {V.shape[1]} PCs, written to {a.output_prefix}.pcrelate.kin")
 
 
 def _indep_pairwise(eng, a, fs, st, keep, by_tag):
@@ -395,6 +439,20 @@ def main(argv=None) -> int:
         raise SystemExit("error: --gpca-king-cutoff must lie in (0, 0.5)")
     if a.gpca_king_cutoff is not None and a.gpca_eigensnp_local_stage:
         raise SystemExit("error: --gpca-king-cutoff cannot be combined with --gpca-eigensnp-local-stage (that stage owns the sample mask)")
+    if a.gpca_make_pcrelate is None and (a.gpca_pcrelate_maf_bound is not None or a.gpca_pcrelate_table_filter is not None):
+        raise SystemExit("error: --gpca-pcrelate-maf-bound and --gpca-pcrelate-table-filter need --gpca-make-pcrelate")
+    if a.gpca_make_pcrelate is not None:
+        if not a.eigensnp:
+            raise SystemExit("error: --gpca-make-pcrelate needs the --eigensnp workflow")
+        if not 0 <= a.gpca_make_pcrelate <= min(a.eigensnp_k_global, 32):
+            raise SystemExit("error: --gpca-make-pcrelate P must lie in [0, min(--eigensnp-k-global, 32)]")
+        if a.gpca_pcrelate_maf_bound is not None and not 0.0 <= a.gpca_pcrelate_maf_bound < 0.5:
+            raise SystemExit("error: --gpca-pcrelate-maf-bound must lie in [0, 0.5)")
+        if a.gpca_eigensnp_local_stage:
+            raise SystemExit("error: --gpca-make-pcrelate cannot be combined with --gpca-eigensnp-local-stage (that stage defines no "
+                             "all-sample scores)")
+        if a.gpca_stream == "on":
+            raise SystemExit(PCRELATE_NEEDS_RESIDENT)
     if a.gpca_indep_pairwise:
         if not a.eigensnp:
             raise SystemExit("error: --gpca-indep-pairwise needs the --eigensnp workflow")

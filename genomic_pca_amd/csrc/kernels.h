@@ -331,4 +331,23 @@ void launch_ld_vec(hipStream_t st, const void* G, int packed, int64_t ldr, const
 void launch_ld_finish(hipStream_t st, const int* W, const unsigned* stat, int64_t N, int64_t row0, int64_t row1, const int64_t* win_end,
                       int wmax, double threshold, double* r2, int* counts, unsigned long long* above);
 
+// ---- PC-Relate: regression of the kept rows on the PCs, then an f32 lower-triangular SYRK over the kept rows (pcrelate.hip) ----------
+// krows [K]: original row of every kept row.  Hw [kPcrBetaWaves][N][width] f64: the hat matrix, coefficient j = wave * width + q (zero
+// columns for samples outside the training set and for j > P); train [N].  betaG [pcr_kpad(K) / 8][P + 1][8] f32 (rows past K: 0),
+// beta_rm (may be NULL) [K][P + 1]; *bad = min original row with a value outside {0, 1, 2, missing} (left as it is when there is none)
+void launch_pcrelate_beta(hipStream_t st, const void* G, int packed, int64_t ldr, const int64_t* krows, int64_t K, int64_t N,
+                          const uint8_t* train, const double* Hw, int P, float* betaG, float* beta_rm, unsigned long long* bad);
+// mu [(row1 - row0)][N] f32: the individual-specific allele frequency of kept rows [row0, row1); X [pcr_npad(N)][P + 1] f32
+void launch_pcrelate_isaf(hipStream_t st, const float* betaG, const float* X, int P, int64_t N, int64_t row0, int64_t row1, float* mu);
+// inv[n] += kept rows where sample n's entry is invalid (missing, or mu outside (tau, 1 - tau)); inv zeroed by the caller
+void launch_pcrelate_inv(hipStream_t st, const void* G, int packed, int64_t ldr, const int64_t* krows, int64_t K, int64_t N,
+                         const float* betaG, const float* X, int P, float tau, unsigned* inv);
+// tiles: (tile row, tile column) pairs of 128 x 128 output tiles, tile row >= tile column; R [2][E] f64: num, den of the band's
+// entries (diagonal included); Q [E]: kept rows where both entries are invalid
+int launch_pcrelate(hipStream_t st, const void* G, int packed, int64_t ldr, const int64_t* krows, int64_t K, int64_t N, const float* betaG,
+                    const float* X, int P, float tau, const int2* tiles, int64_t ntiles, int64_t row0, int64_t row1, double* R, int* Q, int64_t E);
+// kin [E] = num / (4 den) (NaN when nsnp = 0), nsnp (may be NULL) [E] = K - inv_a - inv_b + Q; band rows [row0, row1)
+void launch_pcrelate_finish(hipStream_t st, const double* R, const int* Q, const unsigned* inv, int64_t K, int64_t E, int64_t row0,
+                            int64_t row1, double* kin, int* nsnp);
+
 }  // namespace gpca

@@ -5,6 +5,7 @@
 #pragma once
 #include <stdint.h>
 #include <algorithm>
+#include <initializer_list>
 
 namespace gpca {
 
@@ -244,5 +245,36 @@ inline int64_t ld_stat_capacity(int64_t row0, int64_t hi) { return 3 * (hi - row
 inline int64_t ld_r2_capacity(int64_t rows, int64_t wmax) { return rows * wmax; }
 inline int64_t ld_counts_capacity(int64_t rows, int64_t wmax) { return 6 * rows * wmax; }
 inline int64_t ld_above_capacity(int64_t rows, int64_t wmax) { return rows * ld_above_words(wmax); }
+
+// ---- PC-Relate (pcrelate.hip, gpca_pcrelate.cpp) ---------------------------------------------------------------------------------
+// A workgroup owns one kPcrTile x kPcrTile tile of the sample triangle (tile row >= tile column) and walks the kept rows in stages of
+// kPcrStageRows; the f32 partial sums go to f64 running sums once per kPcrFlushRows kept rows, counted from the first kept row.
+constexpr int kPcrTile = 128, kPcrThreads = 512, kPcrStageRows = 16, kPcrFlushRows = 256, kPcrMaxPcs = 32;
+constexpr int kPcrBetaRows = 64;                     // kept rows per workgroup of the regression kernel (one lane per row)
+constexpr int kPcrBetaWaves = 4;                     // its waves split the P + 1 coefficients between them
+static_assert(kPcrFlushRows % kPcrStageRows == 0 && kPcrBetaRows % kPcrStageRows == 0 && kPcrStageRows % 8 == 0, "stage, flush group, beta block");
+inline int64_t pcr_kpad(int64_t K) { return (K + kPcrBetaRows - 1) / kPcrBetaRows * kPcrBetaRows; }
+inline int64_t pcr_npad(int64_t N) { return (N + kPcrTile - 1) / kPcrTile * kPcrTile; }
+constexpr int64_t pcr_stages(int64_t K) { return (K + kPcrStageRows - 1) / kPcrStageRows; }
+// coefficients of the hat matrix one wave of the regression kernel carries: P + 1 of them spread over kPcrBetaWaves waves, rounded up
+// to a width the kernel is instantiated for
+inline int pcr_beta_width(int P) {
+    const int w = (P + 1 + kPcrBetaWaves - 1) / kPcrBetaWaves;
+    for (int c : {1, 2, 3, 4, 6, 9}) if (w <= c) return c;
+    return 0;
+}
+// elements of the call's buffers: beta in groups of 8 rows [kpad / 8][P + 1][8] (f32) and row-major [K][P + 1]; the design rows
+// [npad][P + 1] (f32, zero past N); the hat matrix per wave of the regression kernel [waves][N][width] (f64); the invalid counts [npad]
+inline int64_t pcr_beta_capacity(int64_t K, int P) { return pcr_kpad(K) * (int64_t)(P + 1); }
+inline int64_t pcr_x_capacity(int64_t N, int P) { return pcr_npad(N) * (int64_t)(P + 1); }
+inline int64_t pcr_hat_capacity(int64_t N, int P) { return (int64_t)kPcrBetaWaves * N * pcr_beta_width(P); }
+inline int64_t pcr_inv_capacity(int64_t N) { return pcr_npad(N); }
+// the band [row0, row1) of the lower triangle with its diagonal: entries, and 128 x 128 tiles that meet it
+inline int64_t pcr_band_entries(int64_t row0, int64_t row1) { return row1 * (row1 + 1) / 2 - row0 * (row0 + 1) / 2; }
+constexpr int64_t pcr_band_index(int64_t row0, int64_t a, int64_t b) { return a * (a + 1) / 2 - row0 * (row0 + 1) / 2 + b; }
+inline int64_t pcr_tiles(int64_t row0, int64_t row1) {
+    const int64_t t0 = row0 / kPcrTile, t1 = (row1 + kPcrTile - 1) / kPcrTile;
+    return t1 * (t1 + 1) / 2 - t0 * (t0 + 1) / 2;
+}
 
 }  // namespace gpca

@@ -453,6 +453,58 @@ class GpcaEngine:
             res["above"] = out_ab[:n]
         return res
 
+    def _pcr_args(self, pcs, train):
+        N = self.dims()[1]
+        V = np.ascontiguousarray(np.zeros((N, 0)) if pcs is None else pcs, np.float64)
+        if V.ndim == 1:
+            V = V.reshape(N, 1) if V.size == N else V.reshape(N, 0)
+        if V.ndim != 2 or V.shape[0] != N:
+            raise ValueError("pcs must be [N][P]: one row of coordinates per sample")
+        t = None if train is None else np.ascontiguousarray(np.asarray(train) != 0, np.uint8)
+        if t is not None and t.shape != (N,):
+            raise ValueError("train must have one entry per sample")
+        return N, V, t
+
+    def pcrelate_isaf(self, pcs, train=None, rows: Optional[Tuple[int, int]] = None):
+        """The regression of PC-Relate (gpca_pcrelate_isaf): kept rows [row0, row1) in PCA-SNP order (default: all) regressed on
+        (1, pcs / rms) over the training samples (train: bool / uint8 [N], None = everyone).  Returns (mu [rows][N] f32: the
+        individual-specific allele frequencies, beta [rows][P + 1] f32: the coefficients the device uses)."""
+        N, V, t = self._pcr_args(pcs, train)
+        K = int(self._lib.gpca_num_pca_snps(self._h))
+        r0, r1 = (0, K) if rows is None else (int(rows[0]), int(rows[1]))
+        n = max(r1 - r0, 0)
+        mu = np.zeros((max(n, 1), N), np.float32)
+        beta = np.zeros((max(n, 1), V.shape[1] + 1), np.float32)
+        self._chk(self._lib.gpca_pcrelate_isaf(self._h, _vp(V), V.shape[1], _vp(t), r0, r1, _vp(mu), _vp(beta)))
+        return mu[:n], beta[:n]
+
+    def pcrelate(self, pcs, train=None, maf_bound: float = 0.01, rows: Optional[Tuple[int, int]] = None, nsnp: bool = False):
+        """PC-Relate kinship of the kept rows (gpca_pcrelate): pcs [N][P] (P <= 32; None or P = 0: the homogeneous estimator), train as
+        in pcrelate_isaf, maf_bound = tau: an entry counts when its call is observed and tau < mu < 1 - tau.  rows = (row0, row1): rows
+        [row0, row1) of the lower triangle WITH the diagonal packed row-major (element (a, b <= a) at a (a + 1) / 2 - row0 (row0 + 1) / 2
+        + b), f64; rows = None: the full symmetric [N][N] f64 array.  The diagonal is the self-kinship (1 + F) / 2; NaN where a pair
+        shares no valid SNP.  nsnp=True also returns the int32 count of SNPs valid in both samples, in the same shape."""
+        N, V, t = self._pcr_args(pcs, train)
+        r0, r1 = (0, N) if rows is None else (int(rows[0]), int(rows[1]))
+        E = max(r1 * (r1 + 1) // 2 - r0 * (r0 + 1) // 2, 0)
+        k = np.empty(max(E, 1), np.float64)
+        cnt = np.empty(max(E, 1), np.int32) if nsnp else None
+        self._chk(self._lib.gpca_pcrelate(self._h, _vp(V), V.shape[1], _vp(t), float(maf_bound), r0, r1, _vp(k), _vp(cnt)))
+        k = k[:E]
+        cnt = cnt[:E] if nsnp else None
+        if rows is not None:
+            return (k, cnt) if nsnp else k
+        il = np.tril_indices(N)
+        full = np.zeros((N, N), np.float64)
+        full[il] = k
+        full.T[il] = k
+        if not nsnp:
+            return full
+        fc = np.zeros((N, N), np.int32)
+        fc[il] = cnt
+        fc.T[il] = cnt
+        return full, fc
+
     # -- f3: the stages of EigenSNPCoreAlgorithm (gpca.h)
     def copy_rows_from(self, src: "GpcaEngine", row0: int, rows: int):
         """This engine receives rows [row0, row0 + rows) of src's resident matrix (device to device)."""

@@ -614,6 +614,51 @@ inline void write_king_cutoff_ids(const std::string& prefix, const std::vector<s
     }
 }
 
+// P.pcrelate.kin and P.pcrelate.inbreed (PC-Relate), written band by band from gpca_pcrelate's output (the lower triangle WITH its
+// diagonal): `#FID1 IID1 FID2 IID2 NSNP KINSHIP` per strictly lower pair (ID1 the earlier sample in .fam order), the kinship as %.6f or
+// nan, only pairs with kinship >= min_kinship if that is set; `#FID IID NSNP F` per sample, F = 2 self-kinship - 1, never filtered
+// (io.write_pcrelate).
+class PcrelateWriter {
+public:
+    PcrelateWriter(const std::string& prefix, const std::vector<std::string>& family_ids, const std::vector<std::string>& sample_ids,
+                   bool filter, double min_kinship)
+        : fids_(family_ids), iids_(sample_ids), k_(prefix + ".pcrelate.kin"), i_(prefix + ".pcrelate.inbreed"), filter_(filter), min_(min_kinship) {
+        if (fids_.size() != iids_.size()) throw std::runtime_error("write_pcrelate: one family ID per sample");
+        std::fputs("#FID1\tIID1\tFID2\tIID2\tNSNP\tKINSHIP\n", k_.f);
+        std::fputs("#FID\tIID\tNSNP\tF\n", i_.f);
+    }
+    void add_band(int64_t row0, int64_t row1, const double* kin, const int32_t* nsnp) {
+        if (row0 != next_) throw std::runtime_error("write_pcrelate: band [" + std::to_string(row0) + ", " + std::to_string(row1) + ") does not follow row " + std::to_string(next_));
+        next_ = row1;
+        size_t i = 0;
+        char num[64];
+        for (int64_t a = row0; a < row1; ++a) {
+            for (int64_t b = 0; b < a; ++b, ++i) {
+                const double v = kin[i];
+                if (filter_ && !(v >= min_)) continue;
+                fmt(num, sizeof num, v);
+                std::fprintf(k_.f, "%s\t%s\t%s\t%s\t%d\t%s\n", fids_[(size_t)b].c_str(), iids_[(size_t)b].c_str(), fids_[(size_t)a].c_str(),
+                             iids_[(size_t)a].c_str(), nsnp[i], num);
+            }
+            fmt(num, sizeof num, 2.0 * kin[i] - 1.0);
+            std::fprintf(i_.f, "%s\t%s\t%d\t%s\n", fids_[(size_t)a].c_str(), iids_[(size_t)a].c_str(), nsnp[i], num);
+            ++i;
+        }
+    }
+    void close() {
+        if (!iids_.empty() && next_ != (int64_t)iids_.size())
+            throw std::runtime_error("write_pcrelate: the bands end at row " + std::to_string(next_) + ", " + std::to_string(iids_.size()) + " samples need " + std::to_string(iids_.size()));
+    }
+
+private:
+    static void fmt(char* buf, size_t n, double v) { if (v != v) std::snprintf(buf, n, "nan"); else std::snprintf(buf, n, "%.6f", v); }
+    std::vector<std::string> fids_, iids_;
+    OutFile k_, i_;
+    bool filter_;
+    double min_;
+    int64_t next_ = 0;
+};
+
 // ---- windowed LD and LD pruning: the twins of io.parse_ld_window, io.ld_windows, io.ld_bands, io.ld_prune, io.maf_from_qc_detail and
 // io.write_prune_ids (same rules, same error texts, byte-identical files) --------------------------------------------------------
 struct LdWindow { bool bp; int64_t w; };   // bp: a span in base pairs; otherwise a count of variants (the SNP itself included)

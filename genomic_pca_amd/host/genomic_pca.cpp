@@ -48,6 +48,10 @@ struct Args {
     bool make_king = false;           // --gpca-make-king: also write P.kin0
     bool have_king_filter = false, have_king_cutoff = false;
     double king_filter = 0.0, king_cutoff = 0.0;   // --gpca-king-table-filter X, --gpca-king-cutoff X
+    bool make_pcrelate = false;       // --gpca-make-pcrelate P: also write P.pcrelate.kin / P.pcrelate.inbreed, adjusted for the first P PCs
+    int64_t pcrelate_pcs = 0;
+    bool have_pcrelate_tau = false, have_pcrelate_filter = false;
+    double pcrelate_tau = 0.01, pcrelate_filter = 0.0;   // --gpca-pcrelate-maf-bound T, --gpca-pcrelate-table-filter X
     bool have_indep = false;          // --gpca-indep-pairwise WINDOW R2: LD pruning of the kept SNPs before the GRM, KING and the PCA
     std::string indep_window, indep_r2_text;
     double indep_r2 = 0.0;
@@ -127,6 +131,16 @@ void print_help() {
         "                                       such partners leaves (ties: the later one in .fam order) -> P.king.cutoff.in.id / .out.id.\n"
         "                                       The PCs are fitted on the in-set and every sample is projected onto them; SNP QC, means\n"
         "                                       and s.d. stay over all samples\n"
+        "      --gpca-make-pcrelate <P>         EigenSNP workflow: also write the PC-Relate kinship of every sample pair over the kept\n"
+        "                                       SNPs, adjusted for the first P PCs of the scores this run writes (0 <= P <=\n"
+        "                                       --eigensnp-k-global, at most 32; 0 = the homogeneous estimator), to P.pcrelate.kin\n"
+        "                                       (#FID1 IID1 FID2 IID2 NSNP KINSHIP, ID1 the earlier sample in .fam order) and the\n"
+        "                                       inbreeding coefficients to P.pcrelate.inbreed (#FID IID NSNP F).  With --gpca-king-cutoff\n"
+        "                                       the regression is fitted on the in-set, otherwise on every sample.  Needs the matrix\n"
+        "                                       resident on the device\n"
+        "      --gpca-pcrelate-maf-bound <T>    --gpca-make-pcrelate: an entry counts when its individual-specific allele frequency\n"
+        "                                       lies in (T, 1 - T); 0 <= T < 0.5 [default: 0.01]\n"
+        "      --gpca-pcrelate-table-filter <X> --gpca-make-pcrelate: write only the pairs with kinship >= X (P.pcrelate.inbreed stays whole)\n"
         "  -h, --help                           Print help");
 }
 
@@ -197,6 +211,9 @@ Args parse(int argc, char** argv) {
         else if (f == "--gpca-make-king") a.make_king = true;
         else if (f == "--gpca-king-table-filter") { a.king_filter = to_f64(f, val()); a.have_king_filter = true; }
         else if (f == "--gpca-king-cutoff") { a.king_cutoff = to_f64(f, val()); a.have_king_cutoff = true; }
+        else if (f == "--gpca-make-pcrelate") { a.pcrelate_pcs = to_i64(f, val()); a.make_pcrelate = true; }
+        else if (f == "--gpca-pcrelate-maf-bound") { a.pcrelate_tau = to_f64(f, val()); a.have_pcrelate_tau = true; }
+        else if (f == "--gpca-pcrelate-table-filter") { a.pcrelate_filter = to_f64(f, val()); a.have_pcrelate_filter = true; }
         else if (f == "--gpca-indep-pairwise") {
             a.indep_window = val();
             if (i + 1 >= argc) usage_error("two values (WINDOW R2) are required for '" + f + "'");
@@ -274,8 +291,9 @@ extern "C" int fill_kept_columns(void* user, int64_t row0, int64_t rows, void* d
     return 0;
 }
 // The .bed payload into the engine: resident, or -- when it does not fit the device, or on request -- out of core with the
-// HBM panel cache on (cli.py:_load_bed; the reference pulls strips through the accessor on every pass, main.rs:322).
-void load_bed(gpca::Engine& eng, const Args& a, const gpca_host::PlinkFileset& fs, KeptColumns* kept) {
+// HBM panel cache on (cli.py:_load_bed; the reference pulls strips through the accessor on every pass, main.rs:322).  Returns true
+// when the matrix is walked out of core.
+bool load_bed(gpca::Engine& eng, const Args& a, const gpca_host::PlinkFileset& fs, KeptColumns* kept) {
     gpca_panel_source src;
     std::memset(&src, 0, sizeof src);
     const int64_t n_samples = kept ? (int64_t)kept->cols.size() : fs.n_samples;
@@ -303,14 +321,19 @@ void load_bed(gpca::Engine& eng, const Args& a, const gpca_host::PlinkFileset& f
         try {
             if (kept) eng.load_from_source(src, fs.n_snps, n_samples);
             else eng.upload_bed2bit(fs.bed_rows, fs.n_snps, fs.n_samples);     // the memory map goes up in 256 MiB row chunks, decoded on the GPU
-            return;
+            return false;
         } catch (const gpca::Error& e) {
             if (mode == "off" || e.status() != GPCA_ERR_OOM) throw;
             logmsg("the genotype matrix does not fit the device: walking it out of core");
         }
     }
     eng.stream_open(src, fs.n_snps, n_samples, a.panel_rows, 3, true, -1);
+    return true;
 }
+
+const char* const kPcrelateNeedsResident =
+    "error: --gpca-make-pcrelate needs the genotype matrix resident on the device: the f32 sums are not associative across the panels of a "
+    "matrix walked out of core\n";
 
 int run_eigensnp_workflow(Args a) {
     if (a.bed_file.empty() || a.ld_block_file.empty()) {
@@ -334,7 +357,7 @@ int run_eigensnp_workflow(Args a) {
         if (kept.cols.empty()) { logmsg("No samples available after sample QC."); return 0; }
         use_kept = true;
     }
-    load_bed(eng, a, fs, use_kept ? &kept : nullptr);
+    if (load_bed(eng, a, fs, use_kept ? &kept : nullptr) && a.make_pcrelate) { std::fputs(kPcrelateNeedsResident, stderr); return 1; }
     const gpca::SnpStats st = eng.snp_stats(gpca::QcConfig{a.min_call_rate, a.min_maf, a.max_hwe_p});
     const auto blocks = gpca_host::parse_ld_block_file(a.ld_block_file);
     std::vector<uint8_t> keep;
@@ -483,6 +506,10 @@ int run_eigensnp_workflow(Args a) {
     cfg.local_rsvd_sketch_oversampling = (int)a.local_oversampling; cfg.local_rsvd_num_power_iterations = (int)a.local_power_iter;
     cfg.random_seed = a.seed; cfg.snp_processing_strip_size = a.strip_size; cfg.refine_pass_count = (int)a.refine_passes;
     cfg.collect_diagnostics = a.collect_diagnostics;
+    if (a.make_pcrelate && a.pcrelate_pcs > k) {
+        std::fprintf(stderr, "error: --gpca-make-pcrelate %lld asks for more PCs than the %lld this run computes\n", (long long)a.pcrelate_pcs, (long long)k);
+        return 1;
+    }
     if (!inset.empty() && n_fit < (int64_t)inset.size()) eng.set_sample_mask(&inset);      // the fit sees the in-set only
     // with the cutoff every sample is projected onto the in-set's PCs (the relatives included), inside compute_pca while the fit is valid
     const gpca::EigenSNPCoreOutput out = gpca::EigenSNPCoreAlgorithm(cfg).compute_pca(acc, specs, a.local_stage, !inset.empty());
@@ -510,6 +537,37 @@ int run_eigensnp_workflow(Args a) {
         m.loadings.assign(out.final_snp_principal_component_loadings.begin(), out.final_snp_principal_component_loadings.begin() + rows.size() * (size_t)kc);
         m.eigenvalues = out.final_principal_component_eigenvalues;
         gpca_host::write_model(a.output_prefix, m);
+    }
+    if (a.make_pcrelate) {
+        // the bands of the PC-Relate triangle into P.pcrelate.kin / P.pcrelate.inbreed: V = the first P columns of the scores written above,
+        // the regression fitted on the KING in-set when there is one, else on everyone (cli.py:_pcrelate)
+        std::vector<std::string> fids = fs.family_ids;
+        if (use_kept) { fids.clear(); for (int64_t c : kept.cols) fids.push_back(fs.family_ids[(size_t)c]); }
+        const int64_t n = (int64_t)sample_ids.size();
+        const int32_t P = (int32_t)a.pcrelate_pcs;
+        std::vector<double> V((size_t)n * (size_t)P + 1);
+        for (int64_t s = 0; s < n; ++s)
+            for (int32_t c = 0; c < P; ++c)
+                V[(size_t)s * P + c] = inset.empty() ? (double)out.final_sample_principal_component_scores[(size_t)s * kc + c] : projected[(size_t)s * kc + c];
+        gpca_host::PcrelateWriter w(a.output_prefix, fids, sample_ids, a.have_pcrelate_filter, a.pcrelate_filter);
+        try {
+            for (int64_t r0 = 0; r0 < n;) {      // row bands of at most 2^26 entries (at least one row), as io.pcrelate_bands cuts them
+                int64_t r1 = r0 + 1;
+                while (r1 < n && (r1 + 1) * (r1 + 2) / 2 - r0 * (r0 + 1) / 2 <= ((int64_t)1 << 26)) ++r1;
+                std::vector<int32_t> cnt;
+                const std::vector<double> kin = eng.pcrelate(V, P, inset.empty() ? nullptr : &inset, a.pcrelate_tau, r0, r1, &cnt);
+                w.add_band(r0, r1, kin.data(), cnt.data());
+                r0 = r1;
+            }
+        } catch (const gpca::Error& e) {
+            if (e.status() != GPCA_ERR_STATE) throw;
+            std::fputs(kPcrelateNeedsResident, stderr);
+            return 1;
+        }
+        w.close();
+        std::snprintf(buf, sizeof buf, "PC-Relate kinship of %lld samples over %zu SNPs, adjusted for %d PCs, written to %s.pcrelate.kin", (long long)n,
+                      rows.size(), (int)P, a.output_prefix.c_str());
+        logmsg(buf);
     }
     std::snprintf(buf, sizeof buf, "EigenSNP workflow done in %.2fs", seconds_since(t0));
     logmsg(buf);
@@ -568,6 +626,23 @@ int main(int argc, char** argv) {
         if (a.have_king_cutoff && a.local_stage) {
             std::fprintf(stderr, "error: --gpca-king-cutoff cannot be combined with --gpca-eigensnp-local-stage (that stage owns the sample mask)\n");
             return 2;
+        }
+        if (!a.make_pcrelate && (a.have_pcrelate_tau || a.have_pcrelate_filter)) {
+            std::fprintf(stderr, "error: --gpca-pcrelate-maf-bound and --gpca-pcrelate-table-filter need --gpca-make-pcrelate\n");
+            return 2;
+        }
+        if (a.make_pcrelate) {
+            if (!a.eigensnp) { std::fprintf(stderr, "error: --gpca-make-pcrelate needs the --eigensnp workflow\n"); return 2; }
+            if (!(a.pcrelate_pcs >= 0 && a.pcrelate_pcs <= std::min<int64_t>(a.k_global, 32))) {
+                std::fprintf(stderr, "error: --gpca-make-pcrelate P must lie in [0, min(--eigensnp-k-global, 32)]\n");
+                return 2;
+            }
+            if (!(a.pcrelate_tau >= 0.0 && a.pcrelate_tau < 0.5)) { std::fprintf(stderr, "error: --gpca-pcrelate-maf-bound must lie in [0, 0.5)\n"); return 2; }
+            if (a.local_stage) {
+                std::fprintf(stderr, "error: --gpca-make-pcrelate cannot be combined with --gpca-eigensnp-local-stage (that stage defines no all-sample scores)\n");
+                return 2;
+            }
+            if (a.stream == "on") { std::fputs(kPcrelateNeedsResident, stderr); return 2; }
         }
         if (!a.project_model.empty()) return run_project_workflow(a);
         if (a.save_model && !a.eigensnp) { std::fprintf(stderr, "error: --gpca-save-model needs the --eigensnp workflow\n"); return 2; }

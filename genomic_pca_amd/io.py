@@ -524,6 +524,57 @@ def write_king_cutoff_ids(prefix: str, family_ids: Sequence[str], sample_ids: Se
     return paths
 
 
+# ------------------------------------------------------------------------------------------------ PC-Relate kinship
+PCRELATE_KIN_HEADER = "#FID1\tIID1\tFID2\tIID2\tNSNP\tKINSHIP\n"
+PCRELATE_INBREED_HEADER = "#FID\tIID\tNSNP\tF\n"
+
+
+def pcrelate_bands(n: int, max_pairs: int = 1 << 26):
+    """Consecutive row bands [row0, row1) of an n-sample lower triangle WITH its diagonal (row a holds a + 1 entries), each of at most
+    max_pairs entries (at least one row): the bands gpca_pcrelate is asked for, one at a time."""
+    r0 = 0
+    while r0 < n:
+        r1 = r0 + 1
+        while r1 < n and (r1 + 1) * (r1 + 2) // 2 - r0 * (r0 + 1) // 2 <= max_pairs:
+            r1 += 1
+        yield r0, r1
+        r0 = r1
+
+
+def write_pcrelate(prefix: str, family_ids: Sequence[str], sample_ids: Sequence[str], bands, min_kinship: Optional[float] = None) -> Tuple[str, str]:
+    """P.pcrelate.kin: one tab-separated line per strictly lower pair, `FID1 IID1 FID2 IID2 NSNP KINSHIP`, ID1 the earlier sample in .fam
+    order, the kinship as %.6f (or nan); P.pcrelate.inbreed: `FID IID NSNP F` per sample, F = 2 self-kinship - 1 from the diagonal.
+    bands: ((row0, row1), kinship, nsnp) in row order (gpca_pcrelate's output: the lower triangle with its diagonal), written as they
+    come.  min_kinship (the table filter): only pairs with kinship >= it (NaN never passes); the inbreeding file is not filtered."""
+    n = len(sample_ids)
+    if len(family_ids) != n:
+        raise ValueError("write_pcrelate: one family ID per sample")
+    paths = (f"{prefix}.pcrelate.kin", f"{prefix}.pcrelate.inbreed")
+    nxt = 0
+    with open(paths[0], "w") as f, open(paths[1], "w") as fi:
+        f.write(PCRELATE_KIN_HEADER)
+        fi.write(PCRELATE_INBREED_HEADER)
+        for (r0, r1), kin, cnt in bands:
+            if r0 != nxt:
+                raise ValueError(f"write_pcrelate: band [{r0}, {r1}) does not follow row {nxt}")
+            nxt = r1
+            kin = np.asarray(kin, np.float64).ravel()
+            cnt = np.asarray(cnt).ravel()
+            need = r1 * (r1 + 1) // 2 - r0 * (r0 + 1) // 2
+            if kin.size != need or cnt.size != need:
+                raise ValueError(f"write_pcrelate: band [{r0}, {r1}) needs {need} entries")
+            o = 0
+            for a in range(r0, r1):
+                row_k, row_c = kin[o:o + a], cnt[o:o + a]
+                sel = np.flatnonzero(row_k >= min_kinship) if min_kinship is not None else range(a)
+                f.writelines(f"{family_ids[b]}\t{sample_ids[b]}\t{family_ids[a]}\t{sample_ids[a]}\t{row_c[b]}\t{_fmt_kin(row_k[b])}\n" for b in sel)
+                fi.write(f"{family_ids[a]}\t{sample_ids[a]}\t{cnt[o + a]}\t{_fmt_kin(2.0 * kin[o + a] - 1.0)}\n")
+                o += a + 1
+    if nxt != n and n > 0:
+        raise ValueError(f"write_pcrelate: the bands end at row {nxt}, {n} samples need {n}")
+    return paths
+
+
 # ------------------------------------------------------------------------------------------------ windowed LD and LD pruning
 def parse_ld_window(text: str) -> Tuple[str, int]:
     """The WINDOW of --gpca-indep-pairwise: "50" -> ("variants", 50): each SNP against the next 49 kept SNPs of its chromosome run

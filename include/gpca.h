@@ -345,6 +345,36 @@ GPCA_API int gpca_ld_window(gpca_handle* h, int64_t row0, int64_t row1, const in
                             double threshold, double* r2 /* [rows][wmax] */, int32_t* counts /* [rows][wmax][6] */,
                             uint64_t* above /* [rows][ceil(wmax / 64)] */);
 
+/* ---- a11: PC-Relate (Conomos et al. 2016): kinship and inbreeding with the ancestry taken out, from this handle's kept rows (K of
+ * them, in PCA-SNP order) and P <= 32 caller-supplied sample coordinates V [N][P] (f64; normally the fitted or projected scores).
+ * train [N] (NULL = everyone): the samples the regression is fitted on (normally the KING in-set).  g = the call, o = [observed].
+ *  1. design and hat matrix (host, f64): x_n = (1, V_n1 / c_1, ..., V_nP / c_P), c_j = the root mean square of column j over the
+ *     training samples; H = (X^T X)^-1 X^T over the training samples by Cholesky, 0 for the other samples.
+ *  2. beta_i = sum_train H_n g'_in + mbar_i sum_train H_n (1 - o_in), mbar_i = the mean of row i's observed training calls (missing
+ *     training calls are imputed to it); accumulated in f64, rounded once to f32, [K][P + 1].  A row with no observed training call
+ *     gets beta = 0 and every entry of it is invalid.
+ *  3. mu_in = 0.5f * (fmaf chain over j = 0 .. P of beta_ij * (float)x_nj, from 0), in f32;  valid_in = o_in and tau_f < mu_in and
+ *     mu_in < 1.0f - tau_f, tau_f = (float)tau.  P = 0: mu_in = mbar_i / 2, the homogeneous estimator.
+ *  4. r = valid (g - 2 mu), s = valid sqrt(mu (1 - mu)) in f32;  num_ab = sum_i r_ia r_ib, den_ab = sum_i s_ia s_ib on
+ *     v_mfma_f32_32x32x2_f32 (bit for bit an fmaf chain over the kept rows), flushed to f64 running sums every 256 kept rows counted
+ *     from the first;  nsnp_ab = sum_i valid_ia valid_ib (exact);  kinship_ab = num_ab / (4 den_ab) in f64, NaN when nsnp_ab = 0.
+ *     The diagonal is the self-kinship (1 + F_a) / 2.
+ * gpca_pcrelate_isaf: mu [rows][N] and / or beta [rows][P + 1] of kept rows [row0, row1), 0 <= row0 <= row1 <= K (either may be NULL,
+ *   not both).  gpca_pcrelate: rows row0 <= a < row1 of the lower triangle WITH the diagonal in gpca_grm's packing: element (a, b <= a)
+ *   at a (a + 1) / 2 - row0 (row0 + 1) / 2 + b; nsnp (may be NULL) in the same packing.  0 <= tau < 0.5.
+ * A band is bit-identical to the same rows of the full call; int8 and 2-bit residency give the same bits, and so does a
+ * GPCA_PREC_F32_MFMA handle (the calls read only the genotypes and the keep mask); the sample mask is ignored and no fitted result is
+ * touched.  Out of scope: the small-sample scale correction of GENESIS, the k0 / k2 IBD-sharing estimates, and streamed and
+ * row-sharded handles (the f32 / f64 sums are not associative across panels or ranks): GPCA_ERR_STATE.
+ * Errors: GPCA_ERR_STATE (no standardisation, K = 0, a streamed handle, a row-sharded handle), GPCA_ERR_BAD_ARG (P outside [0, 32],
+ * fewer than P + 2 training samples, a non-finite V entry, a zero or collinear column of V on the training samples, tau, the row
+ * range, K >= 2^31), GPCA_ERR_INVALID_GENOTYPE (a kept row holds a value outside {0, 1, 2, missing}; the message names the row),
+ * GPCA_ERR_OOM (the band and the regression's workspace do not fit in device memory: checked before any allocation). */
+GPCA_API int gpca_pcrelate_isaf(gpca_handle* h, const double* V /* [N][P] */, int32_t P, const uint8_t* train /* [N] or NULL */, int64_t row0,
+                                int64_t row1, float* mu /* [rows][N] or NULL */, float* beta /* [rows][P + 1] or NULL */);
+GPCA_API int gpca_pcrelate(gpca_handle* h, const double* V /* [N][P] */, int32_t P, const uint8_t* train /* [N] or NULL */, double tau,
+                           int64_t row0, int64_t row1, double* kinship, int32_t* nsnp /* may be NULL */);
+
 /* ---- f3: the stages of EigenSNPCoreAlgorithm::compute_pca (main.rs:311-327, 359-366) ------------------------------------------
  * The algorithm lives in the un-vendored efficient_pca crate (Cargo.toml:30, branch "main", no pinned revision): what follows is
  * the stage structure of its published description -- per-LD-block local bases learnt on a sample subset, condensed features of

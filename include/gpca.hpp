@@ -195,6 +195,28 @@ public:
         if (counts) counts->resize(6 * rows * w);
         if (above) above->resize(rows * ((w + 63) / 64));
     }
+    // PC-Relate (gpca_pcrelate): rows [row0, row1) of the lower triangle WITH the diagonal of the ancestry-adjusted kinship, packed as
+    // grm packs it; V [N][P] sample coordinates, train (may be null: everyone) [N]; nsnp (may be null) receives the SNPs valid in both
+    std::vector<double> pcrelate(const std::vector<double>& V, int32_t P, const std::vector<uint8_t>* train, double tau, int64_t row0,
+                                 int64_t row1, std::vector<int32_t>* nsnp = nullptr) const {
+        const size_t e = row1 > row0 ? (size_t)(row1 * (row1 + 1) / 2 - row0 * (row0 + 1) / 2) : 0;
+        std::vector<double> k(std::max<size_t>(e, 1));
+        if (nsnp) nsnp->assign(std::max<size_t>(e, 1), 0);
+        check(gpca_pcrelate(h_, V.data(), P, train ? train->data() : nullptr, tau, row0, row1, k.data(), nsnp ? nsnp->data() : nullptr));
+        k.resize(e);
+        if (nsnp) nsnp->resize(e);
+        return k;
+    }
+    // the regression behind it (gpca_pcrelate_isaf) for kept rows [row0, row1): mu [rows][N] and / or beta [rows][P + 1], not both null
+    void pcrelate_isaf(const std::vector<double>& V, int32_t P, const std::vector<uint8_t>* train, int64_t row0, int64_t row1, int64_t n_samples,
+                       std::vector<float>* mu, std::vector<float>* beta = nullptr) const {
+        const size_t rows = row1 > row0 ? (size_t)(row1 - row0) : 0;
+        if (mu) mu->assign(std::max<size_t>(rows * (size_t)n_samples, 1), 0.0f);
+        if (beta) beta->assign(std::max<size_t>(rows * (size_t)(P + 1), 1), 0.0f);
+        check(gpca_pcrelate_isaf(h_, V.data(), P, train ? train->data() : nullptr, row0, row1, mu ? mu->data() : nullptr, beta ? beta->data() : nullptr));
+        if (mu) mu->resize(rows * (size_t)n_samples);
+        if (beta) beta->resize(rows * (size_t)(P + 1));
+    }
 
 private:
     gpca_handle* h_ = nullptr;
