@@ -117,6 +117,21 @@ def build_parser() -> argparse.ArgumentParser:
                         "chromosome) or a span such as 250kb; 0 < R2 < 1.  Of a pair of kept SNPs with unphased r^2 > R2 the one with the "
                         "smaller minor-allele frequency leaves (ties: the later one) -> P.prune.in / P.prune.out.  Needs the matrix "
                         "resident on the device; plink's exact output is not claimed")
+    p.add_argument("--gpca-assoc-pheno", default=None, metavar="FILE",
+                   help="EigenSNP workflow: after everything else is written, test every SNP that passes the SNP QC (call rate, MAF, HWE; "
+                        "the LD blocks and --gpca-indep-pairwise shape the PCA, not the test set) against every trait column of FILE "
+                        "(header `FID IID name...`, NA = missing) by least squares with the PCs as covariates, a missing call imputed to "
+                        "the SNP's mean -> P.<trait>.assoc.linear (#CHROM POS ID A1 OBS_CT A1_FREQ BETA SE T_STAT LOG10P).  A sample "
+                        "counts when every trait and covariate is present for it and, with --gpca-king-cutoff, it is in the in-set.  "
+                        "Needs the matrix resident on the device; traits + PCs + covariates <= 64")
+    p.add_argument("--gpca-assoc-pcs", type=int, default=None, metavar="P",
+                   help="--gpca-assoc-pheno: the first P columns of the scores this run writes are covariates (0 <= P <= "
+                        "--eigensnp-k-global) [default: every column]")
+    p.add_argument("--gpca-assoc-covar", default=None, metavar="FILE",
+                   help="--gpca-assoc-pheno: further covariates, a table in the format of the phenotype file")
+    p.add_argument("--gpca-assoc-vif", type=float, default=None, metavar="X",
+                   help="--gpca-assoc-pheno: a SNP whose variance inflation against the covariates exceeds X gets NA (plink's --vif) "
+                        "[default: 50]")
     return p
 
 
@@ -241,8 +256,11 @@ def run_eigensnp_workflow(a) -> int:
         if len(cols) == 0:
             _log("No samples available after sample QC."); return 0
         sample_ids = [fs.sample_ids[i] for i in cols]
-    if _load_bed(eng, a, fs, cols) and a.gpca_make_pcrelate is not None:
+    streamed = _load_bed(eng, a, fs, cols)
+    if streamed and a.gpca_make_pcrelate is not None:
         raise SystemExit(PCRELATE_NEEDS_RESIDENT)
+    if streamed and a.gpca_assoc_pheno is not None:
+        raise SystemExit(ASSOC_NEEDS_RESIDENT)
     st = eng.snp_stats(QcConfig(a.eigensnp_min_call_rate, a.eigensnp_min_maf, a.eigensnp_max_hwe_p))
     blocks = gio.parse_ld_block_file(a.ld_block_file)
     keep, by_tag = gio.map_snps_to_ld_blocks(blocks, fs.chromosomes, fs.positions, st["keep"])
@@ -283,6 +301,8 @@ def run_eigensnp_workflow(a) -> int:
     cfg.global_pca_sketch_oversampling = max(0, min(cfg.global_pca_sketch_oversampling, min(n_fit, len(rows)) - k))
     if a.gpca_make_pcrelate is not None and a.gpca_make_pcrelate > k:
         raise SystemExit(f"error: --gpca-make-pcrelate {a.gpca_make_pcrelate} asks for more PCs than the {k} this run computes")
+    if a.gpca_assoc_pcs is not None and a.gpca_assoc_pcs > k:
+        raise SystemExit(f"error: --gpca-assoc-pcs {a.gpca_assoc_pcs} asks for more PCs than the {k} this run computes")
     if inset is not None and not inset.all():
         eng.set_sample_mask(inset.astype(np.uint8))                                # the fit sees the in-set only
     out, _ = EigenSNPCoreAlgorithm(cfg).compute_pca(acc, specs, local_stage=a.gpca_eigensnp_local_stage, project_all=inset is not None)
@@ -302,6 +322,8 @@ def run_eigensnp_workflow(a) -> int:
             n_fit))
     if a.gpca_make_pcrelate is not None:
         _pcrelate(eng, a, fs, cols, sample_ids, np.asarray(scores, np.float64)[:, :a.gpca_make_pcrelate], inset, len(rows))
+    if a.gpca_assoc_pheno is not None:
+        _assoc(eng, a, fs, cols, sample_ids, np.asarray(scores, np.float64), inset, st)
     eng.close()
     _log(f"EigenSNP workflow done in {time.time() - t0:.2f}s")
     return 0
@@ -364,6 +386,76 @@ def _pcrelate(eng, a, fs, cols, sample_ids, V, inset, n_snps):
             raise SystemExit(PCRELATE_NEEDS_RESIDENT) from None
         raise
     _log(f"PC-Relate kinship of {n} samples over {n_snps} SNPs, adjusted for {V.shape[1]} PCs, written to {a.output_prefix}.pcrelate.kin")
+
+
+ASSOC_NEEDS_RESIDENT = ("error: --gpca-assoc-pheno needs the genotype matrix resident on the device: the scan of a matrix walked out of "
+                        "core is not implemented")
+ASSOC_MAX_COLUMNS = 64
+
+
+def _assoc_tables(a):
+    """The phenotype and covariate tables of --gpca-assoc-pheno / --gpca-assoc-covar, read once before any work on the device; refuses
+    more than 64 columns (traits + PCs + covariates).  Returns (pheno, covar or None)."""
+    def table(flag, path):
+        try:
+            return gio.read_pheno(path)
+        except OSError:
+            raise SystemExit(f"error: {flag}: cannot open {path}") from None
+        except ValueError as e:
+            raise SystemExit(f"error: {flag}: {e}") from None
+    pheno = table("--gpca-assoc-pheno", a.gpca_assoc_pheno)
+    covar = None if a.gpca_assoc_covar is None else table("--gpca-assoc-covar", a.gpca_assoc_covar)
+    t, c = len(pheno.names), 0 if covar is None else len(covar.names)
+    p = a.eigensnp_k_global if a.gpca_assoc_pcs is None else a.gpca_assoc_pcs
+    if t + p + c > ASSOC_MAX_COLUMNS:
+        raise SystemExit(f"error: --gpca-assoc-pheno: {t} traits + {p} PCs + {c} covariates are more than {ASSOC_MAX_COLUMNS} columns")
+    return pheno, covar
+
+
+def _assoc(eng, a, fs, cols, sample_ids, scores, inset, st):
+    """--gpca-assoc-pheno FILE: the linear association scan (gpca_assoc_linear) of every SNP that passes the SNP QC, in row bands, into
+    P.<trait>.assoc.linear.  Runs last: it resets the keep mask to the QC mask (mu, sigma unchanged), which ends the fit's validity.
+    Covariates = the first P columns of the scores the run wrote, then the columns of --gpca-assoc-covar; a sample is included when
+    every trait and covariate is present for it and it is in the KING in-set, when there is one."""
+    from . import _lib
+    pheno, covar = a.gpca_assoc_tables
+    fids = fs.family_ids if cols is None else [fs.family_ids[i] for i in cols]
+    n = len(sample_ids)
+    P = scores.shape[1] if a.gpca_assoc_pcs is None else a.gpca_assoc_pcs
+    Y = gio.align_pheno(pheno, fids, sample_ids)
+    C = scores[:, :P]
+    if covar is not None:
+        C = np.hstack([C, gio.align_pheno(covar, fids, sample_ids)])
+    C = np.ascontiguousarray(C, np.float64)
+    T, Pc = Y.shape[1], C.shape[1]
+    include = np.isfinite(Y).all(1) & np.isfinite(C).all(1)
+    if inset is not None:
+        include &= np.asarray(inset, bool)
+    n_inc = int(include.sum())
+    df = n_inc - Pc - 2
+    if df < 1:
+        raise SystemExit(f"error: --gpca-assoc-pheno: {n_inc} samples have every trait and covariate, which leaves no degree of freedom "
+                         f"beside {Pc} covariates")
+    vif = 50.0 if a.gpca_assoc_vif is None else a.gpca_assoc_vif
+    eng.set_standardization(st["mu"], st["sigma"], st["keep"])                       # every SNP that passes the SNP QC
+    rows = np.flatnonzero(st["keep"])
+    lib = _lib.load()
+    try:
+        for bi, (r0, r1) in enumerate(gio.assoc_bands(len(rows), T + Pc)):
+            r = eng.assoc_linear(Y, C, include=include, max_vif=vif, rows=(r0, r1))
+            rr = rows[r0:r1]
+            meta = ([fs.chromosomes[i] for i in rr], [int(fs.positions[i]) for i in rr], [fs.variant_ids[i] for i in rr],
+                    [fs.allele1[i] for i in rr])
+            for t, name in enumerate(pheno.names):
+                tt = r["t"][:, t]
+                lp = [float("nan") if v != v else lib.gpca_student_t_log10p(float(v), float(df)) for v in tt]
+                gio.write_assoc(a.output_prefix, name, *meta, r["n_obs"], r["a1_freq"], r["beta"][:, t], r["se"][:, t], tt, lp, append=bi > 0)
+    except _lib.GpcaError as e:
+        if e.status == _lib.GPCA_ERR_STATE:
+            raise SystemExit(ASSOC_NEEDS_RESIDENT) from None
+        raise
+    _log(f"association scan of {len(rows)} SNPs against {T} traits with {Pc} covariates ({P} PCs) on {n_inc} of {n} samples, written to "
+         f"{a.output_prefix}.<trait>.assoc.linear")
 
 
 def _indep_pairwise(eng, a, fs, st, keep, by_tag):
@@ -453,6 +545,21 @@ def main(argv=None) -> int:
                              "all-sample scores)")
         if a.gpca_stream == "on":
             raise SystemExit(PCRELATE_NEEDS_RESIDENT)
+    if a.gpca_assoc_pheno is None and (a.gpca_assoc_pcs is not None or a.gpca_assoc_covar is not None or a.gpca_assoc_vif is not None):
+        raise SystemExit("error: --gpca-assoc-pcs, --gpca-assoc-covar and --gpca-assoc-vif need --gpca-assoc-pheno")
+    if a.gpca_assoc_pheno is not None:
+        if not a.eigensnp:
+            raise SystemExit("error: --gpca-assoc-pheno needs the --eigensnp workflow")
+        if a.gpca_assoc_pcs is not None and not 0 <= a.gpca_assoc_pcs <= a.eigensnp_k_global:
+            raise SystemExit("error: --gpca-assoc-pcs P must lie in [0, --eigensnp-k-global]")
+        if a.gpca_assoc_vif is not None and not (1.0 <= a.gpca_assoc_vif < float("inf")):
+            raise SystemExit("error: --gpca-assoc-vif must be finite and at least 1")
+        if a.gpca_eigensnp_local_stage:
+            raise SystemExit("error: --gpca-assoc-pheno cannot be combined with --gpca-eigensnp-local-stage (that stage defines no "
+                             "all-sample scores)")
+        if a.gpca_stream == "on":
+            raise SystemExit(ASSOC_NEEDS_RESIDENT)
+        a.gpca_assoc_tables = _assoc_tables(a)
     if a.gpca_indep_pairwise:
         if not a.eigensnp:
             raise SystemExit("error: --gpca-indep-pairwise needs the --eigensnp workflow")

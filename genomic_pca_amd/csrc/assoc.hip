@@ -1,0 +1,274 @@
+// Linear association scan (gpca_assoc_linear; gpca_assoc.cpp): ordinary least squares of T traits on (1, C, g) for every kept row g,
+// a missing call imputed to the row's mean over the included samples.
+//
+// The host hands over B = [Y~ | Q] (N x L, L = T + Pc <= 64, f32; every column sums to 0 over the included samples and is 0 outside
+// them), transposed and zero-padded to [asc_lpad(L)][asc_npad(N)], and the include mask as one bit per sample.  With o = [observed and
+// included], g' = g o:
+//     n_obs = sum o,  s1 = sum g',  s2 = sum g'^2          (exact integers, counted while the calls are staged)
+//     d_ij = sum_n g'_in B_nj,   e_ij = sum_n [missing and included]_in B_nj
+// k_assoc: a workgroup owns kAscRows = 128 kept rows x all columns, 4 waves of 32 rows x lpad columns, and walks the samples in stages
+// of kAscStage = 64.  A stage in LDS is the calls as bytes [row][sample] (0, 1, 2 or the missing code; an excluded sample and a sample
+// past N are 0) and the panel of B^T [column][sample]; a lane reads 8 consecutive samples of its row (ds_read_b64) and of its column
+// (2 x ds_read_b128) and turns the bytes into the f32 operands g' and [missing] in registers, so every product of the
+// v_mfma_f32_32x32x2_f32 is exact.  The 16 samples of a group of 8 multiplies are taken as (i, 8 + i), i = 0 .. 7: the order is a
+// function of the sample index alone.  e is multiplied only in 16-sample groups where a wave ballot finds a missing call.  Two LDS
+// buffers: the waves multiply stage s from one while stage s + 1 (loaded during stage s - 1) is written to the other and stage s + 2 is
+// requested, one barrier per stage.  Every kAscFlush = 256 samples, counted from sample 0, the f32 accumulators are added to f64
+// running sums held in registers.  No split of the sample axis, no atomics: a row's sums depend on the row and on N alone, so a band
+// gives the bits of the full call and int8 and 2-bit residency (the same bytes in LDS) give the same bits.
+// Registers, lpad = 64: d and e each hold 2 x 16 f32 accumulators and 2 x 16 f64 running sums = 96 registers, 192 for both; with the
+// prefetch of a stage (8 of calls + 16 of B) and the operands of a group (16 + 16) the compiler takes 256 VGPRs + 122 AGPRs of the
+// 512 a wave of a 256-thread workgroup may use (no spill): one wave per SIMD.  lpad = 32 halves the sums: 158 + 32, two waves.
+// Epilogue (f64, no contraction): mbar = s1 / n_obs, xb_ij = d_ij + mbar * e_ij.  k_assoc_finish (one thread per row): xx = s2 - s1 *
+// mbar, sxx = xx - sum_{j >= T} xb_ij^2 (j ascending), and per trait beta = xb / sxx, rss = yy - xb * beta, se = sqrt(rss / df / sxx),
+// t = beta / se; NaN when n_obs = 0, xx <= 0, sxx * max_vif < xx or rss <= 0.
+// Out of scope: logistic regression and case / control traits, per-variant dropping of samples with a missing call, per-trait sample
+// sets, mixed models that use the GRM, streamed and row-sharded handles.
+#include "gemm_i8_common.h"
+
+#pragma clang fp contract(off)
+
+namespace gpca {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr unsigned kAscMissing = 0x81u;             // the int8 missing code (-127) as a byte
+
+// the 32 samples a thread stages: 8 dwords of call bytes (int8 storage: as stored; 2-bit: decoded, 3 -> the missing code)
+struct AscFetch { unsigned w[8]; };
+
+template <bool PACKED>
+__device__ __forceinline__ void asc_fetch(AscFetch& F, const uint8_t* __restrict__ G, int64_t ldr, int64_t orow, int64_t ns) {
+    if (orow < 0) {
+#pragma unroll
+        for (int d = 0; d < 8; ++d) F.w[d] = 0u;
+        return;
+    }
+    if (PACKED) {
+        // (ns is a multiple of 32 and ld2 of 256: the 8 bytes are aligned and inside the row's pitch, see asc_* in plan_math.h)
+        const uint2 v = *reinterpret_cast<const uint2*>(G + orow * ldr + (ns >> 2));
+#pragma unroll
+        for (int d = 0; d < 8; ++d) {
+            const unsigned b = ((d < 4 ? v.x : v.y) >> (8 * (d & 3))) & 0xffu;
+            const unsigned dd = (b & 3u) | ((b & 0xcu) << 6) | ((b & 0x30u) << 12) | ((b & 0xc0u) << 18);
+            const unsigned m = dd & (dd >> 1) & 0x01010101u;
+            F.w[d] = (dd & ~(m * 3u)) | (m * kAscMissing);
+        }
+    } else {
+        const uint4 a = *reinterpret_cast<const uint4*>(G + orow * ldr + ns);
+        const uint4 b = *reinterpret_cast<const uint4*>(G + orow * ldr + ns + 16);
+        F.w[0] = a.x; F.w[1] = a.y; F.w[2] = a.z; F.w[3] = a.w; F.w[4] = b.x; F.w[5] = b.y; F.w[6] = b.z; F.w[7] = b.w;
+    }
+}
+
+// checks, masks and counts the thread's 32 samples and writes them to the stage's buffer.  inb: bit s = sample s lies below N;
+// inc: bit s = sample s is included (zero past N).
+__device__ __forceinline__ void asc_put(const AscFetch& F, unsigned inb, unsigned inc, uint8_t* dst, unsigned& nobs, unsigned& s1,
+                                        unsigned& s2, unsigned& bd) {
+    unsigned o[8];
+#pragma unroll
+    for (int d = 0; d < 8; ++d) {
+        const unsigned vb = (((inb >> (4 * d)) & 0xfu) * 0x00204081u & 0x01010101u) * 0xffu;
+        const unsigned ib = (((inc >> (4 * d)) & 0xfu) * 0x00204081u & 0x01010101u) * 0xffu;
+        const unsigned a = F.w[d] & vb;
+        // valid bytes: 0, 1, 2 and the missing code
+        const unsigned m = (a >> 7) & 0x01010101u, g = a & ~(m * 0xffu);
+        if ((a & (m * 0xffu)) != m * kAscMissing || (g & 0xfcfcfcfcu) != 0u || (g & (g >> 1) & 0x01010101u) != 0u) bd = 1u;
+        const unsigned ai = a & ib, mi = (ai >> 7) & 0x01010101u, gi = ai & ~(mi * 0xffu);
+        const unsigned c1 = __builtin_popcount(gi & 0x01010101u), c2 = __builtin_popcount(gi & 0x02020202u);
+        nobs += __builtin_popcount((inc >> (4 * d)) & 0xfu) - __builtin_popcount(mi);
+        s1 += c1 + 2u * c2;
+        s2 += c1 + 4u * c2;
+        o[d] = ai;
+    }
+#pragma unroll
+    for (int d = 0; d < 4; ++d) *reinterpret_cast<uint2*>(dst + 8 * d) = make_uint2(o[2 * d], o[2 * d + 1]);
+}
+
+template <int NB>
+struct AscSmem {
+    uint8_t g[2][kAscRows * kAscGPitch];
+    float b[2][NB * 32 * kAscBPitch];
+    unsigned sums[kAscRows * 3];
+};
+
+// Bt [32 NB][npad]: the panel of a stage is 32 NB columns x 16 float4
+template <int NB>
+__device__ __forceinline__ void asc_fetch_b(f32x4 (&P)[2 * NB], const float* __restrict__ Bt, int64_t npad, int64_t n0) {
+#pragma unroll
+    for (int i = 0; i < 2 * NB; ++i) {
+        const int idx = threadIdx.x + kAscThreads * i;
+        P[i] = *reinterpret_cast<const f32x4*>(Bt + (int64_t)(idx >> 4) * npad + n0 + 4 * (idx & 15));
+    }
+}
+template <int NB>
+__device__ __forceinline__ void asc_put_b(const f32x4 (&P)[2 * NB], float* dst) {
+#pragma unroll
+    for (int i = 0; i < 2 * NB; ++i) {
+        const int idx = threadIdx.x + kAscThreads * i;
+        *reinterpret_cast<f32x4*>(dst + (idx >> 4) * kAscBPitch + 4 * (idx & 15)) = P[i];
+    }
+}
+
+// xb [row1 - row0][L] f64, sums [row1 - row0][3] u32 of kept rows [row0, row1); *bad = min original row with a value outside
+// {0, 1, 2, missing}
+template <bool PACKED, int NB>
+__global__ __launch_bounds__(kAscThreads) void k_assoc(const void* __restrict__ Gv, int64_t ldr, const int64_t* __restrict__ krows, int64_t N,
+                                                       int64_t npad, const float* __restrict__ Bt, const unsigned* __restrict__ incw, int L,
+                                                       int64_t row0, int64_t row1, double* __restrict__ xb, unsigned* __restrict__ sums,
+                                                       unsigned long long* __restrict__ bad) {
+    __shared__ __attribute__((aligned(16))) AscSmem<NB> sm;
+    const uint8_t* G = (const uint8_t*)Gv;
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int c = lane & 31, h = lane >> 5;
+    const int64_t k0 = row0 + (int64_t)blockIdx.x * kAscRows;
+
+    // staging map: thread t carries 32 samples (half sh of the stage) of row t / 2
+    const int srow = threadIdx.x >> 1, sh = threadIdx.x & 1;
+    const int64_t sorow = k0 + srow < row1 ? krows[k0 + srow] : -1;
+    auto inb_of = [&](int64_t s) {
+        const int64_t left = N - (s * kAscStage + 32 * sh);
+        return left >= 32 ? 0xffffffffu : (left <= 0 ? 0u : (1u << (int)left) - 1u);
+    };
+    auto inc_of = [&](int64_t s) { return incw[s * (kAscStage / 32) + sh]; };
+    unsigned nobs = 0u, s1 = 0u, s2 = 0u, bd = 0u;
+
+    f32x16 ad[NB], ae[NB];
+    double rd[NB][16], re[NB][16];
+#pragma unroll
+    for (int j = 0; j < NB; ++j)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) { ad[j][e] = 0.0f; ae[j][e] = 0.0f; rd[j][e] = 0.0; re[j][e] = 0.0; }
+
+    const int64_t nst = asc_stages(N);
+    const int g_off = (32 * wv + c) * kAscGPitch + 8 * h, b_off = c * kAscBPitch + 8 * h;
+    const int sg_off = srow * kAscGPitch + 32 * sh;
+
+    AscFetch F;
+    f32x4 P[2 * NB];
+    asc_fetch<PACKED>(F, G, ldr, sorow, 32 * sh);
+    asc_fetch_b<NB>(P, Bt, npad, 0);
+    asc_put(F, inb_of(0), inc_of(0), sm.g[0] + sg_off, nobs, s1, s2, bd);
+    asc_put_b<NB>(P, sm.b[0]);
+    if (nst > 1) { asc_fetch<PACKED>(F, G, ldr, sorow, kAscStage + 32 * sh); asc_fetch_b<NB>(P, Bt, npad, kAscStage); }
+    __syncthreads();
+    for (int64_t s = 0; s < nst; ++s) {
+        const uint8_t* lg = sm.g[s & 1] + g_off;
+        const float* lb = sm.b[s & 1] + b_off;
+#pragma unroll
+        for (int q = 0; q < kAscStage / 16; ++q) {
+            const uint2 gb = *reinterpret_cast<const uint2*>(lg + 16 * q);
+            const bool anym = __builtin_amdgcn_ballot_w64(((gb.x | gb.y) & 0x80808080u) != 0u) != 0ull;      // wave-uniform
+            const unsigned mx = (gb.x >> 7) & 0x01010101u, my = (gb.y >> 7) & 0x01010101u;
+            const unsigned gx = gb.x & ~(mx * 0xffu), gy = gb.y & ~(my * 0xffu);
+            float gf[8], mf[8];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                gf[i] = (float)((gx >> (8 * i)) & 0xffu); gf[4 + i] = (float)((gy >> (8 * i)) & 0xffu);
+                mf[i] = (float)((mx >> (8 * i)) & 0xffu); mf[4 + i] = (float)((my >> (8 * i)) & 0xffu);
+            }
+#pragma unroll
+            for (int j = 0; j < NB; ++j) {
+                const f32x4 b0 = *reinterpret_cast<const f32x4*>(lb + 32 * j * kAscBPitch + 16 * q);
+                const f32x4 b1 = *reinterpret_cast<const f32x4*>(lb + 32 * j * kAscBPitch + 16 * q + 4);
+#pragma unroll
+                for (int i = 0; i < 8; ++i) ad[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(gf[i], i < 4 ? b0[i] : b1[i - 4], ad[j], 0, 0, 0);
+                if (anym) {
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) ae[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(mf[i], i < 4 ? b0[i] : b1[i - 4], ae[j], 0, 0, 0);
+                }
+            }
+        }
+        if ((s + 1) % (kAscFlush / kAscStage) == 0 || s + 1 == nst) {
+#pragma unroll
+            for (int j = 0; j < NB; ++j)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    rd[j][e] += (double)ad[j][e]; ad[j][e] = 0.0f;
+                    re[j][e] += (double)ae[j][e]; ae[j][e] = 0.0f;
+                }
+        }
+        if (s + 1 < nst) {
+            asc_put(F, inb_of(s + 1), inc_of(s + 1), sm.g[(s + 1) & 1] + sg_off, nobs, s1, s2, bd);
+            asc_put_b<NB>(P, sm.b[(s + 1) & 1]);
+        }
+        if (s + 2 < nst) {
+            asc_fetch<PACKED>(F, G, ldr, sorow, (s + 2) * kAscStage + 32 * sh);
+            asc_fetch_b<NB>(P, Bt, npad, (s + 2) * kAscStage);
+        }
+        __syncthreads();
+    }
+
+    if (bd && sorow >= 0) atomicMin(bad, (unsigned long long)sorow);
+    // the two halves of a row sit in neighbouring lanes
+    nobs += __shfl_xor(nobs, 1); s1 += __shfl_xor(s1, 1); s2 += __shfl_xor(s2, 1);
+    if (sh == 0) {
+        sm.sums[3 * srow] = nobs; sm.sums[3 * srow + 1] = s1; sm.sums[3 * srow + 2] = s2;
+        if (sorow >= 0) {
+            unsigned* o = sums + (k0 + srow - row0) * 3;
+            o[0] = nobs; o[1] = s1; o[2] = s2;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+        const int r = 32 * wv + (e & 3) + 8 * (e >> 2) + 4 * h;
+        const int64_t kr = k0 + r;
+        if (kr >= row1) continue;
+        const double mbar = (double)sm.sums[3 * r + 1] / (double)sm.sums[3 * r];
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+            const int col = 32 * j + c;
+            if (col < L) xb[(kr - row0) * L + col] = rd[j][e] + mbar * re[j][e];
+        }
+    }
+}
+
+int launch_assoc(hipStream_t st, const void* G, int packed, int64_t ldr, const int64_t* krows, int64_t N, const float* Bt,
+                 const unsigned* incw, int L, int64_t row0, int64_t row1, double* xb, unsigned* sums, unsigned long long* bad) {
+    if (row1 <= row0) return 0;
+    const int64_t nb = asc_row_blocks(row1 - row0);
+    if (L < 1 || L > kAscMaxCols || nb >= ((int64_t)1 << 31)) return (int)hipErrorInvalidValue;
+    const dim3 grid((unsigned)nb), blk(kAscThreads);
+    const int64_t npad = asc_npad(N);
+#define GPCA_ASC(PK, NB) hipLaunchKernelGGL((k_assoc<PK, NB>), grid, blk, 0, st, G, ldr, krows, N, npad, Bt, incw, L, row0, row1, xb, sums, bad)
+    if (asc_lpad(L) == 32) { if (packed) GPCA_ASC(true, 1); else GPCA_ASC(false, 1); }
+    else { if (packed) GPCA_ASC(true, 2); else GPCA_ASC(false, 2); }
+#undef GPCA_ASC
+    return 0;
+}
+
+// one thread per row of the band: rowinfo [rows][4] = n_obs, a1_freq, xx, sxx and stats [rows][T][3] = beta, se, t (each may be NULL)
+__global__ __launch_bounds__(256) void k_assoc_finish(const double* __restrict__ xb, const unsigned* __restrict__ sums,
+                                                      const double* __restrict__ yy, int T, int L, double df, double max_vif, int64_t rows,
+                                                      double* __restrict__ stats, double* __restrict__ info) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= rows) return;
+    const double nobs = (double)sums[3 * i], s1 = (double)sums[3 * i + 1], s2 = (double)sums[3 * i + 2];
+    const double mbar = s1 / nobs;
+    const double xx = s2 - s1 * mbar;
+    const double* x = xb + i * L;
+    double q = 0.0;
+    for (int j = T; j < L; ++j) q = q + x[j] * x[j];
+    const double sxx = xx - q;
+    if (info) { double* o = info + 4 * i; o[0] = nobs; o[1] = mbar / 2.0; o[2] = xx; o[3] = sxx; }
+    if (!stats) return;
+    const bool dead = sums[3 * i] == 0u || !(xx > 0.0) || sxx * max_vif < xx;
+    const double nan = __builtin_nan("");
+    for (int t = 0; t < T; ++t) {
+        const double beta = x[t] / sxx;
+        const double rss = yy[t] - x[t] * beta;
+        const double se = sqrt(rss / df / sxx);
+        const bool ok = !dead && rss > 0.0;
+        double* o = stats + (i * T + t) * 3;
+        o[0] = ok ? beta : nan; o[1] = ok ? se : nan; o[2] = ok ? beta / se : nan;
+    }
+}
+void launch_assoc_finish(hipStream_t st, const double* xb, const unsigned* sums, const double* yy, int T, int L, double df, double max_vif,
+                         int64_t rows, double* stats, double* info) {
+    if (rows <= 0) return;
+    hipLaunchKernelGGL(k_assoc_finish, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, xb, sums, yy, T, L, df, max_vif, rows, stats, info);
+}
+
+}  // namespace gpca

@@ -1,0 +1,250 @@
+// gpca_assoc_linear / gpca_student_t_log10p (include/gpca.h section a12): the linear association scan.  The traits and covariates
+// are reduced on the host in f64 to B = [Y~ | Q] (Q by Cholesky of the centred, unit-scaled covariates: at most 63 x 63); one pass
+// over the band's kept rows multiplies them on the matrix cores (k_assoc), a second kernel makes the statistics (k_assoc_finish).
+// The call has its own workspace, allocated and freed per call, and reads nothing of the handle's state but the genotypes and the
+// list of kept rows.
+#include "gpca_internal.h"
+
+using namespace gpca;
+
+namespace {
+struct AscWs {
+    float* Bt = nullptr;
+    unsigned *incw = nullptr, *sums = nullptr;
+    double *xb = nullptr, *yy = nullptr, *stats = nullptr, *info = nullptr;
+    unsigned long long* bad = nullptr;
+    ~AscWs() { dfree(Bt); dfree(incw); dfree(sums); dfree(xb); dfree(yy); dfree(stats); dfree(info); dfree(bad); }
+};
+template <typename T>
+hipError_t dalloc(T*& p, size_t elems) { return hipMalloc((void**)&p, std::max<size_t>(elems, 1) * sizeof(T)); }
+
+// Host step: S = the included samples; Q = an orthonormal basis of the columns of C centred over S (each scaled to unit norm, then
+// Q = C L^-T with C^T C = L L^T); Y~ = Y centred over S minus Q Q^T Y (taken out twice, so that what rounding leaves of the first pass
+// goes too); Bt [lpad][npad] = (float)[Y~ | Q]^T, zero outside S; yy [T] = |Y~_t|^2; incw = the mask as bits.
+int asc_design(gpca_handle* h, const double* Y, int T, const double* C, int Pc, const uint8_t* include, std::vector<float>& Bt,
+               std::vector<unsigned>& incw, std::vector<double>& yy, int64_t& n_inc) {
+    static const std::string f("gpca_assoc_linear");
+    const int64_t N = h->N, npad = asc_npad(N);
+    const int L = T + Pc;
+    std::vector<int64_t> S;
+    S.reserve((size_t)N);
+    for (int64_t n = 0; n < N; ++n) if (!include || include[n]) S.push_back(n);
+    const int64_t ns = n_inc = (int64_t)S.size();
+    if (ns - Pc - 2 < 1)
+        return fail(h, GPCA_ERR_BAD_ARG, f + ": " + std::to_string(ns) + " included samples leave df = n - Pc - 2 < 1");
+    for (int64_t n : S) {
+        for (int t = 0; t < T; ++t)
+            if (!std::isfinite(Y[n * T + t])) return fail(h, GPCA_ERR_BAD_ARG, f + ": Y[" + std::to_string(n) + "][" + std::to_string(t) + "] is not finite");
+        for (int j = 0; j < Pc; ++j)
+            if (!std::isfinite(C[n * Pc + j])) return fail(h, GPCA_ERR_BAD_ARG, f + ": C[" + std::to_string(n) + "][" + std::to_string(j) + "] is not finite");
+    }
+    // the covariates over S, column-major, centred and scaled to unit norm
+    std::vector<double> Cc((size_t)Pc * (size_t)ns), Yc((size_t)T * (size_t)ns);
+    for (int j = 0; j < Pc; ++j) {
+        double* c = &Cc[(size_t)j * (size_t)ns];
+        double sum = 0.0, raw = 0.0, ss = 0.0;
+        for (int64_t i = 0; i < ns; ++i) { c[i] = C[S[(size_t)i] * Pc + j]; sum += c[i]; raw += c[i] * c[i]; }
+        const double mean = sum / (double)ns;
+        for (int64_t i = 0; i < ns; ++i) { c[i] -= mean; ss += c[i] * c[i]; }
+        if (!std::isfinite(ss) || !(ss > 1e-20 * raw))
+            return fail(h, GPCA_ERR_BAD_ARG, f + ": column " + std::to_string(j) + " of C is constant over the included samples (or overflows)");
+        const double inv = 1.0 / std::sqrt(ss);
+        for (int64_t i = 0; i < ns; ++i) c[i] *= inv;
+    }
+    // A = Cc^T Cc = L L^T (unit diagonal: a pivot that falls to 1e-10 means the columns are collinear to working precision)
+    std::vector<double> A((size_t)Pc * Pc, 0.0);
+    for (int i = 0; i < Pc; ++i)
+        for (int j = 0; j <= i; ++j) {
+            const double *a = &Cc[(size_t)i * (size_t)ns], *b = &Cc[(size_t)j * (size_t)ns];
+            double s = 0.0;
+            for (int64_t n = 0; n < ns; ++n) s += a[n] * b[n];
+            A[(size_t)i * Pc + j] = s;
+        }
+    for (int j = 0; j < Pc; ++j) {
+        double d = A[(size_t)j * Pc + j];
+        for (int k = 0; k < j; ++k) d -= A[(size_t)j * Pc + k] * A[(size_t)j * Pc + k];
+        if (!(d > 1e-10))
+            return fail(h, GPCA_ERR_BAD_ARG, f + ": the covariates (1, C) are collinear over the included samples (Cholesky pivot " + std::to_string(j) + " failed)");
+        const double l = std::sqrt(d);
+        A[(size_t)j * Pc + j] = l;
+        for (int i = j + 1; i < Pc; ++i) {
+            double s = A[(size_t)i * Pc + j];
+            for (int k = 0; k < j; ++k) s -= A[(size_t)i * Pc + k] * A[(size_t)j * Pc + k];
+            A[(size_t)i * Pc + j] = s / l;
+        }
+    }
+    // Q L^T = Cc, column by column: q_j = (c_j - sum_{k < j} L_jk q_k) / L_jj, in place
+    for (int j = 0; j < Pc; ++j) {
+        double* q = &Cc[(size_t)j * (size_t)ns];
+        for (int k = 0; k < j; ++k) {
+            const double l = A[(size_t)j * Pc + k];
+            const double* qk = &Cc[(size_t)k * (size_t)ns];
+            for (int64_t n = 0; n < ns; ++n) q[n] -= l * qk[n];
+        }
+        const double inv = 1.0 / A[(size_t)j * Pc + j];
+        for (int64_t n = 0; n < ns; ++n) q[n] *= inv;
+    }
+    yy.assign((size_t)T, 0.0);
+    for (int t = 0; t < T; ++t) {
+        double* y = &Yc[(size_t)t * (size_t)ns];
+        double sum = 0.0;
+        for (int64_t i = 0; i < ns; ++i) { y[i] = Y[S[(size_t)i] * T + t]; sum += y[i]; }
+        const double mean = sum / (double)ns;
+        for (int64_t i = 0; i < ns; ++i) y[i] -= mean;
+        for (int pass = 0; pass < 2; ++pass)
+            for (int j = 0; j < Pc; ++j) {
+                const double* q = &Cc[(size_t)j * (size_t)ns];
+                double dot = 0.0;
+                for (int64_t i = 0; i < ns; ++i) dot += q[i] * y[i];
+                for (int64_t i = 0; i < ns; ++i) y[i] -= dot * q[i];
+            }
+        double ss = 0.0;
+        for (int64_t i = 0; i < ns; ++i) ss += y[i] * y[i];
+        if (!(ss > 0.0) || !std::isfinite(ss))
+            return fail(h, GPCA_ERR_BAD_ARG, f + ": trait " + std::to_string(t) + " is constant over the included samples once the covariates are taken out (yy = 0)");
+        yy[(size_t)t] = ss;
+    }
+    Bt.assign((size_t)asc_b_capacity(N, L), 0.0f);
+    incw.assign((size_t)asc_inc_capacity(N), 0u);
+    for (int64_t i = 0; i < ns; ++i) {
+        const int64_t n = S[(size_t)i];
+        incw[(size_t)(n >> 5)] |= 1u << (int)(n & 31);
+        for (int t = 0; t < T; ++t) Bt[(size_t)t * (size_t)npad + (size_t)n] = (float)Yc[(size_t)t * (size_t)ns + (size_t)i];
+        for (int j = 0; j < Pc; ++j) Bt[(size_t)(T + j) * (size_t)npad + (size_t)n] = (float)Cc[(size_t)j * (size_t)ns + (size_t)i];
+    }
+    return GPCA_OK;
+}
+}  // namespace
+
+extern "C" int gpca_assoc_linear(gpca_handle* h, const double* Y, int32_t T, const double* C, int32_t Pc, const uint8_t* include,
+                                 double max_vif, int64_t row0, int64_t row1, double* stats, double* xb, double* rowinfo) {
+    if (!h) return GPCA_ERR_BAD_ARG;
+    LOCK(h);
+    static const std::string f("gpca_assoc_linear");
+    if (!have_genotypes(h)) return fail(h, GPCA_ERR_STATE, f + ": no genotypes resident");
+    if (h->sm.on)
+        return fail(h, GPCA_ERR_STATE, f + ": the handle streams its matrix in panels, which is not implemented");
+    if (multi_rank(h)) return fail(h, GPCA_ERR_STATE, f + ": the handle holds a shard of the rows, which is not implemented");
+    if (!h->have_stats) return fail(h, GPCA_ERR_STATE, f + ": no standardisation: run gpca_snp_stats or gpca_set_standardization first");
+    if (h->n_pca == 0) return fail(h, GPCA_ERR_STATE, f + ": no kept row (the keep mask is empty)");
+    const int64_t K = h->n_pca, N = h->N;
+    if (T < 1 || Pc < 0 || (int64_t)T + Pc > kAscMaxCols)
+        return fail(h, GPCA_ERR_BAD_ARG, f + ": T >= 1, Pc >= 0 and T + Pc <= " + std::to_string(kAscMaxCols) + " are required");
+    if (!Y) return fail(h, GPCA_ERR_BAD_ARG, f + ": Y is required");
+    if (Pc > 0 && !C) return fail(h, GPCA_ERR_BAD_ARG, f + ": C is required when Pc > 0");
+    if (!stats && !xb && !rowinfo) return fail(h, GPCA_ERR_BAD_ARG, f + ": stats, xb and rowinfo are all NULL");
+    if (row0 < 0 || row1 < row0 || row1 > K)
+        return fail(h, GPCA_ERR_BAD_ARG, f + ": rows must satisfy 0 <= row0 <= row1 <= K (K = " + std::to_string(K) + " kept rows)");
+    if (!(max_vif >= 1.0) || !std::isfinite(max_vif)) return fail(h, GPCA_ERR_BAD_ARG, f + ": max_vif must be finite and at least 1");
+    if (N >= ((int64_t)1 << 30)) return fail(h, GPCA_ERR_BAD_ARG, f + ": 2^30 or more samples (the per-row sums are 32-bit)");
+    const int L = T + Pc;
+    std::vector<float> Bt; std::vector<unsigned> incw; std::vector<double> yy;
+    int64_t n_inc = 0;
+    CHK(asc_design(h, Y, T, C, Pc, include, Bt, incw, yy, n_inc));
+    const int64_t rows = row1 - row0;
+    if (rows == 0) return GPCA_OK;
+    if (asc_row_blocks(rows) >= ((int64_t)1 << 31)) return fail(h, GPCA_ERR_BAD_ARG, f + ": the band makes 2^31 or more workgroups: ask for fewer rows");
+    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(hipStreamSynchronize(h->st));
+    {
+        const double need = 4.0 * (double)asc_b_capacity(N, L) + 4.0 * (double)asc_inc_capacity(N) + 8.0 * (double)asc_xb_capacity(rows, L) +
+                            4.0 * (double)asc_sums_capacity(rows) + (stats ? 8.0 * (double)asc_stats_capacity(rows, T) : 0.0) +
+                            (rowinfo ? 8.0 * (double)asc_info_capacity(rows) : 0.0) + 8.0 * T + (double)(64 << 20);
+        size_t fr = 0, tot = 0;
+        HIPCHK(hipMemGetInfo(&fr, &tot));
+        if (need > (double)fr) {
+            char buf[256];
+            snprintf(buf, sizeof buf, "gpca_assoc_linear: the band needs %.3g GB of device memory, %.3g GB are free: ask for fewer rows", need * 1e-9, (double)fr * 1e-9);
+            return fail(h, GPCA_ERR_OOM, buf);
+        }
+    }
+    const bool packed = h->storage == GPCA_STORE_2BIT;
+    const void* G = packed ? (const void*)h->dG2 : (const void*)h->dG;
+    const int64_t ldr = packed ? h->ld2 : h->ld8;
+    hipStream_t st = h->st;
+    AscWs ws;
+    HIPCHK(dalloc(ws.Bt, Bt.size())); HIPCHK(dalloc(ws.incw, incw.size())); HIPCHK(dalloc(ws.yy, (size_t)T)); HIPCHK(dalloc(ws.bad, 1));
+    HIPCHK(dalloc(ws.xb, (size_t)asc_xb_capacity(rows, L))); HIPCHK(dalloc(ws.sums, (size_t)asc_sums_capacity(rows)));
+    if (stats) HIPCHK(dalloc(ws.stats, (size_t)asc_stats_capacity(rows, T)));
+    if (rowinfo) HIPCHK(dalloc(ws.info, (size_t)asc_info_capacity(rows)));
+    HIPCHK(hipMemcpyAsync(ws.Bt, Bt.data(), Bt.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(ws.incw, incw.data(), incw.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(ws.yy, yy.data(), (size_t)T * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(ws.bad, 0xff, 8, st));
+    {
+        // flops as the bench and DESIGN count them: the d product over the padded columns (the e product runs only where calls are missing)
+        ScopedTimer t(h, "assoc", 2.0 * (double)rows * (double)N * (double)asc_lpad(L), (double)rows * (double)N * (packed ? 0.25 : 1.0));
+        if (launch_assoc(st, G, packed, ldr, h->d_pca_rows, N, ws.Bt, ws.incw, L, row0, row1, ws.xb, ws.sums, ws.bad) != 0)
+            return fail(h, GPCA_ERR_BAD_ARG, f + ": the launch was refused");
+        HIPCHK(hipGetLastError());
+    }
+    if (stats || rowinfo) {
+        launch_assoc_finish(st, ws.xb, ws.sums, ws.yy, T, L, (double)(n_inc - Pc - 2), max_vif, rows, ws.stats, ws.info);
+        HIPCHK(hipGetLastError());
+    }
+    unsigned long long bad = 0;
+    HIPCHK(hipMemcpyAsync(&bad, ws.bad, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (bad != ~0ull)
+        return fail(h, GPCA_ERR_INVALID_GENOTYPE, f + ": row " + std::to_string(bad) + " holds a genotype outside {0, 1, 2, missing}");
+    if (stats) HIPCHK(hipMemcpyAsync(stats, ws.stats, (size_t)asc_stats_capacity(rows, T) * 8, hipMemcpyDeviceToHost, st));
+    if (xb) HIPCHK(hipMemcpyAsync(xb, ws.xb, (size_t)asc_xb_capacity(rows, L) * 8, hipMemcpyDeviceToHost, st));
+    if (rowinfo) HIPCHK(hipMemcpyAsync(rowinfo, ws.info, (size_t)asc_info_capacity(rows) * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return GPCA_OK;
+}
+
+namespace {
+// ln Gamma(a + 1/2) - ln Gamma(a): Stirling's series of the difference for a >= 10 (its first omitted term is below 1e-12 there, and
+// nothing large is subtracted), lgamma below
+double lgamma_half_step(double a) {
+    if (a < 10.0) return std::lgamma(a + 0.5) - std::lgamma(a);
+    auto tail = [](double z) {
+        const double r = 1.0 / z, r2 = r * r;
+        return r * (1.0 / 12.0 - r2 * (1.0 / 360.0 - r2 * (1.0 / 1260.0 - r2 * (1.0 / 1680.0))));
+    };
+    return (a * std::log1p(0.5 / a) - 0.5) + 0.5 * std::log(a) + (tail(a + 0.5) - tail(a));
+}
+// the continued fraction of the incomplete beta function (modified Lentz); converges quickly for x < (a + 1) / (a + b + 2)
+double beta_cf(double a, double b, double x) {
+    const double tiny = 1e-300, qab = a + b, qap = a + 1.0, qam = a - 1.0;
+    double c = 1.0, d = 1.0 - qab * x / qap;
+    if (std::fabs(d) < tiny) d = tiny;
+    d = 1.0 / d;
+    double hh = d;
+    for (int m = 1; m <= 200000; ++m) {
+        const double m2 = 2.0 * m;
+        double aa = m * (b - m) * x / ((qam + m2) * (a + m2));
+        d = 1.0 + aa * d; if (std::fabs(d) < tiny) d = tiny;
+        c = 1.0 + aa / c; if (std::fabs(c) < tiny) c = tiny;
+        d = 1.0 / d; hh *= d * c;
+        aa = -(a + m) * (qab + m) * x / ((a + m2) * (qap + m2));
+        d = 1.0 + aa * d; if (std::fabs(d) < tiny) d = tiny;
+        c = 1.0 + aa / c; if (std::fabs(c) < tiny) c = tiny;
+        d = 1.0 / d;
+        const double del = d * c;
+        hh *= del;
+        if (std::fabs(del - 1.0) < 1e-16) break;
+    }
+    return hh;
+}
+}  // namespace
+
+// p = I_x(df / 2, 1 / 2), x = df / (df + t^2).  In the tail (x small) the logarithm of the prefactor and of the continued fraction
+// are added, so nothing underflows; near t = 0 the complement 1 - I_{1 - x}(1 / 2, df / 2) goes through log1p.
+extern "C" double gpca_student_t_log10p(double t, double df) {
+    if (std::isnan(t) || !(df > 0.0) || !std::isfinite(df)) return std::nan("");
+    if (std::isinf(t)) return INFINITY;
+    if (t == 0.0) return 0.0;
+    const double t2 = t * t, a = 0.5 * df, b = 0.5;
+    const double x = df / (df + t2), ln_x = -std::log1p(t2 / df), ln_1mx = -std::log1p(df / t2);
+    const double ln_beta = 0.5 * std::log(M_PI) - lgamma_half_step(a);      // ln B(a, 1/2)
+    const double ln10 = std::log(10.0);
+    if (x < (a + 1.0) / (a + b + 2.0)) {
+        const double ln_p = a * ln_x + b * ln_1mx - std::log(a) - ln_beta + std::log(beta_cf(a, b, x));
+        return -ln_p / ln10;
+    }
+    const double y = t2 / (df + t2);
+    const double ln_q = b * ln_1mx + a * ln_x - std::log(b) - ln_beta + std::log(beta_cf(b, a, y));
+    return -std::log1p(-std::exp(ln_q)) / ln10;
+}

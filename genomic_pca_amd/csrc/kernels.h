@@ -350,4 +350,14 @@ int launch_pcrelate(hipStream_t st, const void* G, int packed, int64_t ldr, cons
 void launch_pcrelate_finish(hipStream_t st, const double* R, const int* Q, const unsigned* inv, int64_t K, int64_t E, int64_t row0,
                             int64_t row1, double* kin, int* nsnp);
 
+// ---- linear association scan: kept rows x (traits + covariates) over the samples, missing calls mean-imputed (assoc.hip) -------------
+// krows: original row of every kept row.  Bt [asc_lpad(L)][asc_npad(N)] f32 (zero past N and past L); incw: the include mask, one bit
+// per sample (asc_inc_capacity(N) words, zero past N).  xb [row1 - row0][L] f64 = d + mbar e; sums [row1 - row0][3] u32 = n_obs, sum g',
+// sum g'^2; *bad = min original row with a value outside {0, 1, 2, missing} (left as it is when there is none)
+int launch_assoc(hipStream_t st, const void* G, int packed, int64_t ldr, const int64_t* krows, int64_t N, const float* Bt,
+                 const unsigned* incw, int L, int64_t row0, int64_t row1, double* xb, unsigned* sums, unsigned long long* bad);
+// stats [rows][T][3] = beta, se, t and info [rows][4] = n_obs, a1_freq, xx, sxx (each may be NULL); yy [T]
+void launch_assoc_finish(hipStream_t st, const double* xb, const unsigned* sums, const double* yy, int T, int L, double df, double max_vif,
+                         int64_t rows, double* stats, double* info);
+
 }  // namespace gpca

@@ -277,4 +277,25 @@ inline int64_t pcr_tiles(int64_t row0, int64_t row1) {
     return t1 * (t1 + 1) / 2 - t0 * (t0 + 1) / 2;
 }
 
+// ---- linear association scan (assoc.hip, gpca_assoc.cpp) --------------------------------------------------------------------------
+// A workgroup owns kAscRows consecutive kept rows of the band (32 per wave) and all L = T + Pc columns, padded to 32 or 64; it walks
+// the samples in stages of kAscStage; the f32 partial sums go to f64 running sums once per kAscFlush samples, counted from sample 0.
+constexpr int kAscRows = 128, kAscThreads = 256, kAscStage = 64, kAscFlush = 256, kAscMaxCols = 64;
+constexpr int kAscGPitch = kAscStage + 8;            // bytes per row of a staged block of calls (ds_read_b64 stays 8-byte aligned)
+constexpr int kAscBPitch = kAscStage + 4;            // floats per column of a staged panel of B (ds_read_b128 stays 16-byte aligned)
+static_assert(kAscFlush % kAscStage == 0 && kAscStage % 32 == 0 && kAscThreads * 32 == kAscRows * kAscStage, "stage, flush group, staging map");
+constexpr int asc_lpad(int L) { return L <= 32 ? 32 : 64; }
+constexpr int64_t asc_npad(int64_t N) { return (N + kAscStage - 1) / kAscStage * kAscStage; }
+constexpr int64_t asc_stages(int64_t N) { return (N + kAscStage - 1) / kAscStage; }
+constexpr int64_t asc_row_blocks(int64_t rows) { return (rows + kAscRows - 1) / kAscRows; }
+// elements of the call's buffers: B^T [asc_lpad(L)][asc_npad(N)] (f32, zero past N and past L); the include mask, one bit per sample
+// (u32 words, zero past N); xb [rows][L] (f64); the per-row sums [rows][3] (u32: n_obs, sum g', sum g'^2); stats [rows][T][3] and
+// rowinfo [rows][4] (f64)
+constexpr int64_t asc_b_capacity(int64_t N, int L) { return (int64_t)asc_lpad(L) * asc_npad(N); }
+constexpr int64_t asc_inc_capacity(int64_t N) { return asc_npad(N) / 32; }
+constexpr int64_t asc_xb_capacity(int64_t rows, int L) { return rows * (int64_t)L; }
+constexpr int64_t asc_sums_capacity(int64_t rows) { return 3 * rows; }
+constexpr int64_t asc_stats_capacity(int64_t rows, int T) { return 3 * rows * (int64_t)T; }
+constexpr int64_t asc_info_capacity(int64_t rows) { return 4 * rows; }
+
 }  // namespace gpca

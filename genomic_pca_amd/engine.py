@@ -505,6 +505,46 @@ class GpcaEngine:
         fc.T[il] = cnt
         return full, fc
 
+    def assoc_linear(self, Y, covar=None, include=None, max_vif: float = 50.0, rows: Optional[Tuple[int, int]] = None, xb: bool = False):
+        """Linear association scan (gpca_assoc_linear): ordinary least squares of every trait (column of Y [N][T]) on (1, covar, g)
+        for the kept rows [row0, row1) in PCA-SNP order (default: all); covar [N][Pc] or None, T + Pc <= 64; include: bool / uint8 [N],
+        None = everyone.  A missing call is imputed to the row's mean over the included samples.  Returns a dict: beta, se, t
+        [rows][T]; n_obs, a1_freq, xx, sxx [rows]; with xb=True also xb [rows][T + Pc] (the products the statistics come from).
+        beta, se and t are NaN for a row with no observed call, no variance, a variance inflation above max_vif, or rss <= 0."""
+        N = self.dims()[1]
+        Yv = np.ascontiguousarray(Y, np.float64)
+        if Yv.ndim == 1:
+            Yv = Yv.reshape(-1, 1)
+        if Yv.ndim != 2 or Yv.shape[0] != N:
+            raise ValueError("Y must be [N][T]: one row of traits per sample")
+        Cv = np.ascontiguousarray(np.zeros((N, 0)) if covar is None else covar, np.float64)
+        if Cv.ndim == 1:
+            Cv = Cv.reshape(N, 0) if Cv.size == 0 else Cv.reshape(-1, 1)
+        if Cv.ndim != 2 or Cv.shape[0] != N:
+            raise ValueError("covar must be [N][Pc]: one row of covariates per sample")
+        inc = None if include is None else np.ascontiguousarray(np.asarray(include) != 0, np.uint8)
+        if inc is not None and inc.shape != (N,):
+            raise ValueError("include must have one entry per sample")
+        T, Pc = Yv.shape[1], Cv.shape[1]
+        K = int(self._lib.gpca_num_pca_snps(self._h))
+        r0, r1 = (0, K) if rows is None else (int(rows[0]), int(rows[1]))
+        n = max(r1 - r0, 0)
+        stats = np.zeros((max(n, 1), max(T, 1), 3), np.float64)
+        info = np.zeros((max(n, 1), 4), np.float64)
+        out_xb = np.zeros((max(n, 1), max(T + Pc, 1)), np.float64) if xb else None
+        self._chk(self._lib.gpca_assoc_linear(self._h, _vp(Yv), T, _vp(Cv) if Pc else None, Pc, _vp(inc), float(max_vif), r0, r1,
+                                              _vp(stats), _vp(out_xb), _vp(info)))
+        res = {"beta": stats[:n, :, 0], "se": stats[:n, :, 1], "t": stats[:n, :, 2], "n_obs": info[:n, 0], "a1_freq": info[:n, 1],
+               "xx": info[:n, 2], "sxx": info[:n, 3]}
+        if xb:
+            res["xb"] = out_xb[:n]
+        return res
+
+    @staticmethod
+    def student_t_log10p(t: float, df: float) -> float:
+        """-log10 of the two-sided p-value of a Student t statistic (gpca_student_t_log10p; host only, no underflow)."""
+        return float(_lib.load().gpca_student_t_log10p(float(t), float(df)))
+
     # -- f3: the stages of EigenSNPCoreAlgorithm (gpca.h)
     def copy_rows_from(self, src: "GpcaEngine", row0: int, rows: int):
         """This engine receives rows [row0, row0 + rows) of src's resident matrix (device to device)."""

@@ -764,6 +764,96 @@ inline void write_prune_ids(const std::string& prefix, const std::vector<std::st
     }
 }
 
+// ---- linear association scan: the twins of io.read_pheno, io.align_pheno, io.assoc_bands and io.write_assoc (same rules, same error
+// texts, byte-identical files) --------------------------------------------------------------------------------------------------------
+struct PhenoTable {
+    std::vector<std::string> family_ids, sample_ids, names;
+    std::vector<double> values;      // [samples][names], NaN = missing
+};
+
+// A whitespace-separated phenotype or covariate table.  The header `FID IID name...` (a leading '#' allowed) is required; `NA` and `nan`
+// in any letter case mean missing; a repeated (FID, IID) is refused.
+inline PhenoTable read_pheno(const std::string& path) {
+    std::ifstream in(path);
+    if (!in) throw std::runtime_error("cannot open " + path);
+    PhenoTable t;
+    bool have_header = false;
+    std::set<std::pair<std::string, std::string>> seen;
+    std::string line;
+    const std::string need = path + ": the header `FID IID name...` with at least one column is required";
+    auto upper = [](std::string s) { for (char& c : s) c = (char)std::toupper((unsigned char)c); return s; };
+    for (int64_t ln = 1; std::getline(in, line); ++ln) {
+        const std::vector<std::string> p = split_ws(line);
+        if (p.empty()) continue;
+        if (!have_header) {
+            if (p.size() < 3 || upper(p[0].substr(std::min(p[0].find_first_not_of('#'), p[0].size()))) != "FID" || upper(p[1]) != "IID")
+                throw std::runtime_error(need);
+            t.names.assign(p.begin() + 2, p.end());
+            if (std::set<std::string>(t.names.begin(), t.names.end()).size() != t.names.size())
+                throw std::runtime_error(path + ": a column name is repeated");
+            have_header = true;
+            continue;
+        }
+        const std::string at = path + ":" + std::to_string(ln) + ": ";
+        if (p.size() != 2 + t.names.size())
+            throw std::runtime_error(at + std::to_string(p.size()) + " fields, the header has " + std::to_string(2 + t.names.size()));
+        if (!seen.insert({p[0], p[1]}).second) throw std::runtime_error(at + "sample " + p[0] + " " + p[1] + " appears twice");
+        for (size_t c = 2; c < p.size(); ++c) {
+            const std::string lo = upper(p[c]);
+            if (lo == "NA" || lo == "NAN") { t.values.push_back(std::nan("")); continue; }
+            char* end = nullptr;
+            const double v = std::strtod(p[c].c_str(), &end);
+            if (end == p[c].c_str() || *end || p[c].find_first_of("xX_") != std::string::npos) throw std::runtime_error(at + "`" + p[c] + "` is not a number");
+            t.values.push_back(v);
+        }
+        t.family_ids.push_back(p[0]); t.sample_ids.push_back(p[1]);
+    }
+    if (!have_header) throw std::runtime_error(need);
+    return t;
+}
+
+// The table's rows in .fam order, matched by (FID, IID): [samples][columns]; a sample absent from the table is missing (NaN) in every
+// column; rows of the table that name no sample of the .fam are ignored.
+inline std::vector<double> align_pheno(const PhenoTable& t, const std::vector<std::string>& family_ids, const std::vector<std::string>& sample_ids) {
+    std::map<std::pair<std::string, std::string>, size_t> at;
+    for (size_t r = 0; r < t.sample_ids.size(); ++r) at[{t.family_ids[r], t.sample_ids[r]}] = r;
+    const size_t c = t.names.size();
+    std::vector<double> out(sample_ids.size() * c, std::nan(""));
+    for (size_t n = 0; n < sample_ids.size(); ++n) {
+        const auto it = at.find({family_ids[n], sample_ids[n]});
+        if (it != at.end()) std::copy(t.values.begin() + it->second * c, t.values.begin() + (it->second + 1) * c, out.begin() + n * c);
+    }
+    return out;
+}
+
+// [row0, row1) bands of the K kept rows whose xb workspace (rows x L doubles) holds at most max_values entries (at least one row)
+inline std::vector<std::pair<int64_t, int64_t>> assoc_bands(int64_t K, int64_t L, int64_t max_values = (int64_t)1 << 26) {
+    const int64_t step = std::max<int64_t>(max_values / std::max<int64_t>(L, 1), 1);
+    std::vector<std::pair<int64_t, int64_t>> out;
+    for (int64_t r0 = 0; r0 < K; r0 += step) out.emplace_back(r0, std::min(r0 + step, K));
+    return out;
+}
+
+// P.<trait>.assoc.linear: one tab-separated line per SNP, `#CHROM POS ID A1 OBS_CT A1_FREQ BETA SE T_STAT LOG10P`; numbers as %.6g, NaN
+// as NA, OBS_CT as an integer; rows are added band by band
+class AssocWriter {
+public:
+    AssocWriter(const std::string& prefix, const std::string& trait) : o_(prefix + "." + trait + ".assoc.linear") {
+        std::fputs("#CHROM\tPOS\tID\tA1\tOBS_CT\tA1_FREQ\tBETA\tSE\tT_STAT\tLOG10P\n", o_.f);
+    }
+    void add_row(const std::string& chrom, int64_t pos, const std::string& id, const std::string& a1, double n_obs, double a1_freq, double beta,
+                 double se, double t, double log10p) {
+        char b[5][48];
+        const double v[5] = {a1_freq, beta, se, t, log10p};
+        for (int i = 0; i < 5; ++i) { if (v[i] != v[i]) std::snprintf(b[i], sizeof b[i], "NA"); else std::snprintf(b[i], sizeof b[i], "%.6g", v[i]); }
+        std::fprintf(o_.f, "%s\t%lld\t%s\t%s\t%lld\t%s\t%s\t%s\t%s\t%s\n", chrom.c_str(), (long long)pos, id.c_str(), a1.c_str(), (long long)n_obs, b[0], b[1],
+                     b[2], b[3], b[4]);
+    }
+
+private:
+    OutFile o_;
+};
+
 }  // namespace gpca_host
 
 #endif

@@ -55,6 +55,11 @@ struct Args {
     bool have_indep = false;          // --gpca-indep-pairwise WINDOW R2: LD pruning of the kept SNPs before the GRM, KING and the PCA
     std::string indep_window, indep_r2_text;
     double indep_r2 = 0.0;
+    std::string assoc_pheno, assoc_covar;   // --gpca-assoc-pheno FILE (turns the association scan on), --gpca-assoc-covar FILE
+    bool have_assoc_pcs = false, have_assoc_vif = false;
+    int64_t assoc_pcs = 0;            // --gpca-assoc-pcs P [default: every column of the scores]
+    double assoc_vif = 50.0;          // --gpca-assoc-vif X
+    gpca_host::PhenoTable assoc_pheno_table, assoc_covar_table;   // read in main, before any work on the device
 };
 
 [[noreturn]] void usage_error(const std::string& msg) {
@@ -141,6 +146,19 @@ void print_help() {
         "      --gpca-pcrelate-maf-bound <T>    --gpca-make-pcrelate: an entry counts when its individual-specific allele frequency\n"
         "                                       lies in (T, 1 - T); 0 <= T < 0.5 [default: 0.01]\n"
         "      --gpca-pcrelate-table-filter <X> --gpca-make-pcrelate: write only the pairs with kinship >= X (P.pcrelate.inbreed stays whole)\n"
+        "      --gpca-assoc-pheno <FILE>        EigenSNP workflow: after everything else is written, test every SNP that passes the SNP QC\n"
+        "                                       (call rate, MAF, HWE; the LD blocks and --gpca-indep-pairwise shape the PCA, not the\n"
+        "                                       test set) against every trait column of FILE (header `FID IID name...`, NA = missing) by\n"
+        "                                       least squares with the PCs as covariates, a missing call imputed to the SNP's mean ->\n"
+        "                                       P.<trait>.assoc.linear (#CHROM POS ID A1 OBS_CT A1_FREQ BETA SE T_STAT LOG10P).  A sample\n"
+        "                                       counts when every trait and covariate is present for it and, with --gpca-king-cutoff,\n"
+        "                                       it is in the in-set.  Needs the matrix resident on the device; traits + PCs +\n"
+        "                                       covariates <= 64\n"
+        "      --gpca-assoc-pcs <P>             --gpca-assoc-pheno: the first P columns of the scores this run writes are covariates\n"
+        "                                       (0 <= P <= --eigensnp-k-global) [default: every column]\n"
+        "      --gpca-assoc-covar <FILE>        --gpca-assoc-pheno: further covariates, a table in the format of the phenotype file\n"
+        "      --gpca-assoc-vif <X>             --gpca-assoc-pheno: a SNP whose variance inflation against the covariates exceeds X gets\n"
+        "                                       NA (plink's --vif) [default: 50]\n"
         "  -h, --help                           Print help");
 }
 
@@ -214,6 +232,10 @@ Args parse(int argc, char** argv) {
         else if (f == "--gpca-make-pcrelate") { a.pcrelate_pcs = to_i64(f, val()); a.make_pcrelate = true; }
         else if (f == "--gpca-pcrelate-maf-bound") { a.pcrelate_tau = to_f64(f, val()); a.have_pcrelate_tau = true; }
         else if (f == "--gpca-pcrelate-table-filter") { a.pcrelate_filter = to_f64(f, val()); a.have_pcrelate_filter = true; }
+        else if (f == "--gpca-assoc-pheno") a.assoc_pheno = val();
+        else if (f == "--gpca-assoc-covar") a.assoc_covar = val();
+        else if (f == "--gpca-assoc-pcs") { a.assoc_pcs = to_i64(f, val()); a.have_assoc_pcs = true; }
+        else if (f == "--gpca-assoc-vif") { a.assoc_vif = to_f64(f, val()); a.have_assoc_vif = true; }
         else if (f == "--gpca-indep-pairwise") {
             a.indep_window = val();
             if (i + 1 >= argc) usage_error("two values (WINDOW R2) are required for '" + f + "'");
@@ -335,6 +357,74 @@ const char* const kPcrelateNeedsResident =
     "error: --gpca-make-pcrelate needs the genotype matrix resident on the device: the f32 sums are not associative across the panels of a "
     "matrix walked out of core\n";
 
+const char* const kAssocNeedsResident =
+    "error: --gpca-assoc-pheno needs the genotype matrix resident on the device: the scan of a matrix walked out of core is not implemented\n";
+constexpr int64_t kAssocMaxColumns = 64;
+
+// --gpca-assoc-pheno FILE: the linear association scan (gpca_assoc_linear) of every SNP that passes the SNP QC, in row bands, into
+// P.<trait>.assoc.linear.  Runs last: it resets the keep mask to the QC mask (mu, sigma unchanged), which ends the fit's validity.
+// Covariates = the first P columns of the scores the run wrote, then the columns of --gpca-assoc-covar; a sample is included when every
+// trait and covariate is present for it and it is in the KING in-set, when there is one (cli.py:_assoc).  scores is [n][kc].
+int run_assoc(gpca::Engine& eng, const Args& a, const gpca_host::PlinkFileset& fs, const std::vector<std::string>& fids,
+              const std::vector<std::string>& sample_ids, const std::vector<double>& scores, int kc, const std::vector<uint8_t>& inset,
+              const gpca::SnpStats& st) {
+    const int64_t n = (int64_t)sample_ids.size();
+    const int32_t P = a.have_assoc_pcs ? (int32_t)a.assoc_pcs : (int32_t)kc;
+    const int32_t T = (int32_t)a.assoc_pheno_table.names.size(), nc = a.assoc_covar.empty() ? 0 : (int32_t)a.assoc_covar_table.names.size();
+    const int32_t Pc = P + nc;
+    const std::vector<double> Y = gpca_host::align_pheno(a.assoc_pheno_table, fids, sample_ids);
+    std::vector<double> cv;
+    if (nc) cv = gpca_host::align_pheno(a.assoc_covar_table, fids, sample_ids);
+    std::vector<double> C((size_t)n * (size_t)Pc + 1);
+    std::vector<uint8_t> include((size_t)n, 1);
+    int64_t n_inc = 0;
+    for (int64_t s = 0; s < n; ++s) {
+        bool ok = inset.empty() || inset[(size_t)s];
+        for (int32_t c = 0; c < P; ++c) C[(size_t)s * Pc + c] = scores[(size_t)s * kc + c];
+        for (int32_t c = 0; c < nc; ++c) C[(size_t)s * Pc + P + c] = cv[(size_t)s * nc + c];
+        for (int32_t c = 0; c < Pc; ++c) ok = ok && std::isfinite(C[(size_t)s * Pc + c]);
+        for (int32_t t = 0; t < T; ++t) ok = ok && std::isfinite(Y[(size_t)s * T + t]);
+        include[(size_t)s] = ok ? 1 : 0;
+        n_inc += ok;
+    }
+    const int64_t df = n_inc - Pc - 2;
+    if (df < 1) {
+        std::fprintf(stderr, "error: --gpca-assoc-pheno: %lld samples have every trait and covariate, which leaves no degree of freedom beside %d covariates\n",
+                     (long long)n_inc, (int)Pc);
+        return 1;
+    }
+    eng.set_standardization(st.mu, st.sigma, st.keep);                                // every SNP that passes the SNP QC
+    std::vector<int64_t> rows;
+    for (size_t i = 0; i < st.keep.size(); ++i) if (st.keep[i]) rows.push_back((int64_t)i);
+    std::vector<std::unique_ptr<gpca_host::AssocWriter>> w;
+    gpca_host::ensure_parent(a.output_prefix);
+    for (int32_t t = 0; t < T; ++t) w.emplace_back(new gpca_host::AssocWriter(a.output_prefix, a.assoc_pheno_table.names[(size_t)t]));
+    try {
+        for (const auto& b : gpca_host::assoc_bands((int64_t)rows.size(), T + Pc)) {
+            std::vector<double> stats, info;
+            eng.assoc_linear(Y, T, C, Pc, &include, a.assoc_vif, b.first, b.second, stats, info);
+            for (int64_t r = b.first; r < b.second; ++r) {
+                const size_t i = (size_t)(r - b.first), o = (size_t)rows[(size_t)r];
+                for (int32_t t = 0; t < T; ++t) {
+                    const double* s3 = &stats[(i * (size_t)T + (size_t)t) * 3];
+                    const double lp = s3[2] != s3[2] ? std::nan("") : gpca_student_t_log10p(s3[2], (double)df);
+                    w[(size_t)t]->add_row(fs.chromosomes[o], fs.positions[o], fs.variant_ids[o], fs.allele1[o], info[4 * i], info[4 * i + 1], s3[0], s3[1], s3[2], lp);
+                }
+            }
+        }
+    } catch (const gpca::Error& e) {
+        if (e.status() != GPCA_ERR_STATE) throw;
+        std::fputs(kAssocNeedsResident, stderr);
+        return 1;
+    }
+    w.clear();
+    char buf[512];
+    std::snprintf(buf, sizeof buf, "association scan of %zu SNPs against %d traits with %d covariates (%d PCs) on %lld of %lld samples, written to %s.<trait>.assoc.linear",
+                  rows.size(), (int)T, (int)Pc, (int)P, (long long)n_inc, (long long)n, a.output_prefix.c_str());
+    logmsg(buf);
+    return 0;
+}
+
 int run_eigensnp_workflow(Args a) {
     if (a.bed_file.empty() || a.ld_block_file.empty()) {
         std::fprintf(stderr, "error: --bed-file and --ld-block-file are required when --eigensnp is used\n");           // main.rs:296-301
@@ -357,7 +447,9 @@ int run_eigensnp_workflow(Args a) {
         if (kept.cols.empty()) { logmsg("No samples available after sample QC."); return 0; }
         use_kept = true;
     }
-    if (load_bed(eng, a, fs, use_kept ? &kept : nullptr) && a.make_pcrelate) { std::fputs(kPcrelateNeedsResident, stderr); return 1; }
+    const bool streamed = load_bed(eng, a, fs, use_kept ? &kept : nullptr);
+    if (streamed && a.make_pcrelate) { std::fputs(kPcrelateNeedsResident, stderr); return 1; }
+    if (streamed && !a.assoc_pheno.empty()) { std::fputs(kAssocNeedsResident, stderr); return 1; }
     const gpca::SnpStats st = eng.snp_stats(gpca::QcConfig{a.min_call_rate, a.min_maf, a.max_hwe_p});
     const auto blocks = gpca_host::parse_ld_block_file(a.ld_block_file);
     std::vector<uint8_t> keep;
@@ -510,6 +602,10 @@ int run_eigensnp_workflow(Args a) {
         std::fprintf(stderr, "error: --gpca-make-pcrelate %lld asks for more PCs than the %lld this run computes\n", (long long)a.pcrelate_pcs, (long long)k);
         return 1;
     }
+    if (a.have_assoc_pcs && a.assoc_pcs > k) {
+        std::fprintf(stderr, "error: --gpca-assoc-pcs %lld asks for more PCs than the %lld this run computes\n", (long long)a.assoc_pcs, (long long)k);
+        return 1;
+    }
     if (!inset.empty() && n_fit < (int64_t)inset.size()) eng.set_sample_mask(&inset);      // the fit sees the in-set only
     // with the cutoff every sample is projected onto the in-set's PCs (the relatives included), inside compute_pca while the fit is valid
     const gpca::EigenSNPCoreOutput out = gpca::EigenSNPCoreAlgorithm(cfg).compute_pca(acc, specs, a.local_stage, !inset.empty());
@@ -568,6 +664,14 @@ int run_eigensnp_workflow(Args a) {
         std::snprintf(buf, sizeof buf, "PC-Relate kinship of %lld samples over %zu SNPs, adjusted for %d PCs, written to %s.pcrelate.kin", (long long)n,
                       rows.size(), (int)P, a.output_prefix.c_str());
         logmsg(buf);
+    }
+    if (!a.assoc_pheno.empty()) {
+        std::vector<std::string> fids = fs.family_ids;
+        if (use_kept) { fids.clear(); for (int64_t c : kept.cols) fids.push_back(fs.family_ids[(size_t)c]); }
+        std::vector<double> scores = projected;
+        if (inset.empty()) scores.assign(out.final_sample_principal_component_scores.begin(), out.final_sample_principal_component_scores.end());
+        const int rc = run_assoc(eng, a, fs, fids, sample_ids, scores, kc, inset, st);
+        if (rc) return rc;
     }
     std::snprintf(buf, sizeof buf, "EigenSNP workflow done in %.2fs", seconds_since(t0));
     logmsg(buf);
@@ -643,6 +747,36 @@ int main(int argc, char** argv) {
                 return 2;
             }
             if (a.stream == "on") { std::fputs(kPcrelateNeedsResident, stderr); return 2; }
+        }
+        if (a.assoc_pheno.empty() && (a.have_assoc_pcs || !a.assoc_covar.empty() || a.have_assoc_vif)) {
+            std::fprintf(stderr, "error: --gpca-assoc-pcs, --gpca-assoc-covar and --gpca-assoc-vif need --gpca-assoc-pheno\n");
+            return 2;
+        }
+        if (!a.assoc_pheno.empty()) {
+            if (!a.eigensnp) { std::fprintf(stderr, "error: --gpca-assoc-pheno needs the --eigensnp workflow\n"); return 2; }
+            if (a.have_assoc_pcs && !(a.assoc_pcs >= 0 && a.assoc_pcs <= a.k_global)) {
+                std::fprintf(stderr, "error: --gpca-assoc-pcs P must lie in [0, --eigensnp-k-global]\n");
+                return 2;
+            }
+            if (!(a.assoc_vif >= 1.0) || !std::isfinite(a.assoc_vif)) { std::fprintf(stderr, "error: --gpca-assoc-vif must be finite and at least 1\n"); return 2; }
+            if (a.local_stage) {
+                std::fprintf(stderr, "error: --gpca-assoc-pheno cannot be combined with --gpca-eigensnp-local-stage (that stage defines no all-sample scores)\n");
+                return 2;
+            }
+            if (a.stream == "on") { std::fputs(kAssocNeedsResident, stderr); return 2; }
+            try { a.assoc_pheno_table = gpca_host::read_pheno(a.assoc_pheno); }
+            catch (const std::runtime_error& e) { std::fprintf(stderr, "error: --gpca-assoc-pheno: %s\n", e.what()); return 2; }
+            if (!a.assoc_covar.empty()) {
+                try { a.assoc_covar_table = gpca_host::read_pheno(a.assoc_covar); }
+                catch (const std::runtime_error& e) { std::fprintf(stderr, "error: --gpca-assoc-covar: %s\n", e.what()); return 2; }
+            }
+            const int64_t t = (int64_t)a.assoc_pheno_table.names.size(), c = (int64_t)a.assoc_covar_table.names.size();
+            const int64_t p = a.have_assoc_pcs ? a.assoc_pcs : a.k_global;
+            if (t + p + c > kAssocMaxColumns) {
+                std::fprintf(stderr, "error: --gpca-assoc-pheno: %lld traits + %lld PCs + %lld covariates are more than %lld columns\n", (long long)t, (long long)p,
+                             (long long)c, (long long)kAssocMaxColumns);
+                return 2;
+            }
         }
         if (!a.project_model.empty()) return run_project_workflow(a);
         if (a.save_model && !a.eigensnp) { std::fprintf(stderr, "error: --gpca-save-model needs the --eigensnp workflow\n"); return 2; }

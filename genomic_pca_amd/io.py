@@ -703,3 +703,94 @@ def write_prune_ids(prefix: str, variant_ids: Sequence[str], inset: np.ndarray) 
         with open(path, "w") as f:
             f.writelines(f"{variant_ids[i]}\n" for i in range(len(variant_ids)) if bool(inset[i]) == want)
     return paths
+
+
+# ------------------------------------------------------------------------------------------------ association scan
+@dataclass
+class PhenoTable:
+    family_ids: List[str]
+    sample_ids: List[str]
+    names: List[str]              # the trait (or covariate) columns, in file order
+    values: np.ndarray            # f64 [rows][len(names)], NaN = missing
+
+
+def read_pheno(path: str) -> PhenoTable:
+    """A whitespace-separated phenotype or covariate table.  The header `FID IID name...` (a leading '#' allowed) is required; `NA` and
+    `nan` in any letter case mean missing; a repeated (FID, IID) is refused."""
+    fids, iids, rows, names, seen = [], [], [], None, set()
+    with open(path) as f:
+        for ln, line in enumerate(f, 1):
+            p = line.split()
+            if not p:
+                continue
+            if names is None:
+                if len(p) < 3 or p[0].lstrip("#").upper() != "FID" or p[1].upper() != "IID":
+                    raise ValueError(f"{path}: the header `FID IID name...` with at least one column is required")
+                names = p[2:]
+                if len(set(names)) != len(names):
+                    raise ValueError(f"{path}: a column name is repeated")
+                continue
+            if len(p) != 2 + len(names):
+                raise ValueError(f"{path}:{ln}: {len(p)} fields, the header has {2 + len(names)}")
+            if (p[0], p[1]) in seen:
+                raise ValueError(f"{path}:{ln}: sample {p[0]} {p[1]} appears twice")
+            seen.add((p[0], p[1]))
+            vals = []
+            for v in p[2:]:
+                if v.lower() in ("na", "nan"):
+                    vals.append(np.nan)
+                else:
+                    try:
+                        if "_" in v:
+                            raise ValueError
+                        vals.append(float(v))
+                    except ValueError:
+                        raise ValueError(f"{path}:{ln}: `{v}` is not a number") from None
+            fids.append(p[0]); iids.append(p[1]); rows.append(vals)
+    if names is None:
+        raise ValueError(f"{path}: the header `FID IID name...` with at least one column is required")
+    return PhenoTable(fids, iids, names, np.asarray(rows, np.float64).reshape(len(rows), len(names)))
+
+
+def align_pheno(table: PhenoTable, family_ids: Sequence[str], sample_ids: Sequence[str]) -> np.ndarray:
+    """The table's rows in .fam order, matched by (FID, IID): f64 [len(sample_ids)][columns]; a sample absent from the table is missing
+    (NaN) in every column; rows of the table that name no sample of the .fam are ignored."""
+    at = {(f, i): r for r, (f, i) in enumerate(zip(table.family_ids, table.sample_ids))}
+    out = np.full((len(sample_ids), len(table.names)), np.nan)
+    for n, key in enumerate(zip(family_ids, sample_ids)):
+        r = at.get(key)
+        if r is not None:
+            out[n] = table.values[r]
+    return out
+
+
+def assoc_bands(K: int, L: int, max_values: int = 1 << 26):
+    """[row0, row1) bands of the K kept rows whose xb workspace (rows x L doubles) holds at most max_values entries (at least one row):
+    the bands gpca_assoc_linear is asked for, one at a time."""
+    step = max(max_values // max(L, 1), 1)
+    return [(r0, min(r0 + step, K)) for r0 in range(0, K, step)]
+
+
+def _g6(x) -> str:
+    x = float(x)
+    return "NA" if x != x else "%.6g" % x
+
+
+def write_assoc(prefix: str, trait: str, chromosomes: Sequence[str], positions: Sequence[int], variant_ids: Sequence[str],
+                allele1: Sequence[str], n_obs, a1_freq, beta, se, t, log10p, append: bool = False) -> str:
+    """P.<trait>.assoc.linear: one tab-separated line per SNP, `#CHROM POS ID A1 OBS_CT A1_FREQ BETA SE T_STAT LOG10P`; numbers as %.6g,
+    NaN as NA, OBS_CT as an integer.  append=True adds the rows of a further band to the file (no header)."""
+    path = f"{prefix}.{trait}.assoc.linear"
+    n = len(variant_ids)
+    for a in (chromosomes, positions, allele1, n_obs, a1_freq, beta, se, t, log10p):
+        if len(a) != n:
+            raise ValueError("write_assoc: one entry per SNP in every column")
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    with open(path, "a" if append else "w") as f:
+        if not append:
+            f.write("#CHROM\tPOS\tID\tA1\tOBS_CT\tA1_FREQ\tBETA\tSE\tT_STAT\tLOG10P\n")
+        f.writelines(f"{chromosomes[i]}\t{int(positions[i])}\t{variant_ids[i]}\t{allele1[i]}\t{int(n_obs[i])}\t{_g6(a1_freq[i])}\t{_g6(beta[i])}\t"
+                     f"{_g6(se[i])}\t{_g6(t[i])}\t{_g6(log10p[i])}\n" for i in range(n))
+    return path

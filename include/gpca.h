@@ -375,6 +375,37 @@ GPCA_API int gpca_pcrelate_isaf(gpca_handle* h, const double* V /* [N][P] */, in
 GPCA_API int gpca_pcrelate(gpca_handle* h, const double* V /* [N][P] */, int32_t P, const uint8_t* train /* [N] or NULL */, double tau,
                            int64_t row0, int64_t row1, double* kinship, int32_t* nsnp /* may be NULL */);
 
+/* ---- a12: linear association scan: ordinary least squares of each of T traits on (1, C, g) for every kept row g of the band
+ * [row0, row1), 0 <= row0 <= row1 <= K (PCA-SNP order), T >= 1, Pc >= 0, T + Pc <= 64.  It is plink's --glm on a quantitative trait,
+ * except that a missing call is imputed to the row's mean over the included samples (as BOLT, regenie and fastGWA do; plink drops the
+ * sample for that variant, so plink's output is claimed only for rows with no missing call among the included samples).
+ *  1. host, f64, once per call: S = the included samples (include [N], NULL = everyone), n = |S|; Q [N][Pc] = an orthonormal basis of
+ *     the columns of C centred over S (Cholesky of the centred columns scaled to unit norm), 0 outside S; Y~ = Y centred over S minus
+ *     Q Q^T Y, 0 outside S; yy_t = |Y~_t|^2; B = [Y~ | Q], rounded once to f32; df = n - Pc - 2.
+ *  2. device, one read of the genotypes: o = [observed and in S], g' = g o; n_obs = sum o, s1 = sum g', s2 = sum g'^2 (exact);
+ *     d_ij = sum_n g'_in B_nj and e_ij = sum_n [missing and in S]_in B_nj on v_mfma_f32_32x32x2_f32 (the operand is the call as f32, so
+ *     every product is exact), an f32 accumulator never sums more than 256 samples (groups counted from sample 0) before it is added
+ *     to an f64 running sum; no split of the sample axis and no atomics.
+ *  3. f64, no fused multiply-add: mbar = s1 / n_obs; xb_ij = d_ij + mbar e_ij; xx = s2 - s1 mbar; sxx = xx - sum_{j >= T} xb_ij^2 (j
+ *     ascending); per trait beta = xb_it / sxx, rss = yy_t - xb_it beta, se = sqrt(rss / df / sxx), t = beta / se; a1_freq = mbar / 2.
+ *     beta, se, t are NaN when n_obs = 0, xx <= 0, sxx max_vif < xx (plink's --vif rule) or rss <= 0.
+ * stats [rows][T][3] = beta, se, t; xb [rows][T + Pc]; rowinfo [rows][4] = n_obs, a1_freq, xx, sxx: each may be NULL, not all three.
+ * A band is bit-identical to the same rows of the full call; int8 and 2-bit residency give the same bits, and so does a
+ * GPCA_PREC_F32_MFMA handle (the call reads only the genotypes and the keep mask); the sample mask is ignored and no fitted result is
+ * touched.  Out of scope: logistic regression, per-variant dropping of samples, per-trait sample sets, mixed models, and streamed and
+ * row-sharded handles: GPCA_ERR_STATE.
+ * Errors: GPCA_ERR_STATE (no standardisation, K = 0, a streamed handle, a row-sharded handle), GPCA_ERR_BAD_ARG (T, Pc or the row
+ * range out of bounds, all outputs NULL, a non-finite entry of Y or C on an included sample, df < 1, a column of C that is constant or
+ * collinear over S, a trait with yy_t = 0, max_vif < 1 or not finite), GPCA_ERR_INVALID_GENOTYPE (a row the call reads holds a value
+ * outside {0, 1, 2, missing}; the message names the row), GPCA_ERR_OOM (checked before any allocation). */
+GPCA_API int gpca_assoc_linear(gpca_handle* h, const double* Y /* [N][T] */, int32_t T, const double* C /* [N][Pc] or NULL */, int32_t Pc,
+                               const uint8_t* include /* [N] or NULL */, double max_vif, int64_t row0, int64_t row1,
+                               double* stats /* [rows][T][3] or NULL */, double* xb /* [rows][T + Pc] or NULL */,
+                               double* rowinfo /* [rows][4] or NULL */);
+/* -log10 of the two-sided p-value of a Student t statistic with df degrees of freedom; host only, in log space (a p below 1e-308
+ * does not underflow).  NaN for a NaN t or df <= 0. */
+GPCA_API double gpca_student_t_log10p(double t, double df);
+
 /* ---- f3: the stages of EigenSNPCoreAlgorithm::compute_pca (main.rs:311-327, 359-366) ------------------------------------------
  * The algorithm lives in the un-vendored efficient_pca crate (Cargo.toml:30, branch "main", no pinned revision): what follows is
  * the stage structure of its published description -- per-LD-block local bases learnt on a sample subset, condensed features of

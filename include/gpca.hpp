@@ -218,6 +218,23 @@ public:
         if (beta) beta->resize(rows * (size_t)(P + 1));
     }
 
+    // linear association scan (gpca_assoc_linear) of kept rows [row0, row1): Y [N][T], C [N][Pc] (may be empty when Pc = 0), include
+    // (may be null: everyone) [N]; stats [rows][T][3] = beta, se, t; rowinfo [rows][4] = n_obs, a1_freq, xx, sxx; xb (may be null)
+    // [rows][T + Pc]
+    void assoc_linear(const std::vector<double>& Y, int32_t T, const std::vector<double>& C, int32_t Pc, const std::vector<uint8_t>* include,
+                      double max_vif, int64_t row0, int64_t row1, std::vector<double>& stats, std::vector<double>& rowinfo,
+                      std::vector<double>* xb = nullptr) const {
+        const size_t rows = row1 > row0 ? (size_t)(row1 - row0) : 0;
+        stats.assign(std::max<size_t>(rows * (size_t)T * 3, 1), 0.0);
+        rowinfo.assign(std::max<size_t>(rows * 4, 1), 0.0);
+        if (xb) xb->assign(std::max<size_t>(rows * (size_t)(T + Pc), 1), 0.0);
+        check(gpca_assoc_linear(h_, Y.data(), T, Pc ? C.data() : nullptr, Pc, include ? include->data() : nullptr, max_vif, row0, row1,
+                                stats.data(), xb ? xb->data() : nullptr, rowinfo.data()));
+        stats.resize(rows * (size_t)T * 3);
+        rowinfo.resize(rows * 4);
+        if (xb) xb->resize(rows * (size_t)(T + Pc));
+    }
+
 private:
     gpca_handle* h_ = nullptr;
     int k_ = 0;

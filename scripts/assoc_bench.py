@@ -1,0 +1,73 @@
+#!/usr/bin/env python3
+"""gpca_assoc_linear on one GPU: ms per call (HIP events of the library's "assoc" record: the k_assoc pass over the band; wall_ms adds
+the host design, the per-call workspace, the finish kernel and the copy of the outputs to the host), the f32 matrix-core flops per
+second counted as 2 K N L_pad (the d product; the e product runs only where calls are missing), as a fraction of the 157 TF/s f32
+MFMA peak, and the genotype bytes of one read of the band per second beside the 8 TB/s of the HBM.  One JSON line per L.
+
+usage: python scripts/assoc_bench.py [--rows M] [--samples N] [--storage int8|2bit] [--missing RATE] [--cols L ...] [--band ROWS] [--reps R]
+
+Clean matrices come from the device generator; with --missing > 0 the rows are a 4 096-row host tile (that missing rate, seeded)
+repeated down the matrix and uploaded through a host panel source.  --band ROWS: rows per call (0 = io.assoc_bands' default).  Of the
+L columns a third (at most 20) are covariates: random orthonormal columns; the traits are standard normal."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import genomic_pca_amd as g          # noqa: E402
+from genomic_pca_amd import _lib, io as gio     # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--rows", type=int, default=1_000_000)
+ap.add_argument("--samples", type=int, default=10_000)
+ap.add_argument("--storage", choices=["int8", "2bit"], default="int8")
+ap.add_argument("--missing", type=float, default=0.0)
+ap.add_argument("--cols", type=int, nargs="+", default=[32, 64])
+ap.add_argument("--band", type=int, default=0)
+ap.add_argument("--reps", type=int, default=2)
+a = ap.parse_args()
+M, N = a.rows, a.samples
+store = _lib.STORE_INT8 if a.storage == "int8" else _lib.STORE_2BIT
+rng = np.random.default_rng(7)
+
+with g.GpcaEngine(precision=_lib.PREC_I8_EXACT, storage=store) as e:
+    t0 = time.time()
+    if a.missing > 0:
+        T = 4096
+        th = g.synth_thresholds(T, 6, seed=3, fst=0.1)
+        p = th[:, 0].astype(np.float64) / 2**32
+        tile = ((rng.random((T, N)) < p[:, None]).astype(np.int8) + (rng.random((T, N)) < p[:, None]).astype(np.int8))
+        tile[rng.random((T, N)) < a.missing] = -127
+        e.load_from_source(g.PanelSource.host_i8(lambda r0, r: tile[(r0 + np.arange(r)) % T]), M, N)
+    else:
+        e.synth_genotypes(M, N, 1, g.synth_thresholds(M, 6, seed=1, fst=0.1))
+    e.snp_stats()
+    K = e.num_pca_snps()
+    load_s = time.time() - t0
+    for L in a.cols:
+        Pc = min(L // 3, 20)
+        Y = rng.standard_normal((N, L - Pc))
+        C = np.linalg.qr(rng.standard_normal((N, max(Pc, 1))))[0][:, :Pc]
+        bands = [(r0, min(r0 + a.band, K)) for r0 in range(0, K, a.band)] if a.band else gio.assoc_bands(K, L)
+        e.assoc_linear(Y, C, rows=(0, min(K, 128)))      # warm-up
+        e.enable_timings(True); e.reset_timings()
+        t0 = time.time()
+        for _ in range(a.reps):
+            for b in bands:
+                e.assoc_linear(Y, C, rows=b)
+        wall_ms = (time.time() - t0) * 1e3 / a.reps
+        rec = e.timings().get("assoc", {})
+        ms = rec["total_ms"] / a.reps if rec.get("launches") else float("nan")
+        lpad = 32 if L <= 32 else 64
+        flops = 2.0 * K * N * lpad
+        gbytes = K * N / (4 if store == _lib.STORE_2BIT else 1)
+        read_ms, mfma_ms = gbytes / 8e12 * 1e3, flops / 157e12 * 1e3
+        print(json.dumps({"shape": f"{M} x {N}", "kept_rows": K, "storage": a.storage, "missing": a.missing, "L": L, "traits": L - Pc, "covariates": Pc,
+                          "bands": len(bands), "ms": round(ms, 3), "wall_ms": round(wall_ms, 3), "read_at_8tbs_ms": round(read_ms, 3),
+                          "mfma_at_157tf_ms": round(mfma_ms, 3), "frac_of_larger_bound": round(max(read_ms, mfma_ms) / ms, 3),
+                          "f32_tflops": round(flops / ms / 1e9, 2), "genotype_gb_s": round(gbytes / ms / 1e6, 1), "load_s": round(load_s, 2),
+                          "reps": a.reps}), flush=True)
