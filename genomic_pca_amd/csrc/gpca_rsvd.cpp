@@ -397,7 +397,8 @@ static int stage_orth(gpca_handle* h, int rounds = 2) {
         else {
             launch_sum_partials_f64(h->st, h->d_part64, parts, (int64_t)L * L, h->dW, h->d_scratch64);
             HIPCHK(hipGetLastError());
-            launch_chol_inv(h->st, h->dW, l, L, h->dZ, h->d_cholflag);
+            const int e = launch_chol_inv(h->st, h->dW, l, L, h->dZ, h->d_cholflag);
+            if (e != 0) return fail(h, GPCA_ERR_HIP, "CholeskyQR: the factorisation was not launched (hip error " + std::to_string(e) + ")");
         }
         HIPCHK(hipGetLastError());
         if (round + 1 < rounds) launch_apply_right_inplace(h->st, h->dY, h->N, L, h->dZ, nullptr, h->ldg);
@@ -547,15 +548,69 @@ static int finish_small_eigh(gpca_handle* h, bool take) {
     HIPCHK(hipMemcpyAsync(res, h->d_eigres, sizeof(double) * kEigResCount, hipMemcpyDeviceToHost, h->st));
     HIPCHK(stream_wait(h));
     if (!take) return GPCA_OK;
-    const int flag = (int)res[kEigResFlag];
-    if (flag) {   // (computed redundantly on the replicated Y: the same on every rank)
-        char buf[160];
-        snprintf(buf, sizeof buf, "CholeskyQR: pivot %d of the %d-column sketch is not finite (overflow or NaN in the sketch)", flag - 1, h->l);
-        return fail(h, GPCA_ERR_NOT_CONVERGED, buf);
-    }
+    static_assert(kEigNotConverged == GPCA_ERR_NOT_CONVERGED, "eig_result.h restates the status code");
+    const EigVerdict verdict = eig_result_verdict(res, h->l);      // (the pivot flag, then the eigen step's cap: eig_result.h)
+    if (verdict.status != 0) return fail(h, verdict.status, verdict.msg);
     h->sv.assign(res + kEigResSv, res + kEigResSv + h->l);
     h->eig.assign(res + kEigResEig, res + kEigResEig + h->k);
     return GPCA_OK;
+}
+
+// ---- the tail of a call ----------------------------------------------------------------------------------------------------------------
+// What follows the last GEMM of gpca_rsvd (zmode 0) and of gpca_refine (zmode 1), and what the test hook gpca_device_tail runs on a
+// caller's factors: the Gram of the factor the eigenproblem is built on (zmode 0: B = A Q, f32 in dT, M rows; zmode 1: the sample
+// factor in dY, f64, N rows), the l x l eigen step, scores = dY Z0 with the sign rule, loadings = Xload[pca rows] (Z1 o sign), and the
+// call's one host wait with the verdict on the result block -- all enqueued, no host step in between.
+// lrc: the rank-local status so far.  One rank: GPCA_OK.  A sharded handle: a rank that failed earlier keeps entering the Gram's
+// exchange (its peers are not left inside a collective); the second agreement of gpca_rsvd rides that exchange -- every rank appends
+// its status histogram to the l x l block (no round trip of its own) -- and returns the failure on every rank.
+static int call_tail(gpca_handle* h, int zmode, double denom, const float* Xload, int lrc) {
+    const bool mr = multi_rank(h);
+    const int L = h->L;
+#define LOCAL(x) do { if (lrc == GPCA_OK) lrc = (x); if (lrc != GPCA_OK && !mr) return lrc; } while (0)
+    const double* gsrc = h->dW; int gslices = 0;
+    auto gram = [&]() -> int {
+        const int64_t rows = zmode == 0 ? h->M : h->N;
+        const int64_t parts = gram_num_parts(rows);
+        if (zmode == 0) launch_gram_f32(h->st, h->dT, rows, L, h->d_part64);
+        else launch_gram_f64(h->st, h->dY, rows, L, h->d_part64);
+        HIPCHK(hipGetLastError());
+        if (mr) launch_sum_partials_f64(h->st, h->d_part64, parts, (int64_t)L * L, h->dW, h->d_scratch64);      // the exchange needs the rank's sum in one place
+        else launch_sum_partials_f64_stage1(h->st, h->d_part64, parts, (int64_t)L * L, h->d_scratch64, &gsrc, &gslices);   // (the eigen kernel folds the slices)
+        HIPCHK(hipGetLastError());
+        return GPCA_OK;
+    };
+    LOCAL(gram());
+    if (mr) {
+        h->status_own = h->err;
+        status_histogram(h->h_status, lrc);
+        if (hipMemcpyAsync(h->dW + (size_t)L * L, h->h_status, 16 * sizeof(double), hipMemcpyHostToDevice, h->st) != hipSuccess && lrc == GPCA_OK)
+            lrc = fail(h, GPCA_ERR_HIP, "gpca_rsvd: status copy failed");
+        const int xrc = allreduce_f64(h, h->dW, (int64_t)L * L + 16);
+        if (xrc != GPCA_OK) return xrc;
+    }
+    // C = V diag(w) V^T on the device (small_eig.hip); scores = Q V_k diag(s), sign (largest |score| positive), loadings = B V_k diag(sign / s)
+    auto tail = [&]() -> int {
+        CHK(enqueue_small_eigh(h, gsrc, gslices, zmode, denom));
+        return enqueue_scores_loadings(h, Xload, true);
+    };
+    LOCAL(tail());
+    // The call's one host wait: singular values, eigenvalues, the two flags of the result block and (sharded runs) the agreed status
+    // arrive together.
+    if (mr && hipMemcpyAsync(h->h_status + 16, h->dW + (size_t)L * L, 16 * sizeof(double), hipMemcpyDeviceToHost, h->st) != hipSuccess)
+        return lrc != GPCA_OK ? lrc : fail(h, GPCA_ERR_HIP, "gpca_rsvd: status fetch failed");
+    {
+        const int frc = finish_small_eigh(h, lrc == GPCA_OK);      // (waits for the stream; a rank that failed earlier only waits)
+        if (lrc == GPCA_OK) lrc = frc;                             // (a pivot flag or a capped eigen step joins the agreement below)
+    }
+    if (mr) {
+        const std::string own_now = h->err;
+        const int agreed = status_verdict(h, h->h_status + 16, lrc, h->status_own, "gpca_rsvd (after the last exchange)");
+        if (agreed != GPCA_OK) return agreed;
+        h->err = own_now;
+    }
+#undef LOCAL
+    return lrc;
 }
 
 // ---- compact child (gpca_internal.h): the kept rows as a matrix of their own -------------------------------------------------------
@@ -700,46 +755,11 @@ extern "C" int gpca_rsvd(gpca_handle* h, int32_t k, int32_t oversample, int32_t 
     }
     // 3. projection B = A Q, the l x l eigenproblem of B^T B, scores, loadings: all enqueued, no host step in between.
     LOCAL(stage_AQ(h, 0));
-    const double* gsrc = h->dW; int gslices = 0;
-    auto gram_b = [&]() -> int {
-        const int64_t parts = gram_num_parts(h->M);
-        launch_gram_f32(h->st, h->dT, h->M, L, h->d_part64);
-        HIPCHK(hipGetLastError());
-        if (mr) launch_sum_partials_f64(h->st, h->d_part64, parts, (int64_t)L * L, h->dW, h->d_scratch64);      // the exchange needs the rank's sum in one place
-        else launch_sum_partials_f64_stage1(h->st, h->d_part64, parts, (int64_t)L * L, h->d_scratch64, &gsrc, &gslices);   // (the eigen kernel folds the slices)
-        HIPCHK(hipGetLastError());
-        return GPCA_OK;
-    };
-    LOCAL(gram_b());
-    // the second agreement rides the Gram's exchange: every rank appends its status histogram to the l x l block (no round trip of its own)
-    if (mr) {
-        h->status_own = h->err;
-        status_histogram(h->h_status, lrc);
-        if (hipMemcpyAsync(h->dW + (size_t)L * L, h->h_status, 16 * sizeof(double), hipMemcpyHostToDevice, h->st) != hipSuccess && lrc == GPCA_OK)
-            lrc = fail(h, GPCA_ERR_HIP, "gpca_rsvd: status copy failed");
-    }
-    EXCHANGE(h->dW, (int64_t)L * L + (mr ? 16 : 0));
     // variance over the samples that took part: all N, or the subset of gpca_set_sample_mask (the other rows of the sketch are zero)
     const double n_eff = h->d_smask ? (double)h->n_smask : (double)h->N;
-    // 4. C = V diag(w) V^T on the device (small_eig.hip); scores = Q V_k diag(s), sign (largest |score| positive), loadings = B V_k diag(sign / s)
-    auto tail = [&]() -> int {
-        CHK(enqueue_small_eigh(h, gsrc, gslices, 0, n_eff - 1.0));
-        return enqueue_scores_loadings(h, h->dT, true);
-    };
-    LOCAL(tail());
-    // The call's one host wait: singular values, eigenvalues, the pivot flag and (sharded runs) the agreed status arrive together.
-    if (mr && hipMemcpyAsync(h->h_status + 16, h->dW + (size_t)L * L, 16 * sizeof(double), hipMemcpyDeviceToHost, h->st) != hipSuccess)
-        return lrc != GPCA_OK ? lrc : fail(h, GPCA_ERR_HIP, "gpca_rsvd: status fetch failed");
-    {
-        const int frc = finish_small_eigh(h, lrc == GPCA_OK);      // (waits for the stream; a rank that failed earlier only waits)
-        if (lrc == GPCA_OK) lrc = frc;
-    }
-    if (mr) {
-        const std::string own_now = h->err;
-        const int agreed = status_verdict(h, h->h_status + 16, lrc, h->status_own, "gpca_rsvd (after the last exchange)");
-        if (agreed != GPCA_OK) return agreed;
-        h->err = own_now;
-    }
+    // 4. the Gram of B (its exchange carries the second agreement; the first was taken at the sketch's exchange above), C = V diag(w) V^T
+    //    on the device, scores, sign, loadings, the call's one host wait: call_tail
+    lrc = call_tail(h, 0, n_eff - 1.0, h->dT, lrc);
     if (lrc != GPCA_OK) return lrc;
 #undef LOCAL
 #undef EXCHANGE
@@ -999,7 +1019,8 @@ extern "C" int gpca_refine(gpca_handle* h, const double* S0, int32_t k) {
         HIPCHK(hipGetLastError());
         launch_sum_partials_f64(h->st, h->d_part64, gram_num_parts(h->M), (int64_t)L * L, h->dW, h->d_scratch64);
         HIPCHK(hipGetLastError());
-        launch_chol_inv(h->st, h->dW, l, L, h->dZ, h->d_cholflag);
+        const int e = launch_chol_inv(h->st, h->dW, l, L, h->dZ, h->d_cholflag);
+        if (e != 0) return fail(h, GPCA_ERR_HIP, "gpca_refine: the factorisation was not launched (hip error " + std::to_string(e) + ")");
         HIPCHK(hipGetLastError());
         launch_rightmul_inplace_f32(h->st, h->dT, h->M, L, h->dZ);
         HIPCHK(hipGetLastError());
@@ -1007,14 +1028,55 @@ extern "C" int gpca_refine(gpca_handle* h, const double* S0, int32_t k) {
     HIPCHK(hipMemcpyAsync(h->d_lqr, h->dT, (size_t)h->Mpad * L * 4, hipMemcpyDeviceToDevice, h->st));   // L, kept for the loadings
     CHK(prep_custom_T(h));
     CHK(stage_AtT_local(h));                              // dY = S = A^T L   (N x L f64)
-    launch_gram_f64(h->st, h->dY, h->N, L, h->d_part64);
-    HIPCHK(hipGetLastError());
-    const double* gsrc = nullptr; int gslices = 0;
-    launch_sum_partials_f64_stage1(h->st, h->d_part64, gram_num_parts(h->N), (int64_t)L * L, h->d_scratch64, &gsrc, &gslices);
-    HIPCHK(hipGetLastError());
-    CHK(enqueue_small_eigh(h, gsrc, gslices, 1, (double)(h->N - 1)));      // S^T S = W Sigma^2 W^T: scores = S W, loadings = L W
-    CHK(enqueue_scores_loadings(h, h->d_lqr, true));
-    CHK(finish_small_eigh(h, true));
+    CHK(call_tail(h, 1, (double)(h->N - 1), h->d_lqr, GPCA_OK));     // S^T S = W Sigma^2 W^T: scores = S W, loadings = L W
+    h->have_rsvd = true; h->loadings_valid = true; h->rsvd_on_child = false;
+    return GPCA_OK;
+}
+
+// ---- test hooks (GPU): the small dense chain between the GEMM sweeps on a caller's input ------------------------------------------------
+// Both run the product's own stage functions (stage_orth, call_tail) on the handle's workspace.
+extern "C" int gpca_device_orth(gpca_handle* h, const double* Y, int32_t l, int32_t rounds, double* Q, double* s, int32_t* pivot_flag) {
+    if (!h || !Y || !Q || !pivot_flag || l < 1 || rounds < 1 || rounds > 2) return GPCA_ERR_BAD_ARG;
+    LOCK(h);
+    if (multi_rank(h) || h->sm.on) return fail(h, GPCA_ERR_STATE, "gpca_device_orth: needs a resident, unsharded matrix");
+    CHK(rsvd_preflight(h, l, 0, 0));
+    const int L = h->L;
+    const int64_t N = h->N;
+    std::vector<double> buf((size_t)N * L, 0.0);
+    for (int64_t n = 0; n < N; ++n) for (int c = 0; c < l; ++c) buf[(size_t)n * L + c] = Y[(size_t)n * l + c];
+    HIPCHK(hipMemcpyAsync(h->dY, buf.data(), buf.size() * 8, hipMemcpyHostToDevice, h->st));
+    HIPCHK(hipStreamSynchronize(h->st));
+    CHK(stage_orth(h, rounds));
+    double s64[kMaxSketch];
+    int flag = 0;
+    HIPCHK(hipMemcpyAsync(buf.data(), h->dY, buf.size() * 8, hipMemcpyDeviceToHost, h->st));
+    HIPCHK(hipMemcpyAsync(s64, h->d_s64, sizeof(double) * L, hipMemcpyDeviceToHost, h->st));
+    HIPCHK(hipMemcpyAsync(&flag, h->d_cholflag, 4, hipMemcpyDeviceToHost, h->st));
+    HIPCHK(hipStreamSynchronize(h->st));
+    for (int64_t n = 0; n < N; ++n) for (int c = 0; c < l; ++c) Q[(size_t)n * l + c] = buf[(size_t)n * L + c];
+    if (s) std::copy(s64, s64 + l, s);
+    *pivot_flag = flag;            // (data, not a status: the product reads it once, at the end of its call)
+    return GPCA_OK;
+}
+
+extern "C" int gpca_device_tail(gpca_handle* h, const double* Q, const float* B, int32_t l, int32_t k, int32_t zmode) {
+    if (!h || !Q || !B || k < 1 || l < k || (zmode != 0 && zmode != 1)) return GPCA_ERR_BAD_ARG;
+    LOCK(h);
+    if (multi_rank(h) || h->sm.on) return fail(h, GPCA_ERR_STATE, "gpca_device_tail: needs a resident, unsharded matrix");
+    CHK(rsvd_preflight(h, k, l - k, 0));
+    const int L = h->L;
+    const int64_t N = h->N;
+    {
+        std::vector<double> Yb((size_t)N * L, 0.0);
+        for (int64_t n = 0; n < N; ++n) for (int c = 0; c < l; ++c) Yb[(size_t)n * L + c] = Q[(size_t)n * l + c];
+        std::vector<float> Tb((size_t)h->Mpad * L, 0.f);          // (rows QC dropped stay zero, as stage_AQ leaves them)
+        for (int64_t i : h->pca_rows) for (int c = 0; c < l; ++c) Tb[(size_t)i * L + c] = B[(size_t)i * l + c];
+        HIPCHK(hipMemcpyAsync(h->dY, Yb.data(), Yb.size() * 8, hipMemcpyHostToDevice, h->st));
+        HIPCHK(hipMemcpyAsync(h->dT, Tb.data(), Tb.size() * 4, hipMemcpyHostToDevice, h->st));
+        HIPCHK(hipStreamSynchronize(h->st));
+    }
+    const double n_eff = h->d_smask ? (double)h->n_smask : (double)N;
+    CHK(call_tail(h, zmode, n_eff - 1.0, h->dT, GPCA_OK));
     h->have_rsvd = true; h->loadings_valid = true; h->rsvd_on_child = false;
     return GPCA_OK;
 }

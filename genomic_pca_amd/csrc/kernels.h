@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "eig_result.h"  // the result block of the small dense step and the host's verdict on it, audited by tests/cpp/eig_result_audit.cpp
 #include "plan_math.h"   // part counts, GEMM plans, workspace capacities: plain host arithmetic, audited by tests/cpp/plan_audit.cpp
 
 namespace gpca {
@@ -23,12 +24,7 @@ int init_device_kernels_common();
 int init_device_kernels_eig();
 
 // ---- the small dense step on the device (small_eig.hip) ----------------------------------------------------------------------
-// layout of the result block `res` of launch_small_eigh (doubles): what the host reads back ONCE, at the end of the call
-constexpr int kEigResSv = 0;                         // [128] singular values sqrt(max(w, 0)), descending
-constexpr int kEigResEig = kMaxSketchCols;           // [128] w_c / denom for c < k
-constexpr int kEigResW = 2 * kMaxSketchCols;         // [128] eigenvalues w, descending
-constexpr int kEigResFlag = 3 * kMaxSketchCols;      // [0] the CholeskyQR pivot flag, [1] QL sweep cap hit
-constexpr int kEigResCount = 3 * kMaxSketchCols + 8;
+// (layout of the result block `res` of launch_small_eigh and the host's verdict on it: eig_result.h)
 // Symmetric eigenproblem of the leading n x n block of W (pitch L; nslices > 0: W = the sum of `nslices` partial matrices [L * L] apart),
 // symmetrised; descending.  Z [2][L][k]: zmode 0 -> Z0 = V_k diag(sv), Z1 = V_k diag(1 / sv); zmode 1 -> Z0 = Z1 = V_k.  Vout may be NULL.
 void launch_small_eigh(hipStream_t st, const double* src, int nslices, int n, int L, int k, int zmode, double denom, const int* cholflag,
@@ -148,7 +144,7 @@ void launch_apply_right_tail(hipStream_t st, double* X, int64_t rows, int L, con
 void launch_finish_q(hipStream_t st, const double* csum_part, const double* amax_part, int64_t P, int L, double* s64, float* s32,
                      double* scale, double* inv, int nd = 4);
 // W = R^T R (n x n, pitch ld <= 64), Z = R^-1; *flag = j + 1 on a non-positive pivot (first failure wins)
-void launch_chol_inv(hipStream_t st, const double* W, int n, int ld, double* Z, int* flag);
+int launch_chol_inv(hipStream_t st, const double* W, int n, int ld, double* Z, int* flag);      // a hipError_t value (0 = launched)
 // the same from the Gram's P <= 64 partial sums [P][32 * 32] (ld = 32 only): the fold rides in front of the factorisation, no k_sum_partials launch
 void launch_chol_inv_fold(hipStream_t st, const double* part, int P, int n, int ld, double* Z, int* flag);
 void launch_apply_right_inplace(hipStream_t st, double* X, int64_t rows, int L, const double* Z, float* Qb,

@@ -367,6 +367,7 @@ void launch_standardize_block(hipStream_t st, const int8_t* G, int64_t ld, const
 void launch_gram_any_f64(hipStream_t st, const double* X, int64_t rows, int64_t rpb, int64_t parts, int L, double* part);
 void launch_gram_any_f32(hipStream_t st, const float* X, int64_t rows, int64_t rpb, int64_t parts, int L, double* part);
 int launch_chol_inv_any(hipStream_t st, const double* W, int n, int L, double* Z, int* flag);
+int init_device_kernels_wide();
 void launch_apply_right_any(hipStream_t st, double* X, int64_t rows, int64_t parts, int L, const double* Z, double* csum_part, double* amax_part);
 void launch_rightmul_any_f64(hipStream_t st, const double* X, int64_t rows, int L, const double* Z, int K, double* out64, float* out32);
 void launch_rightmul_any_gather_f32(hipStream_t st, const float* X, const int64_t* row_ids, int64_t nrows, int L, const double* Z, int K, float* out32);
@@ -920,10 +921,11 @@ void launch_chol_inv_fold(hipStream_t st, const double* part, int P, int n, int 
     (void)ld;
     hipLaunchKernelGGL(k_chol_inv_fold32, dim3(1), dim3(256), 0, st, part, P, n, Z, flag);
 }
-void launch_chol_inv(hipStream_t st, const double* W, int n, int ld, double* Z, int* flag) {
+int launch_chol_inv(hipStream_t st, const double* W, int n, int ld, double* Z, int* flag) {
     if (ld == 32) hipLaunchKernelGGL(k_chol_inv<32>, dim3(1), dim3(64), 0, st, W, n, Z, flag);
     else if (ld == 64) hipLaunchKernelGGL(k_chol_inv<64>, dim3(1), dim3(64), 0, st, W, n, Z, flag);
-    else (void)launch_chol_inv_any(st, W, n, ld, Z, flag);       // (ld = 128 = kMaxSketchCols: the factor lives in LDS)
+    else return launch_chol_inv_any(st, W, n, ld, Z, flag);      // (ld = 128 = kMaxSketchCols: the factor lives in LDS)
+    return 0;
 }
 
 void launch_apply_right_inplace(hipStream_t st, double* X, int64_t rows, int L, const double* Z, float* Qout,
@@ -1377,6 +1379,7 @@ void launch_f32_to_f64(hipStream_t st, const float* in, double* out, int64_t n) 
 int init_device_kernels_common() {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_rightmul<double, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_scores<64>), hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024);
+    if (e == hipSuccess) e = (hipError_t)init_device_kernels_wide();      // (k_chol_inv_any, wide_sketch.hip)
     return (int)e;
 }
 

@@ -125,13 +125,16 @@ __global__ __launch_bounds__(256) void k_chol_inv_any(const double* __restrict__
         Zg[e] = (r < n && c < n) ? (r < c ? R[c * P + r] : (r == c ? zdiag[r] : 0.0)) : 0.0;
     }
 }
+// (its 129 KiB of LDS: opted in per device by init_device_kernels_common, through init_device_kernels_wide below)
 int launch_chol_inv_any(hipStream_t st, const double* W, int n, int L, double* Z, int* flag) {
     if (L > kCholAnyMaxL || n > L) return (int)hipErrorInvalidValue;
     const size_t lds = sizeof(double) * ((size_t)L * (L + 1) + L + 1);
-    static bool opted = false;
-    if (!opted) { if (hipFuncSetAttribute((const void*)k_chol_inv_any, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * ((size_t)kCholAnyMaxL * (kCholAnyMaxL + 1) + kCholAnyMaxL + 1))) != hipSuccess) return (int)hipErrorInvalidValue; opted = true; }
     hipLaunchKernelGGL(k_chol_inv_any, dim3(1), dim3(256), lds, st, W, n, L, Z, flag);
     return 0;
+}
+int init_device_kernels_wide() {
+    return (int)hipFuncSetAttribute((const void*)k_chol_inv_any, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)(sizeof(double) * ((size_t)kCholAnyMaxL * (kCholAnyMaxL + 1) + kCholAnyMaxL + 1)));
 }
 
 // X[n][:] <- X[n][:] Z in place (f64): a workgroup takes kTailRows = 64 rows (the partial-array granularity of k_apply_right_tail,

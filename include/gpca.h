@@ -249,6 +249,19 @@ GPCA_API int gpca_host_eigh_desc(const double* a_sym, int32_t n, double* w, doub
  * 64 columns, tridiagonalisation + QL split over waves for 65-128; the call's stream never waits for the host), on a caller's matrix;
  * same conventions as above. */
 GPCA_API int gpca_device_eigh_desc(gpca_handle* h, const double* a_sym, int32_t n, double* w, double* v);
+/* Test hook (GPU): the orthonormalisation gpca_rsvd runs between its GEMM sweeps (CholeskyQR, `rounds` = 1 or 2: Gram, Cholesky +
+ * inverse, right-multiplication, s = Q^T 1) on a caller's sketch Y [N][l], through the product's own stage function and with the
+ * handle's sample mask.  The handle holds genotypes and standardisation (N = its sample count); l <= min(N, PCA SNPs), l <= 128
+ * (64 on GPCA_PREC_F32_MFMA).  Q [N][l]: the basis; s [l] (may be NULL): its column sums; *pivot_flag: the device's pivot flag
+ * (j + 1 for the first pivot j that was not finite, else 0), returned as data -- the hook itself returns GPCA_OK.  The results of an
+ * earlier gpca_rsvd are gone afterwards. */
+GPCA_API int gpca_device_orth(gpca_handle* h, const double* Y, int32_t l, int32_t rounds, double* Q, double* s, int32_t* pivot_flag);
+/* Test hook (GPU): the tail of a call -- Gram, the l x l eigen step, scores with the sign rule, loadings, the verdict on the result
+ * block -- on a caller's factors Q [N][l] (f64, any matrix) and B [M][l] (f32; only PCA SNP rows are read), through the function
+ * gpca_rsvd and gpca_refine share.  zmode 0 (step 4 of gpca_rsvd): B^T B = V diag(w) V^T, scores = Q V_k diag(sv), loadings =
+ * B V_k diag(1 / sv) (0 where sv = 0); zmode 1 (the tail of gpca_refine): Q^T Q = V diag(w) V^T, scores = Q V_k, loadings = B V_k.
+ * Results through the getters (scores, singular values [l], eigenvalues = w / (samples - 1), loadings). */
+GPCA_API int gpca_device_tail(gpca_handle* h, const double* Q, const float* B, int32_t l, int32_t k, int32_t zmode);
 /* Host helper, same branches as prepare.rs:1641-1745. */
 GPCA_API double gpca_hwe_chi_squared_p_value(uint64_t n_hom1, uint64_t n_het, uint64_t n_hom2);
 

@@ -179,6 +179,7 @@ static int run_wide(int n) {
     double *dW, *dZ0, *dZ1, *dwork; int* flag;
     CK(hipMalloc(&dW, L * L * 8)); CK(hipMalloc(&dZ0, L * L * 8)); CK(hipMalloc(&dZ1, L * L * 8)); CK(hipMalloc(&dwork, L * L * 8)); CK(hipMalloc(&flag, 4)); CK(hipMemset(flag, 0, 4));
     CK(hipMemcpy(dW, W.data(), L * L * 8, hipMemcpyHostToDevice));
+    CK((hipError_t)gpca::init_device_kernels_wide());      // (k_chol_inv_any's LDS: opted in per device, as gpca_create does)
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
     double t[2] = {0, 0};
     for (int rep = 0; rep < 3; ++rep)
