@@ -124,6 +124,11 @@ def build_parser() -> argparse.ArgumentParser:
                         "the SNP's mean -> P.<trait>.assoc.linear (#CHROM POS ID A1 OBS_CT A1_FREQ BETA SE T_STAT LOG10P).  A sample "
                         "counts when every trait and covariate is present for it and, with --gpca-king-cutoff, it is in the in-set.  "
                         "Needs the matrix resident on the device; traits + PCs + covariates <= 64")
+    p.add_argument("--gpca-assoc-logistic", action="store_true",
+                   help="--gpca-assoc-pheno: a trait column whose present values are exactly {0, 1} (1 = case) or {1, 2} (plink's coding, "
+                        "2 = case) gets the logistic score test (the null model fitted once per trait, no Firth / SPA correction) -> "
+                        "P.<trait>.assoc.logistic (#CHROM POS ID A1 OBS_CT A1_FREQ BETA SE Z_STAT LOG10P); the other columns go "
+                        "through the linear scan as without the flag.  PCs + covariates + 3 <= 64")
     p.add_argument("--gpca-assoc-pcs", type=int, default=None, metavar="P",
                    help="--gpca-assoc-pheno: the first P columns of the scores this run writes are covariates (0 <= P <= "
                         "--eigensnp-k-global) [default: every column]")
@@ -391,11 +396,15 @@ def _pcrelate(eng, a, fs, cols, sample_ids, V, inset, n_snps):
 ASSOC_NEEDS_RESIDENT = ("error: --gpca-assoc-pheno needs the genotype matrix resident on the device: the scan of a matrix walked out of "
                         "core is not implemented")
 ASSOC_MAX_COLUMNS = 64
+# why gpca_logistic_null refuses a trait, by status (BAD_ARG, NOT_CONVERGED)
+LOGISTIC_NULL_FAILURES = {-1: "the included samples hold one class only, or a covariate is constant or collinear over them",
+                          -6: "Newton's method does not converge: the covariates separate the cases from the controls"}
 
 
 def _assoc_tables(a):
     """The phenotype and covariate tables of --gpca-assoc-pheno / --gpca-assoc-covar, read once before any work on the device; refuses
-    more than 64 columns (traits + PCs + covariates).  Returns (pheno, covar or None)."""
+    more than 64 columns (traits + PCs + covariates; with --gpca-assoc-logistic the quantitative traits only, and PCs + covariates + 3
+    when a column is binary).  Returns (pheno, covar or None)."""
     def table(flag, path):
         try:
             return gio.read_pheno(path)
@@ -407,6 +416,11 @@ def _assoc_tables(a):
     covar = None if a.gpca_assoc_covar is None else table("--gpca-assoc-covar", a.gpca_assoc_covar)
     t, c = len(pheno.names), 0 if covar is None else len(covar.names)
     p = a.eigensnp_k_global if a.gpca_assoc_pcs is None else a.gpca_assoc_pcs
+    if a.gpca_assoc_logistic:
+        nb = sum(gio.binary_trait(pheno.values[:, j]) is not None for j in range(t))
+        if nb and p + c + 3 > ASSOC_MAX_COLUMNS:
+            raise SystemExit(f"error: --gpca-assoc-logistic: {p} PCs + {c} covariates + 3 are more than {ASSOC_MAX_COLUMNS} columns")
+        t -= nb                                                                      # the linear scan takes the quantitative traits
     if t + p + c > ASSOC_MAX_COLUMNS:
         raise SystemExit(f"error: --gpca-assoc-pheno: {t} traits + {p} PCs + {c} covariates are more than {ASSOC_MAX_COLUMNS} columns")
     return pheno, covar
@@ -437,25 +451,57 @@ def _assoc(eng, a, fs, cols, sample_ids, scores, inset, st):
         raise SystemExit(f"error: --gpca-assoc-pheno: {n_inc} samples have every trait and covariate, which leaves no degree of freedom "
                          f"beside {Pc} covariates")
     vif = 50.0 if a.gpca_assoc_vif is None else a.gpca_assoc_vif
+    # --gpca-assoc-logistic: the binary columns (recoded to 0 / 1) leave the linear scan for the score scan
+    names, bnames, Yb = list(pheno.names), [], np.zeros((n, 0))
+    if a.gpca_assoc_logistic:
+        coded = [gio.binary_trait(pheno.values[:, j]) for j in range(T)]
+        shift = [0.0 if c is None else float(np.nanmin(pheno.values[:, j])) for j, c in enumerate(coded)]
+        bcols = [j for j in range(T) if coded[j] is not None]
+        bnames = [names[j] for j in bcols]
+        Yb = np.ascontiguousarray(np.where(include[:, None], Y[:, bcols] - np.asarray([shift[j] for j in bcols])[None, :], 0.0), np.float64)
+        qcols = [j for j in range(T) if coded[j] is None]
+        names, Y = [names[j] for j in qcols], np.ascontiguousarray(Y[:, qcols])
+        for j, name in enumerate(bnames):                                            # before any file of the trait is written
+            try:
+                GpcaEngine.logistic_null(Yb[:, j], C, include)
+            except _lib.GpcaError as e:
+                why = LOGISTIC_NULL_FAILURES.get(e.status, e.message)
+                raise SystemExit(f"error: --gpca-assoc-logistic: trait {name}: the null model cannot be fitted ({why})") from None
+    T = Y.shape[1]
     eng.set_standardization(st["mu"], st["sigma"], st["keep"])                       # every SNP that passes the SNP QC
     rows = np.flatnonzero(st["keep"])
     lib = _lib.load()
+
+    def meta_of(r0, r1):
+        rr = rows[r0:r1]
+        return ([fs.chromosomes[i] for i in rr], [int(fs.positions[i]) for i in rr], [fs.variant_ids[i] for i in rr], [fs.allele1[i] for i in rr])
     try:
-        for bi, (r0, r1) in enumerate(gio.assoc_bands(len(rows), T + Pc)):
+        for bi, (r0, r1) in enumerate(gio.assoc_bands(len(rows), T + Pc) if T else []):
             r = eng.assoc_linear(Y, C, include=include, max_vif=vif, rows=(r0, r1))
-            rr = rows[r0:r1]
-            meta = ([fs.chromosomes[i] for i in rr], [int(fs.positions[i]) for i in rr], [fs.variant_ids[i] for i in rr],
-                    [fs.allele1[i] for i in rr])
-            for t, name in enumerate(pheno.names):
+            meta = meta_of(r0, r1)
+            for t, name in enumerate(names):
                 tt = r["t"][:, t]
                 lp = [float("nan") if v != v else lib.gpca_student_t_log10p(float(v), float(df)) for v in tt]
                 gio.write_assoc(a.output_prefix, name, *meta, r["n_obs"], r["a1_freq"], r["beta"][:, t], r["se"][:, t], tt, lp, append=bi > 0)
+        for t0, t1 in (gio.assoc_score_groups(len(bnames), Pc) if bnames else []):
+            Yg = np.ascontiguousarray(Yb[:, t0:t1])
+            for bi, (r0, r1) in enumerate(gio.assoc_score_bands(len(rows), t1 - t0, Pc)):
+                r = eng.assoc_logistic_score(Yg, C, include=include, max_vif=vif, rows=(r0, r1))
+                meta = meta_of(r0, r1)
+                for t in range(t1 - t0):
+                    zz = r["z"][:, t]
+                    lp = [float("nan") if v != v else lib.gpca_normal_log10p(float(v)) for v in zz]
+                    gio.write_assoc_logistic(a.output_prefix, bnames[t0 + t], *meta, r["n_obs"], r["a1_freq"], r["beta"][:, t], r["se"][:, t], zz,
+                                             lp, append=bi > 0)
     except _lib.GpcaError as e:
         if e.status == _lib.GPCA_ERR_STATE:
             raise SystemExit(ASSOC_NEEDS_RESIDENT) from None
         raise
     _log(f"association scan of {len(rows)} SNPs against {T} traits with {Pc} covariates ({P} PCs) on {n_inc} of {n} samples, written to "
          f"{a.output_prefix}.<trait>.assoc.linear")
+    if bnames:
+        _log(f"logistic score scan of {len(rows)} SNPs against {len(bnames)} case / control traits with {Pc} covariates on {n_inc} of {n} "
+             f"samples, written to {a.output_prefix}.<trait>.assoc.logistic")
 
 
 def _indep_pairwise(eng, a, fs, st, keep, by_tag):
@@ -547,6 +593,8 @@ def main(argv=None) -> int:
             raise SystemExit(PCRELATE_NEEDS_RESIDENT)
     if a.gpca_assoc_pheno is None and (a.gpca_assoc_pcs is not None or a.gpca_assoc_covar is not None or a.gpca_assoc_vif is not None):
         raise SystemExit("error: --gpca-assoc-pcs, --gpca-assoc-covar and --gpca-assoc-vif need --gpca-assoc-pheno")
+    if a.gpca_assoc_logistic and a.gpca_assoc_pheno is None:
+        raise SystemExit("error: --gpca-assoc-logistic needs --gpca-assoc-pheno")
     if a.gpca_assoc_pheno is not None:
         if not a.eigensnp:
             raise SystemExit("error: --gpca-assoc-pheno needs the --eigensnp workflow")

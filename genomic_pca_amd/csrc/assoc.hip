@@ -1,5 +1,6 @@
 // Linear association scan (gpca_assoc_linear; gpca_assoc.cpp): ordinary least squares of T traits on (1, C, g) for every kept row g,
-// a missing call imputed to the row's mean over the included samples.
+// a missing call imputed to the row's mean over the included samples.  (The staging helpers live in assoc_stage.h, shared with
+// assoc_score.hip.)
 //
 // The host hands over B = [Y~ | Q] (N x L, L = T + Pc <= 64, f32; every column sums to 0 over the included samples and is 0 outside
 // them), transposed and zero-padded to [asc_lpad(L)][asc_npad(N)], and the include mask as one bit per sample.  With o = [observed and
@@ -22,69 +23,13 @@
 // Epilogue (f64, no contraction): mbar = s1 / n_obs, xb_ij = d_ij + mbar * e_ij.  k_assoc_finish (one thread per row): xx = s2 - s1 *
 // mbar, sxx = xx - sum_{j >= T} xb_ij^2 (j ascending), and per trait beta = xb / sxx, rss = yy - xb * beta, se = sqrt(rss / df / sxx),
 // t = beta / se; NaN when n_obs = 0, xx <= 0, sxx * max_vif < xx or rss <= 0.
-// Out of scope: logistic regression and case / control traits, per-variant dropping of samples with a missing call, per-trait sample
-// sets, mixed models that use the GRM, streamed and row-sharded handles.
-#include "gemm_i8_common.h"
+// Out of scope: case / control traits (assoc_score.hip has their score test), per-variant dropping of samples with a missing call,
+// per-trait sample sets, mixed models that use the GRM, streamed and row-sharded handles.
+#include "assoc_stage.h"
 
 #pragma clang fp contract(off)
 
 namespace gpca {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr unsigned kAscMissing = 0x81u;             // the int8 missing code (-127) as a byte
-
-// the 32 samples a thread stages: 8 dwords of call bytes (int8 storage: as stored; 2-bit: decoded, 3 -> the missing code)
-struct AscFetch { unsigned w[8]; };
-
-template <bool PACKED>
-__device__ __forceinline__ void asc_fetch(AscFetch& F, const uint8_t* __restrict__ G, int64_t ldr, int64_t orow, int64_t ns) {
-    if (orow < 0) {
-#pragma unroll
-        for (int d = 0; d < 8; ++d) F.w[d] = 0u;
-        return;
-    }
-    if (PACKED) {
-        // (ns is a multiple of 32 and ld2 of 256: the 8 bytes are aligned and inside the row's pitch, see asc_* in plan_math.h)
-        const uint2 v = *reinterpret_cast<const uint2*>(G + orow * ldr + (ns >> 2));
-#pragma unroll
-        for (int d = 0; d < 8; ++d) {
-            const unsigned b = ((d < 4 ? v.x : v.y) >> (8 * (d & 3))) & 0xffu;
-            const unsigned dd = (b & 3u) | ((b & 0xcu) << 6) | ((b & 0x30u) << 12) | ((b & 0xc0u) << 18);
-            const unsigned m = dd & (dd >> 1) & 0x01010101u;
-            F.w[d] = (dd & ~(m * 3u)) | (m * kAscMissing);
-        }
-    } else {
-        const uint4 a = *reinterpret_cast<const uint4*>(G + orow * ldr + ns);
-        const uint4 b = *reinterpret_cast<const uint4*>(G + orow * ldr + ns + 16);
-        F.w[0] = a.x; F.w[1] = a.y; F.w[2] = a.z; F.w[3] = a.w; F.w[4] = b.x; F.w[5] = b.y; F.w[6] = b.z; F.w[7] = b.w;
-    }
-}
-
-// checks, masks and counts the thread's 32 samples and writes them to the stage's buffer.  inb: bit s = sample s lies below N;
-// inc: bit s = sample s is included (zero past N).
-__device__ __forceinline__ void asc_put(const AscFetch& F, unsigned inb, unsigned inc, uint8_t* dst, unsigned& nobs, unsigned& s1,
-                                        unsigned& s2, unsigned& bd) {
-    unsigned o[8];
-#pragma unroll
-    for (int d = 0; d < 8; ++d) {
-        const unsigned vb = (((inb >> (4 * d)) & 0xfu) * 0x00204081u & 0x01010101u) * 0xffu;
-        const unsigned ib = (((inc >> (4 * d)) & 0xfu) * 0x00204081u & 0x01010101u) * 0xffu;
-        const unsigned a = F.w[d] & vb;
-        // valid bytes: 0, 1, 2 and the missing code
-        const unsigned m = (a >> 7) & 0x01010101u, g = a & ~(m * 0xffu);
-        if ((a & (m * 0xffu)) != m * kAscMissing || (g & 0xfcfcfcfcu) != 0u || (g & (g >> 1) & 0x01010101u) != 0u) bd = 1u;
-        const unsigned ai = a & ib, mi = (ai >> 7) & 0x01010101u, gi = ai & ~(mi * 0xffu);
-        const unsigned c1 = __builtin_popcount(gi & 0x01010101u), c2 = __builtin_popcount(gi & 0x02020202u);
-        nobs += __builtin_popcount((inc >> (4 * d)) & 0xfu) - __builtin_popcount(mi);
-        s1 += c1 + 2u * c2;
-        s2 += c1 + 4u * c2;
-        o[d] = ai;
-    }
-#pragma unroll
-    for (int d = 0; d < 4; ++d) *reinterpret_cast<uint2*>(dst + 8 * d) = make_uint2(o[2 * d], o[2 * d + 1]);
-}
 
 template <int NB>
 struct AscSmem {
@@ -92,24 +37,6 @@ struct AscSmem {
     float b[2][NB * 32 * kAscBPitch];
     unsigned sums[kAscRows * 3];
 };
-
-// Bt [32 NB][npad]: the panel of a stage is 32 NB columns x 16 float4
-template <int NB>
-__device__ __forceinline__ void asc_fetch_b(f32x4 (&P)[2 * NB], const float* __restrict__ Bt, int64_t npad, int64_t n0) {
-#pragma unroll
-    for (int i = 0; i < 2 * NB; ++i) {
-        const int idx = threadIdx.x + kAscThreads * i;
-        P[i] = *reinterpret_cast<const f32x4*>(Bt + (int64_t)(idx >> 4) * npad + n0 + 4 * (idx & 15));
-    }
-}
-template <int NB>
-__device__ __forceinline__ void asc_put_b(const f32x4 (&P)[2 * NB], float* dst) {
-#pragma unroll
-    for (int i = 0; i < 2 * NB; ++i) {
-        const int idx = threadIdx.x + kAscThreads * i;
-        *reinterpret_cast<f32x4*>(dst + (idx >> 4) * kAscBPitch + 4 * (idx & 15)) = P[i];
-    }
-}
 
 // xb [row1 - row0][L] f64, sums [row1 - row0][3] u32 of kept rows [row0, row1); *bad = min original row with a value outside
 // {0, 1, 2, missing}

@@ -356,4 +356,17 @@ int launch_assoc(hipStream_t st, const void* G, int packed, int64_t ldr, const i
 void launch_assoc_finish(hipStream_t st, const double* xb, const unsigned* sums, const double* yy, int T, int L, double df, double max_vif,
                          int64_t rows, double* stats, double* info);
 
+// ---- logistic score scan: kept rows x T (Pc + 3) panel columns over the samples, the operand coded by the minor allele (assoc_score.hip)
+// sums [row1 - row0][3] u32 = n_obs, sum g o, sum g^2 o; *bad as in launch_assoc
+int launch_assoc_score_count(hipStream_t st, const void* G, int packed, int64_t ldr, const int64_t* krows, int64_t N, const unsigned* incw,
+                             int64_t row0, int64_t row1, unsigned* sums, unsigned long long* bad);
+// Bt [asc_lpad(L)][asc_npad(N)] f32, L = T (Pc + 3), columns in the order of asr_col_* (plan_math.h); sums: the count kernel's, same band;
+// dv [row1 - row0][L] f64 = d + xbar e, and q + xbar^2 e in the w columns
+int launch_assoc_score(hipStream_t st, const void* G, int packed, int64_t ldr, const int64_t* krows, int64_t N, const float* Bt,
+                       const unsigned* incw, int T, int L, int64_t row0, int64_t row1, const unsigned* sums, double* dv);
+// stats [rows][T][5] = beta, se, z, vw, V; ua [rows][T][Pc + 3] = U, gwg, a_0 .. a_Pc; info [rows][5] = n_obs, a1_freq, xx, flipped, 0
+// (each may be NULL)
+void launch_assoc_score_finish(hipStream_t st, const double* dv, const unsigned* sums, int T, int Pc, double max_vif, int64_t rows,
+                               double* stats, double* ua, double* info);
+
 }  // namespace gpca

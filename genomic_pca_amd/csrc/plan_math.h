@@ -298,4 +298,26 @@ constexpr int64_t asc_sums_capacity(int64_t rows) { return 3 * rows; }
 constexpr int64_t asc_stats_capacity(int64_t rows, int T) { return 3 * rows * (int64_t)T; }
 constexpr int64_t asc_info_capacity(int64_t rows) { return 4 * rows; }
 
+// ---- logistic score scan (assoc_score.hip, gpca_assoc_score.cpp) ------------------------------------------------------------------
+// The tile, the stages and the flush groups are k_assoc's (kAsc*, asc_npad, asc_stages, asc_row_blocks, asc_lpad, asc_b_capacity,
+// asc_inc_capacity).  The panel holds Pc + 3 columns per trait, L = T (Pc + 3) <= kAsrMaxCols: the T columns w_t first (the product
+// with the squared operand needs no other, and T <= 21 keeps them in the first block of 32), then the T columns r_t, then
+// A_t,0 .. A_t,Pc trait by trait.  k_assoc_score_count: a wave counts one row, a lane 32 samples of each chunk of kAsrChunk.
+constexpr int kAsrMaxCols = 64, kAsrCountRows = 4, kAsrCountThreads = 64 * kAsrCountRows, kAsrChunk = 64 * 32;
+static_assert(kAsrMaxCols == kAscMaxCols && kAsrChunk % kAscStage == 0, "the score scan stages its panel as k_assoc does");
+constexpr int asr_cols(int T, int Pc) { return T * (Pc + 3); }
+constexpr int asr_max_traits(int Pc) { return kAsrMaxCols / (Pc + 3); }
+constexpr int asr_col_w(int t) { return t; }
+constexpr int asr_col_r(int T, int t) { return T + t; }
+constexpr int asr_col_a(int T, int Pc, int t, int j) { return 2 * T + t * (Pc + 1) + j; }
+constexpr int64_t asr_count_blocks(int64_t rows) { return (rows + kAsrCountRows - 1) / kAsrCountRows; }
+constexpr int64_t asr_count_chunks(int64_t N) { return (asc_npad(N) + kAsrChunk - 1) / kAsrChunk; }
+// elements of the call's own buffers: dv [rows][L] (f64, the panel's column order, gwg_t in the place of w_t); the per-row sums
+// [rows][3] (u32); stats [rows][T][5], ua [rows][T][Pc + 3] and rowinfo [rows][5] (f64)
+constexpr int64_t asr_dv_capacity(int64_t rows, int L) { return rows * (int64_t)L; }
+constexpr int64_t asr_sums_capacity(int64_t rows) { return 3 * rows; }
+constexpr int64_t asr_stats_capacity(int64_t rows, int T) { return 5 * rows * (int64_t)T; }
+constexpr int64_t asr_ua_capacity(int64_t rows, int T, int Pc) { return rows * (int64_t)asr_cols(T, Pc); }
+constexpr int64_t asr_info_capacity(int64_t rows) { return 5 * rows; }
+
 }  // namespace gpca

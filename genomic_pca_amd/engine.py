@@ -545,6 +545,71 @@ class GpcaEngine:
         """-log10 of the two-sided p-value of a Student t statistic (gpca_student_t_log10p; host only, no underflow)."""
         return float(_lib.load().gpca_student_t_log10p(float(t), float(df)))
 
+    def assoc_logistic_score(self, Y, covar=None, include=None, max_vif: float = 50.0, rows: Optional[Tuple[int, int]] = None, ua: bool = False):
+        """Logistic score scan (gpca_assoc_logistic_score): the score test of every case / control trait (column of Y [N][T], 0 / 1 on
+        the included samples) for the kept rows [row0, row1) in PCA-SNP order (default: all), the null model logit P(y = 1) = (1, covar)
+        alpha fitted once per trait; covar [N][Pc] or None, T (Pc + 3) <= 64; include: bool / uint8 [N], None = everyone.  A missing
+        call is imputed to the row's mean over the included samples.  Returns a dict: beta, se, z, vw, V [rows][T]; n_obs, a1_freq, xx,
+        flipped [rows]; with ua=True also ua [rows][T][Pc + 3] = U, gwg, a_0 .. a_Pc in the operand's coding (2 - g on a flipped row).
+        beta, se and z (for allele A1) are NaN for a row with no observed call, no variance, V <= 0 or a variance inflation above
+        max_vif."""
+        N = self.dims()[1]
+        Yv = np.ascontiguousarray(Y, np.float64)
+        if Yv.ndim == 1:
+            Yv = Yv.reshape(-1, 1)
+        if Yv.ndim != 2 or Yv.shape[0] != N:
+            raise ValueError("Y must be [N][T]: one row of traits per sample")
+        Cv = np.ascontiguousarray(np.zeros((N, 0)) if covar is None else covar, np.float64)
+        if Cv.ndim == 1:
+            Cv = Cv.reshape(N, 0) if Cv.size == 0 else Cv.reshape(-1, 1)
+        if Cv.ndim != 2 or Cv.shape[0] != N:
+            raise ValueError("covar must be [N][Pc]: one row of covariates per sample")
+        inc = None if include is None else np.ascontiguousarray(np.asarray(include) != 0, np.uint8)
+        if inc is not None and inc.shape != (N,):
+            raise ValueError("include must have one entry per sample")
+        T, Pc = Yv.shape[1], Cv.shape[1]
+        K = int(self._lib.gpca_num_pca_snps(self._h))
+        r0, r1 = (0, K) if rows is None else (int(rows[0]), int(rows[1]))
+        n = max(r1 - r0, 0)
+        stats = np.zeros((max(n, 1), max(T, 1), 5), np.float64)
+        info = np.zeros((max(n, 1), 5), np.float64)
+        out_ua = np.zeros((max(n, 1), max(T, 1), Pc + 3), np.float64) if ua else None
+        self._chk(self._lib.gpca_assoc_logistic_score(self._h, _vp(Yv), T, _vp(Cv) if Pc else None, Pc, _vp(inc), float(max_vif), r0, r1,
+                                                      _vp(stats), _vp(out_ua), _vp(info)))
+        res = {"beta": stats[:n, :, 0], "se": stats[:n, :, 1], "z": stats[:n, :, 2], "vw": stats[:n, :, 3], "V": stats[:n, :, 4],
+               "n_obs": info[:n, 0], "a1_freq": info[:n, 1], "xx": info[:n, 2], "flipped": info[:n, 3]}
+        if ua:
+            res["ua"] = out_ua[:n]
+        return res
+
+    @staticmethod
+    def logistic_null(y, covar=None, include=None):
+        """The null logistic model of one case / control trait (gpca_logistic_null; host only): y [N] in {0, 1} on the included samples,
+        covar [N][Pc] or None.  Returns (alpha [Pc + 1] in the coordinates of the standardised design, mu [N] with 0 outside the
+        included samples, Newton steps); raises GpcaError (BAD_ARG: the inputs; NOT_CONVERGED: 25 steps or separation)."""
+        yv = np.ascontiguousarray(y, np.float64).reshape(-1)
+        N = yv.shape[0]
+        Cv = np.ascontiguousarray(np.zeros((N, 0)) if covar is None else covar, np.float64)
+        if Cv.ndim == 1:
+            Cv = Cv.reshape(N, 0) if Cv.size == 0 else Cv.reshape(-1, 1)
+        if Cv.ndim != 2 or Cv.shape[0] != N:
+            raise ValueError("covar must be [N][Pc]: one row of covariates per sample")
+        inc = None if include is None else np.ascontiguousarray(np.asarray(include) != 0, np.uint8)
+        if inc is not None and inc.shape != (N,):
+            raise ValueError("include must have one entry per sample")
+        Pc = Cv.shape[1]
+        alpha, mu, it = np.zeros(Pc + 1), np.zeros(max(N, 1)), C.c_int32(0)
+        lib = _lib.load()
+        rc = lib.gpca_logistic_null(_vp(yv), _vp(Cv) if Pc else None, Pc, _vp(inc), N, _vp(alpha), _vp(mu), C.byref(it))
+        if rc != 0:
+            raise GpcaError(rc, "gpca_logistic_null: " + lib.gpca_status_string(rc).decode())
+        return alpha, mu[:N], int(it.value)
+
+    @staticmethod
+    def normal_log10p(z: float) -> float:
+        """-log10 of the two-sided p-value of a standard normal statistic (gpca_normal_log10p; host only, no underflow)."""
+        return float(_lib.load().gpca_normal_log10p(float(z)))
+
     # -- f3: the stages of EigenSNPCoreAlgorithm (gpca.h)
     def copy_rows_from(self, src: "GpcaEngine", row0: int, rows: int):
         """This engine receives rows [row0, row0 + rows) of src's resident matrix (device to device)."""

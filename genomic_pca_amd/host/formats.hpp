@@ -854,6 +854,55 @@ private:
     OutFile o_;
 };
 
+// ---- logistic score scan: the twins of io.binary_trait, io.assoc_score_groups, io.assoc_score_bands and io.write_assoc_logistic ------
+// true when column c of the table is binary: its present (non-NaN) values are exactly {0, 1} (1 = case) or exactly {1, 2} (plink's
+// coding, 2 = case); *shift = what to take off a value to reach the 0 / 1 coding.  A column with one class only is not binary.
+inline bool binary_trait(const PhenoTable& t, size_t c, double* shift) {
+    const size_t nc = t.names.size();
+    bool has[3] = {false, false, false};
+    for (size_t r = 0; r * nc + c < t.values.size(); ++r) {
+        const double v = t.values[r * nc + c];
+        if (v != v) continue;
+        if (v == 0.0) has[0] = true; else if (v == 1.0) has[1] = true; else if (v == 2.0) has[2] = true; else return false;
+    }
+    if (has[0] && has[1] && !has[2]) { if (shift) *shift = 0.0; return true; }
+    if (!has[0] && has[1] && has[2]) { if (shift) *shift = 1.0; return true; }
+    return false;
+}
+
+constexpr int64_t kAssocScoreMaxColumns = 64;
+// [t0, t1) groups of T case / control traits, floor(64 / (Pc + 3)) to a group
+inline std::vector<std::pair<int64_t, int64_t>> assoc_score_groups(int64_t T, int64_t Pc) {
+    const int64_t g = kAssocScoreMaxColumns / (Pc + 3);
+    if (g < 1) throw std::runtime_error(std::to_string(Pc) + " covariates + 3 are more than " + std::to_string(kAssocScoreMaxColumns) + " columns");
+    std::vector<std::pair<int64_t, int64_t>> out;
+    for (int64_t t0 = 0; t0 < T; t0 += g) out.emplace_back(t0, std::min(t0 + g, T));
+    return out;
+}
+inline std::vector<std::pair<int64_t, int64_t>> assoc_score_bands(int64_t K, int64_t T, int64_t Pc, int64_t max_values = (int64_t)1 << 26) {
+    return assoc_bands(K, T * (Pc + 3), max_values);
+}
+
+// P.<trait>.assoc.logistic: one tab-separated line per SNP, `#CHROM POS ID A1 OBS_CT A1_FREQ BETA SE Z_STAT LOG10P`; numbers as %.6g,
+// NaN as NA, OBS_CT as an integer; rows are added band by band
+class AssocLogisticWriter {
+public:
+    AssocLogisticWriter(const std::string& prefix, const std::string& trait) : o_(prefix + "." + trait + ".assoc.logistic") {
+        std::fputs("#CHROM\tPOS\tID\tA1\tOBS_CT\tA1_FREQ\tBETA\tSE\tZ_STAT\tLOG10P\n", o_.f);
+    }
+    void add_row(const std::string& chrom, int64_t pos, const std::string& id, const std::string& a1, double n_obs, double a1_freq, double beta,
+                 double se, double z, double log10p) {
+        char b[5][48];
+        const double v[5] = {a1_freq, beta, se, z, log10p};
+        for (int i = 0; i < 5; ++i) { if (v[i] != v[i]) std::snprintf(b[i], sizeof b[i], "NA"); else std::snprintf(b[i], sizeof b[i], "%.6g", v[i]); }
+        std::fprintf(o_.f, "%s\t%lld\t%s\t%s\t%lld\t%s\t%s\t%s\t%s\t%s\n", chrom.c_str(), (long long)pos, id.c_str(), a1.c_str(), (long long)n_obs, b[0], b[1],
+                     b[2], b[3], b[4]);
+    }
+
+private:
+    OutFile o_;
+};
+
 }  // namespace gpca_host
 
 #endif

@@ -57,6 +57,7 @@ struct Args {
     double indep_r2 = 0.0;
     std::string assoc_pheno, assoc_covar;   // --gpca-assoc-pheno FILE (turns the association scan on), --gpca-assoc-covar FILE
     bool have_assoc_pcs = false, have_assoc_vif = false;
+    bool assoc_logistic = false;      // --gpca-assoc-logistic: binary trait columns go through the logistic score scan
     int64_t assoc_pcs = 0;            // --gpca-assoc-pcs P [default: every column of the scores]
     double assoc_vif = 50.0;          // --gpca-assoc-vif X
     gpca_host::PhenoTable assoc_pheno_table, assoc_covar_table;   // read in main, before any work on the device
@@ -154,6 +155,11 @@ void print_help() {
         "                                       counts when every trait and covariate is present for it and, with --gpca-king-cutoff,\n"
         "                                       it is in the in-set.  Needs the matrix resident on the device; traits + PCs +\n"
         "                                       covariates <= 64\n"
+        "      --gpca-assoc-logistic            --gpca-assoc-pheno: a trait column whose present values are exactly {0, 1} (1 = case) or\n"
+        "                                       {1, 2} (plink's coding, 2 = case) gets the logistic score test (the null model fitted\n"
+        "                                       once per trait, no Firth / SPA correction) -> P.<trait>.assoc.logistic (#CHROM POS ID A1\n"
+        "                                       OBS_CT A1_FREQ BETA SE Z_STAT LOG10P); the other columns go through the linear scan as\n"
+        "                                       without the flag.  PCs + covariates + 3 <= 64\n"
         "      --gpca-assoc-pcs <P>             --gpca-assoc-pheno: the first P columns of the scores this run writes are covariates\n"
         "                                       (0 <= P <= --eigensnp-k-global) [default: every column]\n"
         "      --gpca-assoc-covar <FILE>        --gpca-assoc-pheno: further covariates, a table in the format of the phenotype file\n"
@@ -234,6 +240,7 @@ Args parse(int argc, char** argv) {
         else if (f == "--gpca-pcrelate-table-filter") { a.pcrelate_filter = to_f64(f, val()); a.have_pcrelate_filter = true; }
         else if (f == "--gpca-assoc-pheno") a.assoc_pheno = val();
         else if (f == "--gpca-assoc-covar") a.assoc_covar = val();
+        else if (f == "--gpca-assoc-logistic") a.assoc_logistic = true;
         else if (f == "--gpca-assoc-pcs") { a.assoc_pcs = to_i64(f, val()); a.have_assoc_pcs = true; }
         else if (f == "--gpca-assoc-vif") { a.assoc_vif = to_f64(f, val()); a.have_assoc_vif = true; }
         else if (f == "--gpca-indep-pairwise") {
@@ -393,22 +400,81 @@ int run_assoc(gpca::Engine& eng, const Args& a, const gpca_host::PlinkFileset& f
                      (long long)n_inc, (int)Pc);
         return 1;
     }
+    // --gpca-assoc-logistic: the binary columns (recoded to 0 / 1) leave the linear scan for the score scan
+    const int32_t Tall = T;
+    std::vector<std::string> names = a.assoc_pheno_table.names, bnames;
+    std::vector<double> Yq = Y, Yb;
+    int32_t Tq = Tall, Tb = 0;
+    if (a.assoc_logistic) {
+        std::vector<int32_t> qcols, bcols;
+        std::vector<double> shift;
+        for (int32_t j = 0; j < Tall; ++j) {
+            double sh = 0.0;
+            if (gpca_host::binary_trait(a.assoc_pheno_table, (size_t)j, &sh)) { bcols.push_back(j); shift.push_back(sh); } else qcols.push_back(j);
+        }
+        Tq = (int32_t)qcols.size(); Tb = (int32_t)bcols.size();
+        names.clear();
+        for (int32_t j : qcols) names.push_back(a.assoc_pheno_table.names[(size_t)j]);
+        for (int32_t j : bcols) bnames.push_back(a.assoc_pheno_table.names[(size_t)j]);
+        Yq.assign((size_t)n * (size_t)Tq + 1, 0.0); Yb.assign((size_t)n * (size_t)Tb + 1, 0.0);
+        for (int64_t s = 0; s < n; ++s) {
+            for (int32_t j = 0; j < Tq; ++j) Yq[(size_t)s * Tq + j] = Y[(size_t)s * Tall + qcols[(size_t)j]];
+            for (int32_t j = 0; j < Tb; ++j) Yb[(size_t)s * Tb + j] = include[(size_t)s] ? Y[(size_t)s * Tall + bcols[(size_t)j]] - shift[(size_t)j] : 0.0;
+        }
+        for (int32_t j = 0; j < Tb; ++j) {                                            // before any file of the trait is written
+            std::vector<double> y((size_t)n), alpha, mu;
+            for (int64_t s = 0; s < n; ++s) y[(size_t)s] = Yb[(size_t)s * Tb + j];
+            try { gpca::Engine::logistic_null(y, C, Pc, &include, alpha, mu); }
+            catch (const gpca::Error& e) {
+                // (cli.py:LOGISTIC_NULL_FAILURES)
+                const char* why = e.status() == GPCA_ERR_BAD_ARG ? "the included samples hold one class only, or a covariate is constant or collinear over them"
+                                  : e.status() == GPCA_ERR_NOT_CONVERGED ? "Newton's method does not converge: the covariates separate the cases from the controls"
+                                                                         : gpca_status_string(e.status());
+                std::fprintf(stderr, "error: --gpca-assoc-logistic: trait %s: the null model cannot be fitted (%s)\n", bnames[(size_t)j].c_str(), why);
+                return 1;
+            }
+        }
+    }
     eng.set_standardization(st.mu, st.sigma, st.keep);                                // every SNP that passes the SNP QC
     std::vector<int64_t> rows;
     for (size_t i = 0; i < st.keep.size(); ++i) if (st.keep[i]) rows.push_back((int64_t)i);
-    std::vector<std::unique_ptr<gpca_host::AssocWriter>> w;
     gpca_host::ensure_parent(a.output_prefix);
-    for (int32_t t = 0; t < T; ++t) w.emplace_back(new gpca_host::AssocWriter(a.output_prefix, a.assoc_pheno_table.names[(size_t)t]));
     try {
-        for (const auto& b : gpca_host::assoc_bands((int64_t)rows.size(), T + Pc)) {
-            std::vector<double> stats, info;
-            eng.assoc_linear(Y, T, C, Pc, &include, a.assoc_vif, b.first, b.second, stats, info);
-            for (int64_t r = b.first; r < b.second; ++r) {
-                const size_t i = (size_t)(r - b.first), o = (size_t)rows[(size_t)r];
-                for (int32_t t = 0; t < T; ++t) {
-                    const double* s3 = &stats[(i * (size_t)T + (size_t)t) * 3];
-                    const double lp = s3[2] != s3[2] ? std::nan("") : gpca_student_t_log10p(s3[2], (double)df);
-                    w[(size_t)t]->add_row(fs.chromosomes[o], fs.positions[o], fs.variant_ids[o], fs.allele1[o], info[4 * i], info[4 * i + 1], s3[0], s3[1], s3[2], lp);
+        if (Tq) {
+            std::vector<std::unique_ptr<gpca_host::AssocWriter>> w;
+            for (int32_t t = 0; t < Tq; ++t) w.emplace_back(new gpca_host::AssocWriter(a.output_prefix, names[(size_t)t]));
+            for (const auto& b : gpca_host::assoc_bands((int64_t)rows.size(), Tq + Pc)) {
+                std::vector<double> stats, info;
+                eng.assoc_linear(Yq, Tq, C, Pc, &include, a.assoc_vif, b.first, b.second, stats, info);
+                for (int64_t r = b.first; r < b.second; ++r) {
+                    const size_t i = (size_t)(r - b.first), o = (size_t)rows[(size_t)r];
+                    for (int32_t t = 0; t < Tq; ++t) {
+                        const double* s3 = &stats[(i * (size_t)Tq + (size_t)t) * 3];
+                        const double lp = s3[2] != s3[2] ? std::nan("") : gpca_student_t_log10p(s3[2], (double)df);
+                        w[(size_t)t]->add_row(fs.chromosomes[o], fs.positions[o], fs.variant_ids[o], fs.allele1[o], info[4 * i], info[4 * i + 1], s3[0], s3[1], s3[2], lp);
+                    }
+                }
+            }
+        }
+        if (Tb) {
+            for (const auto& g : gpca_host::assoc_score_groups(Tb, Pc)) {
+                const int32_t Tg = (int32_t)(g.second - g.first);
+                std::vector<double> Yg((size_t)n * (size_t)Tg);
+                for (int64_t s = 0; s < n; ++s)
+                    for (int32_t t = 0; t < Tg; ++t) Yg[(size_t)s * Tg + t] = Yb[(size_t)s * Tb + (size_t)g.first + t];
+                std::vector<std::unique_ptr<gpca_host::AssocLogisticWriter>> w;
+                for (int32_t t = 0; t < Tg; ++t) w.emplace_back(new gpca_host::AssocLogisticWriter(a.output_prefix, bnames[(size_t)g.first + t]));
+                for (const auto& b : gpca_host::assoc_score_bands((int64_t)rows.size(), Tg, Pc)) {
+                    std::vector<double> stats, info;
+                    eng.assoc_logistic_score(Yg, Tg, C, Pc, &include, a.assoc_vif, b.first, b.second, stats, info);
+                    for (int64_t r = b.first; r < b.second; ++r) {
+                        const size_t i = (size_t)(r - b.first), o = (size_t)rows[(size_t)r];
+                        for (int32_t t = 0; t < Tg; ++t) {
+                            const double* s5 = &stats[(i * (size_t)Tg + (size_t)t) * 5];
+                            const double lp = s5[2] != s5[2] ? std::nan("") : gpca_normal_log10p(s5[2]);
+                            w[(size_t)t]->add_row(fs.chromosomes[o], fs.positions[o], fs.variant_ids[o], fs.allele1[o], info[5 * i], info[5 * i + 1], s5[0], s5[1], s5[2], lp);
+                        }
+                    }
                 }
             }
         }
@@ -417,11 +483,15 @@ int run_assoc(gpca::Engine& eng, const Args& a, const gpca_host::PlinkFileset& f
         std::fputs(kAssocNeedsResident, stderr);
         return 1;
     }
-    w.clear();
     char buf[512];
     std::snprintf(buf, sizeof buf, "association scan of %zu SNPs against %d traits with %d covariates (%d PCs) on %lld of %lld samples, written to %s.<trait>.assoc.linear",
-                  rows.size(), (int)T, (int)Pc, (int)P, (long long)n_inc, (long long)n, a.output_prefix.c_str());
+                  rows.size(), (int)Tq, (int)Pc, (int)P, (long long)n_inc, (long long)n, a.output_prefix.c_str());
     logmsg(buf);
+    if (Tb) {
+        std::snprintf(buf, sizeof buf, "logistic score scan of %zu SNPs against %d case / control traits with %d covariates on %lld of %lld samples, written to %s.<trait>.assoc.logistic",
+                      rows.size(), (int)Tb, (int)Pc, (long long)n_inc, (long long)n, a.output_prefix.c_str());
+        logmsg(buf);
+    }
     return 0;
 }
 
@@ -752,6 +822,7 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "error: --gpca-assoc-pcs, --gpca-assoc-covar and --gpca-assoc-vif need --gpca-assoc-pheno\n");
             return 2;
         }
+        if (a.assoc_logistic && a.assoc_pheno.empty()) { std::fprintf(stderr, "error: --gpca-assoc-logistic needs --gpca-assoc-pheno\n"); return 2; }
         if (!a.assoc_pheno.empty()) {
             if (!a.eigensnp) { std::fprintf(stderr, "error: --gpca-assoc-pheno needs the --eigensnp workflow\n"); return 2; }
             if (a.have_assoc_pcs && !(a.assoc_pcs >= 0 && a.assoc_pcs <= a.k_global)) {
@@ -770,8 +841,18 @@ int main(int argc, char** argv) {
                 try { a.assoc_covar_table = gpca_host::read_pheno(a.assoc_covar); }
                 catch (const std::runtime_error& e) { std::fprintf(stderr, "error: --gpca-assoc-covar: %s\n", e.what()); return 2; }
             }
-            const int64_t t = (int64_t)a.assoc_pheno_table.names.size(), c = (int64_t)a.assoc_covar_table.names.size();
-            const int64_t p = a.have_assoc_pcs ? a.assoc_pcs : a.k_global;
+            int64_t t = (int64_t)a.assoc_pheno_table.names.size();
+            const int64_t c = (int64_t)a.assoc_covar_table.names.size(), p = a.have_assoc_pcs ? a.assoc_pcs : a.k_global;
+            if (a.assoc_logistic) {
+                int64_t nb = 0;
+                for (size_t j = 0; j < a.assoc_pheno_table.names.size(); ++j) nb += gpca_host::binary_trait(a.assoc_pheno_table, j, nullptr);
+                if (nb && p + c + 3 > kAssocMaxColumns) {
+                    std::fprintf(stderr, "error: --gpca-assoc-logistic: %lld PCs + %lld covariates + 3 are more than %lld columns\n", (long long)p, (long long)c,
+                                 (long long)kAssocMaxColumns);
+                    return 2;
+                }
+                t -= nb;                                                              // the linear scan takes the quantitative traits
+            }
             if (t + p + c > kAssocMaxColumns) {
                 std::fprintf(stderr, "error: --gpca-assoc-pheno: %lld traits + %lld PCs + %lld covariates are more than %lld columns\n", (long long)t, (long long)p,
                              (long long)c, (long long)kAssocMaxColumns);

@@ -794,3 +794,51 @@ def write_assoc(prefix: str, trait: str, chromosomes: Sequence[str], positions: 
         f.writelines(f"{chromosomes[i]}\t{int(positions[i])}\t{variant_ids[i]}\t{allele1[i]}\t{int(n_obs[i])}\t{_g6(a1_freq[i])}\t{_g6(beta[i])}\t"
                      f"{_g6(se[i])}\t{_g6(t[i])}\t{_g6(log10p[i])}\n" for i in range(n))
     return path
+
+
+def binary_trait(values):
+    """None, or the 0 / 1 recoding (1 = case, NaN stays NaN) of a trait column that is binary: its present (non-NaN) values are exactly
+    {0, 1} (1 = case) or exactly {1, 2} (plink's coding, 2 = case).  A column with one class only is not binary."""
+    v = np.asarray(values, np.float64).reshape(-1)
+    present = set(np.unique(v[~np.isnan(v)]).tolist())
+    if present == {0.0, 1.0}:
+        return v.copy()
+    if present == {1.0, 2.0}:
+        return v - 1.0
+    return None
+
+
+ASSOC_SCORE_MAX_COLUMNS = 64
+
+
+def assoc_score_groups(T: int, Pc: int):
+    """[t0, t1) groups of T case / control traits, floor(64 / (Pc + 3)) to a group: what one gpca_assoc_logistic_score call takes."""
+    g = ASSOC_SCORE_MAX_COLUMNS // (Pc + 3)
+    if g < 1:
+        raise ValueError(f"{Pc} covariates + 3 are more than {ASSOC_SCORE_MAX_COLUMNS} columns")
+    return [(t0, min(t0 + g, T)) for t0 in range(0, T, g)]
+
+
+def assoc_score_bands(K: int, T: int, Pc: int, max_values: int = 1 << 26):
+    """[row0, row1) bands of the K kept rows for a group of T traits, sized as assoc_bands sizes them on the T (Pc + 3) panel columns."""
+    return assoc_bands(K, T * (Pc + 3), max_values)
+
+
+def write_assoc_logistic(prefix: str, trait: str, chromosomes: Sequence[str], positions: Sequence[int], variant_ids: Sequence[str],
+                         allele1: Sequence[str], n_obs, a1_freq, beta, se, z, log10p, append: bool = False) -> str:
+    """P.<trait>.assoc.logistic: one tab-separated line per SNP, `#CHROM POS ID A1 OBS_CT A1_FREQ BETA SE Z_STAT LOG10P`; numbers as
+    %.6g, NaN as NA, OBS_CT as an integer.  append=True adds the rows of a further band to the file (no header)."""
+    path = f"{prefix}.{trait}.assoc.logistic"
+    n = len(variant_ids)
+    for a in (chromosomes, positions, allele1, n_obs, a1_freq, beta, se, z, log10p):
+        if len(a) != n:
+            raise ValueError("write_assoc_logistic: one entry per SNP in every column")
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    with open(path, "a" if append else "w") as f:
+        if not append:
+            f.write("#CHROM\tPOS\tID\tA1\tOBS_CT\tA1_FREQ\tBETA\tSE\tZ_STAT\tLOG10P\n")
+        f.writelines(f"{chromosomes[i]}\t{int(positions[i])}\t{variant_ids[i]}\t{allele1[i]}\t{int(n_obs[i])}\t{_g6(a1_freq[i])}\t{_g6(beta[i])}\t"
+                     f"{_g6(se[i])}\t{_g6(z[i])}\t{_g6(log10p[i])}\n" for i in range(n))
+    return path

@@ -62,7 +62,7 @@ typedef enum gpca_status {
     GPCA_ERR_RCCL = -4,
     /* replaces the hard error of prepare.rs:1909-1911, 1961-1963, 2008-2009 */
     GPCA_ERR_MISSING_GENOTYPE = -5,
-    GPCA_ERR_NOT_CONVERGED = -6, /* sketch lost rank (CholQR pivot <= 0) */
+    GPCA_ERR_NOT_CONVERGED = -6, /* sketch lost rank (CholQR pivot <= 0); a null logistic fit that does not converge (a13) */
     GPCA_ERR_STATE = -7,         /* call order: e.g. rsvd before stats */
     GPCA_ERR_NO_DEVICE = -8,
     GPCA_ERR_INVALID_GENOTYPE = -9 /* a kept SNP holds a value outside {0,1,2} */
@@ -405,8 +405,8 @@ GPCA_API int gpca_pcrelate(gpca_handle* h, const double* V /* [N][P] */, int32_t
  * stats [rows][T][3] = beta, se, t; xb [rows][T + Pc]; rowinfo [rows][4] = n_obs, a1_freq, xx, sxx: each may be NULL, not all three.
  * A band is bit-identical to the same rows of the full call; int8 and 2-bit residency give the same bits, and so does a
  * GPCA_PREC_F32_MFMA handle (the call reads only the genotypes and the keep mask); the sample mask is ignored and no fitted result is
- * touched.  Out of scope: logistic regression, per-variant dropping of samples, per-trait sample sets, mixed models, and streamed and
- * row-sharded handles: GPCA_ERR_STATE.
+ * touched.  Out of scope: case / control traits (a13 has their score test), per-variant dropping of samples, per-trait sample sets,
+ * mixed models, and streamed and row-sharded handles: GPCA_ERR_STATE.
  * Errors: GPCA_ERR_STATE (no standardisation, K = 0, a streamed handle, a row-sharded handle), GPCA_ERR_BAD_ARG (T, Pc or the row
  * range out of bounds, all outputs NULL, a non-finite entry of Y or C on an included sample, df < 1, a column of C that is constant or
  * collinear over S, a trait with yy_t = 0, max_vif < 1 or not finite), GPCA_ERR_INVALID_GENOTYPE (a row the call reads holds a value
@@ -418,6 +418,52 @@ GPCA_API int gpca_assoc_linear(gpca_handle* h, const double* Y /* [N][T] */, int
 /* -log10 of the two-sided p-value of a Student t statistic with df degrees of freedom; host only, in log space (a p below 1e-308
  * does not underflow).  NaN for a NaN t or df <= 0. */
 GPCA_API double gpca_student_t_log10p(double t, double df);
+
+/* ---- a13: logistic score scan: the score test of each of T case / control traits (Y in {0, 1}) for every kept row g of the band
+ * [row0, row1), the null model logit P(y = 1) = (1, C) alpha fitted once per trait and no SNP refitted: regenie step 2 --bt without
+ * --firth / --spa, SAIGE without SPA, fastGWA-GLMM without the random effect.  T >= 1, Pc >= 0, T (Pc + 3) <= 64.  A missing call is
+ * imputed to the row's mean over the included samples, as in a12.
+ *  1. host, f64, gpca_logistic_null: S = the included samples, n = |S|; X = (1, the columns of C centred over S and scaled to unit
+ *     norm: a12's standardisation and constant-column test).  Newton from alpha = (logit(ybar), 0, ...): mu = 1 / (1 + exp(-X alpha)),
+ *     w = mu (1 - mu), (X^T W X) delta = X^T (y - mu) by Cholesky, alpha += delta, until max |delta| <= 1e-10 (1 + max |alpha|); mu is
+ *     recomputed from the final alpha.  alpha [Pc + 1] is in the coordinates of X; mu [N] is 0 outside S.
+ *     GPCA_ERR_BAD_ARG: y outside {0, 1} or not finite on S, only one class, n - Pc - 1 < 1, a non-finite entry of C on S, a constant
+ *     column, a Cholesky pivot below 1e-10 of its diagonal entry (collinear).  GPCA_ERR_NOT_CONVERGED: 25 steps, or some
+ *     |X alpha| > 30 (separation).  Host only, no handle, no message.
+ *  2. host, f64, per trait t: r_t = y - mu, w_t = mu (1 - mu), A_t,j (j = 0 .. Pc) = the columns of W X L^-T with X^T W X = L L^T
+ *     (column 0 is the intercept's); Pc + 3 columns, each rounded once to f32 and 0 outside S: the panel B.
+ *  3. device: o = [observed and in S], m = [missing and in S]; the exact integers n_obs = sum o, s1 = sum g o, s2 = sum g^2 o.  A row is
+ *     FLIPPED iff s1 > n_obs (its A1 mean is above 1).  The operand is x = g o on a plain row and (2 - g) o on a flipped one.
+ *     d_c = sum_n x_n B_nc, e_c = sum_n m_n B_nc, q_t = sum_n x_n^2 w_t,n on v_mfma_f32_32x32x2_f32 (x, m, x^2 are 0, 1, 2, 4: every
+ *     product is exact), an f32 accumulator never sums more than 256 samples (groups counted from sample 0) before it is added to an
+ *     f64 running sum; no split of the sample axis and no atomics on sums.
+ *  4. f64, no fused multiply-add: xbar = (s1 or 2 n_obs - s1) / n_obs, the operand's mean; U_t = d[r_t] + xbar e[r_t];
+ *     a_t,j = d[A_t,j] + xbar e[A_t,j]; gwg_t = q_t + (xbar xbar) e[w_t]; vw = gwg - a_0^2; V = vw - sum_{j = 1 .. Pc} a_j^2 (j
+ *     ascending); s = -1 on a flipped row, else +1; beta = s U / V, se = 1 / sqrt(V), z = s U / sqrt(V) (all for allele A1);
+ *     a1_freq = (s1 / n_obs) / 2; xx = s2 - s1 (s1 / n_obs).  beta, se, z are NaN when n_obs = 0, xx <= 0, !(V > 0) or
+ *     V max_vif < vw.  (V is the same in either coding; the flip keeps the cancellation in gwg - a_0^2 near a factor 3, against about
+ *     200 at an A1 frequency of 0.99.)
+ * stats [rows][T][5] = beta, se, z, vw, V; ua [rows][T][Pc + 3] = U, gwg, a_0 .. a_Pc in the operand's coding; rowinfo [rows][5] =
+ * n_obs, a1_freq, xx, flipped (0 / 1), 0: each may be NULL, not all three.  The null fits run inside the call through the function
+ * behind gpca_logistic_null; a failure returns its status and names the trait in gpca_last_error.
+ * A band is bit-identical to the same rows of the full call; int8 and 2-bit residency give the same bits, and so does a
+ * GPCA_PREC_F32_MFMA handle; the sample mask is ignored and no fitted result is touched.  Out of scope: Firth and saddle-point
+ * corrections, a Wald / IRLS fit per SNP, per-variant dropping of samples, case / control frequency columns, mixed models, and
+ * streamed and row-sharded handles: GPCA_ERR_STATE.
+ * Errors: GPCA_ERR_STATE (no standardisation, K = 0, a streamed handle, a row-sharded handle), GPCA_ERR_BAD_ARG (T, Pc or the row range
+ * out of bounds, all outputs NULL, max_vif < 1 or not finite, and those of step 1), GPCA_ERR_NOT_CONVERGED (step 1),
+ * GPCA_ERR_INVALID_GENOTYPE (a row the call reads holds a value outside {0, 1, 2, missing}; the message names the row), GPCA_ERR_OOM
+ * (checked before any allocation). */
+GPCA_API int gpca_logistic_null(const double* y /* [N] */, const double* C /* [N][Pc] or NULL */, int32_t Pc,
+                                const uint8_t* include /* [N] or NULL */, int64_t N, double* alpha /* [Pc + 1] */,
+                                double* mu /* [N], 0 outside S */, int32_t* iters /* may be NULL */);
+GPCA_API int gpca_assoc_logistic_score(gpca_handle* h, const double* Y /* [N][T], 0 / 1 */, int32_t T, const double* C /* [N][Pc] or NULL */,
+                                       int32_t Pc, const uint8_t* include /* [N] or NULL */, double max_vif, int64_t row0, int64_t row1,
+                                       double* stats /* [rows][T][5] or NULL */, double* ua /* [rows][T][Pc + 3] or NULL */,
+                                       double* rowinfo /* [rows][5] or NULL */);
+/* -log10 of the two-sided p-value of a standard normal statistic, -log10(2 Phi(-|z|)); host only, in log space (a p below 1e-308 does
+ * not underflow).  NaN for a NaN z. */
+GPCA_API double gpca_normal_log10p(double z);
 
 /* ---- f3: the stages of EigenSNPCoreAlgorithm::compute_pca (main.rs:311-327, 359-366) ------------------------------------------
  * The algorithm lives in the un-vendored efficient_pca crate (Cargo.toml:30, branch "main", no pinned revision): what follows is

@@ -235,6 +235,37 @@ public:
         if (xb) xb->resize(rows * (size_t)(T + Pc));
     }
 
+    // logistic score scan (gpca_assoc_logistic_score) of kept rows [row0, row1): Y [N][T] in {0, 1}, C [N][Pc] (may be empty when
+    // Pc = 0), include (may be null: everyone) [N], T (Pc + 3) <= 64; stats [rows][T][5] = beta, se, z, vw, V; rowinfo [rows][5] = n_obs,
+    // a1_freq, xx, flipped, 0; ua (may be null) [rows][T][Pc + 3] = U, gwg, a_0 .. a_Pc
+    void assoc_logistic_score(const std::vector<double>& Y, int32_t T, const std::vector<double>& C, int32_t Pc,
+                              const std::vector<uint8_t>* include, double max_vif, int64_t row0, int64_t row1, std::vector<double>& stats,
+                              std::vector<double>& rowinfo, std::vector<double>* ua = nullptr) const {
+        const size_t rows = row1 > row0 ? (size_t)(row1 - row0) : 0;
+        stats.assign(std::max<size_t>(rows * (size_t)T * 5, 1), 0.0);
+        rowinfo.assign(std::max<size_t>(rows * 5, 1), 0.0);
+        if (ua) ua->assign(std::max<size_t>(rows * (size_t)T * (size_t)(Pc + 3), 1), 0.0);
+        check(gpca_assoc_logistic_score(h_, Y.data(), T, Pc ? C.data() : nullptr, Pc, include ? include->data() : nullptr, max_vif, row0, row1,
+                                        stats.data(), ua ? ua->data() : nullptr, rowinfo.data()));
+        stats.resize(rows * (size_t)T * 5);
+        rowinfo.resize(rows * 5);
+        if (ua) ua->resize(rows * (size_t)T * (size_t)(Pc + 3));
+    }
+    // the null logistic model of one trait (gpca_logistic_null; host only): y [N] in {0, 1}, C [N][Pc]; alpha [Pc + 1], mu [N] (0 outside
+    // the included samples); returns the number of Newton steps; throws Error with the status (no message: there is no handle)
+    static int logistic_null(const std::vector<double>& y, const std::vector<double>& C, int32_t Pc, const std::vector<uint8_t>* include,
+                             std::vector<double>& alpha, std::vector<double>& mu) {
+        alpha.assign((size_t)Pc + 1, 0.0);
+        mu.assign(std::max<size_t>(y.size(), 1), 0.0);
+        int32_t iters = 0;
+        const int rc = gpca_logistic_null(y.data(), Pc ? C.data() : nullptr, Pc, include ? include->data() : nullptr, (int64_t)y.size(), alpha.data(),
+                                          mu.data(), &iters);
+        if (rc != GPCA_OK) throw Error(rc, std::string("gpca_logistic_null: ") + gpca_status_string(rc));
+        mu.resize(y.size());
+        return (int)iters;
+    }
+    static double normal_log10p(double z) { return gpca_normal_log10p(z); }
+
 private:
     gpca_handle* h_ = nullptr;
     int k_ = 0;

@@ -5,10 +5,17 @@ second counted as 2 K N L_pad (the d product; the e product runs only where call
 MFMA peak, and the genotype bytes of one read of the band per second beside the 8 TB/s of the HBM.  One JSON line per L.
 
 usage: python scripts/assoc_bench.py [--rows M] [--samples N] [--storage int8|2bit] [--missing RATE] [--cols L ...] [--band ROWS] [--reps R]
+                                     [--score]
 
 Clean matrices come from the device generator; with --missing > 0 the rows are a 4 096-row host tile (that missing rate, seeded)
 repeated down the matrix and uploaded through a host panel source.  --band ROWS: rows per call (0 = io.assoc_bands' default).  Of the
-L columns a third (at most 20) are covariates: random orthonormal columns; the traits are standard normal."""
+L columns a third (at most 20) are covariates: random orthonormal columns; the traits are standard normal.
+
+--score: gpca_assoc_logistic_score beside gpca_assoc_linear at the same panel width in the same run (k_assoc is the yardstick): per L
+(32 = 8 traits x (1 covariate + 3), 64 = 16 x 4; any other L is taken as T = L // 4 traits with one covariate) one JSON line with
+"assoc_score" ms (the k_assoc_score pass), "assoc_score_count" ms (the count sweep that decides the flip), "assoc" ms at the same L and
+the ratio (score + count) / assoc; wall_ms adds the null fits on the host.  The traits are Bernoulli(0.4), the covariate standard
+normal."""
 import argparse
 import json
 import os
@@ -29,6 +36,7 @@ ap.add_argument("--missing", type=float, default=0.0)
 ap.add_argument("--cols", type=int, nargs="+", default=[32, 64])
 ap.add_argument("--band", type=int, default=0)
 ap.add_argument("--reps", type=int, default=2)
+ap.add_argument("--score", action="store_true")
 a = ap.parse_args()
 M, N = a.rows, a.samples
 store = _lib.STORE_INT8 if a.storage == "int8" else _lib.STORE_2BIT
@@ -48,7 +56,34 @@ with g.GpcaEngine(precision=_lib.PREC_I8_EXACT, storage=store) as e:
     e.snp_stats()
     K = e.num_pca_snps()
     load_s = time.time() - t0
-    for L in a.cols:
+    for L in a.cols if a.score else []:
+        T, Pc = max(L // 4, 1), 1
+        Ls = T * (Pc + 3)
+        Yb = (rng.random((N, T)) < 0.4).astype(np.float64)
+        Cs = rng.standard_normal((N, Pc))
+        Yl = rng.standard_normal((N, Ls - Pc))
+        bands = [(r0, min(r0 + a.band, K)) for r0 in range(0, K, a.band)] if a.band else gio.assoc_score_bands(K, T, Pc)
+        e.assoc_logistic_score(Yb, Cs, rows=(0, min(K, 128))); e.assoc_linear(Yl, Cs, rows=(0, min(K, 128)))      # warm-up
+        e.enable_timings(True); e.reset_timings()
+        t0 = time.time()
+        for _ in range(a.reps):
+            for b in bands:
+                e.assoc_logistic_score(Yb, Cs, rows=b)
+        wall_ms = (time.time() - t0) * 1e3 / a.reps
+        for _ in range(a.reps):
+            for b in bands:
+                e.assoc_linear(Yl, Cs, rows=b)
+        tm = e.timings()
+        ms = {k: (tm[k]["total_ms"] / a.reps if tm.get(k, {}).get("launches") else float("nan")) for k in ("assoc_score", "assoc_score_count", "assoc")}
+        lpad = 32 if Ls <= 32 else 64
+        gbytes = K * N / (4 if store == _lib.STORE_2BIT else 1)
+        print(json.dumps({"shape": f"{M} x {N}", "kept_rows": K, "storage": a.storage, "missing": a.missing, "L": Ls, "traits": T, "covariates": Pc,
+                          "bands": len(bands), "assoc_score_ms": round(ms["assoc_score"], 3), "assoc_score_count_ms": round(ms["assoc_score_count"], 3),
+                          "assoc_ms_same_L": round(ms["assoc"], 3), "ratio_to_assoc": round((ms["assoc_score"] + ms["assoc_score_count"]) / ms["assoc"], 3),
+                          "issued_multiplies_ratio": round((8 * lpad / 32 + 8) / (8 * lpad / 32), 3), "wall_ms": round(wall_ms, 3),
+                          "read_at_8tbs_ms": round(gbytes / 8e12 * 1e3, 3), "mfma_at_157tf_ms": round(2.0 * K * N * (lpad + 32) / 157e12 * 1e3, 3),
+                          "load_s": round(load_s, 2), "reps": a.reps}), flush=True)
+    for L in [] if a.score else a.cols:
         Pc = min(L // 3, 20)
         Y = rng.standard_normal((N, L - Pc))
         C = np.linalg.qr(rng.standard_normal((N, max(Pc, 1))))[0][:, :Pc]
