@@ -7,4 +7,6 @@ from .engine import (EigenSNPCoreAlgorithm, EigenSNPCoreAlgorithmConfig, EigenSN
 from .synth import synth_thresholds, synth_thresholds16  # noqa: F401
 from .distributed import shard_rows  # noqa: F401
 
+spa_log10p = GpcaEngine.spa_log10p
+
 __version__ = "0.2.2"

@@ -126,9 +126,17 @@ def build_parser() -> argparse.ArgumentParser:
                         "Needs the matrix resident on the device; traits + PCs + covariates <= 64")
     p.add_argument("--gpca-assoc-logistic", action="store_true",
                    help="--gpca-assoc-pheno: a trait column whose present values are exactly {0, 1} (1 = case) or {1, 2} (plink's coding, "
-                        "2 = case) gets the logistic score test (the null model fitted once per trait, no Firth / SPA correction) -> "
+                        "2 = case) gets the logistic score test (the null model fitted once per trait; no Firth correction; --gpca-assoc-spa adds "
+                        "the saddle-point correction) -> "
                         "P.<trait>.assoc.logistic (#CHROM POS ID A1 OBS_CT A1_FREQ BETA SE Z_STAT LOG10P); the other columns go "
                         "through the linear scan as without the flag.  PCs + covariates + 3 <= 64")
+    p.add_argument("--gpca-assoc-spa", action="store_true",
+                   help="--gpca-assoc-logistic: the saddle-point correction (SPA, as SAIGE and regenie --spa) of every test with "
+                        "|Z_STAT| >= the cutoff: LOG10P then comes from the saddle-point approximation of the score's null distribution, "
+                        "which a rare variant in an unbalanced trait needs, and a column SPA says Y (corrected), N (below the cutoff: the "
+                        "normal value) or F (the correction did not converge: the normal value); BETA, SE and Z_STAT stay the score test's")
+    p.add_argument("--gpca-assoc-spa-z", type=float, default=None, metavar="X",
+                   help="--gpca-assoc-spa: the cutoff, at least 0.5, or inf for no correction [default: 2]")
     p.add_argument("--gpca-assoc-pcs", type=int, default=None, metavar="P",
                    help="--gpca-assoc-pheno: the first P columns of the scores this run writes are covariates (0 <= P <= "
                         "--eigensnp-k-global) [default: every column]")
@@ -471,6 +479,7 @@ def _assoc(eng, a, fs, cols, sample_ids, scores, inset, st):
     eng.set_standardization(st["mu"], st["sigma"], st["keep"])                       # every SNP that passes the SNP QC
     rows = np.flatnonzero(st["keep"])
     lib = _lib.load()
+    spa_z = 2.0 if a.gpca_assoc_spa_z is None else a.gpca_assoc_spa_z
 
     def meta_of(r0, r1):
         rr = rows[r0:r1]
@@ -486,13 +495,19 @@ def _assoc(eng, a, fs, cols, sample_ids, scores, inset, st):
         for t0, t1 in (gio.assoc_score_groups(len(bnames), Pc) if bnames else []):
             Yg = np.ascontiguousarray(Yb[:, t0:t1])
             for bi, (r0, r1) in enumerate(gio.assoc_score_bands(len(rows), t1 - t0, Pc)):
-                r = eng.assoc_logistic_score(Yg, C, include=include, max_vif=vif, rows=(r0, r1))
+                if a.gpca_assoc_spa:
+                    r = eng.assoc_logistic_spa(Yg, C, include=include, max_vif=vif, spa_z=spa_z, rows=(r0, r1))
+                else:
+                    r = eng.assoc_logistic_score(Yg, C, include=include, max_vif=vif, rows=(r0, r1))
                 meta = meta_of(r0, r1)
                 for t in range(t1 - t0):
                     zz = r["z"][:, t]
-                    lp = [float("nan") if v != v else lib.gpca_normal_log10p(float(v)) for v in zz]
+                    if a.gpca_assoc_spa:
+                        lp, spa = r["log10p"][:, t], r["spa_status"][:, t]
+                    else:
+                        lp, spa = [float("nan") if v != v else lib.gpca_normal_log10p(float(v)) for v in zz], None
                     gio.write_assoc_logistic(a.output_prefix, bnames[t0 + t], *meta, r["n_obs"], r["a1_freq"], r["beta"][:, t], r["se"][:, t], zz,
-                                             lp, append=bi > 0)
+                                             lp, append=bi > 0, spa=spa)
     except _lib.GpcaError as e:
         if e.status == _lib.GPCA_ERR_STATE:
             raise SystemExit(ASSOC_NEEDS_RESIDENT) from None
@@ -595,6 +610,12 @@ def main(argv=None) -> int:
         raise SystemExit("error: --gpca-assoc-pcs, --gpca-assoc-covar and --gpca-assoc-vif need --gpca-assoc-pheno")
     if a.gpca_assoc_logistic and a.gpca_assoc_pheno is None:
         raise SystemExit("error: --gpca-assoc-logistic needs --gpca-assoc-pheno")
+    if a.gpca_assoc_spa and not a.gpca_assoc_logistic:
+        raise SystemExit("error: --gpca-assoc-spa needs --gpca-assoc-logistic")
+    if a.gpca_assoc_spa_z is not None and not a.gpca_assoc_spa:
+        raise SystemExit("error: --gpca-assoc-spa-z needs --gpca-assoc-spa")
+    if a.gpca_assoc_spa_z is not None and not gio.spa_z_ok(a.gpca_assoc_spa_z):
+        raise SystemExit("error: --gpca-assoc-spa-z must be at least 0.5, or inf for no correction")
     if a.gpca_assoc_pheno is not None:
         if not a.eigensnp:
             raise SystemExit("error: --gpca-assoc-pheno needs the --eigensnp workflow")

@@ -27,7 +27,7 @@
 // Why the flip: V does not change under g -> 2 - g (the projection annihilates constants), but gwg - a_0^2 cancels by about
 // (2pq + 4p^2) / (2pq), 200 at an A1 frequency of 0.99, against f32 sums of relative error (F + 3) u; with the operand's mean at most
 // 1 the factor stays near 3.
-// Out of scope: Firth and saddle-point corrections, a Wald / IRLS fit per SNP, per-variant dropping of samples, case / control
+// Out of scope: Firth's correction (assoc_spa.hip has the saddle-point correction), a Wald / IRLS fit per SNP, per-variant dropping of samples, case / control
 // frequency columns, mixed models, streamed and row-sharded handles.
 #include "assoc_stage.h"
 
@@ -64,23 +64,6 @@ __global__ __launch_bounds__(kAsrCountThreads) void k_assoc_score_count(const vo
         o[0] = nobs; o[1] = s1; o[2] = s2;
         if (bd) atomicMin(bad, (unsigned long long)orow);
     }
-}
-
-// masks the thread's 32 samples, recodes them to the operand (flip: 2 - g where observed) and writes them to the stage's buffer
-__device__ __forceinline__ void asr_put(const AscFetch& F, unsigned inb, unsigned inc, bool flip, uint8_t* dst) {
-    unsigned o[8];
-#pragma unroll
-    for (int d = 0; d < 8; ++d) {
-        const unsigned vb = (((inb >> (4 * d)) & 0xfu) * 0x00204081u & 0x01010101u) * 0xffu;
-        const unsigned ib = (((inc >> (4 * d)) & 0xfu) * 0x00204081u & 0x01010101u) * 0xffu;
-        const unsigned a = F.w[d] & vb & ib;
-        const unsigned m = (a >> 7) & 0x01010101u, g = a & ~(m * 0xffu);
-        // (a valid byte of g is 0, 1 or 2: 2 - g borrows nothing from its neighbour; an invalid one fails the call in the count kernel)
-        const unsigned x = flip ? ((0x02020202u - g) & vb & ib & ~(m * 0xffu)) : g;
-        o[d] = x | (m * kAscMissing);
-    }
-#pragma unroll
-    for (int d = 0; d < 4; ++d) *reinterpret_cast<uint2*>(dst + 8 * d) = make_uint2(o[2 * d], o[2 * d + 1]);
 }
 
 template <int NB>

@@ -1,0 +1,159 @@
+// Saddle-point correction of the logistic score scan (gpca_assoc_logistic_spa; gpca_assoc_score.cpp; include/gpca.h section a14).
+//
+// After k_assoc_score_finish the band's (row, trait) items are walked in ranges of kAspListItems.  k_assoc_spa_flag (a thread per item)
+// writes the item's normal value with status 0 and, where z is finite, |z| >= spa_z and U != 0, takes a slot of the range's list from an
+// atomic counter: the slot decides only which workgroup computes the item, every result goes to the item's own address.
+// k_assoc_spa: asp_slots(N) persistent workgroups of kAspThreads threads take the listed items in turn.  For an item the workgroup
+//  1. reads the row once, in chunks of kAspChunk samples: a thread fetches 32 samples (asc_fetch), masks and flips them as the score
+//     kernel does (asr_put) into an LDS buffer; then thread t owns the samples t + kAspThreads k: x~ = the operand, the operand's mean
+//     xbar on a missing call, 0 outside S; g~ = x~ - sum_j a_j Z_nj (j ascending, a_j from dv, Z = X L^-T in f64 from the host), written
+//     to the workgroup's slice of the workspace; the bounds of the support are summed on the way;
+//  2. runs both tails' guarded Newton (spa_math.h), every evaluation of K' and K'' one pass over g~ and mu (both stay in L2: 16 bytes
+//     a sample), and a last pass with K at each root.
+// Every sum over the samples: a thread adds its samples in ascending order, a wave adds its lanes by a butterfly (every lane ends with
+// the same bits), the four waves' sums are added in the order (0 + 1) + (2 + 3).  The tree depends on N alone, there is no atomic on a
+// sum, every thread holds the same value and takes the same branch of the root rule.  A band therefore gives the bits of the full
+// call, and int8 and 2-bit residency (the same bytes in LDS) the same bits.
+// Registers, LDS and scratch as hipcc reports them are in DESIGN section 7 (no scratch, no VGPR spill; an SGPR spill of 52 to VGPR lanes
+// outside the per-sample loops, discussed there).
+#include "assoc_stage.h"
+#include "spa_math.h"
+
+#pragma clang fp contract(off)
+
+namespace gpca {
+
+__global__ __launch_bounds__(256) void k_assoc_spa_flag(const double* __restrict__ stats, const double* __restrict__ dv, int T, int Pc,
+                                                        int64_t item0, int64_t nitems, double spa_z, double* __restrict__ out,
+                                                        int* __restrict__ list, unsigned* __restrict__ count) {
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= nitems) return;
+    const int64_t item = item0 + k, i = item / T;
+    const int t = (int)(item - i * T);
+    const double z = stats[item * 5 + 2], U = dv[i * asr_cols(T, Pc) + asr_col_r(T, t)];
+    double* o = out + item * 4;
+    const double nan = __builtin_nan("");
+    o[0] = spa_normal_log10p(z); o[1] = 0.0; o[2] = nan; o[3] = nan;
+    if (z == z && fabs(z) != INFINITY && fabs(z) >= spa_z && U != 0.0) list[atomicAdd(count, 1u)] = (int)k;
+}
+
+// the sums of up to three values over the workgroup: the same bits in every thread
+__device__ __forceinline__ void asp_reduce3(double& a, double& b, double& c, double* red) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) { a = a + __shfl_xor(a, d); b = b + __shfl_xor(b, d); c = c + __shfl_xor(c, d); }
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (lane == 0) { red[wv] = a; red[4 + wv] = b; red[8 + wv] = c; }
+    __syncthreads();
+    a = (red[0] + red[1]) + (red[2] + red[3]);
+    b = (red[4] + red[5]) + (red[6] + red[7]);
+    c = (red[8] + red[9]) + (red[10] + red[11]);
+    __syncthreads();
+}
+
+struct AspEval {
+    const double* g;
+    const double* mu;
+    int64_t npad;
+    double* red;
+    __device__ void operator()(double tau, bool want0, double& k0, double& k1, double& k2) const {
+        double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+        for (int64_t n = threadIdx.x; n < npad; n += kAspThreads) {
+            const double gg = g[n], m = mu[n];
+            double t1, t2;
+            spa_terms12(gg, m, tau, t1, t2);
+            s1 = s1 + t1; s2 = s2 + t2;
+            if (want0) s0 = s0 + spa_term0(gg, m, tau);
+        }
+        asp_reduce3(s0, s1, s2, red);
+        k0 = s0; k1 = s1; k2 = s2;
+    }
+};
+
+// out [rows][T][4] of the band that starts at kept row row0; list [*count]: the flagged items of the range that starts at item0
+template <bool PACKED>
+__global__ __launch_bounds__(kAspThreads) void k_assoc_spa(const void* __restrict__ Gv, int64_t ldr, const int64_t* __restrict__ krows, int64_t N,
+                                                           int64_t npad, const unsigned* __restrict__ incw, const unsigned* __restrict__ sums,
+                                                           const double* __restrict__ dv, const double* __restrict__ Z,
+                                                           const double* __restrict__ mu, int T, int Pc, int64_t row0, int64_t item0,
+                                                           const int* __restrict__ list, const unsigned* __restrict__ count, double* gws,
+                                                           double* out) {
+    __shared__ __attribute__((aligned(16))) uint8_t sx[kAspChunk];
+    __shared__ double sa[kAsrMaxCols], red[12];
+    const uint8_t* G = (const uint8_t*)Gv;
+    const int tid = threadIdx.x, P = Pc + 1, L = asr_cols(T, Pc);
+    const unsigned cnt = *count;
+    double* gw = gws + (int64_t)blockIdx.x * npad;
+    for (unsigned it = blockIdx.x; it < cnt; it += gridDim.x) {                 // (block-uniform)
+        const int64_t item = item0 + list[it], i = item / T;
+        const int t = (int)(item - i * T);
+        const int64_t orow = krows[row0 + i];
+        const unsigned nobs = sums[3 * i], s1 = sums[3 * i + 1];
+        const bool flip = s1 > nobs;
+        const double xbar = (double)(flip ? 2u * nobs - s1 : s1) / (double)nobs;
+        if (tid < P) sa[tid] = dv[i * L + asr_col_a(T, Pc, t, tid)];
+        const double* Zt = Z + (int64_t)t * P * npad;
+        const double* mut = mu + (int64_t)t * npad;
+        double hi = 0.0, lo = 0.0, unused = 0.0;
+        for (int64_t c0 = 0; c0 < npad; c0 += kAspChunk) {
+            const int64_t n0 = c0 + 32 * tid;
+            // (n0 is a multiple of 32 below npad: the read stays inside the row's pitch and the include word exists, as in k_assoc)
+            if (n0 < npad) {
+                AscFetch F;
+                asc_fetch<PACKED>(F, G, ldr, orow, n0);
+                const int64_t left = N - n0;
+                const unsigned inb = left >= 32 ? 0xffffffffu : (left <= 0 ? 0u : (1u << (int)left) - 1u);
+                asr_put(F, inb, incw[n0 >> 5], flip, sx + 32 * tid);
+            }
+            __syncthreads();                                                    // (also orders sa before its first use)
+#pragma nounroll
+            for (int k = 0; k < 32; ++k) {
+                const int64_t n = c0 + tid + kAspThreads * k;
+                if (n >= npad) break;
+                const unsigned b = sx[tid + kAspThreads * k];
+                const double xt = b == kAscMissing ? xbar : (double)b;
+                double acc = 0.0;
+                for (int j = 0; j < P; ++j) acc = acc + sa[j] * Zt[(int64_t)j * npad + n];
+                const double gg = xt - acc;
+                gw[n] = gg;
+                double p, q;
+                spa_support(gg, mut[n], p, q);
+                hi = hi + p; lo = lo + q;
+            }
+            __syncthreads();
+        }
+        const double U = dv[i * L + asr_col_r(T, t)], normal = out[item * 4];   // (the flag kernel's value; thread 0 overwrites it below)
+        asp_reduce3(hi, lo, unused, red);                                       // (its barriers make g~ visible to the workgroup)
+        AspEval ev{gw, mut, npad, red};
+        SpaResult r;
+        spa_item(ev, U, hi, lo, normal, r);
+        if (tid == 0) {
+            double* o = out + item * 4;
+            o[0] = r.log10p; o[1] = (double)r.status; o[2] = r.zeta[0]; o[3] = r.zeta[1];
+        }
+        __syncthreads();                                                        // (sa is rewritten for the next item)
+    }
+}
+
+void launch_assoc_spa_flag(hipStream_t st, const double* stats, const double* dv, int T, int Pc, int64_t item0, int64_t nitems, double spa_z,
+                           double* out, int* list, unsigned* count) {
+    if (nitems <= 0) return;
+    hipLaunchKernelGGL(k_assoc_spa_flag, dim3((unsigned)((nitems + 255) / 256)), dim3(256), 0, st, stats, dv, T, Pc, item0, nitems, spa_z, out,
+                       list, count);
+}
+
+int launch_assoc_spa(hipStream_t st, const void* G, int packed, int64_t ldr, const int64_t* krows, int64_t N, const unsigned* incw,
+                     const unsigned* sums, const double* dv, const double* Z, const double* mu, int T, int Pc, int64_t row0,
+                     int64_t item0, const int* list, const unsigned* count, double* gws, double* out) {
+    if (T < 1 || Pc < 0 || asr_cols(T, Pc) > kAsrMaxCols || N < 1) return (int)hipErrorInvalidValue;
+    const dim3 grid((unsigned)asp_slots(N)), blk(kAspThreads);
+    const int64_t npad = asp_gpad(N);
+    if (packed)
+        hipLaunchKernelGGL((k_assoc_spa<true>), grid, blk, 0, st, G, ldr, krows, N, npad, incw, sums, dv, Z, mu, T, Pc, row0, item0, list,
+                           count, gws, out);
+    else
+        hipLaunchKernelGGL((k_assoc_spa<false>), grid, blk, 0, st, G, ldr, krows, N, npad, incw, sums, dv, Z, mu, T, Pc, row0, item0, list,
+                           count, gws, out);
+    return 0;
+}
+
+}  // namespace gpca

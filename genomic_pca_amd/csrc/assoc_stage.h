@@ -1,4 +1,4 @@
-// The staging helpers of the association kernels (assoc.hip, assoc_score.hip): the fetch of 32 samples of a row from either storage,
+// The staging helpers of the association kernels (assoc.hip, assoc_score.hip, assoc_spa.hip): the fetch of 32 samples of a row from either storage,
 // the check / mask / count of those samples on their way into a stage's LDS buffer, and the fetch and store of a stage's panel of B^T.
 #pragma once
 #include "gemm_i8_common.h"
@@ -62,6 +62,23 @@ __device__ __forceinline__ void asc_put(const AscFetch& F, unsigned inb, unsigne
                                         unsigned& s2, unsigned& bd) {
     unsigned o[8];
     asc_mask_count(F, inb, inc, o, nobs, s1, s2, bd);
+#pragma unroll
+    for (int d = 0; d < 4; ++d) *reinterpret_cast<uint2*>(dst + 8 * d) = make_uint2(o[2 * d], o[2 * d + 1]);
+}
+
+// masks the thread's 32 samples, recodes them to the operand (flip: 2 - g where observed) and writes them to the stage's buffer
+__device__ __forceinline__ void asr_put(const AscFetch& F, unsigned inb, unsigned inc, bool flip, uint8_t* dst) {
+    unsigned o[8];
+#pragma unroll
+    for (int d = 0; d < 8; ++d) {
+        const unsigned vb = (((inb >> (4 * d)) & 0xfu) * 0x00204081u & 0x01010101u) * 0xffu;
+        const unsigned ib = (((inc >> (4 * d)) & 0xfu) * 0x00204081u & 0x01010101u) * 0xffu;
+        const unsigned a = F.w[d] & vb & ib;
+        const unsigned m = (a >> 7) & 0x01010101u, g = a & ~(m * 0xffu);
+        // (a valid byte of g is 0, 1 or 2: 2 - g borrows nothing from its neighbour; an invalid one fails the call in the count kernel)
+        const unsigned x = flip ? ((0x02020202u - g) & vb & ib & ~(m * 0xffu)) : g;
+        o[d] = x | (m * kAscMissing);
+    }
 #pragma unroll
     for (int d = 0; d < 4; ++d) *reinterpret_cast<uint2*>(dst + 8 * d) = make_uint2(o[2 * d], o[2 * d + 1]);
 }

@@ -3,7 +3,11 @@
 // reduced to Pc + 3 panel columns; a count kernel takes the exact per-row sums and with them the flip, one pass over the band's kept
 // rows multiplies the panel on the matrix cores (k_assoc_score), a third kernel makes the statistics (k_assoc_score_finish).  The call
 // has its own workspace, allocated and freed per call, and reads nothing of the handle's state but the genotypes and the kept rows.
+// gpca_assoc_logistic_spa / gpca_spa_log10p (section a14): the same call with the saddle-point correction after the finish kernel
+// (assoc_spa.hip: the items with |z| >= spa_z, flagged and computed in ranges of kAspListItems), and the correction for one given
+// vector on the host; both run the rules of spa_math.h.
 #include "gpca_internal.h"
+#include "spa_math.h"
 
 using namespace gpca;
 
@@ -13,7 +17,14 @@ struct AsrWs {
     unsigned *incw = nullptr, *sums = nullptr;
     double *dv = nullptr, *stats = nullptr, *ua = nullptr, *info = nullptr;
     unsigned long long* bad = nullptr;
-    ~AsrWs() { dfree(Bt); dfree(incw); dfree(sums); dfree(dv); dfree(stats); dfree(ua); dfree(info); dfree(bad); }
+    // the saddle-point correction's: Z and mu of the traits, the slices of g~, the list of a range and its counter, the results
+    double *Z = nullptr, *mu = nullptr, *g = nullptr, *spa = nullptr;
+    int* list = nullptr;
+    unsigned* count = nullptr;
+    ~AsrWs() {
+        dfree(Bt); dfree(incw); dfree(sums); dfree(dv); dfree(stats); dfree(ua); dfree(info); dfree(bad);
+        dfree(Z); dfree(mu); dfree(g); dfree(spa); dfree(list); dfree(count);
+    }
 };
 template <typename T>
 hipError_t dalloc(T*& p, size_t elems) { return hipMalloc((void**)&p, std::max<size_t>(elems, 1) * sizeof(T)); }
@@ -155,6 +166,28 @@ int logit_null(const LogitDesign& D, const double* y, int64_t ys, std::vector<do
     if (!logit_mu(D, alpha, mu)) { msg = "some |X alpha| exceeds 30 (separation)"; return GPCA_ERR_NOT_CONVERGED; }
     return GPCA_OK;
 }
+
+// the sums of spa_math.h over one given vector, in sample order
+struct HostSpaEval {
+    const double *g, *mu;
+    int64_t n;
+    void operator()(double tau, bool want0, double& k0, double& k1, double& k2) const {
+#pragma clang fp contract(off)
+        double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+        for (int64_t i = 0; i < n; ++i) {
+            double t1, t2;
+            spa_terms12(g[i], mu[i], tau, t1, t2);
+            s1 = s1 + t1; s2 = s2 + t2;
+            if (want0) s0 = s0 + spa_term0(g[i], mu[i], tau);
+        }
+        k0 = s0; k1 = s1; k2 = s2;
+    }
+};
+
+// gpca_assoc_logistic_score (spa = nullptr) and gpca_assoc_logistic_spa: one path; the correction only adds to it
+int assoc_logistic(gpca_handle* h, const std::string& f, const double* Y, int32_t T, const double* C, int32_t Pc, const uint8_t* include,
+                   double max_vif, bool with_spa, double spa_z, int64_t row0, int64_t row1, double* stats, double* spa, double* ua,
+                   double* rowinfo);
 }  // namespace
 
 extern "C" int gpca_logistic_null(const double* y, const double* C, int32_t Pc, const uint8_t* include, int64_t N, double* alpha,
@@ -180,8 +213,21 @@ extern "C" int gpca_logistic_null(const double* y, const double* C, int32_t Pc, 
 extern "C" int gpca_assoc_logistic_score(gpca_handle* h, const double* Y, int32_t T, const double* C, int32_t Pc, const uint8_t* include,
                                          double max_vif, int64_t row0, int64_t row1, double* stats, double* ua, double* rowinfo) {
     if (!h) return GPCA_ERR_BAD_ARG;
+    return assoc_logistic(h, "gpca_assoc_logistic_score", Y, T, C, Pc, include, max_vif, false, INFINITY, row0, row1, stats, nullptr, ua, rowinfo);
+}
+
+extern "C" int gpca_assoc_logistic_spa(gpca_handle* h, const double* Y, int32_t T, const double* C, int32_t Pc, const uint8_t* include,
+                                       double max_vif, double spa_z, int64_t row0, int64_t row1, double* stats, double* spa, double* ua,
+                                       double* rowinfo) {
+    if (!h) return GPCA_ERR_BAD_ARG;
+    return assoc_logistic(h, "gpca_assoc_logistic_spa", Y, T, C, Pc, include, max_vif, true, spa_z, row0, row1, stats, spa, ua, rowinfo);
+}
+
+namespace {
+int assoc_logistic(gpca_handle* h, const std::string& f, const double* Y, int32_t T, const double* C, int32_t Pc, const uint8_t* include,
+                   double max_vif, bool with_spa, double spa_z, int64_t row0, int64_t row1, double* stats, double* spa, double* ua,
+                   double* rowinfo) {
     LOCK(h);
-    static const std::string f("gpca_assoc_logistic_score");
     if (!have_genotypes(h)) return fail(h, GPCA_ERR_STATE, f + ": no genotypes resident");
     if (h->sm.on)
         return fail(h, GPCA_ERR_STATE, f + ": the handle streams its matrix in panels, which is not implemented");
@@ -193,10 +239,12 @@ extern "C" int gpca_assoc_logistic_score(gpca_handle* h, const double* Y, int32_
         return fail(h, GPCA_ERR_BAD_ARG, f + ": T >= 1, Pc >= 0 and T (Pc + 3) <= " + std::to_string(kAsrMaxCols) + " are required");
     if (!Y) return fail(h, GPCA_ERR_BAD_ARG, f + ": Y is required");
     if (Pc > 0 && !C) return fail(h, GPCA_ERR_BAD_ARG, f + ": C is required when Pc > 0");
-    if (!stats && !ua && !rowinfo) return fail(h, GPCA_ERR_BAD_ARG, f + ": stats, ua and rowinfo are all NULL");
+    if (with_spa && !spa) return fail(h, GPCA_ERR_BAD_ARG, f + ": spa is required");
+    if (!with_spa && !stats && !ua && !rowinfo) return fail(h, GPCA_ERR_BAD_ARG, f + ": stats, ua and rowinfo are all NULL");
     if (row0 < 0 || row1 < row0 || row1 > K)
         return fail(h, GPCA_ERR_BAD_ARG, f + ": rows must satisfy 0 <= row0 <= row1 <= K (K = " + std::to_string(K) + " kept rows)");
     if (!(max_vif >= 1.0) || !std::isfinite(max_vif)) return fail(h, GPCA_ERR_BAD_ARG, f + ": max_vif must be finite and at least 1");
+    if (with_spa && !spa_z_ok(spa_z)) return fail(h, GPCA_ERR_BAD_ARG, f + ": spa_z must be at least 0.5, or +inf for no correction");
     if (N >= ((int64_t)1 << 30)) return fail(h, GPCA_ERR_BAD_ARG, f + ": 2^30 or more samples (the per-row sums are 32-bit)");
     const int L = asr_cols(T, Pc), P = Pc + 1;
     const int64_t npad = asc_npad(N);
@@ -210,8 +258,13 @@ extern "C" int gpca_assoc_logistic_score(gpca_handle* h, const double* Y, int32_
     std::vector<float> Bt((size_t)asc_b_capacity(N, L), 0.0f);
     std::vector<unsigned> incw((size_t)asc_inc_capacity(N), 0u);
     for (int64_t n : D.S) incw[(size_t)(n >> 5)] |= 1u << (int)(n & 31);
+    // (the correction's: Z_t = X L_t^-T and mu_t in f64, 0 outside S and past N; with spa_z = +inf no item is corrected: the flag
+    // kernel alone runs, and the correction's inputs and workspace are neither built nor allocated)
+    const bool correct = with_spa && std::isfinite(spa_z);
+    const int64_t gpad = asp_gpad(N);
+    std::vector<double> Zh(correct ? (size_t)asp_z_capacity(N, T, Pc) : 0, 0.0), muh(correct ? (size_t)asp_mu_capacity(N, T) : 0, 0.0);
     {
-        std::vector<double> alpha, mu, w((size_t)ns), A, col((size_t)P * (size_t)ns);
+        std::vector<double> alpha, mu, w((size_t)ns), A, col((size_t)P * (size_t)ns), zc(correct ? (size_t)P * (size_t)ns : 0);
         for (int t = 0; t < T; ++t) {
             int it = 0;
             rc = logit_null(D, Y + t, T, alpha, mu, it, msg);
@@ -238,23 +291,45 @@ extern "C" int gpca_assoc_logistic_score(gpca_handle* h, const double* Y, int32_
                 Bt[(size_t)asr_col_r(T, t) * (size_t)npad + n] = (float)(Y[(int64_t)n * T + t] - mu[(size_t)i]);
                 for (int j = 0; j < P; ++j) Bt[(size_t)asr_col_a(T, Pc, t, j) * (size_t)npad + n] = (float)col[(size_t)j * (size_t)ns + (size_t)i];
             }
+            if (!correct) continue;
+            // Z L^T = X, column by column: z_j = (x_j - sum_{k < j} L_jk z_k) / L_jj
+            for (int j = 0; j < P; ++j) {
+                double* z = &zc[(size_t)j * (size_t)ns];
+                const double* x = &D.X[(size_t)j * (size_t)ns];
+                for (int64_t i = 0; i < ns; ++i) z[i] = x[i];
+                for (int k = 0; k < j; ++k) {
+                    const double l = A[(size_t)j * P + k];
+                    const double* zk = &zc[(size_t)k * (size_t)ns];
+                    for (int64_t i = 0; i < ns; ++i) z[i] -= l * zk[i];
+                }
+                const double inv = 1.0 / A[(size_t)j * P + j];
+                for (int64_t i = 0; i < ns; ++i) z[i] *= inv;
+            }
+            for (int64_t i = 0; i < ns; ++i) {
+                const size_t n = (size_t)D.S[(size_t)i];
+                muh[(size_t)t * (size_t)gpad + n] = mu[(size_t)i];
+                for (int j = 0; j < P; ++j) Zh[((size_t)t * P + (size_t)j) * (size_t)gpad + n] = zc[(size_t)j * (size_t)ns + (size_t)i];
+            }
         }
     }
     const int64_t rows = row1 - row0;
     if (rows == 0) return GPCA_OK;
+    const bool dstats = stats || with_spa;                      // (the flag kernel reads z from the device's stats)
     if (asr_count_blocks(rows) >= ((int64_t)1 << 31)) return fail(h, GPCA_ERR_BAD_ARG, f + ": the band makes 2^31 or more workgroups: ask for fewer rows");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->st));
     {
         const double need = 4.0 * (double)asc_b_capacity(N, L) + 4.0 * (double)asc_inc_capacity(N) + 8.0 * (double)asr_dv_capacity(rows, L) +
-                            4.0 * (double)asr_sums_capacity(rows) + (stats ? 8.0 * (double)asr_stats_capacity(rows, T) : 0.0) +
+                            4.0 * (double)asr_sums_capacity(rows) + (dstats ? 8.0 * (double)asr_stats_capacity(rows, T) : 0.0) +
+                            (with_spa ? 8.0 * (double)asp_out_capacity(rows, T) + 4.0 * (double)asp_list_capacity(rows, T) : 0.0) +
+                            (correct ? 8.0 * (double)(asp_g_capacity(N) + asp_z_capacity(N, T, Pc) + asp_mu_capacity(N, T)) : 0.0) +
                             (ua ? 8.0 * (double)asr_ua_capacity(rows, T, Pc) : 0.0) + (rowinfo ? 8.0 * (double)asr_info_capacity(rows) : 0.0) +
                             (double)(64 << 20);
         size_t fr = 0, tot = 0;
         HIPCHK(hipMemGetInfo(&fr, &tot));
         if (need > (double)fr) {
             char buf[256];
-            snprintf(buf, sizeof buf, "gpca_assoc_logistic_score: the band needs %.3g GB of device memory, %.3g GB are free: ask for fewer rows", need * 1e-9, (double)fr * 1e-9);
+            snprintf(buf, sizeof buf, "%s: the band needs %.3g GB of device memory, %.3g GB are free: ask for fewer rows", f.c_str(), need * 1e-9, (double)fr * 1e-9);
             return fail(h, GPCA_ERR_OOM, buf);
         }
     }
@@ -265,12 +340,21 @@ extern "C" int gpca_assoc_logistic_score(gpca_handle* h, const double* Y, int32_
     AsrWs ws;
     HIPCHK(dalloc(ws.Bt, Bt.size())); HIPCHK(dalloc(ws.incw, incw.size())); HIPCHK(dalloc(ws.bad, 1));
     HIPCHK(dalloc(ws.dv, (size_t)asr_dv_capacity(rows, L))); HIPCHK(dalloc(ws.sums, (size_t)asr_sums_capacity(rows)));
-    if (stats) HIPCHK(dalloc(ws.stats, (size_t)asr_stats_capacity(rows, T)));
+    if (dstats) HIPCHK(dalloc(ws.stats, (size_t)asr_stats_capacity(rows, T)));
     if (ua) HIPCHK(dalloc(ws.ua, (size_t)asr_ua_capacity(rows, T, Pc)));
     if (rowinfo) HIPCHK(dalloc(ws.info, (size_t)asr_info_capacity(rows)));
     HIPCHK(hipMemcpyAsync(ws.Bt, Bt.data(), Bt.size() * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(ws.incw, incw.data(), incw.size() * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(ws.bad, 0xff, 8, st));
+    if (with_spa) {
+        HIPCHK(dalloc(ws.spa, (size_t)asp_out_capacity(rows, T))); HIPCHK(dalloc(ws.list, (size_t)asp_list_capacity(rows, T)));
+        HIPCHK(dalloc(ws.count, 1));
+    }
+    if (correct) {
+        HIPCHK(dalloc(ws.Z, Zh.size())); HIPCHK(dalloc(ws.mu, muh.size())); HIPCHK(dalloc(ws.g, (size_t)asp_g_capacity(N)));
+        HIPCHK(hipMemcpyAsync(ws.Z, Zh.data(), Zh.size() * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(ws.mu, muh.data(), muh.size() * 8, hipMemcpyHostToDevice, st));
+    }
     const double gbytes = (double)rows * (double)N * (packed ? 0.25 : 1.0);
     {
         ScopedTimer t(h, "assoc_score_count", 0.0, gbytes);
@@ -287,6 +371,20 @@ extern "C" int gpca_assoc_logistic_score(gpca_handle* h, const double* Y, int32_
     }
     launch_assoc_score_finish(st, ws.dv, ws.sums, T, Pc, max_vif, rows, ws.stats, ws.ua, ws.info);
     HIPCHK(hipGetLastError());
+    if (with_spa) {
+        ScopedTimer t(h, "assoc_spa", 0.0, 0.0);
+        const int64_t items = rows * (int64_t)T;
+        for (int64_t item0 = 0; item0 < items; item0 += kAspListItems) {
+            HIPCHK(hipMemsetAsync(ws.count, 0, 4, st));
+            launch_assoc_spa_flag(st, ws.stats, ws.dv, T, Pc, item0, std::min<int64_t>(kAspListItems, items - item0), spa_z, ws.spa, ws.list, ws.count);
+            HIPCHK(hipGetLastError());
+            if (!correct) continue;
+            if (launch_assoc_spa(st, G, packed, ldr, h->d_pca_rows, N, ws.incw, ws.sums, ws.dv, ws.Z, ws.mu, T, Pc, row0, item0, ws.list, ws.count,
+                                 ws.g, ws.spa) != 0)
+                return fail(h, GPCA_ERR_BAD_ARG, f + ": the launch was refused");
+            HIPCHK(hipGetLastError());
+        }
+    }
     unsigned long long bad = 0;
     HIPCHK(hipMemcpyAsync(&bad, ws.bad, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -295,30 +393,31 @@ extern "C" int gpca_assoc_logistic_score(gpca_handle* h, const double* Y, int32_
     if (stats) HIPCHK(hipMemcpyAsync(stats, ws.stats, (size_t)asr_stats_capacity(rows, T) * 8, hipMemcpyDeviceToHost, st));
     if (ua) HIPCHK(hipMemcpyAsync(ua, ws.ua, (size_t)asr_ua_capacity(rows, T, Pc) * 8, hipMemcpyDeviceToHost, st));
     if (rowinfo) HIPCHK(hipMemcpyAsync(rowinfo, ws.info, (size_t)asr_info_capacity(rows) * 8, hipMemcpyDeviceToHost, st));
+    if (with_spa) HIPCHK(hipMemcpyAsync(spa, ws.spa, (size_t)asp_out_capacity(rows, T) * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     return GPCA_OK;
 }
+}  // namespace
 
-// -log10(2 Phi(-|z|)) = -log10(erfc(x)), x = |z| / sqrt(2).  Near 0 through log1p(-erf(x)) (erfc(x) is close to 1 there); up to x = 5
-// through erfc; beyond, ln erfc(x) = -x^2 - ln(sqrt(pi)) + ln(1 / (x + (1/2) / (x + 1 / (x + (3/2) / (x + ...))))) with the continued
-// fraction by the modified Lentz method, so nothing underflows.
-extern "C" double gpca_normal_log10p(double z) {
-    if (std::isnan(z)) return std::nan("");
-    if (std::isinf(z)) return INFINITY;
-    const double x = std::fabs(z) / std::sqrt(2.0), ln10 = std::log(10.0);
-    if (x == 0.0) return 0.0;
-    if (x < 0.5) return -std::log1p(-std::erf(x)) / ln10;
-    if (x < 5.0) return -std::log(std::erfc(x)) / ln10;
-    const double tiny = 1e-300;
-    double fcf = x, c = x, d = 0.0;
-    for (int k = 1; k <= 500; ++k) {
-        const double a = 0.5 * k;
-        d = x + a * d; if (std::fabs(d) < tiny) d = tiny;
-        c = x + a / c; if (std::fabs(c) < tiny) c = tiny;
-        d = 1.0 / d;
-        const double del = c * d;
-        fcf *= del;
-        if (std::fabs(del - 1.0) < 1e-16) break;
+extern "C" int gpca_spa_log10p(const double* gt, const double* mu, int64_t n, double u, double* log10p, double* zeta, int32_t* status) {
+#pragma clang fp contract(off)
+    if (!gt || !mu || n < 1 || !log10p || !std::isfinite(u)) return GPCA_ERR_BAD_ARG;
+    double V = 0.0, hi = 0.0, lo = 0.0;
+    for (int64_t i = 0; i < n; ++i) {
+        if (!std::isfinite(gt[i]) || !(mu[i] >= 0.0 && mu[i] <= 1.0)) return GPCA_ERR_BAD_ARG;
+        double p, q;
+        spa_support(gt[i], mu[i], p, q);
+        hi = hi + p; lo = lo + q;
+        V = V + (1.0 - mu[i]) * mu[i] * (gt[i] * gt[i]);
     }
-    return (x * x + 0.5 * std::log(M_PI) + std::log(fcf)) / ln10;
+    const HostSpaEval ev{gt, mu, n};
+    SpaResult r;
+    spa_item(ev, u, hi, lo, u == 0.0 ? 0.0 : spa_normal_log10p(u / std::sqrt(V)), r);
+    *log10p = r.log10p;
+    if (zeta) { zeta[0] = r.zeta[0]; zeta[1] = r.zeta[1]; }
+    if (status) *status = r.status;
+    return GPCA_OK;
 }
+
+// (spa_math.h holds the function: the kernels of assoc_spa.hip use it too)
+extern "C" double gpca_normal_log10p(double z) { return spa_normal_log10p(z); }

@@ -369,4 +369,15 @@ int launch_assoc_score(hipStream_t st, const void* G, int packed, int64_t ldr, c
 void launch_assoc_score_finish(hipStream_t st, const double* dv, const unsigned* sums, int T, int Pc, double max_vif, int64_t rows,
                                double* stats, double* ua, double* info);
 
+// ---- saddle-point correction of the score scan (assoc_spa.hip): the items [item0, item0 + nitems) of a band (item = row T + trait)
+// out [rows][T][4] = the normal -log10 p, status 0, NaN, NaN; list [*count] = the items with finite |z| >= spa_z and U != 0, relative to
+// item0, in any order (*count is zero on entry; stats, dv: what the score kernels left for the band)
+void launch_assoc_spa_flag(hipStream_t st, const double* stats, const double* dv, int T, int Pc, int64_t item0, int64_t nitems, double spa_z,
+                           double* out, int* list, unsigned* count);
+// the listed items' out = -log10 p, status, zeta+, zeta-; Z [T][Pc + 1][asp_gpad(N)] and mu [T][asp_gpad(N)] f64, 0 outside the included
+// samples; gws: asp_g_capacity(N) doubles; row0: the band's first kept row
+int launch_assoc_spa(hipStream_t st, const void* G, int packed, int64_t ldr, const int64_t* krows, int64_t N, const unsigned* incw,
+                     const unsigned* sums, const double* dv, const double* Z, const double* mu, int T, int Pc, int64_t row0, int64_t item0,
+                     const int* list, const unsigned* count, double* gws, double* out);
+
 }  // namespace gpca

@@ -320,4 +320,27 @@ constexpr int64_t asr_stats_capacity(int64_t rows, int T) { return 5 * rows * (i
 constexpr int64_t asr_ua_capacity(int64_t rows, int T, int Pc) { return rows * (int64_t)asr_cols(T, Pc); }
 constexpr int64_t asr_info_capacity(int64_t rows) { return 5 * rows; }
 
+// ---- saddle-point correction of the score scan (assoc_spa.hip, gpca_assoc_score.cpp) ----------------------------------------------
+// The items (row, trait) of the band are flagged in ranges of kAspListItems; a range's flagged items are taken in turn by asp_slots(N)
+// persistent workgroups of kAspThreads threads.  A workgroup stages a row in chunks of kAspChunk samples (a thread fetches 32, as in
+// k_assoc_score_count) and keeps the item's g~ in its own slice of asp_gpad(N) doubles; a thread then owns the samples tid + kAspThreads k.
+// The slices together hold at most kAspWsBytes, or one slice where a single one is larger: no extent but out grows with the band.
+constexpr int kAspThreads = 256, kAspChunk = kAspThreads * 32, kAspMaxSlots = 1024;
+constexpr int64_t kAspWsBytes = (int64_t)256 << 20, kAspListItems = (int64_t)1 << 20;
+static_assert(kAspChunk % kAscStage == 0, "a chunk is whole stages: a fetch below asc_npad(N) stays inside the row's pitch");
+constexpr int64_t asp_gpad(int64_t N) { return asc_npad(N); }
+constexpr int64_t asp_chunks(int64_t N) { return (asp_gpad(N) + kAspChunk - 1) / kAspChunk; }
+constexpr int64_t asp_slots(int64_t N) {
+    const int64_t s = kAspWsBytes / (8 * asp_gpad(N > 0 ? N : 1));
+    return s < 1 ? 1 : (s > kAspMaxSlots ? kAspMaxSlots : s);
+}
+constexpr int64_t asp_ranges(int64_t rows, int T) { return (rows * (int64_t)T + kAspListItems - 1) / kAspListItems; }
+// elements of the call's own buffers: g~ [asp_slots][asp_gpad] (f64); Z [T][Pc + 1][asp_gpad] and mu [T][asp_gpad] (f64, 0 outside S and
+// past N); the list of a range's flagged items (i32, relative to the range) and out [rows][T][4] (f64)
+constexpr int64_t asp_g_capacity(int64_t N) { return asp_slots(N) * asp_gpad(N); }
+constexpr int64_t asp_z_capacity(int64_t N, int T, int Pc) { return (int64_t)T * (Pc + 1) * asp_gpad(N); }
+constexpr int64_t asp_mu_capacity(int64_t N, int T) { return (int64_t)T * asp_gpad(N); }
+constexpr int64_t asp_list_capacity(int64_t rows, int T) { return rows * (int64_t)T < kAspListItems ? rows * (int64_t)T : kAspListItems; }
+constexpr int64_t asp_out_capacity(int64_t rows, int T) { return 4 * rows * (int64_t)T; }
+
 }  // namespace gpca

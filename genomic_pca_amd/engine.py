@@ -553,6 +553,18 @@ class GpcaEngine:
         flipped [rows]; with ua=True also ua [rows][T][Pc + 3] = U, gwg, a_0 .. a_Pc in the operand's coding (2 - g on a flipped row).
         beta, se and z (for allele A1) are NaN for a row with no observed call, no variance, V <= 0 or a variance inflation above
         max_vif."""
+        return self._assoc_logistic(Y, covar, include, max_vif, None, rows, ua)
+
+    def assoc_logistic_spa(self, Y, covar=None, include=None, max_vif: float = 50.0, spa_z: float = 2.0,
+                           rows: Optional[Tuple[int, int]] = None, ua: bool = False):
+        """Logistic score scan with the saddle-point correction (gpca_assoc_logistic_spa): assoc_logistic_score's arguments and its
+        dict with the same bits, and beside them log10p, spa_status, zeta [rows][T] (and zeta [rows][T][2]).  Where |z| >= spa_z
+        (at least 0.5, or inf for no correction; SAIGE's 2 by default) the two-sided -log10 p comes from the saddle-point approximation
+        of U's distribution under the null (spa_status 1; 2 where a tail did not converge: the normal value); elsewhere it is the
+        normal value of z (spa_status 0).  zeta are the two tails' roots in the operand's coding; NaN statistics give NaN."""
+        return self._assoc_logistic(Y, covar, include, max_vif, float(spa_z), rows, ua)
+
+    def _assoc_logistic(self, Y, covar, include, max_vif, spa_z, rows, ua):
         N = self.dims()[1]
         Yv = np.ascontiguousarray(Y, np.float64)
         if Yv.ndim == 1:
@@ -574,12 +586,19 @@ class GpcaEngine:
         stats = np.zeros((max(n, 1), max(T, 1), 5), np.float64)
         info = np.zeros((max(n, 1), 5), np.float64)
         out_ua = np.zeros((max(n, 1), max(T, 1), Pc + 3), np.float64) if ua else None
-        self._chk(self._lib.gpca_assoc_logistic_score(self._h, _vp(Yv), T, _vp(Cv) if Pc else None, Pc, _vp(inc), float(max_vif), r0, r1,
-                                                      _vp(stats), _vp(out_ua), _vp(info)))
+        if spa_z is None:
+            self._chk(self._lib.gpca_assoc_logistic_score(self._h, _vp(Yv), T, _vp(Cv) if Pc else None, Pc, _vp(inc), float(max_vif), r0, r1,
+                                                          _vp(stats), _vp(out_ua), _vp(info)))
+        else:
+            spa = np.zeros((max(n, 1), max(T, 1), 4), np.float64)
+            self._chk(self._lib.gpca_assoc_logistic_spa(self._h, _vp(Yv), T, _vp(Cv) if Pc else None, Pc, _vp(inc), float(max_vif), spa_z, r0,
+                                                        r1, _vp(stats), _vp(spa), _vp(out_ua), _vp(info)))
         res = {"beta": stats[:n, :, 0], "se": stats[:n, :, 1], "z": stats[:n, :, 2], "vw": stats[:n, :, 3], "V": stats[:n, :, 4],
                "n_obs": info[:n, 0], "a1_freq": info[:n, 1], "xx": info[:n, 2], "flipped": info[:n, 3]}
         if ua:
             res["ua"] = out_ua[:n]
+        if spa_z is not None:
+            res.update(log10p=spa[:n, :, 0], spa_status=spa[:n, :, 1], zeta=spa[:n, :, 2:4])
         return res
 
     @staticmethod
@@ -604,6 +623,22 @@ class GpcaEngine:
         if rc != 0:
             raise GpcaError(rc, "gpca_logistic_null: " + lib.gpca_status_string(rc).decode())
         return alpha, mu[:N], int(it.value)
+
+    @staticmethod
+    def spa_log10p(gt, mu, u: float):
+        """The saddle-point correction for one given vector (gpca_spa_log10p; host only): gt [n] = the genotype with the covariates
+        taken out, mu [n] = the null model's probabilities, u = the score sum gt (y - mu).  Returns (-log10 of the two-sided p,
+        status, (zeta+, zeta-)): status 0 for u = 0 (p = 1), 1 for the correction, 2 where a tail did not converge or failed (the
+        normal value of u / sqrt(sum mu (1 - mu) gt^2))."""
+        gv, mv = np.ascontiguousarray(gt, np.float64).reshape(-1), np.ascontiguousarray(mu, np.float64).reshape(-1)
+        if gv.shape != mv.shape:
+            raise ValueError("gt and mu must have one entry per sample each")
+        lp, zeta, st = C.c_double(0.0), np.zeros(2), C.c_int32(0)
+        lib = _lib.load()
+        rc = lib.gpca_spa_log10p(_vp(gv), _vp(mv), gv.shape[0], float(u), C.byref(lp), _vp(zeta), C.byref(st))
+        if rc != 0:
+            raise GpcaError(rc, "gpca_spa_log10p: " + lib.gpca_status_string(rc).decode())
+        return float(lp.value), int(st.value), (float(zeta[0]), float(zeta[1]))
 
     @staticmethod
     def normal_log10p(z: float) -> float:

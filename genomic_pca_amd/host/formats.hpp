@@ -883,24 +883,31 @@ inline std::vector<std::pair<int64_t, int64_t>> assoc_score_bands(int64_t K, int
     return assoc_bands(K, T * (Pc + 3), max_values);
 }
 
+// the rule of gpca_assoc_logistic_spa's cutoff (io.spa_z_ok): at least 0.5, or inf (no correction); NaN is refused
+inline bool spa_z_ok(double x) { return x >= 0.5; }
+
 // P.<trait>.assoc.logistic: one tab-separated line per SNP, `#CHROM POS ID A1 OBS_CT A1_FREQ BETA SE Z_STAT LOG10P`; numbers as %.6g,
-// NaN as NA, OBS_CT as an integer; rows are added band by band
+// NaN as NA, OBS_CT as an integer; rows are added band by band.  spa = true adds the column `SPA`: N, Y, F for the status 0, 1, 2 of the
+// saddle-point correction (gpca_assoc_logistic_spa), NA where LOG10P is NA
 class AssocLogisticWriter {
 public:
-    AssocLogisticWriter(const std::string& prefix, const std::string& trait) : o_(prefix + "." + trait + ".assoc.logistic") {
-        std::fputs("#CHROM\tPOS\tID\tA1\tOBS_CT\tA1_FREQ\tBETA\tSE\tZ_STAT\tLOG10P\n", o_.f);
+    AssocLogisticWriter(const std::string& prefix, const std::string& trait, bool spa = false)
+        : o_(prefix + "." + trait + ".assoc.logistic"), spa_(spa) {
+        std::fputs(spa ? "#CHROM\tPOS\tID\tA1\tOBS_CT\tA1_FREQ\tBETA\tSE\tZ_STAT\tLOG10P\tSPA\n" : "#CHROM\tPOS\tID\tA1\tOBS_CT\tA1_FREQ\tBETA\tSE\tZ_STAT\tLOG10P\n", o_.f);
     }
     void add_row(const std::string& chrom, int64_t pos, const std::string& id, const std::string& a1, double n_obs, double a1_freq, double beta,
-                 double se, double z, double log10p) {
+                 double se, double z, double log10p, int spa_status = 0) {
         char b[5][48];
         const double v[5] = {a1_freq, beta, se, z, log10p};
         for (int i = 0; i < 5; ++i) { if (v[i] != v[i]) std::snprintf(b[i], sizeof b[i], "NA"); else std::snprintf(b[i], sizeof b[i], "%.6g", v[i]); }
-        std::fprintf(o_.f, "%s\t%lld\t%s\t%s\t%lld\t%s\t%s\t%s\t%s\t%s\n", chrom.c_str(), (long long)pos, id.c_str(), a1.c_str(), (long long)n_obs, b[0], b[1],
-                     b[2], b[3], b[4]);
+        const char* tail = !spa_ ? "" : (log10p != log10p ? "\tNA" : (spa_status == 1 ? "\tY" : (spa_status == 2 ? "\tF" : "\tN")));
+        std::fprintf(o_.f, "%s\t%lld\t%s\t%s\t%lld\t%s\t%s\t%s\t%s\t%s%s\n", chrom.c_str(), (long long)pos, id.c_str(), a1.c_str(), (long long)n_obs, b[0], b[1],
+                     b[2], b[3], b[4], tail);
     }
 
 private:
     OutFile o_;
+    bool spa_;
 };
 
 }  // namespace gpca_host

@@ -60,6 +60,9 @@ struct Args {
     bool assoc_logistic = false;      // --gpca-assoc-logistic: binary trait columns go through the logistic score scan
     int64_t assoc_pcs = 0;            // --gpca-assoc-pcs P [default: every column of the scores]
     double assoc_vif = 50.0;          // --gpca-assoc-vif X
+    bool assoc_spa = false;           // --gpca-assoc-spa: the saddle-point correction of the logistic score scan
+    bool have_assoc_spa_z = false;
+    double assoc_spa_z = 2.0;         // --gpca-assoc-spa-z X
     gpca_host::PhenoTable assoc_pheno_table, assoc_covar_table;   // read in main, before any work on the device
 };
 
@@ -157,9 +160,16 @@ void print_help() {
         "                                       covariates <= 64\n"
         "      --gpca-assoc-logistic            --gpca-assoc-pheno: a trait column whose present values are exactly {0, 1} (1 = case) or\n"
         "                                       {1, 2} (plink's coding, 2 = case) gets the logistic score test (the null model fitted\n"
-        "                                       once per trait, no Firth / SPA correction) -> P.<trait>.assoc.logistic (#CHROM POS ID A1\n"
-        "                                       OBS_CT A1_FREQ BETA SE Z_STAT LOG10P); the other columns go through the linear scan as\n"
-        "                                       without the flag.  PCs + covariates + 3 <= 64\n"
+        "                                       once per trait; no Firth correction; --gpca-assoc-spa adds the saddle-point correction)\n"
+        "                                       -> P.<trait>.assoc.logistic (#CHROM POS ID A1 OBS_CT A1_FREQ BETA SE Z_STAT LOG10P); the\n"
+        "                                       other columns go through the linear scan as without the flag.  PCs + covariates + 3 <= 64\n"
+        "      --gpca-assoc-spa                 --gpca-assoc-logistic: the saddle-point correction (SPA, as SAIGE and regenie --spa) of\n"
+        "                                       every test with |Z_STAT| >= the cutoff: LOG10P then comes from the saddle-point\n"
+        "                                       approximation of the score's null distribution, which a rare variant in an unbalanced\n"
+        "                                       trait needs, and a column SPA says Y (corrected), N (below the cutoff: the normal value)\n"
+        "                                       or F (the correction did not converge: the normal value); BETA, SE and Z_STAT stay the\n"
+        "                                       score test's\n"
+        "      --gpca-assoc-spa-z <X>           --gpca-assoc-spa: the cutoff, at least 0.5, or inf for no correction [default: 2]\n"
         "      --gpca-assoc-pcs <P>             --gpca-assoc-pheno: the first P columns of the scores this run writes are covariates\n"
         "                                       (0 <= P <= --eigensnp-k-global) [default: every column]\n"
         "      --gpca-assoc-covar <FILE>        --gpca-assoc-pheno: further covariates, a table in the format of the phenotype file\n"
@@ -241,6 +251,8 @@ Args parse(int argc, char** argv) {
         else if (f == "--gpca-assoc-pheno") a.assoc_pheno = val();
         else if (f == "--gpca-assoc-covar") a.assoc_covar = val();
         else if (f == "--gpca-assoc-logistic") a.assoc_logistic = true;
+        else if (f == "--gpca-assoc-spa") a.assoc_spa = true;
+        else if (f == "--gpca-assoc-spa-z") { a.assoc_spa_z = to_f64(f, val()); a.have_assoc_spa_z = true; }
         else if (f == "--gpca-assoc-pcs") { a.assoc_pcs = to_i64(f, val()); a.have_assoc_pcs = true; }
         else if (f == "--gpca-assoc-vif") { a.assoc_vif = to_f64(f, val()); a.have_assoc_vif = true; }
         else if (f == "--gpca-indep-pairwise") {
@@ -463,16 +475,19 @@ int run_assoc(gpca::Engine& eng, const Args& a, const gpca_host::PlinkFileset& f
                 for (int64_t s = 0; s < n; ++s)
                     for (int32_t t = 0; t < Tg; ++t) Yg[(size_t)s * Tg + t] = Yb[(size_t)s * Tb + (size_t)g.first + t];
                 std::vector<std::unique_ptr<gpca_host::AssocLogisticWriter>> w;
-                for (int32_t t = 0; t < Tg; ++t) w.emplace_back(new gpca_host::AssocLogisticWriter(a.output_prefix, bnames[(size_t)g.first + t]));
+                for (int32_t t = 0; t < Tg; ++t) w.emplace_back(new gpca_host::AssocLogisticWriter(a.output_prefix, bnames[(size_t)g.first + t], a.assoc_spa));
                 for (const auto& b : gpca_host::assoc_score_bands((int64_t)rows.size(), Tg, Pc)) {
-                    std::vector<double> stats, info;
-                    eng.assoc_logistic_score(Yg, Tg, C, Pc, &include, a.assoc_vif, b.first, b.second, stats, info);
+                    std::vector<double> stats, info, spa;
+                    if (a.assoc_spa) eng.assoc_logistic_spa(Yg, Tg, C, Pc, &include, a.assoc_vif, a.assoc_spa_z, b.first, b.second, stats, spa, info);
+                    else eng.assoc_logistic_score(Yg, Tg, C, Pc, &include, a.assoc_vif, b.first, b.second, stats, info);
                     for (int64_t r = b.first; r < b.second; ++r) {
                         const size_t i = (size_t)(r - b.first), o = (size_t)rows[(size_t)r];
                         for (int32_t t = 0; t < Tg; ++t) {
                             const double* s5 = &stats[(i * (size_t)Tg + (size_t)t) * 5];
-                            const double lp = s5[2] != s5[2] ? std::nan("") : gpca_normal_log10p(s5[2]);
-                            w[(size_t)t]->add_row(fs.chromosomes[o], fs.positions[o], fs.variant_ids[o], fs.allele1[o], info[5 * i], info[5 * i + 1], s5[0], s5[1], s5[2], lp);
+                            const double* s4 = a.assoc_spa ? &spa[(i * (size_t)Tg + (size_t)t) * 4] : nullptr;
+                            const double lp = s4 ? s4[0] : (s5[2] != s5[2] ? std::nan("") : gpca_normal_log10p(s5[2]));
+                            w[(size_t)t]->add_row(fs.chromosomes[o], fs.positions[o], fs.variant_ids[o], fs.allele1[o], info[5 * i], info[5 * i + 1], s5[0], s5[1], s5[2], lp,
+                                                  s4 ? (int)s4[1] : 0);
                         }
                     }
                 }
@@ -823,6 +838,12 @@ int main(int argc, char** argv) {
             return 2;
         }
         if (a.assoc_logistic && a.assoc_pheno.empty()) { std::fprintf(stderr, "error: --gpca-assoc-logistic needs --gpca-assoc-pheno\n"); return 2; }
+        if (a.assoc_spa && !a.assoc_logistic) { std::fprintf(stderr, "error: --gpca-assoc-spa needs --gpca-assoc-logistic\n"); return 2; }
+        if (a.have_assoc_spa_z && !a.assoc_spa) { std::fprintf(stderr, "error: --gpca-assoc-spa-z needs --gpca-assoc-spa\n"); return 2; }
+        if (a.have_assoc_spa_z && !gpca_host::spa_z_ok(a.assoc_spa_z)) {
+            std::fprintf(stderr, "error: --gpca-assoc-spa-z must be at least 0.5, or inf for no correction\n");
+            return 2;
+        }
         if (!a.assoc_pheno.empty()) {
             if (!a.eigensnp) { std::fprintf(stderr, "error: --gpca-assoc-pheno needs the --eigensnp workflow\n"); return 2; }
             if (a.have_assoc_pcs && !(a.assoc_pcs >= 0 && a.assoc_pcs <= a.k_global)) {

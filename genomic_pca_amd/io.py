@@ -824,21 +824,28 @@ def assoc_score_bands(K: int, T: int, Pc: int, max_values: int = 1 << 26):
     return assoc_bands(K, T * (Pc + 3), max_values)
 
 
+def spa_z_ok(x) -> bool:
+    """The rule of gpca_assoc_logistic_spa's cutoff: at least 0.5, or inf (no correction); NaN is refused."""
+    return bool(float(x) >= 0.5)
+
+
 def write_assoc_logistic(prefix: str, trait: str, chromosomes: Sequence[str], positions: Sequence[int], variant_ids: Sequence[str],
-                         allele1: Sequence[str], n_obs, a1_freq, beta, se, z, log10p, append: bool = False) -> str:
+                         allele1: Sequence[str], n_obs, a1_freq, beta, se, z, log10p, append: bool = False, spa=None) -> str:
     """P.<trait>.assoc.logistic: one tab-separated line per SNP, `#CHROM POS ID A1 OBS_CT A1_FREQ BETA SE Z_STAT LOG10P`; numbers as
-    %.6g, NaN as NA, OBS_CT as an integer.  append=True adds the rows of a further band to the file (no header)."""
+    %.6g, NaN as NA, OBS_CT as an integer.  append=True adds the rows of a further band to the file (no header).  spa: the status of
+    the saddle-point correction per SNP (gpca_assoc_logistic_spa: 0, 1, 2) adds the column `SPA` = N, Y, F (NA where LOG10P is NA)."""
     path = f"{prefix}.{trait}.assoc.logistic"
     n = len(variant_ids)
-    for a in (chromosomes, positions, allele1, n_obs, a1_freq, beta, se, z, log10p):
+    for a in (chromosomes, positions, allele1, n_obs, a1_freq, beta, se, z, log10p) + (() if spa is None else (spa,)):
         if len(a) != n:
             raise ValueError("write_assoc_logistic: one entry per SNP in every column")
     d = os.path.dirname(path)
     if d:
         os.makedirs(d, exist_ok=True)
+    tail = (lambda i: "") if spa is None else (lambda i: "\tNA" if log10p[i] != log10p[i] else "\t" + "NYF"[int(spa[i])])
     with open(path, "a" if append else "w") as f:
         if not append:
-            f.write("#CHROM\tPOS\tID\tA1\tOBS_CT\tA1_FREQ\tBETA\tSE\tZ_STAT\tLOG10P\n")
+            f.write("#CHROM\tPOS\tID\tA1\tOBS_CT\tA1_FREQ\tBETA\tSE\tZ_STAT\tLOG10P" + ("" if spa is None else "\tSPA") + "\n")
         f.writelines(f"{chromosomes[i]}\t{int(positions[i])}\t{variant_ids[i]}\t{allele1[i]}\t{int(n_obs[i])}\t{_g6(a1_freq[i])}\t{_g6(beta[i])}\t"
-                     f"{_g6(se[i])}\t{_g6(z[i])}\t{_g6(log10p[i])}\n" for i in range(n))
+                     f"{_g6(se[i])}\t{_g6(z[i])}\t{_g6(log10p[i])}{tail(i)}\n" for i in range(n))
     return path

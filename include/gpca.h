@@ -447,9 +447,9 @@ GPCA_API double gpca_student_t_log10p(double t, double df);
  * n_obs, a1_freq, xx, flipped (0 / 1), 0: each may be NULL, not all three.  The null fits run inside the call through the function
  * behind gpca_logistic_null; a failure returns its status and names the trait in gpca_last_error.
  * A band is bit-identical to the same rows of the full call; int8 and 2-bit residency give the same bits, and so does a
- * GPCA_PREC_F32_MFMA handle; the sample mask is ignored and no fitted result is touched.  Out of scope: Firth and saddle-point
- * corrections, a Wald / IRLS fit per SNP, per-variant dropping of samples, case / control frequency columns, mixed models, and
- * streamed and row-sharded handles: GPCA_ERR_STATE.
+ * GPCA_PREC_F32_MFMA handle; the sample mask is ignored and no fitted result is touched.  Out of scope: Firth's correction (a14 has
+ * the saddle-point correction), a Wald / IRLS fit per SNP, per-variant dropping of samples, case / control frequency columns, mixed
+ * models, and streamed and row-sharded handles: GPCA_ERR_STATE.
  * Errors: GPCA_ERR_STATE (no standardisation, K = 0, a streamed handle, a row-sharded handle), GPCA_ERR_BAD_ARG (T, Pc or the row range
  * out of bounds, all outputs NULL, max_vif < 1 or not finite, and those of step 1), GPCA_ERR_NOT_CONVERGED (step 1),
  * GPCA_ERR_INVALID_GENOTYPE (a row the call reads holds a value outside {0, 1, 2, missing}; the message names the row), GPCA_ERR_OOM
@@ -464,6 +464,58 @@ GPCA_API int gpca_assoc_logistic_score(gpca_handle* h, const double* Y /* [N][T]
 /* -log10 of the two-sided p-value of a standard normal statistic, -log10(2 Phi(-|z|)); host only, in log space (a p below 1e-308 does
  * not underflow).  NaN for a NaN z. */
 GPCA_API double gpca_normal_log10p(double z);
+
+/* ---- a14: the saddle-point correction of the logistic score scan (SPA: Dey et al. 2017, SAIGE's Saddle_Prob, regenie --spa): the
+ * p-value of a13's U_t from the cumulant function of U under the null instead of the normal approximation of U / sqrt(V), which is
+ * wrong by many decades for a rare variant in an unbalanced trait.  gpca_assoc_logistic_spa is gpca_assoc_logistic_score (the same
+ * path: stats, ua and rowinfo carry the same bits) followed by the correction of the items (row, trait) with |z| >= spa_z.
+ *  Setting.  For trait t and kept row i, in the operand's coding of a13 (a flipped row stays flipped; the two-sided p does not change
+ *     under the flip): x~_n = x_n where the call is observed and in S, xbar where it is missing and in S, 0 outside S;
+ *     g~_n = x~_n - sum_{j = 0 .. Pc} a_t,j Z_t,n,j (j ascending), Z_t = X L_t^-T with X and L_t of a13 steps 1 - 2: N x (Pc + 1), f64,
+ *     0 outside S, built on the host beside the f32 panel; a_t,j = the values of a13 step 4, the ones ua reports.  Then X^T W g~ = 0
+ *     and g~^T W g~ = V.  s = |U|.
+ *  The cumulant function of U = sum_S g~_n (y_n - mu_n), y_n ~ Bernoulli(mu_n):
+ *     K(tau)   = sum_S [log1p(mu_n expm1(g~_n tau)) - tau g~_n mu_n]
+ *     K'(tau)  = sum_S mu_n g~_n [1 / ((1 - mu_n) e^(-g~_n tau) + mu_n) - 1]
+ *     K''(tau) = sum_S (1 - mu_n) mu_n g~_n^2 e^(g~_n tau) / (1 - mu_n + mu_n e^(g~_n tau))^2
+ *     each term in the form that takes only e^(-|g~_n tau|), so neither sign overflows; f64, no fused multiply-add.
+ *  Support.  sup = sum_S max(g~_n (1 - mu_n), -g~_n mu_n), inf = sum_S min(the same two).  A tail whose target lies at or beyond its
+ *     bound (s >= sup for the upper tail, -s <= inf for the lower) has no saddle point: probability 0, converged, zeta = +-inf.
+ *  Root.  For each tail with target c in {+s, -s}, K'(zeta) = c by SPAtest's guarded Newton:
+ *         tau = 0, k = K'(tau) - c, prev = +inf
+ *         for rep = 1 .. 100:
+ *             tau' = tau - k / K''(tau)
+ *             tau' not finite: stop, not converged
+ *             |tau' - tau| <= 1e-10 (1 + |tau|): zeta = tau', converged
+ *             k' = K'(tau') - c
+ *             if sign(k) != sign(k'):
+ *                 if |tau' - tau| > prev - 1e-10: tau' = tau + sign(k' - k) prev / 2, k' = K'(tau') - c, prev = prev / 2
+ *                 else: prev = |tau' - tau|
+ *             tau = tau', k = k'
+ *  Tail.  w = sign(zeta) sqrt(2 (zeta c - K(zeta))), v = zeta sqrt(K''(zeta)), r = w + log(v / w) / w; the upper tail is 1 - Phi(r),
+ *     the lower Phi(r), by gpca_normal_log10p's scheme in log space; the tail fails if r is not finite or has the sign opposite to c.
+ *     The two-sided p is the sum of the two tails, formed in log space as max + log1p.
+ * spa [rows][T][4] = -log10 p, status, zeta+, zeta- (zeta in the operand's coding: on a flipped row they are those of allele A1 negated
+ * and swapped).  status 0: |z| < spa_z or U = 0: the normal value gpca_normal_log10p(z), zeta NaN.  1: the correction applied.  2: a
+ * tail did not converge or failed: the normal value (SAIGE's behaviour), zeta what was reached.  Where a13 gives NaN statistics,
+ * -log10 p and zeta are NaN and the status is 0.  spa_z is at least 0.5 (below it w and v both tend to 0 and log(v / w) / w cancels) or
+ * +inf (no item is corrected); SAIGE's cutoff is 2.
+ * Device: the items are flagged and compacted after a13's finish kernel; a workgroup owns an item, reads its row once, keeps g~ in its
+ * slice of a workspace bounded independently of the band, and every sum over the samples runs through a fixed tree that depends on N
+ * alone (no atomics on sums), so a band is bit-identical to the same rows of the full call and int8, 2-bit and a GPCA_PREC_F32_MFMA
+ * handle give the same bits.  Out of scope: Firth's correction, the fast partially-normal variant of SAIGE for non-carriers, and
+ * everything a13 leaves out.
+ * Errors: those of gpca_assoc_logistic_score, and GPCA_ERR_BAD_ARG for a NULL spa or an spa_z below 0.5 or NaN.
+ * gpca_spa_log10p: the same rules for one given vector g~ [n] with mu [n] (in [0, 1]; a sample with mu (1 - mu) = 0 adds nothing) and
+ * U = u, sums in sample order; host only, no handle.  Its normal value (u = 0, status 2) is that of u / sqrt(sum mu (1 - mu) g~^2);
+ * there is no cutoff: status 0 only for u = 0.  zeta [2] and status may be NULL.  GPCA_ERR_BAD_ARG: a NULL vector or log10p, n < 1, a
+ * non-finite g~ or u, a mu outside [0, 1]. */
+GPCA_API int gpca_assoc_logistic_spa(gpca_handle* h, const double* Y /* [N][T], 0 / 1 */, int32_t T, const double* C /* [N][Pc] or NULL */,
+                                     int32_t Pc, const uint8_t* include /* [N] or NULL */, double max_vif, double spa_z, int64_t row0,
+                                     int64_t row1, double* stats /* [rows][T][5] or NULL */, double* spa /* [rows][T][4] */,
+                                     double* ua /* [rows][T][Pc + 3] or NULL */, double* rowinfo /* [rows][5] or NULL */);
+GPCA_API int gpca_spa_log10p(const double* gt /* [n] */, const double* mu /* [n] */, int64_t n, double u, double* log10p,
+                             double* zeta /* [2] or NULL */, int32_t* status /* may be NULL */);
 
 /* ---- f3: the stages of EigenSNPCoreAlgorithm::compute_pca (main.rs:311-327, 359-366) ------------------------------------------
  * The algorithm lives in the un-vendored efficient_pca crate (Cargo.toml:30, branch "main", no pinned revision): what follows is

@@ -251,6 +251,30 @@ public:
         rowinfo.resize(rows * 5);
         if (ua) ua->resize(rows * (size_t)T * (size_t)(Pc + 3));
     }
+    // the same scan with the saddle-point correction (gpca_assoc_logistic_spa; gpca.h section a14) of the items with |z| >= spa_z (at
+    // least 0.5, or inf): spa [rows][T][4] = -log10 p, status (0 not applied, 1 applied, 2 not converged: the normal value), zeta+, zeta-
+    void assoc_logistic_spa(const std::vector<double>& Y, int32_t T, const std::vector<double>& C, int32_t Pc, const std::vector<uint8_t>* include,
+                            double max_vif, double spa_z, int64_t row0, int64_t row1, std::vector<double>& stats, std::vector<double>& spa,
+                            std::vector<double>& rowinfo, std::vector<double>* ua = nullptr) const {
+        const size_t rows = row1 > row0 ? (size_t)(row1 - row0) : 0;
+        stats.assign(std::max<size_t>(rows * (size_t)T * 5, 1), 0.0);
+        spa.assign(std::max<size_t>(rows * (size_t)T * 4, 1), 0.0);
+        rowinfo.assign(std::max<size_t>(rows * 5, 1), 0.0);
+        if (ua) ua->assign(std::max<size_t>(rows * (size_t)T * (size_t)(Pc + 3), 1), 0.0);
+        check(gpca_assoc_logistic_spa(h_, Y.data(), T, Pc ? C.data() : nullptr, Pc, include ? include->data() : nullptr, max_vif, spa_z, row0, row1,
+                                      stats.data(), spa.data(), ua ? ua->data() : nullptr, rowinfo.data()));
+        stats.resize(rows * (size_t)T * 5);
+        spa.resize(rows * (size_t)T * 4);
+        rowinfo.resize(rows * 5);
+        if (ua) ua->resize(rows * (size_t)T * (size_t)(Pc + 3));
+    }
+    // the saddle-point correction for one given vector (gpca_spa_log10p; host only): returns -log10 p; zeta [2] and status may be null
+    static double spa_log10p(const std::vector<double>& gt, const std::vector<double>& mu, double u, double* zeta = nullptr, int32_t* status = nullptr) {
+        double lp = 0.0;
+        const int rc = gt.size() != mu.size() ? GPCA_ERR_BAD_ARG : gpca_spa_log10p(gt.data(), mu.data(), (int64_t)gt.size(), u, &lp, zeta, status);
+        if (rc != GPCA_OK) throw Error(rc, std::string("gpca_spa_log10p: ") + gpca_status_string(rc));
+        return lp;
+    }
     // the null logistic model of one trait (gpca_logistic_null; host only): y [N] in {0, 1}, C [N][Pc]; alpha [Pc + 1], mu [N] (0 outside
     // the included samples); returns the number of Newton steps; throws Error with the status (no message: there is no handle)
     static int logistic_null(const std::vector<double>& y, const std::vector<double>& C, int32_t Pc, const std::vector<uint8_t>* include,

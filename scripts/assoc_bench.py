@@ -5,7 +5,7 @@ second counted as 2 K N L_pad (the d product; the e product runs only where call
 MFMA peak, and the genotype bytes of one read of the band per second beside the 8 TB/s of the HBM.  One JSON line per L.
 
 usage: python scripts/assoc_bench.py [--rows M] [--samples N] [--storage int8|2bit] [--missing RATE] [--cols L ...] [--band ROWS] [--reps R]
-                                     [--score]
+                                     [--score] [--spa]
 
 Clean matrices come from the device generator; with --missing > 0 the rows are a 4 096-row host tile (that missing rate, seeded)
 repeated down the matrix and uploaded through a host panel source.  --band ROWS: rows per call (0 = io.assoc_bands' default).  Of the
@@ -15,7 +15,14 @@ L columns a third (at most 20) are covariates: random orthonormal columns; the t
 (32 = 8 traits x (1 covariate + 3), 64 = 16 x 4; any other L is taken as T = L // 4 traits with one covariate) one JSON line with
 "assoc_score" ms (the k_assoc_score pass), "assoc_score_count" ms (the count sweep that decides the flip), "assoc" ms at the same L and
 the ratio (score + count) / assoc; wall_ms adds the null fits on the host.  The traits are Bernoulli(0.4), the covariate standard
-normal."""
+normal.
+
+--spa (with the shapes of --score): gpca_assoc_logistic_spa beside gpca_assoc_logistic_score on the same traits in the same run, the
+three calls alternating rep by rep: per L one JSON line with the wall ms of a pass over the bands for the score call, for the new call
+at spa_z = inf (nothing corrected: the flag kernel and the copy of its output are all it adds) and at spa_z = 2, each as the median
+of the reps with the smallest and largest beside it, the "assoc_spa" ms of the library's record (the flag and correction kernels) at
+either cutoff, and the share of the items with status >= 1 at spa_z = 2.  The traits are Bernoulli(0.1) here: the unbalanced case the
+correction exists for."""
 import argparse
 import json
 import os
@@ -37,6 +44,7 @@ ap.add_argument("--cols", type=int, nargs="+", default=[32, 64])
 ap.add_argument("--band", type=int, default=0)
 ap.add_argument("--reps", type=int, default=2)
 ap.add_argument("--score", action="store_true")
+ap.add_argument("--spa", action="store_true")
 a = ap.parse_args()
 M, N = a.rows, a.samples
 store = _lib.STORE_INT8 if a.storage == "int8" else _lib.STORE_2BIT
@@ -56,7 +64,34 @@ with g.GpcaEngine(precision=_lib.PREC_I8_EXACT, storage=store) as e:
     e.snp_stats()
     K = e.num_pca_snps()
     load_s = time.time() - t0
-    for L in a.cols if a.score else []:
+    for L in a.cols if a.spa else []:
+        T, Pc = max(L // 4, 1), 1
+        Yb = (rng.random((N, T)) < 0.1).astype(np.float64)
+        Cs = rng.standard_normal((N, Pc))
+        bands = [(r0, min(r0 + a.band, K)) for r0 in range(0, K, a.band)] if a.band else gio.assoc_score_bands(K, T, Pc)
+        calls = {"score": lambda b: e.assoc_logistic_score(Yb, Cs, rows=b), "spa_inf": lambda b: e.assoc_logistic_spa(Yb, Cs, spa_z=float("inf"), rows=b),
+                 "spa_2": lambda b: e.assoc_logistic_spa(Yb, Cs, spa_z=2.0, rows=b)}
+        for f in calls.values():
+            f((0, min(K, 128)))                          # warm-up
+        e.enable_timings(True)
+        wall, spa_ms, flagged, items = {k: [] for k in calls}, {}, 0, 0
+        for r in range(a.reps):
+            for k, f in calls.items():
+                e.reset_timings()
+                t0 = time.time()
+                for b in bands:
+                    res = f(b)
+                    if k == "spa_2" and r == 0:
+                        flagged += int((res["spa_status"] >= 1).sum()); items += res["spa_status"].size
+                wall[k].append((time.time() - t0) * 1e3)
+                spa_ms[k] = e.timings().get("assoc_spa", {}).get("total_ms", float("nan"))
+        stat = lambda v: [round(float(np.median(v)), 3), round(min(v), 3), round(max(v), 3)]
+        print(json.dumps({"shape": f"{M} x {N}", "kept_rows": K, "storage": a.storage, "missing": a.missing, "L": T * (Pc + 3), "traits": T,
+                          "covariates": Pc, "bands": len(bands), "score_wall_ms_med_min_max": stat(wall["score"]),
+                          "spa_inf_wall_ms_med_min_max": stat(wall["spa_inf"]), "spa_2_wall_ms_med_min_max": stat(wall["spa_2"]),
+                          "assoc_spa_ms_at_inf": round(spa_ms["spa_inf"], 3), "assoc_spa_ms_at_2": round(spa_ms["spa_2"], 3),
+                          "flagged_share_at_2": round(flagged / max(items, 1), 5), "load_s": round(load_s, 2), "reps": a.reps}), flush=True)
+    for L in a.cols if a.score and not a.spa else []:
         T, Pc = max(L // 4, 1), 1
         Ls = T * (Pc + 3)
         Yb = (rng.random((N, T)) < 0.4).astype(np.float64)
@@ -83,7 +118,7 @@ with g.GpcaEngine(precision=_lib.PREC_I8_EXACT, storage=store) as e:
                           "issued_multiplies_ratio": round((8 * lpad / 32 + 8) / (8 * lpad / 32), 3), "wall_ms": round(wall_ms, 3),
                           "read_at_8tbs_ms": round(gbytes / 8e12 * 1e3, 3), "mfma_at_157tf_ms": round(2.0 * K * N * (lpad + 32) / 157e12 * 1e3, 3),
                           "load_s": round(load_s, 2), "reps": a.reps}), flush=True)
-    for L in [] if a.score else a.cols:
+    for L in [] if a.score or a.spa else a.cols:
         Pc = min(L // 3, 20)
         Y = rng.standard_normal((N, L - Pc))
         C = np.linalg.qr(rng.standard_normal((N, max(Pc, 1))))[0][:, :Pc]
