@@ -1,42 +1,29 @@
 // Linear association scan (gpca_assoc_linear; gpca_assoc.cpp): ordinary least squares of T traits on (1, C, g) for every kept row g,
-// a missing call imputed to the row's mean over the included samples.  (The staging helpers live in assoc_stage.h, shared with
-// assoc_score.hip.)
+// a missing call imputed to the row's mean over the included samples.  (The stage pipeline lives in assoc_tile.h and the staging
+// helpers in assoc_stage.h, both shared with assoc_score.hip.)
 //
 // The host hands over B = [Y~ | Q] (N x L, L = T + Pc <= 64, f32; every column sums to 0 over the included samples and is 0 outside
 // them), transposed and zero-padded to [asc_lpad(L)][asc_npad(N)], and the include mask as one bit per sample.  With o = [observed and
 // included], g' = g o:
 //     n_obs = sum o,  s1 = sum g',  s2 = sum g'^2          (exact integers, counted while the calls are staged)
 //     d_ij = sum_n g'_in B_nj,   e_ij = sum_n [missing and included]_in B_nj
-// k_assoc: a workgroup owns kAscRows = 128 kept rows x all columns, 4 waves of 32 rows x lpad columns, and walks the samples in stages
-// of kAscStage = 64.  A stage in LDS is the calls as bytes [row][sample] (0, 1, 2 or the missing code; an excluded sample and a sample
-// past N are 0) and the panel of B^T [column][sample]; a lane reads 8 consecutive samples of its row (ds_read_b64) and of its column
-// (2 x ds_read_b128) and turns the bytes into the f32 operands g' and [missing] in registers, so every product of the
-// v_mfma_f32_32x32x2_f32 is exact.  The 16 samples of a group of 8 multiplies are taken as (i, 8 + i), i = 0 .. 7: the order is a
-// function of the sample index alone.  e is multiplied only in 16-sample groups where a wave ballot finds a missing call.  Two LDS
-// buffers: the waves multiply stage s from one while stage s + 1 (loaded during stage s - 1) is written to the other and stage s + 2 is
-// requested, one barrier per stage.  Every kAscFlush = 256 samples, counted from sample 0, the f32 accumulators are added to f64
-// running sums held in registers.  No split of the sample axis, no atomics: a row's sums depend on the row and on N alone, so a band
+// k_assoc: asc_pipeline (assoc_tile.h: the tile, the stages through two LDS buffers, the exact products, the order of the samples and
+// the flush into f64 running sums) with asc_put as the stager: the staged bytes are the calls (0, 1, 2 or the missing code), checked
+// and counted on their way into LDS.  No split of the sample axis, no atomics: a row's sums depend on the row and on N alone, so a band
 // gives the bits of the full call and int8 and 2-bit residency (the same bytes in LDS) give the same bits.
 // Registers, lpad = 64: d and e each hold 2 x 16 f32 accumulators and 2 x 16 f64 running sums = 96 registers, 192 for both; with the
-// prefetch of a stage (8 of calls + 16 of B) and the operands of a group (16 + 16) the compiler takes 256 VGPRs + 122 AGPRs of the
+// prefetch of a stage (8 of calls + 16 of B) and the operands of a group (16 + 16) the compiler takes 256 VGPRs + 76 AGPRs of the
 // 512 a wave of a 256-thread workgroup may use (no spill): one wave per SIMD.  lpad = 32 halves the sums: 158 + 32, two waves.
 // Epilogue (f64, no contraction): mbar = s1 / n_obs, xb_ij = d_ij + mbar * e_ij.  k_assoc_finish (one thread per row): xx = s2 - s1 *
 // mbar, sxx = xx - sum_{j >= T} xb_ij^2 (j ascending), and per trait beta = xb / sxx, rss = yy - xb * beta, se = sqrt(rss / df / sxx),
 // t = beta / se; NaN when n_obs = 0, xx <= 0, sxx * max_vif < xx or rss <= 0.
 // Out of scope: case / control traits (assoc_score.hip has their score test), per-variant dropping of samples with a missing call,
 // per-trait sample sets, mixed models that use the GRM, streamed and row-sharded handles.
-#include "assoc_stage.h"
+#include "assoc_tile.h"
 
 #pragma clang fp contract(off)
 
 namespace gpca {
-
-template <int NB>
-struct AscSmem {
-    uint8_t g[2][kAscRows * kAscGPitch];
-    float b[2][NB * 32 * kAscBPitch];
-    unsigned sums[kAscRows * 3];
-};
 
 // xb [row1 - row0][L] f64, sums [row1 - row0][3] u32 of kept rows [row0, row1); *bad = min original row with a value outside
 // {0, 1, 2, missing}
@@ -45,87 +32,18 @@ __global__ __launch_bounds__(kAscThreads) void k_assoc(const void* __restrict__ 
                                                        int64_t npad, const float* __restrict__ Bt, const unsigned* __restrict__ incw, int L,
                                                        int64_t row0, int64_t row1, double* __restrict__ xb, unsigned* __restrict__ sums,
                                                        unsigned long long* __restrict__ bad) {
-    __shared__ __attribute__((aligned(16))) AscSmem<NB> sm;
-    const uint8_t* G = (const uint8_t*)Gv;
+    __shared__ __attribute__((aligned(16))) AscSmem<NB, 3> sm;
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int c = lane & 31, h = lane >> 5;
     const int64_t k0 = row0 + (int64_t)blockIdx.x * kAscRows;
 
-    // staging map: thread t carries 32 samples (half sh of the stage) of row t / 2
+    // (the pipeline's staging map: this thread stages half sh of row srow)
     const int srow = threadIdx.x >> 1, sh = threadIdx.x & 1;
     const int64_t sorow = k0 + srow < row1 ? krows[k0 + srow] : -1;
-    auto inb_of = [&](int64_t s) {
-        const int64_t left = N - (s * kAscStage + 32 * sh);
-        return left >= 32 ? 0xffffffffu : (left <= 0 ? 0u : (1u << (int)left) - 1u);
-    };
-    auto inc_of = [&](int64_t s) { return incw[s * (kAscStage / 32) + sh]; };
     unsigned nobs = 0u, s1 = 0u, s2 = 0u, bd = 0u;
-
-    f32x16 ad[NB], ae[NB];
     double rd[NB][16], re[NB][16];
-#pragma unroll
-    for (int j = 0; j < NB; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) { ad[j][e] = 0.0f; ae[j][e] = 0.0f; rd[j][e] = 0.0; re[j][e] = 0.0; }
-
-    const int64_t nst = asc_stages(N);
-    const int g_off = (32 * wv + c) * kAscGPitch + 8 * h, b_off = c * kAscBPitch + 8 * h;
-    const int sg_off = srow * kAscGPitch + 32 * sh;
-
-    AscFetch F;
-    f32x4 P[2 * NB];
-    asc_fetch<PACKED>(F, G, ldr, sorow, 32 * sh);
-    asc_fetch_b<NB>(P, Bt, npad, 0);
-    asc_put(F, inb_of(0), inc_of(0), sm.g[0] + sg_off, nobs, s1, s2, bd);
-    asc_put_b<NB>(P, sm.b[0]);
-    if (nst > 1) { asc_fetch<PACKED>(F, G, ldr, sorow, kAscStage + 32 * sh); asc_fetch_b<NB>(P, Bt, npad, kAscStage); }
-    __syncthreads();
-    for (int64_t s = 0; s < nst; ++s) {
-        const uint8_t* lg = sm.g[s & 1] + g_off;
-        const float* lb = sm.b[s & 1] + b_off;
-#pragma unroll
-        for (int q = 0; q < kAscStage / 16; ++q) {
-            const uint2 gb = *reinterpret_cast<const uint2*>(lg + 16 * q);
-            const bool anym = __builtin_amdgcn_ballot_w64(((gb.x | gb.y) & 0x80808080u) != 0u) != 0ull;      // wave-uniform
-            const unsigned mx = (gb.x >> 7) & 0x01010101u, my = (gb.y >> 7) & 0x01010101u;
-            const unsigned gx = gb.x & ~(mx * 0xffu), gy = gb.y & ~(my * 0xffu);
-            float gf[8], mf[8];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                gf[i] = (float)((gx >> (8 * i)) & 0xffu); gf[4 + i] = (float)((gy >> (8 * i)) & 0xffu);
-                mf[i] = (float)((mx >> (8 * i)) & 0xffu); mf[4 + i] = (float)((my >> (8 * i)) & 0xffu);
-            }
-#pragma unroll
-            for (int j = 0; j < NB; ++j) {
-                const f32x4 b0 = *reinterpret_cast<const f32x4*>(lb + 32 * j * kAscBPitch + 16 * q);
-                const f32x4 b1 = *reinterpret_cast<const f32x4*>(lb + 32 * j * kAscBPitch + 16 * q + 4);
-#pragma unroll
-                for (int i = 0; i < 8; ++i) ad[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(gf[i], i < 4 ? b0[i] : b1[i - 4], ad[j], 0, 0, 0);
-                if (anym) {
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) ae[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(mf[i], i < 4 ? b0[i] : b1[i - 4], ae[j], 0, 0, 0);
-                }
-            }
-        }
-        if ((s + 1) % (kAscFlush / kAscStage) == 0 || s + 1 == nst) {
-#pragma unroll
-            for (int j = 0; j < NB; ++j)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    rd[j][e] += (double)ad[j][e]; ad[j][e] = 0.0f;
-                    re[j][e] += (double)ae[j][e]; ae[j][e] = 0.0f;
-                }
-        }
-        if (s + 1 < nst) {
-            asc_put(F, inb_of(s + 1), inc_of(s + 1), sm.g[(s + 1) & 1] + sg_off, nobs, s1, s2, bd);
-            asc_put_b<NB>(P, sm.b[(s + 1) & 1]);
-        }
-        if (s + 2 < nst) {
-            asc_fetch<PACKED>(F, G, ldr, sorow, (s + 2) * kAscStage + 32 * sh);
-            asc_fetch_b<NB>(P, Bt, npad, (s + 2) * kAscStage);
-        }
-        __syncthreads();
-    }
+    asc_pipeline<PACKED, NB, false>(sm, (const uint8_t*)Gv, ldr, sorow, N, npad, Bt, incw,
+                         [&](const AscFetch& F, unsigned inb, unsigned inc, uint8_t* dst) { asc_put(F, inb, inc, dst, nobs, s1, s2, bd); }, rd, re, nullptr, wv, lane);
 
     if (bd && sorow >= 0) atomicMin(bad, (unsigned long long)sorow);
     // the two halves of a row sit in neighbouring lanes
@@ -140,7 +58,7 @@ __global__ __launch_bounds__(kAscThreads) void k_assoc(const void* __restrict__ 
     __syncthreads();
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-        const int r = 32 * wv + (e & 3) + 8 * (e >> 2) + 4 * h;
+        const int r = asc_acc_row(wv, h, e);
         const int64_t kr = k0 + r;
         if (kr >= row1) continue;
         const double mbar = (double)sm.sums[3 * r + 1] / (double)sm.sums[3 * r];

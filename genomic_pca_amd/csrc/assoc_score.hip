@@ -2,22 +2,21 @@
 // g, the null logistic model of each trait fitted once on the host, a missing call imputed to the row's mean over the included samples.
 //
 // The host hands over the panel B (N x L, L = T (Pc + 3) <= 64, f32, 0 outside the included samples S), transposed and zero-padded
-// to [asc_lpad(L)][asc_npad(N)] as k_assoc's is, and the include mask as one bit per sample.  Per trait t, with mu the fitted
+// to [asc_lpad(L)][asc_npad(N)] as the linear scan's is, and the include mask as one bit per sample.  Per trait t, with mu the fitted
 // probabilities, X = (1, C centred over S and scaled to unit norm) and X^T W X = L L^T:
 //     w_t = mu (1 - mu)   (columns 0 .. T - 1),     r_t = y - mu   (columns T .. 2 T - 1),
 //     A_t,j, j = 0 .. Pc = the columns of W X L^-T   (columns 2 T + t (Pc + 1) + j; j = 0 is the intercept's).
 // k_assoc_score_count (a wave per row, a lane 32 samples of every 2 048): o = [observed and in S], the exact integers n_obs = sum o,
 // s1 = sum g o, s2 = sum g^2 o, and the invalid-genotype flag.  Row i is FLIPPED iff s1 > n_obs (its A1 mean is above 1): a function
 // of the row and S alone.
-// k_assoc_score: k_assoc's tile and pipeline (a workgroup owns kAscRows = 128 kept rows x all columns, 4 waves of 32 rows, stages of
-// kAscStage = 64 samples through two LDS buffers, one barrier per stage; see assoc.hip).  The staged byte of a sample is the operand
-// x = g o on a plain row and (2 - g) o on a flipped one (0, 1, 2), or the missing code for m = [missing and in S].  Per 16-sample group
+// k_assoc_score: asc_pipeline (assoc_tile.h: the tile and pipeline that k_assoc runs too) with asr_put as the stager and the x^2
+// accumulator on.  The staged byte of a sample is the operand x = g o on a plain row and (2 - g) o on a flipped one (0, 1, 2), or the
+// missing code for m = [missing and in S].  Per 16-sample group
 //     d_c += x B_c   (all columns),     e_c += m B_c   (only where a wave ballot finds a missing call),     q_c += x^2 B_c   (the first
 //     block of 32 columns only: it holds every w_t)
-// on v_mfma_f32_32x32x2_f32; x, m and x^2 are 0, 1, 2 or 4, so every product is exact.  Every kAscFlush = 256 samples, counted from
-// sample 0, the f32 accumulators are added to f64 running sums held in registers.  No split of the sample axis, no atomics on sums: a
-// row's sums depend on the row, S and N alone, so a band gives the bits of the full call and int8 and 2-bit residency (the same bytes
-// in LDS) give the same bits.  A 16-sample group issues 8 NB + 8 multiplies against k_assoc's 8 NB.
+// x, m and x^2 are 0, 1, 2 or 4, so every product is exact.  No split of the sample axis, no atomics on sums: a row's sums depend on
+// the row, S and N alone, so a band gives the bits of the full call and int8 and 2-bit residency (the same bytes in LDS) give the same
+// bits.  A 16-sample group issues 8 NB + 8 multiplies against k_assoc's 8 NB.
 // Registers: d and e as in k_assoc (lpad = 64: 2 x (32 f32 + 32 f64) each), q adds 16 f32 + 16 f64; the figures hipcc reports are in
 // DESIGN section 7 (no spill at either width).
 // Epilogue (f64, no contraction): xbar = (s1 or 2 n_obs - s1) / n_obs, the operand's mean; dv_c = d_c + xbar e_c for c >= T (U_t and
@@ -29,7 +28,7 @@
 // 1 the factor stays near 3.
 // Out of scope: Firth's correction (assoc_spa.hip has the saddle-point correction), a Wald / IRLS fit per SNP, per-variant dropping of samples, case / control
 // frequency columns, mixed models, streamed and row-sharded handles.
-#include "assoc_stage.h"
+#include "assoc_tile.h"
 
 #pragma clang fp contract(off)
 
@@ -50,10 +49,8 @@ __global__ __launch_bounds__(kAsrCountThreads) void k_assoc_score_count(const vo
     for (int64_t n0 = 32 * lane; n0 < npad; n0 += kAsrChunk) {
         AscFetch F;
         asc_fetch<PACKED>(F, G, ldr, orow, n0);
-        const int64_t left = N - n0;
-        const unsigned inb = left >= 32 ? 0xffffffffu : (left <= 0 ? 0u : (1u << (int)left) - 1u);
         unsigned o[8];
-        asc_mask_count(F, inb, incw[n0 >> 5], o, nobs, s1, s2, bd);
+        asc_mask_count(F, asc_inb(N, n0), incw[n0 >> 5], o, nobs, s1, s2, bd);
     }
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) {
@@ -66,118 +63,32 @@ __global__ __launch_bounds__(kAsrCountThreads) void k_assoc_score_count(const vo
     }
 }
 
-template <int NB>
-struct AsrSmem {
-    uint8_t g[2][kAscRows * kAscGPitch];
-    float b[2][NB * 32 * kAscBPitch];
-    unsigned sums[kAscRows * 2];
-};
-
 // dv [row1 - row0][L] f64 of kept rows [row0, row1); sums: what k_assoc_score_count left for the same band
 template <bool PACKED, int NB>
 __global__ __launch_bounds__(kAscThreads) void k_assoc_score(const void* __restrict__ Gv, int64_t ldr, const int64_t* __restrict__ krows, int64_t N,
                                                              int64_t npad, const float* __restrict__ Bt, const unsigned* __restrict__ incw, int T,
                                                              int L, int64_t row0, int64_t row1, const unsigned* __restrict__ sums,
                                                              double* __restrict__ dv) {
-    __shared__ __attribute__((aligned(16))) AsrSmem<NB> sm;
-    const uint8_t* G = (const uint8_t*)Gv;
+    __shared__ __attribute__((aligned(16))) AscSmem<NB, 2> sm;
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int c = lane & 31, h = lane >> 5;
     const int64_t k0 = row0 + (int64_t)blockIdx.x * kAscRows;
 
-    // staging map: thread t carries 32 samples (half sh of the stage) of row t / 2
+    // (the pipeline's staging map: this thread stages half sh of row srow)
     const int srow = threadIdx.x >> 1, sh = threadIdx.x & 1;
     const bool slive = k0 + srow < row1;
     const int64_t sorow = slive ? krows[k0 + srow] : -1;
     const unsigned snobs = slive ? sums[(k0 + srow - row0) * 3] : 0u, ss1 = slive ? sums[(k0 + srow - row0) * 3 + 1] : 0u;
     const bool flip = ss1 > snobs;
     if (sh == 0) { sm.sums[2 * srow] = snobs; sm.sums[2 * srow + 1] = flip ? 2u * snobs - ss1 : ss1; }
-    auto inb_of = [&](int64_t s) {
-        const int64_t left = N - (s * kAscStage + 32 * sh);
-        return left >= 32 ? 0xffffffffu : (left <= 0 ? 0u : (1u << (int)left) - 1u);
-    };
-    auto inc_of = [&](int64_t s) { return incw[s * (kAscStage / 32) + sh]; };
-
-    f32x16 ad[NB], ae[NB], aq;
     double rd[NB][16], re[NB][16], rq[16];
-#pragma unroll
-    for (int e = 0; e < 16; ++e) { aq[e] = 0.0f; rq[e] = 0.0; }
-#pragma unroll
-    for (int j = 0; j < NB; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) { ad[j][e] = 0.0f; ae[j][e] = 0.0f; rd[j][e] = 0.0; re[j][e] = 0.0; }
-
-    const int64_t nst = asc_stages(N);
-    const int g_off = (32 * wv + c) * kAscGPitch + 8 * h, b_off = c * kAscBPitch + 8 * h;
-    const int sg_off = srow * kAscGPitch + 32 * sh;
-
-    AscFetch F;
-    f32x4 P[2 * NB];
-    asc_fetch<PACKED>(F, G, ldr, sorow, 32 * sh);
-    asc_fetch_b<NB>(P, Bt, npad, 0);
-    asr_put(F, inb_of(0), inc_of(0), flip, sm.g[0] + sg_off);
-    asc_put_b<NB>(P, sm.b[0]);
-    if (nst > 1) { asc_fetch<PACKED>(F, G, ldr, sorow, kAscStage + 32 * sh); asc_fetch_b<NB>(P, Bt, npad, kAscStage); }
-    __syncthreads();
-    for (int64_t s = 0; s < nst; ++s) {
-        const uint8_t* lg = sm.g[s & 1] + g_off;
-        const float* lb = sm.b[s & 1] + b_off;
-#pragma unroll
-        for (int q = 0; q < kAscStage / 16; ++q) {
-            const uint2 gb = *reinterpret_cast<const uint2*>(lg + 16 * q);
-            const bool anym = __builtin_amdgcn_ballot_w64(((gb.x | gb.y) & 0x80808080u) != 0u) != 0ull;      // wave-uniform
-            const unsigned mx = (gb.x >> 7) & 0x01010101u, my = (gb.y >> 7) & 0x01010101u;
-            const unsigned gx = gb.x & ~(mx * 0xffu), gy = gb.y & ~(my * 0xffu);
-            float gf[8], mf[8], g2[8];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                gf[i] = (float)((gx >> (8 * i)) & 0xffu); gf[4 + i] = (float)((gy >> (8 * i)) & 0xffu);
-                mf[i] = (float)((mx >> (8 * i)) & 0xffu); mf[4 + i] = (float)((my >> (8 * i)) & 0xffu);
-            }
-#pragma unroll
-            for (int i = 0; i < 8; ++i) g2[i] = gf[i] * gf[i];
-#pragma unroll
-            for (int j = 0; j < NB; ++j) {
-                const f32x4 b0 = *reinterpret_cast<const f32x4*>(lb + 32 * j * kAscBPitch + 16 * q);
-                const f32x4 b1 = *reinterpret_cast<const f32x4*>(lb + 32 * j * kAscBPitch + 16 * q + 4);
-#pragma unroll
-                for (int i = 0; i < 8; ++i) ad[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(gf[i], i < 4 ? b0[i] : b1[i - 4], ad[j], 0, 0, 0);
-                if (j == 0) {
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) aq = __builtin_amdgcn_mfma_f32_32x32x2f32(g2[i], i < 4 ? b0[i] : b1[i - 4], aq, 0, 0, 0);
-                }
-                if (anym) {
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) ae[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(mf[i], i < 4 ? b0[i] : b1[i - 4], ae[j], 0, 0, 0);
-                }
-            }
-        }
-        if ((s + 1) % (kAscFlush / kAscStage) == 0 || s + 1 == nst) {
-#pragma unroll
-            for (int e = 0; e < 16; ++e) { rq[e] += (double)aq[e]; aq[e] = 0.0f; }
-#pragma unroll
-            for (int j = 0; j < NB; ++j)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    rd[j][e] += (double)ad[j][e]; ad[j][e] = 0.0f;
-                    re[j][e] += (double)ae[j][e]; ae[j][e] = 0.0f;
-                }
-        }
-        if (s + 1 < nst) {
-            asr_put(F, inb_of(s + 1), inc_of(s + 1), flip, sm.g[(s + 1) & 1] + sg_off);
-            asc_put_b<NB>(P, sm.b[(s + 1) & 1]);
-        }
-        if (s + 2 < nst) {
-            asc_fetch<PACKED>(F, G, ldr, sorow, (s + 2) * kAscStage + 32 * sh);
-            asc_fetch_b<NB>(P, Bt, npad, (s + 2) * kAscStage);
-        }
-        __syncthreads();
-    }
+    asc_pipeline<PACKED, NB, true>(sm, (const uint8_t*)Gv, ldr, sorow, N, npad, Bt, incw,
+                         [&](const AscFetch& F, unsigned inb, unsigned inc, uint8_t* dst) { asr_put(F, inb, inc, flip, dst); }, rd, re, rq, wv, lane);
 
     // (sm.sums was written before the first barrier: n_obs and the operand's sum of every row of the tile)
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-        const int r = 32 * wv + (e & 3) + 8 * (e >> 2) + 4 * h;
+        const int r = asc_acc_row(wv, h, e);
         const int64_t kr = k0 + r;
         if (kr >= row1) continue;
         const double xbar = (double)sm.sums[2 * r + 1] / (double)sm.sums[2 * r];

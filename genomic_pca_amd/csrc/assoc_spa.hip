@@ -100,9 +100,7 @@ __global__ __launch_bounds__(kAspThreads) void k_assoc_spa(const void* __restric
             if (n0 < npad) {
                 AscFetch F;
                 asc_fetch<PACKED>(F, G, ldr, orow, n0);
-                const int64_t left = N - n0;
-                const unsigned inb = left >= 32 ? 0xffffffffu : (left <= 0 ? 0u : (1u << (int)left) - 1u);
-                asr_put(F, inb, incw[n0 >> 5], flip, sx + 32 * tid);
+                asr_put(F, asc_inb(N, n0), incw[n0 >> 5], flip, sx + 32 * tid);
             }
             __syncthreads();                                                    // (also orders sa before its first use)
 #pragma nounroll

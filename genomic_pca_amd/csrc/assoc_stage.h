@@ -1,5 +1,6 @@
 // The staging helpers of the association kernels (assoc.hip, assoc_score.hip, assoc_spa.hip): the fetch of 32 samples of a row from either storage,
 // the check / mask / count of those samples on their way into a stage's LDS buffer, and the fetch and store of a stage's panel of B^T.
+// (assoc_tile.h holds the stage pipeline that the two mainloop kernels build from them.)
 #pragma once
 #include "gemm_i8_common.h"
 
@@ -35,6 +36,12 @@ __device__ __forceinline__ void asc_fetch(AscFetch& F, const uint8_t* __restrict
         const uint4 b = *reinterpret_cast<const uint4*>(G + orow * ldr + ns + 16);
         F.w[0] = a.x; F.w[1] = a.y; F.w[2] = a.z; F.w[3] = a.w; F.w[4] = b.x; F.w[5] = b.y; F.w[6] = b.z; F.w[7] = b.w;
     }
+}
+
+// the "samples left of N" mask of the 32 samples that start at n0: bit s = sample n0 + s lies below N
+__device__ __forceinline__ unsigned asc_inb(int64_t N, int64_t n0) {
+    const int64_t left = N - n0;
+    return left >= 32 ? 0xffffffffu : (left <= 0 ? 0u : (1u << (int)left) - 1u);
 }
 
 // checks, masks and counts the thread's 32 samples: o = the bytes a stage holds (an excluded sample and a sample past N are 0).

@@ -3,9 +3,127 @@
 // over the band's kept rows multiplies them on the matrix cores (k_assoc), a second kernel makes the statistics (k_assoc_finish).
 // The call has its own workspace, allocated and freed per call, and reads nothing of the handle's state but the genotypes and the
 // list of kept rows.
+// The host front end that this scan shares with the logistic scans of gpca_assoc_score.cpp is defined here too (declared in
+// gpca_internal.h): the argument checks, S and the include words, the standardised covariates, the Cholesky factor, X L^-T, the
+// invalid-genotype read-back and the copies of the outputs.
 #include "gpca_internal.h"
 
 using namespace gpca;
+
+// ---- the host front end shared with gpca_assoc_score.cpp (declared in gpca_internal.h) ---------------------------------------
+int asc_check_call(gpca_handle* h, const std::string& f, bool cols_ok, const std::string& cols_rule, const double* Y, const double* C, int Pc,
+                   const char* out_err, int64_t row0, int64_t row1, double max_vif, const char* late_err) {
+    if (!have_genotypes(h)) return fail(h, GPCA_ERR_STATE, f + ": no genotypes resident");
+    if (h->sm.on)
+        return fail(h, GPCA_ERR_STATE, f + ": the handle streams its matrix in panels, which is not implemented");
+    if (multi_rank(h)) return fail(h, GPCA_ERR_STATE, f + ": the handle holds a shard of the rows, which is not implemented");
+    if (!h->have_stats) return fail(h, GPCA_ERR_STATE, f + ": no standardisation: run gpca_snp_stats or gpca_set_standardization first");
+    if (h->n_pca == 0) return fail(h, GPCA_ERR_STATE, f + ": no kept row (the keep mask is empty)");
+    const int64_t K = h->n_pca;
+    if (!cols_ok) return fail(h, GPCA_ERR_BAD_ARG, f + ": " + cols_rule + " are required");
+    if (!Y) return fail(h, GPCA_ERR_BAD_ARG, f + ": Y is required");
+    if (Pc > 0 && !C) return fail(h, GPCA_ERR_BAD_ARG, f + ": C is required when Pc > 0");
+    if (out_err) return fail(h, GPCA_ERR_BAD_ARG, f + ": " + out_err);
+    if (row0 < 0 || row1 < row0 || row1 > K)
+        return fail(h, GPCA_ERR_BAD_ARG, f + ": rows must satisfy 0 <= row0 <= row1 <= K (K = " + std::to_string(K) + " kept rows)");
+    if (!(max_vif >= 1.0) || !std::isfinite(max_vif)) return fail(h, GPCA_ERR_BAD_ARG, f + ": max_vif must be finite and at least 1");
+    if (late_err) return fail(h, GPCA_ERR_BAD_ARG, f + ": " + late_err);
+    if (h->N >= ((int64_t)1 << 30)) return fail(h, GPCA_ERR_BAD_ARG, f + ": 2^30 or more samples (the per-row sums are 32-bit)");
+    return GPCA_OK;
+}
+
+void asc_sample_set(const uint8_t* include, int64_t N, std::vector<int64_t>& S, std::vector<unsigned>* incw) {
+    S.clear();
+    S.reserve((size_t)N);
+    for (int64_t n = 0; n < N; ++n) if (!include || include[n]) S.push_back(n);
+    if (!incw) return;
+    incw->assign((size_t)asc_inc_capacity(N), 0u);
+    for (int64_t n : S) (*incw)[(size_t)(n >> 5)] |= 1u << (int)(n & 31);
+}
+
+int asc_standardise(const double* C, int Pc, const std::vector<int64_t>& S, double* X, std::string& msg) {
+    const int64_t ns = (int64_t)S.size();
+    for (int j = 0; j < Pc; ++j) {
+        double* c = X + (size_t)j * (size_t)ns;
+        double sum = 0.0, raw = 0.0, ss = 0.0;
+        for (int64_t i = 0; i < ns; ++i) {
+            c[i] = C[S[(size_t)i] * Pc + j];
+            if (!std::isfinite(c[i])) { msg = "C[" + std::to_string(S[(size_t)i]) + "][" + std::to_string(j) + "] is not finite"; return GPCA_ERR_BAD_ARG; }
+            sum += c[i]; raw += c[i] * c[i];
+        }
+        const double mean = sum / (double)ns;
+        for (int64_t i = 0; i < ns; ++i) { c[i] -= mean; ss += c[i] * c[i]; }
+        if (!std::isfinite(ss) || !(ss > 1e-20 * raw)) {
+            msg = "column " + std::to_string(j) + " of C is constant over the included samples (or overflows)";
+            return GPCA_ERR_BAD_ARG;
+        }
+        const double inv = 1.0 / std::sqrt(ss);
+        for (int64_t i = 0; i < ns; ++i) c[i] *= inv;
+    }
+    return GPCA_OK;
+}
+
+int asc_cholesky(const double* X, int P, int64_t ns, const double* w, bool (*accept)(double d, double diag), std::vector<double>& A,
+                 std::string& msg) {
+    A.assign((size_t)P * P, 0.0);
+    for (int i = 0; i < P; ++i)
+        for (int j = 0; j <= i; ++j) {
+            const double *a = X + (size_t)i * (size_t)ns, *b = X + (size_t)j * (size_t)ns;
+            double s = 0.0;
+            if (w) for (int64_t n = 0; n < ns; ++n) s += w[n] * a[n] * b[n];
+            else for (int64_t n = 0; n < ns; ++n) s += a[n] * b[n];
+            A[(size_t)i * P + j] = s;
+        }
+    for (int j = 0; j < P; ++j) {
+        const double diag = A[(size_t)j * P + j];
+        double d = diag;
+        for (int k = 0; k < j; ++k) d -= A[(size_t)j * P + k] * A[(size_t)j * P + k];
+        if (!accept(d, diag)) {
+            msg = "the covariates (1, C) are collinear over the included samples (Cholesky pivot " + std::to_string(j) + " failed)";
+            return GPCA_ERR_BAD_ARG;
+        }
+        const double l = std::sqrt(d);
+        A[(size_t)j * P + j] = l;
+        for (int i = j + 1; i < P; ++i) {
+            double s = A[(size_t)i * P + j];
+            for (int k = 0; k < j; ++k) s -= A[(size_t)i * P + k] * A[(size_t)j * P + k];
+            A[(size_t)i * P + j] = s / l;
+        }
+    }
+    return GPCA_OK;
+}
+
+void asc_solve_lt(const std::vector<double>& A, int P, int64_t ns, const double* X, const double* w, double* out) {
+    for (int j = 0; j < P; ++j) {
+        double* a = out + (size_t)j * (size_t)ns;
+        const double* x = X + (size_t)j * (size_t)ns;
+        if (w) for (int64_t i = 0; i < ns; ++i) a[i] = w[i] * x[i];
+        else if (a != x) for (int64_t i = 0; i < ns; ++i) a[i] = x[i];
+        for (int k = 0; k < j; ++k) {
+            const double l = A[(size_t)j * P + k];
+            const double* ak = out + (size_t)k * (size_t)ns;
+            for (int64_t i = 0; i < ns; ++i) a[i] -= l * ak[i];
+        }
+        const double inv = 1.0 / A[(size_t)j * P + j];
+        for (int64_t i = 0; i < ns; ++i) a[i] *= inv;
+    }
+}
+
+int asc_check_genotypes(gpca_handle* h, const std::string& f, const unsigned long long* d_bad, hipStream_t st) {
+    unsigned long long bad = 0;
+    HIPCHK(hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (bad != ~0ull)
+        return fail(h, GPCA_ERR_INVALID_GENOTYPE, f + ": row " + std::to_string(bad) + " holds a genotype outside {0, 1, 2, missing}");
+    return GPCA_OK;
+}
+
+int asc_copy_outputs(gpca_handle* h, hipStream_t st, std::initializer_list<AscOutput> outs) {
+    for (const AscOutput& o : outs)
+        if (o.host) HIPCHK(hipMemcpyAsync(o.host, o.dev, (size_t)o.elems * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return GPCA_OK;
+}
 
 namespace {
 struct AscWs {
@@ -15,8 +133,6 @@ struct AscWs {
     unsigned long long* bad = nullptr;
     ~AscWs() { dfree(Bt); dfree(incw); dfree(sums); dfree(xb); dfree(yy); dfree(stats); dfree(info); dfree(bad); }
 };
-template <typename T>
-hipError_t dalloc(T*& p, size_t elems) { return hipMalloc((void**)&p, std::max<size_t>(elems, 1) * sizeof(T)); }
 
 // Host step: S = the included samples; Q = an orthonormal basis of the columns of C centred over S (each scaled to unit norm, then
 // Q = C L^-T with C^T C = L L^T); Y~ = Y centred over S minus Q Q^T Y (taken out twice, so that what rounding leaves of the first pass
@@ -27,63 +143,25 @@ int asc_design(gpca_handle* h, const double* Y, int T, const double* C, int Pc, 
     const int64_t N = h->N, npad = asc_npad(N);
     const int L = T + Pc;
     std::vector<int64_t> S;
-    S.reserve((size_t)N);
-    for (int64_t n = 0; n < N; ++n) if (!include || include[n]) S.push_back(n);
+    asc_sample_set(include, N, S, &incw);
     const int64_t ns = n_inc = (int64_t)S.size();
     if (ns - Pc - 2 < 1)
         return fail(h, GPCA_ERR_BAD_ARG, f + ": " + std::to_string(ns) + " included samples leave df = n - Pc - 2 < 1");
+    // (sample-major: the first entry that is not finite in the order of the caller's rows, ahead of the column-major standardisation)
     for (int64_t n : S) {
         for (int t = 0; t < T; ++t)
             if (!std::isfinite(Y[n * T + t])) return fail(h, GPCA_ERR_BAD_ARG, f + ": Y[" + std::to_string(n) + "][" + std::to_string(t) + "] is not finite");
         for (int j = 0; j < Pc; ++j)
             if (!std::isfinite(C[n * Pc + j])) return fail(h, GPCA_ERR_BAD_ARG, f + ": C[" + std::to_string(n) + "][" + std::to_string(j) + "] is not finite");
     }
-    // the covariates over S, column-major, centred and scaled to unit norm
-    std::vector<double> Cc((size_t)Pc * (size_t)ns), Yc((size_t)T * (size_t)ns);
-    for (int j = 0; j < Pc; ++j) {
-        double* c = &Cc[(size_t)j * (size_t)ns];
-        double sum = 0.0, raw = 0.0, ss = 0.0;
-        for (int64_t i = 0; i < ns; ++i) { c[i] = C[S[(size_t)i] * Pc + j]; sum += c[i]; raw += c[i] * c[i]; }
-        const double mean = sum / (double)ns;
-        for (int64_t i = 0; i < ns; ++i) { c[i] -= mean; ss += c[i] * c[i]; }
-        if (!std::isfinite(ss) || !(ss > 1e-20 * raw))
-            return fail(h, GPCA_ERR_BAD_ARG, f + ": column " + std::to_string(j) + " of C is constant over the included samples (or overflows)");
-        const double inv = 1.0 / std::sqrt(ss);
-        for (int64_t i = 0; i < ns; ++i) c[i] *= inv;
-    }
-    // A = Cc^T Cc = L L^T (unit diagonal: a pivot that falls to 1e-10 means the columns are collinear to working precision)
-    std::vector<double> A((size_t)Pc * Pc, 0.0);
-    for (int i = 0; i < Pc; ++i)
-        for (int j = 0; j <= i; ++j) {
-            const double *a = &Cc[(size_t)i * (size_t)ns], *b = &Cc[(size_t)j * (size_t)ns];
-            double s = 0.0;
-            for (int64_t n = 0; n < ns; ++n) s += a[n] * b[n];
-            A[(size_t)i * Pc + j] = s;
-        }
-    for (int j = 0; j < Pc; ++j) {
-        double d = A[(size_t)j * Pc + j];
-        for (int k = 0; k < j; ++k) d -= A[(size_t)j * Pc + k] * A[(size_t)j * Pc + k];
-        if (!(d > 1e-10))
-            return fail(h, GPCA_ERR_BAD_ARG, f + ": the covariates (1, C) are collinear over the included samples (Cholesky pivot " + std::to_string(j) + " failed)");
-        const double l = std::sqrt(d);
-        A[(size_t)j * Pc + j] = l;
-        for (int i = j + 1; i < Pc; ++i) {
-            double s = A[(size_t)i * Pc + j];
-            for (int k = 0; k < j; ++k) s -= A[(size_t)i * Pc + k] * A[(size_t)j * Pc + k];
-            A[(size_t)i * Pc + j] = s / l;
-        }
-    }
-    // Q L^T = Cc, column by column: q_j = (c_j - sum_{k < j} L_jk q_k) / L_jj, in place
-    for (int j = 0; j < Pc; ++j) {
-        double* q = &Cc[(size_t)j * (size_t)ns];
-        for (int k = 0; k < j; ++k) {
-            const double l = A[(size_t)j * Pc + k];
-            const double* qk = &Cc[(size_t)k * (size_t)ns];
-            for (int64_t n = 0; n < ns; ++n) q[n] -= l * qk[n];
-        }
-        const double inv = 1.0 / A[(size_t)j * Pc + j];
-        for (int64_t n = 0; n < ns; ++n) q[n] *= inv;
-    }
+    // the covariates over S, column-major, centred and scaled to unit norm; A = Cc^T Cc = L L^T (unit diagonal: a pivot that falls to
+    // 1e-10 means the columns are collinear to working precision); Q L^T = Cc, in place
+    std::vector<double> Cc((size_t)Pc * (size_t)ns), Yc((size_t)T * (size_t)ns), A;
+    std::string msg;
+    int rc = asc_standardise(C, Pc, S, Cc.data(), msg);
+    if (rc == GPCA_OK) rc = asc_cholesky(Cc.data(), Pc, ns, nullptr, [](double d, double) { return d > 1e-10; }, A, msg);
+    if (rc != GPCA_OK) return fail(h, rc, f + ": " + msg);
+    asc_solve_lt(A, Pc, ns, Cc.data(), nullptr, Cc.data());
     yy.assign((size_t)T, 0.0);
     for (int t = 0; t < T; ++t) {
         double* y = &Yc[(size_t)t * (size_t)ns];
@@ -105,10 +183,8 @@ int asc_design(gpca_handle* h, const double* Y, int T, const double* C, int Pc, 
         yy[(size_t)t] = ss;
     }
     Bt.assign((size_t)asc_b_capacity(N, L), 0.0f);
-    incw.assign((size_t)asc_inc_capacity(N), 0u);
     for (int64_t i = 0; i < ns; ++i) {
         const int64_t n = S[(size_t)i];
-        incw[(size_t)(n >> 5)] |= 1u << (int)(n & 31);
         for (int t = 0; t < T; ++t) Bt[(size_t)t * (size_t)npad + (size_t)n] = (float)Yc[(size_t)t * (size_t)ns + (size_t)i];
         for (int j = 0; j < Pc; ++j) Bt[(size_t)(T + j) * (size_t)npad + (size_t)n] = (float)Cc[(size_t)j * (size_t)ns + (size_t)i];
     }
@@ -121,22 +197,9 @@ extern "C" int gpca_assoc_linear(gpca_handle* h, const double* Y, int32_t T, con
     if (!h) return GPCA_ERR_BAD_ARG;
     LOCK(h);
     static const std::string f("gpca_assoc_linear");
-    if (!have_genotypes(h)) return fail(h, GPCA_ERR_STATE, f + ": no genotypes resident");
-    if (h->sm.on)
-        return fail(h, GPCA_ERR_STATE, f + ": the handle streams its matrix in panels, which is not implemented");
-    if (multi_rank(h)) return fail(h, GPCA_ERR_STATE, f + ": the handle holds a shard of the rows, which is not implemented");
-    if (!h->have_stats) return fail(h, GPCA_ERR_STATE, f + ": no standardisation: run gpca_snp_stats or gpca_set_standardization first");
-    if (h->n_pca == 0) return fail(h, GPCA_ERR_STATE, f + ": no kept row (the keep mask is empty)");
-    const int64_t K = h->n_pca, N = h->N;
-    if (T < 1 || Pc < 0 || (int64_t)T + Pc > kAscMaxCols)
-        return fail(h, GPCA_ERR_BAD_ARG, f + ": T >= 1, Pc >= 0 and T + Pc <= " + std::to_string(kAscMaxCols) + " are required");
-    if (!Y) return fail(h, GPCA_ERR_BAD_ARG, f + ": Y is required");
-    if (Pc > 0 && !C) return fail(h, GPCA_ERR_BAD_ARG, f + ": C is required when Pc > 0");
-    if (!stats && !xb && !rowinfo) return fail(h, GPCA_ERR_BAD_ARG, f + ": stats, xb and rowinfo are all NULL");
-    if (row0 < 0 || row1 < row0 || row1 > K)
-        return fail(h, GPCA_ERR_BAD_ARG, f + ": rows must satisfy 0 <= row0 <= row1 <= K (K = " + std::to_string(K) + " kept rows)");
-    if (!(max_vif >= 1.0) || !std::isfinite(max_vif)) return fail(h, GPCA_ERR_BAD_ARG, f + ": max_vif must be finite and at least 1");
-    if (N >= ((int64_t)1 << 30)) return fail(h, GPCA_ERR_BAD_ARG, f + ": 2^30 or more samples (the per-row sums are 32-bit)");
+    CHK(asc_check_call(h, f, T >= 1 && Pc >= 0 && (int64_t)T + Pc <= kAscMaxCols, "T >= 1, Pc >= 0 and T + Pc <= " + std::to_string(kAscMaxCols), Y,
+                       C, Pc, !stats && !xb && !rowinfo ? "stats, xb and rowinfo are all NULL" : nullptr, row0, row1, max_vif));
+    const int64_t N = h->N;
     const int L = T + Pc;
     std::vector<float> Bt; std::vector<unsigned> incw; std::vector<double> yy;
     int64_t n_inc = 0;
@@ -146,18 +209,10 @@ extern "C" int gpca_assoc_linear(gpca_handle* h, const double* Y, int32_t T, con
     if (asc_row_blocks(rows) >= ((int64_t)1 << 31)) return fail(h, GPCA_ERR_BAD_ARG, f + ": the band makes 2^31 or more workgroups: ask for fewer rows");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->st));
-    {
-        const double need = 4.0 * (double)asc_b_capacity(N, L) + 4.0 * (double)asc_inc_capacity(N) + 8.0 * (double)asc_xb_capacity(rows, L) +
-                            4.0 * (double)asc_sums_capacity(rows) + (stats ? 8.0 * (double)asc_stats_capacity(rows, T) : 0.0) +
-                            (rowinfo ? 8.0 * (double)asc_info_capacity(rows) : 0.0) + 8.0 * T + (double)(64 << 20);
-        size_t fr = 0, tot = 0;
-        HIPCHK(hipMemGetInfo(&fr, &tot));
-        if (need > (double)fr) {
-            char buf[256];
-            snprintf(buf, sizeof buf, "gpca_assoc_linear: the band needs %.3g GB of device memory, %.3g GB are free: ask for fewer rows", need * 1e-9, (double)fr * 1e-9);
-            return fail(h, GPCA_ERR_OOM, buf);
-        }
-    }
+    CHK(preflight_device_memory(h, f.c_str(),
+                                4.0 * (double)asc_b_capacity(N, L) + 4.0 * (double)asc_inc_capacity(N) + 8.0 * (double)asc_xb_capacity(rows, L) +
+                                    4.0 * (double)asc_sums_capacity(rows) + (stats ? 8.0 * (double)asc_stats_capacity(rows, T) : 0.0) +
+                                    (rowinfo ? 8.0 * (double)asc_info_capacity(rows) : 0.0) + 8.0 * T + (double)(64 << 20)));
     const bool packed = h->storage == GPCA_STORE_2BIT;
     const void* G = packed ? (const void*)h->dG2 : (const void*)h->dG;
     const int64_t ldr = packed ? h->ld2 : h->ld8;
@@ -182,16 +237,9 @@ extern "C" int gpca_assoc_linear(gpca_handle* h, const double* Y, int32_t T, con
         launch_assoc_finish(st, ws.xb, ws.sums, ws.yy, T, L, (double)(n_inc - Pc - 2), max_vif, rows, ws.stats, ws.info);
         HIPCHK(hipGetLastError());
     }
-    unsigned long long bad = 0;
-    HIPCHK(hipMemcpyAsync(&bad, ws.bad, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (bad != ~0ull)
-        return fail(h, GPCA_ERR_INVALID_GENOTYPE, f + ": row " + std::to_string(bad) + " holds a genotype outside {0, 1, 2, missing}");
-    if (stats) HIPCHK(hipMemcpyAsync(stats, ws.stats, (size_t)asc_stats_capacity(rows, T) * 8, hipMemcpyDeviceToHost, st));
-    if (xb) HIPCHK(hipMemcpyAsync(xb, ws.xb, (size_t)asc_xb_capacity(rows, L) * 8, hipMemcpyDeviceToHost, st));
-    if (rowinfo) HIPCHK(hipMemcpyAsync(rowinfo, ws.info, (size_t)asc_info_capacity(rows) * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return GPCA_OK;
+    CHK(asc_check_genotypes(h, f, ws.bad, st));
+    return asc_copy_outputs(h, st, {{stats, ws.stats, asc_stats_capacity(rows, T)}, {xb, ws.xb, asc_xb_capacity(rows, L)},
+                                    {rowinfo, ws.info, asc_info_capacity(rows)}});
 }
 
 namespace {

@@ -6,6 +6,8 @@
 // gpca_assoc_logistic_spa / gpca_spa_log10p (section a14): the same call with the saddle-point correction after the finish kernel
 // (assoc_spa.hip: the items with |z| >= spa_z, flagged and computed in ranges of kAspListItems), and the correction for one given
 // vector on the host; both run the rules of spa_math.h.
+// What is here: the Newton fit, the per-trait panel columns, the saddle-point orchestration and the host-only entry points; the rest
+// of the host front end is the linear scan's (gpca_assoc.cpp, declared in gpca_internal.h).
 #include "gpca_internal.h"
 #include "spa_math.h"
 
@@ -26,76 +28,30 @@ struct AsrWs {
         dfree(Z); dfree(mu); dfree(g); dfree(spa); dfree(list); dfree(count);
     }
 };
-template <typename T>
-hipError_t dalloc(T*& p, size_t elems) { return hipMalloc((void**)&p, std::max<size_t>(elems, 1) * sizeof(T)); }
 
 constexpr int kLogitMaxSteps = 25;
 constexpr double kLogitStop = 1e-10, kLogitMaxEta = 30.0, kLogitPivot = 1e-10;
 
 // The design shared by the traits of a call: S and X = (1, the columns of C centred over S and scaled to unit norm), column-major
-// [Pc + 1][n] (asc_design's standardisation and its constant-column test).
+// [Pc + 1][n] (the front end's standardisation and its constant-column test; incw as asc_sample_set leaves it).
 struct LogitDesign {
     std::vector<int64_t> S;
     std::vector<double> X;
     int P = 0;                      // Pc + 1
 };
-int logit_design(const double* C, int Pc, const uint8_t* include, int64_t N, LogitDesign& D, std::string& msg) {
-    D.S.clear();
-    D.S.reserve((size_t)N);
-    for (int64_t n = 0; n < N; ++n) if (!include || include[n]) D.S.push_back(n);
+int logit_design(const double* C, int Pc, const uint8_t* include, int64_t N, LogitDesign& D, std::vector<unsigned>* incw, std::string& msg) {
+    asc_sample_set(include, N, D.S, incw);
     const int64_t ns = (int64_t)D.S.size();
     D.P = Pc + 1;
     if (ns - Pc - 1 < 1) { msg = std::to_string(ns) + " included samples leave n - Pc - 1 < 1"; return GPCA_ERR_BAD_ARG; }
     D.X.assign((size_t)D.P * (size_t)ns, 1.0);
-    for (int j = 0; j < Pc; ++j) {
-        double* c = &D.X[(size_t)(j + 1) * (size_t)ns];
-        double sum = 0.0, raw = 0.0, ss = 0.0;
-        for (int64_t i = 0; i < ns; ++i) {
-            c[i] = C[D.S[(size_t)i] * Pc + j];
-            if (!std::isfinite(c[i])) { msg = "C[" + std::to_string(D.S[(size_t)i]) + "][" + std::to_string(j) + "] is not finite"; return GPCA_ERR_BAD_ARG; }
-            sum += c[i]; raw += c[i] * c[i];
-        }
-        const double mean = sum / (double)ns;
-        for (int64_t i = 0; i < ns; ++i) { c[i] -= mean; ss += c[i] * c[i]; }
-        if (!std::isfinite(ss) || !(ss > 1e-20 * raw)) {
-            msg = "column " + std::to_string(j) + " of C is constant over the included samples (or overflows)";
-            return GPCA_ERR_BAD_ARG;
-        }
-        const double inv = 1.0 / std::sqrt(ss);
-        for (int64_t i = 0; i < ns; ++i) c[i] *= inv;
-    }
-    return GPCA_OK;
+    return asc_standardise(C, Pc, D.S, D.X.data() + ns, msg);
 }
 
-// A = X^T diag(w) X = L L^T in place (lower triangle, row-major [P][P]); a pivot below kLogitPivot of its diagonal entry = collinear
+// A = X^T diag(w) X = L L^T (lower triangle, row-major [P][P]); a pivot below kLogitPivot of its diagonal entry = collinear
 int logit_cholesky(const LogitDesign& D, const std::vector<double>& w, std::vector<double>& A, std::string& msg) {
-    const int P = D.P;
-    const int64_t ns = (int64_t)D.S.size();
-    A.assign((size_t)P * P, 0.0);
-    for (int i = 0; i < P; ++i)
-        for (int j = 0; j <= i; ++j) {
-            const double *a = &D.X[(size_t)i * (size_t)ns], *b = &D.X[(size_t)j * (size_t)ns];
-            double s = 0.0;
-            for (int64_t n = 0; n < ns; ++n) s += w[(size_t)n] * a[n] * b[n];
-            A[(size_t)i * P + j] = s;
-        }
-    for (int j = 0; j < P; ++j) {
-        const double diag = A[(size_t)j * P + j];
-        double d = diag;
-        for (int k = 0; k < j; ++k) d -= A[(size_t)j * P + k] * A[(size_t)j * P + k];
-        if (!(d > kLogitPivot * diag) || !std::isfinite(d)) {
-            msg = "the covariates (1, C) are collinear over the included samples (Cholesky pivot " + std::to_string(j) + " failed)";
-            return GPCA_ERR_BAD_ARG;
-        }
-        const double l = std::sqrt(d);
-        A[(size_t)j * P + j] = l;
-        for (int i = j + 1; i < P; ++i) {
-            double s = A[(size_t)i * P + j];
-            for (int k = 0; k < j; ++k) s -= A[(size_t)i * P + k] * A[(size_t)j * P + k];
-            A[(size_t)i * P + j] = s / l;
-        }
-    }
-    return GPCA_OK;
+    return asc_cholesky(D.X.data(), D.P, (int64_t)D.S.size(), w.data(), [](double d, double diag) { return d > kLogitPivot * diag && std::isfinite(d); },
+                        A, msg);
 }
 
 // eta = X alpha, mu = 1 / (1 + exp(-eta)) over S; false when some |eta| > kLogitMaxEta (or is not finite)
@@ -195,7 +151,7 @@ extern "C" int gpca_logistic_null(const double* y, const double* C, int32_t Pc, 
     if (!y || N < 1 || Pc < 0 || (Pc > 0 && !C) || (!alpha && !mu)) return GPCA_ERR_BAD_ARG;
     LogitDesign D;
     std::string msg;
-    int rc = logit_design(C, Pc, include, N, D, msg);
+    int rc = logit_design(C, Pc, include, N, D, nullptr, msg);
     if (rc != GPCA_OK) return rc;
     std::vector<double> a, m;
     int it = 0;
@@ -228,36 +184,22 @@ int assoc_logistic(gpca_handle* h, const std::string& f, const double* Y, int32_
                    double max_vif, bool with_spa, double spa_z, int64_t row0, int64_t row1, double* stats, double* spa, double* ua,
                    double* rowinfo) {
     LOCK(h);
-    if (!have_genotypes(h)) return fail(h, GPCA_ERR_STATE, f + ": no genotypes resident");
-    if (h->sm.on)
-        return fail(h, GPCA_ERR_STATE, f + ": the handle streams its matrix in panels, which is not implemented");
-    if (multi_rank(h)) return fail(h, GPCA_ERR_STATE, f + ": the handle holds a shard of the rows, which is not implemented");
-    if (!h->have_stats) return fail(h, GPCA_ERR_STATE, f + ": no standardisation: run gpca_snp_stats or gpca_set_standardization first");
-    if (h->n_pca == 0) return fail(h, GPCA_ERR_STATE, f + ": no kept row (the keep mask is empty)");
-    const int64_t K = h->n_pca, N = h->N;
-    if (T < 1 || Pc < 0 || (int64_t)T * ((int64_t)Pc + 3) > kAsrMaxCols)
-        return fail(h, GPCA_ERR_BAD_ARG, f + ": T >= 1, Pc >= 0 and T (Pc + 3) <= " + std::to_string(kAsrMaxCols) + " are required");
-    if (!Y) return fail(h, GPCA_ERR_BAD_ARG, f + ": Y is required");
-    if (Pc > 0 && !C) return fail(h, GPCA_ERR_BAD_ARG, f + ": C is required when Pc > 0");
-    if (with_spa && !spa) return fail(h, GPCA_ERR_BAD_ARG, f + ": spa is required");
-    if (!with_spa && !stats && !ua && !rowinfo) return fail(h, GPCA_ERR_BAD_ARG, f + ": stats, ua and rowinfo are all NULL");
-    if (row0 < 0 || row1 < row0 || row1 > K)
-        return fail(h, GPCA_ERR_BAD_ARG, f + ": rows must satisfy 0 <= row0 <= row1 <= K (K = " + std::to_string(K) + " kept rows)");
-    if (!(max_vif >= 1.0) || !std::isfinite(max_vif)) return fail(h, GPCA_ERR_BAD_ARG, f + ": max_vif must be finite and at least 1");
-    if (with_spa && !spa_z_ok(spa_z)) return fail(h, GPCA_ERR_BAD_ARG, f + ": spa_z must be at least 0.5, or +inf for no correction");
-    if (N >= ((int64_t)1 << 30)) return fail(h, GPCA_ERR_BAD_ARG, f + ": 2^30 or more samples (the per-row sums are 32-bit)");
+    CHK(asc_check_call(h, f, T >= 1 && Pc >= 0 && (int64_t)T * ((int64_t)Pc + 3) <= kAsrMaxCols,
+                       "T >= 1, Pc >= 0 and T (Pc + 3) <= " + std::to_string(kAsrMaxCols), Y, C, Pc,
+                       with_spa ? (spa ? nullptr : "spa is required") : (!stats && !ua && !rowinfo ? "stats, ua and rowinfo are all NULL" : nullptr),
+                       row0, row1, max_vif, with_spa && !spa_z_ok(spa_z) ? "spa_z must be at least 0.5, or +inf for no correction" : nullptr));
+    const int64_t N = h->N;
     const int L = asr_cols(T, Pc), P = Pc + 1;
     const int64_t npad = asc_npad(N);
 
     // host: the design, then per trait the null fit and its Pc + 3 columns
     LogitDesign D;
     std::string msg;
-    int rc = logit_design(C, Pc, include, N, D, msg);
+    std::vector<unsigned> incw;
+    int rc = logit_design(C, Pc, include, N, D, &incw, msg);
     if (rc != GPCA_OK) return fail(h, rc, f + ": " + msg);
     const int64_t ns = (int64_t)D.S.size();
     std::vector<float> Bt((size_t)asc_b_capacity(N, L), 0.0f);
-    std::vector<unsigned> incw((size_t)asc_inc_capacity(N), 0u);
-    for (int64_t n : D.S) incw[(size_t)(n >> 5)] |= 1u << (int)(n & 31);
     // (the correction's: Z_t = X L_t^-T and mu_t in f64, 0 outside S and past N; with spa_z = +inf no item is corrected: the flag
     // kernel alone runs, and the correction's inputs and workspace are neither built nor allocated)
     const bool correct = with_spa && std::isfinite(spa_z);
@@ -272,19 +214,7 @@ int assoc_logistic(gpca_handle* h, const std::string& f, const double* Y, int32_
             for (int64_t i = 0; i < ns; ++i) w[(size_t)i] = mu[(size_t)i] * (1.0 - mu[(size_t)i]);
             rc = logit_cholesky(D, w, A, msg);
             if (rc != GPCA_OK) return fail(h, rc, f + ": trait " + std::to_string(t) + ": " + msg);
-            // A L^T = W X, column by column: a_j = (w x_j - sum_{k < j} L_jk a_k) / L_jj
-            for (int j = 0; j < P; ++j) {
-                double* a = &col[(size_t)j * (size_t)ns];
-                const double* x = &D.X[(size_t)j * (size_t)ns];
-                for (int64_t i = 0; i < ns; ++i) a[i] = w[(size_t)i] * x[i];
-                for (int k = 0; k < j; ++k) {
-                    const double l = A[(size_t)j * P + k];
-                    const double* ak = &col[(size_t)k * (size_t)ns];
-                    for (int64_t i = 0; i < ns; ++i) a[i] -= l * ak[i];
-                }
-                const double inv = 1.0 / A[(size_t)j * P + j];
-                for (int64_t i = 0; i < ns; ++i) a[i] *= inv;
-            }
+            asc_solve_lt(A, P, ns, D.X.data(), w.data(), col.data());            // A L^T = W X
             for (int64_t i = 0; i < ns; ++i) {
                 const size_t n = (size_t)D.S[(size_t)i];
                 Bt[(size_t)asr_col_w(t) * (size_t)npad + n] = (float)w[(size_t)i];
@@ -292,19 +222,7 @@ int assoc_logistic(gpca_handle* h, const std::string& f, const double* Y, int32_
                 for (int j = 0; j < P; ++j) Bt[(size_t)asr_col_a(T, Pc, t, j) * (size_t)npad + n] = (float)col[(size_t)j * (size_t)ns + (size_t)i];
             }
             if (!correct) continue;
-            // Z L^T = X, column by column: z_j = (x_j - sum_{k < j} L_jk z_k) / L_jj
-            for (int j = 0; j < P; ++j) {
-                double* z = &zc[(size_t)j * (size_t)ns];
-                const double* x = &D.X[(size_t)j * (size_t)ns];
-                for (int64_t i = 0; i < ns; ++i) z[i] = x[i];
-                for (int k = 0; k < j; ++k) {
-                    const double l = A[(size_t)j * P + k];
-                    const double* zk = &zc[(size_t)k * (size_t)ns];
-                    for (int64_t i = 0; i < ns; ++i) z[i] -= l * zk[i];
-                }
-                const double inv = 1.0 / A[(size_t)j * P + j];
-                for (int64_t i = 0; i < ns; ++i) z[i] *= inv;
-            }
+            asc_solve_lt(A, P, ns, D.X.data(), nullptr, zc.data());               // Z L^T = X
             for (int64_t i = 0; i < ns; ++i) {
                 const size_t n = (size_t)D.S[(size_t)i];
                 muh[(size_t)t * (size_t)gpad + n] = mu[(size_t)i];
@@ -318,21 +236,13 @@ int assoc_logistic(gpca_handle* h, const std::string& f, const double* Y, int32_
     if (asr_count_blocks(rows) >= ((int64_t)1 << 31)) return fail(h, GPCA_ERR_BAD_ARG, f + ": the band makes 2^31 or more workgroups: ask for fewer rows");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->st));
-    {
-        const double need = 4.0 * (double)asc_b_capacity(N, L) + 4.0 * (double)asc_inc_capacity(N) + 8.0 * (double)asr_dv_capacity(rows, L) +
-                            4.0 * (double)asr_sums_capacity(rows) + (dstats ? 8.0 * (double)asr_stats_capacity(rows, T) : 0.0) +
-                            (with_spa ? 8.0 * (double)asp_out_capacity(rows, T) + 4.0 * (double)asp_list_capacity(rows, T) : 0.0) +
-                            (correct ? 8.0 * (double)(asp_g_capacity(N) + asp_z_capacity(N, T, Pc) + asp_mu_capacity(N, T)) : 0.0) +
-                            (ua ? 8.0 * (double)asr_ua_capacity(rows, T, Pc) : 0.0) + (rowinfo ? 8.0 * (double)asr_info_capacity(rows) : 0.0) +
-                            (double)(64 << 20);
-        size_t fr = 0, tot = 0;
-        HIPCHK(hipMemGetInfo(&fr, &tot));
-        if (need > (double)fr) {
-            char buf[256];
-            snprintf(buf, sizeof buf, "%s: the band needs %.3g GB of device memory, %.3g GB are free: ask for fewer rows", f.c_str(), need * 1e-9, (double)fr * 1e-9);
-            return fail(h, GPCA_ERR_OOM, buf);
-        }
-    }
+    CHK(preflight_device_memory(h, f.c_str(),
+                                4.0 * (double)asc_b_capacity(N, L) + 4.0 * (double)asc_inc_capacity(N) + 8.0 * (double)asr_dv_capacity(rows, L) +
+                                    4.0 * (double)asr_sums_capacity(rows) + (dstats ? 8.0 * (double)asr_stats_capacity(rows, T) : 0.0) +
+                                    (with_spa ? 8.0 * (double)asp_out_capacity(rows, T) + 4.0 * (double)asp_list_capacity(rows, T) : 0.0) +
+                                    (correct ? 8.0 * (double)(asp_g_capacity(N) + asp_z_capacity(N, T, Pc) + asp_mu_capacity(N, T)) : 0.0) +
+                                    (ua ? 8.0 * (double)asr_ua_capacity(rows, T, Pc) : 0.0) + (rowinfo ? 8.0 * (double)asr_info_capacity(rows) : 0.0) +
+                                    (double)(64 << 20)));
     const bool packed = h->storage == GPCA_STORE_2BIT;
     const void* G = packed ? (const void*)h->dG2 : (const void*)h->dG;
     const int64_t ldr = packed ? h->ld2 : h->ld8;
@@ -385,17 +295,9 @@ int assoc_logistic(gpca_handle* h, const std::string& f, const double* Y, int32_
             HIPCHK(hipGetLastError());
         }
     }
-    unsigned long long bad = 0;
-    HIPCHK(hipMemcpyAsync(&bad, ws.bad, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (bad != ~0ull)
-        return fail(h, GPCA_ERR_INVALID_GENOTYPE, f + ": row " + std::to_string(bad) + " holds a genotype outside {0, 1, 2, missing}");
-    if (stats) HIPCHK(hipMemcpyAsync(stats, ws.stats, (size_t)asr_stats_capacity(rows, T) * 8, hipMemcpyDeviceToHost, st));
-    if (ua) HIPCHK(hipMemcpyAsync(ua, ws.ua, (size_t)asr_ua_capacity(rows, T, Pc) * 8, hipMemcpyDeviceToHost, st));
-    if (rowinfo) HIPCHK(hipMemcpyAsync(rowinfo, ws.info, (size_t)asr_info_capacity(rows) * 8, hipMemcpyDeviceToHost, st));
-    if (with_spa) HIPCHK(hipMemcpyAsync(spa, ws.spa, (size_t)asp_out_capacity(rows, T) * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return GPCA_OK;
+    CHK(asc_check_genotypes(h, f, ws.bad, st));
+    return asc_copy_outputs(h, st, {{stats, ws.stats, asr_stats_capacity(rows, T)}, {ua, ws.ua, asr_ua_capacity(rows, T, Pc)},
+                                    {rowinfo, ws.info, asr_info_capacity(rows)}, {spa, ws.spa, asp_out_capacity(rows, T)}});
 }
 }  // namespace
 

@@ -20,8 +20,6 @@ struct GrmWs {
         dfree(tiles); dfree(cnt); dfree(bad);
     }
 };
-template <typename T>
-hipError_t dalloc(T*& p, size_t elems) { return hipMalloc((void**)&p, std::max<size_t>(elems, 1) * sizeof(T)); }
 // an exchange buffer: device memory, or pinned host memory the device can address when the device has none left (gpca_project's rule)
 struct XBuf {
     double* p = nullptr; bool pinned = false;
@@ -92,17 +90,7 @@ extern "C" int gpca_grm(gpca_handle* h, int32_t scaling, int64_t row0, int64_t r
     const size_t outn = (size_t)E * (npairs ? 2 : 1) + 16;           // band | npairs | status slots: one exchange
     const double need = 12.0 * (double)E + 8.0 * (double)outn + (double)(Mpad / 32) * (kGrmTabBytes + 4) + 17.0 * (double)M +
                         16.0 * (double)ngroups * (double)Npad + 20.0 * (double)Npad + 8.0 * (double)ntiles + (64 << 20);
-    auto preflight = [&]() -> int {
-        size_t fr = 0, tot = 0;
-        HIPCHK(hipMemGetInfo(&fr, &tot));
-        if (need > (double)fr) {
-            char buf[256];
-            snprintf(buf, sizeof buf, "gpca_grm: the band needs %.3g GB of device memory, %.3g GB are free: ask for fewer rows", need * 1e-9, (double)fr * 1e-9);
-            return fail(h, GPCA_ERR_OOM, buf);
-        }
-        return GPCA_OK;
-    };
-    LOCAL(preflight());
+    LOCAL(preflight_device_memory(h, "gpca_grm", need));
 
     // 3. sharded handles: one small exchange of every rank's largest value, kept-row count and status, so that every rank quantises on
     //    the scale one rank would use (the integer sums stay the one-rank ones) and a failure so far reaches every rank

@@ -278,6 +278,20 @@ inline int ensure(gpca_handle* h, T*& p, size_t& cap, size_t need_elems) {
 }
 template <typename T>
 inline void dfree(T*& p) { if (p) { (void)hipFree(p); p = nullptr; } }
+// a buffer of a per-call workspace (freed with dfree by the workspace's destructor); at least one element
+template <typename T>
+inline hipError_t dalloc(T*& p, size_t elems) { return hipMalloc((void**)&p, std::max<size_t>(elems, 1) * sizeof(T)); }
+// the check before a per-call workspace is allocated: need_bytes = everything the call allocates on the device
+inline int preflight_device_memory(gpca_handle* h, const char* name, double need_bytes) {
+    size_t fr = 0, tot = 0;
+    HIPCHK(hipMemGetInfo(&fr, &tot));
+    if (need_bytes > (double)fr) {
+        char buf[256];
+        snprintf(buf, sizeof buf, "%s: the band needs %.3g GB of device memory, %.3g GB are free: ask for fewer rows", name, need_bytes * 1e-9, (double)fr * 1e-9);
+        return fail(h, GPCA_ERR_OOM, buf);
+    }
+    return GPCA_OK;
+}
 
 // Genotype storage (resident matrix, panel ring, panel cache).  Plain hipMalloc on purpose: physically contiguous allocations
 // (hipExtMallocWithFlags + hipDeviceMallocContiguous) stream 0 - 4 % faster in a microbenchmark (profiles/r3_kbench_place_contig.log)
@@ -336,6 +350,28 @@ int agree_status_end(gpca_handle* h, int local_rc, const char* where);       // 
 void status_histogram(double* slots16, int local_rc);
 int status_verdict(gpca_handle* h, const double* v, int local_rc, const std::string& own, const char* where);
 void drop_child(gpca_handle* h);    // the compact child is stale (rows, statistics or keep mask changed) or the handle goes away
+// gpca_assoc.cpp: the host front end of the association scans (gpca_assoc.cpp, gpca_assoc_score.cpp).  A step that fails returns its
+// code and leaves the text in msg for the caller to put the entry point's name (and the trait) in front of.
+// the state and argument checks of an entry point f, in their fixed order: cols_ok / cols_rule = the scan's rule for T and Pc,
+// out_err = what is wrong with the output pointers (NULL: nothing), late_err = a check of the scan's own that comes after max_vif's
+int asc_check_call(gpca_handle* h, const std::string& f, bool cols_ok, const std::string& cols_rule, const double* Y, const double* C, int Pc,
+                   const char* out_err, int64_t row0, int64_t row1, double max_vif, const char* late_err = nullptr);
+// S = the included samples, ascending; incw (may be NULL) = the mask as bits, asc_inc_capacity(N) words
+void asc_sample_set(const uint8_t* include, int64_t N, std::vector<int64_t>& S, std::vector<unsigned>* incw);
+// X [Pc][|S|] column-major = the columns of C [N][Pc] over S, centred and scaled to unit norm; refuses an entry that is not finite (the
+// first in column-major order) and a column that is constant over S
+int asc_standardise(const double* C, int Pc, const std::vector<int64_t>& S, double* X, std::string& msg);
+// A [P][P] row-major, lower = L with X^T diag(w) X = L L^T (w = NULL: X^T X) of X [P][ns] column-major; pivot j is taken iff
+// accept(d_j, A_jj before the elimination)
+int asc_cholesky(const double* X, int P, int64_t ns, const double* w, bool (*accept)(double d, double diag), std::vector<double>& A,
+                 std::string& msg);
+// out [P][ns] = diag(w) X L^-T (w = NULL: X L^-T), column by column: out_j = (w x_j - sum_{k < j} L_jk out_k) / L_jj; out may be X
+void asc_solve_lt(const std::vector<double>& A, int P, int64_t ns, const double* X, const double* w, double* out);
+// reads the kernels' invalid-genotype word back (the stream is synchronised) and refuses the call if a row was flagged
+int asc_check_genotypes(gpca_handle* h, const std::string& f, const unsigned long long* d_bad, hipStream_t st);
+// copies every requested output (host != NULL) from the workspace and waits for the copies
+struct AscOutput { double* host; const double* dev; int64_t elems; };
+int asc_copy_outputs(gpca_handle* h, hipStream_t st, std::initializer_list<AscOutput> outs);
 
 // fn(view) once for the resident matrix, or once per panel (generated / copied ahead on the fill stream)
 template <class F>

@@ -15,8 +15,6 @@ struct KingWs {
     unsigned *het = nullptr, *miss = nullptr, *bad = nullptr;    // (device memory: the per-sample counts take atomics)
     ~KingWs() { dfree(kin); dfree(counts); dfree(kmask); dfree(keep); dfree(tiles); dfree(het); dfree(miss); dfree(bad); }
 };
-template <typename T>
-hipError_t dalloc(T*& p, size_t elems) { return hipMalloc((void**)&p, std::max<size_t>(elems, 1) * sizeof(T)); }
 // the exchange buffer: device memory, or pinned host memory the device can address when the device has none left (gpca_grm's rule)
 struct XBuf {
     double* p = nullptr; bool pinned = false;
@@ -66,17 +64,7 @@ extern "C" int gpca_king(gpca_handle* h, int64_t row0, int64_t row1, double* kin
     const size_t outn = (size_t)E * 5 + 2 * (size_t)Npad + 1 + 16;     // XX HH HM MH MM | het | miss | K | status slots: one exchange
     const double need = 8.0 * (double)outn + (counts ? 20.0 : 8.0) * (double)E + 8.0 * (double)Npad + (double)(Mpad / 32) * 4 + (double)M + 8.0 * (double)ntiles +
                         (64 << 20);
-    auto preflight = [&]() -> int {
-        size_t fr = 0, tot = 0;
-        HIPCHK(hipMemGetInfo(&fr, &tot));
-        if (need > (double)fr) {
-            char buf[256];
-            snprintf(buf, sizeof buf, "gpca_king: the band needs %.3g GB of device memory, %.3g GB are free: ask for fewer rows", need * 1e-9, (double)fr * 1e-9);
-            return fail(h, GPCA_ERR_OOM, buf);
-        }
-        return GPCA_OK;
-    };
-    LOCAL(preflight());
+    LOCAL(preflight_device_memory(h, "gpca_king", need));
 
     KingWs ws;
     XBuf xb;

@@ -17,8 +17,6 @@ struct LdWs {
     unsigned long long* above = nullptr;
     ~LdWs() { dfree(W); dfree(stat); dfree(bad); dfree(win_end); dfree(r2); dfree(counts); dfree(above); }
 };
-template <typename T>
-hipError_t dalloc(T*& p, size_t elems) { return hipMalloc((void**)&p, std::max<size_t>(elems, 1) * sizeof(T)); }
 }  // namespace
 
 extern "C" int gpca_ld_window(gpca_handle* h, int64_t row0, int64_t row1, const int64_t* win_end, int32_t wmax, double threshold, double* r2,
@@ -62,15 +60,7 @@ extern "C" int gpca_ld_window(gpca_handle* h, int64_t row0, int64_t row1, const 
     const double need = 4.0 * kLdProducts * slots + (r2 ? 8.0 * slots : 0.0) + (counts ? 24.0 * slots : 0.0) +
                         (above ? 8.0 * (double)rows * (double)ld_above_words(wmax) : 0.0) + 8.0 * (double)rows + 12.0 * (double)(hi - row0) +
                         (double)(64 << 20);
-    {
-        size_t fr = 0, tot = 0;
-        HIPCHK(hipMemGetInfo(&fr, &tot));
-        if (need > (double)fr) {
-            char buf[256];
-            snprintf(buf, sizeof buf, "gpca_ld_window: the band needs %.3g GB of device memory, %.3g GB are free: ask for fewer rows", need * 1e-9, (double)fr * 1e-9);
-            return fail(h, GPCA_ERR_OOM, buf);
-        }
-    }
+    CHK(preflight_device_memory(h, "gpca_ld_window", need));
     const int64_t nblocks = ld_row_blocks(rows) * ld_col_chunks(weff);
     if (nblocks >= ((int64_t)1 << 31) || rows * ((ld_above_words(wmax) + 3) / 4) >= ((int64_t)1 << 31))
         return fail(h, GPCA_ERR_BAD_ARG, "gpca_ld_window: the band makes 2^31 or more workgroups: ask for fewer rows");

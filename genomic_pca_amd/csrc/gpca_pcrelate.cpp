@@ -20,8 +20,6 @@ struct PcrWs {
         dfree(nsnp); dfree(tiles);
     }
 };
-template <typename T>
-hipError_t dalloc(T*& p, size_t elems) { return hipMalloc((void**)&p, std::max<size_t>(elems, 1) * sizeof(T)); }
 
 // what both entry points check before they touch the device
 int pcr_check(gpca_handle* h, const char* fn, const double* V, int32_t P) {

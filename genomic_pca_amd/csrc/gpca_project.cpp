@@ -24,8 +24,6 @@ struct ProjWs {
         dfree(Ypa); dfree(Ypb); dfree(Yia); dfree(Yib); dfree(cnt); dfree(bad);
     }
 };
-template <typename T>
-hipError_t dalloc(T*& p, size_t elems) { return hipMalloc((void**)&p, std::max<size_t>(elems, 1) * sizeof(T)); }
 // A buffer that crosses the ranks' exchange: device memory, or -- when the device has none left -- pinned host memory the device
 // can address, so that a rank that is out of memory still reaches the exchange and reports its failure there instead of leaving
 // the other ranks waiting in it.

@@ -505,18 +505,9 @@ class GpcaEngine:
         fc.T[il] = cnt
         return full, fc
 
-    def assoc_linear(self, Y, covar=None, include=None, max_vif: float = 50.0, rows: Optional[Tuple[int, int]] = None, xb: bool = False):
-        """Linear association scan (gpca_assoc_linear): ordinary least squares of every trait (column of Y [N][T]) on (1, covar, g)
-        for the kept rows [row0, row1) in PCA-SNP order (default: all); covar [N][Pc] or None, T + Pc <= 64; include: bool / uint8 [N],
-        None = everyone.  A missing call is imputed to the row's mean over the included samples.  Returns a dict: beta, se, t
-        [rows][T]; n_obs, a1_freq, xx, sxx [rows]; with xb=True also xb [rows][T + Pc] (the products the statistics come from).
-        beta, se and t are NaN for a row with no observed call, no variance, a variance inflation above max_vif, or rss <= 0."""
-        N = self.dims()[1]
-        Yv = np.ascontiguousarray(Y, np.float64)
-        if Yv.ndim == 1:
-            Yv = Yv.reshape(-1, 1)
-        if Yv.ndim != 2 or Yv.shape[0] != N:
-            raise ValueError("Y must be [N][T]: one row of traits per sample")
+    @staticmethod
+    def _assoc_design(covar, include, N):
+        """(Cv [N][Pc] f64, inc uint8 [N] or None) of an association call, checked."""
         Cv = np.ascontiguousarray(np.zeros((N, 0)) if covar is None else covar, np.float64)
         if Cv.ndim == 1:
             Cv = Cv.reshape(N, 0) if Cv.size == 0 else Cv.reshape(-1, 1)
@@ -525,10 +516,29 @@ class GpcaEngine:
         inc = None if include is None else np.ascontiguousarray(np.asarray(include) != 0, np.uint8)
         if inc is not None and inc.shape != (N,):
             raise ValueError("include must have one entry per sample")
+        return Cv, inc
+
+    def _assoc_args(self, Y, covar, include, rows):
+        """(Yv, Cv, inc, T, Pc, r0, r1, n) of an association scan: the checked arrays, their widths, the band and its row count."""
+        N = self.dims()[1]
+        Yv = np.ascontiguousarray(Y, np.float64)
+        if Yv.ndim == 1:
+            Yv = Yv.reshape(-1, 1)
+        if Yv.ndim != 2 or Yv.shape[0] != N:
+            raise ValueError("Y must be [N][T]: one row of traits per sample")
+        Cv, inc = self._assoc_design(covar, include, N)
         T, Pc = Yv.shape[1], Cv.shape[1]
         K = int(self._lib.gpca_num_pca_snps(self._h))
         r0, r1 = (0, K) if rows is None else (int(rows[0]), int(rows[1]))
-        n = max(r1 - r0, 0)
+        return Yv, Cv, inc, T, Pc, r0, r1, max(r1 - r0, 0)
+
+    def assoc_linear(self, Y, covar=None, include=None, max_vif: float = 50.0, rows: Optional[Tuple[int, int]] = None, xb: bool = False):
+        """Linear association scan (gpca_assoc_linear): ordinary least squares of every trait (column of Y [N][T]) on (1, covar, g)
+        for the kept rows [row0, row1) in PCA-SNP order (default: all); covar [N][Pc] or None, T + Pc <= 64; include: bool / uint8 [N],
+        None = everyone.  A missing call is imputed to the row's mean over the included samples.  Returns a dict: beta, se, t
+        [rows][T]; n_obs, a1_freq, xx, sxx [rows]; with xb=True also xb [rows][T + Pc] (the products the statistics come from).
+        beta, se and t are NaN for a row with no observed call, no variance, a variance inflation above max_vif, or rss <= 0."""
+        Yv, Cv, inc, T, Pc, r0, r1, n = self._assoc_args(Y, covar, include, rows)
         stats = np.zeros((max(n, 1), max(T, 1), 3), np.float64)
         info = np.zeros((max(n, 1), 4), np.float64)
         out_xb = np.zeros((max(n, 1), max(T + Pc, 1)), np.float64) if xb else None
@@ -565,24 +575,7 @@ class GpcaEngine:
         return self._assoc_logistic(Y, covar, include, max_vif, float(spa_z), rows, ua)
 
     def _assoc_logistic(self, Y, covar, include, max_vif, spa_z, rows, ua):
-        N = self.dims()[1]
-        Yv = np.ascontiguousarray(Y, np.float64)
-        if Yv.ndim == 1:
-            Yv = Yv.reshape(-1, 1)
-        if Yv.ndim != 2 or Yv.shape[0] != N:
-            raise ValueError("Y must be [N][T]: one row of traits per sample")
-        Cv = np.ascontiguousarray(np.zeros((N, 0)) if covar is None else covar, np.float64)
-        if Cv.ndim == 1:
-            Cv = Cv.reshape(N, 0) if Cv.size == 0 else Cv.reshape(-1, 1)
-        if Cv.ndim != 2 or Cv.shape[0] != N:
-            raise ValueError("covar must be [N][Pc]: one row of covariates per sample")
-        inc = None if include is None else np.ascontiguousarray(np.asarray(include) != 0, np.uint8)
-        if inc is not None and inc.shape != (N,):
-            raise ValueError("include must have one entry per sample")
-        T, Pc = Yv.shape[1], Cv.shape[1]
-        K = int(self._lib.gpca_num_pca_snps(self._h))
-        r0, r1 = (0, K) if rows is None else (int(rows[0]), int(rows[1]))
-        n = max(r1 - r0, 0)
+        Yv, Cv, inc, T, Pc, r0, r1, n = self._assoc_args(Y, covar, include, rows)
         stats = np.zeros((max(n, 1), max(T, 1), 5), np.float64)
         info = np.zeros((max(n, 1), 5), np.float64)
         out_ua = np.zeros((max(n, 1), max(T, 1), Pc + 3), np.float64) if ua else None
@@ -608,14 +601,7 @@ class GpcaEngine:
         included samples, Newton steps); raises GpcaError (BAD_ARG: the inputs; NOT_CONVERGED: 25 steps or separation)."""
         yv = np.ascontiguousarray(y, np.float64).reshape(-1)
         N = yv.shape[0]
-        Cv = np.ascontiguousarray(np.zeros((N, 0)) if covar is None else covar, np.float64)
-        if Cv.ndim == 1:
-            Cv = Cv.reshape(N, 0) if Cv.size == 0 else Cv.reshape(-1, 1)
-        if Cv.ndim != 2 or Cv.shape[0] != N:
-            raise ValueError("covar must be [N][Pc]: one row of covariates per sample")
-        inc = None if include is None else np.ascontiguousarray(np.asarray(include) != 0, np.uint8)
-        if inc is not None and inc.shape != (N,):
-            raise ValueError("include must have one entry per sample")
+        Cv, inc = GpcaEngine._assoc_design(covar, include, N)
         Pc = Cv.shape[1]
         alpha, mu, it = np.zeros(Pc + 1), np.zeros(max(N, 1)), C.c_int32(0)
         lib = _lib.load()
