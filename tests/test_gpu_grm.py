@@ -13,6 +13,7 @@ import genomic_pca_amd as gpca
 from genomic_pca_amd import _lib
 from genomic_pca_amd._lib import GpcaError
 from _edges import edge_keeps, edge_shapes
+from test_gpu_grm_exact import check_device, flush_groups, grm_model
 
 pytestmark = pytest.mark.gpu
 
@@ -55,6 +56,20 @@ def ref_grm(G, st, scaling):
     return (Z.T @ Z) / K, o.T @ o
 
 
+_MODELS = {}
+
+
+def model_check(key, G, st, scaling, g, npairs, P, ranks=1):
+    """the exact integer model of test_gpu_grm_exact.py next to the f64 bar: equality where every integer stays below 2^53, the per-element
+    rounding bar elsewhere.  One model is kept at a time (they are large): the resident and the streamed call of a case share it."""
+    hit = _MODELS.get(key)
+    if hit is None or not all(np.array_equal(hit[0][k], st[k], equal_nan=True) for k in ("mu", "sigma", "keep")):
+        _MODELS.clear()
+        hit = _MODELS[key] = ({k: np.array(v) for k, v in st.items()}, grm_model(G, st["mu"], st["sigma"], st["keep"], scaling))
+    il = np.tril_indices(G.shape[1])
+    return check_device(g[il], None if npairs is None else npairs[il], hit[1], P, key, ranks=ranks)
+
+
 def keep_some(e, seed, frac=0.9):
     st = e.snp_stats()
     M = e.dims()[0]
@@ -79,6 +94,7 @@ def test_matches_numpy(store, N, miss):
             assert g.shape == (N, N) and np.array_equal(g, g.T)
             assert np.max(np.abs(g - ref)) <= 1e-8 * np.max(np.diag(ref)), scaling
             assert np.array_equal(npairs, ref_np.astype(np.float32))
+            model_check(("numpy", N, miss, scaling), G, st, scaling, g, npairs, flush_groups(M))
             if miss:
                 assert np.all(npairs[N // 3] == 0) and np.max(np.abs(g[N // 3])) <= 1e-8 * np.max(np.diag(ref))
 
@@ -115,7 +131,8 @@ def test_bands_bit_identical(store):
             assert np.array_equal(sq[np.tril_indices(N)], full)
 
 
-# 4. streamed equals resident: bit for bit with panels of a multiple of the flush group, 1e-12 otherwise
+# 4. streamed equals resident: bit for bit with panels of a multiple of the flush group, 1e-12 otherwise -- and, while every integer of the
+#    call stays below 2^53, bit for bit whatever the panels are (exact integers do not depend on the grouping): model_check asserts it
 @pytest.mark.parametrize("store", ["int8", "2bit"])
 @pytest.mark.parametrize("panel_rows,exact", [(8192, True), (3072, False)])
 def test_streamed_equals_resident(store, panel_rows, exact):
@@ -130,8 +147,11 @@ def test_streamed_equals_resident(store, panel_rows, exact):
         e.snp_stats()
         e.set_standardization(st["mu"], st["sigma"], st["keep"])
         strm = [e.grm(s, npairs=True) for s in ("standardized", "centred")]
-    for (g, n), (gs, ns) in zip(res, strm):
+        pr = e.stream_info()["panel_rows"]
+    for (g, n), (gs, ns), scaling in zip(res, strm, ("standardized", "centred")):
         assert np.array_equal(n, ns)
+        model_check(("streamed", scaling), G, st, scaling, g, n, flush_groups(M))
+        model_check(("streamed", scaling), G, st, scaling, gs, ns, flush_groups(M, pr))
         if exact:
             assert np.array_equal(g, gs)
         else:
@@ -182,6 +202,7 @@ def test_two_ranks_hook(scaling):
     for g, n in _two_ranks(G, st, scaling):
         assert np.max(np.abs(g - g1)) <= 1e-12 * np.max(np.abs(g1))
         assert np.array_equal(n, n1)
+        model_check(("two ranks", scaling), G, st, scaling, g, n, sum(flush_groups(b - a) for a, b in (gpca.shard_rows(M, 2, r) for r in range(2))), ranks=2)
     for poison, code in (("genotype", _lib.GPCA_ERR_INVALID_GENOTYPE), ("sigma", _lib.GPCA_ERR_BAD_ARG)):
         if poison == "sigma" and scaling == "centred":
             continue                                     # (sigma does not enter the centred scaling)
@@ -276,6 +297,20 @@ def test_errors():
         keep = np.ones(M, np.uint8); keep[17] = 0                 # outside the kept rows: fine
         e.set_standardization(np.ones(M, np.float32), np.ones(M, np.float32), keep)
         e.grm("centred")
+    with gpca.GpcaEngine() as e:                                  # a kept row whose mean gpca_grm cannot use: refused, and the row is named
+        e.upload_genotypes_i8(G)
+        st = e.snp_stats()
+        for bad_mu, scalings in ((-0.25, ("standardized",)), (np.inf, ("standardized", "centred"))):
+            mu = st["mu"].copy(); mu[123] = bad_mu
+            sigma = np.where(st["sigma"] > 0, st["sigma"], np.float32(1)).astype(np.float32)
+            for keep123 in (1, 0):
+                keep = np.ones(M, np.uint8); keep[123] = keep123
+                e.set_standardization(mu, sigma, keep)
+                for sc in scalings:
+                    rc = lib.gpca_grm(e._h, 0 if sc == "standardized" else 1, 0, N, out.ctypes.data, None)
+                    assert rc == (_lib.GPCA_ERR_BAD_ARG if keep123 else _lib.GPCA_OK), (bad_mu, sc, keep123)
+                    if keep123:
+                        assert "kept row 123 " in lib.gpca_last_error(e._h).decode(), lib.gpca_last_error(e._h)
     Nw = 600_000                                                  # a band that cannot fit in device memory (1.8e11 entries)
     Gw = genotypes(128, Nw, seed=62)
     with gpca.GpcaEngine(storage=_lib.STORE_INT8) as e:
@@ -317,6 +352,7 @@ def test_tile_edges(store, M, N):
                 assert g.shape == (N, N) and npairs.shape == (N, N) and np.array_equal(g, g.T), (name, scaling)
                 assert np.max(np.abs(g - ref)) <= 1e-8 * np.max(np.diag(ref)), (name, scaling)
                 assert np.array_equal(npairs, ref_np.astype(np.float32)), (name, scaling)
+                model_check(("edges", M, N, name, scaling), G, st, scaling, g, npairs, flush_groups(M))
                 tri = e.grm(scaling, rows=(0, N))
                 assert tri.shape == (N * (N + 1) // 2,) and np.array_equal(tri, g[np.tril_indices(N)]), (name, scaling)
 
