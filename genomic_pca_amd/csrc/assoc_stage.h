@@ -2,14 +2,14 @@
 // the check / mask / count of those samples on their way into a stage's LDS buffer, and the fetch and store of a stage's panel of B^T.
 // (assoc_tile.h holds the stage pipeline that the two mainloop kernels build from them.)
 #pragma once
-#include "gemm_i8_common.h"
+#include "syrk_tile.h"
 
 namespace gpca {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr unsigned kAscMissing = 0x81u;             // the int8 missing code (-127) as a byte
+constexpr unsigned kAscMissing = kMissingByte;
 
 // the 32 samples a thread stages: 8 dwords of call bytes (int8 storage: as stored; 2-bit: decoded, 3 -> the missing code)
 struct AscFetch { unsigned w[8]; };
@@ -27,9 +27,7 @@ __device__ __forceinline__ void asc_fetch(AscFetch& F, const uint8_t* __restrict
 #pragma unroll
         for (int d = 0; d < 8; ++d) {
             const unsigned b = ((d < 4 ? v.x : v.y) >> (8 * (d & 3))) & 0xffu;
-            const unsigned dd = (b & 3u) | ((b & 0xcu) << 6) | ((b & 0x30u) << 12) | ((b & 0xc0u) << 18);
-            const unsigned m = dd & (dd >> 1) & 0x01010101u;
-            F.w[d] = (dd & ~(m * 3u)) | (m * kAscMissing);
+            F.w[d] = unpack4(b);
         }
     } else {
         const uint4 a = *reinterpret_cast<const uint4*>(G + orow * ldr + ns);
@@ -50,8 +48,8 @@ __device__ __forceinline__ void asc_mask_count(const AscFetch& F, unsigned inb, 
                                                unsigned& s2, unsigned& bd) {
 #pragma unroll
     for (int d = 0; d < 8; ++d) {
-        const unsigned vb = (((inb >> (4 * d)) & 0xfu) * 0x00204081u & 0x01010101u) * 0xffu;
-        const unsigned ib = (((inc >> (4 * d)) & 0xfu) * 0x00204081u & 0x01010101u) * 0xffu;
+        const unsigned vb = kept_bytes(inb, d) * 0xffu;
+        const unsigned ib = kept_bytes(inc, d) * 0xffu;
         const unsigned a = F.w[d] & vb;
         // valid bytes: 0, 1, 2 and the missing code
         const unsigned m = (a >> 7) & 0x01010101u, g = a & ~(m * 0xffu);
@@ -78,8 +76,8 @@ __device__ __forceinline__ void asr_put(const AscFetch& F, unsigned inb, unsigne
     unsigned o[8];
 #pragma unroll
     for (int d = 0; d < 8; ++d) {
-        const unsigned vb = (((inb >> (4 * d)) & 0xfu) * 0x00204081u & 0x01010101u) * 0xffu;
-        const unsigned ib = (((inc >> (4 * d)) & 0xfu) * 0x00204081u & 0x01010101u) * 0xffu;
+        const unsigned vb = kept_bytes(inb, d) * 0xffu;
+        const unsigned ib = kept_bytes(inc, d) * 0xffu;
         const unsigned a = F.w[d] & vb & ib;
         const unsigned m = (a >> 7) & 0x01010101u, g = a & ~(m * 0xffu);
         // (a valid byte of g is 0, 1 or 2: 2 - g borrows nothing from its neighbour; an invalid one fails the call in the count kernel)

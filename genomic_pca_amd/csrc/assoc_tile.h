@@ -28,7 +28,7 @@ struct AscSmem {
 
 // the row of the tile that accumulator element e (of any column block) of wave wv holds in lane half h = lane >> 5; its column is
 // 32 j + (lane & 31) in column block j
-__device__ __forceinline__ int asc_acc_row(int wv, int h, int e) { return 32 * wv + (e & 3) + 8 * (e >> 2) + 4 * h; }
+__device__ __forceinline__ int asc_acc_row(int wv, int h, int e) { return acc_row(32 * wv, e, h); }
 
 // sorow: the original row that this thread stages (-1: none, zeros are staged); Bt [32 NB][npad]; rd, re and (WITH_Q) rq [16]: the
 // caller's running sums, zeroed here (rq is not touched without WITH_Q); wv, lane: the thread's wave (wave-uniform) and lane

@@ -168,7 +168,7 @@ __device__ __forceinline__ void gq_group(const void* __restrict__ Gv, int64_t ld
     for (int t = 0; t < R; ++t) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            const int64_t row = row0 + 32 * t + (e & 3) + 8 * (e >> 2) + 4 * h;
+            const int64_t row = acc_row(row0 + 32 * t, e, h);
             const float ri = rv[row], bi = bv[row];
 #pragma unroll
             for (int lt = 0; lt < LT; ++lt) {
@@ -345,7 +345,7 @@ __global__ __launch_bounds__(256, 1) void k_gtt_f32(const uint8_t* __restrict__ 
         for (int lt = 0; lt < LT; ++lt)
 #pragma unroll
             for (int e = 0; e < 16; e += 4) {
-                const int j = 32 * lt + 8 * (e >> 2) + 4 * h;
+                const int j = acc_row(32 * lt, e, h);
                 float4 o;
                 o.x = acc[t][lt][e]; o.y = acc[t][lt][e + 1]; o.z = acc[t][lt][e + 2]; o.w = acc[t][lt][e + 3];
                 *reinterpret_cast<float4*>(yp + n * L + j) = o;

@@ -87,7 +87,7 @@ __global__ __launch_bounds__(256, 1) void k_gq_n(const int8_t* __restrict__ G, i
                     float ct = 0.f;
 #pragma unroll
                     for (int e = 0; e < 16; ++e) {
-                        const int rin = (e & 3) + 8 * (e >> 2) + 4 * h;          // row of element e inside the unit
+                        const int rin = acc_row(0, e, h);          // row of element e inside the unit
                         const float ri = __shfl(rrow, rin), bi = __shfl(brow, rin);
                         const float gq = (float)(combine_digits(acc, e) * qs);
                         const float tv = __fmaf_rn(ri, gq, __fmul_rn(bi, sj));   // roundings pinned: every K1 variant returns the same bits
@@ -287,7 +287,7 @@ __device__ __forceinline__ void gq2_group(const uint8_t* __restrict__ G2, int64_
         float ct = 0.f;     // this tile's share of c = b^T T: one partial per 32-row unit, so c does not depend on the grid partition
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            const int64_t row = row0 + 32 * t + (e & 3) + 8 * (e >> 2) + 4 * h;
+            const int64_t row = acc_row(row0 + 32 * t, e, h);
             const float ri = rv[row], bi = bv[row];
             const float gq = (float)(combine_digits<ND == 3 ? 8 : 7>(acc[t], e) * qs);
             const float tv = __fmaf_rn(ri, gq, __fmul_rn(bi, sj));   // roundings pinned: every K1 variant returns the same bits
@@ -491,7 +491,7 @@ __device__ __forceinline__ void gq_tile_out(const i32x16 (&a)[kDigits], float rr
     float ct = 0.f;
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-        const int rin = (e & 3) + 8 * (e >> 2) + 4 * h;          // row of element e inside the tile
+        const int rin = acc_row(0, e, h);          // row of element e inside the tile
         // r and b of that row: from the wave's LDS staging (k_gq_d: DMA-ed at the start of the round, no compiler-visible load whose
         // wait would drain the DMA queue), or from lane `rin` of registers loaded one row per lane
         const float ri = RB_LDS ? rl[rin] : __shfl(rrow, rin), bi = RB_LDS ? bl[rin] : __shfl(brow, rin);
@@ -993,7 +993,7 @@ __device__ __forceinline__ void gtt_tiles_out(const i32x16 (&acc)[4][kDigits], d
     for (int t = 0; t < 4; ++t) {
 #pragma unroll
         for (int e = 0; e < 16; e += 2) {
-            const int j = (e & 3) + 8 * (e >> 2);
+            const int j = acc_row(0, e, 0);        // (yp holds the lane half's 4 h)
             double2 o;
             o.x = combine_digits<BITS>(acc[t], e); o.y = combine_digits<BITS>(acc[t], e + 1);
             *reinterpret_cast<double2*>(yp + t * 32 + j) = o;

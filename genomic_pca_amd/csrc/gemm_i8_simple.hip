@@ -84,7 +84,7 @@ __device__ __forceinline__ void gq8_group(const int8_t* __restrict__ G, int64_t 
         float ct = 0.f;     // this tile's share of c = b^T T: one partial per 32-row unit, so c does not depend on the grid partition
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            const int64_t row = row0 + 32 * t + (e & 3) + 8 * (e >> 2) + 4 * h;
+            const int64_t row = acc_row(row0 + 32 * t, e, h);
             const float ri = rv[row], bi = bv[row];
             const float gq = (float)(combine_digits(acc[t], e) * qs);
             const float tv = __fmaf_rn(ri, gq, __fmul_rn(bi, sj));   // roundings pinned: every K1 variant returns the same bits
@@ -232,7 +232,7 @@ __global__ __launch_bounds__(256, 1) void k_gtt_i8(const int8_t* __restrict__ G,
         const int64_t n = n0 + 4 * c + t;
 #pragma unroll
         for (int e = 0; e < 16; e += 2) {
-            const int j = (e & 3) + 8 * (e >> 2) + 4 * h;
+            const int j = acc_row(0, e, h);
             double2 o;
             o.x = combine_digits(acc[t], e); o.y = combine_digits(acc[t], e + 1);
             *reinterpret_cast<double2*>(yp + n * 32 + j) = o;
@@ -367,7 +367,7 @@ __global__ __launch_bounds__(256, 1) void k_gtt_2bit(const uint8_t* __restrict__
         const int64_t n = n0 + 4 * c + t;
 #pragma unroll
         for (int e = 0; e < 16; e += 2) {
-            const int j = (e & 3) + 8 * (e >> 2) + 4 * h;
+            const int j = acc_row(0, e, h);
             double2 o;
             o.x = combine_digits<ND == 3 ? 8 : 7>(acc[t], e); o.y = combine_digits<ND == 3 ? 8 : 7>(acc[t], e + 1);
             *reinterpret_cast<double2*>(yp + n * 32 + j) = o;

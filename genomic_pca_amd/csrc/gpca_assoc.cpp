@@ -209,13 +209,12 @@ extern "C" int gpca_assoc_linear(gpca_handle* h, const double* Y, int32_t T, con
     if (asc_row_blocks(rows) >= ((int64_t)1 << 31)) return fail(h, GPCA_ERR_BAD_ARG, f + ": the band makes 2^31 or more workgroups: ask for fewer rows");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->st));
-    CHK(preflight_device_memory(h, f.c_str(),
+    CHK(preflight_device_memory(h, f.c_str(), "the band needs",
                                 4.0 * (double)asc_b_capacity(N, L) + 4.0 * (double)asc_inc_capacity(N) + 8.0 * (double)asc_xb_capacity(rows, L) +
                                     4.0 * (double)asc_sums_capacity(rows) + (stats ? 8.0 * (double)asc_stats_capacity(rows, T) : 0.0) +
                                     (rowinfo ? 8.0 * (double)asc_info_capacity(rows) : 0.0) + 8.0 * T + (double)(64 << 20)));
     const bool packed = h->storage == GPCA_STORE_2BIT;
-    const void* G = packed ? (const void*)h->dG2 : (const void*)h->dG;
-    const int64_t ldr = packed ? h->ld2 : h->ld8;
+    const auto [G, ldr] = panel_rows(h, resident_view(h));
     hipStream_t st = h->st;
     AscWs ws;
     HIPCHK(dalloc(ws.Bt, Bt.size())); HIPCHK(dalloc(ws.incw, incw.size())); HIPCHK(dalloc(ws.yy, (size_t)T)); HIPCHK(dalloc(ws.bad, 1));

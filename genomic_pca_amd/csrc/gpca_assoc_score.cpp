@@ -236,7 +236,7 @@ int assoc_logistic(gpca_handle* h, const std::string& f, const double* Y, int32_
     if (asr_count_blocks(rows) >= ((int64_t)1 << 31)) return fail(h, GPCA_ERR_BAD_ARG, f + ": the band makes 2^31 or more workgroups: ask for fewer rows");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->st));
-    CHK(preflight_device_memory(h, f.c_str(),
+    CHK(preflight_device_memory(h, f.c_str(), "the band needs",
                                 4.0 * (double)asc_b_capacity(N, L) + 4.0 * (double)asc_inc_capacity(N) + 8.0 * (double)asr_dv_capacity(rows, L) +
                                     4.0 * (double)asr_sums_capacity(rows) + (dstats ? 8.0 * (double)asr_stats_capacity(rows, T) : 0.0) +
                                     (with_spa ? 8.0 * (double)asp_out_capacity(rows, T) + 4.0 * (double)asp_list_capacity(rows, T) : 0.0) +
@@ -244,8 +244,7 @@ int assoc_logistic(gpca_handle* h, const std::string& f, const double* Y, int32_
                                     (ua ? 8.0 * (double)asr_ua_capacity(rows, T, Pc) : 0.0) + (rowinfo ? 8.0 * (double)asr_info_capacity(rows) : 0.0) +
                                     (double)(64 << 20)));
     const bool packed = h->storage == GPCA_STORE_2BIT;
-    const void* G = packed ? (const void*)h->dG2 : (const void*)h->dG;
-    const int64_t ldr = packed ? h->ld2 : h->ld8;
+    const auto [G, ldr] = panel_rows(h, resident_view(h));
     hipStream_t st = h->st;
     AsrWs ws;
     HIPCHK(dalloc(ws.Bt, Bt.size())); HIPCHK(dalloc(ws.incw, incw.size())); HIPCHK(dalloc(ws.bad, 1));

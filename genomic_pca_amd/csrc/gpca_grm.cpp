@@ -20,17 +20,6 @@ struct GrmWs {
         dfree(tiles); dfree(cnt); dfree(bad);
     }
 };
-// an exchange buffer: device memory, or pinned host memory the device can address when the device has none left (gpca_project's rule)
-struct XBuf {
-    double* p = nullptr; bool pinned = false;
-    hipError_t alloc(size_t n) {
-        if (hipMalloc((void**)&p, std::max<size_t>(n, 1) * 8) == hipSuccess) return hipSuccess;
-        (void)hipGetLastError();
-        p = nullptr; pinned = true;
-        return hipHostMalloc((void**)&p, std::max<size_t>(n, 1) * 8, hipHostMallocDefault);
-    }
-    ~XBuf() { if (p) { if (pinned) (void)hipHostFree(p); else (void)hipFree(p); } }
-};
 constexpr double kGrmQMax = 4398046511103.0;   // 128^kGrmDigits - 1
 static_assert(kGrmDigits == 6, "kGrmQMax");
 }  // namespace
@@ -50,10 +39,8 @@ extern "C" int gpca_grm(gpca_handle* h, int32_t scaling, int64_t row0, int64_t r
     HIPCHK(hipStreamSynchronize(h->st));
     const bool mr = multi_rank(h);
     const bool packed = h->storage == GPCA_STORE_2BIT;
-    const int64_t E = row1 * (row1 + 1) / 2 - row0 * (row0 + 1) / 2;
-    int lrc = GPCA_OK;
-    // A rank-local failure does not return before the exchanges on a sharded handle: every rank must reach them (gpca_project's rule).
-#define LOCAL(x) do { if (lrc == GPCA_OK) lrc = (x); if (lrc != GPCA_OK && !mr) return lrc; } while (0)
+    const int64_t E = band_entries(row0, row1, true);
+    int lrc = GPCA_OK;                       // (the LOCAL rule: gpca_internal.h)
 
     // 1. the rows' values on the host: w = r^2, c = -r b, e = b^2 (centred: r = 1, b = -mu) of the kept rows, and their largest value
     std::vector<float> mu((size_t)M), r((size_t)M), b((size_t)M);
@@ -63,12 +50,12 @@ extern "C" int gpca_grm(gpca_handle* h, int32_t scaling, int64_t row0, int64_t r
     HIPCHK(hipMemcpy(b.data(), h->d_b, (size_t)M * 4, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(keep.data(), h->d_keep, (size_t)M, hipMemcpyDeviceToHost));
     std::vector<double> vw((size_t)M, 0.0), vc((size_t)M, 0.0), ve((size_t)M, 0.0);
-    int64_t K_local = 0;
+    std::vector<uint32_t> kmask;
+    const int64_t K_local = kept_row_mask(keep, Mpad, kmask);
     double vmax = 0.0;
     auto scan = [&]() -> int {
         for (int64_t i = 0; i < M; ++i) {
             if (!keep[(size_t)i]) continue;
-            ++K_local;
             const double ri = scaling == GPCA_GRM_CENTRED ? 1.0 : (double)r[(size_t)i];
             const double bi = scaling == GPCA_GRM_CENTRED ? -(double)mu[(size_t)i] : (double)b[(size_t)i];
             const double w = ri * ri, c = -ri * bi, e = bi * bi;
@@ -85,12 +72,11 @@ extern "C" int gpca_grm(gpca_handle* h, int32_t scaling, int64_t row0, int64_t r
     // 2. preflight: everything the call allocates on the device, before any allocation
     const int64_t rows_max = h->sm.on ? std::min<int64_t>(h->sm.panel_rows, M) : M;
     const int64_t ngroups = (rows_max + kGrmFlushRows - 1) / kGrmFlushRows;
-    const int64_t t0 = row0 / 64, t1 = (row1 + 63) / 64;
-    const int64_t ntiles = t1 * (t1 + 1) / 2 - t0 * (t0 + 1) / 2;
+    const int64_t ntiles = band_tile_count(row0, row1, kGrmTile);
     const size_t outn = (size_t)E * (npairs ? 2 : 1) + 16;           // band | npairs | status slots: one exchange
     const double need = 12.0 * (double)E + 8.0 * (double)outn + (double)(Mpad / 32) * (kGrmTabBytes + 4) + 17.0 * (double)M +
                         16.0 * (double)ngroups * (double)Npad + 20.0 * (double)Npad + 8.0 * (double)ntiles + (64 << 20);
-    LOCAL(preflight_device_memory(h, "gpca_grm", need));
+    LOCAL(preflight_device_memory(h, "gpca_grm", "the band needs", need));
 
     // 3. sharded handles: one small exchange of every rank's largest value, kept-row count and status, so that every rank quantises on
     //    the scale one rank would use (the integer sums stay the one-rank ones) and a failure so far reaches every rank
@@ -102,19 +88,10 @@ extern "C" int gpca_grm(gpca_handle* h, int32_t scaling, int64_t row0, int64_t r
         auto body = [&]() -> int {
             HIPCHK(xb.alloc(xn));
             if (lrc == GPCA_OK) { hx[(size_t)h->rank] = vmax; hx[(size_t)h->world] = (double)K_local; }
-            h->status_own = h->err;
-            status_histogram(hx.data() + h->world + 1, lrc);
             HIPCHK(hipMemcpyAsync(xb.p, hx.data(), xn * 8, hipMemcpyHostToDevice, h->st));
-            CHK(allreduce_f64(h, xb.p, (int64_t)xn));
-            HIPCHK(hipMemcpyAsync(hx.data(), xb.p, xn * 8, hipMemcpyDeviceToHost, h->st));
-            HIPCHK(hipStreamSynchronize(h->st));
-            return GPCA_OK;
+            return exchange_with_status(h, "gpca_grm", xb.p, xn, lrc, hx.data(), xn);
         };
-        const int xrc = body();
-        if (xrc != GPCA_OK) return xrc;
-        const int own_rc = lrc;
-        lrc = status_verdict(h, hx.data() + h->world + 1, own_rc, h->status_own, "gpca_grm");
-        if (lrc == GPCA_OK) lrc = own_rc;
+        CHK(body());
         if (lrc != GPCA_OK) return lrc;
         vmax = 0.0;
         for (int k = 0; k < h->world; ++k) vmax = std::max(vmax, hx[(size_t)k]);
@@ -132,12 +109,10 @@ extern "C" int gpca_grm(gpca_handle* h, int32_t scaling, int64_t row0, int64_t r
         while (vmax / S > kGrmQMax) S *= 2.0;
     }
     std::vector<int8_t> tab((size_t)(Mpad / 32) * kGrmTabBytes, 0);
-    std::vector<uint32_t> kmask((size_t)(Mpad / 32), 0u);
     std::vector<int64_t> qc((size_t)M, 0), qe((size_t)M, 0);
     unsigned __int128 qe_sum = 0;
     for (int64_t i = 0; i < M; ++i) {
         if (!keep[(size_t)i]) continue;
-        kmask[(size_t)(i >> 5)] |= 1u << (i & 31);
         const int64_t q[4] = {(int64_t)std::llround(vw[(size_t)i] / S), (int64_t)std::llround(2.0 * vw[(size_t)i] / S),
                               (int64_t)std::llround(vc[(size_t)i] / S), (int64_t)std::llround(ve[(size_t)i] / S)};
         int8_t* tb = tab.data() + (size_t)(i >> 5) * kGrmTabBytes + (i & 31);
@@ -153,9 +128,7 @@ extern "C" int gpca_grm(gpca_handle* h, int32_t scaling, int64_t row0, int64_t r
     double* const out = xout.p;
     HIPCHK(hipMemsetAsync(out, 0, outn * 8, h->st));
     std::vector<int2> tiles;
-    tiles.reserve((size_t)ntiles);
-    for (int64_t ta = t0; ta < t1; ++ta)
-        for (int64_t tb = 0; tb <= ta; ++tb) tiles.push_back(make_int2((int)ta, (int)tb));
+    band_tile_list(row0, row1, kGrmTile, tiles);
     auto prep = [&]() -> int {
         HIPCHK(dalloc(ws.R, E)); HIPCHK(dalloc(ws.Q, E));
         HIPCHK(dalloc(ws.tab, tab.size())); HIPCHK(dalloc(ws.kmask, kmask.size()));
@@ -182,8 +155,7 @@ extern "C" int gpca_grm(gpca_handle* h, int32_t scaling, int64_t row0, int64_t r
         const double elems = (double)M * (double)N;
         ScopedTimer t(h, "grm", 2.0 * kGrmDigits * (double)M * 4096.0 * (double)ntiles, (packed ? elems / 4 : elems));
         CHK(for_each_panel(h, [&](const PanelView& pv) -> int {
-            const void* G = packed ? (const void*)pv.g2 : (const void*)pv.g8;
-            const int64_t ldr = packed ? h->ld2 : h->ld8;
+            const auto [G, ldr] = panel_rows(h, pv);
             const size_t blk0 = (size_t)(pv.row0 >> 5);
             launch_grm_vec(h->st, G, packed, ldr, pv.rows, Npad, ws.keep + pv.row0, ws.qc + pv.row0, ws.qe + pv.row0, ws.Up, ws.Vp, ws.cnt, ws.bad);
             launch_grm_vec_fold(h->st, ws.Up, ws.Vp, pv.rows, Npad, ws.u, ws.v);
@@ -197,31 +169,14 @@ extern "C" int gpca_grm(gpca_handle* h, int32_t scaling, int64_t row0, int64_t r
         return GPCA_OK;
     };
     LOCAL(sweep());
-    auto check = [&]() -> int {
-        unsigned bad = 0;
-        HIPCHK(hipMemcpyAsync(&bad, ws.bad, 4, hipMemcpyDeviceToHost, h->st));
-        HIPCHK(hipStreamSynchronize(h->st));
-        if (bad) return fail(h, GPCA_ERR_INVALID_GENOTYPE, "gpca_grm: a kept row holds a genotype outside {0, 1, 2, missing}");
-        return GPCA_OK;
-    };
-    LOCAL(check());
+    LOCAL(check_genotype_flag(h, "gpca_grm", "kept", ws.bad));
 
     // 6. sharded handles: one exchange of band, counts and status word (the numerators and NPAIRS are sums over the ranks' rows)
     if (mr) {
-        h->status_own = h->err;
-        status_histogram(h->h_status, lrc);
-        if (hipMemcpyAsync(out + outn - 16, h->h_status, 16 * sizeof(double), hipMemcpyHostToDevice, h->st) != hipSuccess && lrc == GPCA_OK)
-            lrc = fail(h, GPCA_ERR_HIP, "gpca_grm: status copy failed");
-        { const int xrc = allreduce_f64(h, out, (int64_t)outn); if (xrc != GPCA_OK) return xrc; }
         double slots[16];
-        HIPCHK(hipMemcpyAsync(slots, out + outn - 16, 16 * sizeof(double), hipMemcpyDeviceToHost, h->st));
-        HIPCHK(hipStreamSynchronize(h->st));
-        const int own_rc = lrc;
-        lrc = status_verdict(h, slots, own_rc, h->status_own, "gpca_grm");
-        if (lrc == GPCA_OK) lrc = own_rc;
+        CHK(exchange_with_status(h, "gpca_grm", out, outn, lrc, slots));
     }
     if (lrc != GPCA_OK) return lrc;
-#undef LOCAL
     HIPCHK(hipMemcpyAsync(grm, out, (size_t)E * 8, hipMemcpyDeviceToHost, h->st));
     std::vector<double> np(npairs ? (size_t)E : 0);
     if (npairs) HIPCHK(hipMemcpyAsync(np.data(), out + E, (size_t)E * 8, hipMemcpyDeviceToHost, h->st));

@@ -281,13 +281,14 @@ inline void dfree(T*& p) { if (p) { (void)hipFree(p); p = nullptr; } }
 // a buffer of a per-call workspace (freed with dfree by the workspace's destructor); at least one element
 template <typename T>
 inline hipError_t dalloc(T*& p, size_t elems) { return hipMalloc((void**)&p, std::max<size_t>(elems, 1) * sizeof(T)); }
-// the check before a per-call workspace is allocated: need_bytes = everything the call allocates on the device
-inline int preflight_device_memory(gpca_handle* h, const char* name, double need_bytes) {
+// the check before a per-call workspace is allocated: need_bytes = everything the call allocates on the device; what = the subject of
+// the refusal with its verb ("the band needs", "the band and the regression need")
+inline int preflight_device_memory(gpca_handle* h, const char* name, const char* what, double need_bytes) {
     size_t fr = 0, tot = 0;
     HIPCHK(hipMemGetInfo(&fr, &tot));
     if (need_bytes > (double)fr) {
         char buf[256];
-        snprintf(buf, sizeof buf, "%s: the band needs %.3g GB of device memory, %.3g GB are free: ask for fewer rows", name, need_bytes * 1e-9, (double)fr * 1e-9);
+        snprintf(buf, sizeof buf, "%s: %s %.3g GB of device memory, %.3g GB are free: ask for fewer rows", name, what, need_bytes * 1e-9, (double)fr * 1e-9);
         return fail(h, GPCA_ERR_OOM, buf);
     }
     return GPCA_OK;
@@ -350,6 +351,41 @@ int agree_status_end(gpca_handle* h, int local_rc, const char* where);       // 
 void status_histogram(double* slots16, int local_rc);
 int status_verdict(gpca_handle* h, const double* v, int local_rc, const std::string& own, const char* where);
 void drop_child(gpca_handle* h);    // the compact child is stale (rows, statistics or keep mask changed) or the handle goes away
+// gpca_band.cpp: the host front end of the calls that sweep the matrix for a band of a sample-by-sample product (gpca_grm.cpp,
+// gpca_king.cpp, gpca_pcrelate.cpp) and of their neighbours gpca_project.cpp and gpca_ld.cpp.
+// A buffer that crosses the ranks' exchange: device memory, or -- when the device has none left -- pinned host memory the device
+// can address, so that a rank that is out of memory still reaches the exchange and reports its failure there instead of leaving
+// the other ranks waiting in it.
+struct XBuf {
+    double* p = nullptr; bool pinned = false;
+    hipError_t alloc(size_t n) {
+        if (hipMalloc((void**)&p, std::max<size_t>(n, 1) * 8) == hipSuccess) return hipSuccess;
+        (void)hipGetLastError();
+        p = nullptr; pinned = true;
+        return hipHostMalloc((void**)&p, std::max<size_t>(n, 1) * 8, hipHostMallocDefault);
+    }
+    ~XBuf() { if (p) { if (pinned) (void)hipHostFree(p); else (void)hipFree(p); } }
+};
+// The LOCAL rule of an entry point that exchanges between ranks (it keeps `int lrc` and `const bool mr = multi_rank(h)`): a rank-local
+// failure does not return before the exchange on a sharded handle, because every rank must reach it; the steps after the first failure
+// are skipped and the failure travels in the exchange's status word.
+#define LOCAL(x) do { if (lrc == GPCA_OK) lrc = (x); if (lrc != GPCA_OK && !mr) return lrc; } while (0)
+// One exchange with the status word behind the block (sharded handles): this rank's status goes into the last 16 of the n doubles at buf
+// (device memory or an XBuf), buf is summed over the ranks, its last ntail >= 16 doubles come back to tail and lrc becomes what the ranks
+// agreed on (fn names the entry point in the texts).  A return other than GPCA_OK is a failure of the transport or of the copy back: there is
+// no later exchange to meet at, the caller returns it at once.
+int exchange_with_status(gpca_handle* h, const char* fn, double* buf, size_t n, int& lrc, double* tail, size_t ntail = 16);
+// the kept rows as the kernels take them: bit i & 31 of word i >> 5 per kept row i (Mpad / 32 words); returns their count
+inline void set_row_bit(std::vector<uint32_t>& mask, int64_t i) { mask[(size_t)(i >> 5)] |= 1u << (i & 31); }
+int64_t kept_row_mask(const std::vector<uint8_t>& keep, int64_t Mpad, std::vector<uint32_t>& mask);
+// reads the kernels' invalid-genotype flag back (the stream is synchronised) and refuses the call if it is set; whose = "kept" or "model"
+int check_genotype_flag(gpca_handle* h, const char* fn, const char* whose, const unsigned* d_bad);
+// where the rows of a view start in the handle's storage, and their pitch in bytes
+struct PanelRows { const void* G; int64_t ldr; };
+inline PanelRows panel_rows(const gpca_handle* h, const PanelView& pv) {
+    return h->storage == GPCA_STORE_2BIT ? PanelRows{pv.g2, h->ld2} : PanelRows{pv.g8, h->ld8};
+}
+inline PanelView resident_view(const gpca_handle* h) { return PanelView{h->dG, h->dG2, 0, h->M, h->Mpad, 0}; }
 // gpca_assoc.cpp: the host front end of the association scans (gpca_assoc.cpp, gpca_assoc_score.cpp).  A step that fails returns its
 // code and leaves the text in msg for the caller to put the entry point's name (and the trait) in front of.
 // the state and argument checks of an entry point f, in their fixed order: cols_ok / cols_rule = the scan's rule for T and Pc,
@@ -416,7 +452,7 @@ inline int for_each_panel_walk(gpca_handle* h, F&& fn) {
 }
 template <class F>
 inline int for_each_panel(gpca_handle* h, F&& fn) {
-    if (!h->sm.on) { const PanelView pv{h->dG, h->dG2, 0, h->M, h->Mpad, 0}; return fn(pv); }
+    if (!h->sm.on) return fn(resident_view(h));
     StreamState& sm = h->sm;
     // the worker of a host source learns the whole sweep up front (every panel that will be asked of the source, in order) and
     // stages ahead of the walk below

@@ -15,18 +15,6 @@ struct KingWs {
     unsigned *het = nullptr, *miss = nullptr, *bad = nullptr;    // (device memory: the per-sample counts take atomics)
     ~KingWs() { dfree(kin); dfree(counts); dfree(kmask); dfree(keep); dfree(tiles); dfree(het); dfree(miss); dfree(bad); }
 };
-// the exchange buffer: device memory, or pinned host memory the device can address when the device has none left (gpca_grm's rule)
-struct XBuf {
-    double* p = nullptr; bool pinned = false;
-    hipError_t alloc(size_t n) {
-        if (hipMalloc((void**)&p, std::max<size_t>(n, 1) * 8) == hipSuccess) return hipSuccess;
-        (void)hipGetLastError();
-        p = nullptr; pinned = true;
-        return hipHostMalloc((void**)&p, std::max<size_t>(n, 1) * 8, hipHostMallocDefault);
-    }
-    ~XBuf() { if (p) { if (pinned) (void)hipHostFree(p); else (void)hipFree(p); } }
-};
-constexpr int kKingTileSamples = 128;   // (king.hip: kKingTile)
 }  // namespace
 
 extern "C" int gpca_king(gpca_handle* h, int64_t row0, int64_t row1, double* kinship, int32_t* counts) {
@@ -42,29 +30,24 @@ extern "C" int gpca_king(gpca_handle* h, int64_t row0, int64_t row1, double* kin
     HIPCHK(hipStreamSynchronize(h->st));
     const bool mr = multi_rank(h);
     const bool packed = h->storage == GPCA_STORE_2BIT;
-    const int64_t E = row1 * (row1 - 1) / 2 - row0 * (row0 - 1) / 2;      // strictly lower: row j holds j entries
-    int lrc = GPCA_OK;
-    // A rank-local failure does not return before the exchange on a sharded handle: every rank must reach it (gpca_grm's rule).
-#define LOCAL(x) do { if (lrc == GPCA_OK) lrc = (x); if (lrc != GPCA_OK && !mr) return lrc; } while (0)
+    const int64_t E = band_entries(row0, row1, false);                    // strictly lower: row j holds j entries
+    int lrc = GPCA_OK;                       // (the LOCAL rule: gpca_internal.h)
 
     // 1. the kept rows: their bit mask per 32-row block and their count
     std::vector<uint8_t> keep((size_t)M);
     HIPCHK(hipMemcpy(keep.data(), h->d_keep, (size_t)M, hipMemcpyDeviceToHost));
-    std::vector<uint32_t> kmask((size_t)(Mpad / 32), 0u);
-    int64_t K_local = 0;
-    for (int64_t i = 0; i < M; ++i)
-        if (keep[(size_t)i]) { kmask[(size_t)(i >> 5)] |= 1u << (i & 31); ++K_local; }
+    std::vector<uint32_t> kmask;
+    const int64_t K_local = kept_row_mask(keep, Mpad, kmask);
     constexpr int64_t kMaxK = (int64_t)1 << 31;
     if (!mr && K_local == 0) return fail(h, GPCA_ERR_STATE, "gpca_king: no kept row (the keep mask is empty)");
     if (K_local >= kMaxK) LOCAL(fail(h, GPCA_ERR_BAD_ARG, "gpca_king: 2^31 or more kept rows (the counts are 32-bit)"));
 
     // 2. preflight: everything the call allocates on the device, before any allocation
-    const int64_t t0 = row0 / kKingTileSamples, t1 = (row1 + kKingTileSamples - 1) / kKingTileSamples;
-    const int64_t ntiles = t1 * (t1 + 1) / 2 - t0 * (t0 + 1) / 2;
+    const int64_t ntiles = band_tile_count(row0, row1, kKingTile);
     const size_t outn = (size_t)E * 5 + 2 * (size_t)Npad + 1 + 16;     // XX HH HM MH MM | het | miss | K | status slots: one exchange
     const double need = 8.0 * (double)outn + (counts ? 20.0 : 8.0) * (double)E + 8.0 * (double)Npad + (double)(Mpad / 32) * 4 + (double)M + 8.0 * (double)ntiles +
                         (64 << 20);
-    LOCAL(preflight_device_memory(h, "gpca_king", need));
+    LOCAL(preflight_device_memory(h, "gpca_king", "the band needs", need));
 
     KingWs ws;
     XBuf xb;
@@ -75,9 +58,7 @@ extern "C" int gpca_king(gpca_handle* h, int64_t row0, int64_t row1, double* kin
     double* const miss = het + Npad;
     std::vector<int2> tiles;
     auto prep = [&]() -> int {
-        tiles.reserve((size_t)ntiles);
-        for (int64_t ta = t0; ta < t1; ++ta)
-            for (int64_t tb = 0; tb <= ta; ++tb) tiles.push_back(make_int2((int)ta, (int)tb));
+        band_tile_list(row0, row1, kKingTile, tiles);
         HIPCHK(dalloc(ws.kmask, kmask.size())); HIPCHK(dalloc(ws.keep, M)); HIPCHK(dalloc(ws.tiles, tiles.size())); HIPCHK(dalloc(ws.bad, 1));
         HIPCHK(dalloc(ws.het, Npad)); HIPCHK(dalloc(ws.miss, Npad));
         HIPCHK(dalloc(ws.kin, E));
@@ -98,8 +79,7 @@ extern "C" int gpca_king(gpca_handle* h, int64_t row0, int64_t row1, double* kin
         const double elems = (double)M * (double)N;
         ScopedTimer t(h, "king", 2.0 * 2.0 * 32768.0 * (double)(Mpad / 32) * 16.0 * (double)ntiles, (packed ? elems / 4 : elems));
         CHK(for_each_panel(h, [&](const PanelView& pv) -> int {
-            const void* G = packed ? (const void*)pv.g2 : (const void*)pv.g8;
-            const int64_t ldr = packed ? h->ld2 : h->ld8;
+            const auto [G, ldr] = panel_rows(h, pv);
             launch_king_vec(h->st, G, packed, ldr, pv.rows, Npad, ws.keep + pv.row0, ws.het, ws.miss, ws.bad);
             launch_king(h->st, G, packed, ldr, pv.rows_pad, ws.kmask + (pv.row0 >> 5), ws.tiles, ntiles, row0, row1, N, R, E,
                         pv.index == 0 ? 1 : 0);
@@ -111,14 +91,7 @@ extern "C" int gpca_king(gpca_handle* h, int64_t row0, int64_t row1, double* kin
         return GPCA_OK;
     };
     LOCAL(sweep());
-    auto check = [&]() -> int {
-        unsigned bad = 0;
-        HIPCHK(hipMemcpyAsync(&bad, ws.bad, 4, hipMemcpyDeviceToHost, h->st));
-        HIPCHK(hipStreamSynchronize(h->st));
-        if (bad) return fail(h, GPCA_ERR_INVALID_GENOTYPE, "gpca_king: a kept row holds a genotype outside {0, 1, 2, missing}");
-        return GPCA_OK;
-    };
-    LOCAL(check());
+    LOCAL(check_genotype_flag(h, "gpca_king", "kept", ws.bad));
 
     // 4. sharded handles: one exchange of the integer counts (exact in f64 below 2^53), the kept-row count and the status word; the
     //    kinship is computed after the sum, so every rank gets the one-rank bits
@@ -126,26 +99,17 @@ extern "C" int gpca_king(gpca_handle* h, int64_t row0, int64_t row1, double* kin
     if (mr) {
         double* slot = xb.p + outn - 17;
         const double kl = lrc == GPCA_OK ? (double)K_local : 0.0;
-        h->status_own = h->err;
-        status_histogram(h->h_status, lrc);
-        if ((hipMemcpyAsync(slot, &kl, 8, hipMemcpyHostToDevice, h->st) != hipSuccess ||
-             hipMemcpyAsync(slot + 1, h->h_status, 16 * sizeof(double), hipMemcpyHostToDevice, h->st) != hipSuccess ||
-             hipStreamSynchronize(h->st) != hipSuccess) && lrc == GPCA_OK)
+        // (kl is a stack variable: the stream is synchronised before it goes out of use; gpca_grm's exchanges carry no such value)
+        if ((hipMemcpyAsync(slot, &kl, 8, hipMemcpyHostToDevice, h->st) != hipSuccess || hipStreamSynchronize(h->st) != hipSuccess) && lrc == GPCA_OK)
             lrc = fail(h, GPCA_ERR_HIP, "gpca_king: status copy failed");
-        { const int xrc = allreduce_f64(h, xb.p, (int64_t)outn); if (xrc != GPCA_OK) return xrc; }
         double slots[17];
-        HIPCHK(hipMemcpyAsync(slots, slot, 17 * sizeof(double), hipMemcpyDeviceToHost, h->st));
-        HIPCHK(hipStreamSynchronize(h->st));
-        const int own_rc = lrc;
-        lrc = status_verdict(h, slots + 1, own_rc, h->status_own, "gpca_king");
-        if (lrc == GPCA_OK) lrc = own_rc;
+        CHK(exchange_with_status(h, "gpca_king", xb.p, outn, lrc, slots, 17));
         if (lrc != GPCA_OK) return lrc;
         K_total = slots[0];
         if (K_total < 0.5) return fail(h, GPCA_ERR_STATE, "gpca_king: no kept row on any rank (the keep masks are empty)");
         if (K_total >= (double)kMaxK) return fail(h, GPCA_ERR_BAD_ARG, "gpca_king: 2^31 or more kept rows over the ranks (the counts are 32-bit)");
     }
     if (lrc != GPCA_OK) return lrc;
-#undef LOCAL
 
     // 5. the kinship of the band from the summed counts
     launch_king_finish(h->st, R, E, het, miss, K_total, row0, row1, ws.kin, ws.counts);

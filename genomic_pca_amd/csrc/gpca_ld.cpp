@@ -52,15 +52,14 @@ extern "C" int gpca_ld_window(gpca_handle* h, int64_t row0, int64_t row1, const 
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->st));
     const bool packed = h->storage == GPCA_STORE_2BIT;
-    const void* G = packed ? (const void*)h->dG2 : (const void*)h->dG;
-    const int64_t ldr = packed ? h->ld2 : h->ld8;
+    const auto [G, ldr] = panel_rows(h, resident_view(h));
 
     // preflight: everything the call allocates on the device, before any allocation
     const double slots = (double)rows * (double)wmax;
     const double need = 4.0 * kLdProducts * slots + (r2 ? 8.0 * slots : 0.0) + (counts ? 24.0 * slots : 0.0) +
                         (above ? 8.0 * (double)rows * (double)ld_above_words(wmax) : 0.0) + 8.0 * (double)rows + 12.0 * (double)(hi - row0) +
                         (double)(64 << 20);
-    CHK(preflight_device_memory(h, "gpca_ld_window", need));
+    CHK(preflight_device_memory(h, "gpca_ld_window", "the band needs", need));
     const int64_t nblocks = ld_row_blocks(rows) * ld_col_chunks(weff);
     if (nblocks >= ((int64_t)1 << 31) || rows * ((ld_above_words(wmax) + 3) / 4) >= ((int64_t)1 << 31))
         return fail(h, GPCA_ERR_BAD_ARG, "gpca_ld_window: the band makes 2^31 or more workgroups: ask for fewer rows");
@@ -85,11 +84,7 @@ extern "C" int gpca_ld_window(gpca_handle* h, int64_t row0, int64_t row1, const 
         launch_ld(st, G, packed, ldr, h->d_pca_rows, K, N, row0, row1, ws.win_end, wmax, (int)weff, ws.W);
         HIPCHK(hipGetLastError());
     }
-    unsigned long long bad = 0;
-    HIPCHK(hipMemcpyAsync(&bad, ws.bad, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (bad != ~0ull)
-        return fail(h, GPCA_ERR_INVALID_GENOTYPE, "gpca_ld_window: row " + std::to_string(bad) + " holds a genotype outside {0, 1, 2, missing}");
+    CHK(asc_check_genotypes(h, "gpca_ld_window", ws.bad, st));
     launch_ld_finish(st, ws.W, ws.stat, N, row0, row1, ws.win_end, wmax, threshold, ws.r2, ws.counts, ws.above);
     HIPCHK(hipGetLastError());
     if (r2) HIPCHK(hipMemcpyAsync(r2, ws.r2, nslots * 8, hipMemcpyDeviceToHost, st));

@@ -110,16 +110,6 @@ int pcr_design(gpca_handle* h, const char* fn, const double* V, int P, const uin
     return GPCA_OK;
 }
 
-int pcr_preflight(gpca_handle* h, const char* fn, double need) {
-    size_t fr = 0, tot = 0;
-    HIPCHK(hipMemGetInfo(&fr, &tot));
-    if (need > (double)fr) {
-        char buf[256];
-        snprintf(buf, sizeof buf, "%s: the band and the regression need %.3g GB of device memory, %.3g GB are free: ask for fewer rows", fn, need * 1e-9, (double)fr * 1e-9);
-        return fail(h, GPCA_ERR_OOM, buf);
-    }
-    return GPCA_OK;
-}
 double pcr_common_bytes(int64_t K, int64_t N, int P, bool rm) {
     return 4.0 * (double)pcr_beta_capacity(K, P) * (rm ? 2.0 : 1.0) + 4.0 * (double)pcr_x_capacity(N, P) + 8.0 * (double)pcr_hat_capacity(N, P) + (double)N;
 }
@@ -129,8 +119,7 @@ int pcr_regress(gpca_handle* h, const char* fn, PcrWs& ws, int P, bool rm, const
                 const std::vector<uint8_t>& tr) {
     const int64_t K = h->n_pca, N = h->N;
     const bool packed = h->storage == GPCA_STORE_2BIT;
-    const void* G = packed ? (const void*)h->dG2 : (const void*)h->dG;
-    const int64_t ldr = packed ? h->ld2 : h->ld8;
+    const auto [G, ldr] = panel_rows(h, resident_view(h));
     hipStream_t st = h->st;
     HIPCHK(dalloc(ws.betaG, (size_t)pcr_beta_capacity(K, P)));
     if (rm) HIPCHK(dalloc(ws.beta_rm, (size_t)pcr_beta_capacity(K, P)));
@@ -144,12 +133,7 @@ int pcr_regress(gpca_handle* h, const char* fn, PcrWs& ws, int P, bool rm, const
         launch_pcrelate_beta(st, G, packed, ldr, h->d_pca_rows, K, N, ws.train, ws.Hw, P, ws.betaG, ws.beta_rm, ws.bad);
         HIPCHK(hipGetLastError());
     }
-    unsigned long long bad = 0;
-    HIPCHK(hipMemcpyAsync(&bad, ws.bad, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (bad != ~0ull)
-        return fail(h, GPCA_ERR_INVALID_GENOTYPE, std::string(fn) + ": row " + std::to_string(bad) + " holds a genotype outside {0, 1, 2, missing}");
-    return GPCA_OK;
+    return asc_check_genotypes(h, fn, ws.bad, st);
 }
 }  // namespace
 
@@ -169,7 +153,7 @@ extern "C" int gpca_pcrelate_isaf(gpca_handle* h, const double* V, int32_t P, co
     if (rows == 0) return GPCA_OK;
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->st));
-    CHK(pcr_preflight(h, fn, pcr_common_bytes(K, N, P, beta != nullptr) + (mu ? 4.0 * (double)rows * (double)N : 0.0) + (double)(64 << 20)));
+    CHK(preflight_device_memory(h, fn, "the band and the regression need", pcr_common_bytes(K, N, P, beta != nullptr) + (mu ? 4.0 * (double)rows * (double)N : 0.0) + (double)(64 << 20)));
     PcrWs ws;
     CHK(pcr_regress(h, fn, ws, P, beta != nullptr, Xf, Hw, tr));
     hipStream_t st = h->st;
@@ -200,19 +184,16 @@ extern "C" int gpca_pcrelate(gpca_handle* h, const double* V, int32_t P, const u
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->st));
     const bool packed = h->storage == GPCA_STORE_2BIT;
-    const void* G = packed ? (const void*)h->dG2 : (const void*)h->dG;
-    const int64_t ldr = packed ? h->ld2 : h->ld8;
-    const int64_t E = pcr_band_entries(row0, row1), ntiles = pcr_tiles(row0, row1);
+    const auto [G, ldr] = panel_rows(h, resident_view(h));
+    const int64_t E = band_entries(row0, row1, true), ntiles = band_tile_count(row0, row1, kPcrTile);
     if (ntiles >= ((int64_t)1 << 31)) return fail(h, GPCA_ERR_BAD_ARG, "gpca_pcrelate: the band makes 2^31 or more workgroups: ask for fewer rows");
-    CHK(pcr_preflight(h, fn, pcr_common_bytes(K, N, P, false) + (28.0 + (nsnp ? 4.0 : 0.0)) * (double)E + 4.0 * (double)pcr_inv_capacity(N) +
+    CHK(preflight_device_memory(h, fn, "the band and the regression need", pcr_common_bytes(K, N, P, false) + (28.0 + (nsnp ? 4.0 : 0.0)) * (double)E + 4.0 * (double)pcr_inv_capacity(N) +
                                  8.0 * (double)ntiles + (double)(64 << 20)));
     PcrWs ws;
     CHK(pcr_regress(h, fn, ws, P, false, Xf, Hw, tr));
     hipStream_t st = h->st;
     std::vector<int2> tiles;
-    tiles.reserve((size_t)ntiles);
-    for (int64_t ta = row0 / kPcrTile; ta < (row1 + kPcrTile - 1) / kPcrTile; ++ta)
-        for (int64_t tb = 0; tb <= ta; ++tb) tiles.push_back(make_int2((int)ta, (int)tb));
+    band_tile_list(row0, row1, kPcrTile, tiles);
     HIPCHK(dalloc(ws.tiles, tiles.size())); HIPCHK(dalloc(ws.inv, (size_t)pcr_inv_capacity(N)));
     HIPCHK(dalloc(ws.R, 2 * (size_t)E)); HIPCHK(dalloc(ws.Q, (size_t)E)); HIPCHK(dalloc(ws.kin, (size_t)E));
     if (nsnp) HIPCHK(dalloc(ws.nsnp, (size_t)E));

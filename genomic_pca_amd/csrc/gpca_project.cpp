@@ -24,19 +24,6 @@ struct ProjWs {
         dfree(Ypa); dfree(Ypb); dfree(Yia); dfree(Yib); dfree(cnt); dfree(bad);
     }
 };
-// A buffer that crosses the ranks' exchange: device memory, or -- when the device has none left -- pinned host memory the device
-// can address, so that a rank that is out of memory still reaches the exchange and reports its failure there instead of leaving
-// the other ranks waiting in it.
-struct XBuf {
-    double* p = nullptr; bool pinned = false;
-    hipError_t alloc(size_t n) {
-        if (hipMalloc((void**)&p, std::max<size_t>(n, 1) * 8) == hipSuccess) return hipSuccess;
-        (void)hipGetLastError();
-        p = nullptr; pinned = true;
-        return hipHostMalloc((void**)&p, std::max<size_t>(n, 1) * 8, hipHostMallocDefault);
-    }
-    ~XBuf() { if (p) { if (pinned) (void)hipHostFree(p); else (void)hipFree(p); } }
-};
 }  // namespace
 
 extern "C" int gpca_project(gpca_handle* h, const float* mu, const float* sigma, const float* W, int32_t k, double* scores, int32_t* n_used) {
@@ -51,9 +38,7 @@ extern "C" int gpca_project(gpca_handle* h, const float* mu, const float* sigma,
     const bool mr = multi_rank(h);
     const int64_t M = h->M, N = h->N, Mpad = h->Mpad, Npad = h->ldg;
     const int Lp = (int)round_up(k, 32), halves = Lp / 32;
-    int lrc = GPCA_OK;
-    // A rank-local failure does not return before the exchange on a sharded handle: every rank must reach it (gpca_transform's rule).
-#define LOCAL(x) do { if (lrc == GPCA_OK) lrc = (x); if (lrc != GPCA_OK && !mr) return lrc; } while (0)
+    int lrc = GPCA_OK;                       // (the LOCAL rule: gpca_internal.h)
 
     // 1. the model on the host: rows with a nonzero W row are in it; those need finite mu, sigma, W and sigma > 0
     std::vector<uint8_t> keep((size_t)M, 0);
@@ -69,7 +54,7 @@ extern "C" int gpca_project(gpca_handle* h, const float* mu, const float* sigma,
             if (!finite || !std::isfinite(mu[i]) || !std::isfinite(sigma[i]) || !(sigma[i] > 0.f))
                 return fail(h, GPCA_ERR_BAD_ARG, "gpca_project: model row " + std::to_string(i + h->snp_offset) +
                                                      " has a non-finite mu, sigma or W entry, or sigma <= 0");
-            keep[(size_t)i] = 1; rmask[(size_t)(i >> 5)] |= 1u << (i & 31); ++n_model;
+            keep[(size_t)i] = 1; set_row_bit(rmask, i); ++n_model;
             std::copy(wi, wi + k, Wp.begin() + (size_t)i * Lp);
         }
         return GPCA_OK;
@@ -181,8 +166,7 @@ extern "C" int gpca_project(gpca_handle* h, const float* mu, const float* sigma,
         ScopedTimer t(h, "project", 4.0 * elems * k, (packed ? elems / 4 : elems) * halves);
         CHK(for_each_panel(h, [&](const PanelView& pv) -> int {
             const PrjPlan plan = prj_plan(pv.rows_pad, Npad, h->gtt_waves_target);
-            const void* G = packed ? (const void*)pv.g2 : (const void*)pv.g8;
-            const int64_t ldr = packed ? h->ld2 : h->ld8;
+            const auto [G, ldr] = panel_rows(h, pv);
             const size_t blk0 = (size_t)(pv.row0 >> 5);
             for (int hf = 0; hf < halves; ++hf) {
                 launch_project(h->st, G, packed, ldr, pv.rows_pad, Npad, ws.Ta + hf * td_half + blk0 * kPlaneBytesPerBlock,
@@ -208,33 +192,16 @@ extern "C" int gpca_project(gpca_handle* h, const float* mu, const float* sigma,
     };
     LOCAL(sweep());
     // the dosage check of the kernel: its verdict must be known before the exchange carries the status word
-    auto check = [&]() -> int {
-        unsigned bad = 0;
-        HIPCHK(hipMemcpyAsync(&bad, ws.bad, 4, hipMemcpyDeviceToHost, h->st));
-        HIPCHK(hipStreamSynchronize(h->st));
-        if (bad) return fail(h, GPCA_ERR_INVALID_GENOTYPE, "gpca_project: a model row holds a genotype outside {0, 1, 2, missing}");
-        return GPCA_OK;
-    };
-    LOCAL(check());
+    LOCAL(check_genotype_flag(h, "gpca_project", "model", ws.bad));
 
-    // 3. one exchange of scores, counts and the status word (sharded handles: 16 status slots behind the block, gpca_transform's form)
+    // 3. one exchange of scores, counts and the status word (sharded handles: exchange_with_status, the whole block comes back)
     std::vector<double> host(outn, 0.0);
-    if (mr) {
-        h->status_own = h->err;
-        status_histogram(h->h_status, lrc);
-        if (hipMemcpyAsync(out + outn - 16, h->h_status, 16 * sizeof(double), hipMemcpyHostToDevice, h->st) != hipSuccess && lrc == GPCA_OK)
-            lrc = fail(h, GPCA_ERR_HIP, "gpca_project: status copy failed");
-    }
-    { const int xrc = allreduce_f64(h, out, (int64_t)outn); if (xrc != GPCA_OK) return xrc; }
-    HIPCHK(hipMemcpyAsync(host.data(), out, outn * 8, hipMemcpyDeviceToHost, h->st));
-    HIPCHK(hipStreamSynchronize(h->st));
-    if (mr) {
-        const int own_rc = lrc;
-        lrc = status_verdict(h, host.data() + outn - 16, own_rc, h->status_own, "gpca_project");
-        if (lrc == GPCA_OK) lrc = own_rc;
+    if (mr) CHK(exchange_with_status(h, "gpca_project", out, outn, lrc, host.data(), outn));
+    else {
+        HIPCHK(hipMemcpyAsync(host.data(), out, outn * 8, hipMemcpyDeviceToHost, h->st));
+        HIPCHK(hipStreamSynchronize(h->st));
     }
     if (lrc != GPCA_OK) return lrc;
-#undef LOCAL
     for (int64_t n = 0; n < N; ++n) {
         for (int c = 0; c < k; ++c) scores[(size_t)n * k + c] = host[(size_t)n * Lp + c];
         if (n_used) n_used[n] = (int32_t)host[(size_t)N * Lp + n];

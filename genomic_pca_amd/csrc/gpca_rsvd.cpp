@@ -567,7 +567,6 @@ static int finish_small_eigh(gpca_handle* h, bool take) {
 static int call_tail(gpca_handle* h, int zmode, double denom, const float* Xload, int lrc) {
     const bool mr = multi_rank(h);
     const int L = h->L;
-#define LOCAL(x) do { if (lrc == GPCA_OK) lrc = (x); if (lrc != GPCA_OK && !mr) return lrc; } while (0)
     const double* gsrc = h->dW; int gslices = 0;
     auto gram = [&]() -> int {
         const int64_t rows = zmode == 0 ? h->M : h->N;
@@ -609,7 +608,6 @@ static int call_tail(gpca_handle* h, int zmode, double denom, const float* Xload
         if (agreed != GPCA_OK) return agreed;
         h->err = own_now;
     }
-#undef LOCAL
     return lrc;
 }
 
@@ -715,7 +713,6 @@ extern "C" int gpca_rsvd(gpca_handle* h, int32_t k, int32_t oversample, int32_t 
     const int l = h->l, L = h->L;
     // ... and from here on a rank-local failure is remembered (lrc) while the rank keeps entering every exchange of the call, so
     // that its peers are not left inside a collective; the second agreement below returns the failure on every rank.
-#define LOCAL(x) do { if (lrc == GPCA_OK) lrc = (x); if (lrc != GPCA_OK && !mr) return lrc; } while (0)
 #define EXCHANGE(buf, count) do { \
         if (agreement_pending) { \
             agreement_pending = false; \
@@ -761,7 +758,6 @@ extern "C" int gpca_rsvd(gpca_handle* h, int32_t k, int32_t oversample, int32_t 
     //    on the device, scores, sign, loadings, the call's one host wait: call_tail
     lrc = call_tail(h, 0, n_eff - 1.0, h->dT, lrc);
     if (lrc != GPCA_OK) return lrc;
-#undef LOCAL
 #undef EXCHANGE
     h->have_rsvd = true; h->loadings_valid = true;
     return GPCA_OK;
@@ -814,7 +810,6 @@ extern "C" int gpca_transform(gpca_handle* h, double* out) {
     const int L = h->L, k = h->k;
     const bool mr = multi_rank(h);
     int lrc = GPCA_OK;
-#define LOCAL(x) do { if (lrc == GPCA_OK) lrc = (x); if (lrc != GPCA_OK && !mr) return lrc; } while (0)
     auto prep = [&]() -> int {
         // T' = r o U (zero rows for dropped SNPs), c = b^T U
         HIPCHK(hipMemsetAsync(h->dT, 0, (size_t)h->Mpad * L * 4, h->st));
@@ -846,7 +841,6 @@ extern "C" int gpca_transform(gpca_handle* h, double* out) {
         if (lrc == GPCA_OK) lrc = own_rc;
     }
     if (lrc != GPCA_OK) return lrc;
-#undef LOCAL
     // only the k columns asked for leave the device (the whole N x L block was 256 MB at N = 500k, L = 64): compacted on the device
     // by a right-multiplication with the L x k selection matrix, then one contiguous copy into the caller's buffer
     CHK(ensure(h, h->d_tr64, h->cap_tr64, (size_t)h->N * k));

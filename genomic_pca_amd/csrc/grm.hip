@@ -16,26 +16,12 @@
 // Integer partials are flushed to an f64 running sum once per kGrmFlushRows rows counted from the panel's first row, in row order, and
 // the running sums live in the caller's buffer between panels: the bits do not depend on the launch grid, the band or (when the panel
 // rows are a multiple of kGrmFlushRows) the panels.
-#include "gemm_i8_common.h"
+#include "syrk_tile.h"
 
 namespace gpca {
 
 static_assert(kGrmFlushRows % 32 == 0 && (int64_t)kGrmFlushRows * 254 < ((int64_t)1 << 31), "flush group");
 constexpr int kGrmLdsPitch = 48;      // bytes per sample of a staged block (32 rows + 16: ds_read_b128 stays 16-byte aligned)
-
-// 4 x 4 byte transpose: x[r] holds bytes (r, 0..3) -> y[k] holds bytes (0..3, k)
-__device__ __forceinline__ void tr4x4(const unsigned (&x)[4], unsigned (&y)[4]) {
-    const unsigned a = (unsigned)permb((int)x[1], (int)x[0], 0x05010400u), b = (unsigned)permb((int)x[1], (int)x[0], 0x07030602u);
-    const unsigned c = (unsigned)permb((int)x[3], (int)x[2], 0x05010400u), d = (unsigned)permb((int)x[3], (int)x[2], 0x07030602u);
-    y[0] = (unsigned)permb((int)c, (int)a, 0x05040100u); y[1] = (unsigned)permb((int)c, (int)a, 0x07060302u);
-    y[2] = (unsigned)permb((int)d, (int)b, 0x05040100u); y[3] = (unsigned)permb((int)d, (int)b, 0x07060302u);
-}
-// four 2-bit codes (sample k at bits 2k) -> four int8 calls (code 3 = missing -> -127)
-__device__ __forceinline__ unsigned unpack4(unsigned v) {
-    unsigned d = (v & 3u) | ((v & 0xcu) << 6) | ((v & 0x30u) << 12) | ((v & 0xc0u) << 18);
-    const unsigned m = d & (d >> 1) & 0x01010101u;
-    return (d & ~(m * 3u)) | (m * 0x81u);
-}
 
 // Staging of block `blk` of the two sample ranges, in two halves so that the global loads of block blk + 1 are in flight while the
 // waves multiply block blk: thread t < 128 loads side a, t >= 128 side b, (rq, cq) = 4 rows x 4 samples; t < 48 also loads the tables.
@@ -45,38 +31,30 @@ __device__ __forceinline__ void grm_fetch(GrmFetch& F, const uint8_t* __restrict
                                           const int8_t* __restrict__ tab) {
     const int t = threadIdx.x, side = t >> 7, u = t & 127, rq = u >> 4, cq = u & 15;
     const int64_t col = (side ? cb0 : ca0) + 4 * cq;
-    const uint8_t* src = G + (blk * 32 + 4 * rq) * ldr + (PACKED ? col / 4 : col);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) F.x[r] = PACKED ? (unsigned)src[r * ldr] : *reinterpret_cast<const unsigned*>(src + r * ldr);
+    unit_fetch<PACKED>(F.x, G + (blk * 32 + 4 * rq) * ldr + (PACKED ? col / 4 : col), ldr);
     if (t < kGrmTabBytes / 16) F.t = *reinterpret_cast<const i32x4*>(tab + blk * kGrmTabBytes + 16 * t);
 }
 template <bool PACKED>
 __device__ __forceinline__ void grm_put(const GrmFetch& F, uint8_t* la, uint8_t* lb, uint8_t* lt) {
     const int t = threadIdx.x, side = t >> 7, u = t & 127, rq = u >> 4, cq = u & 15;
-    unsigned x[4], y[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) x[r] = PACKED ? unpack4(F.x[r]) : F.x[r];
-    tr4x4(x, y);
-    uint8_t* dst = (side ? lb : la) + (4 * cq) * kGrmLdsPitch + 4 * rq;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) *reinterpret_cast<unsigned*>(dst + k * kGrmLdsPitch) = y[k];
+    unit_put<PACKED>(F.x, (side ? lb : la) + (4 * cq) * kGrmLdsPitch + 4 * rq, kGrmLdsPitch);
     if (t < kGrmTabBytes / 16) *reinterpret_cast<i32x4*>(lt + 16 * t) = F.t;
 }
 
 // R [band]: running f64 sums of the digit-combined integer partials (unscaled); Q [band]: sum over kept rows of m_a m_b.
-// Band element (a, b <= a), row0 <= a < row1, a < N, at a (a + 1) / 2 - row0 (row0 + 1) / 2 + b.  first: R and Q start at 0.
+// Band element (a, b <= a), row0 <= a < row1, a < N, at band_index(row0, a, b, true).  first: R and Q start at 0.
 template <bool PACKED>
 __global__ __launch_bounds__(256, 1) void k_grm(const void* __restrict__ Gv, int64_t ldr, int64_t rows_pad, const int8_t* __restrict__ tab,
                                                  const uint32_t* __restrict__ kmask, const int2* __restrict__ tiles, int64_t row0,
                                                  int64_t row1, int64_t N, double* __restrict__ R, int* __restrict__ Q, int first) {
-    __shared__ __attribute__((aligned(16))) uint8_t la[64 * kGrmLdsPitch];
-    __shared__ __attribute__((aligned(16))) uint8_t lb[64 * kGrmLdsPitch];
+    __shared__ __attribute__((aligned(16))) uint8_t la[kGrmTile * kGrmLdsPitch];
+    __shared__ __attribute__((aligned(16))) uint8_t lb[kGrmTile * kGrmLdsPitch];
     __shared__ __attribute__((aligned(16))) uint8_t lt[kGrmTabBytes];
     const uint8_t* G = (const uint8_t*)Gv;
     const int2 tl = tiles[blockIdx.x];
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int c = lane & 31, h = lane >> 5, wa = wv >> 1, wb = wv & 1;
-    const int64_t ca0 = (int64_t)tl.x * 64, cb0 = (int64_t)tl.y * 64;
+    const int64_t ca0 = (int64_t)tl.x * kGrmTile, cb0 = (int64_t)tl.y * kGrmTile;
     const bool active = !(tl.x == tl.y && wa == 0 && wb == 1);   // (the upper sub-tile of a diagonal tile)
     constexpr int ND = kGrmDigits;
 
@@ -85,12 +63,12 @@ __global__ __launch_bounds__(256, 1) void k_grm(const void* __restrict__ Gv, int
 #pragma unroll
     for (int e = 0; e < 16; ++e) { q0[e] = 0; run[e] = 0.0; }
     const int64_t a_base = ca0 + 32 * wa, b_col = cb0 + 32 * wb + c;
-    const int64_t base = row0 * (row0 + 1) / 2;
+    const int64_t base = band_entries(0, row0, true);
     if (!first && active && b_col < N) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            const int64_t a = a_base + (e & 3) + 8 * (e >> 2) + 4 * h;
-            if (a >= row0 && a < row1 && a < N && b_col <= a) { const int64_t ix = a * (a + 1) / 2 - base + b_col; run[e] = R[ix]; q0[e] = Q[ix]; }
+            const int64_t a = acc_row(a_base, e, h);
+            if (band_holds<true>(row0, row1, N, a, b_col)) { const int64_t ix = band_entries(0, a, true) - base + b_col; run[e] = R[ix]; q0[e] = Q[ix]; }
         }
     }
     const int64_t nblk = rows_pad >> 5;
@@ -157,7 +135,7 @@ __global__ __launch_bounds__(256, 1) void k_grm(const void* __restrict__ Gv, int
                 const unsigned km = (kmask[blk] >> (16 * h)) & 0xffffu;
                 i32x4 mk;
 #pragma unroll
-                for (int k = 0; k < 4; ++k) mk[k] = (int)((unsigned)ma[k] & ((((km >> (4 * k)) & 0xfu) * 0x00204081u) & 0x01010101u));
+                for (int k = 0; k < 4; ++k) mk[k] = (int)((unsigned)ma[k] & kept_bytes(km, k));
                 q0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(mk, mb, q0, 0, 0, 0);
             }
         }
@@ -174,8 +152,8 @@ __global__ __launch_bounds__(256, 1) void k_grm(const void* __restrict__ Gv, int
     if (!active || b_col >= N) return;
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-        const int64_t a = a_base + (e & 3) + 8 * (e >> 2) + 4 * h;
-        if (a >= row0 && a < row1 && a < N && b_col <= a) { const int64_t ix = a * (a + 1) / 2 - base + b_col; R[ix] = run[e]; Q[ix] = q0[e]; }
+        const int64_t a = acc_row(a_base, e, h);
+        if (band_holds<true>(row0, row1, N, a, b_col)) { const int64_t ix = band_entries(0, a, true) - base + b_col; R[ix] = run[e]; Q[ix] = q0[e]; }
     }
 }
 
@@ -201,11 +179,9 @@ __global__ __launch_bounds__(256) void k_grm_vec(const void* __restrict__ Gv, in
     unsigned nm = 0, bd = 0;
     for (int64_t i = i0; i < i1; ++i) {
         if (!keep[i]) continue;
-        int v;
-        if (PACKED) { const unsigned code = (G[i * ldr + (n >> 2)] >> (2 * (n & 3))) & 3u; v = code == 3u ? -127 : (int)code; }
-        else v = (int8_t)G[i * ldr + n];
-        if (v == -127) { ++nm; sv += qe[i]; }
-        else if (v >= 0 && v <= 2) su += (long long)v * qc[i];
+        const unsigned v = call_at<PACKED>(G, ldr, i, n);
+        if (v == kMissingByte) { ++nm; sv += qe[i]; }
+        else if (v <= 2u) su += (long long)v * qc[i];
         else bd = 1u;
     }
     Up[gi * Npad + n] = (double)su;
@@ -240,7 +216,7 @@ __global__ __launch_bounds__(256) void k_grm_finish(const double* __restrict__ R
                                                     const double* __restrict__ v, const unsigned* __restrict__ cnt, double S, double beta,
                                                     double K, int64_t row0, double* __restrict__ out, double* __restrict__ npairs) {
     const int64_t a = row0 + blockIdx.x;
-    const int64_t o = a * (a + 1) / 2 - row0 * (row0 + 1) / 2;
+    const int64_t o = band_index(row0, a, 0, true);
     for (int64_t b = threadIdx.x; b <= a; b += 256) {
         out[o + b] = S * ((((R[o + b] - u[a]) - u[b]) + beta) - v[a] - v[b]);
         if (npairs) npairs[o + b] = (K - (double)cnt[a] - (double)cnt[b]) + (double)Q[o + b];

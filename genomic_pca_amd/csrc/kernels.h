@@ -30,6 +30,11 @@ int init_device_kernels_eig();
 void launch_small_eigh(hipStream_t st, const double* src, int nslices, int n, int L, int k, int zmode, double denom, const int* cholflag,
                        double* Z, double* res, double* Vout);
 
+// C/D of a 32 x 32 MFMA: register e (0 .. 15) of a lane of half h (= lane >> 5) holds row (e & 3) + 8 (e >> 2) + 4 h of column
+// lane & 31; acc_row = that row of the sub-tile whose first row is row0
+template <class T>
+__host__ __device__ inline constexpr T acc_row(T row0, int e, int h) { return row0 + (e & 3) + 8 * (e >> 2) + 4 * h; }
+
 // Blocked layouts of the skinny GEMM operands (gemm_f32.hip): a lane's 8 / 16 k-steps are contiguous.
 //   Tb [group = row/16][lt][lane = 32*(row&1) + col%32][u = (row%16)/2]      (8 floats per lane)
 //   Qb [chunk = n/32][lt][lane = 32*((n%32)/16) + col%32][u = n%16]           (16 floats per lane)

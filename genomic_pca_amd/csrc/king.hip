@@ -12,31 +12,16 @@
 // blocks where a wave ballot finds a missing call on a kept row add three (H M^T, M H^T, M M^T).  Rows that are not kept are zeroed in
 // the row-side operands (and in the column side's M, for the ballot) from the call's kept-row bit mask.
 // The sums are exact in i32 (K < 2^31) and are added to f64 running sums once per launch: the bits depend on nothing but the counts.
-#include "gemm_i8_common.h"
+#include "syrk_tile.h"
 
 namespace gpca {
 
-constexpr int kKingTile = 128;                 // samples per side of a workgroup tile
 constexpr int kKingThreads = 512;              // 8 waves: 4 x 2 strips of 32 x 64 (two 32 x 32 sub-tiles that share the row side)
 constexpr int kKingStageRows = 64;             // rows per LDS stage (2 blocks of 32)
 constexpr int kKingPitch = kKingStageRows + 16;  // bytes per sample of a staged side (ds_read_b128 stays 16-byte aligned)
 constexpr int kKingUnits = 2 * kKingTile / 4 * kKingStageRows / 4 / kKingThreads;   // 4 x 4 (rows x samples) units per thread and stage
 constexpr int kKingRQ = kKingStageRows / 4;       // row quads of a stage
 static_assert(kKingUnits >= 1 && kKingRQ % 16 == 0 && (kKingRQ / 16 & (kKingRQ / 16 - 1)) == 0, "staging map");
-
-// 4 x 4 byte transpose: x[r] holds bytes (r, 0..3) -> y[k] holds bytes (0..3, k)
-__device__ __forceinline__ void king_tr4x4(const unsigned (&x)[4], unsigned (&y)[4]) {
-    const unsigned a = (unsigned)permb((int)x[1], (int)x[0], 0x05010400u), b = (unsigned)permb((int)x[1], (int)x[0], 0x07030602u);
-    const unsigned c = (unsigned)permb((int)x[3], (int)x[2], 0x05010400u), d = (unsigned)permb((int)x[3], (int)x[2], 0x07030602u);
-    y[0] = (unsigned)permb((int)c, (int)a, 0x05040100u); y[1] = (unsigned)permb((int)c, (int)a, 0x07060302u);
-    y[2] = (unsigned)permb((int)d, (int)b, 0x05040100u); y[3] = (unsigned)permb((int)d, (int)b, 0x07060302u);
-}
-// four 2-bit codes (sample k at bits 2k) -> four int8 calls (code 3 = missing -> -127)
-__device__ __forceinline__ unsigned king_unpack4(unsigned v) {
-    unsigned d = (v & 3u) | ((v & 0xcu) << 6) | ((v & 0x30u) << 12) | ((v & 0xc0u) << 18);
-    const unsigned m = d & (d >> 1) & 0x01010101u;
-    return (d & ~(m * 3u)) | (m * 0x81u);
-}
 
 // Unit q of a stage (q = threadIdx.x + kKingThreads * j): side = q / (32 kKingRQ), then kKingRQ row quads x 32 sample quads per side,
 // laid out so that a wave covers 16 row quads x 4 sample quads (its LDS stores spread over the banks).
@@ -55,9 +40,7 @@ __device__ __forceinline__ void king_fetch(KingFetch& F, const uint8_t* __restri
         int side, rq, cq;
         king_unit((int)threadIdx.x + kKingThreads * j, side, rq, cq);
         const int64_t col = (side ? cb0 : ca0) + 4 * cq;
-        const uint8_t* src = G + (stage * kKingStageRows + 4 * rq) * ldr + (PACKED ? col / 4 : col);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) F.x[j][r] = PACKED ? (unsigned)src[r * ldr] : *reinterpret_cast<const unsigned*>(src + r * ldr);
+        unit_fetch<PACKED>(F.x[j], G + (stage * kKingStageRows + 4 * rq) * ldr + (PACKED ? col / 4 : col), ldr);
     }
 }
 template <bool PACKED>
@@ -66,18 +49,12 @@ __device__ __forceinline__ void king_put(const KingFetch& F, uint8_t* buf) {
     for (int j = 0; j < kKingUnits; ++j) {
         int side, rq, cq;
         king_unit((int)threadIdx.x + kKingThreads * j, side, rq, cq);
-        unsigned x[4], y[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) x[r] = PACKED ? king_unpack4(F.x[j][r]) : F.x[j][r];
-        king_tr4x4(x, y);
-        uint8_t* dst = buf + (side * kKingTile + 4 * cq) * kKingPitch + 4 * rq;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) *reinterpret_cast<unsigned*>(dst + k * kKingPitch) = y[k];
+        unit_put<PACKED>(F.x[j], buf + (side * kKingTile + 4 * cq) * kKingPitch + 4 * rq, kKingPitch);
     }
 }
 
 // R [5][E]: f64 running sums XX, HH, HM, MH, MM of the band (E entries; first: they start at 0).  Band element (a, b < a),
-// row0 <= a < row1, a < N, at a (a - 1) / 2 - row0 (row0 - 1) / 2 + b; HM / MH: H / M of the row-side sample a.
+// row0 <= a < row1, a < N, at band_index(row0, a, b, false); HM / MH: H / M of the row-side sample a.
 template <bool PACKED>
 __global__ __launch_bounds__(kKingThreads, 1) void k_king(const void* __restrict__ Gv, int64_t ldr, int64_t rows_pad,
                                                           const uint32_t* __restrict__ kmask, const int2* __restrict__ tiles, int64_t row0,
@@ -117,7 +94,7 @@ __global__ __launch_bounds__(kKingThreads, 1) void k_king(const void* __restrict
                 unsigned anym = 0u;
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    const unsigned kb = (((km >> (4 * k)) & 0xfu) * 0x00204081u) & 0x01010101u;   // kept rows of these 4 bytes
+                    const unsigned kb = kept_bytes(km, k);   // kept rows of these 4 bytes
                     const unsigned a = (unsigned)va[k];
                     const unsigned ma = (a >> 7) & 0x01010101u;
                     // X: hom = bit 0 clear (0 or 2; the missing code 0x81 has it set), two = bit 1 set (2 only)
@@ -132,7 +109,7 @@ __global__ __launch_bounds__(kKingThreads, 1) void k_king(const void* __restrict
                     const i32x4 vb = *reinterpret_cast<const i32x4*>(buf + b_off + 32 * j * kKingPitch + 32 * bi + 16 * h);
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
-                        const unsigned kb = (((km >> (4 * k)) & 0xfu) * 0x00204081u) & 0x01010101u;
+                        const unsigned kb = kept_bytes(km, k);
                         const unsigned b = (unsigned)vb[k];
                         const unsigned mb = (b >> 7) & 0x01010101u;
                         const unsigned ob = ~b & 0x01010101u, tb = (b >> 1) & 0x01010101u;
@@ -161,16 +138,16 @@ __global__ __launch_bounds__(kKingThreads, 1) void k_king(const void* __restrict
         __syncthreads();
     }
     const int64_t a_base = ca0 + 32 * wa;
-    const int64_t base = row0 * (row0 - 1) / 2;
+    const int64_t base = band_entries(0, row0, false);
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int64_t b_col = cb0 + 32 * (wb + j) + c;
         if (!(j ? act1 : act0) || b_col >= N) continue;
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            const int64_t a = a_base + (e & 3) + 8 * (e >> 2) + 4 * h;
-            if (a >= row0 && a < row1 && a < N && b_col < a) {
-                const int64_t ix = a * (a - 1) / 2 - base + b_col;
+            const int64_t a = acc_row(a_base, e, h);
+            if (band_holds<false>(row0, row1, N, a, b_col)) {
+                const int64_t ix = band_entries(0, a, false) - base + b_col;
                 const double v[5] = {(double)xx[j][e], (double)hh[j][e], (double)hm[j][e], (double)mh[j][e], (double)mm[j][e]};
 #pragma unroll
                 for (int t = 0; t < 5; ++t) R[t * E + ix] = first ? v[t] : R[t * E + ix] + v[t];
@@ -200,12 +177,10 @@ __global__ __launch_bounds__(256) void k_king_vec(const void* __restrict__ Gv, i
     unsigned nh = 0, nm = 0, bd = 0;
     for (int64_t i = i0; i < i1; ++i) {
         if (!keep[i]) continue;
-        int v;
-        if (PACKED) { const unsigned code = (G[i * ldr + (n >> 2)] >> (2 * (n & 3))) & 3u; v = code == 3u ? -127 : (int)code; }
-        else v = (int8_t)G[i * ldr + n];
-        if (v == -127) ++nm;
-        else if (v == 1) ++nh;
-        else if (v != 0 && v != 2) bd = 1u;
+        const unsigned v = call_at<PACKED>(G, ldr, i, n);
+        if (v == kMissingByte) ++nm;
+        else if (v == 1u) ++nh;
+        else if (v != 0u && v != 2u) bd = 1u;
     }
     if (nh) atomicAdd(het + n, nh);
     if (nm) atomicAdd(miss + n, nm);
@@ -240,7 +215,7 @@ __global__ __launch_bounds__(256) void k_king_finish(const double* __restrict__ 
                                                      const double* __restrict__ miss, double K, int64_t row0, double* __restrict__ kin,
                                                      int* __restrict__ counts) {
     const int64_t a = row0 + blockIdx.x;
-    const int64_t o = a * (a - 1) / 2 - row0 * (row0 - 1) / 2;
+    const int64_t o = band_index(row0, a, 0, false);
     for (int64_t b = threadIdx.x; b < a; b += 256) {
         const int64_t ix = o + b;
         const double XX = R[ix], HH = R[E + ix], HM = R[2 * E + ix], MH = R[3 * E + ix], MM = R[4 * E + ix];

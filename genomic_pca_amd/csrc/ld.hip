@@ -14,7 +14,7 @@
 // of stage s + 2 are issued: two stages in flight, one barrier per stage.  Kept rows are reached through the handle's list of
 // original row indices.  When rows x chunks do not fill the device the sample axis is split over workgroups and the i32 partial sums
 // meet in atomics (integer addition: any order gives the same bits).
-#include "gemm_i8_common.h"
+#include "syrk_tile.h"
 
 namespace gpca {
 
@@ -26,12 +26,6 @@ constexpr int kLdUnitsA = kLdRows * kLdSegs / kLdThreads;           // the first
 static_assert(kLdStageRows * kLdSegs % kLdThreads == 0 && kLdRows * kLdSegs % kLdThreads == 0, "staging map");
 static_assert(kLdCols / 32 == kLdThreads / 64 && kLdRows == 64, "one column tile per wave, two row tiles");
 
-// four 2-bit codes (sample k at bits 2k) -> four int8 calls (code 3 = missing -> -127)
-__device__ __forceinline__ unsigned ld_unpack4(unsigned v) {
-    unsigned d = (v & 3u) | ((v & 0xcu) << 6) | ((v & 0x30u) << 12) | ((v & 0xc0u) << 18);
-    const unsigned m = d & (d >> 1) & 0x01010101u;
-    return (d & ~(m * 3u)) | (m * 0x81u);
-}
 // byte mask of dword w of a 16-sample segment of which the first nvalid samples exist
 __device__ __forceinline__ unsigned ld_tail_mask(int w, int nvalid) {
     const int nb = nvalid - 4 * w;
@@ -68,7 +62,7 @@ __device__ __forceinline__ void ld_put(const LdFetch& F, uint8_t* buf, int64_t s
         uint4 v;
         if (PACKED) {
             const unsigned p = F.x[j].x;
-            v = make_uint4(ld_unpack4(p & 0xffu), ld_unpack4((p >> 8) & 0xffu), ld_unpack4((p >> 16) & 0xffu), ld_unpack4(p >> 24));
+            v = make_uint4(unpack4(p & 0xffu), unpack4((p >> 8) & 0xffu), unpack4((p >> 16) & 0xffu), unpack4(p >> 24));
         } else v = F.x[j];
         if (nvalid < 16) { v.x &= ld_tail_mask(0, nvalid); v.y &= ld_tail_mask(1, nvalid); v.z &= ld_tail_mask(2, nvalid); v.w &= ld_tail_mask(3, nvalid); }
         *reinterpret_cast<uint4*>(buf + (lrow0 + j * (kLdThreads / kLdSegs)) * kLdPitch + 16 * seg) = v;
@@ -179,7 +173,7 @@ __global__ __launch_bounds__(kLdThreads) void k_ld(const void* __restrict__ Gv, 
         if (!act[rt]) continue;
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            const int64_t i = i0 + 32 * rt + (e & 3) + 8 * (e >> 2) + 4 * h;
+            const int64_t i = acc_row(i0 + 32 * rt, e, h);
             if (i >= row1 || j <= i) continue;
             if (j >= win_end[i - row0]) continue;
             const int64_t ix = (i - row0) * wmax + (j - i - 1);
@@ -226,7 +220,7 @@ __global__ __launch_bounds__(256) void k_ld_vec(const void* __restrict__ Gv, int
         uint4 v;
         if (PACKED) {
             const unsigned p = *reinterpret_cast<const unsigned*>(src + k / 4);
-            v = make_uint4(ld_unpack4(p & 0xffu), ld_unpack4((p >> 8) & 0xffu), ld_unpack4((p >> 16) & 0xffu), ld_unpack4(p >> 24));
+            v = make_uint4(unpack4(p & 0xffu), unpack4((p >> 8) & 0xffu), unpack4((p >> 16) & 0xffu), unpack4(p >> 24));
         } else v = *reinterpret_cast<const uint4*>(src + k);
         const int nvalid = N - k >= 16 ? 16 : (int)(N - k);
         const unsigned d[4] = {v.x, v.y, v.z, v.w};

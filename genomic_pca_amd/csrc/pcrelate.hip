@@ -20,7 +20,7 @@
 // sum) x 2 products, with the pair counts, is 224 of the 256 registers a wave of a 512-thread workgroup has.  Each product rebuilds mu.
 // The pair count is exact: nsnp_ab = K - inv_a - inv_b + sum_i inv_ia inv_ib (inv = the entry is invalid, k_pcrelate_inv counts it per
 // sample), the last sum on v_mfma_i32_32x32x16_i8 and only in stages where a wave ballot finds an invalid entry on both sides.
-#include "gemm_i8_common.h"
+#include "syrk_tile.h"
 
 namespace gpca {
 
@@ -30,18 +30,8 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int kPcrP1Max = kPcrMaxPcs + 1;
 constexpr int kPcrPitch = kPcrStageRows + 4;        // floats per sample of a staged side (ds_read_b128 stays 16-byte aligned)
 constexpr int kPcrInvPitch = kPcrStageRows + 8;     // bytes per sample of the staged invalid indicator (ds_read_b64 stays 8-byte aligned)
-constexpr int kPcrMissing = 0x81;                   // the int8 missing code (-127) as a byte
+constexpr int kPcrMissing = (int)kMissingByte;
 static_assert(kPcrStageRows == 16 && kPcrThreads == 4 * kPcrTile && kPcrFlushRows / kPcrStageRows >= 1, "staging map: 2 sides x 128 samples x 2 row halves");
-
-// the call of (original row orow, sample n) as a byte: 0, 1, 2 or kPcrMissing (anything else: k_pcrelate_beta reports the row)
-template <bool PACKED>
-__device__ __forceinline__ unsigned pcr_call(const uint8_t* __restrict__ G, int64_t ldr, int64_t orow, int64_t n) {
-    if (PACKED) {
-        const unsigned code = (G[orow * ldr + (n >> 2)] >> (2 * (int)(n & 3))) & 3u;
-        return code == 3u ? (unsigned)kPcrMissing : code;
-    }
-    return G[orow * ldr + n];
-}
 
 // The individual-specific allele frequencies of one sample at 8 consecutive kept rows: bg = the rows' coefficients [P1][8] (the same
 // for every lane), x = the sample's design row.  mu[r] = 0.5f * (fmaf chain over j = 0 .. P1 - 1, from 0).
@@ -66,7 +56,8 @@ __device__ __forceinline__ void pcr_load_x(float (&x)[kPcrP1Max], const float* _
     for (int j = 0; j < kPcrP1Max; ++j) x[j] = j < P1 ? X[n * P1 + j] : 0.0f;
 }
 
-// the 8 calls of one sample at kept rows kr0 .. kr0 + 7 (rows past K and samples past N: missing)
+// the 8 calls of one sample at kept rows kr0 .. kr0 + 7 (rows past K and samples past N: missing; a byte that is no call:
+// k_pcrelate_beta reports the row)
 struct PcrFetch { unsigned lo, hi; };
 template <bool PACKED>
 __device__ __forceinline__ void pcr_fetch(PcrFetch& F, const uint8_t* __restrict__ G, int64_t ldr, const int64_t* __restrict__ krows,
@@ -75,7 +66,7 @@ __device__ __forceinline__ void pcr_fetch(PcrFetch& F, const uint8_t* __restrict
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
         b[r] = (unsigned)kPcrMissing;
-        if (kr0 + r < K && n_ok) b[r] = pcr_call<PACKED>(G, ldr, krows[kr0 + r], n);
+        if (kr0 + r < K && n_ok) b[r] = call_at<PACKED>(G, ldr, krows[kr0 + r], n);
     }
     F.lo = b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24);
     F.hi = b[4] | (b[5] << 8) | (b[6] << 16) | (b[7] << 24);
@@ -114,7 +105,7 @@ struct PcrSmem {
 };
 
 // R [2][E]: num (WHICH 0) and den (WHICH 1) of the band; Q [E]: sum of inv_a inv_b.  Band element (a, b <= a), row0 <= a < row1,
-// a < N, at a (a + 1) / 2 - row0 (row0 + 1) / 2 + b.
+// a < N, at band_index(row0, a, b, true).
 template <bool PACKED, int WHICH>
 __device__ __forceinline__ void pcr_tile(PcrSmem& sm, const uint8_t* __restrict__ G, int64_t ldr, const int64_t* __restrict__ krows,
                                          int64_t K, int64_t N, const float* __restrict__ betaG, const float* __restrict__ X, int P1,
@@ -200,9 +191,9 @@ __device__ __forceinline__ void pcr_tile(PcrSmem& sm, const uint8_t* __restrict_
         if (!(j ? act1 : act0) || b_col >= N) continue;
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-            const int64_t a = a_base + (e & 3) + 8 * (e >> 2) + 4 * h;
-            if (a >= row0 && a < row1 && a < N && b_col <= a) {
-                const int64_t ix = pcr_band_index(row0, a, b_col);
+            const int64_t a = acc_row(a_base, e, h);
+            if (band_holds<true>(row0, row1, N, a, b_col)) {
+                const int64_t ix = band_index(row0, a, b_col, true);
                 R[(int64_t)WHICH * E + ix] = run[j][e];
                 if (WHICH == 1) Q[ix] = qq[j][e];
             }
@@ -264,10 +255,7 @@ __global__ __launch_bounds__(64 * kPcrBetaWaves) void k_pcrelate_beta(const void
             unsigned a = 0u;
             if (sorow >= 0 && ns < N) {
                 if (PACKED) {
-                    const unsigned v = G[sorow * ldr + (ns >> 2)];
-                    unsigned dd = (v & 3u) | ((v & 0xcu) << 6) | ((v & 0x30u) << 12) | ((v & 0xc0u) << 18);
-                    const unsigned m = dd & (dd >> 1) & 0x01010101u;
-                    a = (dd & ~(m * 3u)) | (m * 0x81u);
+                    a = unpack4(G[sorow * ldr + (ns >> 2)]);
                 } else a = *reinterpret_cast<const unsigned*>(G + sorow * ldr + ns);
                 const int64_t left = N - ns;
                 if (left < 4) a &= (1u << (8 * (int)left)) - 1u;
@@ -400,7 +388,7 @@ void launch_pcrelate_inv(hipStream_t st, const void* G, int packed, int64_t ldr,
 __global__ __launch_bounds__(256) void k_pcrelate_finish(const double* __restrict__ R, const int* __restrict__ Q, const unsigned* __restrict__ inv,
                                                          int64_t K, int64_t E, int64_t row0, double* __restrict__ kin, int* __restrict__ nsnp) {
     const int64_t a = row0 + blockIdx.x;
-    const int64_t o = pcr_band_index(row0, a, 0);
+    const int64_t o = band_index(row0, a, 0, true);
     for (int64_t b = threadIdx.x; b <= a; b += 256) {
         const int64_t ix = o + b;
         const int64_t ns = ((K - (int64_t)inv[a]) - (int64_t)inv[b]) + (int64_t)Q[ix];      // (a = b: Q = inv_a, so K - inv_a)

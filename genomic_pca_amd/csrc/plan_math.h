@@ -6,6 +6,7 @@
 #include <stdint.h>
 #include <algorithm>
 #include <initializer_list>
+#include <vector>
 
 namespace gpca {
 
@@ -269,12 +270,28 @@ inline int64_t pcr_beta_capacity(int64_t K, int P) { return pcr_kpad(K) * (int64
 inline int64_t pcr_x_capacity(int64_t N, int P) { return pcr_npad(N) * (int64_t)(P + 1); }
 inline int64_t pcr_hat_capacity(int64_t N, int P) { return (int64_t)kPcrBetaWaves * N * pcr_beta_width(P); }
 inline int64_t pcr_inv_capacity(int64_t N) { return pcr_npad(N); }
-// the band [row0, row1) of the lower triangle with its diagonal: entries, and 128 x 128 tiles that meet it
-inline int64_t pcr_band_entries(int64_t row0, int64_t row1) { return row1 * (row1 + 1) / 2 - row0 * (row0 + 1) / 2; }
-constexpr int64_t pcr_band_index(int64_t row0, int64_t a, int64_t b) { return a * (a + 1) / 2 - row0 * (row0 + 1) / 2 + b; }
-inline int64_t pcr_tiles(int64_t row0, int64_t row1) {
-    const int64_t t0 = row0 / kPcrTile, t1 = (row1 + kPcrTile - 1) / kPcrTile;
-    return t1 * (t1 + 1) / 2 - t0 * (t0 + 1) / 2;
+
+// ---- bands of the sample triangle (gpca_grm, gpca_king, gpca_pcrelate: the kernels, their finish passes and the host front end) ----
+// A call computes the rows [row0, row1) of the lower triangle of the N x N sample matrix, packed row-major; diag: the diagonal belongs
+// to it (GRM, PC-Relate) or not (KING).  A workgroup owns one tile x tile block (tile row >= tile column) that meets the band.
+constexpr int kGrmTile = 64, kKingTile = 128;        // samples per side of a workgroup's tile (PC-Relate: kPcrTile)
+constexpr int64_t band_entries(int64_t row0, int64_t row1, bool diag) {
+    return diag ? row1 * (row1 + 1) / 2 - row0 * (row0 + 1) / 2 : row1 * (row1 - 1) / 2 - row0 * (row0 - 1) / 2;
+}
+// entry (a, b) of the band, row0 <= a, b <= a (diag) or b < a
+constexpr int64_t band_index(int64_t row0, int64_t a, int64_t b, bool diag) {
+    return (diag ? a * (a + 1) / 2 - row0 * (row0 + 1) / 2 : a * (a - 1) / 2 - row0 * (row0 - 1) / 2) + b;
+}
+constexpr int64_t band_tile_count(int64_t row0, int64_t row1, int tile) {
+    return ((row1 + tile - 1) / tile) * ((row1 + tile - 1) / tile + 1) / 2 - (row0 / tile) * (row0 / tile + 1) / 2;
+}
+// the band's tiles (x = tile row, y = tile column <= x) in the order the workgroups take them; Tile: int2 or anything like it
+template <class Tile>
+inline void band_tile_list(int64_t row0, int64_t row1, int tile, std::vector<Tile>& tiles) {
+    tiles.clear();
+    tiles.reserve((size_t)band_tile_count(row0, row1, tile));
+    for (int64_t ta = row0 / tile; ta < (row1 + tile - 1) / tile; ++ta)
+        for (int64_t tb = 0; tb <= ta; ++tb) { Tile t{}; t.x = (int)ta; t.y = (int)tb; tiles.push_back(t); }
 }
 
 // ---- linear association scan (assoc.hip, gpca_assoc.cpp) --------------------------------------------------------------------------

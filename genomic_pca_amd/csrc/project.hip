@@ -10,7 +10,7 @@
 //
 // Register-only, in the style of gemm_i8_simple.hip.  A wave covers 64 samples (not K2's 128): two sides x two 32-sample tiles x
 // four digit planes x 16 = 256 accumulator registers; with 128 samples it would be 512, the whole register file.
-#include "gemm_i8_common.h"
+#include "syrk_tile.h"
 
 namespace gpca {
 
@@ -50,7 +50,7 @@ __device__ __forceinline__ void prj_block(const PrjBuf& B, unsigned sh, int h, i
 #pragma unroll
     for (int w = 0; w < 4; ++w) {
         const unsigned x = p[4 * w] | (p[4 * w + 1] << 16), y = p[4 * w + 2] | (p[4 * w + 3] << 16);
-        mm[w] = ((((mask16 >> (4 * w)) & 0xfu) * 0x00204081u) & 0x01010101u);   // byte q = 1: row 4w + q is a model row
+        mm[w] = kept_bytes(mask16, w);   // byte q = 1: row 4w + q is a model row
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             const unsigned v = (unsigned)permb((int)y, (int)x, t ? 0x07050301u : 0x06040200u);   // rows 4w .. 4w + 3 of sample t
@@ -150,7 +150,7 @@ __global__ __launch_bounds__(256, 1) void k_project(const void* __restrict__ G, 
         prj_load<ND, LAZYB>(B2, rg, gvo, (4u * more + 2u) * L32, (uint32_t)ldr, rmk, 4 * more + 2, ra, rb, tvo, (4 * more + 2) * TKB);
         prj_block<PACKED, ND, LAZYB>(B3, sh, h, acc_a, acc_b, cnt, bad, any_missing, rb, tvo, 3 * TKB);
     }
-    // D[j][col]: j = (reg&3) + 8*(reg>>2) + 4*h, col = c -> sample n0 + 2c + t.  Exact integers as f64.
+    // D[j][col]: j = acc_row(0, reg, h), col = c -> sample n0 + 2c + t.  Exact integers as f64.
     double* ya = Ypa + (wchunk * Npad) * 32;
     double* yb = Ypb + (wchunk * Npad) * 32;
     constexpr int BITS = ND == 3 ? 8 : 7;
@@ -159,7 +159,7 @@ __global__ __launch_bounds__(256, 1) void k_project(const void* __restrict__ G, 
         const int64_t n = n0 + 2 * c + t;
 #pragma unroll
         for (int e = 0; e < 16; e += 2) {
-            const int j = (e & 3) + 8 * (e >> 2) + 4 * h;
+            const int j = acc_row(0, e, h);
             double2 o;
             o.x = combine_digits<BITS>(acc_a[t], e); o.y = combine_digits<BITS>(acc_a[t], e + 1);
             *reinterpret_cast<double2*>(ya + n * 32 + j) = o;

@@ -32,6 +32,21 @@ def _vp(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _band_entries(row0: int, row1: int, diag: bool) -> int:
+    """Entries of the rows [row0, row1) of the lower triangle packed row-major, with or without the diagonal (plan_math.h: band_entries)."""
+    return max(row1 * (row1 + 1) // 2 - row0 * (row0 + 1) // 2 if diag else row1 * (row1 - 1) // 2 - row0 * (row0 - 1) // 2, 0)
+
+
+def _band_to_full(band: np.ndarray, N: int, diag: bool, fill=0) -> np.ndarray:
+    """The full symmetric [N][N] (+ band's trailing dimensions) array of a packed band that holds every row; `fill` where the band has
+    no entry (the diagonal of a band without one)."""
+    il = np.tril_indices(N, 0 if diag else -1)
+    full = np.full((N, N) + band.shape[1:], fill, band.dtype)
+    full[il] = band
+    full.swapaxes(0, 1)[il] = band
+    return full
+
+
 @dataclass
 class QcConfig:
     """MicroarrayDataPreparerConfig thresholds; defaults = clap's effective ones (main.rs:545-560)."""
@@ -375,8 +390,7 @@ class GpcaEngine:
         sc = _lib.GRM_STANDARDIZED if scaling == "standardized" else _lib.GRM_CENTRED
         N = self.dims()[1]
         r0, r1 = (0, N) if rows is None else (int(rows[0]), int(rows[1]))
-        n0 = r0 * (r0 + 1) // 2
-        E = max(r1 * (r1 + 1) // 2 - n0, 0)
+        E = _band_entries(r0, r1, True)
         g = np.empty(max(E, 1), np.float64)
         npv = np.empty(max(E, 1), np.float32) if npairs else None
         self._chk(self._lib.gpca_grm(self._h, sc, r0, r1, _vp(g), _vp(npv)))
@@ -384,16 +398,8 @@ class GpcaEngine:
         npv = npv[:E] if npairs else None
         if rows is not None:
             return (g, npv) if npairs else g
-        il = np.tril_indices(N)
-        full = np.zeros((N, N), np.float64)
-        full[il] = g
-        full.T[il] = g
-        if not npairs:
-            return full
-        fp = np.zeros((N, N), np.float32)
-        fp[il] = npv
-        fp.T[il] = npv
-        return full, fp
+        full = _band_to_full(g, N, True)
+        return (full, _band_to_full(npv, N, True)) if npairs else full
 
     def king(self, rows: Optional[Tuple[int, int]] = None, counts: bool = False):
         """KING-robust kinship of the kept rows (gpca_king).  rows = (row0, row1): rows [row0, row1) of the STRICTLY lower triangle packed
@@ -402,7 +408,7 @@ class GpcaEngine:
         int32 counts NSNP, HETHET, IBS0 per pair ([pairs][3], or [N][N][3] with zeros on the diagonal)."""
         N = self.dims()[1]
         r0, r1 = (0, N) if rows is None else (int(rows[0]), int(rows[1]))
-        E = max(r1 * (r1 - 1) // 2 - r0 * (r0 - 1) // 2, 0)
+        E = _band_entries(r0, r1, False)
         k = np.empty(max(E, 1), np.float64)
         cnt = np.empty((max(E, 1), 3), np.int32) if counts else None
         self._chk(self._lib.gpca_king(self._h, r0, r1, _vp(k), _vp(cnt)))
@@ -410,16 +416,8 @@ class GpcaEngine:
         cnt = cnt[:E] if counts else None
         if rows is not None:
             return (k, cnt) if counts else k
-        il = np.tril_indices(N, -1)
-        full = np.full((N, N), 0.5, np.float64)
-        full[il] = k
-        full.T[il] = k
-        if not counts:
-            return full
-        fc = np.zeros((N, N, 3), np.int32)
-        fc[il] = cnt
-        fc.transpose(1, 0, 2)[il] = cnt
-        return full, fc
+        full = _band_to_full(k, N, False, fill=0.5)
+        return (full, _band_to_full(cnt, N, False)) if counts else full
 
     def ld_window(self, win_end, wmax: Optional[int] = None, rows: Optional[Tuple[int, int]] = None, threshold: Optional[float] = None,
                   r2: bool = True, counts: bool = False):
@@ -486,7 +484,7 @@ class GpcaEngine:
         shares no valid SNP.  nsnp=True also returns the int32 count of SNPs valid in both samples, in the same shape."""
         N, V, t = self._pcr_args(pcs, train)
         r0, r1 = (0, N) if rows is None else (int(rows[0]), int(rows[1]))
-        E = max(r1 * (r1 + 1) // 2 - r0 * (r0 + 1) // 2, 0)
+        E = _band_entries(r0, r1, True)
         k = np.empty(max(E, 1), np.float64)
         cnt = np.empty(max(E, 1), np.int32) if nsnp else None
         self._chk(self._lib.gpca_pcrelate(self._h, _vp(V), V.shape[1], _vp(t), float(maf_bound), r0, r1, _vp(k), _vp(cnt)))
@@ -494,16 +492,8 @@ class GpcaEngine:
         cnt = cnt[:E] if nsnp else None
         if rows is not None:
             return (k, cnt) if nsnp else k
-        il = np.tril_indices(N)
-        full = np.zeros((N, N), np.float64)
-        full[il] = k
-        full.T[il] = k
-        if not nsnp:
-            return full
-        fc = np.zeros((N, N), np.int32)
-        fc[il] = cnt
-        fc.T[il] = cnt
-        return full, fc
+        full = _band_to_full(k, N, True)
+        return (full, _band_to_full(cnt, N, True)) if nsnp else full
 
     @staticmethod
     def _assoc_design(covar, include, N):

@@ -1,8 +1,8 @@
 // Extent audit of the PC-Relate host arithmetic (genomic_pca_amd/csrc/plan_math.h, the pcr_* functions): for kept-row counts, sample
-// counts, coordinate counts and bands at the tile edges and at their limits, every writer of pcrelate.hip stays inside the buffer
-// gpca_pcrelate.cpp allocates for it, the tiles cover every entry of the band exactly once, the stages and flush groups cover the kept
-// rows once, and the staged reads stay inside a row's pitch.  Restates the kernels' index arithmetic on the host; includes the header
-// the engine itself uses.
+// counts and coordinate counts at the tile edges and at their limits, every writer of pcrelate.hip stays inside the buffer
+// gpca_pcrelate.cpp allocates for it, the stages and flush groups cover the kept rows once, and the staged reads stay inside a row's
+// pitch.  Restates the kernels' index arithmetic on the host; includes the header the engine itself uses.  (The band -- entries,
+// indices, tiles -- is audited with GRM's and KING's in band_plan_audit.cpp.)
 #include "plan_math.h"
 
 #include <cstdio>
@@ -56,27 +56,6 @@ static void audit_samples(int64_t N, int P) {
     EXPECT(last + 4 <= ld8 && last / 4 < ld2, "staged read past the pitch N=%lld", (long long)N);
 }
 
-// the band: entries, tiles, and the tile that owns an entry
-static void audit_band(int64_t N, int64_t row0, int64_t row1) {
-    const int64_t E = pcr_band_entries(row0, row1);
-    EXPECT(pcr_band_index(row0, row0, 0) == 0 && pcr_band_index(row0, row1 - 1, row1 - 1) == E - 1, "band ends row0=%lld row1=%lld", (long long)row0, (long long)row1);
-    const int64_t t0 = row0 / kPcrTile, t1 = (row1 + kPcrTile - 1) / kPcrTile;
-    int64_t nt = 0;
-    for (int64_t ta = t0; ta < t1; ++ta) nt += ta + 1;
-    EXPECT(nt == pcr_tiles(row0, row1), "tiles row0=%lld row1=%lld", (long long)row0, (long long)row1);
-    for (int64_t a : {row0, (row0 + row1) / 2, row1 - 1})
-        for (int64_t b : {(int64_t)0, a / 2, a}) {
-            const int64_t ta = a / kPcrTile, tb = b / kPcrTile;
-            EXPECT(ta >= t0 && ta < t1 && tb <= ta, "entry (%lld, %lld) in no tile", (long long)a, (long long)b);
-            // the wave of the tile that holds it: sub-tile (wa, wb), skipped only above the diagonal of a diagonal tile
-            const int64_t wa = (a % kPcrTile) / 32, wb = (b % kPcrTile) / 32;
-            EXPECT(!(ta == tb && wb > wa), "entry (%lld, %lld) in a skipped sub-tile", (long long)a, (long long)b);
-            const int64_t ix = pcr_band_index(row0, a, b);
-            EXPECT(ix >= 0 && ix < E, "index (%lld, %lld)", (long long)a, (long long)b);
-        }
-    EXPECT(row1 <= N, "band inside the samples");
-}
-
 int main() {
     static_assert(kPcrThreads == 4 * kPcrTile && kPcrStageRows == 16, "staging map: 2 sides x 128 samples x 2 row halves of 8");
     std::mt19937_64 rng(11);
@@ -87,12 +66,6 @@ int main() {
         for (int64_t K : Ks) audit_rows(K, P);
         for (int64_t N : Ns) audit_samples(N, P);
     }
-    for (int64_t N : Ns)
-        for (int t = 0; t < 40; ++t) {
-            int64_t r0 = t == 0 ? 0 : (int64_t)(rng() % (uint64_t)N), r1 = t == 0 ? N : r0 + 1 + (int64_t)(rng() % (uint64_t)(N - r0));
-            for (int64_t e0 : {r0, r0 / kPcrTile * kPcrTile}) audit_band(N, e0, r1);
-            audit_band(N, r0, r0 + 1);
-        }
     printf("pcrelate_plan_audit: %lld checks, %lld failures\n", g_checks, g_fail);
     return g_fail ? 1 : 0;
 }

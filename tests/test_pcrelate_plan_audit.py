@@ -1,10 +1,10 @@
 """CPU-only: the extent audit of the PC-Relate host arithmetic (the pcr_* functions of genomic_pca_amd/csrc/plan_math.h).
 
 tests/cpp/pcrelate_plan_audit.cpp includes the header gpca_pcrelate.cpp sizes its launches and buffers with and checks, over a sweep of
-(K, N, P, band) -- kept rows up to 2^31 - 1, samples up to 500 000, every P from 0 to 32, bands at the tile edges and 300 seeded random
-values per axis -- that the grouped and row-major coefficient buffers, the design rows, the hat matrix and the invalid counts hold
-every index their readers and writers reach, that the stages and flush groups cover the kept rows once, that every entry of a band
-lies in a tile and sub-tile the kernel multiplies, and that no staged read leaves a row's pitch."""
+(K, N, P) -- kept rows up to 2^31 - 1, samples up to 500 000, every P from 0 to 32 and 300 seeded random values per axis -- that the
+grouped and row-major coefficient buffers, the design rows, the hat matrix and the invalid counts hold every index their readers and
+writers reach, that the stages and flush groups cover the kept rows once, and that no staged read leaves a row's pitch.  (The band
+geometry it shares with GRM and KING: test_band_plan_audit.py.)"""
 import os
 import subprocess
 
