@@ -1,10 +1,12 @@
 // Extent audit of the windowed-LD host arithmetic (genomic_pca_amd/csrc/plan_math.h, the ld_* functions): for band sizes, window widths and
 // sample counts at the tile edges and at their limits, every writer of ld.hip stays inside the buffer gpca_ld.cpp allocates for it, the
 // grid covers every slot of the band exactly once, and the staged reads stay inside a row's pitch.  Restates the kernels' index
-// arithmetic on the host; includes the header the engine itself uses.
+// arithmetic on the host; includes the header the engine itself uses.  With arguments `rows weff N` (any number of triples) it prints
+// the launch plan of each triple instead (tests/test_gpu_ld_exact.py holds its Python mirror of the plan to these lines).
 #include "plan_math.h"
 
 #include <cstdio>
+#include <cstdlib>
 #include <random>
 #include <vector>
 
@@ -71,7 +73,22 @@ static void audit_samples(int64_t N, int64_t nblocks) {
     EXPECT((N + 15) / 16 * 16 <= ld8 && (N + 15) / 16 * 4 <= ld2, "k_ld_vec read past the pitch N=%lld", (long long)N);
 }
 
-int main() {
+// print mode: the launch plan of k_ld for each (rows, weff, N) triple of the command line, one line per triple, from the header's own
+// functions: workgroups, column chunks, sample stages, stages per split, splits, and whether the sums meet in plain stores or atomics
+static int print_plans(int argc, char** argv) {
+    if ((argc - 1) % 3 != 0) { fprintf(stderr, "usage: ld_plan_audit [rows weff N]...\n"); return 2; }
+    for (int a = 1; a + 2 < argc; a += 3) {
+        const int64_t rows = atoll(argv[a]), weff = atoll(argv[a + 1]), N = atoll(argv[a + 2]);
+        const int64_t nch = ld_col_chunks(weff), nb = ld_row_blocks(rows) * nch, nst = ld_stages(N);
+        const int64_t per = ld_stages_per_split(nb, nst), S = ld_splits(nb, nst);
+        printf("%lld %lld %lld: %lld %lld %lld %lld %lld %s\n", (long long)rows, (long long)weff, (long long)N, (long long)nb, (long long)nch,
+               (long long)nst, (long long)per, (long long)S, S > 1 ? "atomic" : "plain");
+    }
+    return 0;
+}
+
+int main(int argc, char** argv) {
+    if (argc > 1) return print_plans(argc, argv);
     static_assert(kLdRows * (kLdStage / 16) % kLdThreads == 0 && (kLdRows + kLdCols) * (kLdStage / 16) % kLdThreads == 0, "staging map covers the stage");
     static_assert(kLdCols / 32 == kLdThreads / 64, "one column tile per wave");
     std::mt19937_64 rng(7);
