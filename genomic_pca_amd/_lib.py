@@ -117,6 +117,8 @@ PROTOTYPES = {
     "gpca_device_eigh_desc": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "gpca_device_orth": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
     "gpca_device_tail": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
+    "gpca_device_sketch": (C.c_int, [_H, C.c_int32, C.c_uint64, C.c_void_p, C.POINTER(C.c_int32)]),
+    "gpca_device_power": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gpca_standardize_block": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "gpca_num_pca_snps": (C.c_int64, [_H]),
     "gpca_num_qc_samples": (C.c_int64, [_H]),

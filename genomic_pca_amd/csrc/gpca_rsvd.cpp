@@ -681,6 +681,29 @@ static int ensure_child(gpca_handle* h) {
     return GPCA_OK;
 }
 
+// a streamed power iteration reads every panel once (stage_power_fused) unless gpca_stream_set_fused(h, 0) or a K1 without the abs-max epilogue
+static inline bool power_fused(const gpca_handle* h) {
+    return h->sm.on && h->sm.fused && (h->storage == GPCA_STORE_2BIT || !h->simple_kernels || narrow_shape(h));   // (k_gq_i8 has no abs-max epilogue)
+}
+// 1. sketch: T' = r o Omega, c = b^T Omega (the partials of c; stage_sum_c folds them)
+static int stage_sketch(gpca_handle* h, uint64_t seed) {
+    const int l = h->l, L = h->L;
+    ScopedTimer t(h, "omega", 0.0, (double)h->M * L * 4.0);
+    if (h->precision == GPCA_PREC_I8_EXACT) {
+        // the digit planes of T' leave k_omega directly, scaled by the analytic bound 6.67 * max r (no f32 T', no quantisation pass)
+        if (!h->rmax_valid) {
+            HIPCHK(hipMemsetAsync(h->d_rmax, 0, 4, h->st));
+            launch_max_f32(h->st, h->d_r, h->Mpad, h->d_rmax);
+            HIPCHK(hipGetLastError());
+            h->rmax_valid = true;
+        }
+        launch_omega_planes(h->st, h->M, h->Mpad, l, L, h->snp_offset, seed, h->d_r, h->d_b, h->d_cpart, h->dTd, h->d_rmax, h->d_tscale, h->d_tinv, h->nd, h->d_row_ids);
+        h->apart_valid = false;
+    } else launch_omega(h->st, h->M, h->Mpad, l, L, h->snp_offset, seed, h->d_r, h->d_b, h->dTb, h->d_cpart, nullptr, 1, h->d_row_ids);
+    HIPCHK(hipGetLastError());
+    return GPCA_OK;
+}
+
 extern "C" int gpca_rsvd(gpca_handle* h, int32_t k, int32_t oversample, int32_t power_iters, uint64_t seed) {
     if (!h) return GPCA_ERR_BAD_ARG;
     LOCK(h);
@@ -710,7 +733,7 @@ extern "C" int gpca_rsvd(gpca_handle* h, int32_t k, int32_t oversample, int32_t 
     }
     bool agreement_pending = mr;
     int lrc = GPCA_OK;
-    const int l = h->l, L = h->L;
+    const int L = h->L;
     // ... and from here on a rank-local failure is remembered (lrc) while the rank keeps entering every exchange of the call, so
     // that its peers are not left inside a collective; the second agreement below returns the failure on every rank.
 #define EXCHANGE(buf, count) do { \
@@ -720,30 +743,13 @@ extern "C" int gpca_rsvd(gpca_handle* h, int32_t k, int32_t oversample, int32_t 
             if (arc_ != GPCA_OK) { (void)hipStreamSynchronize(h->st); return arc_; }   /* a peer's preflight failed: nobody enters the exchange */ \
         } \
         const int xrc_ = allreduce_f64(h, (buf), (count)); if (xrc_ != GPCA_OK) return xrc_; } while (0)
-    auto omega = [&]() -> int {
-        // 1. sketch: T' = r o Omega, c = b^T Omega
-        ScopedTimer t(h, "omega", 0.0, (double)h->M * L * 4.0);
-        if (h->precision == GPCA_PREC_I8_EXACT) {
-            // the digit planes of T' leave k_omega directly, scaled by the analytic bound 6.67 * max r (no f32 T', no quantisation pass)
-            if (!h->rmax_valid) {
-                HIPCHK(hipMemsetAsync(h->d_rmax, 0, 4, h->st));
-                launch_max_f32(h->st, h->d_r, h->Mpad, h->d_rmax);
-                HIPCHK(hipGetLastError());
-                h->rmax_valid = true;
-            }
-            launch_omega_planes(h->st, h->M, h->Mpad, l, L, h->snp_offset, seed, h->d_r, h->d_b, h->d_cpart, h->dTd, h->d_rmax, h->d_tscale, h->d_tinv, h->nd, h->d_row_ids);
-            h->apart_valid = false;
-        } else launch_omega(h->st, h->M, h->Mpad, l, L, h->snp_offset, seed, h->d_r, h->d_b, h->dTb, h->d_cpart, nullptr, 1, h->d_row_ids);
-        HIPCHK(hipGetLastError());
-        return GPCA_OK;
-    };
-    LOCAL(omega());
+    LOCAL(stage_sketch(h, seed));
     LOCAL(stage_sum_c(h, omega_num_parts(h->Mpad)));
     LOCAL(stage_AtT_local(h, h->precision == GPCA_PREC_I8_EXACT));                       // Y = A^T Omega (exact path: planes already made)
     EXCHANGE(h->dY, h->N * (int64_t)L);
     LOCAL(stage_orth(h, power_iters == 0 ? 2 : 1));   // (the last basis before the projection gets CholeskyQR2, the earlier ones one round)
     // 2. power iterations
-    const bool fused = h->sm.on && h->sm.fused && (h->storage == GPCA_STORE_2BIT || !h->simple_kernels || narrow_shape(h));   // (k_gq_i8 has no abs-max epilogue)
+    const bool fused = power_fused(h);
     for (int it = 0; it < power_iters; ++it) {
         if (fused) LOCAL(stage_power_fused(h));
         else { LOCAL(stage_AQ(h, 1)); LOCAL(stage_AtT_local(h)); }
@@ -1072,5 +1078,63 @@ extern "C" int gpca_device_tail(gpca_handle* h, const double* Q, const float* B,
     const double n_eff = h->d_smask ? (double)h->n_smask : (double)N;
     CHK(call_tail(h, zmode, n_eff - 1.0, h->dT, GPCA_OK));
     h->have_rsvd = true; h->loadings_valid = true; h->rsvd_on_child = false;
+    return GPCA_OK;
+}
+
+// ---- test hooks (GPU): the two GEMM passes gpca_transform cannot reach, through the product's own stage functions --------------------
+// The sketch Y = A^T Omega of gpca_rsvd(l, 0, .., seed) before any exchange: the rank-local dY, compacted to l columns.
+extern "C" int gpca_device_sketch(gpca_handle* h, int32_t l, uint64_t seed, double* Y, int32_t* on_child) {
+    if (!h || !Y || !on_child || l < 1) return GPCA_ERR_BAD_ARG;
+    LOCK(h);
+    *on_child = 0;
+    if (wants_child(h, l, 0) && ensure_child(h) == GPCA_OK) {      // (as gpca_rsvd: the kept rows gathered into a matrix of their own)
+        const int rc = gpca_device_sketch(h->child, l, seed, Y, on_child);
+        if (rc != GPCA_OK) h->err = h->child->err;
+        h->have_rsvd = false;
+        *on_child = 1;
+        return rc;
+    }
+    CHK(rsvd_preflight(h, l, 0, 0));
+    CHK(stage_sketch(h, seed));
+    CHK(stage_sum_c(h, omega_num_parts(h->Mpad)));
+    CHK(stage_AtT_local(h, h->precision == GPCA_PREC_I8_EXACT));
+    const int L = h->L;
+    const int64_t N = h->N;
+    std::vector<double> buf((size_t)N * L);
+    HIPCHK(hipMemcpyAsync(buf.data(), h->dY, buf.size() * 8, hipMemcpyDeviceToHost, h->st));
+    HIPCHK(hipStreamSynchronize(h->st));
+    for (int64_t n = 0; n < N; ++n) for (int c = 0; c < l; ++c) Y[(size_t)n * l + c] = buf[(size_t)n * L + c];
+    return GPCA_OK;
+}
+
+// One power iteration of gpca_rsvd on a caller's sketch: CholeskyQR2 of Yin, then Y = A^T (A Q) as the call chooses it for this handle.
+extern "C" int gpca_device_power(gpca_handle* h, const double* Yin, int32_t l, double* Q, float* Tq, double* c, double* Yout) {
+    if (!h || !Yin || !Q || !Tq || !c || !Yout || l < 1) return GPCA_ERR_BAD_ARG;
+    LOCK(h);
+    if (multi_rank(h)) return fail(h, GPCA_ERR_STATE, "gpca_device_power: needs an unsharded handle");
+    if (h->precision != GPCA_PREC_I8_EXACT)      // (on GPCA_PREC_F32_MFMA K1 writes the scaled operand blocked into dTb: there is no row-major T' to return)
+        return fail(h, GPCA_ERR_STATE, "gpca_device_power: needs GPCA_PREC_I8_EXACT");
+    CHK(rsvd_preflight(h, l, 0, 1));
+    const int L = h->L;
+    const int64_t N = h->N, M = h->M;
+    std::vector<double> buf((size_t)N * L, 0.0);
+    for (int64_t n = 0; n < N; ++n) for (int j = 0; j < l; ++j) buf[(size_t)n * L + j] = Yin[(size_t)n * l + j];
+    HIPCHK(hipMemcpyAsync(h->dY, buf.data(), buf.size() * 8, hipMemcpyHostToDevice, h->st));
+    HIPCHK(hipStreamSynchronize(h->st));
+    CHK(stage_orth(h, 2));
+    HIPCHK(hipMemcpyAsync(buf.data(), h->dY, buf.size() * 8, hipMemcpyDeviceToHost, h->st));
+    HIPCHK(hipStreamSynchronize(h->st));
+    for (int64_t n = 0; n < N; ++n) for (int j = 0; j < l; ++j) Q[(size_t)n * l + j] = buf[(size_t)n * L + j];
+    if (power_fused(h)) CHK(stage_power_fused(h));
+    else { CHK(stage_AQ(h, 1)); CHK(stage_AtT_local(h)); }
+    std::vector<float> tb((size_t)M * L);
+    double c64[kMaxSketch];
+    HIPCHK(hipMemcpyAsync(tb.data(), h->dT, tb.size() * 4, hipMemcpyDeviceToHost, h->st));
+    HIPCHK(hipMemcpyAsync(c64, h->d_c, sizeof(double) * L, hipMemcpyDeviceToHost, h->st));
+    HIPCHK(hipMemcpyAsync(buf.data(), h->dY, buf.size() * 8, hipMemcpyDeviceToHost, h->st));
+    HIPCHK(hipStreamSynchronize(h->st));
+    for (int64_t i = 0; i < M; ++i) for (int j = 0; j < l; ++j) Tq[(size_t)i * l + j] = tb[(size_t)i * L + j];
+    for (int64_t n = 0; n < N; ++n) for (int j = 0; j < l; ++j) Yout[(size_t)n * l + j] = buf[(size_t)n * L + j];
+    std::copy(c64, c64 + l, c);
     return GPCA_OK;
 }

@@ -262,6 +262,20 @@ GPCA_API int gpca_device_orth(gpca_handle* h, const double* Y, int32_t l, int32_
  * B V_k diag(1 / sv) (0 where sv = 0); zmode 1 (the tail of gpca_refine): Q^T Q = V diag(w) V^T, scores = Q V_k, loadings = B V_k.
  * Results through the getters (scores, singular values [l], eigenvalues = w / (samples - 1), loadings). */
 GPCA_API int gpca_device_tail(gpca_handle* h, const double* Q, const float* B, int32_t l, int32_t k, int32_t zmode);
+/* Test hook (GPU): the sketch Y = A^T Omega that opens gpca_rsvd(h, l, 0, .., seed) -- Omega into T' = r o Omega and c = b^T Omega (on
+ * GPCA_PREC_I8_EXACT straight into digit planes against the analytic column bound), the fold of c, K2 -- through the product's own
+ * stage functions and before any exchange: Y [N][l] is the rank-local result.  Runs on the compact child of the kept rows whenever
+ * gpca_rsvd would (*on_child = 1, else 0).  Resident and streamed handles, both precisions; a handle with an all-reduce hook is
+ * accepted (that is how a handle gets its snp_offset) and the hook is not called.  The results of an earlier gpca_rsvd are gone
+ * afterwards. */
+GPCA_API int gpca_device_sketch(gpca_handle* h, int32_t l, uint64_t seed, double* Y, int32_t* on_child);
+/* Test hook (GPU): one power iteration of gpca_rsvd on a caller's sketch Yin [N][l]: CholeskyQR2 (two rounds), then Y = A^T (A Q) as
+ * gpca_rsvd chooses it for this handle -- the fused one-read sweep on a streamed handle unless gpca_stream_set_fused(h, 0), otherwise
+ * K1 over all rows followed by K2 -- on the handle's own matrix (never the compact child).  Q [N][l]: the f64 basis; Tq [M][l]: T' =
+ * r o (A Q) in f32 as K2 reads it (rows QC dropped are zero); c [l]: b^T (A Q); Yout [N][l]: the new sketch.  Needs an unsharded handle on
+ * GPCA_PREC_I8_EXACT (GPCA_ERR_STATE otherwise: the f32 path keeps T' blocked, not row-major).
+ * The results of an earlier gpca_rsvd are gone afterwards. */
+GPCA_API int gpca_device_power(gpca_handle* h, const double* Yin, int32_t l, double* Q, float* Tq, double* c, double* Yout);
 /* Host helper, same branches as prepare.rs:1641-1745. */
 GPCA_API double gpca_hwe_chi_squared_p_value(uint64_t n_hom1, uint64_t n_het, uint64_t n_hom2);
 

@@ -52,9 +52,10 @@ zero_mu c is identically zero and the mutant must equal the model).
 Streamed handles accept gpca_set_standardization (it runs the stats pass over the panels first), so the streamed cases use both families.
 
 Not reached, and why: K2 inside the fused streamed power sweep (launch_accum_y_scaled / launch_finish_y_sum, stage_power_fused) and the
-sketch pass fed by launch_omega_planes are not reachable from gpca_transform; both stay under the oracle parity tests of
-test_gpu_parity.py and test_gpu_stream.py.  A fault common to every kernel AND the model (a wrong reading of DESIGN.md) is out of reach
-by construction.  On GPCA_PREC_F32_MFMA only gross defects show (see above).  K2 at one sample is refused by gpca_rsvd.
+sketch pass fed by launch_omega_planes are not reachable from gpca_transform; they are held the same way through two test hooks of their
+own, in test_gpu_fused_sweep.py (gpca_device_power) and test_gpu_sketch_pass.py (gpca_device_sketch).  A fault common to every kernel
+AND the model (a wrong reading of DESIGN.md) is out of reach by construction.  On GPCA_PREC_F32_MFMA only gross defects show (see above).
+K2 at one sample is refused by gpca_rsvd.
 
 Measured on one MI355X, the largest fraction of a bar over every case, sample and column (records, not thresholds; each test prints its
 own with -s):
