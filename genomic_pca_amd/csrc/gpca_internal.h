@@ -1,6 +1,6 @@
 #pragma once
 // Internals shared by the translation units of libgpca.so's host driver (gpca_api.cpp: lifecycle, QC statistics, pull API, exchange,
-// timings; gpca_residency.cpp: uploads, panel sources, out-of-core ring; gpca_rsvd.cpp: the randomized-PCA stages).  Nothing here is
+// timings; gpca_residency.cpp: uploads, panel sources, out-of-core ring; gpca_rsvd.cpp: the randomized-PCA stages; gpca_host_eigh.cpp, without this header: the host eigen pin).  Nothing here is
 // exported: the library is built with -fvisibility=hidden and only the extern "C" entry points of include/gpca.h carry GPCA_API.
 //
 // C ABI + host driver of the randomized-PCA engine (declared in include/gpca.h).
@@ -11,6 +11,7 @@
 // = 4 passes over the int8 matrix, 12*l flop per genotype.
 #include "../../include/gpca.h"
 #include "kernels.h"
+#include "k1_handoff.h"
 
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -172,9 +173,8 @@ struct gpca_handle {
     Gtt8Plan plan8{};
     // exact-integer path
     int8_t *dQd = nullptr, *dTd = nullptr;
-    bool c_fold_pending = false;     // K1's tail ran as launch_post_k1: the digit scale is made, c's second stage waits in d_scratch64 for the quantisation
-    double* d_apart = nullptr; size_t cap_apart = 0; bool apart_valid = false; int64_t apart_parts = 0;   // column abs-max partials of T' from the K1 epilogue
-    const double* apart_src[4] = {nullptr, nullptr, nullptr, nullptr};   // where the partials of each 32-column block sit (kMaxSketch / 32 blocks)
+    double* d_apart = nullptr; size_t cap_apart = 0;   // column abs-max partials of T' from the K1 epilogue
+    K1Handoff k1;                    // what the last K1 sweep left for the quantisation in front of K2 (k1_handoff.h)
     float* d_rmax = nullptr; bool rmax_valid = false;   // max_i r[i]: the sketch's digit scale is 6.67 * rmax (k_omega); recomputed when r changes
     double* d_amax_run = nullptr;    // [2][32] running column abs-max over the panels of a streamed K1 sweep
     double* d_yint = nullptr; size_t cap_yint = 0;   // [halves][N][32] integer partial sums of a streamed K2 sweep

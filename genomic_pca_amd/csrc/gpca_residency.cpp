@@ -618,7 +618,7 @@ extern "C" int gpca_copy_rows(gpca_handle* dst, gpca_handle* src, int64_t row0, 
         // depends on the rows is marked stale, the rows past the block are zeroed (pad rows: zero genotypes, r = b = 0)
         HIPCHK(hipStreamSynchronize(dst->st));
         dst->M = rows; dst->Mpad = new_pad;
-        dst->have_stats = false; dst->have_rsvd = false; dst->n_pca = 0; dst->pca_rows.clear(); dst->flags = 0; dst->apart_valid = false; dst->rmax_valid = false;
+        dst->have_stats = false; dst->have_rsvd = false; dst->n_pca = 0; dst->pca_rows.clear(); dst->flags = 0; dst->k1.reset(); dst->rmax_valid = false;
         drop_child(dst);
         free_eigensnp(dst);
         if (dst->d_r && dst->cap_stats_pad < new_pad) free_stats(dst);      // (allocated for a smaller block: the next stats pass re-makes them)

@@ -1,130 +1,12 @@
-// The randomized-PCA driver: host eigen step, the stages over the resident matrix or the streamed panels, gpca_rsvd, result getters,
-// gpca_transform (include/gpca.h section a5/a6).
+// The randomized-PCA driver: the stages over the resident matrix or the streamed panels, gpca_rsvd, result getters, gpca_transform
+// (include/gpca.h section a5/a6), the EigenSNP stage calls and the GPU test hooks.  The eigen step runs on the device (small_eig.hip);
+// its host pin is gpca_host_eigh.cpp.
 #include "gpca_internal.h"
 
 using namespace gpca;
 
-// ---- small dense (host, f64) ----------------------------------------------------------------------------------
-// Symmetric eigenproblem of the l x l Gram of the projection (l <= 64): Householder tridiagonalisation + implicit QL
-// (the EISPACK tred2 / tql2 pair).  It replaced a cyclic Jacobi solver: at l = 30 Jacobi's ~8 sweeps of 435 rotations kept
-// the stream idle for ~190 us per call while the host worked; this pair needs ~20 us.  (The parity checker of tests/ uses LAPACK,
-// oracle/oracle.py:rsvd -- no code in common.)  A: symmetric, row-major, destroyed; V: eigenvectors in columns; w: eigenvalues,
-// sorted descending.
-static void tred2(int n, double* V, double* d, double* e) {
-    for (int j = 0; j < n; ++j) d[j] = V[(n - 1) * n + j];
-    for (int i = n - 1; i > 0; --i) {
-        double scale = 0.0, h = 0.0;
-        for (int k = 0; k < i; ++k) scale += std::fabs(d[k]);
-        if (scale == 0.0) {
-            e[i] = d[i - 1];
-            for (int j = 0; j < i; ++j) { d[j] = V[(i - 1) * n + j]; V[i * n + j] = 0.0; V[j * n + i] = 0.0; }
-        } else {
-            for (int k = 0; k < i; ++k) { d[k] /= scale; h += d[k] * d[k]; }
-            double f = d[i - 1];
-            double g = std::sqrt(h);
-            if (f > 0) g = -g;
-            e[i] = scale * g; h -= f * g; d[i - 1] = f - g;
-            for (int j = 0; j < i; ++j) e[j] = 0.0;
-            for (int j = 0; j < i; ++j) {
-                f = d[j]; V[j * n + i] = f; g = e[j] + V[j * n + j] * f;
-                for (int k = j + 1; k <= i - 1; ++k) { g += V[k * n + j] * d[k]; e[k] += V[k * n + j] * f; }
-                e[j] = g;
-            }
-            f = 0.0;
-            for (int j = 0; j < i; ++j) { e[j] /= h; f += e[j] * d[j]; }
-            const double hh = f / (h + h);
-            for (int j = 0; j < i; ++j) e[j] -= hh * d[j];
-            for (int j = 0; j < i; ++j) {
-                f = d[j]; g = e[j];
-                for (int k = j; k <= i - 1; ++k) V[k * n + j] -= (f * e[k] + g * d[k]);
-                d[j] = V[(i - 1) * n + j]; V[i * n + j] = 0.0;
-            }
-        }
-        d[i] = h;
-    }
-    for (int i = 0; i < n - 1; ++i) {        // accumulate the transformations
-        V[(n - 1) * n + i] = V[i * n + i]; V[i * n + i] = 1.0;
-        const double h = d[i + 1];
-        if (h != 0.0) {
-            for (int k = 0; k <= i; ++k) d[k] = V[k * n + (i + 1)] / h;
-            for (int j = 0; j <= i; ++j) {
-                double g = 0.0;
-                for (int k = 0; k <= i; ++k) g += V[k * n + (i + 1)] * V[k * n + j];
-                for (int k = 0; k <= i; ++k) V[k * n + j] -= g * d[k];
-            }
-        }
-        for (int k = 0; k <= i; ++k) V[k * n + (i + 1)] = 0.0;
-    }
-    for (int j = 0; j < n; ++j) { d[j] = V[(n - 1) * n + j]; V[(n - 1) * n + j] = 0.0; }
-    V[(n - 1) * n + (n - 1)] = 1.0; e[0] = 0.0;
-}
-static void tql2(int n, double* V, double* d, double* e) {
-    for (int i = 1; i < n; ++i) e[i - 1] = e[i];
-    e[n - 1] = 0.0;
-    double f = 0.0, tst1 = 0.0;
-    const double eps = 2.220446049250313e-16;
-    for (int l = 0; l < n; ++l) {
-        tst1 = std::max(tst1, std::fabs(d[l]) + std::fabs(e[l]));
-        int m = l;
-        while (m < n - 1 && std::fabs(e[m]) > eps * tst1) ++m;     // e[n-1] = 0 ends the search
-        if (m > l) {
-            int iter = 0;
-            do {
-                ++iter;
-                double g = d[l];
-                double p = (d[l + 1] - g) / (2.0 * e[l]);
-                double r = std::hypot(p, 1.0);
-                if (p < 0) r = -r;
-                d[l] = e[l] / (p + r); d[l + 1] = e[l] * (p + r);
-                const double dl1 = d[l + 1];
-                double h = g - d[l];
-                for (int i = l + 2; i < n; ++i) d[i] -= h;
-                f += h;
-                p = d[m];
-                double c = 1.0, c2 = c, c3 = c, s = 0.0, s2 = 0.0;
-                const double el1 = e[l + 1];
-                for (int i = m - 1; i >= l; --i) {
-                    c3 = c2; c2 = c; s2 = s;
-                    g = c * e[i]; h = c * p;
-                    r = std::hypot(p, e[i]);
-                    e[i + 1] = s * r; s = e[i] / r; c = p / r;
-                    p = c * d[i] - s * g;
-                    d[i + 1] = h + s * (c * g + s * d[i]);
-                    for (int k = 0; k < n; ++k) {
-                        h = V[k * n + i + 1];
-                        V[k * n + i + 1] = s * V[k * n + i] + c * h;
-                        V[k * n + i] = c * V[k * n + i] - s * h;
-                    }
-                }
-                p = -s * s2 * c3 * el1 * e[l] / dl1;
-                e[l] = s * p; d[l] = c * p;
-            } while (std::fabs(e[l]) > eps * tst1 && iter < 200);
-        }
-        d[l] += f; e[l] = 0.0;
-    }
-}
-static void host_eigh_desc(std::vector<double>& A, std::vector<double>& V, std::vector<double>& w, int n) {
-    std::vector<double> e((size_t)n);
-    V = A;
-    if (n == 1) { w[0] = A[0]; V[0] = 1.0; return; }
-    tred2(n, V.data(), w.data(), e.data());
-    tql2(n, V.data(), w.data(), e.data());
-    for (int i = 0; i < n - 1; ++i) {        // selection sort, descending
-        int m = i;
-        for (int j = i + 1; j < n; ++j) if (w[j] > w[m]) m = j;
-        if (m != i) { std::swap(w[i], w[m]); for (int k = 0; k < n; ++k) std::swap(V[k * n + i], V[k * n + m]); }
-    }
-}
-// test hook (host only, no GPU): eigen-decomposition of a symmetric n x n row-major matrix, eigenvalues descending
-extern "C" int gpca_host_eigh_desc(const double* a_sym, int32_t n, double* w, double* v) {
-    if (!a_sym || !w || !v || n < 1 || n > kMaxSketch) return GPCA_ERR_BAD_ARG;
-    std::vector<double> A(a_sym, a_sym + (size_t)n * n), V((size_t)n * n), W((size_t)n);
-    host_eigh_desc(A, V, W, n);
-    std::copy(W.begin(), W.end(), w); std::copy(V.begin(), V.end(), v);
-    return GPCA_OK;
-}
-
-// test hook (GPU): the device solver of gpca_rsvd (small_eig.hip) on a caller's symmetric n x n matrix, same conventions as above
+// test hook (GPU): the device solver of gpca_rsvd (small_eig.hip) on a caller's symmetric n x n matrix, same conventions as the host
+// pin (gpca_host_eigh.cpp): row-major, eigenvalues descending, eigenvectors in columns
 extern "C" int gpca_device_eigh_desc(gpca_handle* h, const double* a_sym, int32_t n, double* w, double* v) {
     if (!h || !a_sym || !w || !v || n < 1 || n > kMaxSketch) return GPCA_ERR_BAD_ARG;
     LOCK(h);
@@ -159,7 +41,6 @@ static int stage_sum_c(gpca_handle* h, int64_t parts) {
     return GPCA_OK;
 }
 
-
 // At most 256 samples on int8 rows (configs[2]'s shape class): the narrow kernels (gemm_i8.hip: k_gq_n, k_gtt_i8<.., NARROW>)
 static inline bool narrow_shape(const gpca_handle* h) {
     return h->narrow_ok && h->precision == GPCA_PREC_I8_EXACT && h->storage == GPCA_STORE_INT8 && h->N <= kNarrowSamples;
@@ -174,6 +55,33 @@ static inline Gtt8Plan k2_plan(const gpca_handle* h, int64_t rows_pad) {
 }
 
 static inline GqPlan k1_plan(const gpca_handle* h, int64_t rows_pad) { return gq_plan(rows_pad, h->gq_waves_target); }
+// this handle's K1 leaves per-wave column abs-max partials of T' in d_apart: every kernel of k1_panel but k_gq_i8, which has no such epilogue
+static inline bool k1_leaves_absmax(const gpca_handle* h) {
+    return h->storage == GPCA_STORE_2BIT || !h->simple_kernels || narrow_shape(h);
+}
+// a streamed power iteration reads every panel once (stage_power_fused) unless gpca_stream_set_fused(h, 0) or a K1 without the abs-max epilogue
+static inline bool power_fused(const gpca_handle* h) { return h->sm.on && h->sm.fused && k1_leaves_absmax(h); }
+
+// The exact-path kernels are 32 columns wide: a sketch of L columns runs as L / 32 column halves over the same genotypes.  What belongs
+// to half hf in the handle's workspace (the strides are stated here only); col = its first column in the row-major dT and dY.
+struct HalfView {
+    int col;
+    int8_t *Qd, *Td;                      // digit planes of Q [ldg / 32 blocks] and of T' [Mpad / 32 blocks]
+    double *qscale, *qinv, *tscale, *tinv, *s64, *c;
+    float *s32, *cpart;                   // cpart: the partials of c, one per 32-row unit x 32 columns
+    double *apart, *cscratch, *yint;      // per-wave abs-max partials of one K1 launch; launch_post_k1's slices; [N][32] sums of a streamed K2 sweep
+};
+static inline HalfView half_view(const gpca_handle* h, int hf) {
+    const size_t planes = (size_t)32 * kDigits, f = (size_t)hf;
+    HalfView v;
+    v.col = 32 * hf;
+    v.Qd = h->dQd + f * (size_t)h->ldg * planes; v.Td = h->dTd + f * (size_t)h->Mpad * planes;
+    v.qscale = h->d_qscale + v.col; v.qinv = h->d_qinv + v.col; v.tscale = h->d_tscale + v.col; v.tinv = h->d_tinv + v.col;
+    v.s64 = h->d_s64 + v.col; v.c = h->d_c + v.col; v.s32 = h->d_s32 + v.col; v.cpart = h->d_cpart + f * (size_t)h->Mpad;
+    v.apart = h->d_apart + f * (size_t)h->gqplan.waves * 32; v.cscratch = h->d_scratch64 + f * (size_t)kPostK1Scratch;
+    v.yint = h->d_yint ? h->d_yint + f * (size_t)h->N * 32 : nullptr;      // (streamed handles only)
+    return v;
+}
 
 // K2 of one 32-column half over one panel: Ypart = (digit planes of T')^T G, exact integers
 static int k2_panel(gpca_handle* h, const PanelView& pv, const int8_t* Td_half, const Gtt8Plan& plan) {
@@ -194,26 +102,43 @@ static int k2_panel(gpca_handle* h, const PanelView& pv, const int8_t* Td_half, 
     return GPCA_OK;
 }
 
+// K1 of 32-column half hf over one panel: the panel's rows of T = A Q into dT (scale_out: T' = r o T, the units' shares of c into cpart
+// and -- every kernel but k_gq_i8 -- the waves' column abs-max into apart)
+static int k1_panel(gpca_handle* h, const PanelView& pv, int hf, const GqPlan& plan, int scale_out) {
+    const HalfView v = half_view(h, hf);
+    const int L = h->L;
+    const float* rr = h->d_r + pv.row0; const float* bb = h->d_b + pv.row0;
+    float* Th = h->dT + (size_t)pv.row0 * L + v.col;
+    float* cp = v.cpart + (size_t)pv.row0;          // (row0 / 32) units x 32 columns
+    int e = 0; const char* kernel = "";
+    if (!k1_leaves_absmax(h)) launch_gq_i8(h->st, pv.g8, h->ld8, plan, h->N, v.Qd, v.qscale, rr, bb, v.s32, Th, cp, scale_out, L, h->ko);   // the register-only reference kernel on int8 rows
+    else if (h->storage == GPCA_STORE_2BIT) launch_gq_2bit(h->st, pv.g2, h->ld2, plan, h->ldg, v.Qd, v.qscale, rr, bb, v.s32, Th, cp, v.apart, scale_out, h->nd, L);
+    else if (narrow_shape(h)) { kernel = "k_gq_n"; e = launch_gq_n(h->st, pv.g8, h->ld8, plan, h->N, v.Qd, v.qscale, rr, bb, v.s32, Th, cp, v.apart, scale_out, L); }
+    else { kernel = "k_gq_d"; e = launch_gq_d(h->st, pv.g8, h->ld8, plan, h->ldg, v.Qd, v.qscale, rr, bb, v.s32, Th, cp, v.apart, scale_out, L, h->ko); }
+    if (e != 0) return fail(h, GPCA_ERR_HIP, std::string(kernel) + " launch failed (hip error " + std::to_string(e) + ")");
+    HIPCHK(hipGetLastError());
+    return GPCA_OK;
+}
+
 // Y = A^T T  (T' = r o T already in dT, c = b^T T in d_c); rank-local part, the exchange of Y follows in the caller
 static int stage_AtT_local(gpca_handle* h, bool planes_ready = false) {
     const double elems = (double)h->M * (double)h->N;
     if (h->precision == GPCA_PREC_I8_EXACT) {
         // T' (f32 row-major in dT) -> digit planes; exact int8 product; integer partials summed exactly in f64.
-        // The kernels are 32 columns wide: a 64-column sketch (32 < l <= 64) runs as two column halves over the same genotypes.
         const int L = h->L, halves = L / 32;
-        const size_t td_half = (size_t)h->Mpad * 32 * kDigits;
+        const K1Handoff k1 = h->k1.take();      // (consumed: whatever happens below, the next quantisation starts from none)
         for (int hf = 0; hf < halves && !planes_ready; ++hf) {      // (planes_ready: the sketch's digit planes came straight out of k_omega)
-            const float* Th = h->dT + 32 * hf;
-            double* tsc = h->d_tscale + 32 * hf; double* tin = h->d_tinv + 32 * hf;
-            if (h->c_fold_pending) launch_quantize_f32_cfold(h->st, Th, h->Mpad, h->Mpad, tin, h->dTd + hf * td_half, 0, h->nd, L, h->d_scratch64 + (size_t)hf * kPostK1Scratch,
-                                                             post_k1_slices(h->Mpad / 32), h->d_c + 32 * hf);      // (scale by launch_post_k1; c's second stage rides along)
-            else if (h->apart_valid) launch_quantize_f32_premax(h->st, Th, h->Mpad, h->Mpad, h->apart_src[hf], h->apart_parts, tsc, tin, h->dTd + hf * td_half, 0, h->nd, L);
-            else launch_quantize_f32(h->st, Th, h->Mpad, h->Mpad, h->d_part64, tsc, tin, h->dTd + hf * td_half, 0, h->nd, L);
+            const HalfView v = half_view(h, hf);
+            const float* Th = h->dT + v.col;
+            switch (k1_quantiser(k1.state)) {
+            case K1Quantiser::CFold:      // (scale by launch_post_k1; c's second stage rides along)
+                launch_quantize_f32_cfold(h->st, Th, h->Mpad, h->Mpad, v.tinv, v.Td, 0, h->nd, L, v.cscratch, post_k1_slices(h->Mpad / 32), v.c); break;
+            case K1Quantiser::PreMax: launch_quantize_f32_premax(h->st, Th, h->Mpad, h->Mpad, k1.amax[hf], k1.parts, v.tscale, v.tinv, v.Td, 0, h->nd, L); break;
+            case K1Quantiser::Plain: launch_quantize_f32(h->st, Th, h->Mpad, h->Mpad, h->d_part64, v.tscale, v.tinv, v.Td, 0, h->nd, L); break;
+            }
             HIPCHK(hipGetLastError());
         }
-        h->apart_valid = false; h->c_fold_pending = false;
         const bool streamed = h->sm.on;
-        const size_t yint_half = (size_t)h->N * 32;
         {
             // resident: one record per launch (the roofline figure of bench.py); streamed: one record per sweep over the panels
             const double by = h->storage == GPCA_STORE_2BIT ? elems / 4 : elems;
@@ -221,12 +146,13 @@ static int stage_AtT_local(gpca_handle* h, bool planes_ready = false) {
             CHK(for_each_panel(h, [&](const PanelView& pv) -> int {
                 const Gtt8Plan plan = streamed ? k2_plan(h, pv.rows_pad) : h->plan8;
                 for (int hf = 0; hf < halves; ++hf) {
+                    const HalfView v = half_view(h, hf);
                     {
                         ScopedTimer t(h, "gemm_GtT", 2.0 * elems * h->l / halves, by, nullptr, !streamed);
-                        CHK(k2_panel(h, pv, h->dTd + hf * td_half, plan));
+                        CHK(k2_panel(h, pv, v.Td, plan));
                     }
-                    if (streamed) launch_accum_y_i8(h->st, h->dYpart64, plan.W, h->ldg, h->N, h->d_yint + hf * yint_half, pv.index == 0);
-                    else launch_reduce_y_i8(h->st, h->dYpart64, plan.W, h->ldg, h->N, h->d_c + 32 * hf, h->d_tscale + 32 * hf, h->dY + 32 * hf, L);
+                    if (streamed) launch_accum_y_i8(h->st, h->dYpart64, plan.W, h->ldg, h->N, v.yint, pv.index == 0);
+                    else launch_reduce_y_i8(h->st, h->dYpart64, plan.W, h->ldg, h->N, v.c, v.tscale, h->dY + v.col, L);
                     HIPCHK(hipGetLastError());
                 }
                 return GPCA_OK;
@@ -234,7 +160,8 @@ static int stage_AtT_local(gpca_handle* h, bool planes_ready = false) {
         }
         if (streamed)
             for (int hf = 0; hf < halves; ++hf) {
-                launch_finish_y_i8(h->st, h->d_yint + hf * yint_half, h->N, h->d_c + 32 * hf, h->d_tscale + 32 * hf, h->dY + 32 * hf, L);
+                const HalfView v = half_view(h, hf);
+                launch_finish_y_i8(h->st, v.yint, h->N, v.c, v.tscale, h->dY + v.col, L);
                 HIPCHK(hipGetLastError());
             }
         return GPCA_OK;
@@ -255,10 +182,8 @@ static int stage_AQ(gpca_handle* h, int scale_out) {
     const double elems = (double)h->M * (double)h->N;
     if (h->precision == GPCA_PREC_I8_EXACT) {
         const int L = h->L, halves = L / 32;
-        const bool packed = h->storage == GPCA_STORE_2BIT, streamed = h->sm.on;
-        const size_t qhalf = (size_t)h->ldg * 32 * kDigits;            // digit planes of one 32-column half of Q
-        const size_t chalf = (size_t)h->Mpad;                           // per-unit partials of c of one half: [Mpad / 32][32]
-        const size_t ahalf = (size_t)h->gqplan.waves * 32;              // per-wave abs-max partials of one launch
+        const bool packed = h->storage == GPCA_STORE_2BIT, streamed = h->sm.on, absmax = k1_leaves_absmax(h);
+        h->k1.reset();      // (dT is rewritten)
         if (streamed && scale_out) HIPCHK(hipMemsetAsync(h->d_amax_run, 0, kMaxSketch * 8, h->st));
         {
             const double by = packed ? elems / 4 : elems;
@@ -266,48 +191,29 @@ static int stage_AQ(gpca_handle* h, int scale_out) {
             CHK(for_each_panel(h, [&](const PanelView& pv) -> int {
                 const GqPlan plan = streamed ? k1_plan(h, pv.rows_pad) : h->gqplan;
                 for (int hf = 0; hf < halves; ++hf) {
-                    const int8_t* Qd = h->dQd + hf * qhalf;
-                    const double* qsc = h->d_qscale + 32 * hf;
-                    const float* s32 = h->d_s32 + 32 * hf;
-                    const float* rr = h->d_r + pv.row0; const float* bb = h->d_b + pv.row0;
-                    float* Th = h->dT + (size_t)pv.row0 * L + 32 * hf;
-                    float* cp = h->d_cpart + hf * chalf + (size_t)pv.row0;          // (row0 / 32) units x 32 columns
-                    double* ap = h->d_apart + hf * ahalf;
-                    ScopedTimer t(h, "gemm_GQ", 2.0 * elems * h->l / halves, by, nullptr, !streamed);
-                    if (packed) launch_gq_2bit(h->st, pv.g2, h->ld2, plan, h->ldg, Qd, qsc, rr, bb, s32, Th, cp, ap, scale_out, h->nd, L);
-                    else if (narrow_shape(h)) {
-                        const int e = launch_gq_n(h->st, pv.g8, h->ld8, plan, h->N, Qd, qsc, rr, bb, s32, Th, cp, ap, scale_out, L);
-                        if (e != 0) return fail(h, GPCA_ERR_HIP, "k_gq_n launch failed (hip error " + std::to_string(e) + ")");
+                    {
+                        ScopedTimer t(h, "gemm_GQ", 2.0 * elems * h->l / halves, by, nullptr, !streamed);
+                        CHK(k1_panel(h, pv, hf, plan, scale_out));
                     }
-                    else if (!h->simple_kernels) {
-                        const int e = launch_gq_d(h->st, pv.g8, h->ld8, plan, h->ldg, Qd, qsc, rr, bb, s32, Th, cp, ap, scale_out, L, h->ko);
-                        if (e != 0) return fail(h, GPCA_ERR_HIP, "k_gq_d launch failed (hip error " + std::to_string(e) + ")");
-                    }
-                    else launch_gq_i8(h->st, pv.g8, h->ld8, plan, h->N, Qd, qsc, rr, bb, s32, Th, cp, scale_out, L, h->ko);
-                    HIPCHK(hipGetLastError());
-                    if (streamed && scale_out && (packed || !h->simple_kernels || narrow_shape(h))) {   // (streamed: the per-launch timer above is disabled) fold this panel's column abs-max before the next launch reuses ap
-                        launch_absmax_fold(h->st, ap, plan.waves, h->d_amax_run + 32 * hf);
+                    if (streamed && scale_out && absmax) {      // fold this panel's column abs-max before the next launch reuses the partials
+                        launch_absmax_fold(h->st, half_view(h, hf).apart, plan.waves, h->d_amax_run + 32 * hf);
                         HIPCHK(hipGetLastError());
                     }
                 }
                 return GPCA_OK;
             }));
         }
-        h->apart_valid = scale_out != 0 && (packed || !h->simple_kernels || narrow_shape(h));   // (k_gq_i8 has no abs-max epilogue)
         // c = b^T T of every half: one partial per 32-row unit, summed in a fixed two-stage tree.  Resident matrices whose K1 left the waves'
         // column abs-max: the first stage runs beside the fold of those into the digit scale (one launch), the second rides the
-        // quantisation that follows in stage_AtT_local -- two launches between K1 and K2 instead of four, the same bits.
-        h->c_fold_pending = scale_out != 0 && !streamed && h->apart_valid;
-        if (scale_out)
-            for (int hf = 0; hf < halves; ++hf) {
-                if (h->c_fold_pending)
-                    launch_post_k1(h->st, h->d_cpart + hf * chalf, h->Mpad / 32, h->d_scratch64 + (size_t)hf * kPostK1Scratch, h->d_apart + hf * ahalf, h->gqplan.waves,
-                                   h->d_tscale + 32 * hf, h->d_tinv + 32 * hf, h->nd);
-                else launch_sum_partials_f32(h->st, h->d_cpart + hf * chalf, h->Mpad / 32, 32, h->d_c + 32 * hf, h->d_scratch64);
-                HIPCHK(hipGetLastError());
-            }
-        for (int hf = 0; hf < kMaxSketch / 32; ++hf) h->apart_src[hf] = streamed ? h->d_amax_run + 32 * hf : h->d_apart + hf * ahalf;
-        h->apart_parts = streamed ? 1 : h->gqplan.waves;
+        // quantisation that follows in stage_AtT_local -- two launches between K1 and K2 instead of four, the same bits (k1_handoff.h).
+        h->k1 = k1_handoff_after(scale_out, streamed, absmax, h->d_amax_run);
+        const K1CSum csum = k1_csum(h->k1.state, scale_out);
+        for (int hf = 0; hf < halves && csum != K1CSum::NotFormed; ++hf) {
+            const HalfView v = half_view(h, hf);
+            if (csum == K1CSum::PostK1) launch_post_k1(h->st, v.cpart, h->Mpad / 32, v.cscratch, v.apart, h->gqplan.waves, v.tscale, v.tinv, h->nd);
+            else launch_sum_partials_f32(h->st, v.cpart, h->Mpad / 32, 32, v.c, h->d_scratch64);
+            HIPCHK(hipGetLastError());
+        }
         return GPCA_OK;
     }
     {
@@ -331,52 +237,46 @@ static int stage_AQ(gpca_handle* h, int scale_out) {
 static int stage_power_fused(gpca_handle* h) {
     const double elems = (double)h->M * (double)h->N;
     const int L = h->L, halves = L / 32;
-    const bool packed = h->storage == GPCA_STORE_2BIT;
-    const size_t qhalf = (size_t)h->ldg * 32 * kDigits, chalf = (size_t)h->Mpad, ahalf = (size_t)h->gqplan.waves * 32;
-    const size_t td_half = (size_t)h->Mpad * 32 * kDigits, yint_half = (size_t)h->N * 32;
+    if (!power_fused(h)) return fail(h, GPCA_ERR_STATE, "the fused sweep needs a streamed matrix and a K1 with the abs-max epilogue");   // (stage_power never asks)
+    h->k1.reset();      // (dT is rewritten, and quantised here panel by panel: nothing is handed on)
     {
-        const double by = packed ? elems / 4 : elems;
+        const double by = h->storage == GPCA_STORE_2BIT ? elems / 4 : elems;
         ScopedTimer sweep(h, "gemm_fused", 4.0 * elems * h->l, by * halves);
         CHK(for_each_panel(h, [&](const PanelView& pv) -> int {
             const GqPlan plan1 = k1_plan(h, pv.rows_pad);
             const Gtt8Plan plan2 = k2_plan(h, pv.rows_pad);
-            const float* rr = h->d_r + pv.row0; const float* bb = h->d_b + pv.row0;
             for (int hf = 0; hf < halves; ++hf) {
-                const int8_t* Qd = h->dQd + hf * qhalf;
-                float* Th = h->dT + (size_t)pv.row0 * L + 32 * hf;
-                float* cp = h->d_cpart + hf * chalf + (size_t)pv.row0;
-                double* ap = h->d_apart + hf * ahalf;
-                if (packed) launch_gq_2bit(h->st, pv.g2, h->ld2, plan1, h->ldg, Qd, h->d_qscale + 32 * hf, rr, bb, h->d_s32 + 32 * hf, Th, cp, ap, 1, h->nd, L);
-                else if (narrow_shape(h)) {
-                    const int e = launch_gq_n(h->st, pv.g8, h->ld8, plan1, h->N, Qd, h->d_qscale + 32 * hf, rr, bb, h->d_s32 + 32 * hf, Th, cp, ap, 1, L);
-                    if (e != 0) return fail(h, GPCA_ERR_HIP, "k_gq_n launch failed (hip error " + std::to_string(e) + ")");
-                }
-                else {
-                    const int e = launch_gq_d(h->st, pv.g8, h->ld8, plan1, h->ldg, Qd, h->d_qscale + 32 * hf, rr, bb, h->d_s32 + 32 * hf, Th, cp, ap, 1, L, h->ko);
-                    if (e != 0) return fail(h, GPCA_ERR_HIP, "k_gq_d launch failed (hip error " + std::to_string(e) + ")");
-                }
-                HIPCHK(hipGetLastError());
+                const HalfView v = half_view(h, hf);
+                CHK(k1_panel(h, pv, hf, plan1, 1));
                 // this panel's rows of T' -> digit planes against this panel's column maxima
-                launch_quantize_f32_premax(h->st, Th, pv.rows_pad, pv.rows_pad, ap, plan1.waves, h->d_tscale + 32 * hf, h->d_tinv + 32 * hf,
-                                           h->dTd + hf * td_half + (size_t)(pv.row0 >> 5) * kPlaneBytesPerBlock, 0, h->nd, L);
+                launch_quantize_f32_premax(h->st, h->dT + (size_t)pv.row0 * L + v.col, pv.rows_pad, pv.rows_pad, v.apart, plan1.waves, v.tscale, v.tinv,
+                                           v.Td + (size_t)(pv.row0 >> 5) * kPlaneBytesPerBlock, 0, h->nd, L);
                 HIPCHK(hipGetLastError());
             }
             for (int hf = 0; hf < halves; ++hf) {
-                CHK(k2_panel(h, pv, h->dTd + hf * td_half, plan2));
-                launch_accum_y_scaled(h->st, h->dYpart64, plan2.W, h->ldg, h->N, h->d_tscale + 32 * hf, h->d_yint + hf * yint_half, pv.index == 0);
+                const HalfView v = half_view(h, hf);
+                CHK(k2_panel(h, pv, v.Td, plan2));
+                launch_accum_y_scaled(h->st, h->dYpart64, plan2.W, h->ldg, h->N, v.tscale, v.yint, pv.index == 0);
                 HIPCHK(hipGetLastError());
             }
             return GPCA_OK;
         }));
     }
     for (int hf = 0; hf < halves; ++hf) {
-        launch_sum_partials_f32(h->st, h->d_cpart + hf * chalf, h->Mpad / 32, 32, h->d_c + 32 * hf, h->d_scratch64);
+        const HalfView v = half_view(h, hf);
+        launch_sum_partials_f32(h->st, v.cpart, h->Mpad / 32, 32, v.c, h->d_scratch64);
         HIPCHK(hipGetLastError());
-        launch_finish_y_sum(h->st, h->d_yint + hf * yint_half, h->N, h->d_c + 32 * hf, h->dY + 32 * hf, L);
+        launch_finish_y_sum(h->st, v.yint, h->N, v.c, h->dY + v.col, L);
         HIPCHK(hipGetLastError());
     }
-    h->apart_valid = false;
     return GPCA_OK;
+}
+
+// One power iteration Y = A^T (A Q) as the call chooses it for this handle (rank-local; the exchange of Y follows in the caller)
+static int stage_power(gpca_handle* h) {
+    if (power_fused(h)) return stage_power_fused(h);
+    CHK(stage_AQ(h, 1));
+    return stage_AtT_local(h);
 }
 
 // CholeskyQR of dY -> dQ (f32, padded), s = 1^T Q.  rounds = 2 (CholeskyQR2): orthonormal to rounding -- the basis the projection and
@@ -410,22 +310,17 @@ static int stage_orth(gpca_handle* h, int rounds = 2) {
     const int64_t tparts = tail_num_parts(h->ldg);
     const double* csum_part = h->d_part64;
     const double* amax_part = h->d_part64 + tparts * L;
-    if (i8 && tparts <= kFinishQFoldMax) {      // one launch per 32 columns: the quantisation folds the tail's partials itself
-        for (int hf = 0; hf < L / 32; ++hf) {
-            launch_quantize_f64_finishq(h->st, h->dY + 32 * hf, h->N, h->ldg, h->dQd + (size_t)hf * h->ldg * 32 * kDigits, h->storage == GPCA_STORE_2BIT ? 1 : 0, h->nd, L,
-                                        csum_part + 32 * hf, amax_part + 32 * hf, tparts, L, h->d_s64 + 32 * hf, h->d_s32 + 32 * hf, h->d_qscale + 32 * hf, h->d_qinv + 32 * hf);
-            HIPCHK(hipGetLastError());
-        }
-        return GPCA_OK;
+    const bool folds = i8 && tparts <= kFinishQFoldMax;      // one launch per 32 columns: the quantisation folds the tail's partials itself
+    if (!folds) {
+        launch_finish_q(h->st, csum_part, amax_part, tparts, L, h->d_s64, h->d_s32, i8 ? h->d_qscale : nullptr, i8 ? h->d_qinv : nullptr, h->nd);
+        HIPCHK(hipGetLastError());
     }
-    launch_finish_q(h->st, csum_part, amax_part, tparts, L, h->d_s64, h->d_s32, i8 ? h->d_qscale : nullptr, i8 ? h->d_qinv : nullptr, h->nd);
-    HIPCHK(hipGetLastError());
-    if (i8) {
-        for (int hf = 0; hf < L / 32; ++hf) {
-            launch_quantize_f64_prescaled(h->st, h->dY + 32 * hf, h->N, h->ldg, h->d_qinv + 32 * hf, h->dQd + (size_t)hf * h->ldg * 32 * kDigits,
-                                          h->storage == GPCA_STORE_2BIT ? 1 : 0, h->nd, L);
-            HIPCHK(hipGetLastError());
-        }
+    for (int hf = 0; hf < L / 32 && i8; ++hf) {
+        const HalfView v = half_view(h, hf);
+        const int layout = h->storage == GPCA_STORE_2BIT ? 1 : 0;
+        if (folds) launch_quantize_f64_finishq(h->st, h->dY + v.col, h->N, h->ldg, v.Qd, layout, h->nd, L, csum_part + v.col, amax_part + v.col, tparts, L, v.s64, v.s32, v.qscale, v.qinv);
+        else launch_quantize_f64_prescaled(h->st, h->dY + v.col, h->N, h->ldg, v.qinv, v.Qd, layout, h->nd, L);
+        HIPCHK(hipGetLastError());
     }
     return GPCA_OK;
 }
@@ -485,6 +380,7 @@ static int ensure_workspace(gpca_handle* h) {
 
 // argument / state checks of gpca_rsvd + workspace: everything that can fail on one rank only before the first exchange
 static int rsvd_preflight(gpca_handle* h, int32_t k, int32_t oversample, int32_t power_iters) {
+    h->k1.reset();      // (whatever an earlier call that ended between its K1 and its K2 left behind)
     if (!have_genotypes(h)) return fail(h, GPCA_ERR_STATE, "gpca_rsvd: no genotypes resident and no panel stream open");
     if (!h->have_stats) return fail(h, GPCA_ERR_STATE, "gpca_rsvd: run gpca_snp_stats or gpca_set_standardization first");
     if (k <= 0) return fail(h, GPCA_ERR_BAD_ARG, "Number of components (-k) must be > 0.");  // main.rs:607-609
@@ -681,9 +577,14 @@ static int ensure_child(gpca_handle* h) {
     return GPCA_OK;
 }
 
-// a streamed power iteration reads every panel once (stage_power_fused) unless gpca_stream_set_fused(h, 0) or a K1 without the abs-max epilogue
-static inline bool power_fused(const gpca_handle* h) {
-    return h->sm.on && h->sm.fused && (h->storage == GPCA_STORE_2BIT || !h->simple_kernels || narrow_shape(h));   // (k_gq_i8 has no abs-max epilogue)
+// T' = r o X, c = b^T X for an arbitrary M x L f32 factor X sitting in dT (gpca_transform: the loadings; the EigenSNP stages: W P and L)
+static int prep_custom_T(gpca_handle* h) {
+    const int L = h->L;
+    if (h->precision == GPCA_PREC_I8_EXACT) launch_scale_rows(h->st, h->dT, h->M, h->Mpad, L, h->d_r, h->d_b, h->dT, h->d_cpart, 0);   // in place, row-major
+    else launch_scale_rows(h->st, h->dT, h->M, h->Mpad, L, h->d_r, h->d_b, h->dTb, h->d_cpart);
+    HIPCHK(hipGetLastError());
+    h->k1.reset();
+    return stage_sum_c(h, omega_num_parts(h->Mpad));
 }
 // 1. sketch: T' = r o Omega, c = b^T Omega (the partials of c; stage_sum_c folds them)
 static int stage_sketch(gpca_handle* h, uint64_t seed) {
@@ -698,7 +599,7 @@ static int stage_sketch(gpca_handle* h, uint64_t seed) {
             h->rmax_valid = true;
         }
         launch_omega_planes(h->st, h->M, h->Mpad, l, L, h->snp_offset, seed, h->d_r, h->d_b, h->d_cpart, h->dTd, h->d_rmax, h->d_tscale, h->d_tinv, h->nd, h->d_row_ids);
-        h->apart_valid = false;
+        h->k1.reset();
     } else launch_omega(h->st, h->M, h->Mpad, l, L, h->snp_offset, seed, h->d_r, h->d_b, h->dTb, h->d_cpart, nullptr, 1, h->d_row_ids);
     HIPCHK(hipGetLastError());
     return GPCA_OK;
@@ -749,10 +650,8 @@ extern "C" int gpca_rsvd(gpca_handle* h, int32_t k, int32_t oversample, int32_t 
     EXCHANGE(h->dY, h->N * (int64_t)L);
     LOCAL(stage_orth(h, power_iters == 0 ? 2 : 1));   // (the last basis before the projection gets CholeskyQR2, the earlier ones one round)
     // 2. power iterations
-    const bool fused = power_fused(h);
     for (int it = 0; it < power_iters; ++it) {
-        if (fused) LOCAL(stage_power_fused(h));
-        else { LOCAL(stage_AQ(h, 1)); LOCAL(stage_AtT_local(h)); }
+        LOCAL(stage_power(h));
         EXCHANGE(h->dY, h->N * (int64_t)L);
         LOCAL(stage_orth(h, it + 1 == power_iters ? 2 : 1));
     }
@@ -821,11 +720,7 @@ extern "C" int gpca_transform(gpca_handle* h, double* out) {
         HIPCHK(hipMemsetAsync(h->dT, 0, (size_t)h->Mpad * L * 4, h->st));
         launch_expand_loadings(h->st, h->d_load32, h->d_pca_rows, h->n_pca, k, L, h->dT);
         HIPCHK(hipGetLastError());
-        if (h->precision == GPCA_PREC_I8_EXACT) launch_scale_rows(h->st, h->dT, h->M, h->Mpad, L, h->d_r, h->d_b, h->dT, h->d_cpart, 0);   // in place, row-major
-        else launch_scale_rows(h->st, h->dT, h->M, h->Mpad, L, h->d_r, h->d_b, h->dTb, h->d_cpart);
-        HIPCHK(hipGetLastError());
-        h->apart_valid = false;
-        return stage_sum_c(h, omega_num_parts(h->Mpad));
+        return prep_custom_T(h);
     };
     LOCAL(prep());
     LOCAL(stage_AtT_local(h));
@@ -929,16 +824,6 @@ extern "C" int gpca_set_condensed_basis(gpca_handle* h, const float* W, const in
     return GPCA_OK;
 }
 
-// T' = r o X, c = b^T X for an arbitrary M x L f32 factor X sitting in dT (what gpca_transform does for the loadings)
-static int prep_custom_T(gpca_handle* h) {
-    const int L = h->L;
-    if (h->precision == GPCA_PREC_I8_EXACT) launch_scale_rows(h->st, h->dT, h->M, h->Mpad, L, h->d_r, h->d_b, h->dT, h->d_cpart, 0);
-    else launch_scale_rows(h->st, h->dT, h->M, h->Mpad, L, h->d_r, h->d_b, h->dTb, h->d_cpart);
-    HIPCHK(hipGetLastError());
-    h->apart_valid = false;
-    return stage_sum_c(h, omega_num_parts(h->Mpad));
-}
-
 // Initial global PCs from the row-standardised condensed features C* = W^T X (never formed): randomized PCA of C* with its
 // products factored through the genotype GEMMs -- C*^T Z = A^T (W Z), C* Q = W^T (A Q).  Leaves the N x k sample scores
 // (gpca_get_scores / _f64) and the eigenvalues of C*; loadings are not defined for this call.
@@ -991,6 +876,24 @@ extern "C" int gpca_rsvd_condensed(gpca_handle* h, int32_t k, int32_t oversample
     return GPCA_OK;
 }
 
+// A caller's [rows][l] array into a device array of pitch L (zero pad columns), and the converse; both wait for the stream.
+template <typename T>
+static int upload_padded(gpca_handle* h, const T* src, int64_t rows, int l, int L, T* dst) {
+    std::vector<T> buf((size_t)rows * L, T(0));
+    for (int64_t i = 0; i < rows; ++i) for (int c = 0; c < l; ++c) buf[(size_t)i * L + c] = src[(size_t)i * l + c];
+    HIPCHK(hipMemcpyAsync(dst, buf.data(), buf.size() * sizeof(T), hipMemcpyHostToDevice, h->st));
+    HIPCHK(hipStreamSynchronize(h->st));
+    return GPCA_OK;
+}
+template <typename T>
+static int download_compact(gpca_handle* h, const T* src, int64_t rows, int l, int L, T* dst) {
+    std::vector<T> buf((size_t)rows * L);
+    HIPCHK(hipMemcpyAsync(buf.data(), src, buf.size() * sizeof(T), hipMemcpyDeviceToHost, h->st));
+    HIPCHK(hipStreamSynchronize(h->st));
+    for (int64_t i = 0; i < rows; ++i) for (int c = 0; c < l; ++c) dst[(size_t)i * l + c] = buf[(size_t)i * L + c];
+    return GPCA_OK;
+}
+
 // One refinement pass from given sample scores S0 (N x k, any basis of the current estimate of the PC subspace):
 //   L = orth(A S0) (SNP side, CholeskyQR2 over the M rows), S = A^T L (N x k), S^T S = W Sigma^2 W^T,
 //   scores = S W, loadings = L W, eigenvalues = Sigma^2 / (N - 1).
@@ -1006,12 +909,7 @@ extern "C" int gpca_refine(gpca_handle* h, const double* S0, int32_t k) {
     const int l = h->l, L = h->L;
     CHK(ensure(h, h->d_lqr, h->cap_lqr, (size_t)h->Mpad * L));
     // Q = orth(S0) (a basis of the same subspace; keeps the digit scales of the exact path well conditioned)
-    {
-        std::vector<double> Y((size_t)h->N * L, 0.0);
-        for (int64_t n = 0; n < h->N; ++n) for (int c = 0; c < k; ++c) Y[(size_t)n * L + c] = S0[(size_t)n * k + c];
-        HIPCHK(hipMemcpyAsync(h->dY, Y.data(), Y.size() * 8, hipMemcpyHostToDevice, h->st));
-        HIPCHK(hipStreamSynchronize(h->st));
-    }
+    CHK(upload_padded(h, S0, h->N, k, L, h->dY));
     CHK(stage_orth(h));
     CHK(stage_AQ(h, 0));                                  // dT = A Q   (M x L f32)
     for (int round = 0; round < 2; ++round) {             // CholeskyQR2 over the SNP rows
@@ -1041,19 +939,14 @@ extern "C" int gpca_device_orth(gpca_handle* h, const double* Y, int32_t l, int3
     if (multi_rank(h) || h->sm.on) return fail(h, GPCA_ERR_STATE, "gpca_device_orth: needs a resident, unsharded matrix");
     CHK(rsvd_preflight(h, l, 0, 0));
     const int L = h->L;
-    const int64_t N = h->N;
-    std::vector<double> buf((size_t)N * L, 0.0);
-    for (int64_t n = 0; n < N; ++n) for (int c = 0; c < l; ++c) buf[(size_t)n * L + c] = Y[(size_t)n * l + c];
-    HIPCHK(hipMemcpyAsync(h->dY, buf.data(), buf.size() * 8, hipMemcpyHostToDevice, h->st));
-    HIPCHK(hipStreamSynchronize(h->st));
+    CHK(upload_padded(h, Y, h->N, l, L, h->dY));
     CHK(stage_orth(h, rounds));
     double s64[kMaxSketch];
     int flag = 0;
-    HIPCHK(hipMemcpyAsync(buf.data(), h->dY, buf.size() * 8, hipMemcpyDeviceToHost, h->st));
+    CHK(download_compact(h, h->dY, h->N, l, L, Q));
     HIPCHK(hipMemcpyAsync(s64, h->d_s64, sizeof(double) * L, hipMemcpyDeviceToHost, h->st));
     HIPCHK(hipMemcpyAsync(&flag, h->d_cholflag, 4, hipMemcpyDeviceToHost, h->st));
     HIPCHK(hipStreamSynchronize(h->st));
-    for (int64_t n = 0; n < N; ++n) for (int c = 0; c < l; ++c) Q[(size_t)n * l + c] = buf[(size_t)n * L + c];
     if (s) std::copy(s64, s64 + l, s);
     *pivot_flag = flag;            // (data, not a status: the product reads it once, at the end of its call)
     return GPCA_OK;
@@ -1066,12 +959,10 @@ extern "C" int gpca_device_tail(gpca_handle* h, const double* Q, const float* B,
     CHK(rsvd_preflight(h, k, l - k, 0));
     const int L = h->L;
     const int64_t N = h->N;
+    CHK(upload_padded(h, Q, N, l, L, h->dY));
     {
-        std::vector<double> Yb((size_t)N * L, 0.0);
-        for (int64_t n = 0; n < N; ++n) for (int c = 0; c < l; ++c) Yb[(size_t)n * L + c] = Q[(size_t)n * l + c];
         std::vector<float> Tb((size_t)h->Mpad * L, 0.f);          // (rows QC dropped stay zero, as stage_AQ leaves them)
         for (int64_t i : h->pca_rows) for (int c = 0; c < l; ++c) Tb[(size_t)i * L + c] = B[(size_t)i * l + c];
-        HIPCHK(hipMemcpyAsync(h->dY, Yb.data(), Yb.size() * 8, hipMemcpyHostToDevice, h->st));
         HIPCHK(hipMemcpyAsync(h->dT, Tb.data(), Tb.size() * 4, hipMemcpyHostToDevice, h->st));
         HIPCHK(hipStreamSynchronize(h->st));
     }
@@ -1098,13 +989,7 @@ extern "C" int gpca_device_sketch(gpca_handle* h, int32_t l, uint64_t seed, doub
     CHK(stage_sketch(h, seed));
     CHK(stage_sum_c(h, omega_num_parts(h->Mpad)));
     CHK(stage_AtT_local(h, h->precision == GPCA_PREC_I8_EXACT));
-    const int L = h->L;
-    const int64_t N = h->N;
-    std::vector<double> buf((size_t)N * L);
-    HIPCHK(hipMemcpyAsync(buf.data(), h->dY, buf.size() * 8, hipMemcpyDeviceToHost, h->st));
-    HIPCHK(hipStreamSynchronize(h->st));
-    for (int64_t n = 0; n < N; ++n) for (int c = 0; c < l; ++c) Y[(size_t)n * l + c] = buf[(size_t)n * L + c];
-    return GPCA_OK;
+    return download_compact(h, h->dY, h->N, l, h->L, Y);
 }
 
 // One power iteration of gpca_rsvd on a caller's sketch: CholeskyQR2 of Yin, then Y = A^T (A Q) as the call chooses it for this handle.
@@ -1116,25 +1001,14 @@ extern "C" int gpca_device_power(gpca_handle* h, const double* Yin, int32_t l, d
         return fail(h, GPCA_ERR_STATE, "gpca_device_power: needs GPCA_PREC_I8_EXACT");
     CHK(rsvd_preflight(h, l, 0, 1));
     const int L = h->L;
-    const int64_t N = h->N, M = h->M;
-    std::vector<double> buf((size_t)N * L, 0.0);
-    for (int64_t n = 0; n < N; ++n) for (int j = 0; j < l; ++j) buf[(size_t)n * L + j] = Yin[(size_t)n * l + j];
-    HIPCHK(hipMemcpyAsync(h->dY, buf.data(), buf.size() * 8, hipMemcpyHostToDevice, h->st));
-    HIPCHK(hipStreamSynchronize(h->st));
+    CHK(upload_padded(h, Yin, h->N, l, L, h->dY));
     CHK(stage_orth(h, 2));
-    HIPCHK(hipMemcpyAsync(buf.data(), h->dY, buf.size() * 8, hipMemcpyDeviceToHost, h->st));
-    HIPCHK(hipStreamSynchronize(h->st));
-    for (int64_t n = 0; n < N; ++n) for (int j = 0; j < l; ++j) Q[(size_t)n * l + j] = buf[(size_t)n * L + j];
-    if (power_fused(h)) CHK(stage_power_fused(h));
-    else { CHK(stage_AQ(h, 1)); CHK(stage_AtT_local(h)); }
-    std::vector<float> tb((size_t)M * L);
+    CHK(download_compact(h, h->dY, h->N, l, L, Q));
+    CHK(stage_power(h));
     double c64[kMaxSketch];
-    HIPCHK(hipMemcpyAsync(tb.data(), h->dT, tb.size() * 4, hipMemcpyDeviceToHost, h->st));
+    CHK(download_compact(h, h->dT, h->M, l, L, Tq));
     HIPCHK(hipMemcpyAsync(c64, h->d_c, sizeof(double) * L, hipMemcpyDeviceToHost, h->st));
-    HIPCHK(hipMemcpyAsync(buf.data(), h->dY, buf.size() * 8, hipMemcpyDeviceToHost, h->st));
-    HIPCHK(hipStreamSynchronize(h->st));
-    for (int64_t i = 0; i < M; ++i) for (int j = 0; j < l; ++j) Tq[(size_t)i * l + j] = tb[(size_t)i * L + j];
-    for (int64_t n = 0; n < N; ++n) for (int j = 0; j < l; ++j) Yout[(size_t)n * l + j] = buf[(size_t)n * L + j];
+    CHK(download_compact(h, h->dY, h->N, l, L, Yout));      // (waits for the copy of c as well)
     std::copy(c64, c64 + l, c);
     return GPCA_OK;
 }
