@@ -8,5 +8,6 @@ from .synth import synth_thresholds, synth_thresholds16  # noqa: F401
 from .distributed import shard_rows  # noqa: F401
 
 spa_log10p = GpcaEngine.spa_log10p
+firth_log10p = GpcaEngine.firth_log10p
 
 __version__ = "0.2.2"

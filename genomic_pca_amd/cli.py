@@ -126,8 +126,8 @@ def build_parser() -> argparse.ArgumentParser:
                         "Needs the matrix resident on the device; traits + PCs + covariates <= 64")
     p.add_argument("--gpca-assoc-logistic", action="store_true",
                    help="--gpca-assoc-pheno: a trait column whose present values are exactly {0, 1} (1 = case) or {1, 2} (plink's coding, "
-                        "2 = case) gets the logistic score test (the null model fitted once per trait; no Firth correction; --gpca-assoc-spa adds "
-                        "the saddle-point correction) -> "
+                        "2 = case) gets the logistic score test (the null model fitted once per trait; --gpca-assoc-spa adds "
+                        "the saddle-point correction, --gpca-assoc-firth the approximate Firth correction) -> "
                         "P.<trait>.assoc.logistic (#CHROM POS ID A1 OBS_CT A1_FREQ BETA SE Z_STAT LOG10P); the other columns go "
                         "through the linear scan as without the flag.  PCs + covariates + 3 <= 64")
     p.add_argument("--gpca-assoc-spa", action="store_true",
@@ -137,6 +137,14 @@ def build_parser() -> argparse.ArgumentParser:
                         "normal value) or F (the correction did not converge: the normal value); BETA, SE and Z_STAT stay the score test's")
     p.add_argument("--gpca-assoc-spa-z", type=float, default=None, metavar="X",
                    help="--gpca-assoc-spa: the cutoff, at least 0.5, or inf for no correction [default: 2]")
+    p.add_argument("--gpca-assoc-firth", action="store_true",
+                   help="--gpca-assoc-logistic: the approximate Firth correction (as regenie --firth --approx) of every test with "
+                        "|Z_STAT| >= the cutoff: one coefficient on the covariate-adjusted genotype by Firth's penalised likelihood, the null "
+                        "model as offset.  BETA, SE and LOG10P are then Firth's (finite where every carrier is a case), Z_STAT stays the score "
+                        "test's, and a column FIRTH says Y (corrected), N (below the cutoff) or F (the fit failed: the score test's values).  "
+                        "Not together with --gpca-assoc-spa")
+    p.add_argument("--gpca-assoc-firth-z", type=float, default=None, metavar="X",
+                   help="--gpca-assoc-firth: the cutoff, at least 0, or inf for no correction [default: 1.959964]")
     p.add_argument("--gpca-assoc-pcs", type=int, default=None, metavar="P",
                    help="--gpca-assoc-pheno: the first P columns of the scores this run writes are covariates (0 <= P <= "
                         "--eigensnp-k-global) [default: every column]")
@@ -480,6 +488,7 @@ def _assoc(eng, a, fs, cols, sample_ids, scores, inset, st):
     rows = np.flatnonzero(st["keep"])
     lib = _lib.load()
     spa_z = 2.0 if a.gpca_assoc_spa_z is None else a.gpca_assoc_spa_z
+    firth_z = 1.959964 if a.gpca_assoc_firth_z is None else a.gpca_assoc_firth_z
 
     def meta_of(r0, r1):
         rr = rows[r0:r1]
@@ -495,19 +504,24 @@ def _assoc(eng, a, fs, cols, sample_ids, scores, inset, st):
         for t0, t1 in (gio.assoc_score_groups(len(bnames), Pc) if bnames else []):
             Yg = np.ascontiguousarray(Yb[:, t0:t1])
             for bi, (r0, r1) in enumerate(gio.assoc_score_bands(len(rows), t1 - t0, Pc)):
-                if a.gpca_assoc_spa:
+                if a.gpca_assoc_firth:
+                    r = eng.assoc_logistic_firth(Yg, C, include=include, max_vif=vif, firth_z=firth_z, rows=(r0, r1))
+                elif a.gpca_assoc_spa:
                     r = eng.assoc_logistic_spa(Yg, C, include=include, max_vif=vif, spa_z=spa_z, rows=(r0, r1))
                 else:
                     r = eng.assoc_logistic_score(Yg, C, include=include, max_vif=vif, rows=(r0, r1))
                 meta = meta_of(r0, r1)
                 for t in range(t1 - t0):
-                    zz = r["z"][:, t]
-                    if a.gpca_assoc_spa:
+                    zz, beta, se, spa, firth = r["z"][:, t], r["beta"][:, t], r["se"][:, t], None, None
+                    if a.gpca_assoc_firth:
+                        lp, firth = r["log10p"][:, t], r["firth_status"][:, t]
+                        beta, se = np.where(firth == 1, r["firth_beta"][:, t], beta), np.where(firth == 1, r["firth_se"][:, t], se)
+                    elif a.gpca_assoc_spa:
                         lp, spa = r["log10p"][:, t], r["spa_status"][:, t]
                     else:
-                        lp, spa = [float("nan") if v != v else lib.gpca_normal_log10p(float(v)) for v in zz], None
-                    gio.write_assoc_logistic(a.output_prefix, bnames[t0 + t], *meta, r["n_obs"], r["a1_freq"], r["beta"][:, t], r["se"][:, t], zz,
-                                             lp, append=bi > 0, spa=spa)
+                        lp = [float("nan") if v != v else lib.gpca_normal_log10p(float(v)) for v in zz]
+                    gio.write_assoc_logistic(a.output_prefix, bnames[t0 + t], *meta, r["n_obs"], r["a1_freq"], beta, se, zz,
+                                             lp, append=bi > 0, spa=spa, firth=firth)
     except _lib.GpcaError as e:
         if e.status == _lib.GPCA_ERR_STATE:
             raise SystemExit(ASSOC_NEEDS_RESIDENT) from None
@@ -616,6 +630,14 @@ def main(argv=None) -> int:
         raise SystemExit("error: --gpca-assoc-spa-z needs --gpca-assoc-spa")
     if a.gpca_assoc_spa_z is not None and not gio.spa_z_ok(a.gpca_assoc_spa_z):
         raise SystemExit("error: --gpca-assoc-spa-z must be at least 0.5, or inf for no correction")
+    if a.gpca_assoc_firth and not a.gpca_assoc_logistic:
+        raise SystemExit("error: --gpca-assoc-firth needs --gpca-assoc-logistic")
+    if a.gpca_assoc_firth and a.gpca_assoc_spa:
+        raise SystemExit("error: --gpca-assoc-firth and --gpca-assoc-spa exclude each other")
+    if a.gpca_assoc_firth_z is not None and not a.gpca_assoc_firth:
+        raise SystemExit("error: --gpca-assoc-firth-z needs --gpca-assoc-firth")
+    if a.gpca_assoc_firth_z is not None and not gio.firth_z_ok(a.gpca_assoc_firth_z):
+        raise SystemExit("error: --gpca-assoc-firth-z must be at least 0, or inf for no correction")
     if a.gpca_assoc_pheno is not None:
         if not a.eigensnp:
             raise SystemExit("error: --gpca-assoc-pheno needs the --eigensnp workflow")

@@ -4,7 +4,7 @@
 // writes the item's normal value with status 0 and, where z is finite, |z| >= spa_z and U != 0, takes a slot of the range's list from an
 // atomic counter: the slot decides only which workgroup computes the item, every result goes to the item's own address.
 // k_assoc_spa: asp_slots(N) persistent workgroups of kAspThreads threads take the listed items in turn.  For an item the workgroup
-//  1. reads the row once, in chunks of kAspChunk samples: a thread fetches 32 samples (asc_fetch), masks and flips them as the score
+//  1. (asp_stage_gt, assoc_stage.h, shared with k_assoc_firth) reads the row once, in chunks of kAspChunk samples: a thread fetches 32 samples (asc_fetch), masks and flips them as the score
 //     kernel does (asr_put) into an LDS buffer; then thread t owns the samples t + kAspThreads k: x~ = the operand, the operand's mean
 //     xbar on a missing call, 0 outside S; g~ = x~ - sum_j a_j Z_nj (j ascending, a_j from dv, Z = X L^-T in f64 from the host), written
 //     to the workgroup's slice of the workspace; the bounds of the support are summed on the way;
@@ -94,31 +94,11 @@ __global__ __launch_bounds__(kAspThreads) void k_assoc_spa(const void* __restric
         const double* Zt = Z + (int64_t)t * P * npad;
         const double* mut = mu + (int64_t)t * npad;
         double hi = 0.0, lo = 0.0, unused = 0.0;
-        for (int64_t c0 = 0; c0 < npad; c0 += kAspChunk) {
-            const int64_t n0 = c0 + 32 * tid;
-            // (n0 is a multiple of 32 below npad: the read stays inside the row's pitch and the include word exists, as in k_assoc)
-            if (n0 < npad) {
-                AscFetch F;
-                asc_fetch<PACKED>(F, G, ldr, orow, n0);
-                asr_put(F, asc_inb(N, n0), incw[n0 >> 5], flip, sx + 32 * tid);
-            }
-            __syncthreads();                                                    // (also orders sa before its first use)
-#pragma nounroll
-            for (int k = 0; k < 32; ++k) {
-                const int64_t n = c0 + tid + kAspThreads * k;
-                if (n >= npad) break;
-                const unsigned b = sx[tid + kAspThreads * k];
-                const double xt = b == kAscMissing ? xbar : (double)b;
-                double acc = 0.0;
-                for (int j = 0; j < P; ++j) acc = acc + sa[j] * Zt[(int64_t)j * npad + n];
-                const double gg = xt - acc;
-                gw[n] = gg;
-                double p, q;
-                spa_support(gg, mut[n], p, q);
-                hi = hi + p; lo = lo + q;
-            }
-            __syncthreads();
-        }
+        asp_stage_gt<PACKED>(G, ldr, orow, N, npad, incw, flip, xbar, sa, P, Zt, sx, gw, [&](int64_t n, double gg) {
+            double p, q;
+            spa_support(gg, mut[n], p, q);
+            hi = hi + p; lo = lo + q;
+        });
         const double U = dv[i * L + asr_col_r(T, t)], normal = out[item * 4];   // (the flag kernel's value; thread 0 overwrites it below)
         asp_reduce3(hi, lo, unused, red);                                       // (its barriers make g~ visible to the workgroup)
         AspEval ev{gw, mut, npad, red};

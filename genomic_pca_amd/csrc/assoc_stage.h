@@ -1,5 +1,6 @@
-// The staging helpers of the association kernels (assoc.hip, assoc_score.hip, assoc_spa.hip): the fetch of 32 samples of a row from either storage,
-// the check / mask / count of those samples on their way into a stage's LDS buffer, and the fetch and store of a stage's panel of B^T.
+// The staging helpers of the association kernels (assoc.hip, assoc_score.hip, assoc_spa.hip, assoc_firth.hip): the fetch of 32 samples of a
+// row from either storage, the check / mask / count of those samples on their way into a stage's LDS buffer, the staging of one item's
+// covariate-adjusted genotype for the two corrections, and the fetch and store of a stage's panel of B^T.
 // (assoc_tile.h holds the stage pipeline that the two mainloop kernels build from them.)
 #pragma once
 #include "syrk_tile.h"
@@ -86,6 +87,43 @@ __device__ __forceinline__ void asr_put(const AscFetch& F, unsigned inb, unsigne
     }
 #pragma unroll
     for (int d = 0; d < 4; ++d) *reinterpret_cast<uint2*>(dst + 8 * d) = make_uint2(o[2 * d], o[2 * d + 1]);
+}
+
+// The covariate-adjusted genotype g~ of one (row, trait) item, staged by a workgroup of kAspThreads threads (k_assoc_spa, k_assoc_firth;
+// include/gpca.h section a14, "Setting").  The row is read once, in chunks of kAspChunk samples: a thread fetches 32 samples
+// (asc_fetch) and masks and flips them as the score kernel does (asr_put) into sx [kAspChunk]; then thread t owns the samples
+// t + kAspThreads k: x~ = the operand, xbar on a missing call, 0 outside S; g~ = x~ - sum_j sa[j] Z_nj (j ascending, f64, no fused
+// multiply-add), written to gw [npad]; each(n, g~) sees every sample the thread owns, in ascending order.  sa [P] is written by the
+// caller before the call (the first barrier here orders it); g~ is visible to the workgroup after the caller's next barrier.
+template <bool PACKED, class Each>
+__device__ __forceinline__ void asp_stage_gt(const uint8_t* __restrict__ G, int64_t ldr, int64_t orow, int64_t N, int64_t npad,
+                                             const unsigned* __restrict__ incw, bool flip, double xbar, const double* sa, int P,
+                                             const double* __restrict__ Zt, uint8_t* sx, double* gw, Each&& each) {
+#pragma clang fp contract(off)
+    const int tid = threadIdx.x;
+    for (int64_t c0 = 0; c0 < npad; c0 += kAspChunk) {
+        const int64_t n0 = c0 + 32 * tid;
+        // (n0 is a multiple of 32 below npad: the read stays inside the row's pitch and the include word exists, as in k_assoc)
+        if (n0 < npad) {
+            AscFetch F;
+            asc_fetch<PACKED>(F, G, ldr, orow, n0);
+            asr_put(F, asc_inb(N, n0), incw[n0 >> 5], flip, sx + 32 * tid);
+        }
+        __syncthreads();                                                    // (also orders sa before its first use)
+#pragma nounroll
+        for (int k = 0; k < 32; ++k) {
+            const int64_t n = c0 + tid + kAspThreads * k;
+            if (n >= npad) break;
+            const unsigned b = sx[tid + kAspThreads * k];
+            const double xt = b == kAscMissing ? xbar : (double)b;
+            double acc = 0.0;
+            for (int j = 0; j < P; ++j) acc = acc + sa[j] * Zt[(int64_t)j * npad + n];
+            const double gg = xt - acc;
+            gw[n] = gg;
+            each(n, gg);
+        }
+        __syncthreads();
+    }
 }
 
 // Bt [32 NB][npad]: the panel of a stage is 32 NB columns x 16 float4

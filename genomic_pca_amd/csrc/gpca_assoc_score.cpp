@@ -6,7 +6,9 @@
 // gpca_assoc_logistic_spa / gpca_spa_log10p (section a14): the same call with the saddle-point correction after the finish kernel
 // (assoc_spa.hip: the items with |z| >= spa_z, flagged and computed in ranges of kAspListItems), and the correction for one given
 // vector on the host; both run the rules of spa_math.h.
-// What is here: the Newton fit, the per-trait panel columns, the saddle-point orchestration and the host-only entry points; the rest
+// gpca_assoc_logistic_firth / gpca_firth_log10p (section a15): the same call again with the approximate Firth correction in the
+// saddle-point correction's place (assoc_firth.hip: the items with |z| >= firth_z, the same ranges, lists and inputs), and its host twin.
+// What is here: the Newton fit, the per-trait panel columns, the two corrections' orchestration and the host-only entry points; the rest
 // of the host front end is the linear scan's (gpca_assoc.cpp, declared in gpca_internal.h).
 #include "gpca_internal.h"
 #include "spa_math.h"
@@ -19,13 +21,13 @@ struct AsrWs {
     unsigned *incw = nullptr, *sums = nullptr;
     double *dv = nullptr, *stats = nullptr, *ua = nullptr, *info = nullptr;
     unsigned long long* bad = nullptr;
-    // the saddle-point correction's: Z and mu of the traits, the slices of g~, the list of a range and its counter, the results
-    double *Z = nullptr, *mu = nullptr, *g = nullptr, *spa = nullptr;
+    // a correction's (saddle-point or Firth): Z and mu of the traits, the slices of g~, the list of a range and its counter, the results
+    double *Z = nullptr, *mu = nullptr, *g = nullptr, *corr = nullptr;
     int* list = nullptr;
     unsigned* count = nullptr;
     ~AsrWs() {
         dfree(Bt); dfree(incw); dfree(sums); dfree(dv); dfree(stats); dfree(ua); dfree(info); dfree(bad);
-        dfree(Z); dfree(mu); dfree(g); dfree(spa); dfree(list); dfree(count);
+        dfree(Z); dfree(mu); dfree(g); dfree(corr); dfree(list); dfree(count);
     }
 };
 
@@ -140,9 +142,28 @@ struct HostSpaEval {
     }
 };
 
-// gpca_assoc_logistic_score (spa = nullptr) and gpca_assoc_logistic_spa: one path; the correction only adds to it
+// the sums of the Firth correction over one given vector, in sample order
+struct HostFirthEval {
+    const double *g, *mu;
+    int64_t n;
+    void operator()(double beta, double& k0, double& k1, double& k2, double& k3, double& k4) const {
+#pragma clang fp contract(off)
+        double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0, s4 = 0.0;
+        for (int64_t i = 0; i < n; ++i) {
+            double t1, t2, t3, t4;
+            firth_terms1234(g[i], mu[i], beta, t1, t2, t3, t4);
+            s0 = s0 + spa_term0(g[i], mu[i], beta);
+            s1 = s1 + t1; s2 = s2 + t2; s3 = s3 + t3; s4 = s4 + t4;
+        }
+        k0 = s0; k1 = s1; k2 = s2; k3 = s3; k4 = s4;
+    }
+};
+
+// gpca_assoc_logistic_score (kCorrNone, corr = nullptr), gpca_assoc_logistic_spa and gpca_assoc_logistic_firth: one path; a correction
+// only adds to it.  corr_z = spa_z or firth_z; corr = the correction's output, [rows][T][4] or [rows][T][kAfiWidth]
+enum Correction { kCorrNone, kCorrSpa, kCorrFirth };
 int assoc_logistic(gpca_handle* h, const std::string& f, const double* Y, int32_t T, const double* C, int32_t Pc, const uint8_t* include,
-                   double max_vif, bool with_spa, double spa_z, int64_t row0, int64_t row1, double* stats, double* spa, double* ua,
+                   double max_vif, Correction mode, double corr_z, int64_t row0, int64_t row1, double* stats, double* corr, double* ua,
                    double* rowinfo);
 }  // namespace
 
@@ -169,25 +190,37 @@ extern "C" int gpca_logistic_null(const double* y, const double* C, int32_t Pc, 
 extern "C" int gpca_assoc_logistic_score(gpca_handle* h, const double* Y, int32_t T, const double* C, int32_t Pc, const uint8_t* include,
                                          double max_vif, int64_t row0, int64_t row1, double* stats, double* ua, double* rowinfo) {
     if (!h) return GPCA_ERR_BAD_ARG;
-    return assoc_logistic(h, "gpca_assoc_logistic_score", Y, T, C, Pc, include, max_vif, false, INFINITY, row0, row1, stats, nullptr, ua, rowinfo);
+    return assoc_logistic(h, "gpca_assoc_logistic_score", Y, T, C, Pc, include, max_vif, kCorrNone, INFINITY, row0, row1, stats, nullptr, ua, rowinfo);
 }
 
 extern "C" int gpca_assoc_logistic_spa(gpca_handle* h, const double* Y, int32_t T, const double* C, int32_t Pc, const uint8_t* include,
                                        double max_vif, double spa_z, int64_t row0, int64_t row1, double* stats, double* spa, double* ua,
                                        double* rowinfo) {
     if (!h) return GPCA_ERR_BAD_ARG;
-    return assoc_logistic(h, "gpca_assoc_logistic_spa", Y, T, C, Pc, include, max_vif, true, spa_z, row0, row1, stats, spa, ua, rowinfo);
+    return assoc_logistic(h, "gpca_assoc_logistic_spa", Y, T, C, Pc, include, max_vif, kCorrSpa, spa_z, row0, row1, stats, spa, ua, rowinfo);
+}
+
+extern "C" int gpca_assoc_logistic_firth(gpca_handle* h, const double* Y, int32_t T, const double* C, int32_t Pc, const uint8_t* include,
+                                         double max_vif, double firth_z, int64_t row0, int64_t row1, double* stats, double* firth, double* ua,
+                                         double* rowinfo) {
+    if (!h) return GPCA_ERR_BAD_ARG;
+    return assoc_logistic(h, "gpca_assoc_logistic_firth", Y, T, C, Pc, include, max_vif, kCorrFirth, firth_z, row0, row1, stats, firth, ua, rowinfo);
 }
 
 namespace {
 int assoc_logistic(gpca_handle* h, const std::string& f, const double* Y, int32_t T, const double* C, int32_t Pc, const uint8_t* include,
-                   double max_vif, bool with_spa, double spa_z, int64_t row0, int64_t row1, double* stats, double* spa, double* ua,
+                   double max_vif, Correction mode, double corr_z, int64_t row0, int64_t row1, double* stats, double* corr, double* ua,
                    double* rowinfo) {
     LOCK(h);
+    const bool with_spa = mode == kCorrSpa, with_firth = mode == kCorrFirth, with_corr = mode != kCorrNone;
     CHK(asc_check_call(h, f, T >= 1 && Pc >= 0 && (int64_t)T * ((int64_t)Pc + 3) <= kAsrMaxCols,
                        "T >= 1, Pc >= 0 and T (Pc + 3) <= " + std::to_string(kAsrMaxCols), Y, C, Pc,
-                       with_spa ? (spa ? nullptr : "spa is required") : (!stats && !ua && !rowinfo ? "stats, ua and rowinfo are all NULL" : nullptr),
-                       row0, row1, max_vif, with_spa && !spa_z_ok(spa_z) ? "spa_z must be at least 0.5, or +inf for no correction" : nullptr));
+                       with_corr ? (corr ? nullptr : (with_spa ? "spa is required" : "firth is required"))
+                                 : (!stats && !ua && !rowinfo ? "stats, ua and rowinfo are all NULL" : nullptr),
+                       row0, row1, max_vif,
+                       with_spa && !spa_z_ok(corr_z)       ? "spa_z must be at least 0.5, or +inf for no correction"
+                       : with_firth && !firth_z_ok(corr_z) ? "firth_z must be at least 0, or +inf for no correction"
+                                                           : nullptr));
     const int64_t N = h->N;
     const int L = asr_cols(T, Pc), P = Pc + 1;
     const int64_t npad = asc_npad(N);
@@ -200,9 +233,9 @@ int assoc_logistic(gpca_handle* h, const std::string& f, const double* Y, int32_
     if (rc != GPCA_OK) return fail(h, rc, f + ": " + msg);
     const int64_t ns = (int64_t)D.S.size();
     std::vector<float> Bt((size_t)asc_b_capacity(N, L), 0.0f);
-    // (the correction's: Z_t = X L_t^-T and mu_t in f64, 0 outside S and past N; with spa_z = +inf no item is corrected: the flag
+    // (a correction's: Z_t = X L_t^-T and mu_t in f64, 0 outside S and past N; with spa_z / firth_z = +inf no item is corrected: the flag
     // kernel alone runs, and the correction's inputs and workspace are neither built nor allocated)
-    const bool correct = with_spa && std::isfinite(spa_z);
+    const bool correct = with_corr && std::isfinite(corr_z);
     const int64_t gpad = asp_gpad(N);
     std::vector<double> Zh(correct ? (size_t)asp_z_capacity(N, T, Pc) : 0, 0.0), muh(correct ? (size_t)asp_mu_capacity(N, T) : 0, 0.0);
     {
@@ -232,16 +265,13 @@ int assoc_logistic(gpca_handle* h, const std::string& f, const double* Y, int32_
     }
     const int64_t rows = row1 - row0;
     if (rows == 0) return GPCA_OK;
-    const bool dstats = stats || with_spa;                      // (the flag kernel reads z from the device's stats)
+    const int64_t out_cap = with_firth ? afi_out_capacity(rows, T) : asp_out_capacity(rows, T);
+    const bool dstats = stats || with_corr;                     // (the flag kernel reads z from the device's stats)
     if (asr_count_blocks(rows) >= ((int64_t)1 << 31)) return fail(h, GPCA_ERR_BAD_ARG, f + ": the band makes 2^31 or more workgroups: ask for fewer rows");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->st));
     CHK(preflight_device_memory(h, f.c_str(), "the band needs",
-                                4.0 * (double)asc_b_capacity(N, L) + 4.0 * (double)asc_inc_capacity(N) + 8.0 * (double)asr_dv_capacity(rows, L) +
-                                    4.0 * (double)asr_sums_capacity(rows) + (dstats ? 8.0 * (double)asr_stats_capacity(rows, T) : 0.0) +
-                                    (with_spa ? 8.0 * (double)asp_out_capacity(rows, T) + 4.0 * (double)asp_list_capacity(rows, T) : 0.0) +
-                                    (correct ? 8.0 * (double)(asp_g_capacity(N) + asp_z_capacity(N, T, Pc) + asp_mu_capacity(N, T)) : 0.0) +
-                                    (ua ? 8.0 * (double)asr_ua_capacity(rows, T, Pc) : 0.0) + (rowinfo ? 8.0 * (double)asr_info_capacity(rows) : 0.0) +
+                                asr_call_bytes(N, rows, T, Pc, dstats, ua != nullptr, rowinfo != nullptr, with_corr ? out_cap : 0, correct) +
                                     (double)(64 << 20)));
     const bool packed = h->storage == GPCA_STORE_2BIT;
     const auto [G, ldr] = panel_rows(h, resident_view(h));
@@ -255,8 +285,8 @@ int assoc_logistic(gpca_handle* h, const std::string& f, const double* Y, int32_
     HIPCHK(hipMemcpyAsync(ws.Bt, Bt.data(), Bt.size() * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(ws.incw, incw.data(), incw.size() * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(ws.bad, 0xff, 8, st));
-    if (with_spa) {
-        HIPCHK(dalloc(ws.spa, (size_t)asp_out_capacity(rows, T))); HIPCHK(dalloc(ws.list, (size_t)asp_list_capacity(rows, T)));
+    if (with_corr) {
+        HIPCHK(dalloc(ws.corr, (size_t)out_cap)); HIPCHK(dalloc(ws.list, (size_t)asp_list_capacity(rows, T)));
         HIPCHK(dalloc(ws.count, 1));
     }
     if (correct) {
@@ -280,23 +310,25 @@ int assoc_logistic(gpca_handle* h, const std::string& f, const double* Y, int32_
     }
     launch_assoc_score_finish(st, ws.dv, ws.sums, T, Pc, max_vif, rows, ws.stats, ws.ua, ws.info);
     HIPCHK(hipGetLastError());
-    if (with_spa) {
-        ScopedTimer t(h, "assoc_spa", 0.0, 0.0);
+    if (with_corr) {
+        ScopedTimer t(h, with_firth ? "assoc_firth" : "assoc_spa", 0.0, 0.0);
         const int64_t items = rows * (int64_t)T;
         for (int64_t item0 = 0; item0 < items; item0 += kAspListItems) {
             HIPCHK(hipMemsetAsync(ws.count, 0, 4, st));
-            launch_assoc_spa_flag(st, ws.stats, ws.dv, T, Pc, item0, std::min<int64_t>(kAspListItems, items - item0), spa_z, ws.spa, ws.list, ws.count);
+            const int64_t nitems = std::min<int64_t>(kAspListItems, items - item0);
+            if (with_firth) launch_assoc_firth_flag(st, ws.stats, T, item0, nitems, corr_z, ws.corr, ws.list, ws.count);
+            else launch_assoc_spa_flag(st, ws.stats, ws.dv, T, Pc, item0, nitems, corr_z, ws.corr, ws.list, ws.count);
             HIPCHK(hipGetLastError());
             if (!correct) continue;
-            if (launch_assoc_spa(st, G, packed, ldr, h->d_pca_rows, N, ws.incw, ws.sums, ws.dv, ws.Z, ws.mu, T, Pc, row0, item0, ws.list, ws.count,
-                                 ws.g, ws.spa) != 0)
+            if ((with_firth ? launch_assoc_firth : launch_assoc_spa)(st, G, packed, ldr, h->d_pca_rows, N, ws.incw, ws.sums, ws.dv, ws.Z, ws.mu, T, Pc,
+                                                                     row0, item0, ws.list, ws.count, ws.g, ws.corr) != 0)
                 return fail(h, GPCA_ERR_BAD_ARG, f + ": the launch was refused");
             HIPCHK(hipGetLastError());
         }
     }
     CHK(asc_check_genotypes(h, f, ws.bad, st));
     return asc_copy_outputs(h, st, {{stats, ws.stats, asr_stats_capacity(rows, T)}, {ua, ws.ua, asr_ua_capacity(rows, T, Pc)},
-                                    {rowinfo, ws.info, asr_info_capacity(rows)}, {spa, ws.spa, asp_out_capacity(rows, T)}});
+                                    {rowinfo, ws.info, asr_info_capacity(rows)}, {corr, ws.corr, with_corr ? out_cap : 0}});
 }
 }  // namespace
 
@@ -317,6 +349,22 @@ extern "C" int gpca_spa_log10p(const double* gt, const double* mu, int64_t n, do
     *log10p = r.log10p;
     if (zeta) { zeta[0] = r.zeta[0]; zeta[1] = r.zeta[1]; }
     if (status) *status = r.status;
+    return GPCA_OK;
+}
+
+extern "C" int gpca_firth_log10p(const double* gt, const double* mu, int64_t n, double u, double* out) {
+#pragma clang fp contract(off)
+    if (!gt || !mu || n < 1 || !out || !std::isfinite(u)) return GPCA_ERR_BAD_ARG;
+    double V = 0.0, gmax = 0.0;
+    for (int64_t i = 0; i < n; ++i) {
+        if (!std::isfinite(gt[i]) || !(mu[i] >= 0.0 && mu[i] <= 1.0)) return GPCA_ERR_BAD_ARG;
+        gmax = std::fmax(gmax, std::fabs(gt[i]));
+        V = V + (1.0 - mu[i]) * mu[i] * (gt[i] * gt[i]);
+    }
+    const HostFirthEval ev{gt, mu, n};
+    FirthResult r;
+    firth_item(ev, u, gmax, u == 0.0 ? 0.0 : spa_normal_log10p(u / std::sqrt(V)), r);
+    out[0] = r.log10p; out[1] = (double)r.status; out[2] = r.beta; out[3] = r.se; out[4] = r.lrt;
     return GPCA_OK;
 }
 

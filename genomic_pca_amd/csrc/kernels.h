@@ -385,4 +385,13 @@ int launch_assoc_spa(hipStream_t st, const void* G, int packed, int64_t ldr, con
                      const unsigned* sums, const double* dv, const double* Z, const double* mu, int T, int Pc, int64_t row0, int64_t item0,
                      const int* list, const unsigned* count, double* gws, double* out);
 
+// ---- Firth correction of the score scan (assoc_firth.hip): the same ranges, list and buffers as the saddle-point correction's
+// out [rows][T][kAfiWidth] = the normal -log10 p, status 0, NaN, NaN, NaN; list [*count] = the items with finite |z| >= firth_z
+void launch_assoc_firth_flag(hipStream_t st, const double* stats, int T, int64_t item0, int64_t nitems, double firth_z, double* out, int* list,
+                             unsigned* count);
+// the listed items' out = -log10 p, status, beta of A1, se, D; the arguments are launch_assoc_spa's
+int launch_assoc_firth(hipStream_t st, const void* G, int packed, int64_t ldr, const int64_t* krows, int64_t N, const unsigned* incw,
+                       const unsigned* sums, const double* dv, const double* Z, const double* mu, int T, int Pc, int64_t row0, int64_t item0,
+                       const int* list, const unsigned* count, double* gws, double* out);
+
 }  // namespace gpca

@@ -360,4 +360,26 @@ constexpr int64_t asp_mu_capacity(int64_t N, int T) { return (int64_t)T * asp_gp
 constexpr int64_t asp_list_capacity(int64_t rows, int T) { return rows * (int64_t)T < kAspListItems ? rows * (int64_t)T : kAspListItems; }
 constexpr int64_t asp_out_capacity(int64_t rows, int T) { return 4 * rows * (int64_t)T; }
 
+// ---- Firth correction of the score scan (assoc_firth.hip, gpca_assoc_score.cpp) ----------------------------------------------------
+// The item ranges, the persistent workgroups, the chunks and the buffers g~, Z, mu and list are the saddle-point correction's (asp_*
+// above); only the result differs: out [rows][T][kAfiWidth] (f64) = -log10 p, status, beta, se, the likelihood-ratio statistic
+constexpr int kAfiWidth = 5;
+constexpr int64_t afi_out_capacity(int64_t rows, int T) { return (int64_t)kAfiWidth * rows * (int64_t)T; }
+
+// The device bytes a logistic scan allocates for a band of `rows` kept rows (gpca_assoc_score.cpp: the sum its GPCA_ERR_OOM check takes
+// before any allocation, without that check's slack).  dstats / ua / info: the buffer exists; corr_out: the elements of a
+// correction's result (asp_out_capacity or afi_out_capacity; 0 without a correction); correct: some item may be corrected (the
+// cutoff is finite), so Z, mu and the slices of g~ exist.
+constexpr double asr_call_bytes(int64_t N, int64_t rows, int T, int Pc, bool dstats, bool ua, bool info, int64_t corr_out, bool correct) {
+    const int L = asr_cols(T, Pc);
+    double b = 4.0 * (double)asc_b_capacity(N, L) + 4.0 * (double)asc_inc_capacity(N) + 8.0 /* the invalid-genotype word */ +
+               8.0 * (double)asr_dv_capacity(rows, L) + 4.0 * (double)asr_sums_capacity(rows);
+    if (dstats) b += 8.0 * (double)asr_stats_capacity(rows, T);
+    if (ua) b += 8.0 * (double)asr_ua_capacity(rows, T, Pc);
+    if (info) b += 8.0 * (double)asr_info_capacity(rows);
+    if (corr_out > 0) b += 8.0 * (double)corr_out + 4.0 * (double)asp_list_capacity(rows, T) + 4.0 /* the list's counter */;
+    if (correct) b += 8.0 * (double)(asp_g_capacity(N) + asp_z_capacity(N, T, Pc) + asp_mu_capacity(N, T));
+    return b;
+}
+
 }  // namespace gpca

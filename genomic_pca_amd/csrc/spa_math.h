@@ -3,6 +3,8 @@
 // for K'(zeta) = c, and the Lugannani-Rice tail.  The caller supplies the sums over the samples (Eval): the host function
 // gpca_spa_log10p adds them in sample order, the kernel k_assoc_spa (assoc_spa.hip) through its workgroup's fixed tree.  Everything is
 // f64; the saddle-point functions allow no fused contraction.
+// The approximate Firth correction (section a15) follows them at the end: it is a function of the same K, so its pass is made of the
+// same per-sample terms plus those of K''' and K'''', and gpca_firth_log10p and k_assoc_firth (assoc_firth.hip) run its root rule.
 #pragma once
 #include <cmath>
 
@@ -52,16 +54,24 @@ GPCA_HD inline bool spa_z_ok(double spa_z) { return spa_z >= kSpaMinZ; }
 //                                                                    = w g expm1(a) / ((1 - mu) + mu e)        for a <= 0;
 //     K'' term = w g^2 e^a / (1 - mu + mu e^a)^2                    = w g^2 e / D^2 with the same denominator D.
 // No exponential of a positive argument is taken, so neither sign of a overflows.  A sample with w = 0 adds nothing.
-GPCA_HD inline void spa_terms12(double g, double mu, double tau, double& k1, double& k2) {
+// (spa_terms12_pw also leaves the tilted probability p = mu e^a / (1 - mu + mu e^a) = mu / D for a > 0, mu e / D for a <= 0, and
+// wt = p (1 - p) = w e / D^2: the Firth correction's higher terms below are made of them.)
+GPCA_HD inline void spa_terms12_pw(double g, double mu, double tau, double& k1, double& k2, double& p, double& wt) {
 #pragma clang fp contract(off)
     const double w = (1.0 - mu) * mu;
-    if (!(w > 0.0)) { k1 = 0.0; k2 = 0.0; return; }
+    if (!(w > 0.0)) { k1 = 0.0; k2 = 0.0; p = mu; wt = 0.0; return; }
     const double a = g * tau, na = -std::fabs(a);
     const double e = std::exp(na), em = std::expm1(na);
     const bool pos = a > 0.0;
     const double D = pos ? (1.0 - mu) * e + mu : (1.0 - mu) + mu * e;
     k1 = w * g * ((pos ? -em : em) / D);
     k2 = w * (g * g) * e / (D * D);
+    p = (pos ? mu : mu * e) / D;
+    wt = w * e / (D * D);
+}
+GPCA_HD inline void spa_terms12(double g, double mu, double tau, double& k1, double& k2) {
+    double p, wt;
+    spa_terms12_pw(g, mu, tau, k1, k2, p, wt);
 }
 // One sample's term of K(tau) = log1p(mu expm1(a)) - a mu; for a > 0 as a (1 - mu) + log1p((1 - mu) expm1(-a)).
 GPCA_HD inline double spa_term0(double g, double mu, double tau) {
@@ -152,6 +162,82 @@ GPCA_HD inline void spa_item(Eval& ev, double u, double hi, double lo, double no
     o.status = 1;
     const double m = nl0 < nl1 ? nl0 : nl1, M = nl0 < nl1 ? nl1 : nl0;
     o.log10p = std::isinf(m) ? m : m - std::log1p(std::pow(10.0, -(M - m))) / std::log(10.0);
+}
+
+// ---- The approximate Firth correction (include/gpca.h section a15): one coefficient beta on g~ with the null model's linear predictor
+// as a fixed offset.  Its penalised log-likelihood ratio is f(beta) = beta U - K(beta) + (1/2) log(K''(beta) / K''(0)) with the K of the
+// saddle-point correction, so a pass over the samples returns K, K', K'' (the terms above) and
+//     K'''  = sum g^3 wt (1 - 2 p),    K'''' = sum g^4 wt (1 - 6 wt),    p the tilted probability, wt = p (1 - p).
+constexpr int kFirthMaxSteps = 50, kFirthMaxHalvings = 10;
+constexpr double kFirthStop = 1e-10, kFirthSmall = 1e-4, kFirthMaxArg = 5.0;
+
+// firth_z is +inf (no item is corrected) or any value >= 0
+GPCA_HD inline bool firth_z_ok(double firth_z) { return firth_z >= 0.0; }
+
+// One sample's terms of K' .. K'''' at beta
+GPCA_HD inline void firth_terms1234(double g, double mu, double beta, double& k1, double& k2, double& k3, double& k4) {
+#pragma clang fp contract(off)
+    double p, wt;
+    spa_terms12_pw(g, mu, beta, k1, k2, p, wt);
+    const double g2 = g * g;
+    k3 = g2 * g * wt * (1.0 - 2.0 * p);
+    k4 = g2 * g2 * wt * (1.0 - 6.0 * wt);
+}
+
+struct FirthResult {
+    double log10p;          // -log10 of the chi^2_1 p of D
+    int status;             // 1: corrected, 2: the rule failed (log10p is the normal value; beta, se, lrt what was reached)
+    double beta, se, lrt;   // the estimate in the operand's coding, 1 / sqrt(K''(beta)), D = max(2 f(beta), 0)
+    int passes;             // evaluations of the sums
+};
+
+// Section a15 for one item: u = U, gmax = max |g~_n|, normal = -log10 p of the normal approximation.  ev(beta, k0, k1, k2, k3, k4)
+// leaves the five sums at beta.  The pass at 0, a Newton step's pass and the passes of its halvings share one call of ev (one copy of
+// the pass over the samples in a kernel): `first` says that the pass in hand is the one at 0, which is accepted as it is.
+template <class Eval>
+GPCA_HD inline void firth_item(Eval& ev, double u, double gmax, double normal, FirthResult& o) {
+#pragma clang fp contract(off)
+    double beta = 0.0, f = 0.0, K2 = 0.0, K20 = 0.0, te = 0.0, step = 0.0;
+    bool first = true, small = false, ok = false;
+    int rep = 0, h = 0;
+    o.passes = 0;
+    for (;;) {
+        double k0 = 0.0, k1 = 0.0, k2 = 0.0, k3 = 0.0, k4 = 0.0;
+        ev(te, k0, k1, k2, k3, k4);
+        ++o.passes;
+        double ft = 0.0;
+        if (first) {
+            K20 = k2; K2 = k2;
+            if (!(k2 > 0.0) || !std::isfinite(k2)) break;                        // no information at 0: failed
+            first = false;
+        } else {
+            ft = te * u - k0 + 0.5 * std::log(k2 / K20);
+            if (!(std::isfinite(ft) && k2 > 0.0 && (small || ft >= f))) {
+                if (h == kFirthMaxHalvings) break;                               // none accepted: failed
+                ++h;
+                step = step * 0.5;
+                te = beta + step;
+                continue;
+            }
+        }
+        beta = te; f = ft; K2 = k2;
+        if (rep == kFirthMaxSteps) break;                                        // not converged
+        ++rep;
+        const double us = u - k1 + k3 / (2.0 * k2);
+        const double d = -k2 + (k4 * k2 - k3 * k3) / (2.0 * (k2 * k2));
+        double delta = d < 0.0 ? -us / d : us / k2;
+        if (!std::isfinite(delta)) break;
+        if (std::fabs(delta) <= kFirthStop * (1.0 + std::fabs(beta))) { ok = true; break; }
+        if (std::fabs(delta) * gmax > kFirthMaxArg) delta = spa_sign(delta) * kFirthMaxArg / gmax;
+        small = std::fabs(delta) <= kFirthSmall * (1.0 + std::fabs(beta));
+        h = 0;
+        step = delta;
+        te = beta + step;
+    }
+    const double D = 2.0 * f > 0.0 ? 2.0 * f : 0.0;
+    o.beta = beta; o.se = 1.0 / std::sqrt(K2); o.lrt = D;
+    o.status = ok ? 1 : 2;
+    o.log10p = ok ? spa_normal_log10p(std::sqrt(D)) : normal;
 }
 
 }  // namespace gpca

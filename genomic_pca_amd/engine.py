@@ -564,12 +564,27 @@ class GpcaEngine:
         normal value of z (spa_status 0).  zeta are the two tails' roots in the operand's coding; NaN statistics give NaN."""
         return self._assoc_logistic(Y, covar, include, max_vif, float(spa_z), rows, ua)
 
-    def _assoc_logistic(self, Y, covar, include, max_vif, spa_z, rows, ua):
+    def assoc_logistic_firth(self, Y, covar=None, include=None, max_vif: float = 50.0, firth_z: float = 1.959964,
+                             rows: Optional[Tuple[int, int]] = None, ua: bool = False):
+        """Logistic score scan with the approximate Firth correction (gpca_assoc_logistic_firth): assoc_logistic_score's arguments and
+        its dict with the same bits, and beside them log10p, firth_status, firth_beta, firth_se, firth_lrt [rows][T].  Where
+        |z| >= firth_z (at least 0, or inf for no correction; two-sided 0.05 by default) one coefficient on the covariate-adjusted
+        genotype is fitted by Firth's penalised likelihood with the null model as offset: -log10 p is the chi^2_1 value of the penalised
+        likelihood-ratio statistic firth_lrt, firth_beta (for allele A1) and firth_se = 1 / sqrt(information) are finite under
+        separation (firth_status 1; 2 where the root rule failed: the normal value); elsewhere -log10 p is the normal value of z and
+        the rest NaN (firth_status 0)."""
+        return self._assoc_logistic(Y, covar, include, max_vif, None, rows, ua, firth_z=float(firth_z))
+
+    def _assoc_logistic(self, Y, covar, include, max_vif, spa_z, rows, ua, firth_z=None):
         Yv, Cv, inc, T, Pc, r0, r1, n = self._assoc_args(Y, covar, include, rows)
         stats = np.zeros((max(n, 1), max(T, 1), 5), np.float64)
         info = np.zeros((max(n, 1), 5), np.float64)
         out_ua = np.zeros((max(n, 1), max(T, 1), Pc + 3), np.float64) if ua else None
-        if spa_z is None:
+        if firth_z is not None:
+            firth = np.zeros((max(n, 1), max(T, 1), 5), np.float64)
+            self._chk(self._lib.gpca_assoc_logistic_firth(self._h, _vp(Yv), T, _vp(Cv) if Pc else None, Pc, _vp(inc), float(max_vif), firth_z,
+                                                          r0, r1, _vp(stats), _vp(firth), _vp(out_ua), _vp(info)))
+        elif spa_z is None:
             self._chk(self._lib.gpca_assoc_logistic_score(self._h, _vp(Yv), T, _vp(Cv) if Pc else None, Pc, _vp(inc), float(max_vif), r0, r1,
                                                           _vp(stats), _vp(out_ua), _vp(info)))
         else:
@@ -580,7 +595,10 @@ class GpcaEngine:
                "n_obs": info[:n, 0], "a1_freq": info[:n, 1], "xx": info[:n, 2], "flipped": info[:n, 3]}
         if ua:
             res["ua"] = out_ua[:n]
-        if spa_z is not None:
+        if firth_z is not None:
+            res.update(log10p=firth[:n, :, 0], firth_status=firth[:n, :, 1], firth_beta=firth[:n, :, 2], firth_se=firth[:n, :, 3],
+                       firth_lrt=firth[:n, :, 4])
+        elif spa_z is not None:
             res.update(log10p=spa[:n, :, 0], spa_status=spa[:n, :, 1], zeta=spa[:n, :, 2:4])
         return res
 
@@ -615,6 +633,21 @@ class GpcaEngine:
         if rc != 0:
             raise GpcaError(rc, "gpca_spa_log10p: " + lib.gpca_status_string(rc).decode())
         return float(lp.value), int(st.value), (float(zeta[0]), float(zeta[1]))
+
+    @staticmethod
+    def firth_log10p(gt, mu, u: float):
+        """The approximate Firth correction for one given vector (gpca_firth_log10p; host only): gt, mu and u as for spa_log10p.
+        Returns (-log10 p, status, beta, se, lrt): status 1 for the correction, 2 where the root rule failed (the normal value of
+        u / sqrt(sum mu (1 - mu) gt^2); beta, se and lrt what was reached).  There is no cutoff."""
+        gv, mv = np.ascontiguousarray(gt, np.float64).reshape(-1), np.ascontiguousarray(mu, np.float64).reshape(-1)
+        if gv.shape != mv.shape:
+            raise ValueError("gt and mu must have one entry per sample each")
+        out = np.zeros(5)
+        lib = _lib.load()
+        rc = lib.gpca_firth_log10p(_vp(gv), _vp(mv), gv.shape[0], float(u), _vp(out))
+        if rc != 0:
+            raise GpcaError(rc, "gpca_firth_log10p: " + lib.gpca_status_string(rc).decode())
+        return float(out[0]), int(out[1]), float(out[2]), float(out[3]), float(out[4])
 
     @staticmethod
     def normal_log10p(z: float) -> float:

@@ -885,15 +885,20 @@ inline std::vector<std::pair<int64_t, int64_t>> assoc_score_bands(int64_t K, int
 
 // the rule of gpca_assoc_logistic_spa's cutoff (io.spa_z_ok): at least 0.5, or inf (no correction); NaN is refused
 inline bool spa_z_ok(double x) { return x >= 0.5; }
+// the rule of gpca_assoc_logistic_firth's cutoff (io.firth_z_ok): at least 0, or inf (no correction); NaN is refused
+inline bool firth_z_ok(double x) { return x >= 0.0; }
 
 // P.<trait>.assoc.logistic: one tab-separated line per SNP, `#CHROM POS ID A1 OBS_CT A1_FREQ BETA SE Z_STAT LOG10P`; numbers as %.6g,
 // NaN as NA, OBS_CT as an integer; rows are added band by band.  spa = true adds the column `SPA`: N, Y, F for the status 0, 1, 2 of the
-// saddle-point correction (gpca_assoc_logistic_spa), NA where LOG10P is NA
+// saddle-point correction (gpca_assoc_logistic_spa), NA where LOG10P is NA.  firth = true (not both) adds the column `FIRTH` in the same
+// way for the Firth correction (gpca_assoc_logistic_firth); the caller passes Firth's BETA and SE on the rows with status 1
 class AssocLogisticWriter {
 public:
-    AssocLogisticWriter(const std::string& prefix, const std::string& trait, bool spa = false)
-        : o_(prefix + "." + trait + ".assoc.logistic"), spa_(spa) {
-        std::fputs(spa ? "#CHROM\tPOS\tID\tA1\tOBS_CT\tA1_FREQ\tBETA\tSE\tZ_STAT\tLOG10P\tSPA\n" : "#CHROM\tPOS\tID\tA1\tOBS_CT\tA1_FREQ\tBETA\tSE\tZ_STAT\tLOG10P\n", o_.f);
+    AssocLogisticWriter(const std::string& prefix, const std::string& trait, bool spa = false, bool firth = false)
+        : o_(prefix + "." + trait + ".assoc.logistic"), spa_(spa || firth) {
+        if (spa && firth) throw std::runtime_error("AssocLogisticWriter: spa or firth, not both");
+        std::fputs("#CHROM\tPOS\tID\tA1\tOBS_CT\tA1_FREQ\tBETA\tSE\tZ_STAT\tLOG10P", o_.f);
+        std::fputs(spa ? "\tSPA\n" : (firth ? "\tFIRTH\n" : "\n"), o_.f);
     }
     void add_row(const std::string& chrom, int64_t pos, const std::string& id, const std::string& a1, double n_obs, double a1_freq, double beta,
                  double se, double z, double log10p, int spa_status = 0) {

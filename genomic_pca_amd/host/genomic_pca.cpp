@@ -63,6 +63,9 @@ struct Args {
     bool assoc_spa = false;           // --gpca-assoc-spa: the saddle-point correction of the logistic score scan
     bool have_assoc_spa_z = false;
     double assoc_spa_z = 2.0;         // --gpca-assoc-spa-z X
+    bool assoc_firth = false;         // --gpca-assoc-firth: the approximate Firth correction of the logistic score scan
+    bool have_assoc_firth_z = false;
+    double assoc_firth_z = 1.959964;  // --gpca-assoc-firth-z X
     gpca_host::PhenoTable assoc_pheno_table, assoc_covar_table;   // read in main, before any work on the device
 };
 
@@ -160,7 +163,8 @@ void print_help() {
         "                                       covariates <= 64\n"
         "      --gpca-assoc-logistic            --gpca-assoc-pheno: a trait column whose present values are exactly {0, 1} (1 = case) or\n"
         "                                       {1, 2} (plink's coding, 2 = case) gets the logistic score test (the null model fitted\n"
-        "                                       once per trait; no Firth correction; --gpca-assoc-spa adds the saddle-point correction)\n"
+        "                                       once per trait; --gpca-assoc-spa adds the saddle-point correction, --gpca-assoc-firth the\n"
+        "                                       approximate Firth correction)\n"
         "                                       -> P.<trait>.assoc.logistic (#CHROM POS ID A1 OBS_CT A1_FREQ BETA SE Z_STAT LOG10P); the\n"
         "                                       other columns go through the linear scan as without the flag.  PCs + covariates + 3 <= 64\n"
         "      --gpca-assoc-spa                 --gpca-assoc-logistic: the saddle-point correction (SPA, as SAIGE and regenie --spa) of\n"
@@ -170,6 +174,13 @@ void print_help() {
         "                                       or F (the correction did not converge: the normal value); BETA, SE and Z_STAT stay the\n"
         "                                       score test's\n"
         "      --gpca-assoc-spa-z <X>           --gpca-assoc-spa: the cutoff, at least 0.5, or inf for no correction [default: 2]\n"
+        "      --gpca-assoc-firth               --gpca-assoc-logistic: the approximate Firth correction (as regenie --firth --approx) of\n"
+        "                                       every test with |Z_STAT| >= the cutoff: one coefficient on the covariate-adjusted\n"
+        "                                       genotype by Firth's penalised likelihood, the null model as offset.  BETA, SE and LOG10P\n"
+        "                                       are then Firth's (finite where every carrier is a case), Z_STAT stays the score test's,\n"
+        "                                       and a column FIRTH says Y (corrected), N (below the cutoff) or F (the fit failed: the\n"
+        "                                       score test's values).  Not together with --gpca-assoc-spa\n"
+        "      --gpca-assoc-firth-z <X>         --gpca-assoc-firth: the cutoff, at least 0, or inf for no correction [default: 1.959964]\n"
         "      --gpca-assoc-pcs <P>             --gpca-assoc-pheno: the first P columns of the scores this run writes are covariates\n"
         "                                       (0 <= P <= --eigensnp-k-global) [default: every column]\n"
         "      --gpca-assoc-covar <FILE>        --gpca-assoc-pheno: further covariates, a table in the format of the phenotype file\n"
@@ -253,6 +264,8 @@ Args parse(int argc, char** argv) {
         else if (f == "--gpca-assoc-logistic") a.assoc_logistic = true;
         else if (f == "--gpca-assoc-spa") a.assoc_spa = true;
         else if (f == "--gpca-assoc-spa-z") { a.assoc_spa_z = to_f64(f, val()); a.have_assoc_spa_z = true; }
+        else if (f == "--gpca-assoc-firth") a.assoc_firth = true;
+        else if (f == "--gpca-assoc-firth-z") { a.assoc_firth_z = to_f64(f, val()); a.have_assoc_firth_z = true; }
         else if (f == "--gpca-assoc-pcs") { a.assoc_pcs = to_i64(f, val()); a.have_assoc_pcs = true; }
         else if (f == "--gpca-assoc-vif") { a.assoc_vif = to_f64(f, val()); a.have_assoc_vif = true; }
         else if (f == "--gpca-indep-pairwise") {
@@ -475,19 +488,22 @@ int run_assoc(gpca::Engine& eng, const Args& a, const gpca_host::PlinkFileset& f
                 for (int64_t s = 0; s < n; ++s)
                     for (int32_t t = 0; t < Tg; ++t) Yg[(size_t)s * Tg + t] = Yb[(size_t)s * Tb + (size_t)g.first + t];
                 std::vector<std::unique_ptr<gpca_host::AssocLogisticWriter>> w;
-                for (int32_t t = 0; t < Tg; ++t) w.emplace_back(new gpca_host::AssocLogisticWriter(a.output_prefix, bnames[(size_t)g.first + t], a.assoc_spa));
+                for (int32_t t = 0; t < Tg; ++t) w.emplace_back(new gpca_host::AssocLogisticWriter(a.output_prefix, bnames[(size_t)g.first + t], a.assoc_spa, a.assoc_firth));
                 for (const auto& b : gpca_host::assoc_score_bands((int64_t)rows.size(), Tg, Pc)) {
-                    std::vector<double> stats, info, spa;
-                    if (a.assoc_spa) eng.assoc_logistic_spa(Yg, Tg, C, Pc, &include, a.assoc_vif, a.assoc_spa_z, b.first, b.second, stats, spa, info);
+                    std::vector<double> stats, info, spa, firth;
+                    if (a.assoc_firth) eng.assoc_logistic_firth(Yg, Tg, C, Pc, &include, a.assoc_vif, a.assoc_firth_z, b.first, b.second, stats, firth, info);
+                    else if (a.assoc_spa) eng.assoc_logistic_spa(Yg, Tg, C, Pc, &include, a.assoc_vif, a.assoc_spa_z, b.first, b.second, stats, spa, info);
                     else eng.assoc_logistic_score(Yg, Tg, C, Pc, &include, a.assoc_vif, b.first, b.second, stats, info);
                     for (int64_t r = b.first; r < b.second; ++r) {
                         const size_t i = (size_t)(r - b.first), o = (size_t)rows[(size_t)r];
                         for (int32_t t = 0; t < Tg; ++t) {
                             const double* s5 = &stats[(i * (size_t)Tg + (size_t)t) * 5];
                             const double* s4 = a.assoc_spa ? &spa[(i * (size_t)Tg + (size_t)t) * 4] : nullptr;
-                            const double lp = s4 ? s4[0] : (s5[2] != s5[2] ? std::nan("") : gpca_normal_log10p(s5[2]));
-                            w[(size_t)t]->add_row(fs.chromosomes[o], fs.positions[o], fs.variant_ids[o], fs.allele1[o], info[5 * i], info[5 * i + 1], s5[0], s5[1], s5[2], lp,
-                                                  s4 ? (int)s4[1] : 0);
+                            const double* f5 = a.assoc_firth ? &firth[(i * (size_t)Tg + (size_t)t) * 5] : nullptr;
+                            const double lp = f5 ? f5[0] : (s4 ? s4[0] : (s5[2] != s5[2] ? std::nan("") : gpca_normal_log10p(s5[2])));
+                            const bool fy = f5 && f5[1] == 1.0;                     // (corrected: BETA and SE are Firth's)
+                            w[(size_t)t]->add_row(fs.chromosomes[o], fs.positions[o], fs.variant_ids[o], fs.allele1[o], info[5 * i], info[5 * i + 1],
+                                                  fy ? f5[2] : s5[0], fy ? f5[3] : s5[1], s5[2], lp, f5 ? (int)f5[1] : (s4 ? (int)s4[1] : 0));
                         }
                     }
                 }
@@ -842,6 +858,13 @@ int main(int argc, char** argv) {
         if (a.have_assoc_spa_z && !a.assoc_spa) { std::fprintf(stderr, "error: --gpca-assoc-spa-z needs --gpca-assoc-spa\n"); return 2; }
         if (a.have_assoc_spa_z && !gpca_host::spa_z_ok(a.assoc_spa_z)) {
             std::fprintf(stderr, "error: --gpca-assoc-spa-z must be at least 0.5, or inf for no correction\n");
+            return 2;
+        }
+        if (a.assoc_firth && !a.assoc_logistic) { std::fprintf(stderr, "error: --gpca-assoc-firth needs --gpca-assoc-logistic\n"); return 2; }
+        if (a.assoc_firth && a.assoc_spa) { std::fprintf(stderr, "error: --gpca-assoc-firth and --gpca-assoc-spa exclude each other\n"); return 2; }
+        if (a.have_assoc_firth_z && !a.assoc_firth) { std::fprintf(stderr, "error: --gpca-assoc-firth-z needs --gpca-assoc-firth\n"); return 2; }
+        if (a.have_assoc_firth_z && !gpca_host::firth_z_ok(a.assoc_firth_z)) {
+            std::fprintf(stderr, "error: --gpca-assoc-firth-z must be at least 0, or inf for no correction\n");
             return 2;
         }
         if (!a.assoc_pheno.empty()) {

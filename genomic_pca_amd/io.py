@@ -829,13 +829,23 @@ def spa_z_ok(x) -> bool:
     return bool(float(x) >= 0.5)
 
 
+def firth_z_ok(x) -> bool:
+    """The rule of gpca_assoc_logistic_firth's cutoff: at least 0, or inf (no correction); NaN is refused."""
+    return bool(float(x) >= 0.0)
+
+
 def write_assoc_logistic(prefix: str, trait: str, chromosomes: Sequence[str], positions: Sequence[int], variant_ids: Sequence[str],
-                         allele1: Sequence[str], n_obs, a1_freq, beta, se, z, log10p, append: bool = False, spa=None) -> str:
+                         allele1: Sequence[str], n_obs, a1_freq, beta, se, z, log10p, append: bool = False, spa=None, firth=None) -> str:
     """P.<trait>.assoc.logistic: one tab-separated line per SNP, `#CHROM POS ID A1 OBS_CT A1_FREQ BETA SE Z_STAT LOG10P`; numbers as
     %.6g, NaN as NA, OBS_CT as an integer.  append=True adds the rows of a further band to the file (no header).  spa: the status of
-    the saddle-point correction per SNP (gpca_assoc_logistic_spa: 0, 1, 2) adds the column `SPA` = N, Y, F (NA where LOG10P is NA)."""
+    the saddle-point correction per SNP (gpca_assoc_logistic_spa: 0, 1, 2) adds the column `SPA` = N, Y, F (NA where LOG10P is NA).  firth: the status
+    of the Firth correction per SNP (gpca_assoc_logistic_firth) adds the column `FIRTH` in the same way; the caller passes Firth's BETA
+    and SE on the rows with status 1 (Z_STAT stays the score statistic).  Not both."""
     path = f"{prefix}.{trait}.assoc.logistic"
     n = len(variant_ids)
+    if spa is not None and firth is not None:
+        raise ValueError("write_assoc_logistic: spa or firth, not both")
+    name, spa = ("FIRTH", firth) if firth is not None else ("SPA", spa)
     for a in (chromosomes, positions, allele1, n_obs, a1_freq, beta, se, z, log10p) + (() if spa is None else (spa,)):
         if len(a) != n:
             raise ValueError("write_assoc_logistic: one entry per SNP in every column")
@@ -845,7 +855,7 @@ def write_assoc_logistic(prefix: str, trait: str, chromosomes: Sequence[str], po
     tail = (lambda i: "") if spa is None else (lambda i: "\tNA" if log10p[i] != log10p[i] else "\t" + "NYF"[int(spa[i])])
     with open(path, "a" if append else "w") as f:
         if not append:
-            f.write("#CHROM\tPOS\tID\tA1\tOBS_CT\tA1_FREQ\tBETA\tSE\tZ_STAT\tLOG10P" + ("" if spa is None else "\tSPA") + "\n")
+            f.write("#CHROM\tPOS\tID\tA1\tOBS_CT\tA1_FREQ\tBETA\tSE\tZ_STAT\tLOG10P" + ("" if spa is None else "\t" + name) + "\n")
         f.writelines(f"{chromosomes[i]}\t{int(positions[i])}\t{variant_ids[i]}\t{allele1[i]}\t{int(n_obs[i])}\t{_g6(a1_freq[i])}\t{_g6(beta[i])}\t"
                      f"{_g6(se[i])}\t{_g6(z[i])}\t{_g6(log10p[i])}{tail(i)}\n" for i in range(n))
     return path

@@ -461,8 +461,8 @@ GPCA_API double gpca_student_t_log10p(double t, double df);
  * n_obs, a1_freq, xx, flipped (0 / 1), 0: each may be NULL, not all three.  The null fits run inside the call through the function
  * behind gpca_logistic_null; a failure returns its status and names the trait in gpca_last_error.
  * A band is bit-identical to the same rows of the full call; int8 and 2-bit residency give the same bits, and so does a
- * GPCA_PREC_F32_MFMA handle; the sample mask is ignored and no fitted result is touched.  Out of scope: Firth's correction (a14 has
- * the saddle-point correction), a Wald / IRLS fit per SNP, per-variant dropping of samples, case / control frequency columns, mixed
+ * GPCA_PREC_F32_MFMA handle; the sample mask is ignored and no fitted result is touched.  Out of scope (a14 has the saddle-point correction, a15 the
+ * approximate Firth correction): a Wald / IRLS fit per SNP, per-variant dropping of samples, case / control frequency columns, mixed
  * models, and streamed and row-sharded handles: GPCA_ERR_STATE.
  * Errors: GPCA_ERR_STATE (no standardisation, K = 0, a streamed handle, a row-sharded handle), GPCA_ERR_BAD_ARG (T, Pc or the row range
  * out of bounds, all outputs NULL, max_vif < 1 or not finite, and those of step 1), GPCA_ERR_NOT_CONVERGED (step 1),
@@ -517,7 +517,7 @@ GPCA_API double gpca_normal_log10p(double z);
  * Device: the items are flagged and compacted after a13's finish kernel; a workgroup owns an item, reads its row once, keeps g~ in its
  * slice of a workspace bounded independently of the band, and every sum over the samples runs through a fixed tree that depends on N
  * alone (no atomics on sums), so a band is bit-identical to the same rows of the full call and int8, 2-bit and a GPCA_PREC_F32_MFMA
- * handle give the same bits.  Out of scope: Firth's correction, the fast partially-normal variant of SAIGE for non-carriers, and
+ * handle give the same bits.  Out of scope: the fast partially-normal variant of SAIGE for non-carriers, and
  * everything a13 leaves out.
  * Errors: those of gpca_assoc_logistic_score, and GPCA_ERR_BAD_ARG for a NULL spa or an spa_z below 0.5 or NaN.
  * gpca_spa_log10p: the same rules for one given vector g~ [n] with mu [n] (in [0, 1]; a sample with mu (1 - mu) = 0 adds nothing) and
@@ -530,6 +530,58 @@ GPCA_API int gpca_assoc_logistic_spa(gpca_handle* h, const double* Y /* [N][T], 
                                      double* ua /* [rows][T][Pc + 3] or NULL */, double* rowinfo /* [rows][5] or NULL */);
 GPCA_API int gpca_spa_log10p(const double* gt /* [n] */, const double* mu /* [n] */, int64_t n, double u, double* log10p,
                              double* zeta /* [2] or NULL */, int32_t* status /* may be NULL */);
+
+/* ---- a15: the approximate Firth correction of the logistic score scan (Firth 1993; regenie --firth --approx, SAIGE's fallback for the
+ * effect size): one coefficient beta on the covariate-adjusted genotype, fitted by the Jeffreys-penalised likelihood with the null
+ * model's linear predictor held fixed as an offset.  It is the one correction that also repairs the effect size: for a rare variant
+ * whose carriers are all cases a13's beta = U / V means nothing and a maximum-likelihood fit diverges; the Firth estimate is finite.
+ * gpca_assoc_logistic_firth is gpca_assoc_logistic_score (the same path: stats, ua and rowinfo carry the same bits) followed by the
+ * correction of the items (row, trait) with |z| >= firth_z.
+ *  Setting.  That of a14: trait t, kept row i, the operand's coding of a13; g~_n, mu_n, U and Z are those of a14, with the same bits.
+ *     eta_n = logit(mu_n) + beta g~_n.  Because X^T W g~ = 0 the unpenalised log-likelihood ratio of that model is
+ *     l(beta) - l(0) = beta U - K(beta) with K, K', K'' the functions of a14, its score U - K'(beta), its information K''(beta); y is
+ *     not needed on the device.  With Jeffreys' penalty (1/2) log K''(beta):
+ *         f(beta) = beta U - K(beta) + (1/2) log(K''(beta) / K''(0))          (f(0) = 0 exactly)
+ *         u(beta) = U - K'(beta) + K'''(beta) / (2 K''(beta))
+ *         d(beta) = -K''(beta) + (K''''(beta) K''(beta) - K'''(beta)^2) / (2 K''(beta)^2)
+ *         K''' = sum_S g~^3 w (1 - 2 p),  K'''' = sum_S g~^4 w (1 - 6 w),  p = mu e^a / (1 - mu + mu e^a), a = g~ beta, w = p (1 - p)
+ *     each term, like a14's, in the form that takes only e^(-|a|); f64, no fused multiply-add.  A pass at beta returns
+ *     (K, K', K'', K''', K'''').  gmax = max_S |g~_n|.
+ *  Root.
+ *         beta = 0, P = pass(0), f = 0
+ *         for rep = 1 .. 50:
+ *             delta = d < 0 ? -u / d : u / K''            (Newton on u; the Fisher step where f is not concave)
+ *             delta not finite: stop, failed
+ *             |delta| <= 1e-10 (1 + |beta|): converged at beta (the sums in hand are beta's)
+ *             |delta| gmax > 5: delta = sign(delta) 5 / gmax
+ *             small = |delta| <= 1e-4 (1 + |beta|)
+ *             for h = 0 .. 10: beta' = beta + delta 2^-h, P' = pass(beta'), f'; accept if f' is finite, K''(beta') > 0 and (small or f' >= f)
+ *             none accepted: stop, failed
+ *             beta, P, f = beta', P', f'
+ *     50 repetitions without convergence, or K''(0) not positive and finite: failed.  (Without the `small` clause the ascent test
+ *     rejects the last Newton steps on rounding alone.)  The answer is the stationary point this rule reaches from 0; u may have more
+ *     than one root on a very small sample.
+ *  D = max(2 f(beta^), 0); -log10 p = gpca_normal_log10p(sqrt(D)) (chi^2_1); se = 1 / sqrt(K''(beta^)) (logistf's convention); the
+ *     reported beta^ is for allele A1: s beta^ with s of a13.
+ * firth [rows][T][5] = -log10 p, status, beta^, se, D.  status 0: z is not finite or |z| < firth_z: the normal value
+ * gpca_normal_log10p(z), the other three NaN.  1: corrected.  2: the rule failed: the normal value, and beta^, se and D what was
+ * reached.  Where a13 gives NaN statistics everything is NaN with status 0.  firth_z >= 0, or +inf (no item is corrected, and no input
+ * of the correction is built or allocated); 1.959964 is the two-sided 0.05 of regenie's --pThresh.
+ * Device: a14's, with a kernel of its own (assoc_firth.hip): the same flagging and compaction, item ranges, workspace and fixed
+ * summation tree, so a band is bit-identical to the same rows of the full call and int8, 2-bit and a GPCA_PREC_F32_MFMA handle give
+ * the same bits.  Out of scope: the exact Firth test with the covariates refitted per SNP, a Firth-penalised null fit,
+ * profile-likelihood intervals, regenie's own numbers (its choices of offset and of genotype coding are not claimed), and everything
+ * a13 leaves out (streamed and row-sharded handles: GPCA_ERR_STATE).
+ * Errors: those of gpca_assoc_logistic_score, and GPCA_ERR_BAD_ARG for a NULL firth or a firth_z that is negative or NaN.
+ * gpca_firth_log10p: the same rules for one given vector g~ [n] with mu [n] (in [0, 1]; a sample with mu (1 - mu) = 0 adds nothing)
+ * and U = u, sums in sample order; host only, no handle; out [5] as above with beta^ in the given coding.  There is no cutoff: status
+ * is 1 or 2, and the normal value of status 2 is that of u / sqrt(sum mu (1 - mu) g~^2).  GPCA_ERR_BAD_ARG: a NULL vector or out,
+ * n < 1, a non-finite g~ or u, a mu outside [0, 1]. */
+GPCA_API int gpca_assoc_logistic_firth(gpca_handle* h, const double* Y /* [N][T], 0 / 1 */, int32_t T, const double* C /* [N][Pc] or NULL */,
+                                       int32_t Pc, const uint8_t* include /* [N] or NULL */, double max_vif, double firth_z, int64_t row0,
+                                       int64_t row1, double* stats /* [rows][T][5] or NULL */, double* firth /* [rows][T][5] */,
+                                       double* ua /* [rows][T][Pc + 3] or NULL */, double* rowinfo /* [rows][5] or NULL */);
+GPCA_API int gpca_firth_log10p(const double* gt /* [n] */, const double* mu /* [n] */, int64_t n, double u, double* out /* [5] */);
 
 /* ---- f3: the stages of EigenSNPCoreAlgorithm::compute_pca (main.rs:311-327, 359-366) ------------------------------------------
  * The algorithm lives in the un-vendored efficient_pca crate (Cargo.toml:30, branch "main", no pinned revision): what follows is

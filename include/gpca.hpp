@@ -275,6 +275,28 @@ public:
         if (rc != GPCA_OK) throw Error(rc, std::string("gpca_spa_log10p: ") + gpca_status_string(rc));
         return lp;
     }
+    // the same scan with the approximate Firth correction (gpca_assoc_logistic_firth; gpca.h section a15) of the items with |z| >= firth_z
+    // (at least 0, or inf): firth [rows][T][5] = -log10 p, status (0 not applied, 1 applied, 2 failed: the normal value), beta (A1), se, D
+    void assoc_logistic_firth(const std::vector<double>& Y, int32_t T, const std::vector<double>& C, int32_t Pc, const std::vector<uint8_t>* include,
+                              double max_vif, double firth_z, int64_t row0, int64_t row1, std::vector<double>& stats, std::vector<double>& firth,
+                              std::vector<double>& rowinfo, std::vector<double>* ua = nullptr) const {
+        const size_t rows = row1 > row0 ? (size_t)(row1 - row0) : 0;
+        stats.assign(std::max<size_t>(rows * (size_t)T * 5, 1), 0.0);
+        firth.assign(std::max<size_t>(rows * (size_t)T * 5, 1), 0.0);
+        rowinfo.assign(std::max<size_t>(rows * 5, 1), 0.0);
+        if (ua) ua->assign(std::max<size_t>(rows * (size_t)T * (size_t)(Pc + 3), 1), 0.0);
+        check(gpca_assoc_logistic_firth(h_, Y.data(), T, Pc ? C.data() : nullptr, Pc, include ? include->data() : nullptr, max_vif, firth_z, row0,
+                                        row1, stats.data(), firth.data(), ua ? ua->data() : nullptr, rowinfo.data()));
+        stats.resize(rows * (size_t)T * 5);
+        firth.resize(rows * (size_t)T * 5);
+        rowinfo.resize(rows * 5);
+        if (ua) ua->resize(rows * (size_t)T * (size_t)(Pc + 3));
+    }
+    // the Firth correction for one given vector (gpca_firth_log10p; host only): out [5] = -log10 p, status, beta, se, D
+    static void firth_log10p(const std::vector<double>& gt, const std::vector<double>& mu, double u, double* out) {
+        const int rc = gt.size() != mu.size() ? GPCA_ERR_BAD_ARG : gpca_firth_log10p(gt.data(), mu.data(), (int64_t)gt.size(), u, out);
+        if (rc != GPCA_OK) throw Error(rc, std::string("gpca_firth_log10p: ") + gpca_status_string(rc));
+    }
     // the null logistic model of one trait (gpca_logistic_null; host only): y [N] in {0, 1}, C [N][Pc]; alpha [Pc + 1], mu [N] (0 outside
     // the included samples); returns the number of Newton steps; throws Error with the status (no message: there is no handle)
     static int logistic_null(const std::vector<double>& y, const std::vector<double>& C, int32_t Pc, const std::vector<uint8_t>* include,

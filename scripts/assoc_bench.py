@@ -5,7 +5,7 @@ second counted as 2 K N L_pad (the d product; the e product runs only where call
 MFMA peak, and the genotype bytes of one read of the band per second beside the 8 TB/s of the HBM.  One JSON line per L.
 
 usage: python scripts/assoc_bench.py [--rows M] [--samples N] [--storage int8|2bit] [--missing RATE] [--cols L ...] [--band ROWS] [--reps R]
-                                     [--score] [--spa]
+                                     [--score] [--spa] [--firth]
 
 Clean matrices come from the device generator; with --missing > 0 the rows are a 4 096-row host tile (that missing rate, seeded)
 repeated down the matrix and uploaded through a host panel source.  --band ROWS: rows per call (0 = io.assoc_bands' default).  Of the
@@ -22,7 +22,12 @@ three calls alternating rep by rep: per L one JSON line with the wall ms of a pa
 at spa_z = inf (nothing corrected: the flag kernel and the copy of its output are all it adds) and at spa_z = 2, each as the median
 of the reps with the smallest and largest beside it, the "assoc_spa" ms of the library's record (the flag and correction kernels) at
 either cutoff, and the share of the items with status >= 1 at spa_z = 2.  The traits are Bernoulli(0.1) here: the unbalanced case the
-correction exists for."""
+correction exists for.
+
+--firth (with the shapes and traits of --spa): gpca_assoc_logistic_firth at firth_z = inf and at 1.959964 beside the score call and the
+saddle-point call at spa_z = 2 on the same traits in the same run, the four calls alternating rep by rep: the wall ms of each as
+median, smallest and largest, the "assoc_firth" ms of the library's record at either cutoff, the share of the items corrected and the
+count of items with status 2."""
 import argparse
 import json
 import os
@@ -45,6 +50,7 @@ ap.add_argument("--band", type=int, default=0)
 ap.add_argument("--reps", type=int, default=2)
 ap.add_argument("--score", action="store_true")
 ap.add_argument("--spa", action="store_true")
+ap.add_argument("--firth", action="store_true")
 a = ap.parse_args()
 M, N = a.rows, a.samples
 store = _lib.STORE_INT8 if a.storage == "int8" else _lib.STORE_2BIT
@@ -91,7 +97,38 @@ with g.GpcaEngine(precision=_lib.PREC_I8_EXACT, storage=store) as e:
                           "spa_inf_wall_ms_med_min_max": stat(wall["spa_inf"]), "spa_2_wall_ms_med_min_max": stat(wall["spa_2"]),
                           "assoc_spa_ms_at_inf": round(spa_ms["spa_inf"], 3), "assoc_spa_ms_at_2": round(spa_ms["spa_2"], 3),
                           "flagged_share_at_2": round(flagged / max(items, 1), 5), "load_s": round(load_s, 2), "reps": a.reps}), flush=True)
-    for L in a.cols if a.score and not a.spa else []:
+    for L in a.cols if a.firth else []:
+        T, Pc = max(L // 4, 1), 1
+        Yb = (rng.random((N, T)) < 0.1).astype(np.float64)
+        Cs = rng.standard_normal((N, Pc))
+        bands = [(r0, min(r0 + a.band, K)) for r0 in range(0, K, a.band)] if a.band else gio.assoc_score_bands(K, T, Pc)
+        inf = float("inf")
+        calls = {"score": lambda b: e.assoc_logistic_score(Yb, Cs, rows=b), "spa_2": lambda b: e.assoc_logistic_spa(Yb, Cs, spa_z=2.0, rows=b),
+                 "firth_inf": lambda b: e.assoc_logistic_firth(Yb, Cs, firth_z=inf, rows=b),
+                 "firth_196": lambda b: e.assoc_logistic_firth(Yb, Cs, firth_z=1.959964, rows=b)}
+        for f in calls.values():
+            f((0, min(K, 128)))                          # warm-up
+        e.enable_timings(True)
+        wall, rec_ms, status = {k: [] for k in calls}, {}, []
+        for r in range(a.reps):
+            for k, f in calls.items():
+                e.reset_timings()
+                t0 = time.time()
+                for b in bands:
+                    res = f(b)
+                    if k == "firth_196" and r == 0:
+                        status.append(res["firth_status"].ravel().copy())
+                wall[k].append((time.time() - t0) * 1e3)
+                rec_ms[k] = e.timings().get("assoc_firth", {}).get("total_ms", float("nan"))
+        st = np.concatenate(status)
+        stat = lambda v: [round(float(np.median(v)), 3), round(min(v), 3), round(max(v), 3)]
+        print(json.dumps({"shape": f"{M} x {N}", "kept_rows": K, "storage": a.storage, "missing": a.missing, "L": T * (Pc + 3), "traits": T,
+                          "covariates": Pc, "bands": len(bands), "score_wall_ms_med_min_max": stat(wall["score"]),
+                          "spa_2_wall_ms_med_min_max": stat(wall["spa_2"]), "firth_inf_wall_ms_med_min_max": stat(wall["firth_inf"]),
+                          "firth_1.959964_wall_ms_med_min_max": stat(wall["firth_196"]), "assoc_firth_ms_at_inf": round(rec_ms["firth_inf"], 3),
+                          "assoc_firth_ms_at_1.959964": round(rec_ms["firth_196"], 3), "corrected_share": round(float((st == 1).mean()), 5),
+                          "failed": int((st == 2).sum()), "load_s": round(load_s, 2), "reps": a.reps}), flush=True)
+    for L in a.cols if a.score and not a.spa and not a.firth else []:
         T, Pc = max(L // 4, 1), 1
         Ls = T * (Pc + 3)
         Yb = (rng.random((N, T)) < 0.4).astype(np.float64)
@@ -118,7 +155,7 @@ with g.GpcaEngine(precision=_lib.PREC_I8_EXACT, storage=store) as e:
                           "issued_multiplies_ratio": round((8 * lpad / 32 + 8) / (8 * lpad / 32), 3), "wall_ms": round(wall_ms, 3),
                           "read_at_8tbs_ms": round(gbytes / 8e12 * 1e3, 3), "mfma_at_157tf_ms": round(2.0 * K * N * (lpad + 32) / 157e12 * 1e3, 3),
                           "load_s": round(load_s, 2), "reps": a.reps}), flush=True)
-    for L in [] if a.score or a.spa else a.cols:
+    for L in [] if a.score or a.spa or a.firth else a.cols:
         Pc = min(L // 3, 20)
         Y = rng.standard_normal((N, L - Pc))
         C = np.linalg.qr(rng.standard_normal((N, max(Pc, 1))))[0][:, :Pc]
