@@ -9,5 +9,6 @@ from .distributed import shard_rows  # noqa: F401
 
 spa_log10p = GpcaEngine.spa_log10p
 firth_log10p = GpcaEngine.firth_log10p
+set_test = GpcaEngine.set_test
 
 __version__ = "0.2.2"

@@ -145,6 +145,18 @@ def build_parser() -> argparse.ArgumentParser:
                         "Not together with --gpca-assoc-spa")
     p.add_argument("--gpca-assoc-firth-z", type=float, default=None, metavar="X",
                    help="--gpca-assoc-firth: the cutoff, at least 0, or inf for no correction [default: 1.959964]")
+    p.add_argument("--gpca-assoc-set-list", default=None, metavar="FILE",
+                   help="--gpca-assoc-logistic: gene-level set tests after the per-SNP scans.  FILE is regenie's set list, one set per "
+                        "line: NAME CHROM POS ID1,ID2,... (IDs that the SNP QC removed are dropped).  Every case / control trait gets "
+                        "P.<trait>.assoc.set (#SET CHROM POS N_VAR N_USED BURDEN_BETA BURDEN_SE BURDEN_Z BURDEN_LOG10P SKAT_Q SKAT_LOG10P "
+                        "SKAT): a weighted burden test and SKAT (its p-value by Kuonen's saddle point: SKAT = Y; N = the bulk "
+                        "approximation, F = the saddle point failed) from the covariance of the set's scores under the null model.  A "
+                        "set with no variant left, or with more than 128, gets NA")
+    p.add_argument("--gpca-assoc-set-max-maf", type=float, default=None, metavar="X",
+                   help="--gpca-assoc-set-list: a listed variant enters its set when its minor-allele frequency over the included "
+                        "observed calls is at most X, 0 < X <= 0.5 [default: 0.01]")
+    p.add_argument("--gpca-assoc-set-weights", default=None, metavar="KIND",
+                   help="--gpca-assoc-set-list: beta = Beta(maf; 1, 25) weights, flat = 1 [default: beta]")
     p.add_argument("--gpca-assoc-pcs", type=int, default=None, metavar="P",
                    help="--gpca-assoc-pheno: the first P columns of the scores this run writes are covariates (0 <= P <= "
                         "--eigensnp-k-global) [default: every column]")
@@ -487,6 +499,7 @@ def _assoc(eng, a, fs, cols, sample_ids, scores, inset, st):
     eng.set_standardization(st["mu"], st["sigma"], st["keep"])                       # every SNP that passes the SNP QC
     rows = np.flatnonzero(st["keep"])
     lib = _lib.load()
+    a1_all = np.full(len(rows), np.nan)                                              # (of every kept row, for the sets' MAF rule)
     spa_z = 2.0 if a.gpca_assoc_spa_z is None else a.gpca_assoc_spa_z
     firth_z = 1.959964 if a.gpca_assoc_firth_z is None else a.gpca_assoc_firth_z
 
@@ -511,6 +524,7 @@ def _assoc(eng, a, fs, cols, sample_ids, scores, inset, st):
                 else:
                     r = eng.assoc_logistic_score(Yg, C, include=include, max_vif=vif, rows=(r0, r1))
                 meta = meta_of(r0, r1)
+                a1_all[r0:r1] = r["a1_freq"]
                 for t in range(t1 - t0):
                     zz, beta, se, spa, firth = r["z"][:, t], r["beta"][:, t], r["se"][:, t], None, None
                     if a.gpca_assoc_firth:
@@ -522,6 +536,8 @@ def _assoc(eng, a, fs, cols, sample_ids, scores, inset, st):
                         lp = [float("nan") if v != v else lib.gpca_normal_log10p(float(v)) for v in zz]
                     gio.write_assoc_logistic(a.output_prefix, bnames[t0 + t], *meta, r["n_obs"], r["a1_freq"], beta, se, zz,
                                              lp, append=bi > 0, spa=spa, firth=firth)
+        if a.gpca_assoc_set_list is not None and bnames:
+            _assoc_sets(eng, a, fs, rows, a1_all, Yb, bnames, C, Pc, include, vif)
     except _lib.GpcaError as e:
         if e.status == _lib.GPCA_ERR_STATE:
             raise SystemExit(ASSOC_NEEDS_RESIDENT) from None
@@ -531,6 +547,36 @@ def _assoc(eng, a, fs, cols, sample_ids, scores, inset, st):
     if bnames:
         _log(f"logistic score scan of {len(rows)} SNPs against {len(bnames)} case / control traits with {Pc} covariates on {n_inc} of {n} "
              f"samples, written to {a.output_prefix}.<trait>.assoc.logistic")
+
+
+def _assoc_sets(eng, a, fs, rows, a1_freq, Yb, bnames, C, Pc, include, vif):
+    """--gpca-assoc-set-list FILE: the gene-level burden and SKAT tests (gpca_assoc_logistic_set, gpca_set_test) of every case / control
+    trait, on the QC mask and the include set of the per-SNP scans, into P.<trait>.assoc.set; one row per set in file order."""
+    sets = gio.read_set_list(a.gpca_assoc_set_list, [fs.variant_ids[i] for i in rows])
+    max_maf = 0.01 if a.gpca_assoc_set_max_maf is None else a.gpca_assoc_set_max_maf
+    kind = "beta" if a.gpca_assoc_set_weights is None else a.gpca_assoc_set_weights
+    enter = gio.set_maf_ok(a1_freq, max_maf)
+    left = [s.rows[enter[s.rows]] for s in sets]
+    n_var = [len(r) for r in left]
+    for s, m in zip(sets, n_var):
+        if m > gio.ASSOC_SET_MAX_ROWS:
+            print(f"note: --gpca-assoc-set-list: set {s.name} keeps {m} variants, more than {gio.ASSOC_SET_MAX_ROWS}: NA", file=sys.stderr)
+    run = [i for i, m in enumerate(n_var) if 1 <= m <= gio.ASSOC_SET_MAX_ROWS]
+    results = [[None] * len(sets) for _ in bnames]
+    for t0, t1 in gio.assoc_score_groups(len(bnames), Pc):
+        Yg = np.ascontiguousarray(Yb[:, t0:t1])
+        for s0, s1 in gio.assoc_set_groups([n_var[i] for i in run], t1 - t0, Pc):
+            r = eng.assoc_logistic_set(Yg, [left[i] for i in run[s0:s1]], C, include=include, max_vif=vif, ua=True)
+            for k, i in enumerate(run[s0:s1]):
+                lo, hi = int(r["set_off"][k]), int(r["set_off"][k + 1])
+                sg = np.where(r["flipped"][lo:hi] == 1, -1.0, 1.0)
+                w = gio.set_weights(r["a1_freq"][lo:hi], kind)
+                for t in range(t1 - t0):
+                    results[t0 + t][i] = GpcaEngine.set_test(sg * r["ua"][lo:hi, t, 0], r["phi"][k][t], w)
+    for t, name in enumerate(bnames):
+        gio.write_assoc_set(a.output_prefix, name, [s.name for s in sets], [s.chrom for s in sets], [s.pos for s in sets], n_var, results[t])
+    _log(f"set tests of {len(run)} of {len(sets)} sets against {len(bnames)} case / control traits, written to "
+         f"{a.output_prefix}.<trait>.assoc.set")
 
 
 def _indep_pairwise(eng, a, fs, st, keep, by_tag):
@@ -638,6 +684,14 @@ def main(argv=None) -> int:
         raise SystemExit("error: --gpca-assoc-firth-z needs --gpca-assoc-firth")
     if a.gpca_assoc_firth_z is not None and not gio.firth_z_ok(a.gpca_assoc_firth_z):
         raise SystemExit("error: --gpca-assoc-firth-z must be at least 0, or inf for no correction")
+    if a.gpca_assoc_set_list is not None and not a.gpca_assoc_logistic:
+        raise SystemExit("error: --gpca-assoc-set-list needs --gpca-assoc-logistic")
+    if a.gpca_assoc_set_list is None and (a.gpca_assoc_set_max_maf is not None or a.gpca_assoc_set_weights is not None):
+        raise SystemExit("error: --gpca-assoc-set-max-maf and --gpca-assoc-set-weights need --gpca-assoc-set-list")
+    if a.gpca_assoc_set_max_maf is not None and not (0.0 < a.gpca_assoc_set_max_maf <= 0.5):
+        raise SystemExit("error: --gpca-assoc-set-max-maf must lie in (0, 0.5]")
+    if a.gpca_assoc_set_weights is not None and a.gpca_assoc_set_weights not in ("beta", "flat"):
+        raise SystemExit("error: --gpca-assoc-set-weights must be beta or flat")
     if a.gpca_assoc_pheno is not None:
         if not a.eigensnp:
             raise SystemExit("error: --gpca-assoc-pheno needs the --eigensnp workflow")
@@ -651,6 +705,13 @@ def main(argv=None) -> int:
         if a.gpca_stream == "on":
             raise SystemExit(ASSOC_NEEDS_RESIDENT)
         a.gpca_assoc_tables = _assoc_tables(a)
+        if a.gpca_assoc_set_list is not None:                                        # (its format, before any work on the device)
+            try:
+                gio.read_set_list(a.gpca_assoc_set_list, [])
+            except OSError:
+                raise SystemExit(f"error: --gpca-assoc-set-list: cannot open {a.gpca_assoc_set_list}") from None
+            except ValueError as e:
+                raise SystemExit(f"error: --gpca-assoc-set-list: {e}") from None
     if a.gpca_indep_pairwise:
         if not a.eigensnp:
             raise SystemExit("error: --gpca-indep-pairwise needs the --eigensnp workflow")

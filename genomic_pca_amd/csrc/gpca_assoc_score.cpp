@@ -25,9 +25,13 @@ struct AsrWs {
     double *Z = nullptr, *mu = nullptr, *g = nullptr, *corr = nullptr;
     int* list = nullptr;
     unsigned* count = nullptr;
+    // a set call's: the listed rows' original rows, the strips of the sets' lower triangles, Phi
+    int64_t* lrows = nullptr;
+    AsgStrip* strips = nullptr;
+    double* phi = nullptr;
     ~AsrWs() {
         dfree(Bt); dfree(incw); dfree(sums); dfree(dv); dfree(stats); dfree(ua); dfree(info); dfree(bad);
-        dfree(Z); dfree(mu); dfree(g); dfree(corr); dfree(list); dfree(count);
+        dfree(Z); dfree(mu); dfree(g); dfree(corr); dfree(list); dfree(count); dfree(lrows); dfree(strips); dfree(phi);
     }
 };
 
@@ -162,9 +166,11 @@ struct HostFirthEval {
 // gpca_assoc_logistic_score (kCorrNone, corr = nullptr), gpca_assoc_logistic_spa and gpca_assoc_logistic_firth: one path; a correction
 // only adds to it.  corr_z = spa_z or firth_z; corr = the correction's output, [rows][T][4] or [rows][T][kAfiWidth]
 enum Correction { kCorrNone, kCorrSpa, kCorrFirth };
+// gpca_assoc_logistic_set (section a16): the band is the list of the sets' rows instead of [row0, row1), and Phi follows the finish kernel
+struct SetCall { int32_t n_sets; const int64_t *off, *rows; double* phi; };
 int assoc_logistic(gpca_handle* h, const std::string& f, const double* Y, int32_t T, const double* C, int32_t Pc, const uint8_t* include,
                    double max_vif, Correction mode, double corr_z, int64_t row0, int64_t row1, double* stats, double* corr, double* ua,
-                   double* rowinfo);
+                   double* rowinfo, const SetCall* sc = nullptr);
 }  // namespace
 
 extern "C" int gpca_logistic_null(const double* y, const double* C, int32_t Pc, const uint8_t* include, int64_t N, double* alpha,
@@ -207,15 +213,51 @@ extern "C" int gpca_assoc_logistic_firth(gpca_handle* h, const double* Y, int32_
     return assoc_logistic(h, "gpca_assoc_logistic_firth", Y, T, C, Pc, include, max_vif, kCorrFirth, firth_z, row0, row1, stats, firth, ua, rowinfo);
 }
 
+extern "C" int gpca_assoc_logistic_set(gpca_handle* h, const double* Y, int32_t T, const double* C, int32_t Pc, const uint8_t* include,
+                                       double max_vif, int32_t n_sets, const int64_t* set_off, const int64_t* set_rows, double* stats,
+                                       double* ua, double* rowinfo, double* phi) {
+    if (!h) return GPCA_ERR_BAD_ARG;
+    const SetCall sc{n_sets, set_off, set_rows, phi};
+    return assoc_logistic(h, "gpca_assoc_logistic_set", Y, T, C, Pc, include, max_vif, kCorrNone, INFINITY, 0, 0, stats, nullptr, ua, rowinfo, &sc);
+}
+
 namespace {
+// the sets of a call, checked: the original row of every listed row and the strips of the lower triangles (plan_math.h: AsgStrip)
+int set_plan(gpca_handle* h, const std::string& f, const SetCall& sc, int T, std::vector<int64_t>& lrows, std::vector<AsgStrip>& strips,
+             int64_t& tri_total) {
+    const int64_t K = h->n_pca;
+    if (sc.n_sets < 1 || !sc.off || !sc.rows) return fail(h, GPCA_ERR_BAD_ARG, f + ": n_sets >= 1, set_off and set_rows are required");
+    if (sc.off[0] != 0) return fail(h, GPCA_ERR_BAD_ARG, f + ": set_off[0] must be 0");
+    tri_total = 0;
+    for (int32_t s = 0; s < sc.n_sets; ++s) {
+        const int64_t m = sc.off[s + 1] - sc.off[s];
+        if (m < 1 || m > GPCA_SET_MAX_ROWS)
+            return fail(h, GPCA_ERR_BAD_ARG, f + ": set " + std::to_string(s) + " lists " + std::to_string(m) + " rows: 1 to " +
+                                                 std::to_string(GPCA_SET_MAX_ROWS) + " are allowed");
+        for (int64_t i = sc.off[s]; i < sc.off[s + 1]; ++i) {
+            const int64_t r = sc.rows[i];
+            if (r < 0 || r >= K)
+                return fail(h, GPCA_ERR_BAD_ARG, f + ": set " + std::to_string(s) + ": row " + std::to_string(r) + " is outside [0, K) (K = " +
+                                                     std::to_string(K) + " kept rows)");
+            if (i > sc.off[s] && r <= sc.rows[i - 1])
+                return fail(h, GPCA_ERR_BAD_ARG, f + ": set " + std::to_string(s) + ": its rows are not strictly ascending");
+            lrows.push_back(h->pca_rows[(size_t)r]);
+        }
+        for (int q = 0; q < asg_strips((int)m); ++q) strips.push_back(AsgStrip{sc.off[s], tri_total * (int64_t)T, (int32_t)m, (int32_t)q});
+        tri_total += asg_tri(m);
+    }
+    return GPCA_OK;
+}
+
 int assoc_logistic(gpca_handle* h, const std::string& f, const double* Y, int32_t T, const double* C, int32_t Pc, const uint8_t* include,
                    double max_vif, Correction mode, double corr_z, int64_t row0, int64_t row1, double* stats, double* corr, double* ua,
-                   double* rowinfo) {
+                   double* rowinfo, const SetCall* sc) {
     LOCK(h);
     const bool with_spa = mode == kCorrSpa, with_firth = mode == kCorrFirth, with_corr = mode != kCorrNone;
     CHK(asc_check_call(h, f, T >= 1 && Pc >= 0 && (int64_t)T * ((int64_t)Pc + 3) <= kAsrMaxCols,
                        "T >= 1, Pc >= 0 and T (Pc + 3) <= " + std::to_string(kAsrMaxCols), Y, C, Pc,
                        with_corr ? (corr ? nullptr : (with_spa ? "spa is required" : "firth is required"))
+                       : sc      ? (sc->phi ? nullptr : "phi is required")
                                  : (!stats && !ua && !rowinfo ? "stats, ua and rowinfo are all NULL" : nullptr),
                        row0, row1, max_vif,
                        with_spa && !spa_z_ok(corr_z)       ? "spa_z must be at least 0.5, or +inf for no correction"
@@ -224,6 +266,14 @@ int assoc_logistic(gpca_handle* h, const std::string& f, const double* Y, int32_
     const int64_t N = h->N;
     const int L = asr_cols(T, Pc), P = Pc + 1;
     const int64_t npad = asc_npad(N);
+    // (a set call: the band of the kernels below is the list, rows [0, listed) of its own kept-row map)
+    std::vector<int64_t> lrows;
+    std::vector<AsgStrip> strips;
+    int64_t tri_total = 0;
+    if (sc) {
+        CHK(set_plan(h, f, *sc, T, lrows, strips, tri_total));
+        row0 = 0; row1 = (int64_t)lrows.size();
+    }
 
     // host: the design, then per trait the null fit and its Pc + 3 columns
     LogitDesign D;
@@ -270,8 +320,9 @@ int assoc_logistic(gpca_handle* h, const std::string& f, const double* Y, int32_
     if (asr_count_blocks(rows) >= ((int64_t)1 << 31)) return fail(h, GPCA_ERR_BAD_ARG, f + ": the band makes 2^31 or more workgroups: ask for fewer rows");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->st));
-    CHK(preflight_device_memory(h, f.c_str(), "the band needs",
-                                asr_call_bytes(N, rows, T, Pc, dstats, ua != nullptr, rowinfo != nullptr, with_corr ? out_cap : 0, correct) +
+    CHK(preflight_device_memory(h, f.c_str(), sc ? "the sets need" : "the band needs",
+                                (sc ? asg_call_bytes(N, rows, (int64_t)strips.size(), tri_total, T, Pc, dstats, ua != nullptr, rowinfo != nullptr)
+                                    : asr_call_bytes(N, rows, T, Pc, dstats, ua != nullptr, rowinfo != nullptr, with_corr ? out_cap : 0, correct)) +
                                     (double)(64 << 20)));
     const bool packed = h->storage == GPCA_STORE_2BIT;
     const auto [G, ldr] = panel_rows(h, resident_view(h));
@@ -285,6 +336,13 @@ int assoc_logistic(gpca_handle* h, const std::string& f, const double* Y, int32_
     HIPCHK(hipMemcpyAsync(ws.Bt, Bt.data(), Bt.size() * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(ws.incw, incw.data(), incw.size() * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(ws.bad, 0xff, 8, st));
+    if (sc) {
+        HIPCHK(dalloc(ws.lrows, (size_t)asg_rows_capacity(rows))); HIPCHK(dalloc(ws.strips, (size_t)asg_strip_capacity((int64_t)strips.size())));
+        HIPCHK(dalloc(ws.phi, (size_t)asg_phi_capacity(tri_total, T)));
+        HIPCHK(hipMemcpyAsync(ws.lrows, lrows.data(), lrows.size() * 8, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(ws.strips, strips.data(), strips.size() * sizeof(AsgStrip), hipMemcpyHostToDevice, st));
+    }
+    const int64_t* krows = sc ? ws.lrows : h->d_pca_rows;
     if (with_corr) {
         HIPCHK(dalloc(ws.corr, (size_t)out_cap)); HIPCHK(dalloc(ws.list, (size_t)asp_list_capacity(rows, T)));
         HIPCHK(dalloc(ws.count, 1));
@@ -297,14 +355,14 @@ int assoc_logistic(gpca_handle* h, const std::string& f, const double* Y, int32_
     const double gbytes = (double)rows * (double)N * (packed ? 0.25 : 1.0);
     {
         ScopedTimer t(h, "assoc_score_count", 0.0, gbytes);
-        if (launch_assoc_score_count(st, G, packed, ldr, h->d_pca_rows, N, ws.incw, row0, row1, ws.sums, ws.bad) != 0)
+        if (launch_assoc_score_count(st, G, packed, ldr, krows, N, ws.incw, row0, row1, ws.sums, ws.bad) != 0)
             return fail(h, GPCA_ERR_BAD_ARG, f + ": the launch was refused");
         HIPCHK(hipGetLastError());
     }
     {
         // flops as for k_assoc, the d product over the padded columns plus the q product over its one block
         ScopedTimer t(h, "assoc_score", 2.0 * (double)rows * (double)N * (double)(asc_lpad(L) + 32), gbytes);
-        if (launch_assoc_score(st, G, packed, ldr, h->d_pca_rows, N, ws.Bt, ws.incw, T, L, row0, row1, ws.sums, ws.dv) != 0)
+        if (launch_assoc_score(st, G, packed, ldr, krows, N, ws.Bt, ws.incw, T, L, row0, row1, ws.sums, ws.dv) != 0)
             return fail(h, GPCA_ERR_BAD_ARG, f + ": the launch was refused");
         HIPCHK(hipGetLastError());
     }
@@ -320,14 +378,22 @@ int assoc_logistic(gpca_handle* h, const std::string& f, const double* Y, int32_
             else launch_assoc_spa_flag(st, ws.stats, ws.dv, T, Pc, item0, nitems, corr_z, ws.corr, ws.list, ws.count);
             HIPCHK(hipGetLastError());
             if (!correct) continue;
-            if ((with_firth ? launch_assoc_firth : launch_assoc_spa)(st, G, packed, ldr, h->d_pca_rows, N, ws.incw, ws.sums, ws.dv, ws.Z, ws.mu, T, Pc,
+            if ((with_firth ? launch_assoc_firth : launch_assoc_spa)(st, G, packed, ldr, krows, N, ws.incw, ws.sums, ws.dv, ws.Z, ws.mu, T, Pc,
                                                                      row0, item0, ws.list, ws.count, ws.g, ws.corr) != 0)
                 return fail(h, GPCA_ERR_BAD_ARG, f + ": the launch was refused");
             HIPCHK(hipGetLastError());
         }
     }
+    if (sc) {
+        // flops: the XX product over the tiles of the strips (the M products run only where calls are missing)
+        ScopedTimer t(h, "assoc_set_gram", 2.0 * (double)tri_total * (double)T * (double)N, gbytes * (double)T);
+        if (launch_assoc_set_gram(st, G, packed, ldr, ws.lrows, N, ws.Bt, ws.incw, T, ws.sums, ws.strips, (int64_t)strips.size(), ws.phi) != 0 ||
+            launch_assoc_set_finish(st, ws.dv, ws.sums, T, Pc, ws.strips, (int64_t)strips.size(), ws.phi) != 0)
+            return fail(h, GPCA_ERR_BAD_ARG, f + ": the launch was refused");
+        HIPCHK(hipGetLastError());
+    }
     CHK(asc_check_genotypes(h, f, ws.bad, st));
-    return asc_copy_outputs(h, st, {{stats, ws.stats, asr_stats_capacity(rows, T)}, {ua, ws.ua, asr_ua_capacity(rows, T, Pc)},
+    return asc_copy_outputs(h, st, {{sc ? sc->phi : nullptr, ws.phi, sc ? asg_phi_capacity(tri_total, T) : 0}, {stats, ws.stats, asr_stats_capacity(rows, T)}, {ua, ws.ua, asr_ua_capacity(rows, T, Pc)},
                                     {rowinfo, ws.info, asr_info_capacity(rows)}, {corr, ws.corr, with_corr ? out_cap : 0}});
 }
 }  // namespace
@@ -365,6 +431,112 @@ extern "C" int gpca_firth_log10p(const double* gt, const double* mu, int64_t n, 
     FirthResult r;
     firth_item(ev, u, gmax, u == 0.0 ? 0.0 : spa_normal_log10p(u / std::sqrt(V)), r);
     out[0] = r.log10p; out[1] = (double)r.status; out[2] = r.beta; out[3] = r.se; out[4] = r.lrt;
+    return GPCA_OK;
+}
+
+// gpca_set_test (section a16): the burden and SKAT rules of one set, host only
+namespace {
+constexpr int kSetMaxSteps = 200;
+constexpr double kSetStop = 1e-10, kSetMinZ = 0.5, kSetKeep = 1e5;
+// -log10 P(Q > q) by Satterthwaite's scaled chi^2 and the Wilson-Hilferty cube root
+double set_bulk(double Q, double c1, double c2) {
+#pragma clang fp contract(off)
+    const double kappa = c2 / c1, nu = c1 * c1 / c2, v = 2.0 / (9.0 * nu);
+    const double x = (std::cbrt(Q / (kappa * nu)) - (1.0 - v)) / std::sqrt(v);
+    return spa_upper_log10p(x);
+}
+}  // namespace
+
+extern "C" int gpca_set_test(const double* u, const double* phi, const double* weight, int32_t m, double* out) {
+#pragma clang fp contract(off)
+    if (!u || !phi || !out || m < 1 || m > GPCA_SET_MAX_ROWS) return GPCA_ERR_BAD_ARG;
+    if (weight)
+        for (int i = 0; i < m; ++i) if (std::isnan(weight[i]) || weight[i] < 0.0) return GPCA_ERR_BAD_ARG;
+    auto P = [&](int i, int j) { return i >= j ? phi[(size_t)i * ((size_t)i + 1) / 2 + (size_t)j] : phi[(size_t)j * ((size_t)j + 1) / 2 + (size_t)i]; };
+    std::vector<int> used;
+    std::vector<double> om;
+    for (int i = 0; i < m; ++i) {
+        const double w = weight ? weight[i] : 1.0, d = P(i, i);
+        if (std::isfinite(u[i]) && std::isfinite(d) && d > 0.0 && std::isfinite(w) && w > 0.0) { used.push_back(i); om.push_back(w); }
+    }
+    const int n = (int)used.size();
+    const double nan = std::nan("");
+    out[0] = (double)n;
+    for (int k = 1; k < 10; ++k) out[k] = nan;
+    out[7] = 0.0;
+    if (n == 0) return GPCA_OK;
+    // A = diag(omega) Phi diag(omega) over the used rows
+    std::vector<double> A((size_t)n * (size_t)n), lam((size_t)n), vec((size_t)n * (size_t)n);
+    bool finite = true;
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) {
+            const double a = (om[(size_t)i] * P(used[(size_t)i], used[(size_t)j])) * om[(size_t)j];
+            A[(size_t)i * n + j] = a;
+            finite = finite && std::isfinite(a);
+        }
+    double B = 0.0, v = 0.0, Q = 0.0;
+    for (int i = 0; i < n; ++i) {
+        const double t = om[(size_t)i] * u[used[(size_t)i]];
+        B = B + t;
+        Q = Q + t * t;
+        for (int j = 0; j < n; ++j) v = v + A[(size_t)i * n + j];
+    }
+    if (v > 0.0) {
+        const double rt = std::sqrt(v);
+        out[1] = B / v; out[2] = 1.0 / rt; out[3] = B / rt; out[4] = spa_normal_log10p(B / rt);
+    }
+    out[5] = Q;
+    if (!finite || gpca_host_eigh_desc(A.data(), n, lam.data(), vec.data()) != GPCA_OK) return GPCA_OK;
+    double pos = 0.0;
+    int npos = 0;
+    for (int i = 0; i < n; ++i) if (lam[(size_t)i] >= 0.0) { pos = pos + lam[(size_t)i]; ++npos; }
+    const double keep = npos ? pos / (double)npos / kSetKeep : 0.0;
+    int nl = 0;
+    while (nl < n && lam[(size_t)nl] > keep) ++nl;                       // (descending: the kept ones lead)
+    double c1 = 0.0, c2 = 0.0;
+    for (int i = 0; i < nl; ++i) { c1 = c1 + lam[(size_t)i]; c2 = c2 + lam[(size_t)i] * lam[(size_t)i]; }
+    if (nl == 0) return GPCA_OK;
+    const double zq = (Q - c1) / std::sqrt(2.0 * c2);
+    out[8] = zq;
+    const double bulk = set_bulk(Q, c1, c2);
+    out[6] = bulk;
+    if (!(zq >= kSetMinZ)) return GPCA_OK;
+    // Kuonen's saddle point: the root of K'(zeta) = Q on (0, 1 / (2 lambda_1)) by a bracketed Newton
+    const double ub = 1.0 / (2.0 * lam[0]);
+    double lo = 0.0, hi = ub, zeta = (Q - c1) / (2.0 * c2);
+    if (!(zeta > lo && zeta < hi)) zeta = 0.5 * (lo + hi);
+    auto k12 = [&](double z, double& k1, double& k2) {
+        double s1 = 0.0, s2 = 0.0;
+        for (int i = 0; i < nl; ++i) {
+            const double l = lam[(size_t)i], d = 1.0 - 2.0 * z * l, r = l / d;
+            s1 = s1 + r; s2 = s2 + r * r;
+        }
+        k1 = s1; k2 = 2.0 * s2;
+    };
+    bool found = false;
+    for (int rep = 0; rep < kSetMaxSteps && !found; ++rep) {
+        double k1, k2;
+        k12(zeta, k1, k2);
+        const double f = k1 - Q;
+        if (!std::isfinite(f)) break;
+        if (f > 0.0) hi = zeta; else lo = zeta;
+        double zn = zeta - f / k2;
+        if (!(zn > lo && zn < hi)) zn = 0.5 * (lo + hi);
+        found = std::fabs(zn - zeta) <= kSetStop * ub;
+        zeta = zn;
+    }
+    out[9] = zeta;
+    out[7] = 2.0;
+    if (!found) return GPCA_OK;
+    double K = 0.0, k1, k2;
+    for (int i = 0; i < nl; ++i) K = K + std::log1p(-2.0 * zeta * lam[(size_t)i]);
+    K = -0.5 * K;
+    k12(zeta, k1, k2);
+    const double w = std::sqrt(2.0 * (zeta * Q - K)), vv = zeta * std::sqrt(k2);
+    const double r = w + std::log(vv / w) / w;
+    if (!std::isfinite(r) || !(r > 0.0)) return GPCA_OK;
+    out[6] = spa_upper_log10p(r);
+    out[7] = 1.0;
     return GPCA_OK;
 }
 

@@ -394,4 +394,12 @@ int launch_assoc_firth(hipStream_t st, const void* G, int packed, int64_t ldr, c
                        const unsigned* sums, const double* dv, const double* Z, const double* mu, int T, int Pc, int64_t row0, int64_t item0,
                        const int* list, const unsigned* count, double* gws, double* out);
 
+// ---- gene-level set tests of the score scan (assoc_set.hip): lrows [listed] = the listed rows' original rows, sums and dv = what the
+// score scan's kernels left for them (band = the list), strips [n_strips] (plan_math.h: AsgStrip), phi [tri_total][T] as asg_phi_index
+// says.  The Gram kernel leaves R_ab, the finish kernel turns it into Phi_ab in place.
+int launch_assoc_set_gram(hipStream_t st, const void* G, int packed, int64_t ldr, const int64_t* lrows, int64_t N, const float* Bt,
+                          const unsigned* incw, int T, const unsigned* sums, const AsgStrip* strips, int64_t n_strips, double* phi);
+int launch_assoc_set_finish(hipStream_t st, const double* dv, const unsigned* sums, int T, int Pc, const AsgStrip* strips, int64_t n_strips,
+                            double* phi);
+
 }  // namespace gpca

@@ -382,4 +382,30 @@ constexpr double asr_call_bytes(int64_t N, int64_t rows, int T, int Pc, bool dst
     return b;
 }
 
+// ---- gene-level set tests of the score scan (assoc_set.hip, gpca_assoc_score.cpp) ---------------------------------------------------
+// A set lists 1 <= m <= kAsgMaxRows rows; its Phi is stored per trait as the packed lower triangle, row by row: entry (a, b), b <= a,
+// at asg_tri(a) + b of asg_tri(m).  The lower triangle is cut into strips of kAsgStripRows rows; a workgroup of kAsgThreads threads owns
+// one (strip, trait): it stages the set's rows [0, asg_staged_rows(m, s)) with the score scan's staging map (thread t: half t & 1 of row
+// t / 2, stages of kAscStage samples, flush every kAscFlush), and wave v <= s owns the 32 x 32 tile (strip s, column block v).
+constexpr int kAsgMaxRows = 128, kAsgStripRows = 32, kAsgThreads = 256;
+static_assert(kAsgMaxRows == kAscRows && kAsgThreads == kAscThreads && kAsgMaxRows == kMaxSketchCols, "a set is one score-scan tile and one host eigenproblem");
+static_assert(kAsgMaxRows / kAsgStripRows == kAsgThreads / 64, "a wave per column block of the last strip");
+constexpr int64_t asg_tri(int64_t m) { return m * (m + 1) / 2; }
+constexpr int asg_strips(int m) { return (m + kAsgStripRows - 1) / kAsgStripRows; }
+constexpr int asg_staged_rows(int m, int s) { return kAsgStripRows * (s + 1) < m ? kAsgStripRows * (s + 1) : m; }
+// one strip of the call: its set's first listed row, the set's first Phi element (of trait 0), the set's size and the strip's index
+struct AsgStrip { int64_t l0, p0; int32_t m, s; };
+// where Phi_ab (b <= a) of trait t lies: p0 = T times the packed entries of the sets before this one
+constexpr int64_t asg_phi_index(int64_t p0, int m, int t, int a, int b) { return p0 + (int64_t)t * asg_tri(m) + asg_tri(a) + b; }
+// elements of the Gram's buffers: the listed rows' original rows (i64), the strips (AsgStrip), Phi (f64)
+constexpr int64_t asg_rows_capacity(int64_t listed) { return listed; }
+constexpr int64_t asg_strip_capacity(int64_t strips) { return strips; }
+constexpr int64_t asg_phi_capacity(int64_t tri_total, int T) { return tri_total * (int64_t)T; }
+// The device bytes a set call allocates (gpca_assoc_logistic_set's GPCA_ERR_OOM sum, without the check's slack): the score scan's for the
+// listed rows, plus the three buffers above.
+constexpr double asg_call_bytes(int64_t N, int64_t listed, int64_t strips, int64_t tri_total, int T, int Pc, bool dstats, bool ua, bool info) {
+    return asr_call_bytes(N, listed, T, Pc, dstats, ua, info, 0, false) + 8.0 * (double)asg_rows_capacity(listed) +
+           (double)sizeof(AsgStrip) * (double)asg_strip_capacity(strips) + 8.0 * (double)asg_phi_capacity(tri_total, T);
+}
+
 }  // namespace gpca

@@ -42,6 +42,15 @@ GPCA_HD inline double spa_normal_log10p(double z) {
     return (x * x + 0.5 * std::log(M_PI) + std::log(fcf)) / ln10;
 }
 
+// -log10(1 - Phi(x)), the one-sided upper tail: the two-sided value plus log10(2) for x >= 0; below 0 the tail is
+// 1 - erfc(|x| / sqrt(2)) / 2, taken through log1p
+GPCA_HD inline double spa_upper_log10p(double x) {
+#pragma clang fp contract(off)
+    if (std::isnan(x)) return std::nan("");
+    if (x >= 0.0) return spa_normal_log10p(x) + std::log10(2.0);
+    return -std::log1p(-0.5 * std::erfc(-x / std::sqrt(2.0))) / std::log(10.0);
+}
+
 constexpr int kSpaMaxSteps = 100;
 constexpr double kSpaStop = 1e-10, kSpaMinZ = 0.5;
 

@@ -602,6 +602,69 @@ class GpcaEngine:
             res.update(log10p=spa[:n, :, 0], spa_status=spa[:n, :, 1], zeta=spa[:n, :, 2:4])
         return res
 
+    def assoc_logistic_set(self, Y, sets, covar=None, include=None, max_vif: float = 50.0, ua: bool = False):
+        """Gene-level set scan (gpca_assoc_logistic_set; gpca.h section a16): sets = a sequence of sets, each 1 .. 128 strictly ascending
+        kept rows in PCA-SNP order; the other arguments are assoc_logistic_score's.  Returns assoc_logistic_score's dict over the LISTED
+        rows (the sets' rows one set after the other, with the bits the score scan gives each row), "set_off" [n_sets + 1] = where each
+        set starts in that list, and "phi" = per set the covariance of its scores for allele A1, [T][m][m] symmetric.  Feed
+        u = sign * U (sign = -1 on a flipped row; with ua=True, U = ua[..., 0]) and phi[s][t] to set_test."""
+        Yv, Cv, inc, T, Pc, _, _, _ = self._assoc_args(Y, covar, include, None)
+        sets = [np.ascontiguousarray(s, np.int64).reshape(-1) for s in sets]
+        off = np.zeros(len(sets) + 1, np.int64)
+        if sets:
+            off[1:] = np.cumsum([s.shape[0] for s in sets])
+        rows = np.ascontiguousarray(np.concatenate(sets) if sets else np.zeros(0, np.int64), np.int64)
+        n = int(off[-1])
+        tri = [int(s.shape[0]) * (int(s.shape[0]) + 1) // 2 for s in sets]
+        stats = np.zeros((max(n, 1), max(T, 1), 5), np.float64)
+        info = np.zeros((max(n, 1), 5), np.float64)
+        out_ua = np.zeros((max(n, 1), max(T, 1), Pc + 3), np.float64) if ua else None
+        phi = np.zeros(max(sum(tri) * max(T, 1), 1), np.float64)
+        self._chk(self._lib.gpca_assoc_logistic_set(self._h, _vp(Yv), T, _vp(Cv) if Pc else None, Pc, _vp(inc), float(max_vif), len(sets),
+                                                    _vp(off), _vp(rows), _vp(stats), _vp(out_ua), _vp(info), _vp(phi)))
+        res = {"beta": stats[:n, :, 0], "se": stats[:n, :, 1], "z": stats[:n, :, 2], "vw": stats[:n, :, 3], "V": stats[:n, :, 4],
+               "n_obs": info[:n, 0], "a1_freq": info[:n, 1], "xx": info[:n, 2], "flipped": info[:n, 3], "set_off": off}
+        if ua:
+            res["ua"] = out_ua[:n]
+        full, p0 = [], 0
+        for s, nt in zip(sets, tri):
+            m = int(s.shape[0])
+            il = np.tril_indices(m)
+            f = np.zeros((T, m, m), np.float64)
+            for t in range(T):
+                lo = phi[p0 + t * nt: p0 + (t + 1) * nt]
+                f[t][il] = lo
+                f[t].T[il] = lo
+            full.append(f)
+            p0 += T * nt
+        res["phi"] = full
+        return res
+
+    @staticmethod
+    def set_test(u, phi, weight=None):
+        """The burden and SKAT tests of one set (gpca_set_test; host only; gpca.h section a16): u [m] = the scores for allele A1,
+        phi [m][m] = their covariance (the lower triangle is read), weight [m] or None = 1.  Returns a dict: m_used, burden_beta,
+        burden_se, burden_z, burden_log10p, skat_q, skat_log10p, skat_status (0 the bulk value, 1 the saddle point, 2 the bulk value
+        after a failed saddle point), z_q, zeta."""
+        uv = np.ascontiguousarray(u, np.float64).reshape(-1)
+        m = uv.shape[0]
+        pv = np.asarray(phi, np.float64)
+        if pv.shape != (m, m):
+            raise ValueError("phi must be [m][m] for u [m]")
+        lo = np.ascontiguousarray(pv[np.tril_indices(m)])
+        wv = None if weight is None else np.ascontiguousarray(weight, np.float64).reshape(-1)
+        if wv is not None and wv.shape[0] != m:
+            raise ValueError("weight must have one entry per row")
+        out = np.zeros(10)
+        lib = _lib.load()
+        rc = lib.gpca_set_test(_vp(uv), _vp(lo), _vp(wv), m, _vp(out))
+        if rc != 0:
+            raise GpcaError(rc, "gpca_set_test: " + lib.gpca_status_string(rc).decode())
+        keys = ("m_used", "burden_beta", "burden_se", "burden_z", "burden_log10p", "skat_q", "skat_log10p", "skat_status", "z_q", "zeta")
+        res = {k: float(v) for k, v in zip(keys, out)}
+        res["m_used"], res["skat_status"] = int(out[0]), int(out[7])
+        return res
+
     @staticmethod
     def logistic_null(y, covar=None, include=None):
         """The null logistic model of one case / control trait (gpca_logistic_null; host only): y [N] in {0, 1} on the included samples,

@@ -33,6 +33,7 @@
 #include <stdexcept>
 #include <set>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 namespace gpca_host {
@@ -913,6 +914,101 @@ public:
 private:
     OutFile o_;
     bool spa_;
+};
+
+// ---- gene-level set tests of the logistic score scan: the twins of io.read_set_list, io.set_weights, io.set_maf_ok,
+// io.assoc_set_groups and io.write_assoc_set ---------------------------------------------------------------------------------------
+constexpr int64_t kAssocSetMaxRows = 128;
+struct VariantSet {
+    std::string name, chrom;
+    int64_t pos = 0;
+    std::vector<int64_t> rows;   // kept rows (PCA-SNP order) of the listed IDs that are among the QC-kept SNPs: ascending, each once
+};
+// regenie's set list: one set per line, `NAME CHROM POS ID1,ID2,...` separated by blanks or tabs (empty lines and lines that start with
+// # are skipped).  kept_ids: the IDs of the QC-kept SNPs in PCA-SNP order; an ID that is not among them is dropped, an ID that occurs
+// twice among them means its first row, and an ID listed twice in a set counts once.  Throws with the file and the line; the text
+// "cannot open" alone when the file cannot be read.
+inline std::vector<VariantSet> read_set_list(const std::string& path, const std::vector<std::string>& kept_ids) {
+    std::unordered_map<std::string, int64_t> at;
+    for (size_t i = 0; i < kept_ids.size(); ++i) at.emplace(kept_ids[i], (int64_t)i);
+    std::ifstream f(path);
+    if (!f) throw std::runtime_error("cannot open " + path);
+    std::vector<VariantSet> out;
+    std::string line;
+    for (int64_t ln = 1; std::getline(f, line); ++ln) {
+        const std::vector<std::string> p = split_ws(line);
+        if (p.empty() || p[0][0] == '#') continue;
+        const std::string where = path + ":" + std::to_string(ln) + ": ";
+        if (p.size() != 4) throw std::runtime_error(where + "`NAME CHROM POS ID1,ID2,...` is required");
+        VariantSet v;
+        v.name = p[0]; v.chrom = p[1];
+        {
+            const std::string& t = p[2];
+            size_t i = (t[0] == '-' || t[0] == '+') ? 1 : 0;
+            bool ok = i < t.size() && t.size() - i <= 18;
+            for (size_t k = i; k < t.size(); ++k) ok = ok && t[k] >= '0' && t[k] <= '9';
+            if (!ok) throw std::runtime_error(where + "`" + t + "` is not a position");
+            v.pos = std::stoll(t);
+        }
+        size_t b = 0;
+        while (b <= p[3].size()) {
+            size_t e = p[3].find(',', b);
+            if (e == std::string::npos) e = p[3].size();
+            const auto it = at.find(p[3].substr(b, e - b));
+            if (it != at.end()) v.rows.push_back(it->second);
+            b = e + 1;
+        }
+        std::sort(v.rows.begin(), v.rows.end());
+        v.rows.erase(std::unique(v.rows.begin(), v.rows.end()), v.rows.end());
+        out.push_back(std::move(v));
+    }
+    return out;
+}
+// the weight of a variant from its A1 frequency: beta = the Beta(maf; 1, 25) density 25 (1 - maf)^24 with maf = min(f, 1 - f) (the power
+// by three squarings and one product, as io.set_weights takes it), otherwise (flat) 1
+inline double set_weight(double a1_freq, bool beta) {
+    if (!beta) return 1.0;
+    const double q = 1.0 - std::min(a1_freq, 1.0 - a1_freq), q2 = q * q, q4 = q2 * q2, q8 = q4 * q4;
+    return 25.0 * ((q8 * q8) * q8);
+}
+// a variant enters a set: min(f, 1 - f) <= max_maf (a variant without an observed call, f = NaN, does not)
+inline bool set_maf_ok(double a1_freq, double max_maf) { return a1_freq == a1_freq && std::min(a1_freq, 1.0 - a1_freq) <= max_maf; }
+// [s0, s1) groups of consecutive sets (sizes = their row counts, each 1 .. 128) for one gpca_assoc_logistic_set call each: the listed
+// rows' workspace (rows x T (Pc + 3) doubles) and Phi (T m (m + 1) / 2 doubles per set) hold at most max_values entries each
+inline std::vector<std::pair<int64_t, int64_t>> assoc_set_groups(const std::vector<int64_t>& sizes, int64_t T, int64_t Pc, int64_t max_values = (int64_t)1 << 26) {
+    std::vector<std::pair<int64_t, int64_t>> out;
+    int64_t s0 = 0, rows = 0, tri = 0;
+    for (int64_t s = 0; s < (int64_t)sizes.size(); ++s) {
+        const int64_t m = sizes[(size_t)s];
+        int64_t r = rows + m, t = tri + m * (m + 1) / 2;
+        if (s > s0 && (r * T * (Pc + 3) > max_values || t * T > max_values)) {
+            out.emplace_back(s0, s);
+            s0 = s; r = m; t = m * (m + 1) / 2;
+        }
+        rows = r; tri = t;
+    }
+    if ((int64_t)sizes.size() > s0) out.emplace_back(s0, (int64_t)sizes.size());
+    return out;
+}
+// P.<trait>.assoc.set: one tab-separated line per set, `#SET CHROM POS N_VAR N_USED BURDEN_BETA BURDEN_SE BURDEN_Z BURDEN_LOG10P SKAT_Q
+// SKAT_LOG10P SKAT`; numbers as %.6g, NaN as NA; SKAT = Y, N, F for the status 1, 0, 2 of gpca_set_test (NA where SKAT_LOG10P is NA).
+// out = gpca_set_test's ten values, or NULL (no test was made: everything after N_VAR is NA)
+class AssocSetWriter {
+public:
+    AssocSetWriter(const std::string& prefix, const std::string& trait) : o_(prefix + "." + trait + ".assoc.set") {
+        std::fputs("#SET\tCHROM\tPOS\tN_VAR\tN_USED\tBURDEN_BETA\tBURDEN_SE\tBURDEN_Z\tBURDEN_LOG10P\tSKAT_Q\tSKAT_LOG10P\tSKAT\n", o_.f);
+    }
+    void add_row(const VariantSet& s, int64_t n_var, const double* out) {
+        std::fprintf(o_.f, "%s\t%s\t%lld\t%lld", s.name.c_str(), s.chrom.c_str(), (long long)s.pos, (long long)n_var);
+        if (!out) { std::fputs("\tNA\tNA\tNA\tNA\tNA\tNA\tNA\tNA\n", o_.f); return; }
+        char b[6][48];
+        for (int i = 0; i < 6; ++i) { const double v = out[1 + i]; if (v != v) std::snprintf(b[i], sizeof b[i], "NA"); else std::snprintf(b[i], sizeof b[i], "%.6g", v); }
+        const char* st = out[6] != out[6] ? "NA" : (out[7] == 1.0 ? "Y" : (out[7] == 2.0 ? "F" : "N"));
+        std::fprintf(o_.f, "\t%lld\t%s\t%s\t%s\t%s\t%s\t%s\t%s\n", (long long)out[0], b[0], b[1], b[2], b[3], b[4], b[5], st);
+    }
+
+private:
+    OutFile o_;
 };
 
 }  // namespace gpca_host

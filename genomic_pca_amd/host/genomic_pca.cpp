@@ -66,6 +66,10 @@ struct Args {
     bool assoc_firth = false;         // --gpca-assoc-firth: the approximate Firth correction of the logistic score scan
     bool have_assoc_firth_z = false;
     double assoc_firth_z = 1.959964;  // --gpca-assoc-firth-z X
+    std::string assoc_set_list;       // --gpca-assoc-set-list FILE: gene-level set tests after the per-SNP logistic scans
+    bool have_assoc_set_max_maf = false, have_assoc_set_weights = false;
+    double assoc_set_max_maf = 0.01;  // --gpca-assoc-set-max-maf X
+    std::string assoc_set_weights = "beta";   // --gpca-assoc-set-weights beta|flat
     gpca_host::PhenoTable assoc_pheno_table, assoc_covar_table;   // read in main, before any work on the device
 };
 
@@ -181,6 +185,16 @@ void print_help() {
         "                                       and a column FIRTH says Y (corrected), N (below the cutoff) or F (the fit failed: the\n"
         "                                       score test's values).  Not together with --gpca-assoc-spa\n"
         "      --gpca-assoc-firth-z <X>         --gpca-assoc-firth: the cutoff, at least 0, or inf for no correction [default: 1.959964]\n"
+        "      --gpca-assoc-set-list <FILE>     --gpca-assoc-logistic: gene-level set tests after the per-SNP scans.  FILE is regenie's set\n"
+        "                                       list, one set per line: NAME CHROM POS ID1,ID2,... (IDs that the SNP QC removed are\n"
+        "                                       dropped).  Every case / control trait gets P.<trait>.assoc.set (#SET CHROM POS N_VAR\n"
+        "                                       N_USED BURDEN_BETA BURDEN_SE BURDEN_Z BURDEN_LOG10P SKAT_Q SKAT_LOG10P SKAT): a weighted\n"
+        "                                       burden test and SKAT (its p-value by Kuonen's saddle point: SKAT = Y; N = the bulk\n"
+        "                                       approximation, F = the saddle point failed) from the covariance of the set's scores\n"
+        "                                       under the null model.  A set with no variant left, or with more than 128, gets NA\n"
+        "      --gpca-assoc-set-max-maf <X>     --gpca-assoc-set-list: a listed variant enters its set when its minor-allele frequency\n"
+        "                                       over the included observed calls is at most X, 0 < X <= 0.5 [default: 0.01]\n"
+        "      --gpca-assoc-set-weights <KIND>  --gpca-assoc-set-list: beta = Beta(maf; 1, 25) weights, flat = 1 [default: beta]\n"
         "      --gpca-assoc-pcs <P>             --gpca-assoc-pheno: the first P columns of the scores this run writes are covariates\n"
         "                                       (0 <= P <= --eigensnp-k-global) [default: every column]\n"
         "      --gpca-assoc-covar <FILE>        --gpca-assoc-pheno: further covariates, a table in the format of the phenotype file\n"
@@ -266,6 +280,9 @@ Args parse(int argc, char** argv) {
         else if (f == "--gpca-assoc-spa-z") { a.assoc_spa_z = to_f64(f, val()); a.have_assoc_spa_z = true; }
         else if (f == "--gpca-assoc-firth") a.assoc_firth = true;
         else if (f == "--gpca-assoc-firth-z") { a.assoc_firth_z = to_f64(f, val()); a.have_assoc_firth_z = true; }
+        else if (f == "--gpca-assoc-set-list") a.assoc_set_list = val();
+        else if (f == "--gpca-assoc-set-max-maf") { a.assoc_set_max_maf = to_f64(f, val()); a.have_assoc_set_max_maf = true; }
+        else if (f == "--gpca-assoc-set-weights") { a.assoc_set_weights = val(); a.have_assoc_set_weights = true; }
         else if (f == "--gpca-assoc-pcs") { a.assoc_pcs = to_i64(f, val()); a.have_assoc_pcs = true; }
         else if (f == "--gpca-assoc-vif") { a.assoc_vif = to_f64(f, val()); a.have_assoc_vif = true; }
         else if (f == "--gpca-indep-pairwise") {
@@ -393,6 +410,72 @@ const char* const kAssocNeedsResident =
     "error: --gpca-assoc-pheno needs the genotype matrix resident on the device: the scan of a matrix walked out of core is not implemented\n";
 constexpr int64_t kAssocMaxColumns = 64;
 
+// --gpca-assoc-set-list FILE: the gene-level burden and SKAT tests (gpca_assoc_logistic_set, gpca_set_test) of every case / control
+// trait, on the QC mask and the include set of the per-SNP scans, into P.<trait>.assoc.set; one row per set in file order
+// (cli.py:_assoc_sets).  rows: the original row of every kept row; a1_freq: of every kept row; Yb [n][Tb].
+void run_assoc_sets(gpca::Engine& eng, const Args& a, const gpca_host::PlinkFileset& fs, const std::vector<int64_t>& rows,
+                    const std::vector<double>& a1_freq, const std::vector<double>& Yb, int32_t Tb, const std::vector<std::string>& bnames,
+                    const std::vector<double>& C, int32_t Pc, const std::vector<uint8_t>& include) {
+    const size_t n = include.size();
+    std::vector<std::string> kept_ids;
+    for (int64_t o : rows) kept_ids.push_back(fs.variant_ids[(size_t)o]);
+    const std::vector<gpca_host::VariantSet> sets = gpca_host::read_set_list(a.assoc_set_list, kept_ids);
+    const bool beta = a.assoc_set_weights == "beta";
+    std::vector<std::vector<int64_t>> left(sets.size());
+    std::vector<size_t> run;
+    for (size_t i = 0; i < sets.size(); ++i) {
+        for (int64_t r : sets[i].rows) if (gpca_host::set_maf_ok(a1_freq[(size_t)r], a.assoc_set_max_maf)) left[i].push_back(r);
+        const int64_t m = (int64_t)left[i].size();
+        if (m > gpca_host::kAssocSetMaxRows)
+            std::fprintf(stderr, "note: --gpca-assoc-set-list: set %s keeps %lld variants, more than %lld: NA\n", sets[i].name.c_str(), (long long)m,
+                         (long long)gpca_host::kAssocSetMaxRows);
+        if (m >= 1 && m <= gpca_host::kAssocSetMaxRows) run.push_back(i);
+    }
+    std::vector<int64_t> sizes;
+    for (size_t i : run) sizes.push_back((int64_t)left[i].size());
+    // results [trait][set][10]; have [set]
+    std::vector<std::vector<double>> results((size_t)Tb, std::vector<double>(sets.size() * 10, 0.0));
+    std::vector<uint8_t> have(sets.size(), 0);
+    for (const auto& g : gpca_host::assoc_score_groups(Tb, Pc)) {
+        const int32_t Tg = (int32_t)(g.second - g.first);
+        std::vector<double> Yg(n * (size_t)Tg);
+        for (size_t s = 0; s < n; ++s)
+            for (int32_t t = 0; t < Tg; ++t) Yg[s * (size_t)Tg + (size_t)t] = Yb[s * (size_t)Tb + (size_t)g.first + (size_t)t];
+        for (const auto& c : gpca_host::assoc_set_groups(sizes, Tg, Pc)) {
+            std::vector<int64_t> off(1, 0), list;
+            for (int64_t k = c.first; k < c.second; ++k) {
+                const std::vector<int64_t>& r = left[run[(size_t)k]];
+                list.insert(list.end(), r.begin(), r.end());
+                off.push_back((int64_t)list.size());
+            }
+            std::vector<double> stats, info, phi, ua;
+            eng.assoc_logistic_set(Yg, Tg, C, Pc, &include, a.assoc_vif, off, list, stats, info, phi, &ua);
+            size_t p0 = 0;
+            for (int64_t k = c.first; k < c.second; ++k) {
+                const size_t i = run[(size_t)k], lo = (size_t)off[(size_t)(k - c.first)], m = left[i].size(), tri = m * (m + 1) / 2;
+                std::vector<double> u(m), w(m);
+                for (size_t q = 0; q < m; ++q) w[q] = gpca_host::set_weight(info[5 * (lo + q) + 1], beta);
+                for (int32_t t = 0; t < Tg; ++t) {
+                    for (size_t q = 0; q < m; ++q)
+                        u[q] = (info[5 * (lo + q) + 3] == 1.0 ? -1.0 : 1.0) * ua[((lo + q) * (size_t)Tg + (size_t)t) * (size_t)(Pc + 3)];
+                    gpca::Engine::set_test(u, std::vector<double>(phi.begin() + (std::ptrdiff_t)(p0 + (size_t)t * tri), phi.begin() + (std::ptrdiff_t)(p0 + ((size_t)t + 1) * tri)),
+                                           w, &results[(size_t)g.first + (size_t)t][i * 10]);
+                }
+                have[i] = 1;
+                p0 += (size_t)Tg * tri;
+            }
+        }
+    }
+    for (int32_t t = 0; t < Tb; ++t) {
+        gpca_host::AssocSetWriter w(a.output_prefix, bnames[(size_t)t]);
+        for (size_t i = 0; i < sets.size(); ++i) w.add_row(sets[i], (int64_t)left[i].size(), have[i] ? &results[(size_t)t][i * 10] : nullptr);
+    }
+    char buf[512];
+    std::snprintf(buf, sizeof buf, "set tests of %zu of %zu sets against %d case / control traits, written to %s.<trait>.assoc.set", run.size(), sets.size(),
+                  (int)Tb, a.output_prefix.c_str());
+    logmsg(buf);
+}
+
 // --gpca-assoc-pheno FILE: the linear association scan (gpca_assoc_linear) of every SNP that passes the SNP QC, in row bands, into
 // P.<trait>.assoc.linear.  Runs last: it resets the keep mask to the QC mask (mu, sigma unchanged), which ends the fit's validity.
 // Covariates = the first P columns of the scores the run wrote, then the columns of --gpca-assoc-covar; a sample is included when every
@@ -464,6 +547,7 @@ int run_assoc(gpca::Engine& eng, const Args& a, const gpca_host::PlinkFileset& f
     std::vector<int64_t> rows;
     for (size_t i = 0; i < st.keep.size(); ++i) if (st.keep[i]) rows.push_back((int64_t)i);
     gpca_host::ensure_parent(a.output_prefix);
+    std::vector<double> a1_all(rows.size(), std::nan(""));                            // (of every kept row, for the sets' MAF rule)
     try {
         if (Tq) {
             std::vector<std::unique_ptr<gpca_host::AssocWriter>> w;
@@ -496,6 +580,7 @@ int run_assoc(gpca::Engine& eng, const Args& a, const gpca_host::PlinkFileset& f
                     else eng.assoc_logistic_score(Yg, Tg, C, Pc, &include, a.assoc_vif, b.first, b.second, stats, info);
                     for (int64_t r = b.first; r < b.second; ++r) {
                         const size_t i = (size_t)(r - b.first), o = (size_t)rows[(size_t)r];
+                        a1_all[(size_t)r] = info[5 * i + 1];
                         for (int32_t t = 0; t < Tg; ++t) {
                             const double* s5 = &stats[(i * (size_t)Tg + (size_t)t) * 5];
                             const double* s4 = a.assoc_spa ? &spa[(i * (size_t)Tg + (size_t)t) * 4] : nullptr;
@@ -509,6 +594,7 @@ int run_assoc(gpca::Engine& eng, const Args& a, const gpca_host::PlinkFileset& f
                 }
             }
         }
+        if (Tb && !a.assoc_set_list.empty()) run_assoc_sets(eng, a, fs, rows, a1_all, Yb, Tb, bnames, C, Pc, include);
     } catch (const gpca::Error& e) {
         if (e.status() != GPCA_ERR_STATE) throw;
         std::fputs(kAssocNeedsResident, stderr);
@@ -867,6 +953,19 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "error: --gpca-assoc-firth-z must be at least 0, or inf for no correction\n");
             return 2;
         }
+        if (!a.assoc_set_list.empty() && !a.assoc_logistic) { std::fprintf(stderr, "error: --gpca-assoc-set-list needs --gpca-assoc-logistic\n"); return 2; }
+        if (a.assoc_set_list.empty() && (a.have_assoc_set_max_maf || a.have_assoc_set_weights)) {
+            std::fprintf(stderr, "error: --gpca-assoc-set-max-maf and --gpca-assoc-set-weights need --gpca-assoc-set-list\n");
+            return 2;
+        }
+        if (a.have_assoc_set_max_maf && !(a.assoc_set_max_maf > 0.0 && a.assoc_set_max_maf <= 0.5)) {
+            std::fprintf(stderr, "error: --gpca-assoc-set-max-maf must lie in (0, 0.5]\n");
+            return 2;
+        }
+        if (a.have_assoc_set_weights && a.assoc_set_weights != "beta" && a.assoc_set_weights != "flat") {
+            std::fprintf(stderr, "error: --gpca-assoc-set-weights must be beta or flat\n");
+            return 2;
+        }
         if (!a.assoc_pheno.empty()) {
             if (!a.eigensnp) { std::fprintf(stderr, "error: --gpca-assoc-pheno needs the --eigensnp workflow\n"); return 2; }
             if (a.have_assoc_pcs && !(a.assoc_pcs >= 0 && a.assoc_pcs <= a.k_global)) {
@@ -901,6 +1000,10 @@ int main(int argc, char** argv) {
                 std::fprintf(stderr, "error: --gpca-assoc-pheno: %lld traits + %lld PCs + %lld covariates are more than %lld columns\n", (long long)t, (long long)p,
                              (long long)c, (long long)kAssocMaxColumns);
                 return 2;
+            }
+            if (!a.assoc_set_list.empty()) {                                          // (its format, before any work on the device)
+                try { gpca_host::read_set_list(a.assoc_set_list, {}); }
+                catch (const std::runtime_error& e) { std::fprintf(stderr, "error: --gpca-assoc-set-list: %s\n", e.what()); return 2; }
             }
         }
         if (!a.project_model.empty()) return run_project_workflow(a);

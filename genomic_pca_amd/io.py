@@ -15,8 +15,9 @@ from __future__ import annotations
 
 import gzip
 import os
+import re
 from dataclasses import dataclass
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -858,4 +859,102 @@ def write_assoc_logistic(prefix: str, trait: str, chromosomes: Sequence[str], po
             f.write("#CHROM\tPOS\tID\tA1\tOBS_CT\tA1_FREQ\tBETA\tSE\tZ_STAT\tLOG10P" + ("" if spa is None else "\t" + name) + "\n")
         f.writelines(f"{chromosomes[i]}\t{int(positions[i])}\t{variant_ids[i]}\t{allele1[i]}\t{int(n_obs[i])}\t{_g6(a1_freq[i])}\t{_g6(beta[i])}\t"
                      f"{_g6(se[i])}\t{_g6(z[i])}\t{_g6(log10p[i])}{tail(i)}\n" for i in range(n))
+    return path
+
+
+# ---- gene-level set tests of the logistic score scan (gpca_assoc_logistic_set, gpca_set_test): twins in host/formats.hpp -----------------
+ASSOC_SET_MAX_ROWS = 128
+
+
+class VariantSet(NamedTuple):
+    name: str
+    chrom: str
+    pos: int
+    rows: np.ndarray        # kept rows (PCA-SNP order) of the listed IDs that are among the QC-kept SNPs: ascending, each once
+
+
+def read_set_list(path: str, kept_ids: Sequence[str]) -> List[VariantSet]:
+    """regenie's set list: one set per line, `NAME CHROM POS ID1,ID2,...` separated by blanks or tabs (empty lines and lines that start
+    with # are skipped).  kept_ids: the IDs of the QC-kept SNPs in PCA-SNP order; an ID that is not among them is dropped, an ID that
+    occurs twice among them means its first row, and an ID listed twice in a set counts once.  ValueError names the file and the line."""
+    at = {}
+    for i, v in enumerate(kept_ids):
+        at.setdefault(v, i)
+    out = []
+    with open(path) as f:
+        for ln, line in enumerate(f, 1):
+            p = line.split()
+            if not p or p[0].startswith("#"):
+                continue
+            if len(p) != 4:
+                raise ValueError(f"{path}:{ln}: `NAME CHROM POS ID1,ID2,...` is required")
+            if not re.fullmatch(r"[+-]?[0-9]{1,18}", p[2], re.ASCII):                  # (what the twin in host/formats.hpp takes)
+                raise ValueError(f"{path}:{ln}: `{p[2]}` is not a position")
+            pos = int(p[2])
+            rows = sorted({at[v] for v in p[3].split(",") if v in at})
+            out.append(VariantSet(p[0], p[1], pos, np.asarray(rows, np.int64)))
+    return out
+
+
+def set_weights(a1_freq, kind: str) -> np.ndarray:
+    """The weights of a set's variants from their A1 frequencies: `beta` = the Beta(maf; 1, 25) density 25 (1 - maf)^24 with
+    maf = min(f, 1 - f) (the power by three squarings and one product, so that both programs round alike), `flat` = 1."""
+    f = np.asarray(a1_freq, np.float64)
+    if kind == "flat":
+        return np.ones_like(f)
+    if kind != "beta":
+        raise ValueError("set_weights: beta or flat")
+    q = 1.0 - np.minimum(f, 1.0 - f)
+    q2 = q * q
+    q4 = q2 * q2
+    q8 = q4 * q4
+    return 25.0 * ((q8 * q8) * q8)
+
+
+def set_maf_ok(a1_freq, max_maf: float) -> np.ndarray:
+    """Which variants enter a set: min(f, 1 - f) <= max_maf (a variant without an observed call, f = NaN, does not)."""
+    f = np.asarray(a1_freq, np.float64)
+    with np.errstate(invalid="ignore"):
+        return np.minimum(f, 1.0 - f) <= max_maf
+
+
+def assoc_set_groups(sizes: Sequence[int], T: int, Pc: int, max_values: int = 1 << 26):
+    """[s0, s1) groups of consecutive sets (sizes = their row counts, each 1 .. 128) for one gpca_assoc_logistic_set call each: the listed
+    rows' workspace (rows x T (Pc + 3) doubles, as assoc_score_bands counts it) and Phi (T m (m + 1) / 2 doubles per set) hold at most
+    max_values entries each (at least one set)."""
+    out, s0, rows, tri = [], 0, 0, 0
+    for s, m in enumerate(sizes):
+        r, t = rows + m, tri + m * (m + 1) // 2
+        if s > s0 and (r * T * (Pc + 3) > max_values or t * T > max_values):
+            out.append((s0, s))
+            s0, r, t = s, m, m * (m + 1) // 2
+        rows, tri = r, t
+    if len(sizes) > s0:
+        out.append((s0, len(sizes)))
+    return out
+
+
+def write_assoc_set(prefix: str, trait: str, names: Sequence[str], chromosomes: Sequence[str], positions: Sequence[int], n_var, results) -> str:
+    """P.<trait>.assoc.set: one tab-separated line per set, in the order given, `#SET CHROM POS N_VAR N_USED BURDEN_BETA BURDEN_SE
+    BURDEN_Z BURDEN_LOG10P SKAT_Q SKAT_LOG10P SKAT`; numbers as %.6g, NaN as NA; SKAT = Y, N, F for the status 1, 0, 2 of gpca_set_test
+    (NA where SKAT_LOG10P is NA).  results: per set None (no test was made: everything after N_VAR is NA) or set_test's dict."""
+    path = f"{prefix}.{trait}.assoc.set"
+    n = len(names)
+    for a in (chromosomes, positions, n_var, results):
+        if len(a) != n:
+            raise ValueError("write_assoc_set: one entry per set in every column")
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    with open(path, "w") as f:
+        f.write("#SET\tCHROM\tPOS\tN_VAR\tN_USED\tBURDEN_BETA\tBURDEN_SE\tBURDEN_Z\tBURDEN_LOG10P\tSKAT_Q\tSKAT_LOG10P\tSKAT\n")
+        for i in range(n):
+            r = results[i]
+            head = f"{names[i]}\t{chromosomes[i]}\t{int(positions[i])}\t{int(n_var[i])}"
+            if r is None:
+                f.write(head + "\tNA" * 8 + "\n")
+                continue
+            lp = float(r["skat_log10p"])
+            f.write(f"{head}\t{int(r['m_used'])}\t{_g6(r['burden_beta'])}\t{_g6(r['burden_se'])}\t{_g6(r['burden_z'])}\t{_g6(r['burden_log10p'])}\t"
+                    f"{_g6(r['skat_q'])}\t{_g6(lp)}\t{'NA' if lp != lp else 'NYF'[int(r['skat_status'])]}\n")
     return path

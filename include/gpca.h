@@ -583,6 +583,74 @@ GPCA_API int gpca_assoc_logistic_firth(gpca_handle* h, const double* Y /* [N][T]
                                        double* ua /* [rows][T][Pc + 3] or NULL */, double* rowinfo /* [rows][5] or NULL */);
 GPCA_API int gpca_firth_log10p(const double* gt /* [n] */, const double* mu /* [n] */, int64_t n, double u, double* out /* [5] */);
 
+/* ---- a16: gene-level set tests of the logistic score scan (regenie --vc-tests, SAIGE-GENE, SKAT): the rare variants of one gene tested
+ * together.  gpca_assoc_logistic_set is gpca_assoc_logistic_score over the LISTED rows of n_sets sets (stats, ua and rowinfo of a listed
+ * row carry the bits gpca_assoc_logistic_score gives that row), followed by the covariance of the scores inside every set,
+ * Phi = G~^T W G~ per trait; gpca_set_test turns the scores and Phi of one set into a burden and a SKAT p-value on the host.
+ *  Setting.  That of a13 / a14: trait t, the included samples S, w = mu (1 - mu) as the f32 panel column a13 multiplies; a kept row i
+ *     has the exact integers n_obs, s1, s2 and its flip; its operand x (g, or 2 - g on a flipped row, where observed and in S, else
+ *     0), m = [missing and in S], xbar the operand's mean, a_i,j (j = 0 .. Pc) the values ua reports.  x~ = x + xbar m and
+ *     g~_i = x~_i - sum_j a_i,j Z_j, so that g~_i^T W g~_i = V_i.
+ *  Per pair (a, b), b <= a, of rows of one set and per trait, four sums over the samples:
+ *         XX = sum x_a x_b w,   XM = sum x_a m_b w,   MX = sum m_a x_b w,   MM = sum m_a m_b w
+ *     with f32 operands x_a or m_a on one side and w x_b or w m_b (w, 2 w or 0: exact) on the other, every product exact.  The
+ *     accumulation is a13's: the 16-sample group order (i, 8 + i); an f32 accumulator holds at most 256 samples, counted from sample 0,
+ *     before it is added to an f64 running sum; no split of the sample axis, no atomics; the M sums run only in groups where a wave
+ *     ballot finds a missing call (a product of 0 more or less changes no sum).  Then in f64, no fused multiply-add, in this order:
+ *         R_ab       = (XX + (xbar_b XM + xbar_a MX)) + (xbar_a xbar_b) MM
+ *         q_ab       = sum_{j = 1 .. Pc} a_a,j a_b,j           (from 0, j ascending)
+ *         Phi^op_ab  = (R_ab - a_a,0 a_b,0) - q_ab
+ *         Phi_ab     = s_a s_b Phi^op_ab,   s = -1 on a flipped row (allele A1's coding: the projection annihilates the constant the
+ *                      flip adds)
+ *     On the diagonal XM = MX = 0 and MM = e[w]: R_aa is a13's gwg and Phi_aa carries the bits of a13's V.  An entry with a row of
+ *     n_obs = 0 is NaN.
+ *  The call.  set_off [n_sets + 1] (set_off[0] = 0) cuts set_rows into the sets; each lists 1 <= m <= GPCA_SET_MAX_ROWS rows, strictly
+ *     ascending, in [0, K) in PCA-SNP order; a row may appear in several sets (it is then listed, and computed, once per set).
+ *     stats [listed][T][5], ua [listed][T][Pc + 3], rowinfo [listed][5] as in a13, each may be NULL; phi (required): set after set,
+ *     per set trait after trait, per trait the packed lower triangle of m (m + 1) / 2 entries row by row ((a, b) at a (a + 1) / 2 + b).
+ *     A Phi entry depends on its two rows, S, N and the trait alone: not on the set's other rows, the pair's position, the other
+ *     sets of the call or the storage mode (int8, 2-bit, a GPCA_PREC_F32_MFMA handle).
+ *     Errors: a13's, and GPCA_ERR_BAD_ARG for a NULL phi, n_sets < 1, a set that is empty, longer than GPCA_SET_MAX_ROWS or not strictly
+ *     ascending (gpca_last_error names the set's index) and a row outside [0, K); GPCA_ERR_OOM is checked before any allocation;
+ *     streamed and row-sharded handles: GPCA_ERR_STATE.
+ *  gpca_set_test (host only, no handle; f64, no fused multiply-add): u [m] = the scores for allele A1 (s U), phi = the packed lower
+ *     triangle, weight [m] or NULL = 1 (a NaN or negative weight, m < 1 or m > GPCA_SET_MAX_ROWS, a NULL u, phi or out: GPCA_ERR_BAD_ARG).
+ *     Rows used: u finite, Phi_ii finite and > 0, weight finite and > 0; with omega their weights and A_ij = (omega_i Phi_ij) omega_j:
+ *     out [10] = m_used, burden beta, burden se, burden z, burden -log10 p, SKAT Q, SKAT -log10 p, SKAT status, z_Q, zeta; with
+ *     m_used = 0 everything after it is NaN and the status 0.
+ *     Burden.  t_i = omega_i u_i; B = sum t_i; v = sum_i sum_j A_ij (i, then j, ascending); z = B / sqrt(v), beta = B / v,
+ *         se = 1 / sqrt(v), -log10 p = gpca_normal_log10p(z); all NaN unless v > 0.
+ *     SKAT.  Q = sum t_i^2.  lambda = the eigenvalues of A, descending, from the function behind gpca_host_eigh_desc; those above
+ *         (mean of the non-negative lambda) / 1e5 are kept (the SKAT package's rule; none kept, or an A that is not finite: Q alone
+ *         is reported).  c1 = sum lambda, c2 = sum lambda^2, z_Q = (Q - c1) / sqrt(2 c2).
+ *         bulk = -log10(1 - Phi_N(x)) with kappa = c2 / c1, nu = c1 c1 / c2, h = 2 / (9 nu),
+ *                x = (cbrt(Q / (kappa nu)) - (1 - h)) / sqrt(h)            (Satterthwaite, Wilson-Hilferty)
+ *             the one-sided normal tail in log space: gpca_normal_log10p(x) + log10(2) for x >= 0, -log1p(-erfc(-x / sqrt 2) / 2) / ln 10
+ *             below.
+ *         status 0 (z_Q < 0.5 or NaN; a14's cutoff for a14's reason: w and v of the tail both tend to 0 there): bulk, zeta NaN.
+ *         otherwise Kuonen's saddle point with K(zeta) = -(1/2) sum log1p(-2 zeta lambda), K' = sum lambda / (1 - 2 zeta lambda),
+ *         K'' = 2 sum (lambda / (1 - 2 zeta lambda))^2.  The root of K' = Q on (lo, hi) = (0, ub), ub = 1 / (2 lambda_1):
+ *             zeta = (Q - c1) / (2 c2); outside (lo, hi): zeta = (lo + hi) / 2
+ *             for rep = 1 .. 200:
+ *                 f = K'(zeta) - Q;  f not finite: stop, no root
+ *                 f > 0: hi = zeta, else lo = zeta
+ *                 zeta' = zeta - f / K''(zeta);  outside (lo, hi): zeta' = (lo + hi) / 2
+ *                 found = |zeta' - zeta| <= 1e-10 ub;  zeta = zeta';  stop when found
+ *         w = sqrt(2 (zeta Q - K)), v = zeta sqrt(K''), r = w + log(v / w) / w at the final zeta.
+ *         status 1: a root was found and r is finite and > 0: -log10 p = the one-sided tail of r.
+ *         status 2: otherwise: bulk (zeta = what was reached).
+ *  Not there: SKAT-O and ACAT; collapsing of ultra-rare variants and sets above GPCA_SET_MAX_ROWS; quantitative traits; SAIGE-GENE+'s
+ *     rescaling of Phi from saddle-point p-values (the set tests inherit the normal approximation at extreme case imbalance); Davies'
+ *     method; annotation and mask files; streamed and row-sharded handles. */
+#define GPCA_SET_MAX_ROWS 128
+GPCA_API int gpca_assoc_logistic_set(gpca_handle* h, const double* Y /* [N][T], 0 / 1 */, int32_t T, const double* C /* [N][Pc] or NULL */,
+                                     int32_t Pc, const uint8_t* include /* [N] or NULL */, double max_vif, int32_t n_sets,
+                                     const int64_t* set_off /* [n_sets + 1] */, const int64_t* set_rows /* [set_off[n_sets]] */,
+                                     double* stats /* [listed][T][5] or NULL */, double* ua /* [listed][T][Pc + 3] or NULL */,
+                                     double* rowinfo /* [listed][5] or NULL */, double* phi /* per set [T][m (m + 1) / 2] */);
+GPCA_API int gpca_set_test(const double* u /* [m] */, const double* phi /* [m (m + 1) / 2] */, const double* weight /* [m] or NULL */,
+                           int32_t m, double* out /* [10] */);
+
 /* ---- f3: the stages of EigenSNPCoreAlgorithm::compute_pca (main.rs:311-327, 359-366) ------------------------------------------
  * The algorithm lives in the un-vendored efficient_pca crate (Cargo.toml:30, branch "main", no pinned revision): what follows is
  * the stage structure of its published description -- per-LD-block local bases learnt on a sample subset, condensed features of

@@ -297,6 +297,40 @@ public:
         const int rc = gt.size() != mu.size() ? GPCA_ERR_BAD_ARG : gpca_firth_log10p(gt.data(), mu.data(), (int64_t)gt.size(), u, out);
         if (rc != GPCA_OK) throw Error(rc, std::string("gpca_firth_log10p: ") + gpca_status_string(rc));
     }
+    // the gene-level set scan (gpca_assoc_logistic_set; gpca.h section a16): set_off [n_sets + 1] cuts set_rows into sets of 1 .. 128
+    // strictly ascending kept rows; stats / rowinfo / ua per LISTED row as in assoc_logistic_score; phi = set after set, trait after
+    // trait, the packed lower triangle of the covariance of the set's scores (allele A1's coding)
+    void assoc_logistic_set(const std::vector<double>& Y, int32_t T, const std::vector<double>& C, int32_t Pc, const std::vector<uint8_t>* include,
+                            double max_vif, const std::vector<int64_t>& set_off, const std::vector<int64_t>& set_rows, std::vector<double>& stats,
+                            std::vector<double>& rowinfo, std::vector<double>& phi, std::vector<double>* ua = nullptr) const {
+        if (set_off.size() < 2 || (size_t)set_off.back() != set_rows.size()) throw Error(GPCA_ERR_BAD_ARG, "assoc_logistic_set: set_off does not cut set_rows");
+        const size_t rows = set_rows.size();
+        size_t tri = 0;
+        for (size_t s = 0; s + 1 < set_off.size(); ++s) {
+            const size_t m = set_off[s + 1] > set_off[s] ? (size_t)(set_off[s + 1] - set_off[s]) : 0;
+            tri += m * (m + 1) / 2;
+        }
+        stats.assign(std::max<size_t>(rows * (size_t)T * 5, 1), 0.0);
+        rowinfo.assign(std::max<size_t>(rows * 5, 1), 0.0);
+        phi.assign(std::max<size_t>(tri * (size_t)T, 1), 0.0);
+        if (ua) ua->assign(std::max<size_t>(rows * (size_t)T * (size_t)(Pc + 3), 1), 0.0);
+        check(gpca_assoc_logistic_set(h_, Y.data(), T, Pc ? C.data() : nullptr, Pc, include ? include->data() : nullptr, max_vif,
+                                      (int32_t)(set_off.size() - 1), set_off.data(), set_rows.data(), stats.data(), ua ? ua->data() : nullptr,
+                                      rowinfo.data(), phi.data()));
+        stats.resize(rows * (size_t)T * 5);
+        rowinfo.resize(rows * 5);
+        phi.resize(tri * (size_t)T);
+        if (ua) ua->resize(rows * (size_t)T * (size_t)(Pc + 3));
+    }
+    // the burden and SKAT tests of one set (gpca_set_test; host only): out [10] = m_used, burden beta, se, z, -log10 p, SKAT Q, -log10 p,
+    // status, z_Q, zeta; weight empty = 1
+    static void set_test(const std::vector<double>& u, const std::vector<double>& phi_lower, const std::vector<double>& weight, double* out) {
+        const size_t m = u.size();
+        const int rc = phi_lower.size() != m * (m + 1) / 2 || (!weight.empty() && weight.size() != m)
+                           ? GPCA_ERR_BAD_ARG
+                           : gpca_set_test(u.data(), phi_lower.data(), weight.empty() ? nullptr : weight.data(), (int32_t)m, out);
+        if (rc != GPCA_OK) throw Error(rc, std::string("gpca_set_test: ") + gpca_status_string(rc));
+    }
     // the null logistic model of one trait (gpca_logistic_null; host only): y [N] in {0, 1}, C [N][Pc]; alpha [Pc + 1], mu [N] (0 outside
     // the included samples); returns the number of Newton steps; throws Error with the status (no message: there is no handle)
     static int logistic_null(const std::vector<double>& y, const std::vector<double>& C, int32_t Pc, const std::vector<uint8_t>* include,
