@@ -10,5 +10,7 @@ from .distributed import shard_rows  # noqa: F401
 spa_log10p = GpcaEngine.spa_log10p
 firth_log10p = GpcaEngine.firth_log10p
 set_test = GpcaEngine.set_test
+fst_hudson = GpcaEngine.fst_hudson
+fst_wc = GpcaEngine.fst_wc
 
 __version__ = "0.2.2"

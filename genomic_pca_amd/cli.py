@@ -157,6 +157,20 @@ def build_parser() -> argparse.ArgumentParser:
                         "observed calls is at most X, 0 < X <= 0.5 [default: 0.01]")
     p.add_argument("--gpca-assoc-set-weights", default=None, metavar="KIND",
                    help="--gpca-assoc-set-list: beta = Beta(maf; 1, 25) weights, flat = 1 [default: beta]")
+    p.add_argument("--gpca-assoc-cc-freq", action="store_true",
+                   help="--gpca-assoc-logistic: the genotype counts and A1 frequencies of every SNP among the controls and the cases "
+                        "of every case / control trait, over the scan's include set -> <out>.<trait>.frq.cc (the .frq.strat format "
+                        "with the groups CTRL and CASE)")
+    p.add_argument("--gpca-within", default=None, metavar="FILE",
+                   help="--eigensnp: the sample groups of --gpca-freq-strat and --gpca-fst, a table `FID IID GROUP` with that header; "
+                        "NA = no group; at most 64 groups")
+    p.add_argument("--gpca-freq-strat", action="store_true",
+                   help="--gpca-within: the genotype counts, A1 frequency and HWE p-value of every SNP that passes the SNP QC inside "
+                        "every group -> <out>.frq.strat")
+    p.add_argument("--gpca-fst", default=None, metavar="METHOD",
+                   help="--gpca-within: Fst between every pair of groups over the SNPs that pass the SNP QC, hudson (Bhatia et al. "
+                        "2013) or wc (Weir and Cockerham 1984; with more than two groups also jointly) -> <out>.fst.summary")
+    p.add_argument("--gpca-fst-variants", action="store_true", help="--gpca-fst: also the per-SNP terms -> <out>.fst.var")
     p.add_argument("--gpca-assoc-pcs", type=int, default=None, metavar="P",
                    help="--gpca-assoc-pheno: the first P columns of the scores this run writes are covariates (0 <= P <= "
                         "--eigensnp-k-global) [default: every column]")
@@ -294,6 +308,8 @@ def run_eigensnp_workflow(a) -> int:
         raise SystemExit(PCRELATE_NEEDS_RESIDENT)
     if streamed and a.gpca_assoc_pheno is not None:
         raise SystemExit(ASSOC_NEEDS_RESIDENT)
+    if streamed and a.gpca_within is not None:
+        raise SystemExit(STRAT_NEEDS_RESIDENT)
     st = eng.snp_stats(QcConfig(a.eigensnp_min_call_rate, a.eigensnp_min_maf, a.eigensnp_max_hwe_p))
     blocks = gio.parse_ld_block_file(a.ld_block_file)
     keep, by_tag = gio.map_snps_to_ld_blocks(blocks, fs.chromosomes, fs.positions, st["keep"])
@@ -355,6 +371,8 @@ def run_eigensnp_workflow(a) -> int:
             n_fit))
     if a.gpca_make_pcrelate is not None:
         _pcrelate(eng, a, fs, cols, sample_ids, np.asarray(scores, np.float64)[:, :a.gpca_make_pcrelate], inset, len(rows))
+    if a.gpca_within is not None:
+        _strat(eng, a, fs, cols, sample_ids, st)
     if a.gpca_assoc_pheno is not None:
         _assoc(eng, a, fs, cols, sample_ids, np.asarray(scores, np.float64), inset, st)
     eng.close()
@@ -419,6 +437,89 @@ def _pcrelate(eng, a, fs, cols, sample_ids, V, inset, n_snps):
             raise SystemExit(PCRELATE_NEEDS_RESIDENT) from None
         raise
     _log(f"PC-Relate kinship of {n} samples over {n_snps} SNPs, adjusted for {V.shape[1]} PCs, written to {a.output_prefix}.pcrelate.kin")
+
+
+STRAT_NEEDS_RESIDENT = ("error: --gpca-within needs the genotype matrix resident on the device: the counts of a matrix walked out of core "
+                        "are not implemented")
+
+
+def _within_table(a):
+    """The table of --gpca-within, read once before any work on the device; refuses more than 64 groups, and fewer than 2 for --gpca-fst."""
+    try:
+        t = gio.read_within(a.gpca_within)
+    except OSError:
+        raise SystemExit(f"error: --gpca-within: cannot open {a.gpca_within}") from None
+    except ValueError as e:
+        raise SystemExit(f"error: --gpca-within: {e}") from None
+    if len(t.names) > gio.GROUPS_MAX:
+        raise SystemExit(f"error: --gpca-within: {len(t.names)} groups are more than {gio.GROUPS_MAX}")
+    if a.gpca_fst is not None and len(t.names) < 2:
+        raise SystemExit(f"error: --gpca-fst needs at least two groups, --gpca-within names {len(t.names)}")
+    if len(t.names) < 1:
+        raise SystemExit("error: --gpca-within names no group")
+    return t
+
+
+def _snp_meta(fs, rr):
+    return ([fs.chromosomes[i] for i in rr], [int(fs.positions[i]) for i in rr], [fs.variant_ids[i] for i in rr], [fs.allele1[i] for i in rr])
+
+
+def _strat(eng, a, fs, cols, sample_ids, st):
+    """--gpca-freq-strat / --gpca-fst: the genotype counts of every SNP that passes the SNP QC inside every group of --gpca-within
+    (gpca_group_counts), in row bands, into P.frq.strat, and Fst from them (gpca_fst_hudson / gpca_fst_wc) into P.fst.summary and
+    P.fst.var.  Resets the keep mask to the QC mask (mu, sigma unchanged), which ends the fit's validity; every kept sample with a
+    group counts, the KING in-set or not."""
+    from . import _lib
+    fids = fs.family_ids if cols is None else [fs.family_ids[i] for i in cols]
+    labels, names = gio.align_within(a.gpca_within_table, fids, sample_ids)
+    P = len(names)
+    eng.set_standardization(st["mu"], st["sigma"], st["keep"])                       # every SNP that passes the SNP QC
+    rows = np.flatnonzero(st["keep"])
+    pairs = gio.fst_pairs(P)
+    hud, wcp, wcj = np.zeros((max(len(pairs), 1), 3)), np.zeros((max(len(pairs), 1), 3)), np.zeros(3)
+    try:
+        for bi, (r0, r1) in enumerate(gio.group_count_bands(len(rows), P)):
+            c = eng.group_counts(labels, P, rows=(r0, r1))
+            meta = _snp_meta(fs, rows[r0:r1])
+            if a.gpca_freq_strat:
+                gio.write_frq_strat(f"{a.output_prefix}.frq.strat", *meta, names, c, append=bi > 0)
+            if a.gpca_fst == "hudson":
+                res = GpcaEngine.fst_hudson(c, sums=hud, per_variant=a.gpca_fst_variants)
+                if a.gpca_fst_variants:
+                    gio.write_fst_var(a.output_prefix, "hudson", *meta[:3], names, np.stack([res[2], res[3]], -1), append=bi > 0)
+            elif a.gpca_fst == "wc":
+                abc = np.zeros((r1 - r0, len(pairs), 3))
+                for q, (j, i) in enumerate(pairs):                                   # r = 2 on each pair
+                    use = np.zeros(P, np.uint8); use[[j, i]] = 1
+                    res = GpcaEngine.fst_wc(c, use, sums=wcp[q], per_variant=a.gpca_fst_variants)
+                    if a.gpca_fst_variants:
+                        abc[:, q] = res[2]
+                if P > 2:
+                    GpcaEngine.fst_wc(c, None, sums=wcj)
+                if a.gpca_fst_variants:
+                    gio.write_fst_var(a.output_prefix, "wc", *meta[:3], names, abc, append=bi > 0)
+    except _lib.GpcaError as e:
+        if e.status == _lib.GPCA_ERR_STATE:
+            raise SystemExit(STRAT_NEEDS_RESIDENT) from None
+        raise
+    n_lab = int((labels >= 0).sum())
+    if a.gpca_freq_strat:
+        _log(f"genotype counts of {len(rows)} SNPs in {P} groups ({n_lab} of {len(sample_ids)} samples), written to {a.output_prefix}.frq.strat")
+    if a.gpca_fst is not None:
+        sums = hud[:len(pairs)] if a.gpca_fst == "hudson" else (np.vstack([wcp[:len(pairs)], wcj[None]]) if P > 2 else wcp[:len(pairs)])
+        gio.write_fst_summary(a.output_prefix, a.gpca_fst, names, sums)
+        _log(f"{a.gpca_fst} Fst of {len(pairs)} pairs of groups over {len(rows)} SNPs, written to {a.output_prefix}.fst.summary")
+
+
+def _cc_freq(eng, a, fs, rows, Yb, bnames, include):
+    """--gpca-assoc-cc-freq: the genotype counts of every SNP among the controls and the cases of every case / control trait, over the
+    scan's include set (label -1 outside it), into P.<trait>.frq.cc in the .frq.strat format."""
+    for t, name in enumerate(bnames):
+        labels = np.where(include, Yb[:, t].astype(np.int32), -1).astype(np.int32)
+        for bi, (r0, r1) in enumerate(gio.group_count_bands(len(rows), 2)):
+            c = eng.group_counts(labels, 2, rows=(r0, r1))
+            gio.write_frq_strat(f"{a.output_prefix}.{name}.frq.cc", *_snp_meta(fs, rows[r0:r1]), ["CTRL", "CASE"], c, append=bi > 0)
+    _log(f"case / control genotype counts of {len(rows)} SNPs for {len(bnames)} traits, written to {a.output_prefix}.<trait>.frq.cc")
 
 
 ASSOC_NEEDS_RESIDENT = ("error: --gpca-assoc-pheno needs the genotype matrix resident on the device: the scan of a matrix walked out of "
@@ -507,6 +608,8 @@ def _assoc(eng, a, fs, cols, sample_ids, scores, inset, st):
         rr = rows[r0:r1]
         return ([fs.chromosomes[i] for i in rr], [int(fs.positions[i]) for i in rr], [fs.variant_ids[i] for i in rr], [fs.allele1[i] for i in rr])
     try:
+        if a.gpca_assoc_cc_freq and bnames:
+            _cc_freq(eng, a, fs, rows, Yb, bnames, include)
         for bi, (r0, r1) in enumerate(gio.assoc_bands(len(rows), T + Pc) if T else []):
             r = eng.assoc_linear(Y, C, include=include, max_vif=vif, rows=(r0, r1))
             meta = meta_of(r0, r1)
@@ -692,6 +795,22 @@ def main(argv=None) -> int:
         raise SystemExit("error: --gpca-assoc-set-max-maf must lie in (0, 0.5]")
     if a.gpca_assoc_set_weights is not None and a.gpca_assoc_set_weights not in ("beta", "flat"):
         raise SystemExit("error: --gpca-assoc-set-weights must be beta or flat")
+    if a.gpca_assoc_cc_freq and not a.gpca_assoc_logistic:
+        raise SystemExit("error: --gpca-assoc-cc-freq needs --gpca-assoc-logistic")
+    if a.gpca_within is None and (a.gpca_freq_strat or a.gpca_fst is not None):
+        raise SystemExit("error: --gpca-freq-strat and --gpca-fst need --gpca-within")
+    if a.gpca_fst_variants and a.gpca_fst is None:
+        raise SystemExit("error: --gpca-fst-variants needs --gpca-fst")
+    if a.gpca_fst is not None and a.gpca_fst not in ("hudson", "wc"):
+        raise SystemExit("error: --gpca-fst must be hudson or wc")
+    if a.gpca_within is not None:
+        if not a.eigensnp:
+            raise SystemExit("error: --gpca-within needs the --eigensnp workflow")
+        if not a.gpca_freq_strat and a.gpca_fst is None:
+            raise SystemExit("error: --gpca-within needs --gpca-freq-strat or --gpca-fst")
+        if a.gpca_stream == "on":
+            raise SystemExit(STRAT_NEEDS_RESIDENT)
+        a.gpca_within_table = _within_table(a)
     if a.gpca_assoc_pheno is not None:
         if not a.eigensnp:
             raise SystemExit("error: --gpca-assoc-pheno needs the --eigensnp workflow")

@@ -402,4 +402,11 @@ int launch_assoc_set_gram(hipStream_t st, const void* G, int packed, int64_t ldr
 int launch_assoc_set_finish(hipStream_t st, const double* dv, const unsigned* sums, int T, int Pc, const AsgStrip* strips, int64_t n_strips,
                             double* phi);
 
+// ---- per-group genotype counts (group_counts.hip): O [gc_ppad(P)][gc_npad(N)] = the one-hot matrix of the labels group [N] (-1: no
+// group), size [P] = the samples of each group; counts [row1 - row0][P][3] u32 = n_obs, n_het, n_hom2 of kept rows [row0, row1) (PCA-SNP
+// order through krows); *bad as in launch_assoc
+void launch_gc_onehot(hipStream_t st, const int32_t* group, int64_t N, int P, uint8_t* O);
+int launch_group_counts(hipStream_t st, const void* G, int packed, int64_t ldr, const int64_t* krows, int64_t N, const uint8_t* O,
+                        const unsigned* size, int P, int64_t row0, int64_t row1, unsigned* counts, unsigned long long* bad);
+
 }  // namespace gpca

@@ -408,4 +408,36 @@ constexpr double asg_call_bytes(int64_t N, int64_t listed, int64_t strips, int64
            (double)sizeof(AsgStrip) * (double)asg_strip_capacity(strips) + 8.0 * (double)asg_phi_capacity(tri_total, T);
 }
 
+// ---- per-group genotype counts (group_counts.hip, gpca_group_counts.cpp) -----------------------------------------------------------
+// A workgroup of kGcThreads threads owns kGcRows consecutive kept rows of the band (32 per wave) and all P <= kGcMaxGroups groups,
+// padded to 32 or 64 one-hot columns; it walks the samples in stages of kGcStage with the scans' staging map (thread t: the 32 samples
+// of half t & 1 of row t / 2) and multiplies blocks of kGcBlock samples (one v_mfma_i32_32x32x32_i8 per plane and column block; the
+// missing plane only where a wave ballot over its 32 rows x kGcBlock samples finds a missing call).  No split of the sample axis: a
+// workgroup writes the counts of its rows once.
+constexpr int kGcRows = 128, kGcThreads = 256, kGcStage = 64, kGcBlock = 32, kGcMaxGroups = 64;
+constexpr int kGcPitch = kGcStage + 16;              // bytes per staged row of calls and per staged one-hot column (ds_read_b128 stays 16-byte aligned)
+static_assert(kGcStage == kAscStage && kGcThreads * 32 == kGcRows * kGcStage && kGcStage % kGcBlock == 0, "the scans' stage and staging map");
+static_assert(kGcMaxGroups * (kGcStage / 16) == kGcThreads, "a thread stages 16 bytes of one one-hot column");
+constexpr int gc_ppad(int P) { return P <= 32 ? 32 : 64; }
+constexpr int64_t gc_npad(int64_t N) { return asc_npad(N); }
+constexpr int64_t gc_stages(int64_t N) { return asc_stages(N); }
+constexpr int64_t gc_row_blocks(int64_t rows) { return (rows + kGcRows - 1) / kGcRows; }
+// where thread t of a stage reads its 16 one-hot bytes of stage s (column t / 4, quarter t & 3), and where a workgroup's thread t
+// reads its 32 samples of a row (a byte offset into the row: int8 32 bytes, 2-bit 8 bytes)
+constexpr int64_t gc_onehot_offset(int64_t npad, int t, int64_t s) { return (int64_t)(t >> 2) * npad + s * kGcStage + 16 * (t & 3); }
+constexpr int64_t gc_row_offset(bool packed, int t, int64_t s) { return packed ? (s * kGcStage + 32 * (t & 1)) >> 2 : s * kGcStage + 32 * (t & 1); }
+// where the count c (0 n_obs, 1 n_het, 2 n_hom2) of band row r and group p lies
+constexpr int64_t gc_counts_index(int64_t r, int P, int p, int c) { return (r * P + p) * 3 + c; }
+// elements of the call's buffers: the one-hot matrix [gc_ppad(P)][gc_npad(N)] (bytes, zero past N, past P and on label -1); the labels
+// [N] (i32); the group sizes [kGcMaxGroups] (u32); counts [rows][P][3] (u32); the invalid-genotype word (8 bytes)
+constexpr int64_t gc_onehot_capacity(int64_t N, int P) { return (int64_t)gc_ppad(P) * gc_npad(N); }
+constexpr int64_t gc_label_capacity(int64_t N) { return N; }
+constexpr int64_t gc_size_capacity() { return kGcMaxGroups; }
+constexpr int64_t gc_counts_capacity(int64_t rows, int P) { return 3 * rows * (int64_t)P; }
+// The device bytes a call allocates (gpca_group_counts' GPCA_ERR_OOM sum, without the check's slack)
+constexpr double gc_call_bytes(int64_t N, int64_t rows, int P) {
+    return (double)gc_onehot_capacity(N, P) + 4.0 * (double)gc_label_capacity(N) + 4.0 * (double)gc_size_capacity() +
+           4.0 * (double)gc_counts_capacity(rows, P) + 8.0;
+}
+
 }  // namespace gpca

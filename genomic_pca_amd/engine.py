@@ -665,6 +665,76 @@ class GpcaEngine:
         res["m_used"], res["skat_status"] = int(out[0]), int(out[7])
         return res
 
+    def group_counts(self, group, n_groups: Optional[int] = None, rows: Optional[Tuple[int, int]] = None) -> np.ndarray:
+        """Genotype counts inside sample groups (gpca_group_counts; gpca.h section a17): group [N] = every sample's group 0 .. P - 1, or
+        -1 for none; n_groups = P (default: the largest label + 1, at least 1; at most 64); rows = (row0, row1): the kept rows
+        [row0, row1) in PCA-SNP order (default: all).  Returns uint32 [rows][P][3] = n_obs, n_het, n_hom2: the group's samples with an
+        observed call on the row, with g = 1 and with g = 2 (copies of A1).  Exact integers; a band carries the bits of the full call."""
+        N = self.dims()[1]
+        gv = np.asarray(group)
+        if gv.shape != (N,) or gv.dtype.kind not in "iu":
+            raise ValueError("group must be an integer array with one label per sample")
+        gv = np.ascontiguousarray(np.clip(gv.astype(np.int64), -1, 1 << 30), np.int32)
+        P = int(n_groups) if n_groups is not None else max(int(gv.max(initial=-1)) + 1, 1)
+        K = int(self._lib.gpca_num_pca_snps(self._h))
+        r0, r1 = (0, K) if rows is None else (int(rows[0]), int(rows[1]))
+        n = max(r1 - r0, 0)
+        out = np.zeros((max(n, 1), max(min(P, 64), 1), 3), np.uint32)
+        self._chk(self._lib.gpca_group_counts(self._h, _vp(gv), P, r0, r1, _vp(out)))
+        return out[:n]
+
+    @staticmethod
+    def _fst_counts(counts):
+        cv = np.ascontiguousarray(counts, np.uint32)
+        if cv.ndim != 3 or cv.shape[2] != 3:
+            raise ValueError("counts must be [rows][P][3] as group_counts returns them")
+        return cv
+
+    @staticmethod
+    def fst_hudson(counts, sums=None, per_variant: bool = False):
+        """Hudson's Fst of every pair of groups (gpca_fst_hudson; host only; gpca.h section a17) from counts [rows][P][3].  sums
+        [P (P - 1) / 2][3] = the running sum of the numerators, of the denominators and the rows used per pair (j < i at
+        i (i - 1) / 2 + j), ADDED TO in place when given (band after band), else started at zero.  Returns (fst [pairs] = sum num /
+        sum den, NaN where that is 0 / 0, sums), and with per_variant=True also num, den [rows][pairs] (NaN where a group of the pair has
+        no observed call)."""
+        cv = GpcaEngine._fst_counts(counts)
+        rows, P = cv.shape[0], cv.shape[1]
+        pairs = P * (P - 1) // 2
+        sv = np.zeros((max(pairs, 1), 3)) if sums is None else sums
+        if sv.dtype != np.float64 or not sv.flags.c_contiguous or sv.shape != (max(pairs, 1), 3):
+            raise ValueError("sums must be a C-contiguous float64 array [P (P - 1) / 2][3]")
+        num = np.zeros((max(rows, 1), max(pairs, 1))) if per_variant else None
+        den = np.zeros((max(rows, 1), max(pairs, 1))) if per_variant else None
+        lib = _lib.load()
+        rc = lib.gpca_fst_hudson(_vp(cv), rows, P, _vp(num), _vp(den), _vp(sv))
+        if rc != 0:
+            raise GpcaError(rc, "gpca_fst_hudson: " + lib.gpca_status_string(rc).decode())
+        with np.errstate(invalid="ignore", divide="ignore"):
+            fst = np.where(sv[:pairs, 1] != 0.0, sv[:pairs, 0] / sv[:pairs, 1], np.nan)
+        return (fst, sv, num[:rows, :pairs], den[:rows, :pairs]) if per_variant else (fst, sv)
+
+    @staticmethod
+    def fst_wc(counts, use=None, sums=None, per_variant: bool = False):
+        """Weir and Cockerham's Fst over the groups with use[p] != 0 (None: all; at least two) (gpca_fst_wc; host only; gpca.h section
+        a17) from counts [rows][P][3].  sums [3] = the running sum of a, of a + b + c and the rows used, ADDED TO in place when given,
+        else started at zero.  Returns (fst = sum a / sum (a + b + c), NaN for 0 / 0, sums), and with per_variant=True also abc
+        [rows][3] (NaN where a used group has no observed call)."""
+        cv = GpcaEngine._fst_counts(counts)
+        rows, P = cv.shape[0], cv.shape[1]
+        uv = None if use is None else np.ascontiguousarray(np.asarray(use) != 0, np.uint8)
+        if uv is not None and uv.shape != (P,):
+            raise ValueError("use must have one entry per group")
+        sv = np.zeros(3) if sums is None else sums
+        if sv.dtype != np.float64 or not sv.flags.c_contiguous or sv.shape != (3,):
+            raise ValueError("sums must be a C-contiguous float64 array [3]")
+        abc = np.zeros((max(rows, 1), 3)) if per_variant else None
+        lib = _lib.load()
+        rc = lib.gpca_fst_wc(_vp(cv), rows, P, _vp(uv), _vp(abc), _vp(sv))
+        if rc != 0:
+            raise GpcaError(rc, "gpca_fst_wc: " + lib.gpca_status_string(rc).decode())
+        fst = float(sv[0] / sv[1]) if sv[1] != 0.0 else float("nan")
+        return (fst, sv, abc[:rows]) if per_variant else (fst, sv)
+
     @staticmethod
     def logistic_null(y, covar=None, include=None):
         """The null logistic model of one case / control trait (gpca_logistic_null; host only): y [N] in {0, 1} on the included samples,

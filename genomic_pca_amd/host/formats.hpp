@@ -1011,6 +1011,145 @@ private:
     OutFile o_;
 };
 
+// ---- genotype counts inside sample groups and Fst: the twins of io.read_within, io.align_within, io.group_count_bands,
+// io.write_frq_strat, io.write_fst_summary and io.write_fst_var (same rules, same error texts, byte-identical files) ---------------------
+constexpr int64_t kGroupsMax = 64;
+struct WithinTable {
+    std::vector<std::string> family_ids, sample_ids, groups;   // groups: "" = in no group (NA)
+    std::vector<uint8_t> has_group;
+    std::vector<std::string> names;                              // the group names in order of first appearance in the file
+};
+// A whitespace-separated table `FID IID GROUP`.  The header (a leading '#' allowed) is required; `NA` means no group; a repeated
+// (FID, IID) is refused.
+inline WithinTable read_within(const std::string& path) {
+    std::ifstream in(path);
+    if (!in) throw std::runtime_error("cannot open " + path);
+    WithinTable t;
+    bool have_header = false;
+    std::set<std::pair<std::string, std::string>> seen;
+    std::set<std::string> known;
+    std::string line;
+    const std::string need = path + ": the header `FID IID GROUP` is required";
+    auto upper = [](std::string s) { for (char& c : s) c = (char)std::toupper((unsigned char)c); return s; };
+    for (int64_t ln = 1; std::getline(in, line); ++ln) {
+        const std::vector<std::string> p = split_ws(line);
+        if (p.empty()) continue;
+        if (!have_header) {
+            if (p.size() != 3 || upper(p[0].substr(std::min(p[0].find_first_not_of('#'), p[0].size()))) != "FID" || upper(p[1]) != "IID" ||
+                upper(p[2]) != "GROUP")
+                throw std::runtime_error(need);
+            have_header = true;
+            continue;
+        }
+        const std::string at = path + ":" + std::to_string(ln) + ": ";
+        if (p.size() != 3) throw std::runtime_error(at + std::to_string(p.size()) + " fields, the header has 3");
+        if (!seen.insert({p[0], p[1]}).second) throw std::runtime_error(at + "sample " + p[0] + " " + p[1] + " appears twice");
+        const bool has = p[2] != "NA";
+        if (has && known.insert(p[2]).second) t.names.push_back(p[2]);
+        t.family_ids.push_back(p[0]); t.sample_ids.push_back(p[1]); t.groups.push_back(has ? p[2] : std::string()); t.has_group.push_back(has ? 1 : 0);
+    }
+    if (!have_header) throw std::runtime_error(need);
+    return t;
+}
+// labels in .fam order: p = the sample is in group names[p], -1 = it is absent from the table or has no group
+inline std::vector<int32_t> align_within(const WithinTable& t, const std::vector<std::string>& family_ids, const std::vector<std::string>& sample_ids) {
+    std::map<std::string, int32_t> index;
+    for (size_t p = 0; p < t.names.size(); ++p) index[t.names[p]] = (int32_t)p;
+    std::map<std::pair<std::string, std::string>, size_t> at;
+    for (size_t r = 0; r < t.sample_ids.size(); ++r) at[{t.family_ids[r], t.sample_ids[r]}] = r;
+    std::vector<int32_t> out(sample_ids.size(), -1);
+    for (size_t n = 0; n < sample_ids.size(); ++n) {
+        const auto it = at.find({family_ids[n], sample_ids[n]});
+        if (it != at.end() && t.has_group[it->second]) out[n] = index[t.groups[it->second]];
+    }
+    return out;
+}
+// [row0, row1) bands of the K kept rows whose counts (rows x P x 3) hold at most max_values entries (at least one row)
+inline std::vector<std::pair<int64_t, int64_t>> group_count_bands(int64_t K, int64_t P, int64_t max_values = (int64_t)1 << 26) {
+    const int64_t step = std::max<int64_t>(max_values / (3 * std::max<int64_t>(P, 1)), 1);
+    std::vector<std::pair<int64_t, int64_t>> out;
+    for (int64_t r0 = 0; r0 < K; r0 += step) out.emplace_back(r0, std::min(r0 + step, K));
+    return out;
+}
+inline void fmt_g6(char (&b)[48], double v) { if (v != v) std::snprintf(b, sizeof b, "NA"); else std::snprintf(b, sizeof b, "%.6g", v); }
+inline void fmt_ratio6(char (&b)[48], double num, double den) {
+    if (num != num || den != den || den == 0.0) std::snprintf(b, sizeof b, "NA"); else fmt_g6(b, num / den);
+}
+// The stratified frequency file `path` (P.frq.strat, P.<trait>.frq.cc): one tab-separated line per SNP and group, SNP-major, `#CHROM POS
+// ID A1 GROUP OBS_CT A1_CT A1_FREQ HET_CT HOM_A1_CT HWE_P` from a SNP's counts [groups][3] = n_obs, n_het, n_hom2; A1_FREQ and HWE_P (the
+// caller's function: gpca_hwe_chi_squared_p_value) as %.6g, NA where OBS_CT = 0; rows are added band by band
+class FrqStratWriter {
+public:
+    FrqStratWriter(const std::string& path, const std::vector<std::string>& names, double (*hwe)(uint64_t, uint64_t, uint64_t))
+        : o_(path), names_(names), hwe_(hwe) {
+        std::fputs("#CHROM\tPOS\tID\tA1\tGROUP\tOBS_CT\tA1_CT\tA1_FREQ\tHET_CT\tHOM_A1_CT\tHWE_P\n", o_.f);
+    }
+    void add_row(const std::string& chrom, int64_t pos, const std::string& id, const std::string& a1, const uint32_t* counts) {
+        for (size_t p = 0; p < names_.size(); ++p) {
+            const uint64_t obs = counts[3 * p], het = counts[3 * p + 1], hom = counts[3 * p + 2], ac = het + 2 * hom;
+            char fr[48], hw[48];
+            if (obs == 0) { fmt_g6(fr, std::nan("")); fmt_g6(hw, std::nan("")); }
+            else { fmt_g6(fr, (double)ac / (2.0 * (double)obs)); fmt_g6(hw, hwe_(obs - het - hom, het, hom)); }
+            std::fprintf(o_.f, "%s\t%lld\t%s\t%s\t%s\t%llu\t%llu\t%s\t%llu\t%llu\t%s\n", chrom.c_str(), (long long)pos, id.c_str(), a1.c_str(),
+                         names_[p].c_str(), (unsigned long long)obs, (unsigned long long)ac, fr, (unsigned long long)het, (unsigned long long)hom, hw);
+        }
+    }
+
+private:
+    OutFile o_;
+    std::vector<std::string> names_;
+    double (*hwe_)(uint64_t, uint64_t, uint64_t);
+};
+// P.fst.summary: `#GROUP1 GROUP2 N_VAR HUDSON_FST` (wc = false) or `... WC_FST`, one line per pair (j < i at i (i - 1) / 2 + j, GROUP1 the
+// earlier group) from sums [pairs][3]; for wc with more than two groups a further last row of sums is written as `* * N_VAR FST`
+inline void write_fst_summary(const std::string& prefix, bool wc, const std::vector<std::string>& names, const std::vector<double>& sums) {
+    const size_t P = names.size(), pairs = P * (P - 1) / 2;
+    const bool joint = wc && P > 2;
+    if (sums.size() != (pairs + (joint ? 1 : 0)) * 3)
+        throw std::runtime_error("write_fst_summary: sums must be [pairs][3] (one more row for the joint wc value of more than two groups)");
+    OutFile o(prefix + ".fst.summary");
+    std::fprintf(o.f, "#GROUP1\tGROUP2\tN_VAR\t%s\n", wc ? "WC_FST" : "HUDSON_FST");
+    char b[48];
+    size_t q = 0;
+    for (size_t i = 1; i < P; ++i)
+        for (size_t j = 0; j < i; ++j, ++q) {
+            if (sums[3 * q + 2] == 0.0) fmt_g6(b, std::nan("")); else fmt_ratio6(b, sums[3 * q], sums[3 * q + 1]);
+            std::fprintf(o.f, "%s\t%s\t%lld\t%s\n", names[j].c_str(), names[i].c_str(), (long long)sums[3 * q + 2], b);
+        }
+    if (joint) {
+        if (sums[3 * q + 2] == 0.0) fmt_g6(b, std::nan("")); else fmt_ratio6(b, sums[3 * q], sums[3 * q + 1]);
+        std::fprintf(o.f, "*\t*\t%lld\t%s\n", (long long)sums[3 * q + 2], b);
+    }
+}
+// P.fst.var: one tab-separated line per SNP and pair (SNP-major): `#CHROM POS ID GROUP1 GROUP2 NUM DEN FST` (wc = false; a SNP's values
+// [pairs][2] = num, den) or `#CHROM POS ID GROUP1 GROUP2 A B C FST` (values [pairs][3] = a, b, c); %.6g, NaN as NA; FST = NUM / DEN or
+// A / ((A + B) + C), NA where that is NaN or the denominator is 0; rows are added band by band
+class FstVarWriter {
+public:
+    FstVarWriter(const std::string& prefix, bool wc, const std::vector<std::string>& names) : o_(prefix + ".fst.var"), wc_(wc), names_(names) {
+        std::fprintf(o_.f, "#CHROM\tPOS\tID\tGROUP1\tGROUP2\t%s\tFST\n", wc ? "A\tB\tC" : "NUM\tDEN");
+    }
+    void add_row(const std::string& chrom, int64_t pos, const std::string& id, const double* values) {
+        const int w = wc_ ? 3 : 2;
+        size_t q = 0;
+        for (size_t i = 1; i < names_.size(); ++i)
+            for (size_t j = 0; j < i; ++j, ++q) {
+                const double* v = values + q * w;
+                char b[4][48];
+                for (int k = 0; k < w; ++k) fmt_g6(b[k], v[k]);
+                fmt_ratio6(b[3], v[0], wc_ ? (v[0] + v[1]) + v[2] : v[1]);
+                std::fprintf(o_.f, "%s\t%lld\t%s\t%s\t%s\t%s\t%s\t", chrom.c_str(), (long long)pos, id.c_str(), names_[j].c_str(), names_[i].c_str(), b[0], b[1]);
+                if (wc_) std::fprintf(o_.f, "%s\t", b[2]);
+                std::fprintf(o_.f, "%s\n", b[3]);
+            }
+    }
+
+private:
+    OutFile o_;
+    bool wc_;
+    std::vector<std::string> names_;
+};
+
 }  // namespace gpca_host
 
 #endif

@@ -71,6 +71,12 @@ struct Args {
     double assoc_set_max_maf = 0.01;  // --gpca-assoc-set-max-maf X
     std::string assoc_set_weights = "beta";   // --gpca-assoc-set-weights beta|flat
     gpca_host::PhenoTable assoc_pheno_table, assoc_covar_table;   // read in main, before any work on the device
+    bool assoc_cc_freq = false;       // --gpca-assoc-cc-freq: P.<trait>.frq.cc beside every logistic scan
+    std::string within;               // --gpca-within FILE: the sample groups of --gpca-freq-strat and --gpca-fst
+    bool freq_strat = false;          // --gpca-freq-strat: P.frq.strat
+    bool have_fst = false, fst_variants = false;   // --gpca-fst hudson|wc: P.fst.summary; --gpca-fst-variants: P.fst.var
+    std::string fst;
+    gpca_host::WithinTable within_table;   // read in main, before any work on the device
 };
 
 [[noreturn]] void usage_error(const std::string& msg) {
@@ -195,6 +201,17 @@ void print_help() {
         "      --gpca-assoc-set-max-maf <X>     --gpca-assoc-set-list: a listed variant enters its set when its minor-allele frequency\n"
         "                                       over the included observed calls is at most X, 0 < X <= 0.5 [default: 0.01]\n"
         "      --gpca-assoc-set-weights <KIND>  --gpca-assoc-set-list: beta = Beta(maf; 1, 25) weights, flat = 1 [default: beta]\n"
+        "      --gpca-assoc-cc-freq             --gpca-assoc-logistic: the genotype counts and A1 frequencies of every SNP among the\n"
+        "                                       controls and the cases of every case / control trait, over the scan's include set ->\n"
+        "                                       <out>.<trait>.frq.cc (the .frq.strat format with the groups CTRL and CASE)\n"
+        "      --gpca-within <FILE>             --eigensnp: the sample groups of --gpca-freq-strat and --gpca-fst, a table `FID IID GROUP`\n"
+        "                                       with that header; NA = no group; at most 64 groups\n"
+        "      --gpca-freq-strat                --gpca-within: the genotype counts, A1 frequency and HWE p-value of every SNP that passes\n"
+        "                                       the SNP QC inside every group -> <out>.frq.strat\n"
+        "      --gpca-fst <METHOD>              --gpca-within: Fst between every pair of groups over the SNPs that pass the SNP QC, hudson\n"
+        "                                       (Bhatia et al. 2013) or wc (Weir and Cockerham 1984; with more than two groups also\n"
+        "                                       jointly) -> <out>.fst.summary\n"
+        "      --gpca-fst-variants              --gpca-fst: also the per-SNP terms -> <out>.fst.var\n"
         "      --gpca-assoc-pcs <P>             --gpca-assoc-pheno: the first P columns of the scores this run writes are covariates\n"
         "                                       (0 <= P <= --eigensnp-k-global) [default: every column]\n"
         "      --gpca-assoc-covar <FILE>        --gpca-assoc-pheno: further covariates, a table in the format of the phenotype file\n"
@@ -283,6 +300,11 @@ Args parse(int argc, char** argv) {
         else if (f == "--gpca-assoc-set-list") a.assoc_set_list = val();
         else if (f == "--gpca-assoc-set-max-maf") { a.assoc_set_max_maf = to_f64(f, val()); a.have_assoc_set_max_maf = true; }
         else if (f == "--gpca-assoc-set-weights") { a.assoc_set_weights = val(); a.have_assoc_set_weights = true; }
+        else if (f == "--gpca-assoc-cc-freq") a.assoc_cc_freq = true;
+        else if (f == "--gpca-within") a.within = val();
+        else if (f == "--gpca-freq-strat") a.freq_strat = true;
+        else if (f == "--gpca-fst") { a.fst = val(); a.have_fst = true; }
+        else if (f == "--gpca-fst-variants") a.fst_variants = true;
         else if (f == "--gpca-assoc-pcs") { a.assoc_pcs = to_i64(f, val()); a.have_assoc_pcs = true; }
         else if (f == "--gpca-assoc-vif") { a.assoc_vif = to_f64(f, val()); a.have_assoc_vif = true; }
         else if (f == "--gpca-indep-pairwise") {
@@ -405,6 +427,91 @@ bool load_bed(gpca::Engine& eng, const Args& a, const gpca_host::PlinkFileset& f
 const char* const kPcrelateNeedsResident =
     "error: --gpca-make-pcrelate needs the genotype matrix resident on the device: the f32 sums are not associative across the panels of a "
     "matrix walked out of core\n";
+
+const char* const kStratNeedsResident =
+    "error: --gpca-within needs the genotype matrix resident on the device: the counts of a matrix walked out of core are not implemented\n";
+
+// --gpca-freq-strat / --gpca-fst: the genotype counts of every SNP that passes the SNP QC inside every group of --gpca-within
+// (gpca_group_counts), in row bands, into P.frq.strat, and Fst from them (gpca_fst_hudson / gpca_fst_wc) into P.fst.summary and
+// P.fst.var.  Resets the keep mask to the QC mask (mu, sigma unchanged), which ends the fit's validity; every kept sample with a group
+// counts, the KING in-set or not (cli.py:_strat).
+int run_strat(gpca::Engine& eng, const Args& a, const gpca_host::PlinkFileset& fs, const std::vector<std::string>& fids,
+              const std::vector<std::string>& sample_ids, const gpca::SnpStats& st) {
+    const std::vector<int32_t> labels = gpca_host::align_within(a.within_table, fids, sample_ids);
+    const std::vector<std::string>& names = a.within_table.names;
+    const int32_t P = (int32_t)names.size();
+    eng.set_standardization(st.mu, st.sigma, st.keep);                                // every SNP that passes the SNP QC
+    std::vector<int64_t> rows;
+    for (size_t i = 0; i < st.keep.size(); ++i) if (st.keep[i]) rows.push_back((int64_t)i);
+    gpca_host::ensure_parent(a.output_prefix);
+    const size_t pairs = (size_t)P * (size_t)(P - 1) / 2;
+    const bool hudson = a.have_fst && a.fst == "hudson", wc = a.have_fst && a.fst == "wc";
+    std::vector<double> hud(pairs * 3, 0.0), wcp(pairs * 3, 0.0);
+    double wcj[3] = {0.0, 0.0, 0.0};
+    std::unique_ptr<gpca_host::FrqStratWriter> wf;
+    std::unique_ptr<gpca_host::FstVarWriter> wv;
+    if (a.freq_strat) wf.reset(new gpca_host::FrqStratWriter(a.output_prefix + ".frq.strat", names, gpca_hwe_chi_squared_p_value));
+    if (a.have_fst && a.fst_variants) wv.reset(new gpca_host::FstVarWriter(a.output_prefix, wc, names));
+    try {
+        for (const auto& b : gpca_host::group_count_bands((int64_t)rows.size(), P)) {
+            std::vector<uint32_t> c;
+            eng.group_counts(labels, P, b.first, b.second, c);
+            const size_t nr = (size_t)(b.second - b.first);
+            if (wf)
+                for (size_t i = 0; i < nr; ++i) {
+                    const size_t o = (size_t)rows[(size_t)b.first + i];
+                    wf->add_row(fs.chromosomes[o], fs.positions[o], fs.variant_ids[o], fs.allele1[o], &c[i * (size_t)P * 3]);
+                }
+            std::vector<double> vals;                                                   // [rows][pairs][2 or 3]
+            if (hudson) {
+                std::vector<double> num, den;
+                gpca::Engine::fst_hudson(c, P, hud, wv ? &num : nullptr, wv ? &den : nullptr);
+                if (wv) {
+                    vals.resize(nr * pairs * 2);
+                    for (size_t k = 0; k < nr * pairs; ++k) { vals[2 * k] = num[k]; vals[2 * k + 1] = den[k]; }
+                }
+            } else if (wc) {
+                if (wv) vals.resize(nr * pairs * 3);
+                size_t q = 0;
+                for (int32_t i = 1; i < P; ++i)
+                    for (int32_t j = 0; j < i; ++j, ++q) {                              // r = 2 on each pair
+                        std::vector<uint8_t> use((size_t)P, 0);
+                        use[(size_t)j] = use[(size_t)i] = 1;
+                        std::vector<double> abc;
+                        gpca::Engine::fst_wc(c, P, use, &wcp[3 * q], wv ? &abc : nullptr);
+                        if (wv) for (size_t r = 0; r < nr; ++r) for (int k = 0; k < 3; ++k) vals[(r * pairs + q) * 3 + (size_t)k] = abc[3 * r + (size_t)k];
+                    }
+                if (P > 2) gpca::Engine::fst_wc(c, P, {}, wcj, nullptr);
+            }
+            if (wv)
+                for (size_t i = 0; i < nr; ++i) {
+                    const size_t o = (size_t)rows[(size_t)b.first + i];
+                    wv->add_row(fs.chromosomes[o], fs.positions[o], fs.variant_ids[o], &vals[i * pairs * (wc ? 3 : 2)]);
+                }
+        }
+    } catch (const gpca::Error& e) {
+        if (e.status() != GPCA_ERR_STATE) throw;
+        std::fputs(kStratNeedsResident, stderr);
+        return 1;
+    }
+    int64_t n_lab = 0;
+    for (int32_t g : labels) n_lab += g >= 0;
+    char buf[512];
+    if (a.freq_strat) {
+        std::snprintf(buf, sizeof buf, "genotype counts of %zu SNPs in %d groups (%lld of %zu samples), written to %s.frq.strat", rows.size(), (int)P,
+                      (long long)n_lab, sample_ids.size(), a.output_prefix.c_str());
+        logmsg(buf);
+    }
+    if (a.have_fst) {
+        std::vector<double> sums = hudson ? hud : wcp;
+        if (wc && P > 2) sums.insert(sums.end(), wcj, wcj + 3);
+        gpca_host::write_fst_summary(a.output_prefix, wc, names, sums);
+        std::snprintf(buf, sizeof buf, "%s Fst of %zu pairs of groups over %zu SNPs, written to %s.fst.summary", a.fst.c_str(), pairs, rows.size(),
+                      a.output_prefix.c_str());
+        logmsg(buf);
+    }
+    return 0;
+}
 
 const char* const kAssocNeedsResident =
     "error: --gpca-assoc-pheno needs the genotype matrix resident on the device: the scan of a matrix walked out of core is not implemented\n";
@@ -549,6 +656,27 @@ int run_assoc(gpca::Engine& eng, const Args& a, const gpca_host::PlinkFileset& f
     gpca_host::ensure_parent(a.output_prefix);
     std::vector<double> a1_all(rows.size(), std::nan(""));                            // (of every kept row, for the sets' MAF rule)
     try {
+        if (a.assoc_cc_freq && Tb) {
+            // --gpca-assoc-cc-freq: the counts among the controls and the cases of every case / control trait, over the scan's include
+            // set (label -1 outside it), into P.<trait>.frq.cc (cli.py:_cc_freq)
+            for (int32_t t = 0; t < Tb; ++t) {
+                std::vector<int32_t> labels((size_t)n);
+                for (int64_t s = 0; s < n; ++s) labels[(size_t)s] = include[(size_t)s] ? (int32_t)Yb[(size_t)s * Tb + t] : -1;
+                gpca_host::FrqStratWriter w(a.output_prefix + "." + bnames[(size_t)t] + ".frq.cc", {"CTRL", "CASE"}, gpca_hwe_chi_squared_p_value);
+                for (const auto& b : gpca_host::group_count_bands((int64_t)rows.size(), 2)) {
+                    std::vector<uint32_t> c;
+                    eng.group_counts(labels, 2, b.first, b.second, c);
+                    for (int64_t r = b.first; r < b.second; ++r) {
+                        const size_t o = (size_t)rows[(size_t)r];
+                        w.add_row(fs.chromosomes[o], fs.positions[o], fs.variant_ids[o], fs.allele1[o], &c[(size_t)(r - b.first) * 6]);
+                    }
+                }
+            }
+            char cb[512];
+            std::snprintf(cb, sizeof cb, "case / control genotype counts of %zu SNPs for %d traits, written to %s.<trait>.frq.cc", rows.size(), (int)Tb,
+                          a.output_prefix.c_str());
+            logmsg(cb);
+        }
         if (Tq) {
             std::vector<std::unique_ptr<gpca_host::AssocWriter>> w;
             for (int32_t t = 0; t < Tq; ++t) w.emplace_back(new gpca_host::AssocWriter(a.output_prefix, names[(size_t)t]));
@@ -637,6 +765,7 @@ int run_eigensnp_workflow(Args a) {
     const bool streamed = load_bed(eng, a, fs, use_kept ? &kept : nullptr);
     if (streamed && a.make_pcrelate) { std::fputs(kPcrelateNeedsResident, stderr); return 1; }
     if (streamed && !a.assoc_pheno.empty()) { std::fputs(kAssocNeedsResident, stderr); return 1; }
+    if (streamed && !a.within.empty()) { std::fputs(kStratNeedsResident, stderr); return 1; }
     const gpca::SnpStats st = eng.snp_stats(gpca::QcConfig{a.min_call_rate, a.min_maf, a.max_hwe_p});
     const auto blocks = gpca_host::parse_ld_block_file(a.ld_block_file);
     std::vector<uint8_t> keep;
@@ -852,6 +981,12 @@ int run_eigensnp_workflow(Args a) {
                       rows.size(), (int)P, a.output_prefix.c_str());
         logmsg(buf);
     }
+    if (!a.within.empty()) {
+        std::vector<std::string> fids = fs.family_ids;
+        if (use_kept) { fids.clear(); for (int64_t c : kept.cols) fids.push_back(fs.family_ids[(size_t)c]); }
+        const int rc = run_strat(eng, a, fs, fids, sample_ids, st);
+        if (rc) return rc;
+    }
     if (!a.assoc_pheno.empty()) {
         std::vector<std::string> fids = fs.family_ids;
         if (use_kept) { fids.clear(); for (int64_t c : kept.cols) fids.push_back(fs.family_ids[(size_t)c]); }
@@ -965,6 +1100,24 @@ int main(int argc, char** argv) {
         if (a.have_assoc_set_weights && a.assoc_set_weights != "beta" && a.assoc_set_weights != "flat") {
             std::fprintf(stderr, "error: --gpca-assoc-set-weights must be beta or flat\n");
             return 2;
+        }
+        if (a.assoc_cc_freq && !a.assoc_logistic) { std::fprintf(stderr, "error: --gpca-assoc-cc-freq needs --gpca-assoc-logistic\n"); return 2; }
+        if (a.within.empty() && (a.freq_strat || a.have_fst)) { std::fprintf(stderr, "error: --gpca-freq-strat and --gpca-fst need --gpca-within\n"); return 2; }
+        if (a.fst_variants && !a.have_fst) { std::fprintf(stderr, "error: --gpca-fst-variants needs --gpca-fst\n"); return 2; }
+        if (a.have_fst && a.fst != "hudson" && a.fst != "wc") { std::fprintf(stderr, "error: --gpca-fst must be hudson or wc\n"); return 2; }
+        if (!a.within.empty()) {
+            if (!a.eigensnp) { std::fprintf(stderr, "error: --gpca-within needs the --eigensnp workflow\n"); return 2; }
+            if (!a.freq_strat && !a.have_fst) { std::fprintf(stderr, "error: --gpca-within needs --gpca-freq-strat or --gpca-fst\n"); return 2; }
+            if (a.stream == "on") { std::fputs(kStratNeedsResident, stderr); return 2; }
+            try { a.within_table = gpca_host::read_within(a.within); }
+            catch (const std::runtime_error& e) { std::fprintf(stderr, "error: --gpca-within: %s\n", e.what()); return 2; }
+            const size_t ng = a.within_table.names.size();
+            if ((int64_t)ng > gpca_host::kGroupsMax) {
+                std::fprintf(stderr, "error: --gpca-within: %zu groups are more than %lld\n", ng, (long long)gpca_host::kGroupsMax);
+                return 2;
+            }
+            if (a.have_fst && ng < 2) { std::fprintf(stderr, "error: --gpca-fst needs at least two groups, --gpca-within names %zu\n", ng); return 2; }
+            if (ng < 1) { std::fprintf(stderr, "error: --gpca-within names no group\n"); return 2; }
         }
         if (!a.assoc_pheno.empty()) {
             if (!a.eigensnp) { std::fprintf(stderr, "error: --gpca-assoc-pheno needs the --eigensnp workflow\n"); return 2; }

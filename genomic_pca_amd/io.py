@@ -958,3 +958,163 @@ def write_assoc_set(prefix: str, trait: str, names: Sequence[str], chromosomes: 
             f.write(f"{head}\t{int(r['m_used'])}\t{_g6(r['burden_beta'])}\t{_g6(r['burden_se'])}\t{_g6(r['burden_z'])}\t{_g6(r['burden_log10p'])}\t"
                     f"{_g6(r['skat_q'])}\t{_g6(lp)}\t{'NA' if lp != lp else 'NYF'[int(r['skat_status'])]}\n")
     return path
+
+
+# ---- genotype counts inside sample groups and Fst (gpca_group_counts, gpca_fst_hudson, gpca_fst_wc): twins in host/formats.hpp ------------
+GROUPS_MAX = 64
+
+
+class WithinTable(NamedTuple):
+    family_ids: List[str]
+    sample_ids: List[str]
+    groups: List[Optional[str]]   # None = in no group (NA)
+    names: List[str]              # the group names in order of first appearance in the file
+
+
+def read_within(path: str) -> WithinTable:
+    """A whitespace-separated table `FID IID GROUP`.  The header `FID IID GROUP` (a leading '#' allowed) is required; `NA` means no
+    group; a repeated (FID, IID) is refused."""
+    fids, iids, groups, names, seen, header = [], [], [], [], set(), False
+    need = f"{path}: the header `FID IID GROUP` is required"
+    with open(path) as f:
+        for ln, line in enumerate(f, 1):
+            p = line.split()
+            if not p:
+                continue
+            if not header:
+                if len(p) != 3 or p[0].lstrip("#").upper() != "FID" or p[1].upper() != "IID" or p[2].upper() != "GROUP":
+                    raise ValueError(need)
+                header = True
+                continue
+            if len(p) != 3:
+                raise ValueError(f"{path}:{ln}: {len(p)} fields, the header has 3")
+            if (p[0], p[1]) in seen:
+                raise ValueError(f"{path}:{ln}: sample {p[0]} {p[1]} appears twice")
+            seen.add((p[0], p[1]))
+            g = None if p[2] == "NA" else p[2]
+            if g is not None and g not in names:
+                names.append(g)
+            fids.append(p[0]); iids.append(p[1]); groups.append(g)
+    if not header:
+        raise ValueError(need)
+    return WithinTable(fids, iids, groups, names)
+
+
+def align_within(table: WithinTable, family_ids: Sequence[str], sample_ids: Sequence[str]) -> Tuple[np.ndarray, List[str]]:
+    """(labels int32 [len(sample_ids)] in .fam order, the group names): label p = the sample is in group names[p], -1 = it is absent from
+    the table or has no group.  The names are the table's, in order of first appearance in the file (a group none of whose samples is
+    in the .fam stays, empty)."""
+    index = {g: p for p, g in enumerate(table.names)}
+    at = {(f, i): g for f, i, g in zip(table.family_ids, table.sample_ids, table.groups)}
+    out = np.full(len(sample_ids), -1, np.int32)
+    for n, key in enumerate(zip(family_ids, sample_ids)):
+        g = at.get(key)
+        if g is not None:
+            out[n] = index[g]
+    return out, list(table.names)
+
+
+def group_count_bands(K: int, P: int, max_values: int = 1 << 26):
+    """[row0, row1) bands of the K kept rows whose counts (rows x P x 3) hold at most max_values entries (at least one row): the bands
+    gpca_group_counts is asked for, one at a time."""
+    step = max(max_values // (3 * max(P, 1)), 1)
+    return [(r0, min(r0 + step, K)) for r0 in range(0, K, step)]
+
+
+def _open_out(path: str, append: bool):
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    return open(path, "a" if append else "w")
+
+
+def write_frq_strat(path: str, chromosomes: Sequence[str], positions: Sequence[int], variant_ids: Sequence[str], allele1: Sequence[str],
+                    names: Sequence[str], counts, append: bool = False) -> str:
+    """The stratified frequency file `path` (P.frq.strat, P.<trait>.frq.cc): one tab-separated line per SNP and group, SNP-major,
+    `#CHROM POS ID A1 GROUP OBS_CT A1_CT A1_FREQ HET_CT HOM_A1_CT HWE_P` from counts [SNPs][groups][3] = n_obs, n_het, n_hom2
+    (gpca_group_counts).  Counts as integers, A1_CT = n_het + 2 n_hom2, A1_FREQ = A1_CT / (2 OBS_CT) and HWE_P =
+    gpca_hwe_chi_squared_p_value(n_obs - n_het - n_hom2, n_het, n_hom2) as %.6g; both NA where OBS_CT = 0.  append=True adds the rows
+    of a further band to the file (no header)."""
+    from . import _lib
+    cv = np.asarray(counts)
+    n, P = len(variant_ids), len(names)
+    if cv.shape != (n, P, 3):
+        raise ValueError("write_frq_strat: counts must be [SNPs][groups][3]")
+    for a in (chromosomes, positions, allele1):
+        if len(a) != n:
+            raise ValueError("write_frq_strat: one entry per SNP in every column")
+    hwe = _lib.load().gpca_hwe_chi_squared_p_value
+    with _open_out(path, append) as f:
+        if not append:
+            f.write("#CHROM\tPOS\tID\tA1\tGROUP\tOBS_CT\tA1_CT\tA1_FREQ\tHET_CT\tHOM_A1_CT\tHWE_P\n")
+        for i in range(n):
+            head = f"{chromosomes[i]}\t{int(positions[i])}\t{variant_ids[i]}\t{allele1[i]}\t"
+            for p in range(P):
+                obs, het, hom = int(cv[i, p, 0]), int(cv[i, p, 1]), int(cv[i, p, 2])
+                a1 = het + 2 * hom
+                if obs == 0:
+                    fr, hw = "NA", "NA"
+                else:
+                    fr, hw = _g6(a1 / (2.0 * obs)), _g6(hwe(obs - het - hom, het, hom))
+                f.write(f"{head}{names[p]}\t{obs}\t{a1}\t{fr}\t{het}\t{hom}\t{hw}\n")
+    return path
+
+
+def _ratio6(num: float, den: float) -> str:
+    num, den = float(num), float(den)
+    return "NA" if num != num or den != den or den == 0.0 else _g6(num / den)
+
+
+def fst_pairs(P: int):
+    """the pairs (j, i), j < i, of P groups in the order of gpca_fst_hudson's pair index i (i - 1) / 2 + j"""
+    return [(j, i) for i in range(1, P) for j in range(i)]
+
+
+def write_fst_summary(prefix: str, method: str, names: Sequence[str], sums) -> str:
+    """P.fst.summary: `#GROUP1 GROUP2 N_VAR HUDSON_FST` (method "hudson") or `... WC_FST` ("wc"), tab-separated, one line per pair of
+    groups with GROUP1 the earlier one, in the order of fst_pairs.  sums [pairs][3] = the running sum of the numerators (a), of the
+    denominators (a + b + c) and the rows used; for "wc" with more than two groups a further last row of sums covers all groups jointly
+    and is written as `* * N_VAR FST`.  FST = %.6g of the ratio of sums, NA where no row was used or the denominator is 0."""
+    if method not in ("hudson", "wc"):
+        raise ValueError("write_fst_summary: method is hudson or wc")
+    P = len(names)
+    pairs = fst_pairs(P)
+    sv = np.asarray(sums, np.float64)
+    joint = method == "wc" and P > 2
+    if sv.shape != (len(pairs) + int(joint), 3):
+        raise ValueError("write_fst_summary: sums must be [pairs][3] (one more row for the joint wc value of more than two groups)")
+    path = f"{prefix}.fst.summary"
+    with _open_out(path, False) as f:
+        f.write("#GROUP1\tGROUP2\tN_VAR\t" + ("HUDSON_FST" if method == "hudson" else "WC_FST") + "\n")
+        for q, (j, i) in enumerate(pairs):
+            f.write(f"{names[j]}\t{names[i]}\t{int(sv[q, 2])}\t{'NA' if sv[q, 2] == 0 else _ratio6(sv[q, 0], sv[q, 1])}\n")
+        if joint:
+            f.write(f"*\t*\t{int(sv[-1, 2])}\t{'NA' if sv[-1, 2] == 0 else _ratio6(sv[-1, 0], sv[-1, 1])}\n")
+    return path
+
+
+def write_fst_var(prefix: str, method: str, chromosomes: Sequence[str], positions: Sequence[int], variant_ids: Sequence[str],
+                  names: Sequence[str], values, append: bool = False) -> str:
+    """P.fst.var: one tab-separated line per SNP and pair of groups (SNP-major, the pairs in the order of fst_pairs, GROUP1 the earlier
+    group): `#CHROM POS ID GROUP1 GROUP2 NUM DEN FST` from values [SNPs][pairs][2] = num, den ("hudson"), or `#CHROM POS ID GROUP1 GROUP2
+    A B C FST` from values [SNPs][pairs][3] = a, b, c ("wc", r = 2 on each pair).  Numbers as %.6g, NaN as NA; FST = NUM / DEN or
+    A / ((A + B) + C), NA where that is NaN or the denominator is 0.  append=True adds the rows of a further band (no header)."""
+    if method not in ("hudson", "wc"):
+        raise ValueError("write_fst_var: method is hudson or wc")
+    w = 2 if method == "hudson" else 3
+    pairs = fst_pairs(len(names))
+    n = len(variant_ids)
+    vv = np.asarray(values, np.float64)
+    if vv.shape != (n, len(pairs), w) or len(chromosomes) != n or len(positions) != n:
+        raise ValueError("write_fst_var: values must be [SNPs][pairs][%d] with one entry per SNP in every column" % w)
+    path = f"{prefix}.fst.var"
+    with _open_out(path, append) as f:
+        if not append:
+            f.write("#CHROM\tPOS\tID\tGROUP1\tGROUP2\t" + ("NUM\tDEN" if method == "hudson" else "A\tB\tC") + "\tFST\n")
+        for i in range(n):
+            head = f"{chromosomes[i]}\t{int(positions[i])}\t{variant_ids[i]}\t"
+            for q, (j, k) in enumerate(pairs):
+                v = vv[i, q]
+                den = v[1] if method == "hudson" else (v[0] + v[1]) + v[2]
+                f.write(head + f"{names[j]}\t{names[k]}\t" + "\t".join(_g6(x) for x in v) + f"\t{_ratio6(v[0], den)}\n")
+    return path

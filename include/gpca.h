@@ -462,7 +462,7 @@ GPCA_API double gpca_student_t_log10p(double t, double df);
  * behind gpca_logistic_null; a failure returns its status and names the trait in gpca_last_error.
  * A band is bit-identical to the same rows of the full call; int8 and 2-bit residency give the same bits, and so does a
  * GPCA_PREC_F32_MFMA handle; the sample mask is ignored and no fitted result is touched.  Out of scope (a14 has the saddle-point correction, a15 the
- * approximate Firth correction): a Wald / IRLS fit per SNP, per-variant dropping of samples, case / control frequency columns, mixed
+ * approximate Firth correction): a Wald / IRLS fit per SNP, per-variant dropping of samples, case / control frequency columns (a17 counts them), mixed
  * models, and streamed and row-sharded handles: GPCA_ERR_STATE.
  * Errors: GPCA_ERR_STATE (no standardisation, K = 0, a streamed handle, a row-sharded handle), GPCA_ERR_BAD_ARG (T, Pc or the row range
  * out of bounds, all outputs NULL, max_vif < 1 or not finite, and those of step 1), GPCA_ERR_NOT_CONVERGED (step 1),
@@ -650,6 +650,55 @@ GPCA_API int gpca_assoc_logistic_set(gpca_handle* h, const double* Y /* [N][T], 
                                      double* rowinfo /* [listed][5] or NULL */, double* phi /* per set [T][m (m + 1) / 2] */);
 GPCA_API int gpca_set_test(const double* u /* [m] */, const double* phi /* [m (m + 1) / 2] */, const double* weight /* [m] or NULL */,
                            int32_t m, double* out /* [10] */);
+
+/* ---- a17: genotype counts inside sample groups, and Fst from them (plink --freq --within / --fst, smartpca's Fst table): what a SNP
+ * looks like inside each of P groups of samples -- populations, or cases and controls.
+ * gpca_group_counts: group [N] labels every sample with its group 0 .. P - 1 or with -1 (any negative label: in no group); a group
+ *     without a sample is allowed.  For the kept rows [row0, row1) in PCA-SNP order, counts [rows][P][3] (uint32) = n_obs, n_het, n_hom2:
+ *     the samples of the group with an observed call on the row, those with g = 1 and those with g = 2 (g counts copies of A1).
+ *  Device: 0/1 indicator bytes of the calls ([g = 1], [g = 2], [missing]) times the 0/1 one-hot matrix of the labels on
+ *     v_mfma_i32_32x32x32_i8, in i32: exact integers, n_obs = the group's size - its missing calls; the missing plane runs only in
+ *     blocks of 32 samples where a wave ballot over 32 rows finds a missing call (a product of 0 more or less changes no sum); 33 .. 64
+ *     groups read the genotypes once; no split of the sample axis, no atomics, every count written once.  A sample at or beyond N and
+ *     a sample with label -1 have an all-zero one-hot column.
+ *     A band is bit-identical to the same rows of the full call; int8 and 2-bit residency and a GPCA_PREC_F32_MFMA handle give the
+ *     same counts; the sample mask is ignored and no fitted result is touched.
+ *  Errors: GPCA_ERR_STATE (no standardisation, K = 0, a streamed handle, a row-sharded handle), GPCA_ERR_BAD_ARG (a NULL group or
+ *     counts, P outside 1 .. GPCA_GROUPS_MAX, a label >= P, a row range out of bounds), GPCA_ERR_INVALID_GENOTYPE (a row the call
+ *     reads holds a value outside {0, 1, 2, missing} on a sample below N, in a group or not; the message names the row, as in a12),
+ *     GPCA_ERR_OOM (checked before any allocation).
+ * The two Fst rules are host only, take no handle, work in f64 with no fused multiply-add and read counts [rows][P][3].  Per group
+ * i of a row: n_i = 2 n_obs (allele count, formed in f64), p_i = (n_het + 2 n_hom2) / n_i.  Both add row by row, rows ascending, to the
+ * caller's running sums (zero them before the first band): calls over consecutive bands give the bits of one call over all rows.
+ *  gpca_fst_hudson (Hudson's estimator as in Bhatia et al. 2013; plink 2's default): per pair (i, j), j < i, at pair index
+ *     i (i - 1) / 2 + j of P (P - 1) / 2, per row:
+ *         d   = p_i - p_j
+ *         num = (d d - (p_i (1 - p_i)) / (n_i - 1)) - (p_j (1 - p_j)) / (n_j - 1)
+ *         den = p_i (1 - p_j) + p_j (1 - p_i)
+ *     A row contributes to the pair iff both groups have n_obs >= 1; otherwise num and den are NaN and nothing is added.
+ *     sums [pairs][3] += num, den, 1 (pairs ascending inside a row); the genome-wide value is sums[.][0] / sums[.][1].  num and den
+ *     [rows][pairs] may each be NULL.  GPCA_ERR_BAD_ARG: NULL counts or sums, rows < 0, P outside 2 .. GPCA_GROUPS_MAX.
+ *  gpca_fst_wc (Weir and Cockerham 1984) over the groups with use[p] != 0 (NULL: all), r of them, ascending; n_i = n_obs here,
+ *     h_i = n_het / n_i, p_i as above; every sum from 0, groups ascending:
+ *         n_t = sum n_i,  q = sum n_i n_i
+ *         nbar = n_t / r,  n_c = (n_t - q / n_t) / (r - 1),  pbar = (sum n_i p_i) / n_t,  hbar = (sum n_i h_i) / n_t
+ *         s2 = (sum n_i ((p_i - pbar) (p_i - pbar))) / ((r - 1) nbar)
+ *         core = pbar (1 - pbar) - ((r - 1) / r) s2
+ *         a = (nbar / n_c) (s2 - (core - hbar / 4) / (nbar - 1))
+ *         b = (nbar / (nbar - 1)) (core - ((2 nbar - 1) / (4 nbar)) hbar)
+ *         c = hbar / 2
+ *     A row contributes iff every used group has n_obs >= 1 and n_t > r; otherwise a, b, c are NaN and nothing is added.
+ *     sums [3] += a, (a + b) + c, 1; the genome-wide value is sums[0] / sums[1].  abc [rows][3] may be NULL.  GPCA_ERR_BAD_ARG: NULL
+ *     counts or sums, rows < 0, P outside 1 .. GPCA_GROUPS_MAX, fewer than two groups used.
+ *  Not there: per-variant dropping of samples, haploid and sex chromosomes, weighted or hierarchical F-statistics, jackknife standard
+ *     errors, more than GPCA_GROUPS_MAX groups, streamed and row-sharded handles. */
+#define GPCA_GROUPS_MAX 64
+GPCA_API int gpca_group_counts(gpca_handle* h, const int32_t* group /* [N] */, int32_t P, int64_t row0, int64_t row1,
+                               uint32_t* counts /* [rows][P][3] */);
+GPCA_API int gpca_fst_hudson(const uint32_t* counts, int64_t rows, int32_t P, double* num /* [rows][pairs] or NULL */,
+                             double* den /* same or NULL */, double* sums /* [pairs][3]: sum num, sum den, rows used; ADDED TO */);
+GPCA_API int gpca_fst_wc(const uint32_t* counts, int64_t rows, int32_t P, const uint8_t* use /* [P] or NULL */,
+                         double* abc /* [rows][3] or NULL */, double* sums /* [3]: sum a, sum (a + b + c), rows used; ADDED TO */);
 
 /* ---- f3: the stages of EigenSNPCoreAlgorithm::compute_pca (main.rs:311-327, 359-366) ------------------------------------------
  * The algorithm lives in the un-vendored efficient_pca crate (Cargo.toml:30, branch "main", no pinned revision): what follows is

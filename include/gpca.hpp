@@ -331,6 +331,42 @@ public:
                            : gpca_set_test(u.data(), phi_lower.data(), weight.empty() ? nullptr : weight.data(), (int32_t)m, out);
         if (rc != GPCA_OK) throw Error(rc, std::string("gpca_set_test: ") + gpca_status_string(rc));
     }
+    // genotype counts inside sample groups (gpca_group_counts; gpca.h section a17): group [N] = 0 .. P - 1 or -1; counts [rows][P][3] =
+    // n_obs, n_het, n_hom2 of the kept rows [row0, row1)
+    void group_counts(const std::vector<int32_t>& group, int32_t P, int64_t row0, int64_t row1, std::vector<uint32_t>& counts) const {
+        const size_t rows = row1 > row0 ? (size_t)(row1 - row0) : 0, p = P > 0 && P <= GPCA_GROUPS_MAX ? (size_t)P : 1;
+        counts.assign(std::max<size_t>(rows * p * 3, 1), 0u);
+        check(gpca_group_counts(h_, group.data(), P, row0, row1, counts.data()));
+        counts.resize(rows * p * 3);
+    }
+    // Hudson's Fst of every pair of groups (gpca_fst_hudson; host only): sums [P (P - 1) / 2][3] is ADDED TO (zero it before the first
+    // band); num / den [rows][pairs] when asked for
+    static void fst_hudson(const std::vector<uint32_t>& counts, int32_t P, std::vector<double>& sums, std::vector<double>* num = nullptr,
+                           std::vector<double>* den = nullptr) {
+        const size_t per = P > 0 ? (size_t)P * 3 : 1, rows = counts.size() / per, pairs = P > 1 ? (size_t)P * (size_t)(P - 1) / 2 : 0;
+        int rc = counts.size() != rows * per || sums.size() != pairs * 3 ? GPCA_ERR_BAD_ARG : GPCA_OK;
+        if (rc == GPCA_OK) {
+            if (num) num->assign(std::max<size_t>(rows * pairs, 1), 0.0);
+            if (den) den->assign(std::max<size_t>(rows * pairs, 1), 0.0);
+            rc = gpca_fst_hudson(counts.data(), (int64_t)rows, P, num ? num->data() : nullptr, den ? den->data() : nullptr, sums.data());
+            if (num) num->resize(rows * pairs);
+            if (den) den->resize(rows * pairs);
+        }
+        if (rc != GPCA_OK) throw Error(rc, std::string("gpca_fst_hudson: ") + gpca_status_string(rc));
+    }
+    // Weir and Cockerham's Fst over the groups with use[p] != 0 (empty: all) (gpca_fst_wc; host only): sums [3] is ADDED TO; abc [rows][3]
+    // when asked for
+    static void fst_wc(const std::vector<uint32_t>& counts, int32_t P, const std::vector<uint8_t>& use, double* sums,
+                       std::vector<double>* abc = nullptr) {
+        const size_t per = P > 0 ? (size_t)P * 3 : 1, rows = counts.size() / per;
+        int rc = counts.size() != rows * per || (!use.empty() && use.size() != (size_t)P) ? GPCA_ERR_BAD_ARG : GPCA_OK;
+        if (rc == GPCA_OK) {
+            if (abc) abc->assign(std::max<size_t>(rows * 3, 1), 0.0);
+            rc = gpca_fst_wc(counts.data(), (int64_t)rows, P, use.empty() ? nullptr : use.data(), abc ? abc->data() : nullptr, sums);
+            if (abc) abc->resize(rows * 3);
+        }
+        if (rc != GPCA_OK) throw Error(rc, std::string("gpca_fst_wc: ") + gpca_status_string(rc));
+    }
     // the null logistic model of one trait (gpca_logistic_null; host only): y [N] in {0, 1}, C [N][Pc]; alpha [Pc + 1], mu [N] (0 outside
     // the included samples); returns the number of Newton steps; throws Error with the status (no message: there is no handle)
     static int logistic_null(const std::vector<double>& y, const std::vector<double>& C, int32_t Pc, const std::vector<uint8_t>* include,
