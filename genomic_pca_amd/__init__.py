@@ -12,5 +12,7 @@ firth_log10p = GpcaEngine.firth_log10p
 set_test = GpcaEngine.set_test
 fst_hudson = GpcaEngine.fst_hudson
 fst_wc = GpcaEngine.fst_wc
+het_weights = GpcaEngine.het_weights
+sample_het = GpcaEngine.sample_het
 
 __version__ = "0.2.2"

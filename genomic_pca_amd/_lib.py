@@ -156,6 +156,9 @@ PROTOTYPES = {
     "gpca_group_counts": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p]),
     "gpca_fst_hudson": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gpca_fst_wc": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpca_sample_counts": (C.c_int, [_H, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpca_het_weights": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
+    "gpca_sample_het": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "gpca_comm_get_unique_id": (C.c_int, [C.c_void_p]),
     "gpca_comm_init": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, C.c_int64]),
     "gpca_set_allreduce_hook": (C.c_int, [_H, ALLREDUCE_FN, C.c_void_p, C.c_int32, C.c_int32, C.c_int64]),

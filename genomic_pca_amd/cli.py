@@ -171,6 +171,19 @@ def build_parser() -> argparse.ArgumentParser:
                    help="--gpca-within: Fst between every pair of groups over the SNPs that pass the SNP QC, hudson (Bhatia et al. "
                         "2013) or wc (Weir and Cockerham 1984; with more than two groups also jointly) -> <out>.fst.summary")
     p.add_argument("--gpca-fst-variants", action="store_true", help="--gpca-fst: also the per-SNP terms -> <out>.fst.var")
+    p.add_argument("--gpca-sample-missing", action="store_true",
+                   help="--eigensnp: the missing calls of every sample over the SNPs that pass the SNP QC -> <out>.smiss (#FID IID "
+                        "MISSING_CT OBS_CT F_MISS)")
+    p.add_argument("--gpca-het", action="store_true",
+                   help="--eigensnp: the observed and expected homozygous calls and the inbreeding coefficient F of every sample over "
+                        "the SNPs that pass the SNP QC (plink --het, allele frequencies from all samples) -> <out>.het (#FID IID O_HOM "
+                        "E_HOM OBS_CT F)")
+    p.add_argument("--gpca-mind", type=float, default=None, metavar="X",
+                   help="--eigensnp: drop a sample from the fit, PC-Relate's training set and the scans when more than X of its calls "
+                        "are missing (0 <= X < 1) -> <out>.sampleqc.in.id / .out.id; every sample is still projected")
+    p.add_argument("--gpca-het-sd", type=float, default=None, metavar="K",
+                   help="--eigensnp: drop a sample whose F lies more than K standard deviations from the mean F of the samples that "
+                        "pass --gpca-mind (K > 0; one round) -> <out>.sampleqc.in.id / .out.id")
     p.add_argument("--gpca-assoc-pcs", type=int, default=None, metavar="P",
                    help="--gpca-assoc-pheno: the first P columns of the scores this run writes are covariates (0 <= P <= "
                         "--eigensnp-k-global) [default: every column]")
@@ -310,7 +323,12 @@ def run_eigensnp_workflow(a) -> int:
         raise SystemExit(ASSOC_NEEDS_RESIDENT)
     if streamed and a.gpca_within is not None:
         raise SystemExit(STRAT_NEEDS_RESIDENT)
+    if streamed and _sample_qc_asked(a):
+        raise SystemExit(SAMPLE_QC_NEEDS_RESIDENT)
     st = eng.snp_stats(QcConfig(a.eigensnp_min_call_rate, a.eigensnp_min_maf, a.eigensnp_max_hwe_p))
+    qc_pass = None
+    if _sample_qc_asked(a) and len(sample_ids) and int(st["keep"].sum()):
+        qc_pass = _sample_qc(eng, a, fs, cols, sample_ids, st)
     blocks = gio.parse_ld_block_file(a.ld_block_file)
     keep, by_tag = gio.map_snps_to_ld_blocks(blocks, fs.chromosomes, fs.positions, st["keep"])
     _log(f"{int(st['keep'].sum())} / {len(st['keep'])} SNPs passed QC; {int(keep.sum())} fall in {len(by_tag)} LD blocks")
@@ -328,7 +346,11 @@ def run_eigensnp_workflow(a) -> int:
         _log(f"GRM of {len(sample_ids)} samples over {int(keep.sum())} SNPs written to {a.output_prefix}.grm.bin")
     inset = None
     if a.gpca_make_king or a.gpca_king_cutoff is not None:
-        inset = _king(eng, a, fs, cols, sample_ids, int(keep.sum()))
+        inset = _king(eng, a, fs, cols, sample_ids, int(keep.sum()), qc_pass)
+    if qc_pass is not None:                                                          # the in-set is KING's and the sample QC's
+        inset = qc_pass.copy() if inset is None else (np.asarray(inset, bool) & qc_pass)
+        if int(inset.sum()) < 2:
+            raise SystemExit("error: --gpca-mind / --gpca-het-sd leave fewer than 2 samples to fit the PCA on")
     acc = MicroarrayGenotypeAccessor(eng)
     rows = acc.original_indices_of_pca_snps()
     row_to_id = {int(r): i for i, r in enumerate(rows)}
@@ -380,10 +402,60 @@ def run_eigensnp_workflow(a) -> int:
     return 0
 
 
-def _king(eng, a, fs, cols, sample_ids, n_snps):
+SAMPLE_QC_NEEDS_RESIDENT = ("error: --gpca-sample-missing, --gpca-het, --gpca-mind and --gpca-het-sd need the genotype matrix resident on "
+                            "the device: the per-sample counts of a matrix walked out of core are not implemented")
+
+
+def _sample_qc_asked(a) -> bool:
+    return bool(a.gpca_sample_missing or a.gpca_het or a.gpca_mind is not None or a.gpca_het_sd is not None)
+
+
+def _sample_qc(eng, a, fs, cols, sample_ids, st):
+    """--gpca-sample-missing / --gpca-het / --gpca-mind / --gpca-het-sd: the per-sample counts (gpca_sample_counts, in row bands) over
+    every SNP that passes the SNP QC, with the rows' weights from the QC counts of all samples (gpca_het_weights), into P.smiss and
+    P.het; with a filter, the pass mask (io.sample_qc_pass) and P.sampleqc.in.id / .out.id.  Sets the keep mask to the QC mask (mu,
+    sigma unchanged); the caller sets its own afterwards.  Returns the pass mask (bool [N]), or None without a filter."""
+    from . import _lib
+    fids = fs.family_ids if cols is None else [fs.family_ids[i] for i in cols]
+    n = len(sample_ids)
+    eng.set_standardization(st["mu"], st["sigma"], st["keep"])                       # every SNP that passes the SNP QC
+    rows = np.flatnonzero(st["keep"])
+    K = len(rows)
+    need_het = a.gpca_het or a.gpca_het_sd is not None
+    q = GpcaEngine.het_weights(eng.snp_qc_detail()[0][rows]) if need_het else None
+    counts, qsum = np.zeros((n, 3), np.uint32), np.zeros(n, np.uint64)
+    try:
+        for r0, r1 in gio.sample_count_bands(K):
+            r = eng.sample_counts(None if q is None else q[r0:r1], rows=(r0, r1))
+            counts += r["counts"]
+            if q is not None:
+                qsum += r["qsum"]
+    except _lib.GpcaError as e:
+        if e.status == _lib.GPCA_ERR_STATE:
+            raise SystemExit(SAMPLE_QC_NEEDS_RESIDENT) from None
+        raise
+    het = GpcaEngine.sample_het(counts, qsum) if need_het else None
+    _ensure_parent(a.output_prefix)
+    if a.gpca_sample_missing:
+        gio.write_smiss(a.output_prefix, fids, sample_ids, counts, K)
+        _log(f"missing calls of {n} samples over {K} SNPs written to {a.output_prefix}.smiss")
+    if a.gpca_het:
+        gio.write_het(a.output_prefix, fids, sample_ids, counts, het)
+        _log(f"heterozygosity of {n} samples over {K} SNPs written to {a.output_prefix}.het")
+    if a.gpca_mind is None and a.gpca_het_sd is None:
+        return None
+    ok, reason = gio.sample_qc_pass(counts, K, None if het is None else het[:, 2], a.gpca_mind, a.gpca_het_sd)
+    gio.write_sample_qc_ids(a.output_prefix, fids, sample_ids, ok, reason)
+    _log(f"sample QC: {reason.count('MIND')} samples fail --gpca-mind, {reason.count('HET')} fail --gpca-het-sd, {int(ok.sum())} of {n} pass")
+    return ok.astype(bool)
+
+
+def _king(eng, a, fs, cols, sample_ids, n_snps, qc_pass=None):
     """--gpca-make-king / --gpca-king-cutoff: one pass over the bands of the kinship triangle (gpca_king) that writes P.kin0 and / or
-    collects the pairs above the cutoff; with the cutoff, the greedy in-set (io.king_unrelated) and its id files.  Returns the in-set
-    mask, or None without the cutoff."""
+    collects the pairs above the cutoff; with the cutoff, the greedy in-set (io.king_unrelated) and its id files.  qc_pass: the sample
+    QC's pass mask; a related pair that touches a failed sample is dropped before the greedy rule, so that a failed sample never evicts
+    a relative (the KING id files then hold the rule's verdict on the pairs that are left).  Returns the in-set mask, or None without
+    the cutoff."""
     _ensure_parent(a.output_prefix)
     fids = fs.family_ids if cols is None else [fs.family_ids[i] for i in cols]
     n = len(sample_ids)
@@ -405,6 +477,8 @@ def _king(eng, a, fs, cols, sample_ids, n_snps):
             pass
     if a.gpca_king_cutoff is None:
         return None
+    if qc_pass is not None:
+        related = [(k, j) for k, j in related if qc_pass[k] and qc_pass[j]]
     inset = gio.king_unrelated(n, related)
     gio.write_king_cutoff_ids(a.output_prefix, fids, sample_ids, inset)
     _log(f"KING cutoff {a.gpca_king_cutoff:g}: {len(related)} related pairs, {n - int(inset.sum())} of {n} samples left out of the fit")
@@ -811,6 +885,18 @@ def main(argv=None) -> int:
         if a.gpca_stream == "on":
             raise SystemExit(STRAT_NEEDS_RESIDENT)
         a.gpca_within_table = _within_table(a)
+    if _sample_qc_asked(a):
+        if not a.eigensnp:
+            raise SystemExit("error: --gpca-sample-missing, --gpca-het, --gpca-mind and --gpca-het-sd need the --eigensnp workflow")
+        if a.gpca_mind is not None and not 0.0 <= a.gpca_mind < 1.0:
+            raise SystemExit("error: --gpca-mind must lie in [0, 1)")
+        if a.gpca_het_sd is not None and not (0.0 < a.gpca_het_sd < float("inf")):
+            raise SystemExit("error: --gpca-het-sd must be finite and above 0")
+        if (a.gpca_mind is not None or a.gpca_het_sd is not None) and a.gpca_eigensnp_local_stage:
+            raise SystemExit("error: --gpca-mind and --gpca-het-sd cannot be combined with --gpca-eigensnp-local-stage (that stage owns "
+                             "the sample mask)")
+        if a.gpca_stream == "on":
+            raise SystemExit(SAMPLE_QC_NEEDS_RESIDENT)
     if a.gpca_assoc_pheno is not None:
         if not a.eigensnp:
             raise SystemExit("error: --gpca-assoc-pheno needs the --eigensnp workflow")

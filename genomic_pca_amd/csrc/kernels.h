@@ -409,4 +409,14 @@ void launch_gc_onehot(hipStream_t st, const int32_t* group, int64_t N, int P, ui
 int launch_group_counts(hipStream_t st, const void* G, int packed, int64_t ldr, const int64_t* krows, int64_t N, const uint8_t* O,
                         const unsigned* size, int P, int64_t row0, int64_t row1, unsigned* counts, unsigned long long* bad);
 
+// ---- per-sample genotype counts (sample_counts.hip): part [plan.splits][sc_npad(N)][3] u32 = missing, het, hom2 and (q given)
+// qpart [plan.splits][sc_npad(N)] u64 = the q of the missing calls, per row split of kept rows [row0, row1) (PCA-SNP order through
+// krows; q [row1 - row0]); *bad as in launch_assoc.  launch_sc_sum: counts [N][3] = n_obs, n_het, n_hom2 and qsum [N] = qtot - the
+// missing calls' q (qpart and qsum NULL: counts alone)
+int launch_sample_counts(hipStream_t st, const void* G, int packed, int64_t ldr, const int64_t* krows, int64_t N, const unsigned* q,
+                         int64_t row0, int64_t row1, const ScPlan& plan, unsigned* part, unsigned long long* qpart,
+                         unsigned long long* bad);
+void launch_sc_sum(hipStream_t st, const unsigned* part, const unsigned long long* qpart, int64_t N, int64_t splits, int64_t rows,
+                   unsigned long long qtot, unsigned* counts, unsigned long long* qsum);
+
 }  // namespace gpca

@@ -440,4 +440,49 @@ constexpr double gc_call_bytes(int64_t N, int64_t rows, int P) {
            4.0 * (double)gc_counts_capacity(rows, P) + 8.0;
 }
 
+// ---- per-sample genotype counts (sample_counts.hip, gpca_sample_counts.cpp) ---------------------------------------------------------
+// A thread owns kScLane consecutive samples (one uint4 of an int8 row, one dword of a 2-bit row); a workgroup of kScThreads threads (one
+// wave) owns a chunk of kScChunk samples and one of the plan's row splits: the band's kept rows [split * per, (split + 1) * per).  The
+// workgroups are numbered split-major on a one-dimensional grid.  A thread counts missing, het and hom2 calls of its 16 samples in
+// byte-wise counters that it adds to u32 registers once per kScFlushRows rows (< 256), fetching kScUnroll rows at a time; it writes its
+// sums to the slab of its split, and a second kernel adds the slabs of a sample.
+constexpr int kScThreads = 64, kScLane = 16, kScChunk = kScThreads * kScLane, kScUnroll = 8, kScFlushRows = 248, kScSumThreads = 256;
+// the default split: about this many waves per CU (four rounds of the 2 resident waves per SIMD: one round leaves a tail wherever
+// chunks x splits is not the slot count; 8 -> 32 took 2.68 -> 2.20 ms at 1M x 10k), and a split no shorter than kScMinRows rows
+constexpr int kScWavesPerCu = 32, kScMinRows = 256;
+static_assert(kScFlushRows % kScUnroll == 0 && kScFlushRows <= 255, "a byte counter holds a flush group; a flush group is whole fetch groups");
+constexpr int64_t sc_npad(int64_t N) { return (N + kScLane - 1) / kScLane * kScLane; }
+constexpr int64_t sc_chunks(int64_t N) { return (N + kScChunk - 1) / kScChunk; }
+struct ScPlan { int64_t chunks, splits, per; };      // per = kept rows of a split (the last one may hold fewer)
+// forced > 0 (GPCA_SAMPLE_COUNTS_SPLITS): that many splits, clamped to the band's rows
+inline ScPlan sc_plan(int64_t rows, int64_t N, int cus, int64_t forced = 0) {
+    ScPlan p{};
+    p.chunks = sc_chunks(N > 0 ? N : 1);
+    int64_t s = forced > 0 ? forced : ((int64_t)kScWavesPerCu * (cus > 0 ? cus : 1) + p.chunks - 1) / p.chunks;
+    if (forced <= 0) s = std::min<int64_t>(s, (rows + kScMinRows - 1) / kScMinRows);
+    s = std::max<int64_t>(1, std::min<int64_t>(s, std::max<int64_t>(rows, 1)));
+    p.per = (std::max<int64_t>(rows, 1) + s - 1) / s;
+    p.splits = (std::max<int64_t>(rows, 1) + p.per - 1) / p.per;
+    return p;
+}
+constexpr int64_t sc_grid(const ScPlan& p) { return p.chunks * p.splits; }
+// the sample a thread's 16 start at, and the byte offset of its fetch into a row (int8: 16 bytes, 2-bit: 4 bytes)
+constexpr int64_t sc_thread_sample(int64_t chunk, int t) { return (chunk * kScThreads + t) * kScLane; }
+constexpr int64_t sc_row_offset(bool packed, int64_t n0) { return packed ? n0 >> 2 : n0; }
+// where a split's sums of sample n lie: part [splits][npad][3] (u32: missing, het, hom2), qpart [splits][npad] (u64: the q of the rows
+// on which n is missing)
+constexpr int64_t sc_part_index(int64_t split, int64_t npad, int64_t n, int c) { return (split * npad + n) * 3 + c; }
+constexpr int64_t sc_qpart_index(int64_t split, int64_t npad, int64_t n) { return split * npad + n; }
+// elements of the call's buffers: the two slabs; counts [N][3] (u32) and qsum [N] (u64); q [rows] (u32); the invalid-genotype word
+constexpr int64_t sc_part_capacity(int64_t splits, int64_t N) { return 3 * splits * sc_npad(N); }
+constexpr int64_t sc_qpart_capacity(int64_t splits, int64_t N) { return splits * sc_npad(N); }
+constexpr int64_t sc_counts_capacity(int64_t N) { return 3 * N; }
+constexpr int64_t sc_qsum_capacity(int64_t N) { return N; }
+constexpr int64_t sc_q_capacity(int64_t rows) { return rows; }
+// The device bytes a call allocates (gpca_sample_counts' GPCA_ERR_OOM sum, without the check's slack)
+constexpr double sc_call_bytes(int64_t N, int64_t rows, int64_t splits, bool hasq) {
+    return 4.0 * (double)sc_part_capacity(splits, N) + 4.0 * (double)sc_counts_capacity(N) + 8.0 +
+           (hasq ? 8.0 * (double)sc_qpart_capacity(splits, N) + 8.0 * (double)sc_qsum_capacity(N) + 4.0 * (double)sc_q_capacity(rows) : 0.0);
+}
+
 }  // namespace gpca

@@ -683,6 +683,60 @@ class GpcaEngine:
         self._chk(self._lib.gpca_group_counts(self._h, _vp(gv), P, r0, r1, _vp(out)))
         return out[:n]
 
+    def sample_counts(self, weights=None, rows: Optional[Tuple[int, int]] = None) -> dict:
+        """Genotype counts per sample (gpca_sample_counts; gpca.h section a18) over the kept rows [row0, row1) in PCA-SNP order
+        (rows; default: all).  Returns {"counts": uint32 [N][3] = n_obs, n_het, n_hom2 (the rows on which the sample has an observed
+        call, g = 1 and g = 2), "qsum": uint64 [N] = the sum of weights[j] over the rows on which the sample is observed, or None
+        without weights}.  weights: uint32, one per row of the band, each at most 2^30 (het_weights).  Exact integers, written per
+        call: the caller sums its bands."""
+        N = self.dims()[1]
+        K = int(self._lib.gpca_num_pca_snps(self._h))
+        r0, r1 = (0, K) if rows is None else (int(rows[0]), int(rows[1]))
+        n = max(r1 - r0, 0)
+        qv = None
+        if weights is not None:
+            wv = np.asarray(weights)
+            if wv.shape != (n,) or wv.dtype.kind not in "iu" or (wv.size and (int(wv.min()) < 0 or int(wv.max()) > 0xffffffff)):
+                raise ValueError("weights must be an unsigned integer array with one entry per row of the band")
+            qv = np.zeros(max(n, 1), np.uint32)
+            qv[:n] = wv
+        counts = np.zeros((max(N, 1), 3), np.uint32)
+        qsum = None if qv is None else np.zeros(max(N, 1), np.uint64)
+        self._chk(self._lib.gpca_sample_counts(self._h, r0, r1, _vp(qv), _vp(counts), _vp(qsum)))
+        return {"counts": counts[:N], "qsum": None if qsum is None else qsum[:N]}
+
+    @staticmethod
+    def het_weights(qc_counts) -> np.ndarray:
+        """The rows' weights for the heterozygosity F (gpca_het_weights; host only; gpca.h section a18): qc_counts [rows][4] = n_valid,
+        n_hom0, n_het, n_hom2 as snp_qc_detail gives them; returns uint32 [rows] = the unbiased expected heterozygosity of each row in
+        units of 2^-30 (0 for a row without a call)."""
+        cv = np.ascontiguousarray(qc_counts, np.uint32)
+        if cv.ndim != 2 or cv.shape[1] != 4:
+            raise ValueError("qc_counts must be [rows][4] as snp_qc_detail returns them")
+        q = np.zeros(max(cv.shape[0], 1), np.uint32)
+        lib = _lib.load()
+        rc = lib.gpca_het_weights(_vp(cv if cv.shape[0] else np.zeros((1, 4), np.uint32)), cv.shape[0], _vp(q))
+        if rc != 0:
+            raise GpcaError(rc, "gpca_het_weights: " + lib.gpca_status_string(rc).decode())
+        return q[:cv.shape[0]]
+
+    @staticmethod
+    def sample_het(counts, qsum) -> np.ndarray:
+        """O_HOM, E_HOM and the inbreeding coefficient F of every sample (gpca_sample_het; host only; gpca.h section a18) from counts
+        [N][3] and qsum [N] as sample_counts gives them with het_weights' weights, summed over the bands.  Returns float64 [N][3]; F is
+        NaN for a sample without an observed call or without expected heterozygosity."""
+        cv = np.ascontiguousarray(counts, np.uint32)
+        qv = np.ascontiguousarray(qsum, np.uint64)
+        if cv.ndim != 2 or cv.shape[1] != 3 or qv.shape != (cv.shape[0],):
+            raise ValueError("counts must be [N][3] and qsum [N] as sample_counts returns them")
+        N = cv.shape[0]
+        out = np.zeros((max(N, 1), 3))
+        lib = _lib.load()
+        rc = lib.gpca_sample_het(_vp(cv if N else np.zeros((1, 3), np.uint32)), _vp(qv if N else np.zeros(1, np.uint64)), N, _vp(out))
+        if rc != 0:
+            raise GpcaError(rc, "gpca_sample_het: " + lib.gpca_status_string(rc).decode())
+        return out[:N]
+
     @staticmethod
     def _fst_counts(counts):
         cv = np.ascontiguousarray(counts, np.uint32)

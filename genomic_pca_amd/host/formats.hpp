@@ -1150,6 +1150,90 @@ private:
     std::vector<std::string> names_;
 };
 
+// ---- genotype counts per sample, heterozygosity F and sample QC: the twins of io.sample_count_bands, io.write_smiss, io.write_het,
+// io.sample_qc_pass and io.write_sample_qc_ids (same rules, byte-identical files) --------------------------------------------------------
+inline std::vector<std::pair<int64_t, int64_t>> sample_count_bands(int64_t K, int64_t max_rows = (int64_t)1 << 24) {
+    const int64_t step = std::max<int64_t>(max_rows, 1);
+    std::vector<std::pair<int64_t, int64_t>> out;
+    for (int64_t r0 = 0; r0 < K; r0 += step) out.emplace_back(r0, std::min(r0 + step, K));
+    return out;
+}
+// P.smiss: `#FID IID MISSING_CT OBS_CT F_MISS` from counts [N][3] over K SNPs: MISSING_CT = K - n_obs, OBS_CT = K, F_MISS as %.6g
+inline void write_smiss(const std::string& prefix, const std::vector<std::string>& fids, const std::vector<std::string>& iids,
+                        const std::vector<uint32_t>& counts, int64_t K) {
+    const size_t n = iids.size();
+    if (counts.size() != 3 * n || fids.size() != n) throw std::runtime_error("write_smiss: counts must be [samples][3] with one FID and IID per sample");
+    OutFile o(prefix + ".smiss");
+    std::fputs("#FID\tIID\tMISSING_CT\tOBS_CT\tF_MISS\n", o.f);
+    char b[48];
+    for (size_t i = 0; i < n; ++i) {
+        const int64_t mis = K - (int64_t)counts[3 * i];
+        fmt_g6(b, K == 0 ? std::nan("") : (double)mis / (double)K);
+        std::fprintf(o.f, "%s\t%s\t%lld\t%lld\t%s\n", fids[i].c_str(), iids[i].c_str(), (long long)mis, (long long)K, b);
+    }
+}
+// P.het: `#FID IID O_HOM E_HOM OBS_CT F` from counts [N][3] (OBS_CT = n_obs) and het [N][3] = O_HOM, E_HOM, F; %.6g, NaN as NA
+inline void write_het(const std::string& prefix, const std::vector<std::string>& fids, const std::vector<std::string>& iids,
+                      const std::vector<uint32_t>& counts, const std::vector<double>& het) {
+    const size_t n = iids.size();
+    if (counts.size() != 3 * n || het.size() != 3 * n || fids.size() != n)
+        throw std::runtime_error("write_het: counts and het must be [samples][3] with one FID and IID per sample");
+    OutFile o(prefix + ".het");
+    std::fputs("#FID\tIID\tO_HOM\tE_HOM\tOBS_CT\tF\n", o.f);
+    char b[3][48];
+    for (size_t i = 0; i < n; ++i) {
+        for (int k = 0; k < 3; ++k) fmt_g6(b[k], het[3 * i + k]);
+        std::fprintf(o.f, "%s\t%s\t%s\t%s\t%llu\t%s\n", fids[i].c_str(), iids[i].c_str(), b[0], b[1], (unsigned long long)counts[3 * i], b[2]);
+    }
+}
+// The sample filters: pass [N] and reason [N] (kSampleQcNone, kSampleQcMind, kSampleQcHet) from counts [N][3] over K SNPs and F [N]
+// (read with het_sd).  Sequential f64 loops in sample order:
+//   mind:   F_MISS = (K - n_obs) / K; a sample fails MIND if n_obs = 0 or F_MISS > mind.
+//   het_sd: over the c samples that pass MIND and have a finite F, m = (sum F) / c and s = sqrt(sum (F - m)^2 / (c - 1)); a sample that
+//           passes MIND fails HET if F is NaN or |F - m| > het_sd s.  One round; with c < 2 or s = 0 only NaN fails.
+constexpr uint8_t kSampleQcNone = 0, kSampleQcMind = 1, kSampleQcHet = 2;
+inline void sample_qc_pass(const std::vector<uint32_t>& counts, int64_t K, const std::vector<double>& F, bool use_mind, double mind,
+                           bool use_het, double het_sd, std::vector<uint8_t>& pass, std::vector<uint8_t>& reason) {
+    const size_t n = counts.size() / 3;
+    if (counts.size() != 3 * n) throw std::runtime_error("sample_qc_pass: counts must be [samples][3]");
+    pass.assign(n, 1); reason.assign(n, kSampleQcNone);
+    if (use_mind)
+        for (size_t i = 0; i < n; ++i) {
+            const int64_t nobs = counts[3 * i];
+            if (nobs == 0 || (double)(K - nobs) / (double)K > mind) { pass[i] = 0; reason[i] = kSampleQcMind; }
+        }
+    if (use_het) {
+        if (F.size() != n) throw std::runtime_error("sample_qc_pass: het_sd needs F with one entry per sample");
+        int64_t c = 0;
+        double tot = 0.0;
+        for (size_t i = 0; i < n; ++i)
+            if (pass[i] && std::isfinite(F[i])) { ++c; tot = tot + F[i]; }
+        const double m = c ? tot / (double)c : 0.0;
+        double ss = 0.0;
+        for (size_t i = 0; i < n; ++i)
+            if (pass[i] && std::isfinite(F[i])) { const double d = F[i] - m; ss = ss + d * d; }
+        const double s = c >= 2 ? std::sqrt(ss / (double)(c - 1)) : 0.0;
+        for (size_t i = 0; i < n; ++i) {
+            if (!pass[i]) continue;
+            const double x = F[i];
+            if (x != x || (c >= 2 && s > 0.0 && std::fabs(x - m) > het_sd * s)) { pass[i] = 0; reason[i] = kSampleQcHet; }
+        }
+    }
+}
+// P.sampleqc.in.id (`#FID IID`) and P.sampleqc.out.id (`#FID IID REASON`, MIND or HET), in sample order
+inline void write_sample_qc_ids(const std::string& prefix, const std::vector<std::string>& fids, const std::vector<std::string>& iids,
+                                const std::vector<uint8_t>& pass, const std::vector<uint8_t>& reason) {
+    const size_t n = iids.size();
+    if (fids.size() != n || pass.size() != n || reason.size() != n) throw std::runtime_error("write_sample_qc_ids: one entry per sample in every column");
+    OutFile in(prefix + ".sampleqc.in.id"), out(prefix + ".sampleqc.out.id");
+    std::fputs("#FID\tIID\n", in.f);
+    std::fputs("#FID\tIID\tREASON\n", out.f);
+    for (size_t i = 0; i < n; ++i) {
+        if (pass[i]) std::fprintf(in.f, "%s\t%s\n", fids[i].c_str(), iids[i].c_str());
+        else std::fprintf(out.f, "%s\t%s\t%s\n", fids[i].c_str(), iids[i].c_str(), reason[i] == kSampleQcMind ? "MIND" : reason[i] == kSampleQcHet ? "HET" : "None");
+    }
+}
+
 }  // namespace gpca_host
 
 #endif

@@ -77,6 +77,10 @@ struct Args {
     bool have_fst = false, fst_variants = false;   // --gpca-fst hudson|wc: P.fst.summary; --gpca-fst-variants: P.fst.var
     std::string fst;
     gpca_host::WithinTable within_table;   // read in main, before any work on the device
+    bool sample_missing = false, het = false;      // --gpca-sample-missing: P.smiss; --gpca-het: P.het
+    bool have_mind = false, have_het_sd = false;   // --gpca-mind X, --gpca-het-sd K: the sample filters, P.sampleqc.in.id / .out.id
+    double mind = 0.0, het_sd = 0.0;
+    bool sample_qc_asked() const { return sample_missing || het || have_mind || have_het_sd; }
 };
 
 [[noreturn]] void usage_error(const std::string& msg) {
@@ -212,6 +216,16 @@ void print_help() {
         "                                       (Bhatia et al. 2013) or wc (Weir and Cockerham 1984; with more than two groups also\n"
         "                                       jointly) -> <out>.fst.summary\n"
         "      --gpca-fst-variants              --gpca-fst: also the per-SNP terms -> <out>.fst.var\n"
+        "      --gpca-sample-missing            --eigensnp: the missing calls of every sample over the SNPs that pass the SNP QC ->\n"
+        "                                       <out>.smiss (#FID IID MISSING_CT OBS_CT F_MISS)\n"
+        "      --gpca-het                       --eigensnp: the observed and expected homozygous calls and the inbreeding coefficient F of\n"
+        "                                       every sample over the SNPs that pass the SNP QC (plink --het, allele frequencies from all\n"
+        "                                       samples) -> <out>.het (#FID IID O_HOM E_HOM OBS_CT F)\n"
+        "      --gpca-mind <X>                  --eigensnp: drop a sample from the fit, PC-Relate's training set and the scans when more\n"
+        "                                       than X of its calls are missing (0 <= X < 1) -> <out>.sampleqc.in.id / .out.id; every\n"
+        "                                       sample is still projected\n"
+        "      --gpca-het-sd <K>                --eigensnp: drop a sample whose F lies more than K standard deviations from the mean F of\n"
+        "                                       the samples that pass --gpca-mind (K > 0; one round) -> <out>.sampleqc.in.id / .out.id\n"
         "      --gpca-assoc-pcs <P>             --gpca-assoc-pheno: the first P columns of the scores this run writes are covariates\n"
         "                                       (0 <= P <= --eigensnp-k-global) [default: every column]\n"
         "      --gpca-assoc-covar <FILE>        --gpca-assoc-pheno: further covariates, a table in the format of the phenotype file\n"
@@ -305,6 +319,10 @@ Args parse(int argc, char** argv) {
         else if (f == "--gpca-freq-strat") a.freq_strat = true;
         else if (f == "--gpca-fst") { a.fst = val(); a.have_fst = true; }
         else if (f == "--gpca-fst-variants") a.fst_variants = true;
+        else if (f == "--gpca-sample-missing") a.sample_missing = true;
+        else if (f == "--gpca-het") a.het = true;
+        else if (f == "--gpca-mind") { a.mind = to_f64(f, val()); a.have_mind = true; }
+        else if (f == "--gpca-het-sd") { a.het_sd = to_f64(f, val()); a.have_het_sd = true; }
         else if (f == "--gpca-assoc-pcs") { a.assoc_pcs = to_i64(f, val()); a.have_assoc_pcs = true; }
         else if (f == "--gpca-assoc-vif") { a.assoc_vif = to_f64(f, val()); a.have_assoc_vif = true; }
         else if (f == "--gpca-indep-pairwise") {
@@ -740,6 +758,75 @@ int run_assoc(gpca::Engine& eng, const Args& a, const gpca_host::PlinkFileset& f
     return 0;
 }
 
+const char* const kSampleQcNeedsResident =
+    "error: --gpca-sample-missing, --gpca-het, --gpca-mind and --gpca-het-sd need the genotype matrix resident on the device: the "
+    "per-sample counts of a matrix walked out of core are not implemented\n";
+
+// --gpca-sample-missing / --gpca-het / --gpca-mind / --gpca-het-sd: the per-sample counts (gpca_sample_counts, in row bands) over every
+// SNP that passes the SNP QC, with the rows' weights from the QC counts of all samples (gpca_het_weights), into P.smiss and P.het; with
+// a filter, the pass mask and P.sampleqc.in.id / .out.id.  Sets the keep mask to the QC mask (mu, sigma unchanged); the caller sets its
+// own afterwards.  pass stays empty without a filter (cli.py:_sample_qc).
+int run_sample_qc(gpca::Engine& eng, const Args& a, const std::vector<std::string>& fids, const std::vector<std::string>& sample_ids,
+                  const gpca::SnpStats& st, std::vector<uint8_t>& pass) {
+    const size_t n = sample_ids.size();
+    eng.set_standardization(st.mu, st.sigma, st.keep);                                 // every SNP that passes the SNP QC
+    std::vector<int64_t> rows;
+    for (size_t i = 0; i < st.keep.size(); ++i) if (st.keep[i]) rows.push_back((int64_t)i);
+    const int64_t K = (int64_t)rows.size();
+    const bool need_het = a.het || a.have_het_sd;
+    std::vector<uint32_t> q;
+    if (need_het) {
+        const std::vector<uint32_t> all = eng.snp_qc_counts();
+        std::vector<uint32_t> qc(4 * rows.size());
+        for (size_t t = 0; t < rows.size(); ++t) std::copy(all.begin() + 4 * rows[t], all.begin() + 4 * rows[t] + 4, qc.begin() + 4 * t);
+        q = gpca::Engine::het_weights(qc);
+    }
+    std::vector<uint32_t> counts(3 * n, 0u);
+    std::vector<uint64_t> qsum(n, 0u);
+    try {
+        for (const auto& b : gpca_host::sample_count_bands(K)) {
+            std::vector<uint32_t> c;
+            std::vector<uint64_t> s;
+            const std::vector<uint32_t> qb(need_het ? q.begin() + b.first : q.begin(), need_het ? q.begin() + b.second : q.begin());
+            eng.sample_counts(b.first, b.second, need_het ? &qb : nullptr, c, need_het ? &s : nullptr);
+            for (size_t i = 0; i < 3 * n; ++i) counts[i] += c[i];
+            if (need_het) for (size_t i = 0; i < n; ++i) qsum[i] += s[i];
+        }
+    } catch (const gpca::Error& e) {
+        if (e.status() != GPCA_ERR_STATE) throw;
+        std::fputs(kSampleQcNeedsResident, stderr);
+        return 1;
+    }
+    std::vector<double> het, F;
+    if (need_het) {
+        het = gpca::Engine::sample_het(counts, qsum);
+        F.resize(n);
+        for (size_t i = 0; i < n; ++i) F[i] = het[3 * i + 2];
+    }
+    gpca_host::ensure_parent(a.output_prefix);
+    char buf[320];
+    if (a.sample_missing) {
+        gpca_host::write_smiss(a.output_prefix, fids, sample_ids, counts, K);
+        std::snprintf(buf, sizeof buf, "missing calls of %zu samples over %lld SNPs written to %s.smiss", n, (long long)K, a.output_prefix.c_str());
+        logmsg(buf);
+    }
+    if (a.het) {
+        gpca_host::write_het(a.output_prefix, fids, sample_ids, counts, het);
+        std::snprintf(buf, sizeof buf, "heterozygosity of %zu samples over %lld SNPs written to %s.het", n, (long long)K, a.output_prefix.c_str());
+        logmsg(buf);
+    }
+    if (!a.have_mind && !a.have_het_sd) return 0;
+    std::vector<uint8_t> reason;
+    gpca_host::sample_qc_pass(counts, K, F, a.have_mind, a.mind, a.have_het_sd, a.het_sd, pass, reason);
+    gpca_host::write_sample_qc_ids(a.output_prefix, fids, sample_ids, pass, reason);
+    int64_t n_mind = 0, n_het = 0, n_ok = 0;
+    for (size_t i = 0; i < n; ++i) { n_mind += reason[i] == gpca_host::kSampleQcMind; n_het += reason[i] == gpca_host::kSampleQcHet; n_ok += pass[i]; }
+    std::snprintf(buf, sizeof buf, "sample QC: %lld samples fail --gpca-mind, %lld fail --gpca-het-sd, %lld of %zu pass", (long long)n_mind, (long long)n_het,
+                  (long long)n_ok, n);
+    logmsg(buf);
+    return 0;
+}
+
 int run_eigensnp_workflow(Args a) {
     if (a.bed_file.empty() || a.ld_block_file.empty()) {
         std::fprintf(stderr, "error: --bed-file and --ld-block-file are required when --eigensnp is used\n");           // main.rs:296-301
@@ -766,7 +853,15 @@ int run_eigensnp_workflow(Args a) {
     if (streamed && a.make_pcrelate) { std::fputs(kPcrelateNeedsResident, stderr); return 1; }
     if (streamed && !a.assoc_pheno.empty()) { std::fputs(kAssocNeedsResident, stderr); return 1; }
     if (streamed && !a.within.empty()) { std::fputs(kStratNeedsResident, stderr); return 1; }
+    if (streamed && a.sample_qc_asked()) { std::fputs(kSampleQcNeedsResident, stderr); return 1; }
     const gpca::SnpStats st = eng.snp_stats(gpca::QcConfig{a.min_call_rate, a.min_maf, a.max_hwe_p});
+    std::vector<uint8_t> qc_pass;                                                                                       // empty: no sample filter
+    if (a.sample_qc_asked() && !sample_ids.empty() && std::count(st.keep.begin(), st.keep.end(), (uint8_t)1) > 0) {
+        std::vector<std::string> fids = fs.family_ids;
+        if (use_kept) { fids.clear(); for (int64_t c : kept.cols) fids.push_back(fs.family_ids[(size_t)c]); }
+        const int rc = run_sample_qc(eng, a, fids, sample_ids, st, qc_pass);
+        if (rc != 0) return rc;
+    }
     const auto blocks = gpca_host::parse_ld_block_file(a.ld_block_file);
     std::vector<uint8_t> keep;
     auto by_tag = gpca_host::map_snps_to_ld_blocks(blocks, fs.chromosomes, fs.positions, st.keep, keep);
@@ -879,6 +974,11 @@ int run_eigensnp_workflow(Args a) {
             logmsg(buf);
         }
         if (a.have_king_cutoff) {
+            // a pair that touches a sample the sample QC failed is dropped before the greedy rule: a failed sample evicts no relative
+            if (!qc_pass.empty())
+                related.erase(std::remove_if(related.begin(), related.end(),
+                                             [&](const std::pair<int64_t, int64_t>& p) { return !qc_pass[(size_t)p.first] || !qc_pass[(size_t)p.second]; }),
+                              related.end());
             inset = gpca_host::king_unrelated(n, related);
             gpca_host::write_king_cutoff_ids(a.output_prefix, fids, sample_ids, inset);
             int64_t n_fit = 0;
@@ -890,7 +990,12 @@ int run_eigensnp_workflow(Args a) {
         }
     }
     int64_t n_fit = (int64_t)sample_ids.size();
+    if (!qc_pass.empty()) {                                                                                             // the in-set is KING's and the sample QC's
+        if (inset.empty()) inset = qc_pass;
+        else for (size_t i = 0; i < inset.size(); ++i) inset[i] = inset[i] && qc_pass[i];
+    }
     if (!inset.empty()) { n_fit = 0; for (uint8_t v : inset) n_fit += v; }
+    if (!qc_pass.empty() && n_fit < 2) { std::fprintf(stderr, "error: --gpca-mind / --gpca-het-sd leave fewer than 2 samples to fit the PCA on\n"); return 1; }
     gpca::MicroarrayGenotypeAccessor acc(eng);
     const std::vector<int64_t> rows = acc.original_indices_of_pca_snps();
     std::unordered_map<int64_t, int64_t> row_to_id;
@@ -1118,6 +1223,16 @@ int main(int argc, char** argv) {
             }
             if (a.have_fst && ng < 2) { std::fprintf(stderr, "error: --gpca-fst needs at least two groups, --gpca-within names %zu\n", ng); return 2; }
             if (ng < 1) { std::fprintf(stderr, "error: --gpca-within names no group\n"); return 2; }
+        }
+        if (a.sample_qc_asked()) {
+            if (!a.eigensnp) { std::fprintf(stderr, "error: --gpca-sample-missing, --gpca-het, --gpca-mind and --gpca-het-sd need the --eigensnp workflow\n"); return 2; }
+            if (a.have_mind && !(a.mind >= 0.0 && a.mind < 1.0)) { std::fprintf(stderr, "error: --gpca-mind must lie in [0, 1)\n"); return 2; }
+            if (a.have_het_sd && !(a.het_sd > 0.0 && std::isfinite(a.het_sd))) { std::fprintf(stderr, "error: --gpca-het-sd must be finite and above 0\n"); return 2; }
+            if ((a.have_mind || a.have_het_sd) && a.local_stage) {
+                std::fprintf(stderr, "error: --gpca-mind and --gpca-het-sd cannot be combined with --gpca-eigensnp-local-stage (that stage owns the sample mask)\n");
+                return 2;
+            }
+            if (a.stream == "on") { std::fputs(kSampleQcNeedsResident, stderr); return 2; }
         }
         if (!a.assoc_pheno.empty()) {
             if (!a.eigensnp) { std::fprintf(stderr, "error: --gpca-assoc-pheno needs the --eigensnp workflow\n"); return 2; }

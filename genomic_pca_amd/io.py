@@ -14,6 +14,7 @@ Reference behaviour restated (file:line):
 from __future__ import annotations
 
 import gzip
+import math
 import os
 import re
 from dataclasses import dataclass
@@ -1118,3 +1119,104 @@ def write_fst_var(prefix: str, method: str, chromosomes: Sequence[str], position
                 den = v[1] if method == "hudson" else (v[0] + v[1]) + v[2]
                 f.write(head + f"{names[j]}\t{names[k]}\t" + "\t".join(_g6(x) for x in v) + f"\t{_ratio6(v[0], den)}\n")
     return path
+
+
+# ---- genotype counts per sample, heterozygosity F and sample QC (gpca_sample_counts, gpca_het_weights, gpca_sample_het): twins in
+# host/formats.hpp ------------------------------------------------------------------------------------------------------------------------
+def sample_count_bands(K: int, max_rows: int = 1 << 24):
+    """[row0, row1) bands of the K kept rows of at most max_rows rows: the bands gpca_sample_counts is asked for, one at a time (a band's
+    weights travel with it; its counts are per sample and are summed over the bands by the caller)."""
+    step = max(int(max_rows), 1)
+    return [(r0, min(r0 + step, K)) for r0 in range(0, K, step)]
+
+
+def write_smiss(prefix: str, family_ids: Sequence[str], sample_ids: Sequence[str], counts, K: int) -> str:
+    """P.smiss (plink --missing's sample table): one tab-separated line per sample, `#FID IID MISSING_CT OBS_CT F_MISS` from counts [N][3]
+    = n_obs, n_het, n_hom2 over K SNPs: MISSING_CT = K - n_obs, OBS_CT = K (the SNPs looked at, as plink 2 prints it), F_MISS =
+    MISSING_CT / K as %.6g (NA for K = 0)."""
+    cv = np.asarray(counts)
+    n = len(sample_ids)
+    if cv.shape != (n, 3) or len(family_ids) != n:
+        raise ValueError("write_smiss: counts must be [samples][3] with one FID and IID per sample")
+    path = f"{prefix}.smiss"
+    with _open_out(path, False) as f:
+        f.write("#FID\tIID\tMISSING_CT\tOBS_CT\tF_MISS\n")
+        for i in range(n):
+            mis = int(K) - int(cv[i, 0])
+            f.write(f"{family_ids[i]}\t{sample_ids[i]}\t{mis}\t{int(K)}\t{'NA' if K == 0 else _g6(float(mis) / float(K))}\n")
+    return path
+
+
+def write_het(prefix: str, family_ids: Sequence[str], sample_ids: Sequence[str], counts, het) -> str:
+    """P.het (plink --het): one tab-separated line per sample, `#FID IID O_HOM E_HOM OBS_CT F` from counts [N][3] (OBS_CT = n_obs, the
+    sample's observed calls) and het [N][3] = O_HOM, E_HOM, F (gpca_sample_het); the three numbers as %.6g, NaN as NA."""
+    cv, hv = np.asarray(counts), np.asarray(het, np.float64)
+    n = len(sample_ids)
+    if cv.shape != (n, 3) or hv.shape != (n, 3) or len(family_ids) != n:
+        raise ValueError("write_het: counts and het must be [samples][3] with one FID and IID per sample")
+    path = f"{prefix}.het"
+    with _open_out(path, False) as f:
+        f.write("#FID\tIID\tO_HOM\tE_HOM\tOBS_CT\tF\n")
+        for i in range(n):
+            f.write(f"{family_ids[i]}\t{sample_ids[i]}\t{_g6(hv[i, 0])}\t{_g6(hv[i, 1])}\t{int(cv[i, 0])}\t{_g6(hv[i, 2])}\n")
+    return path
+
+
+def sample_qc_pass(counts, K: int, F=None, mind: Optional[float] = None, het_sd: Optional[float] = None):
+    """The sample filters (plink --mind; the usual heterozygosity rule of GWAS protocols) from counts [N][3] over K SNPs and F [N]
+    (needed with het_sd).  Returns (pass uint8 [N], reason: a list of None, "MIND" or "HET").  Sequential f64 loops in sample order:
+      mind:   F_MISS = (K - n_obs) / K; a sample fails MIND if n_obs = 0 or F_MISS > mind.
+      het_sd: over the c samples that pass MIND and have a finite F, m = (sum F) / c and s = sqrt(sum (F - m)^2 / (c - 1)); a sample
+              that passes MIND fails HET if F is NaN or |F - m| > het_sd s.  One round; with c < 2 or s = 0 only NaN fails."""
+    cv = np.asarray(counts)
+    n = cv.shape[0]
+    if cv.ndim != 2 or cv.shape[1] != 3:
+        raise ValueError("sample_qc_pass: counts must be [samples][3]")
+    ok = np.ones(n, np.uint8)
+    reason: List[Optional[str]] = [None] * n
+    if mind is not None:
+        for i in range(n):
+            nobs = int(cv[i, 0])
+            if nobs == 0 or float(int(K) - nobs) / float(K) > float(mind):
+                ok[i], reason[i] = 0, "MIND"
+    if het_sd is not None:
+        fv = np.asarray(F, np.float64)
+        if fv.shape != (n,):
+            raise ValueError("sample_qc_pass: het_sd needs F with one entry per sample")
+        c, tot = 0, 0.0
+        for i in range(n):
+            if ok[i] and math.isfinite(fv[i]):
+                c += 1
+                tot = tot + float(fv[i])
+        m = tot / c if c else 0.0
+        ss = 0.0
+        for i in range(n):
+            if ok[i] and math.isfinite(fv[i]):
+                d = float(fv[i]) - m
+                ss = ss + d * d
+        s = math.sqrt(ss / (c - 1)) if c >= 2 else 0.0
+        for i in range(n):
+            if not ok[i]:
+                continue
+            x = float(fv[i])
+            if x != x or (c >= 2 and s > 0.0 and abs(x - m) > float(het_sd) * s):
+                ok[i], reason[i] = 0, "HET"
+    return ok, reason
+
+
+def write_sample_qc_ids(prefix: str, family_ids: Sequence[str], sample_ids: Sequence[str], passed, reason) -> Tuple[str, str]:
+    """P.sampleqc.in.id (`#FID IID`: the samples that pass) and P.sampleqc.out.id (`#FID IID REASON`, REASON = MIND or HET), both
+    tab-separated, in sample order."""
+    n = len(sample_ids)
+    if len(family_ids) != n or len(passed) != n or len(reason) != n:
+        raise ValueError("write_sample_qc_ids: one entry per sample in every column")
+    pin, pout = f"{prefix}.sampleqc.in.id", f"{prefix}.sampleqc.out.id"
+    with _open_out(pin, False) as fi, _open_out(pout, False) as fo:
+        fi.write("#FID\tIID\n")
+        fo.write("#FID\tIID\tREASON\n")
+        for i in range(n):
+            if passed[i]:
+                fi.write(f"{family_ids[i]}\t{sample_ids[i]}\n")
+            else:
+                fo.write(f"{family_ids[i]}\t{sample_ids[i]}\t{reason[i]}\n")
+    return pin, pout

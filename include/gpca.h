@@ -700,6 +700,46 @@ GPCA_API int gpca_fst_hudson(const uint32_t* counts, int64_t rows, int32_t P, do
 GPCA_API int gpca_fst_wc(const uint32_t* counts, int64_t rows, int32_t P, const uint8_t* use /* [P] or NULL */,
                          double* abc /* [rows][3] or NULL */, double* sums /* [3]: sum a, sum (a + b + c), rows used; ADDED TO */);
 
+/* ---- a18: genotype counts per sample, and the heterozygosity F from them (plink --missing's sample table and --mind, plink --het):
+ * what a sample looks like over the SNPs.  Contamination gives a strongly negative F, inbreeding or a failed array a positive one.
+ * gpca_sample_counts: for the kept rows [row0, row1) in PCA-SNP order, counts [N][3] (uint32) = n_obs, n_het, n_hom2 of every sample:
+ *     the band's rows on which it has an observed call, those with g = 1 and those with g = 2 (g counts copies of A1).  With q
+ *     [row1 - row0] (each at most 2^30) qsum [N] (uint64) = the sum of q[j] over the band's rows j on which the sample is observed; q and
+ *     qsum are both given or both NULL.  The outputs are WRITTEN, not added to (an empty band writes zeros): the caller sums its bands.
+ *  Device: a reduction over the SNP axis.  A thread owns 16 consecutive samples (one 16-byte load of an int8 row, one dword of a 2-bit
+ *     row); the missing, het and hom2 indicators are added byte-wise (four counters to a dword) and the bytes are added to 32-bit
+ *     registers once per 248 rows, before one can wrap; qsum = (the sum of all q of the band) - (the q of the sample's missing calls) in
+ *     64-bit integers, the per-sample work only on rows where a wave ballot finds a missing call.  The band's rows are split over
+ *     workgroups; each split writes its sums once and a second kernel adds them: integers, so the split changes no bit
+ *     (GPCA_SAMPLE_COUNTS_SPLITS in the environment, read per call, forces the split count, clamped to 1 .. rows: a test hook).  No
+ *     float touches a sum.  A sample at or beyond N never contributes, whatever the pad bytes hold.
+ *     A call over all rows equals the sum of calls over consecutive bands; int8 and 2-bit residency and a GPCA_PREC_F32_MFMA handle give
+ *     the same bits; the sample mask is ignored and no fitted result is touched.
+ *  Errors: GPCA_ERR_STATE (no genotypes, a streamed handle, a row-sharded handle, no standardisation, K = 0), GPCA_ERR_BAD_ARG (a NULL
+ *     counts, q without qsum or the reverse, a q[j] above 2^30, a row range out of bounds, a band of 2^31 or more rows),
+ *     GPCA_ERR_INVALID_GENOTYPE (a row the call reads holds a value outside {0, 1, 2, missing} on a sample below N; the message names
+ *     the row, as in a12), GPCA_ERR_OOM (checked before any allocation).
+ * The two host rules take no handle and work in f64 with no fused multiply-add, in exactly this order.
+ *  gpca_het_weights: qc [rows][4] = n_valid, n_hom0, n_het, n_hom2 as gpca_get_snp_qc_detail gives them.  Per row, every count formed
+ *     in f64:
+ *         t = 2 n_valid,  p = (n_het + 2 n_hom2) / t
+ *         e = ((2 p) (1 - p)) (t / (t - 1))          the unbiased expected heterozygosity of the row (plink 1.9's small-sample term)
+ *         q = (uint32) floor(e 2^30 + 0.5)
+ *     A row with n_valid = 0 gets q = 0.  e <= 1 (2 p (1 - p) <= 1/2, t / (t - 1) <= 2), so q <= 2^30.
+ *     GPCA_ERR_BAD_ARG: NULL qc or q, rows < 0.
+ *  gpca_sample_het: counts [N][3] and qsum [N] as gpca_sample_counts gives them (summed over the bands), with q from gpca_het_weights.
+ *     Per sample, n_obs, n_het and qsum converted to f64 (qsum rounds to nearest above 2^53):
+ *         O_HOM = n_obs - n_het,  E_HOM = n_obs - qsum / 2^30,  d = n_obs - E_HOM,  F = (O_HOM - E_HOM) / d
+ *     out [N][3] = O_HOM, E_HOM, F; F is NaN where n_obs = 0 or d <= 0.  GPCA_ERR_BAD_ARG: a NULL argument, N < 0.
+ *  plink's own printed digits are not claimed: plink 1.9 takes the allele frequencies of --het from the loaded samples too, but rounds
+ *     in its own order.
+ *  Not there: haploid and sex chromosomes and a sex check, an iterated heterozygosity filter, per-sample weights other than one u32 per
+ *     row, streamed and row-sharded handles. */
+GPCA_API int gpca_sample_counts(gpca_handle* h, int64_t row0, int64_t row1, const uint32_t* q /* [row1 - row0] or NULL */,
+                                uint32_t* counts /* [N][3] */, uint64_t* qsum /* [N] or NULL */);
+GPCA_API int gpca_het_weights(const uint32_t* qc /* [rows][4] */, int64_t rows, uint32_t* q /* [rows] */);
+GPCA_API int gpca_sample_het(const uint32_t* counts /* [N][3] */, const uint64_t* qsum /* [N] */, int64_t N, double* out /* [N][3] */);
+
 /* ---- f3: the stages of EigenSNPCoreAlgorithm::compute_pca (main.rs:311-327, 359-366) ------------------------------------------
  * The algorithm lives in the un-vendored efficient_pca crate (Cargo.toml:30, branch "main", no pinned revision): what follows is
  * the stage structure of its published description -- per-LD-block local bases learnt on a sample subset, condensed features of

@@ -367,6 +367,39 @@ public:
         }
         if (rc != GPCA_OK) throw Error(rc, std::string("gpca_fst_wc: ") + gpca_status_string(rc));
     }
+    // genotype counts per sample (gpca_sample_counts; gpca.h section a18) over the kept rows [row0, row1): counts [N][3] = n_obs, n_het,
+    // n_hom2; with q (one weight per row of the band, each <= 2^30) qsum [N] = the sum of q over the rows on which the sample is
+    // observed.  WRITTEN per call: the caller sums its bands.
+    void sample_counts(int64_t row0, int64_t row1, const std::vector<uint32_t>* q, std::vector<uint32_t>& counts,
+                       std::vector<uint64_t>* qsum = nullptr) const {
+        const size_t N = (size_t)dims().second, rows = row1 > row0 ? (size_t)(row1 - row0) : 0;
+        if ((q != nullptr) != (qsum != nullptr) || (q && q->size() != rows))
+            throw std::invalid_argument("sample_counts: q (one entry per row of the band) and qsum go together");
+        counts.assign(std::max<size_t>(3 * N, 1), 0u);
+        if (qsum) qsum->assign(std::max<size_t>(N, 1), 0u);
+        static const uint32_t none = 0;
+        check(gpca_sample_counts(h_, row0, row1, q ? (rows ? q->data() : &none) : nullptr, counts.data(), qsum ? qsum->data() : nullptr));
+        counts.resize(3 * N);
+        if (qsum) qsum->resize(N);
+    }
+    // the rows' weights for the heterozygosity F (gpca_het_weights; host only): qc [rows][4] as snp_qc_detail gives them
+    static std::vector<uint32_t> het_weights(const std::vector<uint32_t>& qc) {
+        const size_t rows = qc.size() / 4;
+        std::vector<uint32_t> q(std::max<size_t>(rows, 1), 0u);
+        const int rc = qc.size() != rows * 4 ? GPCA_ERR_BAD_ARG : (rows ? gpca_het_weights(qc.data(), (int64_t)rows, q.data()) : GPCA_OK);
+        if (rc != GPCA_OK) throw Error(rc, std::string("gpca_het_weights: ") + gpca_status_string(rc));
+        q.resize(rows);
+        return q;
+    }
+    // O_HOM, E_HOM and F of every sample (gpca_sample_het; host only): out [N][3]
+    static std::vector<double> sample_het(const std::vector<uint32_t>& counts, const std::vector<uint64_t>& qsum) {
+        const size_t N = qsum.size();
+        std::vector<double> out(std::max<size_t>(3 * N, 1), 0.0);
+        const int rc = counts.size() != 3 * N ? GPCA_ERR_BAD_ARG : (N ? gpca_sample_het(counts.data(), qsum.data(), (int64_t)N, out.data()) : GPCA_OK);
+        if (rc != GPCA_OK) throw Error(rc, std::string("gpca_sample_het: ") + gpca_status_string(rc));
+        out.resize(3 * N);
+        return out;
+    }
     // the null logistic model of one trait (gpca_logistic_null; host only): y [N] in {0, 1}, C [N][Pc]; alpha [Pc + 1], mu [N] (0 outside
     // the included samples); returns the number of Newton steps; throws Error with the status (no message: there is no handle)
     static int logistic_null(const std::vector<double>& y, const std::vector<double>& C, int32_t Pc, const std::vector<uint8_t>* include,
