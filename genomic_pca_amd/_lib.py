@@ -28,6 +28,7 @@ STORE_AUTO = 0         # 2-bit codes from 1 024 samples on, int8 below (decided 
 STORE_2BIT = 1
 STORE_INT8 = 2
 GROUPS_MAX = 64           # gpca_group_counts: most sample groups of one call (include/gpca.h)
+LDSCORE_UNBIASED = 1      # gpca_ld_score flag (include/gpca.h)
 GRM_STANDARDIZED = 0      # gpca_grm scalings (include/gpca.h)
 GRM_CENTRED = 1
 CFG_SIMPLE_KERNELS = 1     # gpca_config.reserved[0] flags (include/gpca.h)
@@ -159,6 +160,9 @@ PROTOTYPES = {
     "gpca_sample_counts": (C.c_int, [_H, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gpca_het_weights": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
     "gpca_sample_het": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "gpca_ld_score": (C.c_int, [_H, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "gpca_ld_score_total": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
+    "gpca_ldsc_fit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_int32, C.c_double, C.c_void_p]),
     "gpca_comm_get_unique_id": (C.c_int, [C.c_void_p]),
     "gpca_comm_init": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, C.c_int64]),
     "gpca_set_allreduce_hook": (C.c_int, [_H, ALLREDUCE_FN, C.c_void_p, C.c_int32, C.c_int32, C.c_int64]),

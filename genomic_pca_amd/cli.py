@@ -117,6 +117,17 @@ def build_parser() -> argparse.ArgumentParser:
                         "chromosome) or a span such as 250kb; 0 < R2 < 1.  Of a pair of kept SNPs with unphased r^2 > R2 the one with the "
                         "smaller minor-allele frequency leaves (ties: the later one) -> P.prune.in / P.prune.out.  Needs the matrix "
                         "resident on the device; plink's exact output is not claimed")
+    p.add_argument("--gpca-ld-score", default=None, metavar="WINDOW",
+                   help="EigenSNP workflow: after the PCA outputs, the LD score of every SNP that passes the SNP QC: L2 = 1 + the sum of "
+                        "the bias-adjusted unphased r^2 with the SNPs of its chromosome at most WINDOW away on both sides (the grammar of "
+                        "--gpca-indep-pairwise's WINDOW; 1000kb is the recommendation), summed on the device -> P.l2.ldscore (CHR SNP BP "
+                        "L2), P.l2.M, P.l2.M_5_50.  Every sample enters, relatives and samples that fail the sample QC included.  Needs "
+                        "the matrix resident on the device")
+    p.add_argument("--gpca-assoc-ldsc", action="store_true",
+                   help="--gpca-ld-score and --gpca-assoc-pheno: LD-score regression of every trait's scan statistics (T_STAT^2 or "
+                        "Z_STAT^2) on the LD scores, 200 jackknife blocks -> P.ldsc.summary (#TRAIT TEST N M_USED MEAN_CHI2 LAMBDA_GC "
+                        "INTERCEPT INTERCEPT_SE H2 H2_SE RATIO RATIO_SE).  The intercept measures confounding, H2 the SNP heritability "
+                        "(of a case / control trait: on the observed scale)")
     p.add_argument("--gpca-assoc-pheno", default=None, metavar="FILE",
                    help="EigenSNP workflow: after everything else is written, test every SNP that passes the SNP QC (call rate, MAF, HWE; "
                         "the LD blocks and --gpca-indep-pairwise shape the PCA, not the test set) against every trait column of FILE "
@@ -325,6 +336,8 @@ def run_eigensnp_workflow(a) -> int:
         raise SystemExit(STRAT_NEEDS_RESIDENT)
     if streamed and _sample_qc_asked(a):
         raise SystemExit(SAMPLE_QC_NEEDS_RESIDENT)
+    if streamed and a.gpca_ld_score is not None:
+        raise SystemExit(LD_SCORE_NEEDS_RESIDENT)
     st = eng.snp_stats(QcConfig(a.eigensnp_min_call_rate, a.eigensnp_min_maf, a.eigensnp_max_hwe_p))
     qc_pass = None
     if _sample_qc_asked(a) and len(sample_ids) and int(st["keep"].sum()):
@@ -395,11 +408,52 @@ def run_eigensnp_workflow(a) -> int:
         _pcrelate(eng, a, fs, cols, sample_ids, np.asarray(scores, np.float64)[:, :a.gpca_make_pcrelate], inset, len(rows))
     if a.gpca_within is not None:
         _strat(eng, a, fs, cols, sample_ids, st)
+    l2 = _ld_score(eng, a, fs, st) if a.gpca_ld_score is not None else None
     if a.gpca_assoc_pheno is not None:
-        _assoc(eng, a, fs, cols, sample_ids, np.asarray(scores, np.float64), inset, st)
+        _assoc(eng, a, fs, cols, sample_ids, np.asarray(scores, np.float64), inset, st, l2)
     eng.close()
     _log(f"EigenSNP workflow done in {time.time() - t0:.2f}s")
     return 0
+
+
+LD_SCORE_NEEDS_RESIDENT = ("error: --gpca-ld-score needs the genotype matrix resident on the device: with the matrix walked out of core a "
+                           "window crosses the panels, and the halo of rows that needs is not implemented")
+
+
+def _ld_score(eng, a, fs, st):
+    """--gpca-ld-score WINDOW: the LD scores (gpca_ld_score, in the row bands of io.ld_bands, always unbiased; the bands added up by
+    io.ld_score_sum) of every SNP that passes the SNP QC, over every sample, into P.l2.ldscore, P.l2.M and P.l2.M_5_50.  Sets the keep
+    mask to the QC mask (mu, sigma unchanged), which ends the fit's validity.  Returns L2 [K]."""
+    from . import _lib
+    eng.set_standardization(st["mu"], st["sigma"], st["keep"])                       # every SNP that passes the SNP QC
+    rows = np.flatnonzero(st["keep"])
+    K = len(rows)
+    try:
+        win_end = gio.ld_windows([fs.chromosomes[r] for r in rows], np.asarray(fs.positions, np.int64)[rows], a.gpca_ld_score)
+    except ValueError as e:
+        raise SystemExit(f"error: --gpca-ld-score: {e} (variant indices count the SNPs that pass the SNP QC)") from None
+
+    def bands():
+        for r0, r1, wm in gio.ld_bands(win_end):
+            o = eng.ld_score(win_end[r0:r1], wmax=wm, rows=(r0, r1), unbiased=True, partners=True)
+            yield (r0, r1), o["score"], o["partners"]
+    try:
+        acc, part = gio.ld_score_sum(K, bands())
+    except _lib.GpcaError as e:
+        if e.status == _lib.GPCA_ERR_STATE:
+            raise SystemExit(LD_SCORE_NEEDS_RESIDENT) from None
+        raise
+    l2 = GpcaEngine.ld_score_total(acc)
+    counts = eng.snp_qc_detail()[0][rows]
+    maf = gio.maf_from_qc_detail(counts[:, 0], counts[:, 2], counts[:, 3])
+    _ensure_parent(a.output_prefix)
+    gio.write_ldscore(a.output_prefix, [fs.chromosomes[r] for r in rows], [fs.variant_ids[r] for r in rows],
+                      [int(fs.positions[r]) for r in rows], l2, maf)
+    mean_l2 = sum(l2.tolist()) / K if K else float("nan")
+    mean_p = int(part.sum()) / K if K else float("nan")
+    _log(f"LD scores (window {a.gpca_ld_score}) of {K} SNPs over {eng.dims()[1]} samples: mean L2 {mean_l2:.6g}, mean partners "
+         f"{mean_p:.6g}, written to {a.output_prefix}.l2.ldscore")
+    return l2
 
 
 SAMPLE_QC_NEEDS_RESIDENT = ("error: --gpca-sample-missing, --gpca-het, --gpca-mind and --gpca-het-sd need the genotype matrix resident on "
@@ -629,7 +683,7 @@ def _assoc_tables(a):
     return pheno, covar
 
 
-def _assoc(eng, a, fs, cols, sample_ids, scores, inset, st):
+def _assoc(eng, a, fs, cols, sample_ids, scores, inset, st, l2=None):
     """--gpca-assoc-pheno FILE: the linear association scan (gpca_assoc_linear) of every SNP that passes the SNP QC, in row bands, into
     P.<trait>.assoc.linear.  Runs last: it resets the keep mask to the QC mask (mu, sigma unchanged), which ends the fit's validity.
     Covariates = the first P columns of the scores the run wrote, then the columns of --gpca-assoc-covar; a sample is included when
@@ -677,6 +731,7 @@ def _assoc(eng, a, fs, cols, sample_ids, scores, inset, st):
     a1_all = np.full(len(rows), np.nan)                                              # (of every kept row, for the sets' MAF rule)
     spa_z = 2.0 if a.gpca_assoc_spa_z is None else a.gpca_assoc_spa_z
     firth_z = 1.959964 if a.gpca_assoc_firth_z is None else a.gpca_assoc_firth_z
+    ldsc = {name: np.full(len(rows), np.nan) for name in pheno.names} if a.gpca_assoc_ldsc else None     # chi2 of every trait
 
     def meta_of(r0, r1):
         rr = rows[r0:r1]
@@ -691,6 +746,8 @@ def _assoc(eng, a, fs, cols, sample_ids, scores, inset, st):
                 tt = r["t"][:, t]
                 lp = [float("nan") if v != v else lib.gpca_student_t_log10p(float(v), float(df)) for v in tt]
                 gio.write_assoc(a.output_prefix, name, *meta, r["n_obs"], r["a1_freq"], r["beta"][:, t], r["se"][:, t], tt, lp, append=bi > 0)
+                if ldsc is not None:
+                    ldsc[name][r0:r1] = tt * tt
         for t0, t1 in (gio.assoc_score_groups(len(bnames), Pc) if bnames else []):
             Yg = np.ascontiguousarray(Yb[:, t0:t1])
             for bi, (r0, r1) in enumerate(gio.assoc_score_bands(len(rows), t1 - t0, Pc)):
@@ -713,6 +770,8 @@ def _assoc(eng, a, fs, cols, sample_ids, scores, inset, st):
                         lp = [float("nan") if v != v else lib.gpca_normal_log10p(float(v)) for v in zz]
                     gio.write_assoc_logistic(a.output_prefix, bnames[t0 + t], *meta, r["n_obs"], r["a1_freq"], beta, se, zz,
                                              lp, append=bi > 0, spa=spa, firth=firth)
+                    if ldsc is not None:
+                        ldsc[bnames[t0 + t]][r0:r1] = zz * zz
         if a.gpca_assoc_set_list is not None and bnames:
             _assoc_sets(eng, a, fs, rows, a1_all, Yb, bnames, C, Pc, include, vif)
     except _lib.GpcaError as e:
@@ -724,6 +783,18 @@ def _assoc(eng, a, fs, cols, sample_ids, scores, inset, st):
     if bnames:
         _log(f"logistic score scan of {len(rows)} SNPs against {len(bnames)} case / control traits with {Pc} covariates on {n_inc} of {n} "
              f"samples, written to {a.output_prefix}.<trait>.assoc.logistic")
+    if ldsc is not None:
+        # --gpca-assoc-ldsc: one LD-score regression per trait in file order; chi2 = T_STAT^2 or the score Z_STAT^2, NaN rows drop out
+        out = []
+        for name in pheno.names:
+            try:
+                fit = GpcaEngine.ldsc_fit(ldsc[name], l2, n_inc, len(rows), n_blocks=200, chi2_max=max(0.001 * n_inc, 80.0))
+            except _lib.GpcaError:
+                fit = None
+                print(f"note: --gpca-assoc-ldsc: trait {name}: too few SNPs with a statistic, or LD scores without spread: NA", file=sys.stderr)
+            out.append((name, "LOGISTIC" if name in bnames else "LINEAR", n_inc, fit))
+        gio.write_ldsc_summary(a.output_prefix, out)
+        _log(f"LD-score regression of {len(out)} traits over {len(rows)} SNPs, written to {a.output_prefix}.ldsc.summary")
 
 
 def _assoc_sets(eng, a, fs, rows, a1_freq, Yb, bnames, C, Pc, include, vif):
@@ -930,6 +1001,17 @@ def main(argv=None) -> int:
             r2max = float("nan")
         if not 0.0 < r2max < 1.0:
             raise SystemExit("error: --gpca-indep-pairwise R2 must lie in (0, 1)")
+    if a.gpca_assoc_ldsc and (a.gpca_ld_score is None or a.gpca_assoc_pheno is None):
+        raise SystemExit("error: --gpca-assoc-ldsc needs --gpca-ld-score and --gpca-assoc-pheno")
+    if a.gpca_ld_score is not None:
+        if not a.eigensnp:
+            raise SystemExit("error: --gpca-ld-score needs the --eigensnp workflow")
+        try:
+            gio.parse_ld_window(a.gpca_ld_score)
+        except ValueError as e:
+            raise SystemExit(f"error: --gpca-ld-score: {e}") from None
+        if a.gpca_stream == "on":
+            raise SystemExit(LD_SCORE_NEEDS_RESIDENT)
     if a.gpca_project_model:
         return run_project_workflow(a)
     if a.gpca_save_model and not a.eigensnp:

@@ -331,6 +331,10 @@ void launch_ld_vec(hipStream_t st, const void* G, int packed, int64_t ldr, const
 // r2 [rows][wmax], counts [rows][wmax][6], above [rows][ld_above_words(wmax)] (each may be NULL) from the planes and the per-row sums
 void launch_ld_finish(hipStream_t st, const int* W, const unsigned* stat, int64_t N, int64_t row0, int64_t row1, const int64_t* win_end,
                       int wmax, double threshold, double* r2, int* counts, unsigned long long* above);
+// LD scores from the same planes and per-row sums (stat holds rows [row0, hi)): acc [ld_score_span] i64 += rint(v 2^40) of every counted
+// pair at its row and at its partner, partners [ld_score_span] i32 += 1 at the same two places; both zeroed by the caller
+void launch_ld_score(hipStream_t st, const int* W, const unsigned* stat, int64_t N, int64_t row0, int64_t row1, int64_t hi,
+                     const int64_t* win_end, int wmax, int weff, int unbiased, long long* acc, int* partners);
 
 // ---- PC-Relate: regression of the kept rows on the PCs, then an f32 lower-triangular SYRK over the kept rows (pcrelate.hip) ----------
 // krows [K]: original row of every kept row.  Hw [kPcrBetaWaves][N][width] f64: the hat matrix, coefficient j = wave * width + q (zero

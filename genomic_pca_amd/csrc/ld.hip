@@ -3,7 +3,8 @@
 // Per kept row and sample, from the call g: m = [missing], g' = g on an observed call (0 on a missing one), q = g'^2.  A pair i < j
 // inside the window needs sum g'_i g'_j and, where a call is missing, sum g'_i m_j, m_i g'_j, q_i m_j, m_i q_j, m_i m_j; with the
 // per-row sums of g', q and m (k_ld_vec) they give n, sum x, sum y, sum xx, sum yy, sum xy of include/gpca.h (section a10) and r^2
-// (k_ld_finish).  Every sum is an exact integer, so the bits depend on nothing but the counts.
+// (k_ld_finish).  Every sum is an exact integer, so the bits depend on nothing but the counts.  gpca_ld_score (gpca_ld_score.cpp) runs the
+// same sweep and reduces the planes to one integer sum per row instead (k_ld_score, at the end of this file).
 //
 // The sample axis is the K axis of v_mfma_i32_32x32x32_i8 and it is contiguous in both residencies, so rows go to LDS as they are
 // ([row][sample], no transpose) and a lane reads its 16 k-contiguous bytes with one ds_read_b128.  Workgroup = kLdRows kept rows
@@ -302,6 +303,92 @@ void launch_ld_finish(hipStream_t st, const int* W, const unsigned* stat, int64_
     if (row1 <= row0) return;
     const dim3 grid((unsigned)((row1 - row0) * ((ld_above_words(wmax) + 3) / 4)));
     hipLaunchKernelGGL(k_ld_finish, grid, dim3(256), 0, st, W, stat, N, row0, row1 - row0, win_end, wmax, threshold, r2, counts, above);
+}
+
+// LD scores (gpca_ld_score, gpca_ld_score.cpp; include/gpca.h section a19): the planes of a band reduced to one sum per row, no pair
+// leaving the device.  A counted pair (vx > 0, vy > 0, n > 2) is worth v = r2, or r2 - (1 - r2) / (n - 2) when unbiased, as the integer
+// q = rint(v 2^40) (half to even), added to its row AND to its partner; every sum is an integer, so neither the tiling nor the order of
+// the atomics moves a bit.
+// Workgroup = a tile of kLdScoreRows band rows (first: t0) x kLdScoreSlots slots (first: d0).  Thread p owns the partner row
+// t0 + d0 + 1 + p: in step lt it reads slot d0 + p - lt of row t0 + lt, so the threads of a step read consecutive slots of one row (the
+// six plane reads are coalesced) while the partner's sum stays in the thread's registers over the steps -- the anti-diagonal is walked
+// without a strided read and without an atomic.  The row's own sum is the step's sum over the threads: a wave reduction and one LDS
+// atomic per wave.  Count and sum travel in one 64-bit word ((1 << kLdScoreCountShift) + q per pair).  At the end of the tile every
+// touched target gets one 64-bit and one 32-bit global atomic.
+// acc [span] i64 and partners [span] i32, zeroed by the caller; nstat = the rows stat holds from row0 (every valid partner lies below).
+__device__ __forceinline__ long long ld_score_pair(const int* __restrict__ W, int64_t plane, int64_t ix, const unsigned* __restrict__ si,
+                                                   const unsigned (&sj)[3], int64_t N, int unbiased) {
+    // the six counts and r^2: a second copy of k_ld_finish's expression, kept in this file under the same compiler settings so that it
+    // rounds as that kernel does (k_ld_finish itself is left as it is)
+    const int xy = W[ix], gm = W[plane + ix], mg = W[2 * plane + ix], qm = W[3 * plane + ix], mq = W[4 * plane + ix], mm = W[5 * plane + ix];
+    const int c0 = (int)(N - si[2] - sj[2]) + mm;
+    const int c1 = (int)si[0] - gm, c2 = (int)sj[0] - mg, c3 = (int)si[1] - qm, c4 = (int)sj[1] - mq;
+    const double n = c0, sx = c1, sy = c2, sxx = c3, syy = c4, sxy = xy;
+    const double cov = n * sxy - sx * sy, vx = n * sxx - sx * sx, vy = n * syy - sy * sy;
+    if (vx <= 0.0 || vy <= 0.0 || n <= 2.0) return 0;
+    const double r2 = (cov * cov) / (vx * vy);
+    {
+#pragma clang fp contract(off)
+        const double v = unbiased ? r2 - (1.0 - r2) / (n - 2.0) : r2;
+        return (1ll << kLdScoreCountShift) + __double2ll_rn(v * 1099511627776.0);
+    }
+}
+// (count, sum) of a packed word: the sum is the low kLdScoreCountShift bits, signed
+__device__ __forceinline__ void ld_score_unpack(long long s, int& count, long long& sum) {
+    const long long half = 1ll << (kLdScoreCountShift - 1);
+    sum = ((s + half) & ((1ll << kLdScoreCountShift) - 1)) - half;
+    count = (int)((s - sum) >> kLdScoreCountShift);
+}
+__global__ __launch_bounds__(kLdScoreThreads) void k_ld_score(const int* __restrict__ W, const unsigned* __restrict__ stat, int64_t N,
+                                                              int64_t row0, int64_t rows, int64_t nstat, const int64_t* __restrict__ win_end,
+                                                              int wmax, int64_t nrt, int unbiased, long long* __restrict__ acc,
+                                                              int* __restrict__ partners) {
+    __shared__ unsigned long long self[kLdScoreRows];
+    const int p = threadIdx.x, lane = p & 63;
+    const int64_t t0 = ((int64_t)blockIdx.x % nrt) * kLdScoreRows, d0 = ((int64_t)blockIdx.x / nrt) * kLdScoreSlots;
+    if (p < kLdScoreRows) self[p] = 0ull;
+    __syncthreads();
+    const int64_t jr = t0 + d0 + 1 + p;                    // the thread's partner row, from row0
+    const int64_t plane = rows * (int64_t)wmax;
+    unsigned sj[3] = {0u, 0u, 0u};
+    if (jr < nstat) { sj[0] = stat[3 * jr]; sj[1] = stat[3 * jr + 1]; sj[2] = stat[3 * jr + 2]; }
+    const int nlt = rows - t0 < kLdScoreRows ? (int)(rows - t0) : kLdScoreRows;
+    long long part = 0;
+    for (int lt = 0; lt < nlt; ++lt) {
+        const int64_t t = t0 + lt;
+        const int dl = p - lt;
+        const int64_t d = d0 + dl;
+        const bool valid = dl >= 0 && dl < kLdScoreSlots && d < wmax && jr < nstat && row0 + jr < win_end[t];
+        long long add = 0;
+        if (valid) add = ld_score_pair(W, plane, t * wmax + d, stat + 3 * t, sj, N, unbiased);
+        part += add;
+        if (__builtin_amdgcn_ballot_w64(add != 0) != 0ull) {                 // wave-uniform
+            long long s = add;
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o);
+            if (lane == 0) atomicAdd(&self[lt], (unsigned long long)s);
+        }
+    }
+    __syncthreads();
+    int cnt;
+    long long sum;
+    if (part != 0) {
+        ld_score_unpack(part, cnt, sum);
+        atomicAdd(reinterpret_cast<unsigned long long*>(acc) + jr, (unsigned long long)sum);
+        atomicAdd(partners + jr, cnt);
+    }
+    if (p < nlt && self[p] != 0ull) {
+        ld_score_unpack((long long)self[p], cnt, sum);
+        atomicAdd(reinterpret_cast<unsigned long long*>(acc) + t0 + p, (unsigned long long)sum);
+        atomicAdd(partners + t0 + p, cnt);
+    }
+}
+void launch_ld_score(hipStream_t st, const int* W, const unsigned* stat, int64_t N, int64_t row0, int64_t row1, int64_t hi,
+                     const int64_t* win_end, int wmax, int weff, int unbiased, long long* acc, int* partners) {
+    if (row1 <= row0 || weff <= 0) return;
+    const int64_t rows = row1 - row0, nrt = ld_score_row_tiles(rows);
+    const dim3 grid((unsigned)ld_score_grid(rows, weff));
+    hipLaunchKernelGGL(k_ld_score, grid, dim3(kLdScoreThreads), 0, st, W, stat, N, row0, rows, hi - row0, win_end, wmax, nrt, unbiased, acc, partners);
 }
 
 }  // namespace gpca

@@ -247,6 +247,24 @@ inline int64_t ld_r2_capacity(int64_t rows, int64_t wmax) { return rows * wmax; 
 inline int64_t ld_counts_capacity(int64_t rows, int64_t wmax) { return 6 * rows * wmax; }
 inline int64_t ld_above_capacity(int64_t rows, int64_t wmax) { return rows * ld_above_words(wmax); }
 
+// ---- LD scores from the product planes of the banded sweep (k_ld_score in ld.hip, gpca_ld_score.cpp) -----------------------------
+// A workgroup owns a tile of kLdScoreRows band rows x kLdScoreSlots slots of the planes.  Thread p owns the partner row
+// t0 + d0 + 1 + p of the tile (an anti-diagonal: kLdScoreRows + kLdScoreSlots - 1 of them) and walks the tile's rows, so in every
+// step the threads read consecutive slots of one row.
+constexpr int kLdScoreRows = 64, kLdScoreSlots = 256;
+constexpr int kLdScoreThreads = kLdScoreRows + kLdScoreSlots;              // 320 = 5 waves; the last thread owns no partner
+constexpr int kLdScoreMaxWmax = 1 << 20;                                  // 2 wmax pairs of at most 2^41 each stay below 2^63
+// a pair adds (1 << kLdScoreCountShift) + q, |q| <= 2^40, to a 64-bit sum of at most kLdScoreSlots pairs: count and sum in one word
+constexpr int kLdScoreCountShift = 50;
+inline int64_t ld_score_row_tiles(int64_t rows) { return (rows + kLdScoreRows - 1) / kLdScoreRows; }
+inline int64_t ld_score_slot_tiles(int64_t weff) { return (weff + kLdScoreSlots - 1) / kLdScoreSlots; }
+inline int64_t ld_score_grid(int64_t rows, int64_t weff) { return ld_score_row_tiles(rows) * ld_score_slot_tiles(weff); }
+// rows that a band's sums reach, from row0: its own rows and the partners of its windows
+inline int64_t ld_score_span(int64_t K, int64_t row0, int64_t row1, int64_t wmax) { return std::min(K, row1 + wmax) - row0; }
+// elements of acc (i64) and partners (i32)
+inline int64_t ld_score_acc_capacity(int64_t K, int64_t row0, int64_t row1, int64_t wmax) { return ld_score_span(K, row0, row1, wmax); }
+inline int64_t ld_score_partners_capacity(int64_t K, int64_t row0, int64_t row1, int64_t wmax) { return ld_score_span(K, row0, row1, wmax); }
+
 // ---- PC-Relate (pcrelate.hip, gpca_pcrelate.cpp) ---------------------------------------------------------------------------------
 // A workgroup owns one kPcrTile x kPcrTile tile of the sample triangle (tile row >= tile column) and walks the kept rows in stages of
 // kPcrStageRows; the f32 partial sums go to f64 running sums once per kPcrFlushRows kept rows, counted from the first kept row.

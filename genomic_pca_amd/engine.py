@@ -451,6 +451,69 @@ class GpcaEngine:
             res["above"] = out_ab[:n]
         return res
 
+    def ld_score(self, win_end, wmax: Optional[int] = None, rows: Optional[Tuple[int, int]] = None, unbiased: bool = True,
+                 partners: bool = False) -> dict:
+        """LD scores of a band from the windowed-LD sweep (gpca_ld_score; gpca.h section a19), with ld_window's addressing: no pair
+        leaves the device.  Returns {"score": int64 [span]} and, with partners=True, {"partners": int32 [span]}, span =
+        min(K, row1 + wmax) - row0 entries from row0: the sum of rint(v 2^40) over the counted pairs of the band that hold the row (on
+        either side), v = r2 - (1 - r2) / (n - 2) (unbiased) or r2, and the number of those pairs.  Exact integers, written per call:
+        the caller adds its bands at their row0 (io.ld_score_sum)."""
+        K = int(self._lib.gpca_num_pca_snps(self._h))
+        r0, r1 = (0, K) if rows is None else (int(rows[0]), int(rows[1]))
+        we = np.ascontiguousarray(win_end, np.int64)
+        n = max(r1 - r0, 0)
+        if we.shape != (n,):
+            raise ValueError("win_end must have one entry per row of the band")
+        if wmax is None:
+            wmax = max(int(np.max(we - np.arange(r0, r1) - 1)) if n else 1, 1)
+        wmax = int(wmax)
+        span = max(min(K, r1 + max(wmax, 0)) - r0, 0) if n else 0
+        score = np.zeros(max(span, 1), np.int64)
+        part = np.zeros(max(span, 1), np.int32) if partners else None
+        self._chk(self._lib.gpca_ld_score(self._h, r0, r1, _vp(we), wmax, _lib.LDSCORE_UNBIASED if unbiased else 0, _vp(score), _vp(part)))
+        res = {"score": score[:span]}
+        if partners:
+            res["partners"] = part[:span]
+        return res
+
+    @staticmethod
+    def ld_score_total(acc) -> np.ndarray:
+        """L2 of every SNP (gpca_ld_score_total; host only): 1 + acc 2^-40 from the bands' scores added up (io.ld_score_sum); the 1 is
+        the SNP with itself."""
+        av = np.ascontiguousarray(acc, np.int64)
+        if av.ndim != 1:
+            raise ValueError("acc must be a vector of int64 sums")
+        out = np.zeros(max(av.size, 1))
+        lib = _lib.load()
+        rc = lib.gpca_ld_score_total(_vp(av if av.size else np.zeros(1, np.int64)), av.size, _vp(out))
+        if rc != 0:
+            raise GpcaError(rc, "gpca_ld_score_total: " + lib.gpca_status_string(rc).decode())
+        return out[:av.size]
+
+    LDSC_FIELDS = ("m_used", "mean_chi2", "lambda_gc", "intercept", "intercept_se", "h2", "h2_se", "ratio", "ratio_se", "n_blocks")
+
+    @staticmethod
+    def ldsc_fit(chi2, ell, n_samples: float, M: float, w_ell=None, n_blocks: int = 200, chi2_max: Optional[float] = None) -> dict:
+        """LD-score regression of chi2 on the LD scores ell (gpca_ldsc_fit; host only; the rule is written out in gpca.h section a19):
+        iteratively reweighted least squares with a delete-one block jackknife.  Returns a dict of LDSC_FIELDS (m_used and n_blocks as
+        int).  chi2_max None or 0: no cap."""
+        cv = np.ascontiguousarray(chi2, np.float64)
+        lv = np.ascontiguousarray(ell, np.float64)
+        wv = None if w_ell is None else np.ascontiguousarray(w_ell, np.float64)
+        if cv.ndim != 1 or lv.shape != cv.shape or (wv is not None and wv.shape != cv.shape):
+            raise ValueError("chi2, ell and w_ell must be vectors of one length")
+        out = np.zeros(10)
+        one = np.zeros(1)
+        lib = _lib.load()
+        m = cv.size
+        rc = lib.gpca_ldsc_fit(_vp(cv if m else one), _vp(lv if m else one), _vp(wv if (wv is None or m) else one), m, float(n_samples), float(M),
+                               int(n_blocks), float(chi2_max or 0.0), _vp(out))
+        if rc != 0:
+            raise GpcaError(rc, "gpca_ldsc_fit: " + lib.gpca_status_string(rc).decode())
+        res = dict(zip(GpcaEngine.LDSC_FIELDS, (float(v) for v in out)))
+        res["m_used"], res["n_blocks"] = int(out[0]), int(out[9])
+        return res
+
     def _pcr_args(self, pcs, train):
         N = self.dims()[1]
         V = np.ascontiguousarray(np.zeros((N, 0)) if pcs is None else pcs, np.float64)

@@ -765,6 +765,67 @@ inline void write_prune_ids(const std::string& prefix, const std::vector<std::st
     }
 }
 
+// ---- LD scores and LD-score regression: the twins of io.ld_score_sum, io.write_ldscore and io.write_ldsc_summary (same rules,
+// byte-identical files) -----------------------------------------------------------------------------------------------------------
+// adds one band of gpca_ld_score (its span from row0: score and, when not null, partners) into the K-long sums
+inline void ld_score_add_band(std::vector<int64_t>& acc, std::vector<int64_t>& part, int64_t row0, const std::vector<int64_t>& score,
+                              const std::vector<int32_t>* partners) {
+    if (row0 < 0 || (size_t)row0 + score.size() > acc.size() || part.size() != acc.size())
+        throw std::runtime_error("ld_score_sum: the band at row " + std::to_string(row0) + " holds " + std::to_string(score.size()) + " sums, " +
+                                 std::to_string(acc.size()) + " rows are there");
+    if (partners && partners->size() != score.size()) throw std::runtime_error("ld_score_sum: partners and score of a band have one length");
+    for (size_t t = 0; t < score.size(); ++t) {
+        acc[(size_t)row0 + t] += score[t];
+        if (partners) part[(size_t)row0 + t] += (*partners)[t];
+    }
+}
+
+inline std::string g6_or_na(double v) {
+    char b[48];
+    if (v != v) return "NA";
+    std::snprintf(b, sizeof b, "%.6g", v);
+    return b;
+}
+
+// P.l2.ldscore (tab-separated, header `CHR SNP BP L2`, L2 as %.6g: ldsc's column layout), P.l2.M (the number of SNPs summed over) and
+// P.l2.M_5_50 (those with MAF > 0.05)
+inline void write_ldscore(const std::string& prefix, const std::vector<std::string>& chromosomes, const std::vector<std::string>& ids,
+                          const std::vector<int64_t>& positions, const std::vector<double>& l2, const std::vector<double>& maf) {
+    const size_t n = ids.size();
+    if (chromosomes.size() != n || positions.size() != n || l2.size() != n || maf.size() != n)
+        throw std::runtime_error("write_ldscore: one entry per SNP in every column");
+    ensure_parent(prefix);
+    {
+        OutFile o(prefix + ".l2.ldscore");
+        std::fputs("CHR\tSNP\tBP\tL2\n", o.f);
+        for (size_t i = 0; i < n; ++i)
+            std::fprintf(o.f, "%s\t%s\t%lld\t%s\n", chromosomes[i].c_str(), ids[i].c_str(), (long long)positions[i], g6_or_na(l2[i]).c_str());
+    }
+    long long common = 0;
+    for (double m : maf) common += m > 0.05;
+    { OutFile o(prefix + ".l2.M"); std::fprintf(o.f, "%zu\n", n); }
+    { OutFile o(prefix + ".l2.M_5_50"); std::fprintf(o.f, "%lld\n", common); }
+}
+
+// P.ldsc.summary: one tab-separated line per trait; fit = the ten values of gpca_ldsc_fit, or empty where the regression was refused
+// (its numbers are NA then).  N and M_USED are integers, the others %.6g, NaN as NA.
+struct LdscRow { std::string trait, test; int64_t n; std::vector<double> fit; };
+inline void write_ldsc_summary(const std::string& prefix, const std::vector<LdscRow>& rows) {
+    ensure_parent(prefix);
+    OutFile o(prefix + ".ldsc.summary");
+    std::fputs("#TRAIT\tTEST\tN\tM_USED\tMEAN_CHI2\tLAMBDA_GC\tINTERCEPT\tINTERCEPT_SE\tH2\tH2_SE\tRATIO\tRATIO_SE\n", o.f);
+    for (const LdscRow& r : rows) {
+        if (r.test != "LINEAR" && r.test != "LOGISTIC") throw std::runtime_error("write_ldsc_summary: TEST is LINEAR or LOGISTIC, not '" + r.test + "'");
+        std::fprintf(o.f, "%s\t%s\t%lld", r.trait.c_str(), r.test.c_str(), (long long)r.n);
+        if (r.fit.size() != 10) { for (int k = 0; k < 9; ++k) std::fputs("\tNA", o.f); }
+        else {
+            std::fprintf(o.f, "\t%lld", (long long)r.fit[0]);
+            for (int k = 1; k <= 8; ++k) std::fprintf(o.f, "\t%s", g6_or_na(r.fit[(size_t)k]).c_str());
+        }
+        std::fputs("\n", o.f);
+    }
+}
+
 // ---- linear association scan: the twins of io.read_pheno, io.align_pheno, io.assoc_bands and io.write_assoc (same rules, same error
 // texts, byte-identical files) --------------------------------------------------------------------------------------------------------
 struct PhenoTable {

@@ -55,6 +55,8 @@ struct Args {
     bool have_indep = false;          // --gpca-indep-pairwise WINDOW R2: LD pruning of the kept SNPs before the GRM, KING and the PCA
     std::string indep_window, indep_r2_text;
     double indep_r2 = 0.0;
+    std::string ld_score;             // --gpca-ld-score WINDOW: the LD score of every SNP that passes the SNP QC, after the PCA outputs
+    bool assoc_ldsc = false;          // --gpca-assoc-ldsc: LD-score regression of every trait's scan statistics on those LD scores
     std::string assoc_pheno, assoc_covar;   // --gpca-assoc-pheno FILE (turns the association scan on), --gpca-assoc-covar FILE
     bool have_assoc_pcs = false, have_assoc_vif = false;
     bool assoc_logistic = false;      // --gpca-assoc-logistic: binary trait columns go through the logistic score scan
@@ -143,6 +145,15 @@ void print_help() {
         "                                       SNPs where both samples are observed\n"
         "      --gpca-grm-scaling <S>           --gpca-make-grm: standardized ((g - mean) / s.d., the matrix the PCA factorises) or\n"
         "                                       centred (g - mean) [default: standardized]\n"
+        "      --gpca-ld-score <WINDOW>         EigenSNP workflow: after the PCA outputs, the LD score of every SNP that passes the SNP QC:\n"
+        "                                       L2 = 1 + the sum of the bias-adjusted unphased r^2 with the SNPs of its chromosome at most\n"
+        "                                       WINDOW away on both sides (the grammar of --gpca-indep-pairwise's WINDOW; 1000kb is the\n"
+        "                                       recommendation), summed on the device -> P.l2.ldscore (CHR SNP BP L2), P.l2.M, P.l2.M_5_50.\n"
+        "                                       Every sample enters, relatives and samples that fail the sample QC included.  Needs the\n"
+        "                                       matrix resident on the device\n"
+        "      --gpca-assoc-ldsc                --gpca-ld-score and --gpca-assoc-pheno: LD-score regression of every trait's scan statistics\n"
+        "                                       (T_STAT^2 or Z_STAT^2) on the LD scores, 200 jackknife blocks -> P.ldsc.summary.  The intercept\n"
+        "                                       measures confounding, H2 the SNP heritability (case / control: on the observed scale)\n"
         "      --gpca-indep-pairwise <WINDOW> <R2>  EigenSNP workflow: prune SNPs in linkage disequilibrium before the GRM, KING and the PCA\n"
         "                                       (plink's --indep-pairwise, step 1).  WINDOW = a variant count such as 50 or a span such as\n"
         "                                       250kb; 0 < R2 < 1.  Of a pair of kept SNPs with unphased r^2 > R2 the one with the smaller\n"
@@ -325,6 +336,8 @@ Args parse(int argc, char** argv) {
         else if (f == "--gpca-het-sd") { a.het_sd = to_f64(f, val()); a.have_het_sd = true; }
         else if (f == "--gpca-assoc-pcs") { a.assoc_pcs = to_i64(f, val()); a.have_assoc_pcs = true; }
         else if (f == "--gpca-assoc-vif") { a.assoc_vif = to_f64(f, val()); a.have_assoc_vif = true; }
+        else if (f == "--gpca-ld-score") a.ld_score = val();
+        else if (f == "--gpca-assoc-ldsc") a.assoc_ldsc = true;
         else if (f == "--gpca-indep-pairwise") {
             a.indep_window = val();
             if (i + 1 >= argc) usage_error("two values (WINDOW R2) are required for '" + f + "'");
@@ -531,6 +544,62 @@ int run_strat(gpca::Engine& eng, const Args& a, const gpca_host::PlinkFileset& f
     return 0;
 }
 
+const char* const kLdScoreNeedsResident =
+    "error: --gpca-ld-score needs the genotype matrix resident on the device: with the matrix walked out of core a window crosses the "
+    "panels, and the halo of rows that needs is not implemented\n";
+
+// --gpca-ld-score WINDOW: the LD scores (gpca_ld_score, in the row bands of ld_next_band, always unbiased; the bands added up) of every
+// SNP that passes the SNP QC, over every sample, into P.l2.ldscore, P.l2.M and P.l2.M_5_50.  Sets the keep mask to the QC mask (mu, sigma
+// unchanged), which ends the fit's validity.  l2 receives L2 [K] (cli.py:_ld_score).
+int run_ld_score(gpca::Engine& eng, const Args& a, const gpca_host::PlinkFileset& fs, const gpca::SnpStats& st, std::vector<double>& l2) {
+    eng.set_standardization(st.mu, st.sigma, st.keep);                                // every SNP that passes the SNP QC
+    std::vector<int64_t> rows, pos;
+    std::vector<std::string> chrom, ids;
+    for (size_t i = 0; i < st.keep.size(); ++i)
+        if (st.keep[i]) { rows.push_back((int64_t)i); chrom.push_back(fs.chromosomes[i]); pos.push_back(fs.positions[i]); ids.push_back(fs.variant_ids[i]); }
+    const int64_t K = (int64_t)rows.size();
+    std::vector<int64_t> win_end;
+    try { win_end = gpca_host::ld_windows(chrom, pos, a.ld_score); }
+    catch (const std::runtime_error& e) {
+        std::fprintf(stderr, "error: --gpca-ld-score: %s (variant indices count the SNPs that pass the SNP QC)\n", e.what());
+        return 1;
+    }
+    std::vector<int64_t> acc((size_t)K, 0), part((size_t)K, 0);
+    for (int64_t r0 = 0; r0 < K;) {
+        int64_t r1 = 0, wm = 1;
+        gpca_host::ld_next_band(win_end, r0, (int64_t)1 << 26, r1, wm);
+        const std::vector<int64_t> we(win_end.begin() + r0, win_end.begin() + r1);
+        std::vector<int64_t> score;
+        std::vector<int32_t> partners;
+        try { eng.ld_score(r0, r1, we, (int32_t)wm, true, score, &partners); }
+        catch (const gpca::Error& e) {
+            if (e.status() != GPCA_ERR_STATE) throw;
+            std::fputs(kLdScoreNeedsResident, stderr);
+            return 1;
+        }
+        gpca_host::ld_score_add_band(acc, part, r0, score, &partners);
+        r0 = r1;
+    }
+    l2 = gpca::Engine::ld_score_total(acc);
+    const std::vector<uint32_t> counts = eng.snp_qc_counts();
+    std::vector<double> maf((size_t)K);
+    for (size_t t = 0; t < (size_t)K; ++t) {
+        const uint32_t* c = counts.data() + 4 * (size_t)rows[t];
+        maf[t] = gpca_host::maf_from_counts(c[0], c[2], c[3]);
+    }
+    gpca_host::write_ldscore(a.output_prefix, chrom, ids, pos, l2, maf);
+    double sum_l2 = 0.0;
+    long long sum_p = 0;
+    for (double v : l2) sum_l2 += v;
+    for (int64_t v : part) sum_p += v;
+    char buf[512];
+    std::snprintf(buf, sizeof buf, "LD scores (window %s) of %lld SNPs over %lld samples: mean L2 %.6g, mean partners %.6g, written to %s.l2.ldscore",
+                  a.ld_score.c_str(), (long long)K, (long long)eng.dims().second, K ? sum_l2 / (double)K : std::nan(""), K ? (double)sum_p / (double)K : std::nan(""),
+                  a.output_prefix.c_str());
+    logmsg(buf);
+    return 0;
+}
+
 const char* const kAssocNeedsResident =
     "error: --gpca-assoc-pheno needs the genotype matrix resident on the device: the scan of a matrix walked out of core is not implemented\n";
 constexpr int64_t kAssocMaxColumns = 64;
@@ -607,7 +676,7 @@ void run_assoc_sets(gpca::Engine& eng, const Args& a, const gpca_host::PlinkFile
 // trait and covariate is present for it and it is in the KING in-set, when there is one (cli.py:_assoc).  scores is [n][kc].
 int run_assoc(gpca::Engine& eng, const Args& a, const gpca_host::PlinkFileset& fs, const std::vector<std::string>& fids,
               const std::vector<std::string>& sample_ids, const std::vector<double>& scores, int kc, const std::vector<uint8_t>& inset,
-              const gpca::SnpStats& st) {
+              const gpca::SnpStats& st, const std::vector<double>& l2) {
     const int64_t n = (int64_t)sample_ids.size();
     const int32_t P = a.have_assoc_pcs ? (int32_t)a.assoc_pcs : (int32_t)kc;
     const int32_t T = (int32_t)a.assoc_pheno_table.names.size(), nc = a.assoc_covar.empty() ? 0 : (int32_t)a.assoc_covar_table.names.size();
@@ -673,6 +742,9 @@ int run_assoc(gpca::Engine& eng, const Args& a, const gpca_host::PlinkFileset& f
     for (size_t i = 0; i < st.keep.size(); ++i) if (st.keep[i]) rows.push_back((int64_t)i);
     gpca_host::ensure_parent(a.output_prefix);
     std::vector<double> a1_all(rows.size(), std::nan(""));                            // (of every kept row, for the sets' MAF rule)
+    // --gpca-assoc-ldsc: chi2 of every trait over the rows (NaN where there is no statistic), the quantitative traits first
+    std::vector<std::vector<double>> chi2q, chi2b;
+    if (a.assoc_ldsc) { chi2q.assign((size_t)Tq, std::vector<double>(rows.size(), std::nan(""))); chi2b.assign((size_t)Tb, std::vector<double>(rows.size(), std::nan(""))); }
     try {
         if (a.assoc_cc_freq && Tb) {
             // --gpca-assoc-cc-freq: the counts among the controls and the cases of every case / control trait, over the scan's include
@@ -707,6 +779,7 @@ int run_assoc(gpca::Engine& eng, const Args& a, const gpca_host::PlinkFileset& f
                         const double* s3 = &stats[(i * (size_t)Tq + (size_t)t) * 3];
                         const double lp = s3[2] != s3[2] ? std::nan("") : gpca_student_t_log10p(s3[2], (double)df);
                         w[(size_t)t]->add_row(fs.chromosomes[o], fs.positions[o], fs.variant_ids[o], fs.allele1[o], info[4 * i], info[4 * i + 1], s3[0], s3[1], s3[2], lp);
+                        if (a.assoc_ldsc) chi2q[(size_t)t][(size_t)r] = s3[2] * s3[2];
                     }
                 }
             }
@@ -735,6 +808,7 @@ int run_assoc(gpca::Engine& eng, const Args& a, const gpca_host::PlinkFileset& f
                             const bool fy = f5 && f5[1] == 1.0;                     // (corrected: BETA and SE are Firth's)
                             w[(size_t)t]->add_row(fs.chromosomes[o], fs.positions[o], fs.variant_ids[o], fs.allele1[o], info[5 * i], info[5 * i + 1],
                                                   fy ? f5[2] : s5[0], fy ? f5[3] : s5[1], s5[2], lp, f5 ? (int)f5[1] : (s4 ? (int)s4[1] : 0));
+                            if (a.assoc_ldsc) chi2b[(size_t)g.first + (size_t)t][(size_t)r] = s5[2] * s5[2];
                         }
                     }
                 }
@@ -753,6 +827,24 @@ int run_assoc(gpca::Engine& eng, const Args& a, const gpca_host::PlinkFileset& f
     if (Tb) {
         std::snprintf(buf, sizeof buf, "logistic score scan of %zu SNPs against %d case / control traits with %d covariates on %lld of %lld samples, written to %s.<trait>.assoc.logistic",
                       rows.size(), (int)Tb, (int)Pc, (long long)n_inc, (long long)n, a.output_prefix.c_str());
+        logmsg(buf);
+    }
+    if (a.assoc_ldsc) {
+        // one LD-score regression per trait in file order; chi2 = T_STAT^2 or the score Z_STAT^2, NaN rows drop out (cli.py:_assoc)
+        std::vector<gpca_host::LdscRow> out;
+        for (const std::string& name : a.assoc_pheno_table.names) {
+            const auto qb = std::find(bnames.begin(), bnames.end(), name);
+            const bool bin = qb != bnames.end();
+            const std::vector<double>& c2 = bin ? chi2b[(size_t)(qb - bnames.begin())] : chi2q[(size_t)(std::find(names.begin(), names.end(), name) - names.begin())];
+            gpca_host::LdscRow row{name, bin ? "LOGISTIC" : "LINEAR", n_inc, {}};
+            try { row.fit = gpca::Engine::ldsc_fit(c2, l2, (double)n_inc, (double)rows.size(), nullptr, 200, std::max(0.001 * (double)n_inc, 80.0)); }
+            catch (const gpca::Error&) {
+                std::fprintf(stderr, "note: --gpca-assoc-ldsc: trait %s: too few SNPs with a statistic, or LD scores without spread: NA\n", name.c_str());
+            }
+            out.push_back(row);
+        }
+        gpca_host::write_ldsc_summary(a.output_prefix, out);
+        std::snprintf(buf, sizeof buf, "LD-score regression of %zu traits over %zu SNPs, written to %s.ldsc.summary", out.size(), rows.size(), a.output_prefix.c_str());
         logmsg(buf);
     }
     return 0;
@@ -854,6 +946,7 @@ int run_eigensnp_workflow(Args a) {
     if (streamed && !a.assoc_pheno.empty()) { std::fputs(kAssocNeedsResident, stderr); return 1; }
     if (streamed && !a.within.empty()) { std::fputs(kStratNeedsResident, stderr); return 1; }
     if (streamed && a.sample_qc_asked()) { std::fputs(kSampleQcNeedsResident, stderr); return 1; }
+    if (streamed && !a.ld_score.empty()) { std::fputs(kLdScoreNeedsResident, stderr); return 1; }
     const gpca::SnpStats st = eng.snp_stats(gpca::QcConfig{a.min_call_rate, a.min_maf, a.max_hwe_p});
     std::vector<uint8_t> qc_pass;                                                                                       // empty: no sample filter
     if (a.sample_qc_asked() && !sample_ids.empty() && std::count(st.keep.begin(), st.keep.end(), (uint8_t)1) > 0) {
@@ -1092,12 +1185,17 @@ int run_eigensnp_workflow(Args a) {
         const int rc = run_strat(eng, a, fs, fids, sample_ids, st);
         if (rc) return rc;
     }
+    std::vector<double> l2;
+    if (!a.ld_score.empty()) {
+        const int rc = run_ld_score(eng, a, fs, st, l2);
+        if (rc) return rc;
+    }
     if (!a.assoc_pheno.empty()) {
         std::vector<std::string> fids = fs.family_ids;
         if (use_kept) { fids.clear(); for (int64_t c : kept.cols) fids.push_back(fs.family_ids[(size_t)c]); }
         std::vector<double> scores = projected;
         if (inset.empty()) scores.assign(out.final_sample_principal_component_scores.begin(), out.final_sample_principal_component_scores.end());
-        const int rc = run_assoc(eng, a, fs, fids, sample_ids, scores, kc, inset, st);
+        const int rc = run_assoc(eng, a, fs, fids, sample_ids, scores, kc, inset, st, l2);
         if (rc) return rc;
     }
     std::snprintf(buf, sizeof buf, "EigenSNP workflow done in %.2fs", seconds_since(t0));
@@ -1273,6 +1371,16 @@ int main(int argc, char** argv) {
                 try { gpca_host::read_set_list(a.assoc_set_list, {}); }
                 catch (const std::runtime_error& e) { std::fprintf(stderr, "error: --gpca-assoc-set-list: %s\n", e.what()); return 2; }
             }
+        }
+        if (a.assoc_ldsc && (a.ld_score.empty() || a.assoc_pheno.empty())) {
+            std::fprintf(stderr, "error: --gpca-assoc-ldsc needs --gpca-ld-score and --gpca-assoc-pheno\n");
+            return 2;
+        }
+        if (!a.ld_score.empty()) {
+            if (!a.eigensnp) { std::fprintf(stderr, "error: --gpca-ld-score needs the --eigensnp workflow\n"); return 2; }
+            try { gpca_host::parse_ld_window(a.ld_score); }
+            catch (const std::runtime_error& e) { std::fprintf(stderr, "error: --gpca-ld-score: %s\n", e.what()); return 2; }
+            if (a.stream == "on") { std::fputs(kLdScoreNeedsResident, stderr); return 2; }
         }
         if (!a.project_model.empty()) return run_project_workflow(a);
         if (a.save_model && !a.eigensnp) { std::fprintf(stderr, "error: --gpca-save-model needs the --eigensnp workflow\n"); return 2; }

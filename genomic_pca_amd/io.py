@@ -798,6 +798,74 @@ def write_assoc(prefix: str, trait: str, chromosomes: Sequence[str], positions: 
     return path
 
 
+# ---- LD scores and LD-score regression (gpca_ld_score, gpca_ld_score_total, gpca_ldsc_fit; include/gpca.h section a19) -----------
+def ld_score_sum(K: int, bands):
+    """(acc int64 [K], partners int64 [K]) = the bands of GpcaEngine.ld_score added up.  bands: ((row0, row1), score[, partners]) over
+    the bands of ld_bands, in any order; score (and partners) hold the band's span from row0, which reaches past row1 into the rows of
+    the next bands.  partners stays 0 where no band gives one."""
+    K = int(K)
+    acc = np.zeros(K, np.int64)
+    part = np.zeros(K, np.int64)
+    for band in bands:
+        (r0, r1), score = band[0], np.asarray(band[1])
+        r0 = int(r0)
+        if score.ndim != 1 or score.dtype.kind not in "iu" or r0 < 0 or r0 + score.size > K:
+            raise ValueError(f"ld_score_sum: the band ({r0}, {int(r1)}) holds {score.size} sums from row {r0}, {K} rows are there")
+        acc[r0:r0 + score.size] += score.astype(np.int64)
+        if len(band) > 2 and band[2] is not None:
+            pv = np.asarray(band[2])
+            if pv.shape != score.shape:
+                raise ValueError("ld_score_sum: partners and score of a band have one length")
+            part[r0:r0 + pv.size] += pv.astype(np.int64)
+    return acc, part
+
+
+def write_ldscore(prefix: str, chromosomes: Sequence[str], ids: Sequence[str], positions: Sequence[int], l2, maf) -> List[str]:
+    """P.l2.ldscore: tab-separated, header `CHR SNP BP L2`, one line per SNP, L2 as %.6g (ldsc's column layout); P.l2.M: the number of
+    SNPs summed over; P.l2.M_5_50: those with MAF > 0.05."""
+    n = len(ids)
+    for a in (chromosomes, positions, l2, maf):
+        if len(a) != n:
+            raise ValueError("write_ldscore: one entry per SNP in every column")
+    d = os.path.dirname(prefix)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    paths = [f"{prefix}.l2.ldscore", f"{prefix}.l2.M", f"{prefix}.l2.M_5_50"]
+    with open(paths[0], "w") as f:
+        f.write("CHR\tSNP\tBP\tL2\n")
+        f.writelines(f"{chromosomes[i]}\t{ids[i]}\t{int(positions[i])}\t{_g6(l2[i])}\n" for i in range(n))
+    with open(paths[1], "w") as f:
+        f.write(f"{n}\n")
+    with open(paths[2], "w") as f:
+        f.write(f"{int(np.count_nonzero(np.asarray(maf, np.float64) > 0.05))}\n")
+    return paths
+
+
+LDSC_SUMMARY_HEADER = "#TRAIT\tTEST\tN\tM_USED\tMEAN_CHI2\tLAMBDA_GC\tINTERCEPT\tINTERCEPT_SE\tH2\tH2_SE\tRATIO\tRATIO_SE\n"
+
+
+def write_ldsc_summary(prefix: str, rows) -> str:
+    """P.ldsc.summary: one tab-separated line per trait, `#TRAIT TEST N M_USED MEAN_CHI2 LAMBDA_GC INTERCEPT INTERCEPT_SE H2 H2_SE RATIO
+    RATIO_SE`.  rows: (trait, test, n, fit) with test = LINEAR or LOGISTIC, n = the samples of the scan and fit = the dict of
+    GpcaEngine.ldsc_fit, or None where the regression was refused (its numbers are NA then).  N and M_USED are integers, the others
+    %.6g, NaN as NA."""
+    path = f"{prefix}.ldsc.summary"
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    keys = ("mean_chi2", "lambda_gc", "intercept", "intercept_se", "h2", "h2_se", "ratio", "ratio_se")
+    with open(path, "w") as f:
+        f.write(LDSC_SUMMARY_HEADER)
+        for trait, test, n, fit in rows:
+            if test not in ("LINEAR", "LOGISTIC"):
+                raise ValueError(f"write_ldsc_summary: TEST is LINEAR or LOGISTIC, not '{test}'")
+            if fit is None:
+                f.write(f"{trait}\t{test}\t{int(n)}\tNA" + "\tNA" * len(keys) + "\n")
+            else:
+                f.write(f"{trait}\t{test}\t{int(n)}\t{int(fit['m_used'])}\t" + "\t".join(_g6(fit[k]) for k in keys) + "\n")
+    return path
+
+
 def binary_trait(values):
     """None, or the 0 / 1 recoding (1 = case, NaN stays NaN) of a trait column that is binary: its present (non-NaN) values are exactly
     {0, 1} (1 = case) or exactly {1, 2} (plink's coding, 2 = case).  A column with one class only is not binary."""

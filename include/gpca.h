@@ -740,6 +740,56 @@ GPCA_API int gpca_sample_counts(gpca_handle* h, int64_t row0, int64_t row1, cons
 GPCA_API int gpca_het_weights(const uint32_t* qc /* [rows][4] */, int64_t rows, uint32_t* q /* [rows] */);
 GPCA_API int gpca_sample_het(const uint32_t* counts /* [N][3] */, const uint64_t* qsum /* [N] */, int64_t N, double* out /* [N][3] */);
 
+/* ---- a19: LD scores from the windowed-LD sweep, and LD-score regression (Bulik-Sullivan et al. 2015) on a scan's statistics: does the
+ * inflation of the test statistics come from confounding (the intercept) or from polygenic signal (the slope = SNP heritability)?
+ * gpca_ld_score: the sweep of a10 over the same band, with the same addressing, the same win_end contract and the same checks; the
+ *     six pair counts never leave the device.  For every pair (i, j) of the band's windows, from the counts and in f64 as in a10,
+ *         cov = n sxy - sx sy,  vx = n sxx - sx sx,  vy = n syy - sy sy,  r2 = (cov cov) / (vx vy)      (the bits of a10's r2)
+ *     A pair with vx <= 0, vy <= 0 or n <= 2 is SKIPPED: it adds to nothing and is not counted.  A counted pair is worth
+ *         v = r2 - (1.0 - r2) / (n - 2.0)   with GPCA_LDSCORE_UNBIASED (ldsc's bias adjustment, with the pair's own jointly observed n)
+ *         v = r2                            without
+ *         q = (int64) rint(v 2^40), half to even; no fused multiply-add in this chain
+ *     and q is added to score[i - row0] AND to score[j - row0], 1 to partners[...] at the same two places.  The unit of score is 2^-40.
+ *     score and partners hold span = min(K, row1 + wmax) - row0 entries from row0 and are WRITTEN (zeros where no pair reaches).
+ *     Every sum is an integer, so tiling, order and atomics move no bit: the sum over consecutive bands, each added at its row0, is the
+ *     full call (the caller adds its bands; a SNP's LD score needs the windows of the rows before it too), and int8 and 2-bit residency
+ *     and a GPCA_PREC_F32_MFMA handle give the same bits.  rows = 0 returns GPCA_OK and writes nothing.  The sample mask is ignored
+ *     (every sample enters) and no fitted result of the handle is touched.  wmax <= 2^20, so that 2 wmax pairs of at most 2^41 stay
+ *     below 2^63.
+ *  Device: one kernel after the sweep reads the six i32 planes once (24 B per slot).  A workgroup takes 64 rows x 256 slots; thread p
+ *     owns partner row t0 + d0 + 1 + p and walks the tile's rows, so each step reads consecutive slots of one row and the partner's sum
+ *     stays in registers; the row's own sum is a wave reduction and one LDS atomic per wave; one 64-bit and one 32-bit global atomic per
+ *     touched row and tile.
+ *  Errors: GPCA_ERR_STATE (no genotypes, a streamed handle, a row-sharded handle, no standardisation, K = 0), GPCA_ERR_BAD_ARG (ranges,
+ *     win_end, wmax < 1, wmax > 2^20, a NULL score, unknown flag bits, 4 N >= 2^31), GPCA_ERR_INVALID_GENOTYPE (a row the call reads
+ *     holds a value outside {0, 1, 2, missing}; the message names the row), GPCA_ERR_OOM (checked before any allocation).
+ * The two host rules take no handle and work in f64 with no fused multiply-add.
+ *  gpca_ld_score_total: l2[i] = 1 + acc[i] 2^-40 (acc = the bands' scores added up; the 1 is the SNP with itself).
+ *  gpca_ldsc_fit: chi2, ell, w_ell [m] (w_ell NULL = ell); N = n_samples, M = the number of SNPs the LD scores sum over.
+ *   1. Used rows: those with finite chi2, ell, w_ell and, when chi2_max > 0, chi2 <= chi2_max, in the given order; m_used of them.
+ *      B = min(n_blocks, m_used).  GPCA_ERR_BAD_ARG when B < 2, m_used < 3, n_samples <= 0 or M <= 0.
+ *   2. Start: h = clamp(M (mean chi2 - 1) / (N mean l'), 0, 1), a = 1, with l' = max(ell, 1) and wl' = max(w_ell, 1).
+ *   3. Weights: w_j = 1 / (wl'_j 2 (a + N clamp(h, 0, 1) l'_j / M)^2)   (ldsc's heteroskedasticity and over-counting weights).
+ *   4. Solve: weighted least squares of chi2 on (1, l').  The five sums sum w, sum w l, sum w l^2, sum w chi2, sum w l chi2 are
+ *      accumulated sequentially in f64 per jackknife block (block k = used rows [floor(m_used k / B), floor(m_used (k + 1) / B))); the
+ *      totals are the block sums added in block order; the 2 x 2 system is solved by its determinant, and a determinant <= 0 or
+ *      non-finite is GPCA_ERR_BAD_ARG (constant ell).  That gives the intercept a and the slope b; h = b M / N.
+ *   5. Reweighting: two rounds of (solve, recompute the weights from (a, h)), then a final solve: three solves.
+ *   6. Delete-one jackknife over the B blocks with the final weights: estimates from totals minus block sums, pseudo-values
+ *      B theta - (B - 1) theta_(k), se = sqrt(var(pseudo, ddof = 1) / B).
+ *   7. out [10] = m_used, mean chi2, lambda_GC = median chi2 / 0.4549364231195724 (an even count: the mean of the middle two),
+ *      intercept, its se, h2, its se, ratio = (a - 1) / (mean chi2 - 1) and its se = se_a / (mean chi2 - 1) (both NaN when
+ *      mean chi2 <= 1), B.
+ *   h2 of a binary trait is on the observed scale.  ldsc's two-step estimator and its printed digits are not claimed.
+ *  Not there: LD clumping of scan results, partitioned or annotation-stratified LD scores, cM windows (there is no genetic map), ldsc's
+ *     two-step estimator, genetic correlation, liability-scale conversion, streamed and row-sharded handles. */
+#define GPCA_LDSCORE_UNBIASED 1
+GPCA_API int gpca_ld_score(gpca_handle* h, int64_t row0, int64_t row1, const int64_t* win_end /* [row1 - row0] */, int32_t wmax,
+                           int32_t flags, int64_t* score /* [span], units of 2^-40 */, int32_t* partners /* [span]; may be NULL */);
+GPCA_API int gpca_ld_score_total(const int64_t* acc /* [K] */, int64_t K, double* l2 /* [K] */);
+GPCA_API int gpca_ldsc_fit(const double* chi2, const double* ell, const double* w_ell /* NULL = ell */, int64_t m, double n_samples, double M,
+                           int32_t n_blocks, double chi2_max, double* out /* [10] */);
+
 /* ---- f3: the stages of EigenSNPCoreAlgorithm::compute_pca (main.rs:311-327, 359-366) ------------------------------------------
  * The algorithm lives in the un-vendored efficient_pca crate (Cargo.toml:30, branch "main", no pinned revision): what follows is
  * the stage structure of its published description -- per-LD-block local bases learnt on a sample subset, condensed features of

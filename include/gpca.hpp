@@ -195,6 +195,42 @@ public:
         if (counts) counts->resize(6 * rows * w);
         if (above) above->resize(rows * ((w + 63) / 64));
     }
+    // LD scores of kept rows [row0, row1) from the windowed-LD sweep (gpca_ld_score; gpca.h section a19): score [span] in units of 2^-40
+    // and (when not null) partners [span], span = min(K, row1 + wmax) - row0 entries from row0.  WRITTEN per call: the caller adds its bands
+    void ld_score(int64_t row0, int64_t row1, const std::vector<int64_t>& win_end, int32_t wmax, bool unbiased, std::vector<int64_t>& score,
+                  std::vector<int32_t>* partners = nullptr) const {
+        const size_t rows = row1 > row0 ? (size_t)(row1 - row0) : 0;
+        if (win_end.size() != rows) throw std::invalid_argument("gpca::Engine::ld_score: win_end needs one entry per row of the band");
+        const int64_t K = gpca_num_pca_snps(h_);
+        const size_t span = rows ? (size_t)std::max<int64_t>(std::min<int64_t>(K, row1 + std::max<int32_t>(wmax, 0)) - row0, 0) : 0;
+        score.assign(std::max<size_t>(span, 1), 0);
+        if (partners) partners->assign(std::max<size_t>(span, 1), 0);
+        check(gpca_ld_score(h_, row0, row1, win_end.data(), wmax, unbiased ? GPCA_LDSCORE_UNBIASED : 0, score.data(), partners ? partners->data() : nullptr));
+        score.resize(span);
+        if (partners) partners->resize(span);
+    }
+    // L2 = 1 + acc 2^-40 of every SNP (gpca_ld_score_total; host only)
+    static std::vector<double> ld_score_total(const std::vector<int64_t>& acc) {
+        std::vector<double> l2(std::max<size_t>(acc.size(), 1), 0.0);
+        const int rc = acc.empty() ? GPCA_OK : gpca_ld_score_total(acc.data(), (int64_t)acc.size(), l2.data());
+        if (rc != GPCA_OK) throw Error(rc, std::string("gpca_ld_score_total: ") + gpca_status_string(rc));
+        l2.resize(acc.size());
+        return l2;
+    }
+    // LD-score regression (gpca_ldsc_fit; host only; the rule is written out in gpca.h section a19): out [10] = m_used, mean chi2, lambda_GC,
+    // intercept, its se, h2, its se, ratio, its se, blocks; w_ell null = ell; chi2_max 0 = no cap
+    static std::vector<double> ldsc_fit(const std::vector<double>& chi2, const std::vector<double>& ell, double n_samples, double M,
+                                        const std::vector<double>* w_ell = nullptr, int32_t n_blocks = 200, double chi2_max = 0.0) {
+        std::vector<double> out(10, 0.0);
+        static const double none = 0.0;
+        const bool sizes = ell.size() == chi2.size() && (!w_ell || w_ell->size() == chi2.size());
+        const int rc = !sizes ? GPCA_ERR_BAD_ARG
+                              : gpca_ldsc_fit(chi2.empty() ? &none : chi2.data(), chi2.empty() ? &none : ell.data(),
+                                              w_ell ? (chi2.empty() ? &none : w_ell->data()) : nullptr, (int64_t)chi2.size(), n_samples, M, n_blocks, chi2_max,
+                                              out.data());
+        if (rc != GPCA_OK) throw Error(rc, std::string("gpca_ldsc_fit: ") + gpca_status_string(rc));
+        return out;
+    }
     // PC-Relate (gpca_pcrelate): rows [row0, row1) of the lower triangle WITH the diagonal of the ancestry-adjusted kinship, packed as
     // grm packs it; V [N][P] sample coordinates, train (may be null: everyone) [N]; nsnp (may be null) receives the SNPs valid in both
     std::vector<double> pcrelate(const std::vector<double>& V, int32_t P, const std::vector<uint8_t>* train, double tau, int64_t row0,
