@@ -14,5 +14,7 @@ fst_hudson = GpcaEngine.fst_hudson
 fst_wc = GpcaEngine.fst_wc
 het_weights = GpcaEngine.het_weights
 sample_het = GpcaEngine.sample_het
+roh_select = GpcaEngine.roh_select
+roh_threshold = GpcaEngine.roh_threshold
 
 __version__ = "0.2.2"

@@ -29,6 +29,8 @@ STORE_2BIT = 1
 STORE_INT8 = 2
 GROUPS_MAX = 64           # gpca_group_counts: most sample groups of one call (include/gpca.h)
 LDSCORE_UNBIASED = 1      # gpca_ld_score flag (include/gpca.h)
+ROH_WINDOW_MAX = 64       # gpca_roh: the widest window (include/gpca.h)
+ROH_DEN_MAX = 1 << 20     # gpca_roh: the largest denominator of the threshold
 GRM_STANDARDIZED = 0      # gpca_grm scalings (include/gpca.h)
 GRM_CENTRED = 1
 CFG_SIMPLE_KERNELS = 1     # gpca_config.reserved[0] flags (include/gpca.h)
@@ -55,6 +57,11 @@ class gpca_config(C.Structure):
 
 class gpca_qc_config(C.Structure):
     _fields_ = [("min_snp_call_rate", C.c_double), ("min_snp_maf", C.c_double), ("max_snp_hwe_p_value", C.c_double)]
+
+
+class gpca_roh_params(C.Structure):
+    _fields_ = [("window_snp", C.c_int32), ("window_het", C.c_int32), ("window_missing", C.c_int32), ("thr_num", C.c_int32),
+                ("thr_den", C.c_int32), ("min_snp", C.c_int32), ("max_het", C.c_int32)]
 
 
 class gpca_kernel_timing(C.Structure):
@@ -162,6 +169,8 @@ PROTOTYPES = {
     "gpca_sample_het": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "gpca_ld_score": (C.c_int, [_H, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "gpca_ld_score_total": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
+    "gpca_roh": (C.c_int, [_H, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "gpca_roh_select": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
     "gpca_ldsc_fit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_int32, C.c_double, C.c_void_p]),
     "gpca_comm_get_unique_id": (C.c_int, [C.c_void_p]),
     "gpca_comm_init": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, C.c_int64]),

@@ -14,6 +14,7 @@ flags parameterise, as published for that crate (parity unpinned).
 from __future__ import annotations
 
 import argparse
+import math
 import os
 import sys
 import time
@@ -195,6 +196,24 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--gpca-het-sd", type=float, default=None, metavar="K",
                    help="--eigensnp: drop a sample whose F lies more than K standard deviations from the mean F of the samples that "
                         "pass --gpca-mind (K > 0; one round) -> <out>.sampleqc.in.id / .out.id")
+    p.add_argument("--gpca-homozyg", action="store_true",
+                   help="--eigensnp: runs of homozygosity of every sample over the SNPs that pass the SNP QC (plink --homozyg's sliding "
+                        "window) -> <out>.hom (#FID IID CHROM SNP1 SNP2 POS1 POS2 KB NSNP DENSITY PHOM PHET) and <out>.hom.indiv (#FID IID "
+                        "NSEG KB KBAVG FROH); any flag below implies it")
+    p.add_argument("--gpca-homozyg-window-snp", type=int, default=None, metavar="W", help="the scanning window in SNPs (1 .. 64) [default: 50]")
+    p.add_argument("--gpca-homozyg-window-het", type=int, default=None, metavar="H",
+                   help="het calls a window may hold and still be a hit (0 .. W) [default: 1]")
+    p.add_argument("--gpca-homozyg-window-missing", type=int, default=None, metavar="M",
+                   help="missing calls a window may hold and still be a hit (0 .. W) [default: 5]")
+    p.add_argument("--gpca-homozyg-window-threshold", default=None, metavar="X",
+                   help="the share of hits among the windows over a SNP that puts it in a run, a decimal number in [0, 1] taken as its "
+                        "exact fraction [default: 0.05]")
+    p.add_argument("--gpca-homozyg-snp", type=int, default=None, metavar="N", help="SNPs a run needs at least [default: 100]")
+    p.add_argument("--gpca-homozyg-kb", type=float, default=None, metavar="X", help="kb a run spans at least [default: 1000]")
+    p.add_argument("--gpca-homozyg-density", type=float, default=None, metavar="X", help="kb per SNP a run holds at most [default: 50]")
+    p.add_argument("--gpca-homozyg-gap", type=float, default=None, metavar="X",
+                   help="a gap of more than X kb between two SNPs ends a run [default: 1000]")
+    p.add_argument("--gpca-homozyg-het", type=int, default=None, metavar="N", help="het calls a run holds at most [default: no limit]")
     p.add_argument("--gpca-assoc-pcs", type=int, default=None, metavar="P",
                    help="--gpca-assoc-pheno: the first P columns of the scores this run writes are covariates (0 <= P <= "
                         "--eigensnp-k-global) [default: every column]")
@@ -336,12 +355,16 @@ def run_eigensnp_workflow(a) -> int:
         raise SystemExit(STRAT_NEEDS_RESIDENT)
     if streamed and _sample_qc_asked(a):
         raise SystemExit(SAMPLE_QC_NEEDS_RESIDENT)
+    if streamed and _homozyg_asked(a):
+        raise SystemExit(HOMOZYG_NEEDS_RESIDENT)
     if streamed and a.gpca_ld_score is not None:
         raise SystemExit(LD_SCORE_NEEDS_RESIDENT)
     st = eng.snp_stats(QcConfig(a.eigensnp_min_call_rate, a.eigensnp_min_maf, a.eigensnp_max_hwe_p))
     qc_pass = None
     if _sample_qc_asked(a) and len(sample_ids) and int(st["keep"].sum()):
         qc_pass = _sample_qc(eng, a, fs, cols, sample_ids, st)
+    if _homozyg_asked(a) and len(sample_ids) and int(st["keep"].sum()):
+        _homozyg(eng, a, fs, cols, sample_ids, st)
     blocks = gio.parse_ld_block_file(a.ld_block_file)
     keep, by_tag = gio.map_snps_to_ld_blocks(blocks, fs.chromosomes, fs.positions, st["keep"])
     _log(f"{int(st['keep'].sum())} / {len(st['keep'])} SNPs passed QC; {int(keep.sum())} fall in {len(by_tag)} LD blocks")
@@ -502,6 +525,81 @@ def _sample_qc(eng, a, fs, cols, sample_ids, st):
     gio.write_sample_qc_ids(a.output_prefix, fids, sample_ids, ok, reason)
     _log(f"sample QC: {reason.count('MIND')} samples fail --gpca-mind, {reason.count('HET')} fail --gpca-het-sd, {int(ok.sum())} of {n} pass")
     return ok.astype(bool)
+
+
+HOMOZYG_NEEDS_RESIDENT = ("error: --gpca-homozyg needs the genotype matrix resident on the device: the runs of homozygosity of a matrix "
+                          "walked out of core are not implemented")
+HOMOZYG_VALUE_FLAGS = ("window_snp", "window_het", "window_missing", "window_threshold", "snp", "kb", "density", "gap", "het")
+
+
+def _homozyg_asked(a) -> bool:
+    return bool(a.gpca_homozyg or any(getattr(a, "gpca_homozyg_" + f) is not None for f in HOMOZYG_VALUE_FLAGS))
+
+
+def _kb_to_bp(kb: float) -> int:
+    """kb on the command line -> bp: x 1000 rounded half up (genomic_pca.cpp: kb_to_bp)"""
+    return int(math.floor(float(kb) * 1000.0 + 0.5))
+
+
+def _homozyg_params(a) -> dict:
+    """The values of --gpca-homozyg* with their defaults, checked before anything is read; the threshold as (num, den)."""
+    import re
+    from fractions import Fraction
+    W = 50 if a.gpca_homozyg_window_snp is None else a.gpca_homozyg_window_snp
+    H = 1 if a.gpca_homozyg_window_het is None else a.gpca_homozyg_window_het
+    Mi = 5 if a.gpca_homozyg_window_missing is None else a.gpca_homozyg_window_missing
+    if not 1 <= W <= 64:
+        raise SystemExit("error: --gpca-homozyg-window-snp must lie in [1, 64]")
+    if not (0 <= H <= W and 0 <= Mi <= W):
+        raise SystemExit("error: --gpca-homozyg-window-het and --gpca-homozyg-window-missing must lie in [0, --gpca-homozyg-window-snp]")
+    text = "0.05" if a.gpca_homozyg_window_threshold is None else a.gpca_homozyg_window_threshold
+    fr = Fraction(text) if re.fullmatch(r"[0-9]*\.?[0-9]*", text) and re.search(r"[0-9]", text) else None
+    if fr is None or fr > 1 or fr.denominator > 1 << 20:
+        raise SystemExit("error: --gpca-homozyg-window-threshold must be a decimal number in [0, 1] whose exact fraction has a denominator of "
+                         "at most 2^20")
+    snp = 100 if a.gpca_homozyg_snp is None else a.gpca_homozyg_snp
+    if not 1 <= snp < 1 << 31:
+        raise SystemExit("error: --gpca-homozyg-snp must lie in [1, 2^31)")
+    kb = 1000.0 if a.gpca_homozyg_kb is None else a.gpca_homozyg_kb
+    density = 50.0 if a.gpca_homozyg_density is None else a.gpca_homozyg_density
+    gap = 1000.0 if a.gpca_homozyg_gap is None else a.gpca_homozyg_gap
+    if not all(0.0 <= v <= 1e12 for v in (kb, density, gap)):
+        raise SystemExit("error: --gpca-homozyg-kb, --gpca-homozyg-density and --gpca-homozyg-gap must lie in [0, 1e12]")
+    if a.gpca_homozyg_het is not None and not 0 <= a.gpca_homozyg_het < 1 << 31:
+        raise SystemExit("error: --gpca-homozyg-het must lie in [0, 2^31)")
+    return dict(window_snp=W, window_het=H, window_missing=Mi, window_threshold=(fr.numerator, fr.denominator), min_snp=snp,
+                max_het=a.gpca_homozyg_het, min_bp=_kb_to_bp(kb), max_bp_per_snp=_kb_to_bp(density), max_gap_bp=_kb_to_bp(gap))
+
+
+def _homozyg(eng, a, fs, cols, sample_ids, st):
+    """--gpca-homozyg: the runs of homozygosity (gpca_roh, in bands cut at chromosome starts) of every sample over every SNP that
+    passes the SNP QC, the length and density rule on the records (gpca_roh_select), P.hom and P.hom.indiv.  Sets the keep mask to the
+    QC mask (mu, sigma unchanged); the caller sets its own afterwards."""
+    from . import _lib
+    par = dict(a.gpca_homozyg_params)
+    fids = fs.family_ids if cols is None else [fs.family_ids[i] for i in cols]
+    eng.set_standardization(st["mu"], st["sigma"], st["keep"])                       # every SNP that passes the SNP QC
+    rows = np.flatnonzero(st["keep"])
+    chroms = [fs.chromosomes[r] for r in rows]
+    ids = [fs.variant_ids[r] for r in rows]
+    pos = np.asarray([int(fs.positions[r]) for r in rows], np.int64)
+    brk = gio.roh_breaks(chroms, pos, par.pop("max_gap_bp"))
+    min_bp, max_bp_per_snp = par.pop("min_bp"), par.pop("max_bp_per_snp")
+    parts = []
+    try:
+        for r0, r1 in gio.roh_bands(brk):
+            parts.append(eng.roh(brk[r0:r1], rows=(r0, r1), **par)[0])
+    except _lib.GpcaError as e:
+        if e.status == _lib.GPCA_ERR_STATE:
+            raise SystemExit(HOMOZYG_NEEDS_RESIDENT) from None
+        raise
+    segs = np.concatenate(parts) if parts else np.zeros((0, 5), np.uint32)
+    segs = segs[np.argsort(segs[:, 0], kind="stable")]                               # ascending (sample, first): the bands are disjoint in rows
+    keep = GpcaEngine.roh_select(segs, pos, min_bp, max_bp_per_snp)
+    _ensure_parent(a.output_prefix)
+    gio.write_hom(a.output_prefix, fids, sample_ids, chroms, ids, pos, segs, keep, brk)
+    _log(f"runs of homozygosity of {len(sample_ids)} samples over {len(rows)} SNPs: {int(keep.sum())} of {len(segs)} runs pass the length "
+         f"and density rule, written to {a.output_prefix}.hom")
 
 
 def _king(eng, a, fs, cols, sample_ids, n_snps, qc_pass=None):
@@ -968,6 +1066,12 @@ def main(argv=None) -> int:
                              "the sample mask)")
         if a.gpca_stream == "on":
             raise SystemExit(SAMPLE_QC_NEEDS_RESIDENT)
+    if _homozyg_asked(a):
+        if not a.eigensnp:
+            raise SystemExit("error: --gpca-homozyg needs the --eigensnp workflow")
+        a.gpca_homozyg_params = _homozyg_params(a)
+        if a.gpca_stream == "on":
+            raise SystemExit(HOMOZYG_NEEDS_RESIDENT)
     if a.gpca_assoc_pheno is not None:
         if not a.eigensnp:
             raise SystemExit("error: --gpca-assoc-pheno needs the --eigensnp workflow")

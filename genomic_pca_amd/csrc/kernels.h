@@ -423,4 +423,19 @@ int launch_sample_counts(hipStream_t st, const void* G, int packed, int64_t ldr,
 void launch_sc_sum(hipStream_t st, const unsigned* part, const unsigned long long* qpart, int64_t N, int64_t splits, int64_t rows,
                    unsigned long long qtot, unsigned* counts, unsigned long long* qsum);
 
+// ---- runs of homozygosity (roh.hip) over kept rows [row0, row1) (PCA-SNP order through krows), all N samples; extents: plan_math.h roh_*.
+// launch_roh_mark: plane [rows][roh_plane_pitch(N)] = the in-ROH bit of every (row, sample); dom [domains + 1] = the band-relative first
+// rows of the window domains, then rows; window W, at most H het and M missing calls per hit, a row is in iff hits den >= num cov; *bad
+// as in launch_assoc.  launch_roh_runs (k_roh_runs, then k_roh_stitch): segs NULL = the count pass (rec [plan.splits][roh_npad(N)][8] =
+// what crosses the split boundaries; cnt [plan.splits][roh_npad(N)] = per sample the records of the splits before; seg_count [N] = the
+// reported runs); else the fill pass (rec and cnt as the count pass left them, base [N] = the records of the samples before,
+// segs [cap][5]).  brk [rows]: bit 1 = a run may not continue into the row.  The launches return nonzero when an argument is outside the
+// kernels' limits.
+int launch_roh_mark(hipStream_t st, const void* G, int packed, int64_t ldr, const int64_t* krows, int64_t N, int64_t row0, int64_t row1,
+                    const RohPlan& plan, const int* dom, int64_t domains, int W, int H, int M, int num, int den, uint8_t* plane,
+                    unsigned long long* bad);
+int launch_roh_runs(hipStream_t st, const void* G, int packed, int64_t ldr, const int64_t* krows, int64_t N, int64_t row0, int64_t row1,
+                    const RohPlan& plan, const uint8_t* brk, const uint8_t* plane, int64_t min_snp, int64_t max_het, unsigned* rec,
+                    unsigned* cnt, unsigned* seg_count, const unsigned long long* base, unsigned* segs, int64_t cap);
+
 }  // namespace gpca

@@ -503,4 +503,53 @@ constexpr double sc_call_bytes(int64_t N, int64_t rows, int64_t splits, bool has
            (hasq ? 8.0 * (double)sc_qpart_capacity(splits, N) + 8.0 * (double)sc_qsum_capacity(N) + 4.0 * (double)sc_q_capacity(rows) : 0.0);
 }
 
+// ---- runs of homozygosity (roh.hip, gpca_roh.cpp) ----------------------------------------------------------------------------------
+// The access pattern and the launch plan are the sample counts': a thread owns kScLane consecutive samples, a workgroup (one wave) a
+// chunk of kScChunk samples and one row split [split * per, (split + 1) * per) of the band.  Rows are band-relative (0 .. rows - 1)
+// everywhere below.  k_roh_mark decides the rows of its split: inside every window domain [d0, d1) that the split meets it walks the
+// windows [roh_win_lo, roh_win_hi] (window s = rows s .. s + W - 1), so it reads rows roh_win_lo .. roh_win_hi + W - 1: its own rows and
+// a halo of at most W - 1 rows on either side, clipped at the domain.  It writes one bit per (row, sample) to the plane.  k_roh_runs
+// walks the plane over its split's rows and leaves what crosses a split boundary in rec; k_roh_stitch joins it, a thread per sample.
+constexpr int kRohMaxWindow = 64, kRohUnroll = 4, kRohFlushRows = 255, kRohStitchThreads = 64, kRohStitchBatch = 8;
+constexpr int kRohMaxDen = 1 << 20;
+using RohPlan = ScPlan;
+// forced > 0 (GPCA_ROH_SPLITS): that many splits, clamped to the band's rows
+inline RohPlan roh_plan(int64_t rows, int64_t N, int cus, int64_t forced = 0) { return sc_plan(rows, N, cus, forced); }
+constexpr int64_t roh_npad(int64_t N) { return sc_npad(N); }
+// the windows a piece [pa, pb) of the domain [d0, d1) needs (d1 - d0 >= W): first and last window start
+constexpr int64_t roh_win_lo(int64_t d0, int64_t pa, int W) { return pa - W + 1 > d0 ? pa - W + 1 : d0; }
+constexpr int64_t roh_win_hi(int64_t d1, int64_t pb, int W) { return pb - 1 < d1 - W ? pb - 1 : d1 - W; }
+// the windows that cover row j of the domain: roh_cov_lo .. roh_cov_hi (cov = hi - lo + 1, 1 .. W)
+constexpr int64_t roh_cov_lo(int64_t d0, int64_t j, int W) { return j - W + 1 > d0 ? j - W + 1 : d0; }
+constexpr int64_t roh_cov_hi(int64_t d1, int64_t j, int W) { return j < d1 - W ? j : d1 - W; }
+// the plane: inroh [rows][pitch] bytes, bit (n & 7) of byte n / 8 of a row = sample n; a thread writes the two bytes of its 16 samples
+constexpr int64_t roh_plane_pitch(int64_t N) { return roh_npad(N) / 8; }
+constexpr int64_t roh_plane_index(int64_t j, int64_t pitch, int64_t n0) { return j * pitch + (n0 >> 3); }
+constexpr int64_t roh_plane_capacity(int64_t rows, int64_t N) { return rows * roh_plane_pitch(N); }
+// cnt [splits][npad] u32: the reported runs that start in the split, then (k_roh_stitch, in place) the runs of the sample in the splits
+// before it
+constexpr int64_t roh_cnt_index(int64_t split, int64_t npad, int64_t n) { return split * npad + n; }
+constexpr int64_t roh_cnt_capacity(int64_t splits, int64_t N) { return splits * roh_npad(N); }
+// rec [splits][npad][kRohRecWords] u32, what a split knows of a sample: the head = the continuation of a run of the split before (its
+// rows in this split, their het and missing calls; flag kRohFlagThrough: it goes on into the next split), the tail = a run that starts in
+// the split and goes on into the next one (flag kRohFlagTail; its first row, its het and missing calls in this split), and the split's
+// own reported runs.  Words: head rows, head het, head missing, flags, tail first, tail het, tail missing, own runs
+constexpr int kRohRecWords = 8;
+constexpr unsigned kRohFlagThrough = 1u, kRohFlagTail = 2u;
+constexpr int64_t roh_rec_index(int64_t split, int64_t npad, int64_t n) { return (split * npad + n) * kRohRecWords; }
+constexpr int64_t roh_rec_capacity(int64_t splits, int64_t N) { return splits * roh_npad(N) * kRohRecWords; }
+// elements of the call's other buffers: brk [rows] u8; dom [domains + 1] i32 (the domains' first rows, then rows); seg_count [N] u32;
+// base [N] u64 (the records of the samples before n); segs [records][5] u32; the invalid-genotype word
+constexpr int64_t roh_brk_capacity(int64_t rows) { return rows; }
+constexpr int64_t roh_dom_capacity(int64_t domains) { return domains + 1; }
+constexpr int64_t roh_segcount_capacity(int64_t N) { return N; }
+constexpr int64_t roh_base_capacity(int64_t N) { return N; }
+constexpr int64_t roh_seg_capacity(int64_t records) { return 5 * records; }
+// The device bytes a call allocates (gpca_roh's GPCA_ERR_OOM sum, without the check's slack); records = min(cap, n_found)
+constexpr double roh_call_bytes(int64_t N, int64_t rows, int64_t splits, int64_t domains, int64_t records) {
+    return (double)roh_plane_capacity(rows, N) + (double)roh_brk_capacity(rows) + 4.0 * (double)roh_dom_capacity(domains) +
+           4.0 * (double)roh_cnt_capacity(splits, N) + 4.0 * (double)roh_rec_capacity(splits, N) + 4.0 * (double)roh_segcount_capacity(N) + 8.0 * (double)roh_base_capacity(N) +
+           4.0 * (double)roh_seg_capacity(records) + 8.0;
+}
+
 }  // namespace gpca

@@ -769,6 +769,81 @@ class GpcaEngine:
         return {"counts": counts[:N], "qsum": None if qsum is None else qsum[:N]}
 
     @staticmethod
+    def roh_threshold(x) -> Tuple[int, int]:
+        """The window threshold as the ABI takes it: (num, den) = the exact fraction of x's decimal text (Fraction(str(x)): 0.05 is 1/20,
+        not the binary double next to it).  x: a float, an int, a decimal or 'a/b' string, a Fraction, or a (num, den) pair, which is
+        passed on as it is.  ValueError when the reduced denominator is above 2^20 or the value is not a finite number."""
+        from fractions import Fraction
+        if isinstance(x, tuple):
+            if len(x) != 2:
+                raise ValueError("window_threshold as a pair is (num, den)")
+            return int(x[0]), int(x[1])
+        try:
+            fr = x if isinstance(x, Fraction) else Fraction(str(x))
+        except (ValueError, ZeroDivisionError) as err:
+            raise ValueError(f"window_threshold {x!r} is not a finite decimal number") from err
+        if fr.denominator > _lib.ROH_DEN_MAX:
+            raise ValueError(f"window_threshold {x!r} = {fr.numerator}/{fr.denominator}: the denominator is above 2^20")
+        if abs(fr.numerator) >= 1 << 31:
+            raise ValueError(f"window_threshold {x!r} is out of range")
+        return fr.numerator, fr.denominator
+
+    def roh(self, brk, window_snp: int = 50, window_het: int = 1, window_missing: int = 5, window_threshold=0.05, min_snp: int = 100,
+            max_het: Optional[int] = None, rows: Optional[Tuple[int, int]] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """Runs of homozygosity (gpca_roh; gpca.h section a20) over the kept rows [row0, row1) in PCA-SNP order (rows; default: all) and
+        all samples.  brk: uint8, one per row of the band (io.roh_breaks): bit 0 = a window domain (chromosome) starts at the row,
+        bit 1 = no run continues into the row.  A window of window_snp rows is a hit for a sample with at most window_het het and
+        window_missing missing calls; a row is in a run iff the share of hits among the windows that cover it is at least
+        window_threshold (roh_threshold); a run is reported with at least min_snp rows and at most max_het het calls (None: no limit).
+        Returns (segs uint32 [n][5] = sample, first, last, n_het, n_missing in ascending (sample, first) order, first and last being
+        kept-row indices of the handle; seg_count uint32 [N]).  Exact integers; a second call is made when the first buffer was short."""
+        N = self.dims()[1]
+        K = int(self._lib.gpca_num_pca_snps(self._h))
+        r0, r1 = (0, K) if rows is None else (int(rows[0]), int(rows[1]))
+        n = max(r1 - r0, 0)
+        bv = np.asarray(brk)
+        if bv.shape != (n,) or bv.dtype.kind not in "iub" or (bv.size and (int(bv.min()) < 0 or int(bv.max()) > 255)):
+            raise ValueError("brk must be an unsigned byte array with one entry per row of the band")
+        bb = np.zeros(max(n, 1), np.uint8)
+        bb[:n] = bv
+        num, den = self.roh_threshold(window_threshold)
+        vals = (int(window_snp), int(window_het), int(window_missing), num, den, int(min_snp), -1 if max_het is None else int(max_het))
+        if any(abs(v) >= 1 << 31 for v in vals):
+            raise ValueError("a parameter of roh is outside 32 bits")
+        if max_het is not None and int(max_het) < 0:
+            raise ValueError("max_het must be None (no limit) or at least 0")
+        par = _lib.gpca_roh_params(*vals)
+        seg_count = np.zeros(max(N, 1), np.uint32)
+        found = C.c_int64(0)
+        cap = max(4 * N, 1024)
+        while True:
+            segs = np.zeros((cap, 5), np.uint32)
+            self._chk(self._lib.gpca_roh(self._h, r0, r1, _vp(bb), C.byref(par), _vp(seg_count), _vp(segs), cap, C.byref(found)))
+            if found.value <= cap:
+                return segs[:found.value].copy(), seg_count[:N]
+            cap = int(found.value)
+
+    @staticmethod
+    def roh_select(segs, positions, min_bp: int, max_bp_per_snp: int) -> np.ndarray:
+        """The host rule on the records (gpca_roh_select; gpca.h section a20): segs [n][5] as roh gives them, positions [K] = the bp
+        position of every kept row.  Returns uint8 [n]: 1 iff span = pos[last] - pos[first] >= min_bp and span <= max_bp_per_snp x
+        (last - first + 1)."""
+        sv = np.ascontiguousarray(segs, np.uint32)
+        pv = np.ascontiguousarray(positions, np.int64)
+        if sv.ndim != 2 or sv.shape[1] != 5 or pv.ndim != 1:
+            raise ValueError("segs must be [n][5] as roh returns them and positions one entry per kept row")
+        n = sv.shape[0]
+        if n and int(sv[:, 1:3].max()) >= pv.shape[0]:
+            raise ValueError("a record names a row beyond positions")
+        keep = np.zeros(max(n, 1), np.uint8)
+        lib = _lib.load()
+        rc = lib.gpca_roh_select(_vp(sv if n else np.zeros((1, 5), np.uint32)), n, _vp(pv if pv.size else np.zeros(1, np.int64)),
+                                 int(min_bp), int(max_bp_per_snp), _vp(keep))
+        if rc != 0:
+            raise GpcaError(rc, "gpca_roh_select: " + lib.gpca_status_string(rc).decode())
+        return keep[:n]
+
+    @staticmethod
     def het_weights(qc_counts) -> np.ndarray:
         """The rows' weights for the heterozygosity F (gpca_het_weights; host only; gpca.h section a18): qc_counts [rows][4] = n_valid,
         n_hom0, n_het, n_hom2 as snp_qc_detail gives them; returns uint32 [rows] = the unbiased expected heterozygosity of each row in

@@ -1295,6 +1295,138 @@ inline void write_sample_qc_ids(const std::string& prefix, const std::vector<std
     }
 }
 
+// ---- runs of homozygosity: the twins of io.roh_breaks, io.roh_bands, io.roh_select, io.roh_summary and io.write_hom (same rules,
+// byte-identical files) ---------------------------------------------------------------------------------------------------------------------
+// brk [K] over the kept SNPs, in their order: 3 at the first SNP of every chromosome run, 2 at a SNP more than max_gap_bp behind the SNP
+// before it, else 0
+inline std::vector<uint8_t> roh_breaks(const std::vector<std::string>& chromosomes, const std::vector<int64_t>& positions, int64_t max_gap_bp) {
+    const int64_t K = (int64_t)chromosomes.size();
+    if ((int64_t)positions.size() != K) throw std::runtime_error("roh_breaks: one position per chromosome entry");
+    if (max_gap_bp < 0) throw std::runtime_error("roh_breaks: the gap must be at least 0");
+    std::vector<uint8_t> brk((size_t)K, 0);
+    std::set<std::string> seen;
+    for (int64_t s = 0; s < K;) {
+        const std::string c = normalize_chromosome_name(chromosomes[(size_t)s]);
+        if (!seen.insert(c).second)
+            throw std::runtime_error("roh_breaks: chromosome '" + chromosomes[(size_t)s] + "' reappears at variant " + std::to_string(s) +
+                                     " after another chromosome: sort the variants");
+        brk[(size_t)s] = 3;
+        int64_t e = s + 1;
+        while (e < K && normalize_chromosome_name(chromosomes[(size_t)e]) == c) {
+            if (positions[(size_t)e] < positions[(size_t)e - 1])
+                throw std::runtime_error("roh_breaks: the position of variant " + std::to_string(e) + " (" + std::to_string(positions[(size_t)e]) +
+                                         ") is below that of the variant before it on chromosome '" + chromosomes[(size_t)e] + "': sort the variants");
+            if (positions[(size_t)e] - positions[(size_t)e - 1] > max_gap_bp) brk[(size_t)e] = 2;
+            ++e;
+        }
+        s = e;
+    }
+    return brk;
+}
+// the first rows of the window domains of brk (row 0 starts one), then K
+inline std::vector<int64_t> roh_domain_starts(const std::vector<uint8_t>& brk) {
+    std::vector<int64_t> starts{0};
+    for (size_t j = 1; j < brk.size(); ++j) if (brk[j] & 1u) starts.push_back((int64_t)j);
+    starts.push_back((int64_t)brk.size());
+    return starts;
+}
+// [row0, row1) bands cut only where a domain starts: whole domains are added while the band stays within max_rows rows
+inline std::vector<std::pair<int64_t, int64_t>> roh_bands(const std::vector<uint8_t>& brk, int64_t max_rows = (int64_t)1 << 24) {
+    const std::vector<int64_t> starts = roh_domain_starts(brk);
+    std::vector<std::pair<int64_t, int64_t>> out;
+    int64_t r0 = 0;
+    for (size_t d = 1; d < starts.size(); ++d) {
+        if (d + 1 < starts.size() && starts[d + 1] - r0 <= std::max<int64_t>(max_rows, 1)) continue;
+        if (starts[d] > r0) out.emplace_back(r0, starts[d]);
+        r0 = starts[d];
+    }
+    return out;
+}
+// keep [n] of the records segs [n][5] by length and density (gpca_roh_select's rule, in integers)
+inline std::vector<uint8_t> roh_select(const std::vector<uint32_t>& segs, const std::vector<int64_t>& positions, int64_t min_bp, int64_t max_bp_per_snp) {
+    const size_t n = segs.size() / 5;
+    std::vector<uint8_t> keep(n, 0);
+    for (size_t i = 0; i < n; ++i) {
+        const int64_t first = segs[5 * i + 1], last = segs[5 * i + 2];
+        if (last < first) throw std::runtime_error("roh_select: record " + std::to_string(i) + " ends before it starts");
+        const int64_t span = positions[(size_t)last] - positions[(size_t)first], nsnp = last - first + 1;
+        keep[i] = (span >= min_bp && span / nsnp + (span % nsnp != 0 ? 1 : 0) <= max_bp_per_snp) ? 1 : 0;
+    }
+    return keep;
+}
+// per sample, from the kept records: NSEG, total bp and FROH = total bp / (the sum over the domains of pos[last row] - pos[first row]),
+// NaN when that sum is 0
+inline void roh_summary(const std::vector<uint32_t>& segs, const std::vector<uint8_t>& keep, const std::vector<int64_t>& positions,
+                        const std::vector<uint8_t>& brk, size_t n_samples, std::vector<int64_t>& nseg, std::vector<int64_t>& total,
+                        std::vector<double>& froh) {
+    const size_t n = segs.size() / 5;
+    if (keep.size() != n || positions.size() != brk.size()) throw std::runtime_error("roh_summary: one keep flag per record and one position per row of brk");
+    const std::vector<int64_t> starts = roh_domain_starts(brk);
+    int64_t genome = 0;
+    for (size_t d = 0; d + 1 < starts.size(); ++d)
+        if (starts[d + 1] > starts[d]) genome += positions[(size_t)starts[d + 1] - 1] - positions[(size_t)starts[d]];
+    nseg.assign(n_samples, 0); total.assign(n_samples, 0); froh.assign(n_samples, std::nan(""));
+    for (size_t i = 0; i < n; ++i)
+        if (keep[i]) { nseg[segs[5 * i]] += 1; total[segs[5 * i]] += positions[segs[5 * i + 2]] - positions[segs[5 * i + 1]]; }
+    if (genome > 0) for (size_t s = 0; s < n_samples; ++s) froh[s] = (double)total[s] / (double)genome;
+}
+// P.hom: `#FID IID CHROM SNP1 SNP2 POS1 POS2 KB NSNP DENSITY PHOM PHET`, one line per kept record; P.hom.indiv: `#FID IID NSEG KB KBAVG FROH`
+inline void write_hom(const std::string& prefix, const std::vector<std::string>& fids, const std::vector<std::string>& iids,
+                      const std::vector<std::string>& chromosomes, const std::vector<std::string>& variant_ids, const std::vector<int64_t>& positions,
+                      const std::vector<uint32_t>& segs, const std::vector<uint8_t>& keep, const std::vector<uint8_t>& brk) {
+    const size_t n = iids.size(), nrec = segs.size() / 5;
+    if (fids.size() != n || keep.size() != nrec || chromosomes.size() != positions.size() || variant_ids.size() != positions.size())
+        throw std::runtime_error("write_hom: one FID per IID, one keep flag per record, one chromosome and id per position");
+    std::vector<int64_t> nseg, total;
+    std::vector<double> froh;
+    roh_summary(segs, keep, positions, brk, n, nseg, total, froh);
+    char b[4][48];
+    {
+        OutFile o(prefix + ".hom");
+        std::fputs("#FID\tIID\tCHROM\tSNP1\tSNP2\tPOS1\tPOS2\tKB\tNSNP\tDENSITY\tPHOM\tPHET\n", o.f);
+        for (size_t i = 0; i < nrec; ++i) {
+            if (!keep[i]) continue;
+            const size_t s = segs[5 * i], first = segs[5 * i + 1], last = segs[5 * i + 2];
+            const int64_t nsnp = (int64_t)last - (int64_t)first + 1, nh = segs[5 * i + 3], nm = segs[5 * i + 4];
+            const double kb = (double)(positions[last] - positions[first]) / 1000.0;
+            fmt_g6(b[0], kb); fmt_g6(b[1], kb / (double)nsnp); fmt_g6(b[2], (double)(nsnp - nh - nm) / (double)nsnp); fmt_g6(b[3], (double)nh / (double)nsnp);
+            std::fprintf(o.f, "%s\t%s\t%s\t%s\t%s\t%lld\t%lld\t%s\t%lld\t%s\t%s\t%s\n", fids[s].c_str(), iids[s].c_str(), chromosomes[first].c_str(),
+                         variant_ids[first].c_str(), variant_ids[last].c_str(), (long long)positions[first], (long long)positions[last], b[0],
+                         (long long)nsnp, b[1], b[2], b[3]);
+        }
+    }
+    OutFile o(prefix + ".hom.indiv");
+    std::fputs("#FID\tIID\tNSEG\tKB\tKBAVG\tFROH\n", o.f);
+    for (size_t i = 0; i < n; ++i) {
+        const double kb = (double)total[i] / 1000.0;
+        fmt_g6(b[0], kb); fmt_g6(b[1], nseg[i] == 0 ? std::nan("") : kb / (double)nseg[i]); fmt_g6(b[2], froh[i]);
+        std::fprintf(o.f, "%s\t%s\t%lld\t%s\t%s\t%s\n", fids[i].c_str(), iids[i].c_str(), (long long)nseg[i], b[0], b[1], b[2]);
+    }
+}
+// the threshold of --gpca-homozyg-window-threshold as the exact fraction of its decimal text (digits, one optional point, no exponent),
+// reduced; false when the text is not such a number or the reduced denominator is above 2^20 (io / engine: Fraction(str(x)))
+inline bool roh_threshold(const std::string& text, int64_t& num, int64_t& den) {
+    size_t i = 0;
+    __int128 n = 0, d = 1;
+    bool point = false, any = false;
+    for (; i < text.size(); ++i) {
+        const char c = text[i];
+        if (c == '.' && !point) { point = true; continue; }
+        if (c < '0' || c > '9') return false;
+        any = true;
+        n = n * 10 + (c - '0');
+        if (point) d *= 10;
+        if (d > (__int128)1 << 100 || n > (__int128)1 << 100) return false;          // (before either can pass 2^127)
+    }
+    if (!any) return false;
+    __int128 a = n, b = d;
+    while (b) { const __int128 t = a % b; a = b; b = t; }
+    if (a > 1) { n /= a; d /= a; }
+    if (d > ((__int128)1 << 20) || n > ((__int128)1 << 30)) return false;
+    num = (int64_t)n; den = (int64_t)d;
+    return true;
+}
+
 }  // namespace gpca_host
 
 #endif

@@ -83,6 +83,12 @@ struct Args {
     bool have_mind = false, have_het_sd = false;   // --gpca-mind X, --gpca-het-sd K: the sample filters, P.sampleqc.in.id / .out.id
     double mind = 0.0, het_sd = 0.0;
     bool sample_qc_asked() const { return sample_missing || het || have_mind || have_het_sd; }
+    bool homozyg = false;                          // --gpca-homozyg (or any of its value flags): P.hom and P.hom.indiv
+    int64_t hom_window_snp = 50, hom_window_het = 1, hom_window_missing = 5, hom_snp = 100, hom_het = -1;
+    bool have_hom_het = false;
+    std::string hom_threshold = "0.05";
+    int64_t hom_thr_num = 1, hom_thr_den = 20;     // the threshold's exact fraction, set in main
+    double hom_kb = 1000.0, hom_density = 50.0, hom_gap = 1000.0;
 };
 
 [[noreturn]] void usage_error(const std::string& msg) {
@@ -237,6 +243,19 @@ void print_help() {
         "                                       sample is still projected\n"
         "      --gpca-het-sd <K>                --eigensnp: drop a sample whose F lies more than K standard deviations from the mean F of\n"
         "                                       the samples that pass --gpca-mind (K > 0; one round) -> <out>.sampleqc.in.id / .out.id\n"
+        "      --gpca-homozyg                   --eigensnp: runs of homozygosity of every sample over the SNPs that pass the SNP QC (plink\n"
+        "                                       --homozyg's sliding window) -> <out>.hom (#FID IID CHROM SNP1 SNP2 POS1 POS2 KB NSNP DENSITY\n"
+        "                                       PHOM PHET) and <out>.hom.indiv (#FID IID NSEG KB KBAVG FROH); any flag below implies it\n"
+        "      --gpca-homozyg-window-snp <W>    the scanning window in SNPs (1 .. 64) [default: 50]\n"
+        "      --gpca-homozyg-window-het <H>    het calls a window may hold and still be a hit (0 .. W) [default: 1]\n"
+        "      --gpca-homozyg-window-missing <M>  missing calls a window may hold and still be a hit (0 .. W) [default: 5]\n"
+        "      --gpca-homozyg-window-threshold <X>  the share of hits among the windows over a SNP that puts it in a run, a decimal\n"
+        "                                       number in [0, 1] taken as its exact fraction [default: 0.05]\n"
+        "      --gpca-homozyg-snp <N>           SNPs a run needs at least [default: 100]\n"
+        "      --gpca-homozyg-kb <X>            kb a run spans at least [default: 1000]\n"
+        "      --gpca-homozyg-density <X>       kb per SNP a run holds at most [default: 50]\n"
+        "      --gpca-homozyg-gap <X>           a gap of more than X kb between two SNPs ends a run [default: 1000]\n"
+        "      --gpca-homozyg-het <N>           het calls a run holds at most [default: no limit]\n"
         "      --gpca-assoc-pcs <P>             --gpca-assoc-pheno: the first P columns of the scores this run writes are covariates\n"
         "                                       (0 <= P <= --eigensnp-k-global) [default: every column]\n"
         "      --gpca-assoc-covar <FILE>        --gpca-assoc-pheno: further covariates, a table in the format of the phenotype file\n"
@@ -334,6 +353,16 @@ Args parse(int argc, char** argv) {
         else if (f == "--gpca-het") a.het = true;
         else if (f == "--gpca-mind") { a.mind = to_f64(f, val()); a.have_mind = true; }
         else if (f == "--gpca-het-sd") { a.het_sd = to_f64(f, val()); a.have_het_sd = true; }
+        else if (f == "--gpca-homozyg") a.homozyg = true;
+        else if (f == "--gpca-homozyg-window-snp") { a.hom_window_snp = to_i64(f, val()); a.homozyg = true; }
+        else if (f == "--gpca-homozyg-window-het") { a.hom_window_het = to_i64(f, val()); a.homozyg = true; }
+        else if (f == "--gpca-homozyg-window-missing") { a.hom_window_missing = to_i64(f, val()); a.homozyg = true; }
+        else if (f == "--gpca-homozyg-window-threshold") { a.hom_threshold = val(); a.homozyg = true; }
+        else if (f == "--gpca-homozyg-snp") { a.hom_snp = to_i64(f, val()); a.homozyg = true; }
+        else if (f == "--gpca-homozyg-kb") { a.hom_kb = to_f64(f, val()); a.homozyg = true; }
+        else if (f == "--gpca-homozyg-density") { a.hom_density = to_f64(f, val()); a.homozyg = true; }
+        else if (f == "--gpca-homozyg-gap") { a.hom_gap = to_f64(f, val()); a.homozyg = true; }
+        else if (f == "--gpca-homozyg-het") { a.hom_het = to_i64(f, val()); a.have_hom_het = true; a.homozyg = true; }
         else if (f == "--gpca-assoc-pcs") { a.assoc_pcs = to_i64(f, val()); a.have_assoc_pcs = true; }
         else if (f == "--gpca-assoc-vif") { a.assoc_vif = to_f64(f, val()); a.have_assoc_vif = true; }
         else if (f == "--gpca-ld-score") a.ld_score = val();
@@ -919,6 +948,57 @@ int run_sample_qc(gpca::Engine& eng, const Args& a, const std::vector<std::strin
     return 0;
 }
 
+const char* const kHomozygNeedsResident =
+    "error: --gpca-homozyg needs the genotype matrix resident on the device: the runs of homozygosity of a matrix walked out of core are "
+    "not implemented\n";
+
+// kb on the command line -> bp: x 1000 rounded half up (cli.py: math.floor(x * 1000.0 + 0.5))
+inline int64_t kb_to_bp(double kb) { return (int64_t)std::floor(kb * 1000.0 + 0.5); }
+
+// --gpca-homozyg: the runs of homozygosity (gpca_roh, in bands cut at chromosome starts) of every sample over every SNP that passes the
+// SNP QC, the length and density rule on the records (gpca_roh_select), P.hom and P.hom.indiv.  Sets the keep mask to the QC mask (mu,
+// sigma unchanged); the caller sets its own afterwards (cli.py:_homozyg).
+int run_homozyg(gpca::Engine& eng, const Args& a, const gpca_host::PlinkFileset& fs, const std::vector<std::string>& fids,
+                const std::vector<std::string>& sample_ids, const gpca::SnpStats& st) {
+    eng.set_standardization(st.mu, st.sigma, st.keep);                                 // every SNP that passes the SNP QC
+    std::vector<std::string> chroms, ids;
+    std::vector<int64_t> pos;
+    for (size_t i = 0; i < st.keep.size(); ++i)
+        if (st.keep[i]) { chroms.push_back(fs.chromosomes[i]); ids.push_back(fs.variant_ids[i]); pos.push_back(fs.positions[i]); }
+    const std::vector<uint8_t> brk = gpca_host::roh_breaks(chroms, pos, kb_to_bp(a.hom_gap));
+    gpca_roh_params par{};
+    par.window_snp = (int32_t)a.hom_window_snp; par.window_het = (int32_t)a.hom_window_het; par.window_missing = (int32_t)a.hom_window_missing;
+    par.thr_num = (int32_t)a.hom_thr_num; par.thr_den = (int32_t)a.hom_thr_den; par.min_snp = (int32_t)a.hom_snp;
+    par.max_het = a.have_hom_het ? (int32_t)a.hom_het : -1;
+    std::vector<uint32_t> segs;                                                        // bands in row order: ordered by sample below
+    try {
+        for (const auto& b : gpca_host::roh_bands(brk)) {
+            std::vector<uint32_t> s, c;
+            eng.roh(b.first, b.second, std::vector<uint8_t>(brk.begin() + b.first, brk.begin() + b.second), par, s, c);
+            segs.insert(segs.end(), s.begin(), s.end());
+        }
+    } catch (const gpca::Error& e) {
+        if (e.status() != GPCA_ERR_STATE) throw;
+        std::fputs(kHomozygNeedsResident, stderr);
+        return 1;
+    }
+    // ascending (sample, first): the bands are disjoint in rows, so a stable sort by sample keeps the positions in order
+    const size_t nrec = segs.size() / 5;
+    std::vector<size_t> order(nrec);
+    for (size_t i = 0; i < nrec; ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return segs[5 * x] < segs[5 * y]; });
+    std::vector<uint32_t> sorted(segs.size());
+    for (size_t i = 0; i < nrec; ++i) std::copy(segs.begin() + 5 * order[i], segs.begin() + 5 * order[i] + 5, sorted.begin() + 5 * i);
+    const std::vector<uint8_t> keep = gpca::Engine::roh_select(sorted, pos, kb_to_bp(a.hom_kb), kb_to_bp(a.hom_density));
+    gpca_host::ensure_parent(a.output_prefix);
+    gpca_host::write_hom(a.output_prefix, fids, sample_ids, chroms, ids, pos, sorted, keep, brk);
+    char buf[384];
+    std::snprintf(buf, sizeof buf, "runs of homozygosity of %zu samples over %zu SNPs: %lld of %zu runs pass the length and density rule, written to %s.hom",
+                  sample_ids.size(), pos.size(), (long long)std::count(keep.begin(), keep.end(), (uint8_t)1), nrec, a.output_prefix.c_str());
+    logmsg(buf);
+    return 0;
+}
+
 int run_eigensnp_workflow(Args a) {
     if (a.bed_file.empty() || a.ld_block_file.empty()) {
         std::fprintf(stderr, "error: --bed-file and --ld-block-file are required when --eigensnp is used\n");           // main.rs:296-301
@@ -946,6 +1026,7 @@ int run_eigensnp_workflow(Args a) {
     if (streamed && !a.assoc_pheno.empty()) { std::fputs(kAssocNeedsResident, stderr); return 1; }
     if (streamed && !a.within.empty()) { std::fputs(kStratNeedsResident, stderr); return 1; }
     if (streamed && a.sample_qc_asked()) { std::fputs(kSampleQcNeedsResident, stderr); return 1; }
+    if (streamed && a.homozyg) { std::fputs(kHomozygNeedsResident, stderr); return 1; }
     if (streamed && !a.ld_score.empty()) { std::fputs(kLdScoreNeedsResident, stderr); return 1; }
     const gpca::SnpStats st = eng.snp_stats(gpca::QcConfig{a.min_call_rate, a.min_maf, a.max_hwe_p});
     std::vector<uint8_t> qc_pass;                                                                                       // empty: no sample filter
@@ -953,6 +1034,12 @@ int run_eigensnp_workflow(Args a) {
         std::vector<std::string> fids = fs.family_ids;
         if (use_kept) { fids.clear(); for (int64_t c : kept.cols) fids.push_back(fs.family_ids[(size_t)c]); }
         const int rc = run_sample_qc(eng, a, fids, sample_ids, st, qc_pass);
+        if (rc != 0) return rc;
+    }
+    if (a.homozyg && !sample_ids.empty() && std::count(st.keep.begin(), st.keep.end(), (uint8_t)1) > 0) {
+        std::vector<std::string> fids = fs.family_ids;
+        if (use_kept) { fids.clear(); for (int64_t c : kept.cols) fids.push_back(fs.family_ids[(size_t)c]); }
+        const int rc = run_homozyg(eng, a, fs, fids, sample_ids, st);
         if (rc != 0) return rc;
     }
     const auto blocks = gpca_host::parse_ld_block_file(a.ld_block_file);
@@ -1331,6 +1418,26 @@ int main(int argc, char** argv) {
                 return 2;
             }
             if (a.stream == "on") { std::fputs(kSampleQcNeedsResident, stderr); return 2; }
+        }
+        if (a.homozyg) {
+            if (!a.eigensnp) { std::fprintf(stderr, "error: --gpca-homozyg needs the --eigensnp workflow\n"); return 2; }
+            if (!(a.hom_window_snp >= 1 && a.hom_window_snp <= GPCA_ROH_WINDOW_MAX)) { std::fprintf(stderr, "error: --gpca-homozyg-window-snp must lie in [1, 64]\n"); return 2; }
+            if (!(a.hom_window_het >= 0 && a.hom_window_het <= a.hom_window_snp && a.hom_window_missing >= 0 && a.hom_window_missing <= a.hom_window_snp)) {
+                std::fprintf(stderr, "error: --gpca-homozyg-window-het and --gpca-homozyg-window-missing must lie in [0, --gpca-homozyg-window-snp]\n");
+                return 2;
+            }
+            if (!gpca_host::roh_threshold(a.hom_threshold, a.hom_thr_num, a.hom_thr_den) || a.hom_thr_num > a.hom_thr_den) {
+                std::fprintf(stderr, "error: --gpca-homozyg-window-threshold must be a decimal number in [0, 1] whose exact fraction has a denominator of at most 2^20\n");
+                return 2;
+            }
+            if (!(a.hom_snp >= 1 && a.hom_snp <= 2147483647LL)) { std::fprintf(stderr, "error: --gpca-homozyg-snp must lie in [1, 2^31)\n"); return 2; }
+            for (double v : {a.hom_kb, a.hom_density, a.hom_gap})
+                if (!(v >= 0.0 && v <= 1e12)) {
+                    std::fprintf(stderr, "error: --gpca-homozyg-kb, --gpca-homozyg-density and --gpca-homozyg-gap must lie in [0, 1e12]\n");
+                    return 2;
+                }
+            if (a.have_hom_het && !(a.hom_het >= 0 && a.hom_het <= 2147483647LL)) { std::fprintf(stderr, "error: --gpca-homozyg-het must lie in [0, 2^31)\n"); return 2; }
+            if (a.stream == "on") { std::fputs(kHomozygNeedsResident, stderr); return 2; }
         }
         if (!a.assoc_pheno.empty()) {
             if (!a.eigensnp) { std::fprintf(stderr, "error: --gpca-assoc-pheno needs the --eigensnp workflow\n"); return 2; }

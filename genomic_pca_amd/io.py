@@ -1288,3 +1288,134 @@ def write_sample_qc_ids(prefix: str, family_ids: Sequence[str], sample_ids: Sequ
             else:
                 fo.write(f"{family_ids[i]}\t{sample_ids[i]}\t{reason[i]}\n")
     return pin, pout
+
+
+# ---- runs of homozygosity (gpca_roh, gpca_roh_select): twins in host/formats.hpp -----------------------------------------------------------
+def roh_breaks(chromosomes: Sequence[str], positions: Sequence[int], max_gap_bp: int) -> np.ndarray:
+    """brk [K] (uint8) over the kept SNPs, in their order, for gpca_roh: 3 at the first SNP of every chromosome run (a window domain
+    starts, and no run continues into it), 2 at a SNP that lies more than max_gap_bp behind the SNP before it, else 0.  A chromosome
+    that reappears after another, or positions that decrease inside a run, is an error that names the variant (by its index among the
+    SNPs given), as in ld_windows."""
+    K = len(chromosomes)
+    pos = np.asarray(positions, np.int64)
+    if pos.shape != (K,):
+        raise ValueError("roh_breaks: one position per chromosome entry")
+    if int(max_gap_bp) < 0:
+        raise ValueError("roh_breaks: the gap must be at least 0")
+    brk = np.zeros(K, np.uint8)
+    seen = set()
+    s = 0
+    while s < K:
+        c = normalize_chromosome_name(chromosomes[s])
+        if c in seen:
+            raise ValueError(f"roh_breaks: chromosome '{chromosomes[s]}' reappears at variant {s} after another chromosome: sort the variants")
+        seen.add(c)
+        brk[s] = 3
+        e = s + 1
+        while e < K and normalize_chromosome_name(chromosomes[e]) == c:
+            if pos[e] < pos[e - 1]:
+                raise ValueError(f"roh_breaks: the position of variant {e} ({int(pos[e])}) is below that of the variant before it on chromosome "
+                                 f"'{chromosomes[e]}': sort the variants")
+            if int(pos[e]) - int(pos[e - 1]) > int(max_gap_bp):
+                brk[e] = 2
+            e += 1
+        s = e
+    return brk
+
+
+def roh_bands(brk, max_rows: int = 1 << 24):
+    """[row0, row1) bands over the rows of brk that are cut only where a window domain starts (bit 0): whole domains are added to a band
+    while it stays within max_rows rows; a domain longer than that is a band of its own.  The bands gpca_roh is asked for, one at a
+    time: their records and counts add up to the full call's."""
+    bv = np.asarray(brk, np.uint8)
+    K = bv.size
+    starts = [0] + [int(j) for j in np.nonzero(bv & 1)[0] if j > 0] + [K]
+    out = []
+    r0 = 0
+    for d in range(1, len(starts)):
+        if d + 1 < len(starts) and starts[d + 1] - r0 <= max(int(max_rows), 1):
+            continue
+        if starts[d] > r0:
+            out.append((r0, starts[d]))
+        r0 = starts[d]
+    return out
+
+
+def roh_select(segs, positions, min_bp: int, max_bp_per_snp: int) -> np.ndarray:
+    """keep [n] (uint8) of the records segs [n][5] = sample, first, last, n_het, n_missing (first and last index positions [K]), in
+    integers: span = pos[last] - pos[first]; 1 iff span >= min_bp and span <= max_bp_per_snp x (last - first + 1).  The twin of
+    gpca_roh_select."""
+    sv = np.asarray(segs, np.int64).reshape(-1, 5)
+    pos = np.asarray(positions, np.int64)
+    keep = np.zeros(sv.shape[0], np.uint8)
+    for i in range(sv.shape[0]):
+        first, last = int(sv[i, 1]), int(sv[i, 2])
+        if last < first:
+            raise ValueError(f"roh_select: record {i} ends before it starts")
+        span = int(pos[last]) - int(pos[first])
+        keep[i] = 1 if span >= int(min_bp) and span <= int(max_bp_per_snp) * (last - first + 1) else 0
+    return keep
+
+
+def roh_summary(segs, keep, positions, brk, n_samples: int):
+    """Per sample, from the kept records: (NSEG int64 [N], total bp int64 [N], FROH float64 [N]).  total bp = the sum of
+    pos[last] - pos[first] over the sample's kept records; FROH = total bp / genome, genome = the sum over the window domains (bit 0 of
+    brk; row 0 starts one) of pos[last row] - pos[first row]; NaN when that sum is 0."""
+    sv = np.asarray(segs, np.int64).reshape(-1, 5)
+    kv = np.asarray(keep).reshape(-1)
+    pos = np.asarray(positions, np.int64)
+    bv = np.asarray(brk, np.uint8)
+    K = bv.size
+    if kv.shape[0] != sv.shape[0] or pos.shape != (K,):
+        raise ValueError("roh_summary: one keep flag per record and one position per row of brk")
+    starts = [0] + [int(j) for j in np.nonzero(bv & 1)[0] if j > 0] + [K]
+    genome = 0
+    for d in range(len(starts) - 1):
+        if starts[d + 1] > starts[d]:
+            genome += int(pos[starts[d + 1] - 1]) - int(pos[starts[d]])
+    nseg = np.zeros(int(n_samples), np.int64)
+    total = np.zeros(int(n_samples), np.int64)
+    for i in range(sv.shape[0]):
+        if kv[i]:
+            nseg[sv[i, 0]] += 1
+            total[sv[i, 0]] += int(pos[sv[i, 2]]) - int(pos[sv[i, 1]])
+    froh = np.full(int(n_samples), np.nan)
+    if genome > 0:
+        for n in range(int(n_samples)):
+            froh[n] = float(int(total[n])) / float(genome)
+    return nseg, total, froh
+
+
+def write_hom(prefix: str, family_ids: Sequence[str], sample_ids: Sequence[str], chromosomes: Sequence[str], variant_ids: Sequence[str],
+              positions: Sequence[int], segs, keep, brk) -> Tuple[str, str]:
+    """P.hom (plink --homozyg's segment table): one tab-separated line per kept record, in sample order then by position,
+    `#FID IID CHROM SNP1 SNP2 POS1 POS2 KB NSNP DENSITY PHOM PHET`: KB = span / 1000, DENSITY = KB / NSNP, PHOM = (NSNP - het -
+    missing) / NSNP, PHET = het / NSNP, each as %.6g.  P.hom.indiv: one line per sample, `#FID IID NSEG KB KBAVG FROH` (roh_summary):
+    KB = total bp / 1000, KBAVG = KB / NSEG (NA without a segment), FROH (NA where undefined).  chromosomes, variant_ids and positions
+    are those of the kept SNPs."""
+    sv = np.asarray(segs, np.int64).reshape(-1, 5)
+    kv = np.asarray(keep).reshape(-1)
+    pos = np.asarray(positions, np.int64)
+    n = len(sample_ids)
+    if len(family_ids) != n or kv.shape[0] != sv.shape[0] or len(chromosomes) != pos.size or len(variant_ids) != pos.size:
+        raise ValueError("write_hom: one FID per IID, one keep flag per record, one chromosome and id per position")
+    nseg, total, froh = roh_summary(sv, kv, pos, brk, n)
+    phom, pind = f"{prefix}.hom", f"{prefix}.hom.indiv"
+    with _open_out(phom, False) as f:
+        f.write("#FID\tIID\tCHROM\tSNP1\tSNP2\tPOS1\tPOS2\tKB\tNSNP\tDENSITY\tPHOM\tPHET\n")
+        for i in range(sv.shape[0]):
+            if not kv[i]:
+                continue
+            s, first, last, nh, nm = (int(v) for v in sv[i])
+            nsnp = last - first + 1
+            kb = float(int(pos[last]) - int(pos[first])) / 1000.0
+            f.write(f"{family_ids[s]}\t{sample_ids[s]}\t{chromosomes[first]}\t{variant_ids[first]}\t{variant_ids[last]}\t{int(pos[first])}\t"
+                    f"{int(pos[last])}\t{_g6(kb)}\t{nsnp}\t{_g6(kb / float(nsnp))}\t{_g6(float(nsnp - nh - nm) / float(nsnp))}\t"
+                    f"{_g6(float(nh) / float(nsnp))}\n")
+    with _open_out(pind, False) as f:
+        f.write("#FID\tIID\tNSEG\tKB\tKBAVG\tFROH\n")
+        for i in range(n):
+            kb = float(int(total[i])) / 1000.0
+            f.write(f"{family_ids[i]}\t{sample_ids[i]}\t{int(nseg[i])}\t{_g6(kb)}\t{'NA' if nseg[i] == 0 else _g6(kb / float(int(nseg[i])))}\t"
+                    f"{_g6(froh[i])}\n")
+    return phom, pind

@@ -790,6 +790,60 @@ GPCA_API int gpca_ld_score_total(const int64_t* acc /* [K] */, int64_t K, double
 GPCA_API int gpca_ldsc_fit(const double* chi2, const double* ell, const double* w_ell /* NULL = ell */, int64_t m, double n_samples, double M,
                            int32_t n_blocks, double chi2_max, double* out /* [10] */);
 
+/* ---- a20: runs of homozygosity (plink --homozyg): per sample, the stretches of consecutive kept SNPs that a sliding window calls
+ * homozygous, and from them F_ROH, the share of the genome inside runs.  Where a18's F is one number per sample, the runs tell a sample
+ * with a few long autozygous tracts (recent consanguinity) from one whose excess homozygosity is spread thin.
+ * gpca_roh works on the kept rows [row0, row1) of a resident handle, in PCA-SNP order, and on all N samples (the sample mask is
+ * ignored, as in a18).  A call is 0, 1, 2 or missing; "het" means 1.
+ *  brk [row1 - row0], one byte per row: bit 0 = a window domain starts at this row (a new chromosome); bit 1 = a run may not continue
+ *     from the previous row into this one (a new chromosome, or a gap above the caller's limit).  Bit 0 without bit 1, or any other bit
+ *     set, is GPCA_ERR_BAD_ARG naming the row.  Row row0 is taken as 3 whatever it holds: a band is a world of its own, and the caller
+ *     cuts its bands at domain starts.
+ *  gpca_roh_params: window_snp W (1 .. GPCA_ROH_WINDOW_MAX = 64); window_het H and window_missing M (each 0 .. W); thr_num and thr_den
+ *     (0 <= num <= den, 1 <= den <= 2^20); min_snp >= 1; max_het (-1 = no limit, else >= 0).
+ *  1. Windows.  Inside a domain of L rows, window s covers rows s .. s + W - 1 of the domain, s = 0 .. L - W; a domain shorter than W has
+ *     no window.  For a sample, window s is a hit iff its het calls <= H and its missing calls <= M.
+ *  2. SNPs.  Row j of the domain is covered by the windows s with max(0, j - W + 1) <= s <= min(j, L - W); cov = their number, hits = the
+ *     number of them that are hits for the sample.  The row is in-ROH for the sample iff cov > 0 and hits den >= num cov: exact
+ *     integers, no float decides a row.
+ *  3. Runs.  A run is a maximal stretch of consecutive kept rows that are in-ROH for the sample, cut before every row with bit 1 set.
+ *     Its record is five uint32: (sample, first, last, n_het, n_missing); first and last are kept-row indices of the handle (absolute,
+ *     not relative to the band), n_het and n_missing the sample's het and missing calls on the run's rows.  A run is reported iff
+ *     last - first + 1 >= min_snp and (max_het < 0 or n_het <= max_het).
+ *  4. Output.  seg_count [N] (uint32) = the reported runs of every sample, always complete; *n_found = their sum; segs [cap][5] = the
+ *     first min(cap, n_found) records in ascending (sample, first) order.  n_found > cap is GPCA_OK: the caller comes back with a larger
+ *     buffer.  segs may be NULL iff cap = 0.  An empty band writes zeros.  The order and every value are independent of the launch
+ *     plan; int8 and 2-bit residency and a GPCA_PREC_F32_MFMA handle give the same bits; no fitted result is touched.
+ *  Device: the access pattern of a18 (a thread owns 16 consecutive samples, a workgroup 1 024 samples and one row split).  A first
+ *     kernel keeps, per sample, byte-wise running het and missing counts of the last W rows (the entering row added, the row W behind
+ *     fetched again and subtracted) and the hits among the last W windows (a window's hit bits wait in a ring of 64 windows in LDS
+ *     until they leave), decides row j when the last window that covers it completes (W - 1 rows later, or at the domain's end), and
+ *     writes one bit per (row, sample); a split reads a halo of W - 1 rows on either side, clipped at the domain.  A second kernel, run
+ *     as a count pass and as a fill pass, walks the bits over its split's rows, fetching genotypes only where a wave ballot finds a
+ *     run; what crosses a boundary between two splits is joined by a third kernel, a thread per sample; an exclusive scan of the
+ *     counts (per sample over the splits on the device, over the samples on the host) puts the fill in order.  No float, no atomic
+ *     on an output.  GPCA_ROH_SPLITS in the environment, read per call, forces the split count, clamped to 1 .. rows: a test hook.
+ *  Errors: GPCA_ERR_STATE (no genotypes, a streamed handle, a row-sharded handle, no standardisation, K = 0), GPCA_ERR_BAD_ARG (a NULL
+ *     brk, params, seg_count or n_found; segs NULL with cap > 0; cap < 0; a row range out of bounds; a band of 2^31 or more rows; K of
+ *     2^32 or more; a bad brk byte; a parameter out of range), GPCA_ERR_INVALID_GENOTYPE (a row of the band holds a value outside
+ *     {0, 1, 2, missing} on a sample below N; the message names the row, as in a12), GPCA_ERR_OOM (checked before any allocation).
+ * Length in bp and SNP density need positions; they are a host rule on the records, in integers.
+ *  gpca_roh_select: segs [n][5] as gpca_roh gives them, pos [K] = the position of every kept row.  span = pos[last] - pos[first];
+ *     keep[i] = 1 iff span >= min_bp and span <= max_bp_per_snp (last - first + 1), else 0.  GPCA_ERR_BAD_ARG: a NULL argument with n > 0,
+ *     n < 0, min_bp < 0, max_bp_per_snp < 0, a record with last < first.
+ *  Not there: W > 64; plink's own printed digits and its float comparison at the threshold; overlap pools and consensus segments
+ *     (--homozyg-group); kb-based scanning windows; haploid and sex chromosomes; streamed and row-sharded handles. */
+#define GPCA_ROH_WINDOW_MAX 64
+typedef struct gpca_roh_params {
+    int32_t window_snp, window_het, window_missing;
+    int32_t thr_num, thr_den;
+    int32_t min_snp, max_het;
+} gpca_roh_params;
+GPCA_API int gpca_roh(gpca_handle* h, int64_t row0, int64_t row1, const uint8_t* brk /* [row1 - row0] */, const gpca_roh_params* params,
+                      uint32_t* seg_count /* [N] */, uint32_t* segs /* [cap][5]; NULL iff cap = 0 */, int64_t cap, int64_t* n_found);
+GPCA_API int gpca_roh_select(const uint32_t* segs /* [n][5] */, int64_t n, const int64_t* pos /* [K] */, int64_t min_bp,
+                             int64_t max_bp_per_snp, uint8_t* keep /* [n] */);
+
 /* ---- f3: the stages of EigenSNPCoreAlgorithm::compute_pca (main.rs:311-327, 359-366) ------------------------------------------
  * The algorithm lives in the un-vendored efficient_pca crate (Cargo.toml:30, branch "main", no pinned revision): what follows is
  * the stage structure of its published description -- per-LD-block local bases learnt on a sample subset, condensed features of

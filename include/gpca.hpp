@@ -418,6 +418,37 @@ public:
         counts.resize(3 * N);
         if (qsum) qsum->resize(N);
     }
+    // runs of homozygosity (gpca_roh; gpca.h section a20) over the kept rows [row0, row1) and all samples: brk = one byte per row of the
+    // band (bit 0: a window domain starts, bit 1: no run continues into the row); segs [n][5] = sample, first, last, n_het, n_missing in
+    // ascending (sample, first) order, seg_count [N].  Comes back with a larger buffer itself when the first one was short.
+    void roh(int64_t row0, int64_t row1, const std::vector<uint8_t>& brk, const gpca_roh_params& params, std::vector<uint32_t>& segs,
+             std::vector<uint32_t>& seg_count) const {
+        const size_t N = (size_t)dims().second, rows = row1 > row0 ? (size_t)(row1 - row0) : 0;
+        if (brk.size() != rows) throw std::invalid_argument("roh: brk needs one entry per row of the band");
+        seg_count.assign(std::max<size_t>(N, 1), 0u);
+        static const uint8_t none = 0;
+        int64_t cap = (int64_t)std::max<size_t>(4 * N, 1024), found = 0;
+        for (;;) {
+            segs.assign((size_t)cap * 5, 0u);
+            check(gpca_roh(h_, row0, row1, rows ? brk.data() : &none, &params, seg_count.data(), segs.data(), cap, &found));
+            if (found <= cap) break;
+            cap = found;
+        }
+        segs.resize((size_t)found * 5);
+        seg_count.resize(N);
+    }
+    // the host rule on the records (gpca_roh_select; host only): keep [n] by length in bp and bp per SNP; pos [K] = the kept rows' positions
+    static std::vector<uint8_t> roh_select(const std::vector<uint32_t>& segs, const std::vector<int64_t>& pos, int64_t min_bp, int64_t max_bp_per_snp) {
+        const size_t n = segs.size() / 5;
+        std::vector<uint8_t> keep(std::max<size_t>(n, 1), 0);
+        int rc = segs.size() != 5 * n ? GPCA_ERR_BAD_ARG : GPCA_OK;
+        for (size_t i = 0; rc == GPCA_OK && i < n; ++i)
+            if (segs[5 * i + 1] >= pos.size() || segs[5 * i + 2] >= pos.size()) rc = GPCA_ERR_BAD_ARG;
+        if (rc == GPCA_OK && n) rc = gpca_roh_select(segs.data(), (int64_t)n, pos.data(), min_bp, max_bp_per_snp, keep.data());
+        if (rc != GPCA_OK) throw Error(rc, std::string("gpca_roh_select: ") + gpca_status_string(rc));
+        keep.resize(n);
+        return keep;
+    }
     // the rows' weights for the heterozygosity F (gpca_het_weights; host only): qc [rows][4] as snp_qc_detail gives them
     static std::vector<uint32_t> het_weights(const std::vector<uint32_t>& qc) {
         const size_t rows = qc.size() / 4;
