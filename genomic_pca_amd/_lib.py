@@ -64,6 +64,16 @@ class gpca_roh_params(C.Structure):
                 ("thr_den", C.c_int32), ("min_snp", C.c_int32), ("max_het", C.c_int32)]
 
 
+class gpca_admix_params(C.Structure):
+    _fields_ = [("K", C.c_int32), ("max_iter", C.c_int32), ("seed", C.c_uint64), ("tol", C.c_double), ("accel", C.c_int32),
+                ("init", C.c_int32)]
+
+
+class gpca_admix_info(C.Structure):
+    _fields_ = [("steps", C.c_int64), ("cycles", C.c_int64), ("converged", C.c_int32), ("fallbacks", C.c_int32), ("loglik", C.c_double),
+                ("trace", C.c_void_p), ("trace_cap", C.c_int64)]
+
+
 class gpca_kernel_timing(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("launches", C.c_int64), ("total_ms", C.c_double), ("flops", C.c_double),
                 ("bytes", C.c_double)]
@@ -171,6 +181,9 @@ PROTOTYPES = {
     "gpca_ld_score_total": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
     "gpca_roh": (C.c_int, [_H, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "gpca_roh_select": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "gpca_admix_init": (C.c_int, [_H, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "gpca_admix_step": (C.c_int, [_H, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
+    "gpca_admix": (C.c_int, [_H, C.POINTER(gpca_admix_params), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(gpca_admix_info)]),
     "gpca_ldsc_fit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_int32, C.c_double, C.c_void_p]),
     "gpca_comm_get_unique_id": (C.c_int, [C.c_void_p]),
     "gpca_comm_init": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, C.c_int64]),

@@ -214,6 +214,18 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--gpca-homozyg-gap", type=float, default=None, metavar="X",
                    help="a gap of more than X kb between two SNPs ends a run [default: 1000]")
     p.add_argument("--gpca-homozyg-het", type=int, default=None, metavar="N", help="het calls a run holds at most [default: no limit]")
+    p.add_argument("--gpca-admixture", type=int, default=None, metavar="K",
+                   help="--eigensnp: admixture proportions of every sample in K ancestral populations (1 .. 16), the ADMIXTURE model "
+                        "fitted by accelerated EM over the SNPs the PCA is fitted on; samples outside the KING in-set or failing the "
+                        "sample QC get proportions without shaping the frequencies -> <out>.K.Q, .Q.id, .P, .P.id and .admix.log")
+    p.add_argument("--gpca-admixture-seed", type=int, default=None, metavar="S", help="the seed of the starting point [default: 0]")
+    p.add_argument("--gpca-admixture-max-iter", type=int, default=None, metavar="N", help="EM steps at most [default: 2000]")
+    p.add_argument("--gpca-admixture-tol", type=float, default=None, metavar="X",
+                   help="stop when a cycle gains less than X times the log-likelihood [default: 1e-7]")
+    p.add_argument("--gpca-admixture-no-accel", action="store_true", help="plain EM steps, without the SQUAREM acceleration")
+    p.add_argument("--gpca-admixture-supervised", action="store_true",
+                   help="the samples with a group in --gpca-within are references of known ancestry: K must be the number of groups, and "
+                        "column k of the result is group k")
     p.add_argument("--gpca-assoc-pcs", type=int, default=None, metavar="P",
                    help="--gpca-assoc-pheno: the first P columns of the scores this run writes are covariates (0 <= P <= "
                         "--eigensnp-k-global) [default: every column]")
@@ -351,7 +363,7 @@ def run_eigensnp_workflow(a) -> int:
         raise SystemExit(PCRELATE_NEEDS_RESIDENT)
     if streamed and a.gpca_assoc_pheno is not None:
         raise SystemExit(ASSOC_NEEDS_RESIDENT)
-    if streamed and a.gpca_within is not None:
+    if streamed and a.gpca_within is not None and (a.gpca_freq_strat or a.gpca_fst is not None):
         raise SystemExit(STRAT_NEEDS_RESIDENT)
     if streamed and _sample_qc_asked(a):
         raise SystemExit(SAMPLE_QC_NEEDS_RESIDENT)
@@ -359,6 +371,8 @@ def run_eigensnp_workflow(a) -> int:
         raise SystemExit(HOMOZYG_NEEDS_RESIDENT)
     if streamed and a.gpca_ld_score is not None:
         raise SystemExit(LD_SCORE_NEEDS_RESIDENT)
+    if streamed and a.gpca_admixture is not None:
+        raise SystemExit(ADMIX_NEEDS_RESIDENT)
     st = eng.snp_stats(QcConfig(a.eigensnp_min_call_rate, a.eigensnp_min_maf, a.eigensnp_max_hwe_p))
     qc_pass = None
     if _sample_qc_asked(a) and len(sample_ids) and int(st["keep"].sum()):
@@ -427,9 +441,11 @@ def run_eigensnp_workflow(a) -> int:
             [fs.allele1[r] for r in rows], [fs.allele2[r] for r in rows], stz["mu"][rows], stz["sigma"][rows],
             np.asarray(out.final_snp_principal_component_loadings, np.float32), np.asarray(out.final_principal_component_eigenvalues, np.float64),
             n_fit))
+    if a.gpca_admixture is not None:                                                 # while the handle carries the PCA's keep mask
+        _admix(eng, a, fs, cols, sample_ids, rows, inset)
     if a.gpca_make_pcrelate is not None:
         _pcrelate(eng, a, fs, cols, sample_ids, np.asarray(scores, np.float64)[:, :a.gpca_make_pcrelate], inset, len(rows))
-    if a.gpca_within is not None:
+    if a.gpca_within is not None and (a.gpca_freq_strat or a.gpca_fst is not None):
         _strat(eng, a, fs, cols, sample_ids, st)
     l2 = _ld_score(eng, a, fs, st) if a.gpca_ld_score is not None else None
     if a.gpca_assoc_pheno is not None:
@@ -437,6 +453,44 @@ def run_eigensnp_workflow(a) -> int:
     eng.close()
     _log(f"EigenSNP workflow done in {time.time() - t0:.2f}s")
     return 0
+
+
+ADMIX_NEEDS_RESIDENT = ("error: --gpca-admixture needs the genotype matrix resident on the device: the fit of a matrix walked out of core "
+                        "is not implemented")
+
+
+def _admix(eng, a, fs, cols, sample_ids, rows, inset):
+    """--gpca-admixture K: the admixture fit (gpca_admix) over the rows the PCA was fitted on (the handle's keep mask as the PCA left
+    it: after the LD-block mapping and --gpca-indep-pairwise) and every sample: mode 0 inside the in-set of --gpca-king-cutoff and the
+    sample QC, mode 2 outside it, mode 1 for a sample with a group under --gpca-admixture-supervised.  Writes P.K.Q, .Q.id, .P, .P.id
+    and .admix.log with the columns in io.admix_order."""
+    from . import _lib
+    fids = fs.family_ids if cols is None else [fs.family_ids[i] for i in cols]
+    K, n = a.gpca_admixture, len(sample_ids)
+    seed = 0 if a.gpca_admixture_seed is None else a.gpca_admixture_seed
+    kw = dict(seed=seed, max_iter=2000 if a.gpca_admixture_max_iter is None else a.gpca_admixture_max_iter,
+              tol=1e-7 if a.gpca_admixture_tol is None else a.gpca_admixture_tol, accel=not a.gpca_admixture_no_accel)
+    mode = np.zeros(n, np.uint8) if inset is None else np.where(np.asarray(inset, bool), 0, 2).astype(np.uint8)
+    try:
+        if a.gpca_admixture_supervised:
+            labels, _names = gio.align_within(a.gpca_within_table, fids, sample_ids)
+            Q0, F0 = eng.admix_init(K, seed)
+            Q0, fixed = gio.admix_supervised(labels, K, Q0)
+            mode[fixed == 1] = 1                                                     # a labelled sample is a reference wherever it stands
+            r = eng.admix(K, mode=mode, Q=Q0, F=F0, **kw)
+        else:
+            r = eng.admix(K, mode=mode, **kw)
+    except _lib.GpcaError as e:
+        if e.status == _lib.GPCA_ERR_STATE:
+            raise SystemExit(ADMIX_NEEDS_RESIDENT) from None
+        raise
+    order = gio.admix_order(r["Q"], mode)
+    _ensure_parent(a.output_prefix)
+    gio.write_admix(a.output_prefix, K, fids, sample_ids, [fs.variant_ids[i] for i in rows], r["Q"][:, order], r["F"][:, order],
+                    dict(seed=seed, steps=r["steps"], cycles=r["cycles"], converged=r["converged"], loglik=r["loglik"]))
+    _log(f"admixture (K = {K}) of {n} samples ({int((mode == 1).sum())} references, {int((mode == 2).sum())} projected) over {len(rows)} SNPs: "
+         f"{r['steps']} steps, {'converged' if r['converged'] else 'not converged'}, log-likelihood {r['loglik']:.4f}, written to "
+         f"{a.output_prefix}.{K}.Q")
 
 
 LD_SCORE_NEEDS_RESIDENT = ("error: --gpca-ld-score needs the genotype matrix resident on the device: with the matrix walked out of core a "
@@ -1049,9 +1103,9 @@ def main(argv=None) -> int:
     if a.gpca_within is not None:
         if not a.eigensnp:
             raise SystemExit("error: --gpca-within needs the --eigensnp workflow")
-        if not a.gpca_freq_strat and a.gpca_fst is None:
+        if not a.gpca_freq_strat and a.gpca_fst is None and not a.gpca_admixture_supervised:
             raise SystemExit("error: --gpca-within needs --gpca-freq-strat or --gpca-fst")
-        if a.gpca_stream == "on":
+        if a.gpca_stream == "on" and (a.gpca_freq_strat or a.gpca_fst is not None):
             raise SystemExit(STRAT_NEEDS_RESIDENT)
         a.gpca_within_table = _within_table(a)
     if _sample_qc_asked(a):
@@ -1066,6 +1120,31 @@ def main(argv=None) -> int:
                              "the sample mask)")
         if a.gpca_stream == "on":
             raise SystemExit(SAMPLE_QC_NEEDS_RESIDENT)
+    if a.gpca_admixture is None and (a.gpca_admixture_seed is not None or a.gpca_admixture_max_iter is not None or
+                                     a.gpca_admixture_tol is not None or a.gpca_admixture_no_accel or a.gpca_admixture_supervised):
+        raise SystemExit("error: --gpca-admixture-seed, -max-iter, -tol, -no-accel and --gpca-admixture-supervised need --gpca-admixture")
+    if a.gpca_admixture is not None:
+        if not a.eigensnp:
+            raise SystemExit("error: --gpca-admixture needs the --eigensnp workflow")
+        if not 1 <= a.gpca_admixture <= 16:
+            raise SystemExit("error: --gpca-admixture K must lie in [1, 16]")
+        if a.gpca_admixture_seed is not None and not 0 <= a.gpca_admixture_seed < 1 << 63:
+            raise SystemExit("error: --gpca-admixture-seed must lie in [0, 2^63)")
+        if a.gpca_admixture_max_iter is not None and not 0 <= a.gpca_admixture_max_iter < 1 << 31:
+            raise SystemExit("error: --gpca-admixture-max-iter must lie in [0, 2^31)")
+        if a.gpca_admixture_tol is not None and not (0.0 <= a.gpca_admixture_tol < float("inf")):
+            raise SystemExit("error: --gpca-admixture-tol must be finite and at least 0")
+        if a.gpca_admixture_supervised:
+            if a.gpca_within is None:
+                raise SystemExit("error: --gpca-admixture-supervised needs --gpca-within")
+            if len(a.gpca_within_table.names) != a.gpca_admixture:
+                raise SystemExit(f"error: --gpca-admixture-supervised: K = {a.gpca_admixture} but --gpca-within names "
+                                 f"{len(a.gpca_within_table.names)} groups")
+        if a.gpca_eigensnp_local_stage:
+            raise SystemExit("error: --gpca-admixture cannot be combined with --gpca-eigensnp-local-stage (that stage owns the sample "
+                             "mask and the keep mask)")
+        if a.gpca_stream == "on":
+            raise SystemExit(ADMIX_NEEDS_RESIDENT)
     if _homozyg_asked(a):
         if not a.eigensnp:
             raise SystemExit("error: --gpca-homozyg needs the --eigensnp workflow")

@@ -438,4 +438,21 @@ int launch_roh_runs(hipStream_t st, const void* G, int packed, int64_t ldr, cons
                     const RohPlan& plan, const uint8_t* brk, const uint8_t* plane, int64_t min_snp, int64_t max_het, unsigned* rec,
                     unsigned* cnt, unsigned* seg_count, const unsigned long long* base, unsigned* segs, int64_t cap);
 
+// ---- admixture proportions (admix.hip; include/gpca.h section a21) over all `rows` kept rows (PCA-SNP order through krows) and all N
+// samples; extents: plan_math.h adm_*.  Q [N][K], F [rows][K] f32; mode [N] or NULL.  launch_admix_step: one EM step (k_admix_step, then
+// the slab sums with the F and Q updates and the sum of the log-likelihood terms): Qn, Fn and *ll (device f64); *bad as in launch_assoc.
+// launch_admix_init: a21's init from counts [M][4] (the QC counts of every row).  launch_admix_norms: nrm [2] = sum r^2, sum v^2 over Q and
+// F of three parameter sets.  launch_admix_extrap: (Qx, Fx) = the SQUAREM point of step length alpha, clamped.  The launches return
+// nonzero when an argument is outside the kernels' limits.
+struct AdmSet { float* Q; float* F; };
+int launch_admix_step(hipStream_t st, const void* G, int packed, int64_t ldr, const int64_t* krows, int64_t rows, int64_t N, int K,
+                      const float* Q, const float* F, const uint8_t* mode, float* fpart, float* qpart, double* llpart, float* Qn, float* Fn,
+                      double* ll, unsigned long long* bad);
+int launch_admix_init(hipStream_t st, const int64_t* krows, const unsigned* counts, int64_t rows, int64_t N, int K, uint64_t seed, float* Q,
+                      float* F);
+int launch_admix_norms(hipStream_t st, int64_t rows, int64_t N, int K, const AdmSet& t0, const AdmSet& t1, const AdmSet& t2, double* npart,
+                       double* nrm);
+int launch_admix_extrap(hipStream_t st, int64_t rows, int64_t N, int K, const AdmSet& t0, const AdmSet& t1, const AdmSet& t2,
+                        const uint8_t* mode, double alpha, const AdmSet& tx);
+
 }  // namespace gpca

@@ -552,4 +552,45 @@ constexpr double roh_call_bytes(int64_t N, int64_t rows, int64_t splits, int64_t
            4.0 * (double)roh_seg_capacity(records) + 8.0;
 }
 
+// ---- admixture proportions: one EM step and the fit around it (admix.hip, gpca_admix.cpp; include/gpca.h section a21) -----------------
+// A workgroup of kAdmThreads threads owns a chunk of kAdmChunk samples (a thread per sample) and a block of kAdmRowBlock kept rows, which
+// it walks in tiles of kAdmTile rows: a thread forms a and b of its sample on the tile's rows (the sums over rows stay in its registers)
+// and leaves them in LDS, where the same threads, now as kAdmTile rows x kAdmGroups groups of kAdmGroupSamples samples, form the sums over
+// the chunk's samples.  The plan is a function of (rows, N) alone: no CU count, no environment, no storage mode enters, so neither does
+// any enter the order of a sum.  The workgroups are numbered block-major on a one-dimensional grid.
+constexpr int kAdmMaxK = 16, kAdmThreads = 256, kAdmChunk = kAdmThreads, kAdmTile = 16, kAdmRowBlock = 4096;
+constexpr int kAdmGroups = kAdmThreads / kAdmTile, kAdmGroupSamples = kAdmChunk / kAdmGroups, kAdmPitch = kAdmChunk + 1;
+constexpr int kAdmSumThreads = 256, kAdmNormBlock = 4096;
+static_assert(kAdmRowBlock % kAdmTile == 0 && kAdmGroups * kAdmGroupSamples == kAdmChunk && kAdmNormBlock % kAdmSumThreads == 0, "whole tiles, whole groups");
+// the a and b tiles [2][kAdmTile][kAdmPitch] are reused for the groups' partial sums [kAdmMaxK][2][kAdmGroups][kAdmTile]
+static_assert(2 * kAdmTile * kAdmPitch >= kAdmMaxK * 2 * kAdmGroups * kAdmTile, "the partial sums fit in the a and b tiles");
+// the register width a kernel is compiled for: the columns K .. adm_kpad(K) - 1 are zeros, which add nothing to any sum
+constexpr int adm_kpad(int K) { return K <= 4 ? 4 : K <= 8 ? 8 : 16; }
+struct AdmPlan { int64_t chunks, blocks; };
+constexpr AdmPlan adm_plan(int64_t rows, int64_t N) {
+    return AdmPlan{((N > 0 ? N : 1) + kAdmChunk - 1) / kAdmChunk, ((rows > 0 ? rows : 1) + kAdmRowBlock - 1) / kAdmRowBlock};
+}
+constexpr int64_t adm_grid(const AdmPlan& p) { return p.chunks * p.blocks; }
+// the slabs: fpart [chunks][rows][2][K] = the chunk's sums of a q and b q; qpart [blocks][N][K] = the block's sum of a f + b (1 - f);
+// llpart [blocks][chunks] (f64) = the workgroup's log-likelihood terms
+constexpr int64_t adm_fpart_index(int64_t chunk, int64_t rows, int64_t row, int ab, int K, int k) { return ((chunk * rows + row) * 2 + ab) * K + k; }
+constexpr int64_t adm_qpart_index(int64_t block, int64_t N, int64_t n, int K, int k) { return (block * N + n) * K + k; }
+constexpr int64_t adm_llpart_index(int64_t block, int64_t chunks, int64_t chunk) { return block * chunks + chunk; }
+constexpr int64_t adm_fpart_capacity(const AdmPlan& p, int64_t rows, int K) { return p.chunks * rows * 2 * K; }
+constexpr int64_t adm_qpart_capacity(const AdmPlan& p, int64_t N, int K) { return p.blocks * N * K; }
+constexpr int64_t adm_llpart_capacity(const AdmPlan& p) { return p.blocks * p.chunks; }
+constexpr int64_t adm_q_capacity(int64_t N, int K) { return N * K; }
+constexpr int64_t adm_f_capacity(int64_t rows, int K) { return rows * K; }
+// the norms of a SQUAREM cycle: blocks of kAdmNormBlock elements of (Q, then F), two f64 per block
+constexpr int64_t adm_norm_blocks(int64_t N, int64_t rows, int K) { return (adm_q_capacity(N, K) + adm_f_capacity(rows, K) + kAdmNormBlock - 1) / kAdmNormBlock; }
+constexpr int64_t adm_npart_capacity(int64_t N, int64_t rows, int K) { return 2 * adm_norm_blocks(N, rows, K); }
+// The device bytes a call allocates (the GPCA_ERR_OOM sum, without the check's slack): `sets` parameter sets (Q, F) -- 2 for a step, 5
+// for a fit --, the mode bytes, the three slabs, the norms' partials (a fit), the sums (3 f64) and the invalid-genotype word
+constexpr double adm_call_bytes(int64_t N, int64_t rows, int K, int sets, bool fit) {
+    const AdmPlan p = adm_plan(rows, N);
+    return 4.0 * (double)sets * (double)(adm_q_capacity(N, K) + adm_f_capacity(rows, K)) + (double)N + 4.0 * (double)adm_fpart_capacity(p, rows, K) +
+           4.0 * (double)adm_qpart_capacity(p, N, K) + 8.0 * (double)adm_llpart_capacity(p) +
+           (fit ? 8.0 * (double)adm_npart_capacity(N, rows, K) : 0.0) + 24.0 + 8.0;
+}
+
 }  // namespace gpca

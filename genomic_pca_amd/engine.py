@@ -768,6 +768,65 @@ class GpcaEngine:
         self._chk(self._lib.gpca_sample_counts(self._h, r0, r1, _vp(qv), _vp(counts), _vp(qsum)))
         return {"counts": counts[:N], "qsum": None if qsum is None else qsum[:N]}
 
+    def _admix_shape(self, K) -> Tuple[int, int, int]:
+        return self.dims()[1], int(self._lib.gpca_num_pca_snps(self._h)), int(K)
+
+    @staticmethod
+    def _admix_mode(mode, N):
+        if mode is None:
+            return None
+        mv = np.ascontiguousarray(mode, np.uint8)
+        if mv.shape != (N,):
+            raise ValueError("mode must hold one byte per sample (0 = free, 1 = Q fixed, 2 = projected)")
+        return mv
+
+    def admix_init(self, K: int, seed: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+        """The starting point of the admixture fit (gpca_admix_init; gpca.h section a21): (Q float32 [N][K], F float32 [Kr][K]) over
+        the kept rows, a pure function of (seed, K, N, Kr, the kept rows' observed A1 frequencies)."""
+        N, Kr, K = self._admix_shape(K)
+        Q = np.zeros((max(N, 1), max(K, 1)), np.float32)
+        F = np.zeros((max(Kr, 1), max(K, 1)), np.float32)
+        self._chk(self._lib.gpca_admix_init(self._h, K, int(seed) & 0xffffffffffffffff, _vp(Q), _vp(F)))
+        return Q[:N], F[:Kr]
+
+    def admix_step(self, Q, F, mode=None) -> Tuple[np.ndarray, np.ndarray, float]:
+        """One EM step of the admixture model (gpca_admix_step; gpca.h section a21) from Q [N][K] and F [Kr][K] exactly as given:
+        (Q', F', loglik of (Q, F)).  mode: one byte per sample, 0 = Q free and the sample contributes to F, 1 = Q stays and the sample
+        contributes, 2 = Q free and the sample does not contribute."""
+        Qv, Fv = np.ascontiguousarray(Q, np.float32), np.ascontiguousarray(F, np.float32)
+        if Qv.ndim != 2 or Fv.ndim != 2 or Qv.shape[1] != Fv.shape[1]:
+            raise ValueError("Q must be [N][K] and F [Kr][K]")
+        N, Kr, K = self._admix_shape(Qv.shape[1])
+        if Kr > 0 and (Qv.shape != (N, K) or Fv.shape != (Kr, K)):       # (no kept row: the library says what is missing)
+            raise ValueError(f"Q must be [{N}][K] and F [{Kr}][K] (the samples and the kept rows of the handle)")
+        mv = self._admix_mode(mode, N)
+        Qn, Fn, ll = np.zeros_like(Qv), np.zeros_like(Fv), C.c_double()
+        self._chk(self._lib.gpca_admix_step(self._h, K, _vp(Qv), _vp(Fv), _vp(mv), _vp(Qn), _vp(Fn), C.byref(ll)))
+        return Qn, Fn, ll.value
+
+    def admix(self, K: int, seed: int = 0, max_iter: int = 2000, tol: float = 1e-7, accel: bool = True, mode=None, Q=None, F=None) -> dict:
+        """Admixture proportions (gpca_admix; gpca.h section a21): the ADMIXTURE model with K ancestries fitted by EM, with SQUAREM
+        acceleration unless accel is False, over the kept rows and all samples.  Starts from admix_init(K, seed), or from Q and F when
+        both are given.  Returns {"Q": float32 [N][K], "F": float32 [Kr][K], "loglik", "steps", "cycles", "converged", "fallbacks",
+        "trace": the cycle-start log-likelihoods (the first 2^20 at most)}.  max_iter counts EM steps; reaching it is not an error (converged is False)."""
+        if (Q is None) != (F is None):
+            raise ValueError("Q and F go together (both or neither)")
+        N, Kr, K = self._admix_shape(K)
+        if Q is None:
+            Qv, Fv = np.zeros((max(N, 1), max(K, 1)), np.float32), np.zeros((max(Kr, 1), max(K, 1)), np.float32)
+        else:
+            Qv, Fv = np.array(Q, np.float32, order="C"), np.array(F, np.float32, order="C")
+            if Kr > 0 and (Qv.shape != (N, K) or Fv.shape != (Kr, K)):
+                raise ValueError(f"Q must be [{N}][{K}] and F [{Kr}][{K}]")
+        mv = self._admix_mode(mode, N)
+        trace = np.zeros(min(max(int(max_iter), 1), 1 << 20), np.float64)           # (a cycle is at least one step; 2^20 cycles at most are kept)
+        par = _lib.gpca_admix_params(K, int(max_iter), int(seed) & 0xffffffffffffffff, float(tol), 1 if accel else 0, 0 if Q is None else 1)
+        info = _lib.gpca_admix_info()
+        info.trace, info.trace_cap = trace.ctypes.data, trace.size
+        self._chk(self._lib.gpca_admix(self._h, C.byref(par), _vp(mv), _vp(Qv), _vp(Fv), C.byref(info)))
+        return {"Q": Qv[:N], "F": Fv[:Kr], "loglik": info.loglik, "steps": int(info.steps), "cycles": int(info.cycles),
+                "converged": bool(info.converged), "fallbacks": int(info.fallbacks), "trace": trace[:min(int(info.cycles), trace.size)].copy()}
+
     @staticmethod
     def roh_threshold(x) -> Tuple[int, int]:
         """The window threshold as the ABI takes it: (num, den) = the exact fraction of x's decimal text (Fraction(str(x)): 0.05 is 1/20,

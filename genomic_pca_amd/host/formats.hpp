@@ -1403,6 +1403,64 @@ inline void write_hom(const std::string& prefix, const std::vector<std::string>&
         std::fprintf(o.f, "%s\t%s\t%lld\t%s\t%s\t%s\n", fids[i].c_str(), iids[i].c_str(), (long long)nseg[i], b[0], b[1], b[2]);
     }
 }
+// ---- admixture proportions (gpca_admix; gpca.h section a21): the host rules around the fit; twins of io.admix_order, io.admix_supervised
+// and io.write_admix
+// the column order: by descending column sum of Q [n][K] over the samples with mode != 1 (f64, sample order), ties to the lower index;
+// the identity with a mode-1 sample
+inline std::vector<int64_t> admix_order(const std::vector<float>& Q, size_t n, int K, const std::vector<uint8_t>& mode) {
+    std::vector<int64_t> order((size_t)K);
+    for (int k = 0; k < K; ++k) order[(size_t)k] = k;
+    for (size_t s = 0; s < n && s < mode.size(); ++s)
+        if (mode[s] == 1) return order;
+    std::vector<double> sums((size_t)K, 0.0);
+    for (size_t s = 0; s < n; ++s)
+        for (int k = 0; k < K; ++k) sums[(size_t)k] += (double)Q[s * (size_t)K + (size_t)k];
+    std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return sums[(size_t)a] > sums[(size_t)b]; });
+    return order;
+}
+// a labelled sample's row of Q [n][K] becomes the one-hot row of its group, clamped to >= 1e-5 and divided by its sum (f32, columns
+// ascending), and its mode 1; an unlabelled sample (label < 0) keeps its row and mode 0
+inline std::vector<uint8_t> admix_supervised(const std::vector<int32_t>& labels, int K, std::vector<float>& Q) {
+    std::vector<uint8_t> mode(labels.size(), 0);
+    for (size_t s = 0; s < labels.size(); ++s) {
+        if (labels[s] < 0) continue;
+        mode[s] = 1;
+        float* row = Q.data() + s * (size_t)K;
+        float sum = 0.0f;
+        for (int k = 0; k < K; ++k) { row[k] = k == labels[s] ? 1.0f : 1e-5f; sum = sum + row[k]; }
+        const float d = sum;
+        for (int k = 0; k < K; ++k) row[k] = row[k] / d;
+    }
+    return mode;
+}
+// P.K.Q and P.K.P: K `%.6f` per line, separated by spaces, columns in `order`; P.K.Q.id: `#FID IID`; P.K.P.id: one variant id per line;
+// P.K.admix.log: `#K SEED STEPS CYCLES CONVERGED LOGLIK`
+inline void write_admix(const std::string& prefix, int K, const std::vector<std::string>& fids, const std::vector<std::string>& iids,
+                        const std::vector<std::string>& variant_ids, const std::vector<float>& Q, const std::vector<float>& F,
+                        const std::vector<int64_t>& order, uint64_t seed, int64_t steps, int64_t cycles, bool converged, double loglik) {
+    if (fids.size() != iids.size() || Q.size() != iids.size() * (size_t)K || F.size() != variant_ids.size() * (size_t)K || order.size() != (size_t)K)
+        throw std::runtime_error("write_admix: Q must be [samples][K] and F [SNPs][K], with one FID per IID");
+    const std::string base = prefix + "." + std::to_string(K);
+    auto matrix = [&](const std::string& path, const std::vector<float>& m, size_t rows) {
+        OutFile o(path);
+        for (size_t i = 0; i < rows; ++i)
+            for (int k = 0; k < K; ++k) std::fprintf(o.f, k + 1 < K ? "%.6f " : "%.6f\n", (double)m[i * (size_t)K + (size_t)order[(size_t)k]]);
+    };
+    matrix(base + ".Q", Q, iids.size());
+    matrix(base + ".P", F, variant_ids.size());
+    {
+        OutFile o(base + ".Q.id");
+        std::fputs("#FID\tIID\n", o.f);
+        for (size_t i = 0; i < iids.size(); ++i) std::fprintf(o.f, "%s\t%s\n", fids[i].c_str(), iids[i].c_str());
+    }
+    {
+        OutFile o(base + ".P.id");
+        for (const std::string& v : variant_ids) std::fprintf(o.f, "%s\n", v.c_str());
+    }
+    OutFile o(base + ".admix.log");
+    std::fputs("#K\tSEED\tSTEPS\tCYCLES\tCONVERGED\tLOGLIK\n", o.f);
+    std::fprintf(o.f, "%d\t%llu\t%lld\t%lld\t%d\t%.4f\n", K, (unsigned long long)seed, (long long)steps, (long long)cycles, converged ? 1 : 0, loglik);
+}
 // the threshold of --gpca-homozyg-window-threshold as the exact fraction of its decimal text (digits, one optional point, no exponent),
 // reduced; false when the text is not such a number or the reduced denominator is above 2^20 (io / engine: Fraction(str(x)))
 inline bool roh_threshold(const std::string& text, int64_t& num, int64_t& den) {

@@ -89,6 +89,10 @@ struct Args {
     std::string hom_threshold = "0.05";
     int64_t hom_thr_num = 1, hom_thr_den = 20;     // the threshold's exact fraction, set in main
     double hom_kb = 1000.0, hom_density = 50.0, hom_gap = 1000.0;
+    bool admixture = false, admix_value_flag = false;   // --gpca-admixture K; one of its value flags was given
+    int64_t admix_k = 0, admix_seed = 0, admix_max_iter = 2000;
+    double admix_tol = 1e-7;
+    bool admix_no_accel = false, admix_supervised = false;
 };
 
 [[noreturn]] void usage_error(const std::string& msg) {
@@ -256,6 +260,16 @@ void print_help() {
         "      --gpca-homozyg-density <X>       kb per SNP a run holds at most [default: 50]\n"
         "      --gpca-homozyg-gap <X>           a gap of more than X kb between two SNPs ends a run [default: 1000]\n"
         "      --gpca-homozyg-het <N>           het calls a run holds at most [default: no limit]\n"
+        "      --gpca-admixture <K>             --eigensnp: admixture proportions of every sample in K ancestral populations (1 .. 16), the\n"
+        "                                       ADMIXTURE model fitted by accelerated EM over the SNPs the PCA is fitted on; samples outside\n"
+        "                                       the KING in-set or failing the sample QC get proportions without shaping the frequencies\n"
+        "                                       -> <out>.K.Q, .Q.id, .P, .P.id and .admix.log\n"
+        "      --gpca-admixture-seed <S>        the seed of the starting point [default: 0]\n"
+        "      --gpca-admixture-max-iter <N>    EM steps at most [default: 2000]\n"
+        "      --gpca-admixture-tol <X>         stop when a cycle gains less than X times the log-likelihood [default: 1e-7]\n"
+        "      --gpca-admixture-no-accel        plain EM steps, without the SQUAREM acceleration\n"
+        "      --gpca-admixture-supervised      the samples with a group in --gpca-within are references of known ancestry: K must be the\n"
+        "                                       number of groups, and column k of the result is group k\n"
         "      --gpca-assoc-pcs <P>             --gpca-assoc-pheno: the first P columns of the scores this run writes are covariates\n"
         "                                       (0 <= P <= --eigensnp-k-global) [default: every column]\n"
         "      --gpca-assoc-covar <FILE>        --gpca-assoc-pheno: further covariates, a table in the format of the phenotype file\n"
@@ -353,6 +367,12 @@ Args parse(int argc, char** argv) {
         else if (f == "--gpca-het") a.het = true;
         else if (f == "--gpca-mind") { a.mind = to_f64(f, val()); a.have_mind = true; }
         else if (f == "--gpca-het-sd") { a.het_sd = to_f64(f, val()); a.have_het_sd = true; }
+        else if (f == "--gpca-admixture") { a.admix_k = to_i64(f, val()); a.admixture = true; }
+        else if (f == "--gpca-admixture-seed") { a.admix_seed = to_i64(f, val()); a.admix_value_flag = true; }
+        else if (f == "--gpca-admixture-max-iter") { a.admix_max_iter = to_i64(f, val()); a.admix_value_flag = true; }
+        else if (f == "--gpca-admixture-tol") { a.admix_tol = to_f64(f, val()); a.admix_value_flag = true; }
+        else if (f == "--gpca-admixture-no-accel") { a.admix_no_accel = true; a.admix_value_flag = true; }
+        else if (f == "--gpca-admixture-supervised") { a.admix_supervised = true; a.admix_value_flag = true; }
         else if (f == "--gpca-homozyg") a.homozyg = true;
         else if (f == "--gpca-homozyg-window-snp") { a.hom_window_snp = to_i64(f, val()); a.homozyg = true; }
         else if (f == "--gpca-homozyg-window-het") { a.hom_window_het = to_i64(f, val()); a.homozyg = true; }
@@ -955,6 +975,47 @@ const char* const kHomozygNeedsResident =
 // kb on the command line -> bp: x 1000 rounded half up (cli.py: math.floor(x * 1000.0 + 0.5))
 inline int64_t kb_to_bp(double kb) { return (int64_t)std::floor(kb * 1000.0 + 0.5); }
 
+const char* const kAdmixNeedsResident =
+    "error: --gpca-admixture needs the genotype matrix resident on the device: the fit of a matrix walked out of core is not implemented\n";
+
+// --gpca-admixture K: the admixture fit (gpca_admix) over the rows the PCA was fitted on (the handle's keep mask as the PCA left it) and
+// every sample: mode 0 inside the in-set, mode 2 outside it, mode 1 for a sample with a group under --gpca-admixture-supervised; writes
+// P.K.Q, .Q.id, .P, .P.id and .admix.log with the columns in admix_order (cli.py:_admix).
+int run_admix(gpca::Engine& eng, const Args& a, const std::vector<std::string>& fids, const std::vector<std::string>& sample_ids,
+              const std::vector<std::string>& vids, const std::vector<uint8_t>& inset) {
+    const int K = (int)a.admix_k;
+    const size_t n = sample_ids.size();
+    std::vector<uint8_t> mode(n, 0);
+    if (!inset.empty()) for (size_t s = 0; s < n; ++s) mode[s] = inset[s] ? 0 : 2;
+    gpca_admix_params par{};
+    par.K = K; par.max_iter = (int32_t)a.admix_max_iter; par.seed = (uint64_t)a.admix_seed; par.tol = a.admix_tol; par.accel = a.admix_no_accel ? 0 : 1;
+    std::vector<float> Q, F;
+    gpca_admix_info info{};
+    try {
+        if (a.admix_supervised) {
+            const std::vector<int32_t> labels = gpca_host::align_within(a.within_table, fids, sample_ids);
+            eng.admix_init(K, par.seed, Q, F);
+            const std::vector<uint8_t> fixed = gpca_host::admix_supervised(labels, K, Q);
+            for (size_t s = 0; s < n; ++s) if (fixed[s]) mode[s] = 1;                     // a labelled sample is a reference wherever it stands
+            par.init = 1;
+        }
+        info = eng.admix(par, &mode, Q, F);
+    } catch (const gpca::Error& e) {
+        if (e.status() != GPCA_ERR_STATE) throw;
+        std::fputs(kAdmixNeedsResident, stderr);
+        return 1;
+    }
+    const std::vector<int64_t> order = gpca_host::admix_order(Q, n, K, mode);
+    gpca_host::ensure_parent(a.output_prefix);
+    gpca_host::write_admix(a.output_prefix, K, fids, sample_ids, vids, Q, F, order, par.seed, info.steps, info.cycles, info.converged != 0, info.loglik);
+    char buf[512];
+    std::snprintf(buf, sizeof buf, "admixture (K = %d) of %zu samples (%lld references, %lld projected) over %zu SNPs: %lld steps, %s, log-likelihood %.4f, written to %s.%d.Q",
+                  K, n, (long long)std::count(mode.begin(), mode.end(), (uint8_t)1), (long long)std::count(mode.begin(), mode.end(), (uint8_t)2), vids.size(),
+                  (long long)info.steps, info.converged ? "converged" : "not converged", info.loglik, a.output_prefix.c_str(), K);
+    logmsg(buf);
+    return 0;
+}
+
 // --gpca-homozyg: the runs of homozygosity (gpca_roh, in bands cut at chromosome starts) of every sample over every SNP that passes the
 // SNP QC, the length and density rule on the records (gpca_roh_select), P.hom and P.hom.indiv.  Sets the keep mask to the QC mask (mu,
 // sigma unchanged); the caller sets its own afterwards (cli.py:_homozyg).
@@ -1024,10 +1085,11 @@ int run_eigensnp_workflow(Args a) {
     const bool streamed = load_bed(eng, a, fs, use_kept ? &kept : nullptr);
     if (streamed && a.make_pcrelate) { std::fputs(kPcrelateNeedsResident, stderr); return 1; }
     if (streamed && !a.assoc_pheno.empty()) { std::fputs(kAssocNeedsResident, stderr); return 1; }
-    if (streamed && !a.within.empty()) { std::fputs(kStratNeedsResident, stderr); return 1; }
+    if (streamed && !a.within.empty() && (a.freq_strat || a.have_fst)) { std::fputs(kStratNeedsResident, stderr); return 1; }
     if (streamed && a.sample_qc_asked()) { std::fputs(kSampleQcNeedsResident, stderr); return 1; }
     if (streamed && a.homozyg) { std::fputs(kHomozygNeedsResident, stderr); return 1; }
     if (streamed && !a.ld_score.empty()) { std::fputs(kLdScoreNeedsResident, stderr); return 1; }
+    if (streamed && a.admixture) { std::fputs(kAdmixNeedsResident, stderr); return 1; }
     const gpca::SnpStats st = eng.snp_stats(gpca::QcConfig{a.min_call_rate, a.min_maf, a.max_hwe_p});
     std::vector<uint8_t> qc_pass;                                                                                       // empty: no sample filter
     if (a.sample_qc_asked() && !sample_ids.empty() && std::count(st.keep.begin(), st.keep.end(), (uint8_t)1) > 0) {
@@ -1235,6 +1297,12 @@ int run_eigensnp_workflow(Args a) {
         m.eigenvalues = out.final_principal_component_eigenvalues;
         gpca_host::write_model(a.output_prefix, m);
     }
+    if (a.admixture) {                                                                     // while the handle carries the PCA's keep mask
+        std::vector<std::string> fids = fs.family_ids;
+        if (use_kept) { fids.clear(); for (int64_t c : kept.cols) fids.push_back(fs.family_ids[(size_t)c]); }
+        const int rc = run_admix(eng, a, fids, sample_ids, vids, inset);
+        if (rc) return rc;
+    }
     if (a.make_pcrelate) {
         // the bands of the PC-Relate triangle into P.pcrelate.kin / P.pcrelate.inbreed: V = the first P columns of the scores written above,
         // the regression fitted on the KING in-set when there is one, else on everyone (cli.py:_pcrelate)
@@ -1266,7 +1334,7 @@ int run_eigensnp_workflow(Args a) {
                       rows.size(), (int)P, a.output_prefix.c_str());
         logmsg(buf);
     }
-    if (!a.within.empty()) {
+    if (!a.within.empty() && (a.freq_strat || a.have_fst)) {
         std::vector<std::string> fids = fs.family_ids;
         if (use_kept) { fids.clear(); for (int64_t c : kept.cols) fids.push_back(fs.family_ids[(size_t)c]); }
         const int rc = run_strat(eng, a, fs, fids, sample_ids, st);
@@ -1397,8 +1465,8 @@ int main(int argc, char** argv) {
         if (a.have_fst && a.fst != "hudson" && a.fst != "wc") { std::fprintf(stderr, "error: --gpca-fst must be hudson or wc\n"); return 2; }
         if (!a.within.empty()) {
             if (!a.eigensnp) { std::fprintf(stderr, "error: --gpca-within needs the --eigensnp workflow\n"); return 2; }
-            if (!a.freq_strat && !a.have_fst) { std::fprintf(stderr, "error: --gpca-within needs --gpca-freq-strat or --gpca-fst\n"); return 2; }
-            if (a.stream == "on") { std::fputs(kStratNeedsResident, stderr); return 2; }
+            if (!a.freq_strat && !a.have_fst && !a.admix_supervised) { std::fprintf(stderr, "error: --gpca-within needs --gpca-freq-strat or --gpca-fst\n"); return 2; }
+            if (a.stream == "on" && (a.freq_strat || a.have_fst)) { std::fputs(kStratNeedsResident, stderr); return 2; }
             try { a.within_table = gpca_host::read_within(a.within); }
             catch (const std::runtime_error& e) { std::fprintf(stderr, "error: --gpca-within: %s\n", e.what()); return 2; }
             const size_t ng = a.within_table.names.size();
@@ -1418,6 +1486,29 @@ int main(int argc, char** argv) {
                 return 2;
             }
             if (a.stream == "on") { std::fputs(kSampleQcNeedsResident, stderr); return 2; }
+        }
+        if (!a.admixture && a.admix_value_flag) {
+            std::fprintf(stderr, "error: --gpca-admixture-seed, -max-iter, -tol, -no-accel and --gpca-admixture-supervised need --gpca-admixture\n");
+            return 2;
+        }
+        if (a.admixture) {
+            if (!a.eigensnp) { std::fprintf(stderr, "error: --gpca-admixture needs the --eigensnp workflow\n"); return 2; }
+            if (!(a.admix_k >= 1 && a.admix_k <= GPCA_ADMIX_MAX_K)) { std::fprintf(stderr, "error: --gpca-admixture K must lie in [1, 16]\n"); return 2; }
+            if (a.admix_seed < 0) { std::fprintf(stderr, "error: --gpca-admixture-seed must lie in [0, 2^63)\n"); return 2; }
+            if (!(a.admix_max_iter >= 0 && a.admix_max_iter <= 2147483647LL)) { std::fprintf(stderr, "error: --gpca-admixture-max-iter must lie in [0, 2^31)\n"); return 2; }
+            if (!(a.admix_tol >= 0.0 && a.admix_tol < HUGE_VAL)) { std::fprintf(stderr, "error: --gpca-admixture-tol must be finite and at least 0\n"); return 2; }
+            if (a.admix_supervised) {
+                if (a.within.empty()) { std::fprintf(stderr, "error: --gpca-admixture-supervised needs --gpca-within\n"); return 2; }
+                if ((int64_t)a.within_table.names.size() != a.admix_k) {
+                    std::fprintf(stderr, "error: --gpca-admixture-supervised: K = %lld but --gpca-within names %zu groups\n", (long long)a.admix_k, a.within_table.names.size());
+                    return 2;
+                }
+            }
+            if (a.local_stage) {
+                std::fprintf(stderr, "error: --gpca-admixture cannot be combined with --gpca-eigensnp-local-stage (that stage owns the sample mask and the keep mask)\n");
+                return 2;
+            }
+            if (a.stream == "on") { std::fputs(kAdmixNeedsResident, stderr); return 2; }
         }
         if (a.homozyg) {
             if (!a.eigensnp) { std::fprintf(stderr, "error: --gpca-homozyg needs the --eigensnp workflow\n"); return 2; }

@@ -1419,3 +1419,77 @@ def write_hom(prefix: str, family_ids: Sequence[str], sample_ids: Sequence[str],
             f.write(f"{family_ids[i]}\t{sample_ids[i]}\t{int(nseg[i])}\t{_g6(kb)}\t{'NA' if nseg[i] == 0 else _g6(kb / float(int(nseg[i])))}\t"
                     f"{_g6(froh[i])}\n")
     return phom, pind
+
+
+# ---- admixture proportions (gpca_admix; gpca.h section a21): the host rules around the fit ------------------------------------------
+ADMIX_EPS = np.float32(1e-5)
+
+
+def admix_order(Q, mode=None) -> np.ndarray:
+    """The column order of an admixture result: the permutation (int64 [K]) by descending column sum of Q [N][K] over the samples with
+    mode != 1, sums in f64 in sample order, ties to the lower index.  With a mode-1 sample (a supervised fit, whose columns are the
+    groups) it is the identity."""
+    qv = np.asarray(Q, np.float64)
+    if qv.ndim != 2:
+        raise ValueError("admix_order: Q must be [samples][K]")
+    K = qv.shape[1]
+    mv = np.zeros(qv.shape[0], np.uint8) if mode is None else np.asarray(mode)
+    if mv.shape != (qv.shape[0],):
+        raise ValueError("admix_order: one mode byte per sample")
+    if (mv == 1).any():
+        return np.arange(K, dtype=np.int64)
+    sums = [0.0] * K
+    for n in range(qv.shape[0]):
+        for k in range(K):
+            sums[k] += float(qv[n, k])
+    return np.array(sorted(range(K), key=lambda k: (-sums[k], k)), np.int64)
+
+
+def admix_supervised(labels, K: int, Q=None) -> Tuple[np.ndarray, np.ndarray]:
+    """The start of a supervised fit from group labels [N] (0 .. K - 1; negative = no label): (Q float32 [N][K], mode uint8 [N]).  A
+    labelled sample's row is the one-hot row of its group, clamped to >= 1e-5 and divided by its sum (f32, columns ascending), and its
+    mode is 1; an unlabelled sample keeps its row of the given Q (1 / K without one) and mode 0."""
+    lv = np.asarray(labels, np.int64).reshape(-1)
+    K = int(K)
+    if K < 1 or (lv >= K).any():
+        raise ValueError("admix_supervised: a label must be below K")
+    out = np.full((lv.size, K), np.float32(1.0) / np.float32(K), np.float32) if Q is None else np.array(Q, np.float32, order="C")
+    if out.shape != (lv.size, K):
+        raise ValueError("admix_supervised: Q must be [samples][K]")
+    mode = (lv >= 0).astype(np.uint8)
+    for n in np.nonzero(lv >= 0)[0]:
+        row = np.full(K, ADMIX_EPS, np.float32)
+        row[lv[n]] = np.float32(1.0)
+        s = np.float32(0.0)
+        for k in range(K):
+            s = np.float32(s + row[k])
+        out[n] = row / s
+    return out, mode
+
+
+def write_admix(prefix: str, K: int, family_ids: Sequence[str], sample_ids: Sequence[str], variant_ids: Sequence[str], Q, F, info) -> Tuple[str, ...]:
+    """The files of an admixture fit, columns as given (the caller applies admix_order): P.<K>.Q, one line per sample of K `%.6f`
+    separated by spaces (ADMIXTURE's layout); P.<K>.Q.id, `#FID IID` and one tab-separated line per sample; P.<K>.P, one line per SNP
+    of K `%.6f` (the A1 frequency in each ancestry); P.<K>.P.id, one variant id per line; P.<K>.admix.log, `#K SEED STEPS CYCLES
+    CONVERGED LOGLIK` and one tab-separated line from info (seed, steps, cycles, converged, loglik; the log-likelihood as %.4f)."""
+    qv, fv = np.asarray(Q, np.float64), np.asarray(F, np.float64)
+    K = int(K)
+    if qv.shape != (len(sample_ids), K) or fv.shape != (len(variant_ids), K) or len(family_ids) != len(sample_ids):
+        raise ValueError("write_admix: Q must be [samples][K] and F [SNPs][K], with one FID per IID")
+    base = f"{prefix}.{K}"
+    paths = (base + ".Q", base + ".Q.id", base + ".P", base + ".P.id", base + ".admix.log")
+    for path, m in ((paths[0], qv), (paths[2], fv)):
+        with _open_out(path, False) as f:
+            for i in range(m.shape[0]):
+                f.write(" ".join("%.6f" % float(v) for v in m[i]) + "\n")
+    with _open_out(paths[1], False) as f:
+        f.write("#FID\tIID\n")
+        for a, b in zip(family_ids, sample_ids):
+            f.write(f"{a}\t{b}\n")
+    with _open_out(paths[3], False) as f:
+        for v in variant_ids:
+            f.write(f"{v}\n")
+    with _open_out(paths[4], False) as f:
+        f.write("#K\tSEED\tSTEPS\tCYCLES\tCONVERGED\tLOGLIK\n")
+        f.write(f"{K}\t{int(info['seed'])}\t{int(info['steps'])}\t{int(info['cycles'])}\t{1 if info['converged'] else 0}\t{'%.4f' % float(info['loglik'])}\n")
+    return paths

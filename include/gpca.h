@@ -844,6 +844,87 @@ GPCA_API int gpca_roh(gpca_handle* h, int64_t row0, int64_t row1, const uint8_t*
 GPCA_API int gpca_roh_select(const uint32_t* segs /* [n][5] */, int64_t n, const int64_t* pos /* [K] */, int64_t min_bp,
                              int64_t max_bp_per_snp, uint8_t* keep /* [n] */);
 
+/* ---- a21: admixture proportions (the ADMIXTURE model, fitted by EM with SQUAREM acceleration): how much of every sample comes from each
+ * of K ancestral populations, and the A1 frequency of every kept SNP in each of them.  The calls work on ALL kept rows of a resident
+ * handle under its current keep mask, in PCA-SNP order (Kr = gpca_num_pca_snps rows), and on all N samples; the sample mask is ignored
+ * and `mode` alone says what a sample does.  A call is 0, 1, 2 (copies of A1) or missing; a missing call contributes nothing anywhere.
+ *  Q [N][K] f32, rows on the simplex; F [Kr][K] f32, the A1 frequency of each ancestry; 1 <= K <= GPCA_ADMIX_MAX_K = 16;
+ *  eps = (float)1e-5, hi = (float)1 - eps (f32 subtraction).
+ *  mode [N] uint8 or NULL (all 0): 0 = Q free, the sample contributes to F; 1 = Q stays as given, the sample contributes to F (a
+ *     reference sample of known ancestry); 2 = Q free, the sample does not contribute to F (a projected sample: a relative, a QC failure).
+ *  One EM step (Q, F) -> (Q', F', loglik), every quantity a sum, product or quotient of non-negative f32 numbers:
+ *   p1 = sum_k q_jk f_ik and p0 = sum_k q_jk (1 - f_ik) (k ascending, fused multiply-adds; p0 is its own dot product, never 1 - p1);
+ *   a = g / p1 and b = (2 - g) / p0 for an observed call, both 0 for a missing one;
+ *   loglik = the sum over observed calls of g log p1 + (2 - g) log p0: log is the device library's f32 logf, the terms (with g = 0 and
+ *     2 - g = 0 terms left out) are added in f64, and all samples enter whatever their mode;
+ *   F side, over the samples with mode != 2: AQ_ik = sum_j a q_jk, BQ_ik = sum_j b q_jk; num = f_ik AQ_ik, den = num + (1 - f_ik) BQ_ik;
+ *     f'_ik = min(max(num / den, eps), hi); a row with den = 0 (no observed call among the contributors) keeps f;
+ *   Q side, over the kept rows: S_jk = sum_i (a f_ik, then b (1 - f_ik)); t_jk = q_jk S_jk; x_k = max(t_jk / sum_k t_jk, eps);
+ *     q'_jk = x_k / sum_k x_k; a sample with no observed call (sum_k t_jk = 0) or with mode 1 keeps its row.
+ *  Summation shape: no float atomics; the order of every sum is a function of (Kr, N, K) alone -- never of the CU count, the
+ *     environment, the storage mode or the handle's precision.  Samples are cut into chunks of 256, kept rows into blocks of 4 096
+ *     (plan_math.h, adm_plan).  A sum over samples (AQ, BQ) is formed inside a chunk as 16 groups of 16 consecutive samples, each group
+ *     ascending, the groups added ascending; the chunks' sums go to a slab and are added ascending.  A sum over rows (S) is formed
+ *     row by row ascending inside a block; the blocks' sums go to a slab and are added ascending.  loglik: per sample over the block's
+ *     rows ascending, then the chunk's 256 samples ascending, then the (block, chunk) partials p = block * chunks + chunk: stride-256
+ *     classes (p, p + 256, ...) ascending each, then the 256 class sums ascending.  So int8 and 2-bit residency, a GPCA_PREC_F32_MFMA
+ *     handle and any two calls with the same inputs give the same bits.
+ *  gpca_admix_init: a pure function of (seed, K, N, Kr, the kept rows' observed A1 frequencies).  u(stream, index, k) = ((w >> 9) + 0.5)
+ *     2^-23 with w = word k & 3 of philox4x32-10(counter = (index low word, index high word, k >> 2, stream), key = (seed low word, seed
+ *     high word)).  Q, stream 0x41444D51, index = the sample: x_k = 0.1f + 0.9f u (f32, product then sum), q_jk = x_k / sum_k x_k (k
+ *     ascending).  F, stream 0x41444D46, index = the kept row (0 .. Kr - 1): freq_i = (float)((n_het + 2 n_hom2) / (2 n_valid)) of the
+ *     row's counts as gpca_get_snp_qc_detail gives them (the division in f64; 0.5 where n_valid = 0), f_ik = min(max(freq_i (0.5f + u),
+ *     eps), hi) in f32.  The counts are those of the resident genotypes whenever the call is accepted: an upload drops the statistics,
+ *     and gpca_set_standardization on a handle without them runs the counting pass of gpca_snp_stats (no filter) first, so they count
+ *     every sample's calls whichever of the two prepared the handle.
+ *  gpca_admix_step: the step above on the caller's Q and F exactly as given (a Q row must be non-negative with a positive sum, an F
+ *     value in [0, 1]; every function here leaves F in [eps, hi] and Q positive, and a caller who passes zeros gets IEEE's infinities).
+ *     The building block of the fit, and its test hook.
+ *  gpca_admix: the fit.  params: K, seed, max_iter (counts steps), tol (relative), accel (0 or 1), init (0 = gpca_admix_init(seed); 1 =
+ *     the caller's Q and F, clamped: F to [eps, hi], and a row of Q with mode != 1 that holds a value below eps to max(q, eps) / their
+ *     sum).  While steps < max_iter, a cycle from theta0:
+ *      1. step theta0 -> theta1, l0; trace[cycle] = l0 (while it fits the capacity);
+ *      2. stop, converged, when a cycle before this one exists and l0 - l0_prev < tol |l0|: the result is theta1;
+ *      3. accel = 0, or max_iter reached: continue from theta1;
+ *      4. accel = 1 (SQUAREM S3): step theta1 -> theta2, l1; r = theta1 - theta0, v = theta2 - theta1 - r, per element in f64; the sums of
+ *         r^2 and of v^2 run over Q then F, in blocks of 4 096 elements (stride-256 classes ascending, the 256 class sums ascending), the
+ *         blocks' sums in the order of loglik's partials; ||v|| = 0 or max_iter reached: continue from theta2.  alpha = min(-||r|| / ||v||,
+ *         -1); theta_x = (theta0 - (2 alpha) r) + (alpha alpha) v in f64, rounded once to f32; F clamped to [eps, hi]; a Q row clamped to
+ *         >= eps and divided by its sum, a mode-1 row taken from theta0.  step theta_x -> theta3, lx; continue from theta3 if lx >= l1,
+ *         else (a fallback) from theta2.
+ *     Cycle-start logliks are therefore non-decreasing up to evaluation error.  Reaching max_iter is GPCA_OK with converged = 0.
+ *     info: steps, cycles, converged, fallbacks (the cycles continued from theta2 under accel = 1), loglik = the last cycle-start l0 (the
+ *     returned parameters are at least one EM step further on); trace [trace_cap] (the caller's buffer, may be NULL with trace_cap = 0)
+ *     receives the first min(trace_cap, cycles) cycle-start logliks.  Q, F and every intermediate stay on the device; per step only
+ *     loglik, per cycle also the two norms, come back.
+ *  Errors: GPCA_ERR_STATE (no genotypes, a streamed handle, a row-sharded handle, no standardisation, an empty keep mask),
+ *     GPCA_ERR_BAD_ARG (a NULL required pointer; K outside 1 .. 16; a mode byte above 2; tol < 0; max_iter < 0; accel or init not 0 or
+ *     1; trace NULL with trace_cap > 0; with gpca_admix_step or init = 1, a Q row that is not non-negative and finite with a positive sum
+ *     or an F value outside [0, 1]), GPCA_ERR_INVALID_GENOTYPE (a kept row holds a value outside {0, 1, 2, missing} on a sample below N;
+ *     the message names the row, as in a12), GPCA_ERR_OOM (checked before any allocation).
+ *  Not there: K > 16; cross-validation error and the choice of K; restarts from several seeds; projection onto a saved F; standard
+ *     errors or bootstrap; haploid and sex chromosomes; ADMIXTURE's own block-relaxation / quasi-Newton numbers; streamed and
+ *     row-sharded handles. */
+#define GPCA_ADMIX_MAX_K 16
+typedef struct gpca_admix_params {
+    int32_t K, max_iter;
+    uint64_t seed;
+    double tol;
+    int32_t accel, init;
+} gpca_admix_params;
+typedef struct gpca_admix_info {
+    int64_t steps, cycles;
+    int32_t converged, fallbacks;
+    double loglik;
+    double* trace;        /* in: the caller's buffer [trace_cap], or NULL */
+    int64_t trace_cap;    /* in */
+} gpca_admix_info;
+GPCA_API int gpca_admix_init(gpca_handle* h, int32_t K, uint64_t seed, float* Q /* [N][K] */, float* F /* [Kr][K] */);
+GPCA_API int gpca_admix_step(gpca_handle* h, int32_t K, const float* Q, const float* F, const uint8_t* mode /* [N] or NULL */, float* Qn,
+                             float* Fn, double* loglik);
+GPCA_API int gpca_admix(gpca_handle* h, const gpca_admix_params* params, const uint8_t* mode /* [N] or NULL */, float* Q, float* F,
+                        gpca_admix_info* info);
+
 /* ---- f3: the stages of EigenSNPCoreAlgorithm::compute_pca (main.rs:311-327, 359-366) ------------------------------------------
  * The algorithm lives in the un-vendored efficient_pca crate (Cargo.toml:30, branch "main", no pinned revision): what follows is
  * the stage structure of its published description -- per-LD-block local bases learnt on a sample subset, condensed features of

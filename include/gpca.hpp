@@ -437,6 +437,41 @@ public:
         segs.resize((size_t)found * 5);
         seg_count.resize(N);
     }
+    // admixture proportions (gpca.h section a21) over the kept rows and all samples: Q [N][K], F [Kr][K] (Kr = num_pca_snps()); mode [N]
+    // (0 = free, 1 = Q fixed, 2 = projected) or NULL.  admix_init: the starting point of a seed; admix_step: one EM step from Q and F as
+    // given, returns the log-likelihood of (Q, F); admix: the fit, from the seed's init (params.init = 0) or from Q and F (1); trace
+    // receives the cycle-start log-likelihoods (the first 2^20 at most).
+    void admix_init(int32_t K, uint64_t seed, std::vector<float>& Q, std::vector<float>& F) const {
+        const size_t N = (size_t)dims().second, Kr = (size_t)gpca_num_pca_snps(h_), k = (size_t)std::max<int32_t>(K, 1);
+        Q.assign(std::max<size_t>(N * k, 1), 0.0f); F.assign(std::max<size_t>(Kr * k, 1), 0.0f);
+        check(gpca_admix_init(h_, K, seed, Q.data(), F.data()));
+        Q.resize(N * k); F.resize(Kr * k);
+    }
+    double admix_step(int32_t K, const std::vector<float>& Q, const std::vector<float>& F, const std::vector<uint8_t>* mode, std::vector<float>& Qn,
+                      std::vector<float>& Fn) const {
+        const size_t N = (size_t)dims().second, Kr = (size_t)gpca_num_pca_snps(h_), k = (size_t)std::max<int32_t>(K, 1);
+        if (Q.size() != N * k || F.size() != Kr * k || (mode && mode->size() != N)) throw std::invalid_argument("admix_step: Q [N][K], F [Kr][K], mode [N]");
+        Qn.assign(std::max<size_t>(Q.size(), 1), 0.0f); Fn.assign(std::max<size_t>(F.size(), 1), 0.0f);
+        double ll = 0.0;
+        check(gpca_admix_step(h_, K, Q.data(), F.data(), mode ? mode->data() : nullptr, Qn.data(), Fn.data(), &ll));
+        Qn.resize(Q.size()); Fn.resize(F.size());
+        return ll;
+    }
+    gpca_admix_info admix(const gpca_admix_params& params, const std::vector<uint8_t>* mode, std::vector<float>& Q, std::vector<float>& F,
+                          std::vector<double>* trace = nullptr) const {
+        const size_t N = (size_t)dims().second, Kr = (size_t)gpca_num_pca_snps(h_), k = (size_t)std::max<int32_t>(params.K, 1);
+        if (mode && mode->size() != N) throw std::invalid_argument("admix: mode needs one byte per sample");
+        if (params.init == 1 && (Q.size() != N * k || F.size() != Kr * k)) throw std::invalid_argument("admix: init = 1 needs Q [N][K] and F [Kr][K]");
+        if (params.init != 1) { Q.assign(std::max<size_t>(N * k, 1), 0.0f); F.assign(std::max<size_t>(Kr * k, 1), 0.0f); }
+        std::vector<double> tr((size_t)std::min<int32_t>(std::max<int32_t>(params.max_iter, 1), 1 << 20), 0.0);   // (a cycle is at least one step)
+        gpca_admix_info info{};
+        info.trace = tr.data(); info.trace_cap = (int64_t)tr.size();
+        check(gpca_admix(h_, &params, mode ? mode->data() : nullptr, Q.data(), F.data(), &info));
+        Q.resize(N * k); F.resize(Kr * k);
+        if (trace) trace->assign(tr.begin(), tr.begin() + (size_t)std::min<int64_t>(info.cycles, info.trace_cap));
+        info.trace = nullptr; info.trace_cap = 0;
+        return info;
+    }
     // the host rule on the records (gpca_roh_select; host only): keep [n] by length in bp and bp per SNP; pos [K] = the kept rows' positions
     static std::vector<uint8_t> roh_select(const std::vector<uint32_t>& segs, const std::vector<int64_t>& pos, int64_t min_bp, int64_t max_bp_per_snp) {
         const size_t n = segs.size() / 5;
