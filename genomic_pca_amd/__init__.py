@@ -16,5 +16,6 @@ het_weights = GpcaEngine.het_weights
 sample_het = GpcaEngine.sample_het
 roh_select = GpcaEngine.roh_select
 roh_threshold = GpcaEngine.roh_threshold
+admix_cv_fold = GpcaEngine.admix_cv_fold
 
 __version__ = "0.2.2"

@@ -74,6 +74,11 @@ class gpca_admix_info(C.Structure):
                 ("trace", C.c_void_p), ("trace_cap", C.c_int64)]
 
 
+class gpca_admix_cv_fold_info(C.Structure):
+    _fields_ = [("steps", C.c_int64), ("cycles", C.c_int64), ("converged", C.c_int32), ("fallbacks", C.c_int32), ("loglik", C.c_double),
+                ("held_loglik", C.c_double), ("n_held", C.c_int64), ("n_het_held", C.c_int64), ("deviance", C.c_double)]
+
+
 class gpca_kernel_timing(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("launches", C.c_int64), ("total_ms", C.c_double), ("flops", C.c_double),
                 ("bytes", C.c_double)]
@@ -184,7 +189,12 @@ PROTOTYPES = {
     "gpca_admix_init": (C.c_int, [_H, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p]),
     "gpca_admix_step": (C.c_int, [_H, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     "gpca_admix": (C.c_int, [_H, C.POINTER(gpca_admix_params), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(gpca_admix_info)]),
-    "gpca_ldsc_fit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_int32, C.c_double, C.c_void_p]),
+    "gpca_admix_cv_fold": (C.c_int, [C.c_uint64, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p]),
+    "gpca_admix_step_holdout": (C.c_int, [_H, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p,
+                                          C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "gpca_admix_cv": (C.c_int, [_H, C.POINTER(gpca_admix_params), C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p,
+                                C.POINTER(gpca_admix_cv_fold_info), C.POINTER(C.c_double)]),
+    "gpca_ldsc_fit":(C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_int32, C.c_double, C.c_void_p]),
     "gpca_comm_get_unique_id": (C.c_int, [C.c_void_p]),
     "gpca_comm_init": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, C.c_int64]),
     "gpca_set_allreduce_hook": (C.c_int, [_H, ALLREDUCE_FN, C.c_void_p, C.c_int32, C.c_int32, C.c_int64]),

@@ -226,6 +226,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--gpca-admixture-supervised", action="store_true",
                    help="the samples with a group in --gpca-within are references of known ancestry: K must be the number of groups, and "
                         "column k of the result is group k")
+    p.add_argument("--gpca-admixture-cv", type=int, nargs="?", const=5, default=None, metavar="V",
+                   help="--gpca-admixture: the V-fold cross-validation error of the fit (2 .. 64): a random V-th of the observed calls is "
+                        "hidden from a refit and scored by its binomial deviance, once per fold -> <out>.admix.cv [default V: 5]")
+    p.add_argument("--gpca-admixture-cv-seed", type=int, default=None, metavar="S", help="the seed of the folds [default: 0]")
+    p.add_argument("--gpca-admixture-cv-k", default=None, metavar="A-B",
+                   help="--gpca-admixture-cv: also score every K of A .. B (1 <= A <= B <= 16) into <out>.admix.cv, to choose K")
     p.add_argument("--gpca-assoc-pcs", type=int, default=None, metavar="P",
                    help="--gpca-assoc-pheno: the first P columns of the scores this run writes are covariates (0 <= P <= "
                         "--eigensnp-k-global) [default: every column]")
@@ -491,6 +497,17 @@ def _admix(eng, a, fs, cols, sample_ids, rows, inset):
     _log(f"admixture (K = {K}) of {n} samples ({int((mode == 1).sum())} references, {int((mode == 2).sum())} projected) over {len(rows)} SNPs: "
          f"{r['steps']} steps, {'converged' if r['converged'] else 'not converged'}, log-likelihood {r['loglik']:.4f}, written to "
          f"{a.output_prefix}.{K}.Q")
+    if a.gpca_admixture_cv_ks is not None:
+        # --gpca-admixture-cv: the same mode bytes, seed, max-iter, tol and accel, and the supervised fit's start; every K of the range
+        folds, cv_seed = a.gpca_admixture_cv, 0 if a.gpca_admixture_cv_seed is None else a.gpca_admixture_cv_seed
+        table = []
+        for k in a.gpca_admixture_cv_ks:
+            cv = eng.admix_cv(k, folds=folds, cv_seed=cv_seed, mode=mode, **(dict(Q=Q0, F=F0) if a.gpca_admixture_supervised else {}), **kw)
+            table += [dict(K=k, folds=folds, cv_seed=cv_seed, fold=c, **f) for c, f in enumerate(cv["folds"])]
+            _log(f"CV error (K={k}): {'NA' if cv['cv_error'] != cv['cv_error'] else '%.6f' % cv['cv_error']}")
+        gio.write_admix_cv(a.output_prefix, table)
+        _log(f"admixture cross-validation ({folds} folds, seed {cv_seed}) of K = {', '.join(str(k) for k in a.gpca_admixture_cv_ks)} written "
+             f"to {a.output_prefix}.admix.cv")
 
 
 LD_SCORE_NEEDS_RESIDENT = ("error: --gpca-ld-score needs the genotype matrix resident on the device: with the matrix walked out of core a "
@@ -1145,6 +1162,25 @@ def main(argv=None) -> int:
                              "mask and the keep mask)")
         if a.gpca_stream == "on":
             raise SystemExit(ADMIX_NEEDS_RESIDENT)
+    a.gpca_admixture_cv_ks = None
+    if a.gpca_admixture_cv is not None or a.gpca_admixture_cv_seed is not None or a.gpca_admixture_cv_k is not None:
+        if a.gpca_admixture is None:
+            raise SystemExit("error: --gpca-admixture-cv, --gpca-admixture-cv-seed and --gpca-admixture-cv-k need --gpca-admixture")
+        if a.gpca_admixture_cv is None:
+            raise SystemExit("error: --gpca-admixture-cv-seed and --gpca-admixture-cv-k need --gpca-admixture-cv")
+        if not 2 <= a.gpca_admixture_cv <= 64:
+            raise SystemExit("error: --gpca-admixture-cv V must lie in [2, 64]")
+        if a.gpca_admixture_cv_seed is not None and not 0 <= a.gpca_admixture_cv_seed < 1 << 63:
+            raise SystemExit("error: --gpca-admixture-cv-seed must lie in [0, 2^63)")
+        a.gpca_admixture_cv_ks = [a.gpca_admixture]
+        if a.gpca_admixture_cv_k is not None:
+            if a.gpca_admixture_supervised:
+                raise SystemExit("error: --gpca-admixture-cv-k cannot be combined with --gpca-admixture-supervised (the groups fix K)")
+            lo, sep, hi = a.gpca_admixture_cv_k.partition("-")
+            ok = sep == "-" and lo.isascii() and hi.isascii() and lo.isdigit() and hi.isdigit() and len(lo) <= 2 and len(hi) <= 2
+            if not ok or not 1 <= int(lo) <= int(hi) <= 16:
+                raise SystemExit("error: --gpca-admixture-cv-k must be A-B with 1 <= A <= B <= 16")
+            a.gpca_admixture_cv_ks = sorted(set(range(int(lo), int(hi) + 1)) | {a.gpca_admixture})
     if _homozyg_asked(a):
         if not a.eigensnp:
             raise SystemExit("error: --gpca-homozyg needs the --eigensnp workflow")

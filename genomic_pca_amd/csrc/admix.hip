@@ -12,7 +12,8 @@
 //   3. the groups' sums go to LDS over the a and b tiles, are added groups ascending, and the chunk's sums are written to the slab fpart.
 // At the end a thread writes S_k to the slab qpart, and thread 0 adds the 256 f64 sums, ascending, into llpart.
 // k_admix_f_update and k_admix_q_update add the slabs, chunks (blocks) ascending, and apply a21's updates; k_admix_sum64 adds f64 partials
-// in a fixed strided order.  No atomic touches a sum, and no order depends on anything but (rows, N, K): int8 and 2-bit rows run the same
+// in a fixed strided order.  No atomic touches a floating-point sum (the two integer counts of a22's hold-out step alone go through integer
+// atomics), and no order depends on anything but (rows, N, K): int8 and 2-bit rows run the same
 // arithmetic on the same decoded calls.  Every product that enters a sum is an explicit fmaf; everything else is compiled without
 // contraction.  Registers and LDS: the figures hipcc reports are in DESIGN section 7.
 #include "syrk_tile.h"
@@ -25,12 +26,16 @@ namespace gpca {
 constexpr float kAdmEps = 1e-5f;
 constexpr float kAdmHi = 1.0f - 1e-5f;
 
-template <bool PACKED, int KP>
+// HOLD (a22's hold-out step): an observed call whose fold is `fold` counts nothing in any of the sums above; its log terms at the same
+// p1 and p0 go to a second f64 register (same order), and two integer counters take the held calls and the heterozygous ones among them.
+// llpart is then [partial][2], and the workgroup's counts are added to cvcnt [2] with one integer atomicAdd each.
+template <bool PACKED, int KP, bool HOLD>
 __global__ __launch_bounds__(kAdmThreads) void k_admix_step(const void* __restrict__ Gv, int64_t ldr, const int64_t* __restrict__ krows,
                                                             int64_t rows, int64_t N, int K, int64_t chunks, const float* __restrict__ Q,
                                                             const float* __restrict__ F, const uint8_t* __restrict__ mode,
                                                             float* __restrict__ fpart, float* __restrict__ qpart, double* __restrict__ llpart,
-                                                            unsigned long long* __restrict__ bad) {
+                                                            unsigned long long* __restrict__ bad, uint32_t folds, uint32_t fold,
+                                                            uint64_t cv_seed, unsigned long long* __restrict__ cvcnt) {
     __shared__ float s_ab[2 * kAdmTile * kAdmPitch];
     __shared__ float s_q[kAdmChunk * KP];
     __shared__ float s_f[2][kAdmTile * KP];
@@ -48,6 +53,8 @@ __global__ __launch_bounds__(kAdmThreads) void k_admix_step(const void* __restri
 #pragma unroll
     for (int k = 0; k < KP; ++k) s_q[t * KP + k] = contrib ? q[k] : 0.0f;
     double ll = 0.0;
+    [[maybe_unused]] double hl = 0.0;
+    [[maybe_unused]] unsigned n_held = 0u, n_het = 0u;
 
     const int64_t ka = block * kAdmRowBlock, kb = ka + kAdmRowBlock < rows ? ka + kAdmRowBlock : rows;
     for (int64_t i0 = ka; i0 < kb; i0 += kAdmTile) {
@@ -69,6 +76,17 @@ __global__ __launch_bounds__(kAdmThreads) void k_admix_step(const void* __restri
                 if (!PACKED && c[r] > 2u && c[r] != kMissingByte) atomicMin(bad, (unsigned long long)orow);
             }
         }
+        [[maybe_unused]] unsigned held = 0u;                                         // bit r: the call of row i0 + r is observed and held out
+        if constexpr (HOLD) {
+            if (live)
+#pragma unroll
+                for (int qd = 0; qd < kAdmTile / kAdmCvQuad; ++qd) {
+                    const philox_out o = philox4x32_10((uint32_t)n, (uint32_t)((i0 >> 2) + qd), 0u, GPCA_STREAM_ADMIX_CV, (uint32_t)cv_seed, (uint32_t)(cv_seed >> 32));
+#pragma unroll
+                    for (int x = 0; x < kAdmCvQuad; ++x)
+                        if (c[qd * kAdmCvQuad + x] <= 2u && adm_cv_fold_of(o.v[x], folds) == fold) held |= 1u << (qd * kAdmCvQuad + x);
+                }
+        }
         __syncthreads();                                                             // (and the sums of the tile before have left s_ab)
 #pragma unroll 2
         for (int r = 0; r < kAdmTile; ++r) {
@@ -77,7 +95,17 @@ __global__ __launch_bounds__(kAdmThreads) void k_admix_step(const void* __restri
             float p1 = 0.0f, p0 = 0.0f;
 #pragma unroll
             for (int k = 0; k < KP; ++k) { p1 = fmaf(q[k], f[k], p1); p0 = fmaf(q[k], omf[k], p0); }
-            const bool obs = c[r] <= 2u;
+            bool obs = c[r] <= 2u;
+            if constexpr (HOLD) {
+                if ((held >> r) & 1u) {
+                    const float h1 = (float)c[r], h0 = 2.0f - (float)c[r];
+                    if (h1 > 0.0f) hl += (double)h1 * (double)logf(p1);
+                    if (h0 > 0.0f) hl += (double)h0 * (double)logf(p0);
+                    ++n_held;
+                    n_het += c[r] == 1u ? 1u : 0u;
+                    obs = false;
+                }
+            }
             const float w1 = obs ? (float)c[r] : 0.0f, w0 = obs ? 2.0f - (float)c[r] : 0.0f;
             const float a = w1 > 0.0f ? w1 / p1 : 0.0f, b = w0 > 0.0f ? w0 / p0 : 0.0f;
             if (w1 > 0.0f) ll += (double)w1 * (double)logf(p1);
@@ -120,10 +148,32 @@ __global__ __launch_bounds__(kAdmThreads) void k_admix_step(const void* __restri
             if (k < K) qpart[adm_qpart_index(block, N, n, K, k)] = S[k];
     s_ll[t] = ll;
     __syncthreads();
-    if (t == 0) {
-        double s = 0.0;
-        for (int i = 0; i < kAdmThreads; ++i) s += s_ll[i];
-        llpart[adm_llpart_index(block, chunks, chunk)] = s;
+    if constexpr (!HOLD) {
+        if (t == 0) {
+            double s = 0.0;
+            for (int i = 0; i < kAdmThreads; ++i) s += s_ll[i];
+            llpart[adm_llpart_index(block, chunks, chunk)] = s;
+        }
+    } else {
+        __shared__ unsigned s_cnt[2];
+        if (t == 0) {
+            double s = 0.0;
+            for (int i = 0; i < kAdmThreads; ++i) s += s_ll[i];
+            llpart[adm_cv_llpart_index(block, chunks, chunk, 0)] = s;
+            s_cnt[0] = 0u; s_cnt[1] = 0u;
+        }
+        __syncthreads();
+        s_ll[t] = hl;
+        if (n_held) atomicAdd(&s_cnt[0], n_held);                                    // at most kAdmRowBlock per thread: the sums fit 32 bits
+        if (n_het) atomicAdd(&s_cnt[1], n_het);
+        __syncthreads();
+        if (t == 0) {
+            double s = 0.0;
+            for (int i = 0; i < kAdmThreads; ++i) s += s_ll[i];
+            llpart[adm_cv_llpart_index(block, chunks, chunk, 1)] = s;
+            if (s_cnt[0]) atomicAdd(&cvcnt[0], (unsigned long long)s_cnt[0]);
+            if (s_cnt[1]) atomicAdd(&cvcnt[1], (unsigned long long)s_cnt[1]);
+        }
     }
 }
 
@@ -284,18 +334,26 @@ static inline bool adm_shape_ok(int64_t rows, int64_t N, int K) {
 
 int launch_admix_step(hipStream_t st, const void* G, int packed, int64_t ldr, const int64_t* krows, int64_t rows, int64_t N, int K,
                       const float* Q, const float* F, const uint8_t* mode, float* fpart, float* qpart, double* llpart, float* Qn, float* Fn,
-                      double* ll, unsigned long long* bad) {
+                      double* ll, unsigned long long* bad, const AdmHold& hold) {
     if (!adm_shape_ok(rows, N, K)) return (int)hipErrorInvalidValue;
+    if (hold.folds != 0 && (hold.folds < kAdmCvMinFolds || hold.folds > kAdmCvMaxFolds || hold.fold < 0 || hold.fold >= hold.folds || !hold.counts))
+        return (int)hipErrorInvalidValue;
     const AdmPlan p = adm_plan(rows, N);
     const dim3 grid((unsigned)adm_grid(p)), blk(kAdmThreads);
-#define GPCA_ADM(PK, KP) hipLaunchKernelGGL((k_admix_step<PK, KP>), grid, blk, 0, st, G, ldr, krows, rows, N, K, p.chunks, Q, F, mode, fpart, qpart, llpart, bad)
+    const uint32_t folds = (uint32_t)hold.folds, fold = (uint32_t)hold.fold;
+#define GPCA_ADM(PK, KP, HD) hipLaunchKernelGGL((k_admix_step<PK, KP, HD>), grid, blk, 0, st, G, ldr, krows, rows, N, K, p.chunks, Q, F, mode, fpart, qpart, llpart, bad, folds, fold, hold.seed, hold.counts)
     const int kp = adm_kpad(K);
-    if (packed) { if (kp == 4) GPCA_ADM(true, 4); else if (kp == 8) GPCA_ADM(true, 8); else GPCA_ADM(true, 16); }
-    else { if (kp == 4) GPCA_ADM(false, 4); else if (kp == 8) GPCA_ADM(false, 8); else GPCA_ADM(false, 16); }
+    if (hold.folds == 0) {
+        if (packed) { if (kp == 4) GPCA_ADM(true, 4, false); else if (kp == 8) GPCA_ADM(true, 8, false); else GPCA_ADM(true, 16, false); }
+        else { if (kp == 4) GPCA_ADM(false, 4, false); else if (kp == 8) GPCA_ADM(false, 8, false); else GPCA_ADM(false, 16, false); }
+    } else {
+        if (packed) { if (kp == 4) GPCA_ADM(true, 4, true); else if (kp == 8) GPCA_ADM(true, 8, true); else GPCA_ADM(true, 16, true); }
+        else { if (kp == 4) GPCA_ADM(false, 4, true); else if (kp == 8) GPCA_ADM(false, 8, true); else GPCA_ADM(false, 16, true); }
+    }
 #undef GPCA_ADM
     hipLaunchKernelGGL(k_admix_f_update, dim3(adm_blocks(rows * K)), dim3(kAdmSumThreads), 0, st, fpart, F, rows, K, p.chunks, Fn);
     hipLaunchKernelGGL(k_admix_q_update, dim3(adm_blocks(N)), dim3(kAdmSumThreads), 0, st, qpart, Q, mode, N, K, p.blocks, Qn);
-    hipLaunchKernelGGL(k_admix_sum64, dim3(1), dim3(kAdmSumThreads), 0, st, llpart, adm_llpart_capacity(p), 1, ll);
+    hipLaunchKernelGGL(k_admix_sum64, dim3(1), dim3(kAdmSumThreads), 0, st, llpart, adm_llpart_capacity(p), hold.folds == 0 ? 1 : 2, ll);
     return 0;
 }
 

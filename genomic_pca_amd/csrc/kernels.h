@@ -445,9 +445,12 @@ int launch_roh_runs(hipStream_t st, const void* G, int packed, int64_t ldr, cons
 // F of three parameter sets.  launch_admix_extrap: (Qx, Fx) = the SQUAREM point of step length alpha, clamped.  The launches return
 // nonzero when an argument is outside the kernels' limits.
 struct AdmSet { float* Q; float* F; };
+// a22's hold-out: folds = 0 is the plain step (llpart [partial], ll [1]); folds 2 .. 64 masks the observed calls of fold `fold` under `seed`
+// (llpart [partial][2], ll [2] = loglik, held_loglik; counts [2] (device u64) += n_held, n_het_held: the caller zeroes them)
+struct AdmHold { int folds = 0, fold = 0; uint64_t seed = 0; unsigned long long* counts = nullptr; };
 int launch_admix_step(hipStream_t st, const void* G, int packed, int64_t ldr, const int64_t* krows, int64_t rows, int64_t N, int K,
                       const float* Q, const float* F, const uint8_t* mode, float* fpart, float* qpart, double* llpart, float* Qn, float* Fn,
-                      double* ll, unsigned long long* bad);
+                      double* ll, unsigned long long* bad, const AdmHold& hold = AdmHold{});
 int launch_admix_init(hipStream_t st, const int64_t* krows, const unsigned* counts, int64_t rows, int64_t N, int K, uint64_t seed, float* Q,
                       float* F);
 int launch_admix_norms(hipStream_t st, int64_t rows, int64_t N, int K, const AdmSet& t0, const AdmSet& t1, const AdmSet& t2, double* npart,

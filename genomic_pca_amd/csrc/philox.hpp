@@ -4,6 +4,7 @@
 //   0x4F4D4547  sketch matrix Omega  counter = (snp_lo, snp_hi, column/4)
 //   0x41444D51  admixture init of Q  counter = (sample_lo, sample_hi, column/4)
 //   0x41444D46  admixture init of F  counter = (kept_row_lo, kept_row_hi, column/4)
+//   0x41444D43  admixture CV folds   counter = (sample, kept_row/4, 0)
 // The fast panel generator (GPCA_PANEL_SYNTH16) uses SplitMix64 in counter mode instead (below): output (snp << 26) + sample / 4
 // of the stream seeded with `seed` = four 16-bit uniforms.
 #pragma once
@@ -38,6 +39,8 @@ GPCA_HD philox_out philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t
 // the admixture init (gpca.h section a21): counter = (sample or kept row, low and high word; column / 4)
 #define GPCA_STREAM_ADMIX_Q 0x41444D51u
 #define GPCA_STREAM_ADMIX_F 0x41444D46u
+// the fold of a call in the admixture cross-validation (gpca.h section a22): counter = (sample, kept row / 4, 0), word = kept row & 3
+#define GPCA_STREAM_ADMIX_CV 0x41444D43u
 // SplitMix64 (Steele, Lea, Flood 2014; the generator that seeds xoshiro) in counter mode: output number i (0-based) of the stream
 // seeded with `seed` is mix(seed + (i + 1) * gamma) -- any i can be computed directly, consecutive i cost one 64-bit add.
 // Known answers (seed 1234567): 6457827717110365317, 3203168211198807973, 9817491932198370423, ...

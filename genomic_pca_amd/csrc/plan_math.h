@@ -592,5 +592,22 @@ constexpr double adm_call_bytes(int64_t N, int64_t rows, int K, int sets, bool f
            4.0 * (double)adm_qpart_capacity(p, N, K) + 8.0 * (double)adm_llpart_capacity(p) +
            (fit ? 8.0 * (double)adm_npart_capacity(N, rows, K) : 0.0) + 24.0 + 8.0;
 }
+// The hold-out step (gpca.h section a22): the fold of the call (kept row i, sample j) is word i & 3 of the philox call of the quad i >> 2,
+// so a tile of kAdmTile rows takes kAdmTile / 4 calls; tiles start at multiples of kAdmTile, so a quad never straddles two tiles.
+constexpr int kAdmCvMinFolds = 2, kAdmCvMaxFolds = 64, kAdmCvQuad = 4;
+static_assert(kAdmTile % kAdmCvQuad == 0 && kAdmRowBlock % kAdmCvQuad == 0, "whole quads in a tile");
+constexpr uint32_t adm_cv_fold_of(uint32_t word, uint32_t folds) { return (uint32_t)(((uint64_t)word * folds) >> 32); }
+// llpart of a hold-out step is [partial][2]: the training and the held-out log-likelihood terms of the (block, chunk)
+constexpr int64_t adm_cv_llpart_index(int64_t block, int64_t chunks, int64_t chunk, int comp) { return adm_llpart_index(block, chunks, chunk) * 2 + comp; }
+constexpr int64_t adm_cv_llpart_capacity(const AdmPlan& p) { return 2 * adm_llpart_capacity(p); }
+// the sums of a hold-out step (2 f64: loglik, held_loglik) and its counts (2 u64: n_held, n_het_held; integer atomicAdd, one per workgroup)
+constexpr int64_t adm_cv_sums_capacity() { return 2; }
+constexpr int64_t adm_cv_count_capacity() { return 2; }
+// The device bytes of a call that takes hold-out steps: adm_call_bytes with llpart at its [partial][2] size, the two sums and the counts
+constexpr double adm_cv_call_bytes(int64_t N, int64_t rows, int K, int sets, bool fit) {
+    const AdmPlan p = adm_plan(rows, N);
+    return adm_call_bytes(N, rows, K, sets, fit) - 8.0 * (double)adm_llpart_capacity(p) + 8.0 * (double)adm_cv_llpart_capacity(p) +
+           8.0 * (double)adm_cv_sums_capacity() + 8.0 * (double)adm_cv_count_capacity();
+}
 
 }  // namespace gpca

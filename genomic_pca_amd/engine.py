@@ -828,6 +828,60 @@ class GpcaEngine:
                 "converged": bool(info.converged), "fallbacks": int(info.fallbacks), "trace": trace[:min(int(info.cycles), trace.size)].copy()}
 
     @staticmethod
+    def admix_cv_fold(seed: int, folds: int, rows: int, N: int, row0: int = 0) -> np.ndarray:
+        """The fold of every call of the admixture cross-validation (gpca_admix_cv_fold; host only; gpca.h section a22): uint8
+        [rows][N] for the kept rows row0 .. row0 + rows - 1 (positions among the kept rows, PCA-SNP order) and the samples 0 .. N - 1."""
+        out = np.zeros((max(int(rows), 1), max(int(N), 1)), np.uint8)
+        lib = _lib.load()
+        rc = lib.gpca_admix_cv_fold(int(seed) & 0xffffffffffffffff, int(folds), int(row0), int(rows), int(N), _vp(out))
+        if rc != 0:
+            raise GpcaError(rc, "gpca_admix_cv_fold: folds must be 2 .. 64 and the extents non-negative: " + lib.gpca_status_string(rc).decode())
+        return out[:max(int(rows), 0), :max(int(N), 0)]
+
+    def admix_step_holdout(self, Q, F, folds: int, fold: int, cv_seed: int = 0, mode=None) -> dict:
+        """One hold-out step of the admixture model (gpca_admix_step_holdout; gpca.h section a22): admix_step with the observed calls of
+        fold `fold` (of `folds`, under cv_seed) counted as missing.  Returns {"Q", "F", "loglik"} of that step and, evaluated at the
+        input Q and F over the held-out calls, {"held_loglik", "n_held", "n_het_held"}."""
+        Qv, Fv = np.ascontiguousarray(Q, np.float32), np.ascontiguousarray(F, np.float32)
+        if Qv.ndim != 2 or Fv.ndim != 2 or Qv.shape[1] != Fv.shape[1]:
+            raise ValueError("Q must be [N][K] and F [Kr][K]")
+        N, Kr, K = self._admix_shape(Qv.shape[1])
+        if Kr > 0 and (Qv.shape != (N, K) or Fv.shape != (Kr, K)):
+            raise ValueError(f"Q must be [{N}][K] and F [{Kr}][K] (the samples and the kept rows of the handle)")
+        mv = self._admix_mode(mode, N)
+        Qn, Fn = np.zeros_like(Qv), np.zeros_like(Fv)
+        ll, hl, nh, nhet = C.c_double(), C.c_double(), C.c_int64(), C.c_int64()
+        self._chk(self._lib.gpca_admix_step_holdout(self._h, K, _vp(Qv), _vp(Fv), _vp(mv), int(folds), int(fold), int(cv_seed) & 0xffffffffffffffff,
+                                                    _vp(Qn), _vp(Fn), C.byref(ll), C.byref(hl), C.byref(nh), C.byref(nhet)))
+        return {"Q": Qn, "F": Fn, "loglik": ll.value, "held_loglik": hl.value, "n_held": int(nh.value), "n_het_held": int(nhet.value)}
+
+    def admix_cv(self, K: int, folds: int = 5, cv_seed: int = 0, seed: int = 0, max_iter: int = 2000, tol: float = 1e-7, accel: bool = True,
+                 mode=None, Q=None, F=None) -> dict:
+        """The cross-validation error of the admixture fit with K ancestries (gpca_admix_cv; gpca.h section a22): per fold the fit of
+        admix() with the fold's observed calls hidden in the step, then the hidden calls' binomial deviance at the fitted parameters.
+        Starts every fold from admix_init(K, seed), or from Q and F when both are given.  Returns {"cv_error": the summed deviance over
+        the summed n_held (NaN when nothing is held), "folds": one dict per fold of steps, cycles, converged, fallbacks, loglik (training),
+        held_loglik, n_held, n_het_held, deviance}."""
+        if (Q is None) != (F is None):
+            raise ValueError("Q and F go together (both or neither)")
+        N, Kr, K = self._admix_shape(K)
+        Qv = Fv = None
+        if Q is not None:
+            Qv, Fv = np.ascontiguousarray(Q, np.float32), np.ascontiguousarray(F, np.float32)
+            if Kr > 0 and (Qv.shape != (N, K) or Fv.shape != (Kr, K)):
+                raise ValueError(f"Q must be [{N}][{K}] and F [{Kr}][{K}]")
+        mv = self._admix_mode(mode, N)
+        par = _lib.gpca_admix_params(K, int(max_iter), int(seed) & 0xffffffffffffffff, float(tol), 1 if accel else 0, 0 if Q is None else 1)
+        out = (_lib.gpca_admix_cv_fold_info * max(min(int(folds), 64), 1))()
+        cv = C.c_double()
+        self._chk(self._lib.gpca_admix_cv(self._h, C.byref(par), _vp(mv), int(folds), int(cv_seed) & 0xffffffffffffffff, _vp(Qv), _vp(Fv), out,
+                                          C.byref(cv)))
+        rows = [{"steps": int(o.steps), "cycles": int(o.cycles), "converged": bool(o.converged), "fallbacks": int(o.fallbacks),
+                 "loglik": o.loglik, "held_loglik": o.held_loglik, "n_held": int(o.n_held), "n_het_held": int(o.n_het_held),
+                 "deviance": o.deviance} for o in out[:int(folds)]]
+        return {"cv_error": cv.value, "folds": rows}
+
+    @staticmethod
     def roh_threshold(x) -> Tuple[int, int]:
         """The window threshold as the ABI takes it: (num, den) = the exact fraction of x's decimal text (Fraction(str(x)): 0.05 is 1/20,
         not the binary double next to it).  x: a float, an int, a decimal or 'a/b' string, a Fraction, or a (num, den) pair, which is

@@ -1461,6 +1461,33 @@ inline void write_admix(const std::string& prefix, int K, const std::vector<std:
     std::fputs("#K\tSEED\tSTEPS\tCYCLES\tCONVERGED\tLOGLIK\n", o.f);
     std::fprintf(o.f, "%d\t%llu\t%lld\t%lld\t%d\t%.4f\n", K, (unsigned long long)seed, (long long)steps, (long long)cycles, converged ? 1 : 0, loglik);
 }
+// P.admix.cv (io.write_admix_cv; gpca.h section a22): `#K FOLDS CV_SEED FOLD STEPS CONVERGED N_HELD DEVIANCE CV_ERROR`; one line per fold
+// (the folds of one K together, ascending; CV_ERROR = deviance / n_held), then per K one line with FOLD `*` and the totals; `%.6f`, NaN as NA
+struct AdmixCvRow { int K, folds; uint64_t cv_seed; int fold; int64_t steps; bool converged; int64_t n_held; double deviance; };
+inline void write_admix_cv(const std::string& prefix, const std::vector<AdmixCvRow>& rows) {
+    OutFile o(prefix + ".admix.cv");
+    std::fputs("#K\tFOLDS\tCV_SEED\tFOLD\tSTEPS\tCONVERGED\tN_HELD\tDEVIANCE\tCV_ERROR\n", o.f);
+    auto num = [](char* b, size_t n, double x) { if (x != x) std::snprintf(b, n, "NA"); else std::snprintf(b, n, "%.6f", x); };
+    auto line = [&](const AdmixCvRow& r, bool total) {
+        char fold[16], dev[64], cv[64];
+        if (total) std::snprintf(fold, sizeof fold, "*"); else std::snprintf(fold, sizeof fold, "%d", r.fold);
+        num(dev, sizeof dev, r.deviance);
+        num(cv, sizeof cv, r.n_held > 0 ? r.deviance / (double)r.n_held : std::nan(""));
+        std::fprintf(o.f, "%d\t%d\t%llu\t%s\t%lld\t%d\t%lld\t%s\t%s\n", r.K, r.folds, (unsigned long long)r.cv_seed, fold, (long long)r.steps,
+                     r.converged ? 1 : 0, (long long)r.n_held, dev, cv);
+    };
+    for (size_t i = 0; i < rows.size();) {
+        size_t j = i;
+        AdmixCvRow t = rows[i];
+        t.steps = 0; t.converged = true; t.n_held = 0; t.deviance = 0.0;
+        for (; j < rows.size() && rows[j].K == rows[i].K; ++j) {
+            line(rows[j], false);
+            t.steps += rows[j].steps; t.converged = t.converged && rows[j].converged; t.n_held += rows[j].n_held; t.deviance += rows[j].deviance;
+        }
+        line(t, true);
+        i = j;
+    }
+}
 // the threshold of --gpca-homozyg-window-threshold as the exact fraction of its decimal text (digits, one optional point, no exponent),
 // reduced; false when the text is not such a number or the reduced denominator is above 2^20 (io / engine: Fraction(str(x)))
 inline bool roh_threshold(const std::string& text, int64_t& num, int64_t& den) {

@@ -93,6 +93,10 @@ struct Args {
     int64_t admix_k = 0, admix_seed = 0, admix_max_iter = 2000;
     double admix_tol = 1e-7;
     bool admix_no_accel = false, admix_supervised = false;
+    bool admix_cv = false, admix_cv_flag = false;       // --gpca-admixture-cv [V]; -cv-seed or -cv-k was given
+    int64_t admix_cv_folds = 5, admix_cv_seed = 0;
+    std::string admix_cv_k;                             // --gpca-admixture-cv-k A-B, as given
+    std::vector<int> admix_cv_ks;                       // the Ks the cross-validation scores, ascending
 };
 
 [[noreturn]] void usage_error(const std::string& msg) {
@@ -268,6 +272,12 @@ void print_help() {
         "      --gpca-admixture-max-iter <N>    EM steps at most [default: 2000]\n"
         "      --gpca-admixture-tol <X>         stop when a cycle gains less than X times the log-likelihood [default: 1e-7]\n"
         "      --gpca-admixture-no-accel        plain EM steps, without the SQUAREM acceleration\n"
+        "      --gpca-admixture-cv [V]          --gpca-admixture: the V-fold cross-validation error of the fit (2 .. 64): a random V-th of the\n"
+        "                                       observed calls is hidden from a refit and scored by its binomial deviance, once per fold\n"
+        "                                       -> <out>.admix.cv [default V: 5]\n"
+        "      --gpca-admixture-cv-seed <S>     the seed of the folds [default: 0]\n"
+        "      --gpca-admixture-cv-k <A-B>      --gpca-admixture-cv: also score every K of A .. B (1 <= A <= B <= 16) into <out>.admix.cv,\n"
+        "                                       to choose K\n"
         "      --gpca-admixture-supervised      the samples with a group in --gpca-within are references of known ancestry: K must be the\n"
         "                                       number of groups, and column k of the result is group k\n"
         "      --gpca-assoc-pcs <P>             --gpca-assoc-pheno: the first P columns of the scores this run writes are covariates\n"
@@ -373,6 +383,13 @@ Args parse(int argc, char** argv) {
         else if (f == "--gpca-admixture-tol") { a.admix_tol = to_f64(f, val()); a.admix_value_flag = true; }
         else if (f == "--gpca-admixture-no-accel") { a.admix_no_accel = true; a.admix_value_flag = true; }
         else if (f == "--gpca-admixture-supervised") { a.admix_supervised = true; a.admix_value_flag = true; }
+        else if (f == "--gpca-admixture-cv") {                                            // the value is optional: taken unless a flag follows
+            a.admix_cv = true;
+            const bool next = i + 1 < argc && (argv[i + 1][0] != '-' || (argv[i + 1][1] >= '0' && argv[i + 1][1] <= '9'));
+            if (has_inline || next) a.admix_cv_folds = to_i64(f, val());
+        }
+        else if (f == "--gpca-admixture-cv-seed") { a.admix_cv_seed = to_i64(f, val()); a.admix_cv_flag = true; }
+        else if (f == "--gpca-admixture-cv-k") { a.admix_cv_k = val(); a.admix_cv_flag = true; if (a.admix_cv_k.empty()) a.admix_cv_k = " "; }
         else if (f == "--gpca-homozyg") a.homozyg = true;
         else if (f == "--gpca-homozyg-window-snp") { a.hom_window_snp = to_i64(f, val()); a.homozyg = true; }
         else if (f == "--gpca-homozyg-window-het") { a.hom_window_het = to_i64(f, val()); a.homozyg = true; }
@@ -989,7 +1006,7 @@ int run_admix(gpca::Engine& eng, const Args& a, const std::vector<std::string>& 
     if (!inset.empty()) for (size_t s = 0; s < n; ++s) mode[s] = inset[s] ? 0 : 2;
     gpca_admix_params par{};
     par.K = K; par.max_iter = (int32_t)a.admix_max_iter; par.seed = (uint64_t)a.admix_seed; par.tol = a.admix_tol; par.accel = a.admix_no_accel ? 0 : 1;
-    std::vector<float> Q, F;
+    std::vector<float> Q, F, Q0, F0;
     gpca_admix_info info{};
     try {
         if (a.admix_supervised) {
@@ -998,6 +1015,7 @@ int run_admix(gpca::Engine& eng, const Args& a, const std::vector<std::string>& 
             const std::vector<uint8_t> fixed = gpca_host::admix_supervised(labels, K, Q);
             for (size_t s = 0; s < n; ++s) if (fixed[s]) mode[s] = 1;                     // a labelled sample is a reference wherever it stands
             par.init = 1;
+            if (a.admix_cv) { Q0 = Q; F0 = F; }                                           // the cross-validation starts every fold from here
         }
         info = eng.admix(par, &mode, Q, F);
     } catch (const gpca::Error& e) {
@@ -1013,6 +1031,27 @@ int run_admix(gpca::Engine& eng, const Args& a, const std::vector<std::string>& 
                   K, n, (long long)std::count(mode.begin(), mode.end(), (uint8_t)1), (long long)std::count(mode.begin(), mode.end(), (uint8_t)2), vids.size(),
                   (long long)info.steps, info.converged ? "converged" : "not converged", info.loglik, a.output_prefix.c_str(), K);
     logmsg(buf);
+    if (a.admix_cv) {
+        // --gpca-admixture-cv: the same mode bytes, seed, max-iter, tol and accel, and the supervised fit's start; every K of the range
+        std::vector<gpca_host::AdmixCvRow> table;
+        std::string ks;
+        for (int k : a.admix_cv_ks) {
+            gpca_admix_params cp = par;
+            cp.K = k;
+            std::vector<gpca_admix_cv_fold_info> fo;
+            const double cv = eng.admix_cv(cp, &mode, (int32_t)a.admix_cv_folds, (uint64_t)a.admix_cv_seed, &Q0, &F0, fo);
+            for (size_t c = 0; c < fo.size(); ++c)
+                table.push_back(gpca_host::AdmixCvRow{k, (int)a.admix_cv_folds, (uint64_t)a.admix_cv_seed, (int)c, fo[c].steps, fo[c].converged != 0, fo[c].n_held, fo[c].deviance});
+            if (cv != cv) std::snprintf(buf, sizeof buf, "CV error (K=%d): NA", k);
+            else std::snprintf(buf, sizeof buf, "CV error (K=%d): %.6f", k, cv);
+            logmsg(buf);
+            ks += (ks.empty() ? "" : ", ") + std::to_string(k);
+        }
+        gpca_host::write_admix_cv(a.output_prefix, table);
+        std::snprintf(buf, sizeof buf, "admixture cross-validation (%lld folds, seed %lld) of K = %s written to %s.admix.cv", (long long)a.admix_cv_folds,
+                      (long long)a.admix_cv_seed, ks.c_str(), a.output_prefix.c_str());
+        logmsg(buf);
+    }
     return 0;
 }
 
@@ -1509,6 +1548,29 @@ int main(int argc, char** argv) {
                 return 2;
             }
             if (a.stream == "on") { std::fputs(kAdmixNeedsResident, stderr); return 2; }
+        }
+        if (a.admix_cv || a.admix_cv_flag) {
+            if (!a.admixture) { std::fprintf(stderr, "error: --gpca-admixture-cv, --gpca-admixture-cv-seed and --gpca-admixture-cv-k need --gpca-admixture\n"); return 2; }
+            if (!a.admix_cv) { std::fprintf(stderr, "error: --gpca-admixture-cv-seed and --gpca-admixture-cv-k need --gpca-admixture-cv\n"); return 2; }
+            if (!(a.admix_cv_folds >= 2 && a.admix_cv_folds <= GPCA_ADMIX_CV_MAX_FOLDS)) { std::fprintf(stderr, "error: --gpca-admixture-cv V must lie in [2, 64]\n"); return 2; }
+            if (a.admix_cv_seed < 0) { std::fprintf(stderr, "error: --gpca-admixture-cv-seed must lie in [0, 2^63)\n"); return 2; }
+            int lo = (int)a.admix_k, hi = (int)a.admix_k;
+            if (!a.admix_cv_k.empty()) {
+                if (a.admix_supervised) {
+                    std::fprintf(stderr, "error: --gpca-admixture-cv-k cannot be combined with --gpca-admixture-supervised (the groups fix K)\n");
+                    return 2;
+                }
+                const size_t dash = a.admix_cv_k.find('-');
+                const std::string A = a.admix_cv_k.substr(0, dash), B = dash == std::string::npos ? "" : a.admix_cv_k.substr(dash + 1);
+                auto digits = [](const std::string& t) { return !t.empty() && t.size() <= 2 && t.find_first_not_of("0123456789") == std::string::npos; };
+                if (!digits(A) || !digits(B) || !(1 <= std::stoi(A) && std::stoi(A) <= std::stoi(B) && std::stoi(B) <= GPCA_ADMIX_MAX_K)) {
+                    std::fprintf(stderr, "error: --gpca-admixture-cv-k must be A-B with 1 <= A <= B <= 16\n");
+                    return 2;
+                }
+                lo = std::stoi(A); hi = std::stoi(B);
+            }
+            for (int k = std::min(lo, (int)a.admix_k); k <= std::max(hi, (int)a.admix_k); ++k)
+                if ((k >= lo && k <= hi) || k == (int)a.admix_k) a.admix_cv_ks.push_back(k);
         }
         if (a.homozyg) {
             if (!a.eigensnp) { std::fprintf(stderr, "error: --gpca-homozyg needs the --eigensnp workflow\n"); return 2; }

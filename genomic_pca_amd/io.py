@@ -1493,3 +1493,34 @@ def write_admix(prefix: str, K: int, family_ids: Sequence[str], sample_ids: Sequ
         f.write("#K\tSEED\tSTEPS\tCYCLES\tCONVERGED\tLOGLIK\n")
         f.write(f"{K}\t{int(info['seed'])}\t{int(info['steps'])}\t{int(info['cycles'])}\t{1 if info['converged'] else 0}\t{'%.4f' % float(info['loglik'])}\n")
     return paths
+
+
+def write_admix_cv(prefix: str, rows) -> str:
+    """P.admix.cv, the cross-validation of the admixture fit (gpca_admix_cv; gpca.h section a22): `#K FOLDS CV_SEED FOLD STEPS CONVERGED
+    N_HELD DEVIANCE CV_ERROR`, tab-separated.  rows: one dict per fold (K, folds, cv_seed, fold, steps, converged, n_held, deviance), the
+    folds of one K together and ascending; CV_ERROR of a fold is its deviance / n_held.  After the folds of a K comes one line with
+    FOLD `*` and the totals: the summed steps, 1 if every fold converged, the summed n_held and deviance (folds ascending), and the K's
+    cross-validation error, their quotient.  The two floats as `%.6f`, NaN (nothing held) as NA."""
+    def num(x):
+        return "NA" if x != x else "%.6f" % x
+
+    def line(K, folds, seed, fold, steps, conv, held, dev):
+        return f"{K}\t{folds}\t{seed}\t{fold}\t{steps}\t{1 if conv else 0}\t{held}\t{num(dev)}\t{num(dev / held if held > 0 else float('nan'))}\n"
+
+    path = prefix + ".admix.cv"
+    rows = list(rows)
+    with _open_out(path, False) as f:
+        f.write("#K\tFOLDS\tCV_SEED\tFOLD\tSTEPS\tCONVERGED\tN_HELD\tDEVIANCE\tCV_ERROR\n")
+        i = 0
+        while i < len(rows):
+            j = i
+            while j < len(rows) and int(rows[j]["K"]) == int(rows[i]["K"]):
+                j += 1
+            steps, conv, held, dev = 0, True, 0, 0.0
+            for r in rows[i:j]:
+                f.write(line(int(r["K"]), int(r["folds"]), int(r["cv_seed"]), int(r["fold"]), int(r["steps"]), bool(r["converged"]), int(r["n_held"]),
+                             float(r["deviance"])))
+                steps += int(r["steps"]); conv = conv and bool(r["converged"]); held += int(r["n_held"]); dev += float(r["deviance"])
+            f.write(line(int(rows[i]["K"]), int(rows[i]["folds"]), int(rows[i]["cv_seed"]), "*", steps, conv, held, dev))
+            i = j
+    return path

@@ -902,7 +902,7 @@ GPCA_API int gpca_roh_select(const uint32_t* segs /* [n][5] */, int64_t n, const
  *     1; trace NULL with trace_cap > 0; with gpca_admix_step or init = 1, a Q row that is not non-negative and finite with a positive sum
  *     or an F value outside [0, 1]), GPCA_ERR_INVALID_GENOTYPE (a kept row holds a value outside {0, 1, 2, missing} on a sample below N;
  *     the message names the row, as in a12), GPCA_ERR_OOM (checked before any allocation).
- *  Not there: K > 16; cross-validation error and the choice of K; restarts from several seeds; projection onto a saved F; standard
+ *  Not there: K > 16; restarts from several seeds; projection onto a saved F; standard
  *     errors or bootstrap; haploid and sex chromosomes; ADMIXTURE's own block-relaxation / quasi-Newton numbers; streamed and
  *     row-sharded handles. */
 #define GPCA_ADMIX_MAX_K 16
@@ -924,6 +924,51 @@ GPCA_API int gpca_admix_step(gpca_handle* h, int32_t K, const float* Q, const fl
                              float* Fn, double* loglik);
 GPCA_API int gpca_admix(gpca_handle* h, const gpca_admix_params* params, const uint8_t* mode /* [N] or NULL */, float* Q, float* F,
                         gpca_admix_info* info);
+
+/* ---- a22: the cross-validation error of the admixture fit, and with it the choice of K: a random v-th of the observed calls is hidden
+ * from the fit, inside the step's kernel, and scored by its binomial deviance (Alexander & Lange 2011).  Everything of a21 holds as it
+ * stands there: the handle's state, the kept rows in PCA-SNP order, Q, F, mode, eps and the summation shape.
+ *  Fold of a call: a pure function of (cv_seed, v, the kept-row index i in 0 .. Kr - 1, the sample j); i is the position among the kept
+ *     rows, as in a21's F init, not the original row.  w = word i & 3 of philox4x32-10(counter = (j, i >> 2, 0, stream 0x41444D43), key =
+ *     (seed low word, seed high word)); fold = ((uint64)w * v) >> 32; 2 <= v <= GPCA_ADMIX_CV_MAX_FOLDS = 64.  Four consecutive kept rows
+ *     of a sample share one philox call.  gpca_admix_cv_fold writes that rule for the kept rows [row0, row0 + rows) and the samples 0 ..
+ *     N - 1 (host only, no handle: GPCA_ERR_BAD_ARG for out NULL, folds outside 2 .. 64, a negative extent or an index of 2^31 or more).
+ *  Hold-out step (v, c): a21's step with every observed call whose fold is c treated as missing: a = b = 0 on the Q side and on the F
+ *     side, and no term enters loglik.  Q', F' and loglik are the bits gpca_admix_step returns on the same handle after those calls are
+ *     overwritten with the missing code: the same sums in the same order, the held terms absent.  Three more results are evaluated at
+ *     the step's input (Q, F) over the held-out observed calls of all samples, whatever their mode:
+ *      held_loglik = the sum of g log p1 + (2 - g) log p0 with the same f32 p1, p0 and logf, added in f64 in loglik's order (per sample
+ *        over the block's rows, the chunk's 256 samples, the (block, chunk) partials in stride-256 classes);
+ *      n_held = the number of held-out observed calls, n_het_held = the number of those with g = 1: exact 64-bit integer counts (integer
+ *        atomic adds, whose order cannot matter).
+ *  Deviance of fold c: the squared binomial deviance residual of a call with fitted mean 2 p1 is 2 [g log(g / (2 p1)) + (2 - g)
+ *     log((2 - g) / (2 p0))]; summed over the fold that is exactly deviance_c = -2 held_loglik_c - 4 ln 2 n_het_held_c (f64, on the host).
+ *  cv_error = sum_c deviance_c / sum_c n_held_c, folds ascending; NaN if no call is held.  ADMIXTURE's own fold assignment and printed
+ *     digits are not claimed.
+ *  gpca_admix_cv: for c = 0 .. v - 1, exactly gpca_admix's loop (a21's cycle rule, SQUAREM, the stop on the training loglik) with the
+ *     hold-out step (v, c) in place of the step, from the same start for every fold: init 0 = gpca_admix_init(params->seed), init 1 =
+ *     the caller's Q0 and F0, clamped as in a21 (what a supervised fit needs); the caller's mode.  Then one more hold-out step at the
+ *     returned parameters, whose Q' and F' are dropped and whose three held-out sums are the fold's score.  out[c]: steps, cycles,
+ *     converged, fallbacks, loglik (the last cycle-start training value), held_loglik, n_held, n_het_held, deviance.
+ *     The philox init's F uses the row's QC counts over all calls, the held ones included: that is a starting point, not a fit.
+ *  Errors: as in a21 (no trace here), and GPCA_ERR_BAD_ARG for folds outside 2 .. 64, fold outside 0 .. folds - 1, Q0 or F0 NULL with
+ *     init = 1.
+ *  Not there: ADMIXTURE's own fold assignment; standard errors of the CV error; streamed and row-sharded handles. */
+#define GPCA_ADMIX_CV_MAX_FOLDS 64
+typedef struct gpca_admix_cv_fold_info {
+    int64_t steps, cycles;
+    int32_t converged, fallbacks;
+    double loglik, held_loglik;
+    int64_t n_held, n_het_held;
+    double deviance;
+} gpca_admix_cv_fold_info;
+GPCA_API int gpca_admix_cv_fold(uint64_t seed, int32_t folds, int64_t row0, int64_t rows, int64_t N, uint8_t* out /* [rows][N] */);
+GPCA_API int gpca_admix_step_holdout(gpca_handle* h, int32_t K, const float* Q, const float* F, const uint8_t* mode /* [N] or NULL */,
+                                     int32_t folds, int32_t fold, uint64_t cv_seed, float* Qn, float* Fn, double* loglik, double* held_loglik,
+                                     int64_t* n_held, int64_t* n_het_held);
+GPCA_API int gpca_admix_cv(gpca_handle* h, const gpca_admix_params* params, const uint8_t* mode /* [N] or NULL */, int32_t folds,
+                           uint64_t cv_seed, const float* Q0 /* [N][K], init = 1 */, const float* F0 /* [Kr][K], init = 1 */,
+                           gpca_admix_cv_fold_info* out /* [folds] */, double* cv_error);
 
 /* ---- f3: the stages of EigenSNPCoreAlgorithm::compute_pca (main.rs:311-327, 359-366) ------------------------------------------
  * The algorithm lives in the un-vendored efficient_pca crate (Cargo.toml:30, branch "main", no pinned revision): what follows is

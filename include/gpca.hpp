@@ -472,6 +472,33 @@ public:
         info.trace = nullptr; info.trace_cap = 0;
         return info;
     }
+    // one hold-out step (gpca.h section a22): admix_step with the observed calls of fold `fold` of `folds` under cv_seed counted as
+    // missing; held = held_loglik, n_held, n_het_held of those calls at (Q, F).  Returns the training log-likelihood.
+    struct AdmixHeld { double held_loglik; int64_t n_held, n_het_held; };
+    double admix_step_holdout(int32_t K, const std::vector<float>& Q, const std::vector<float>& F, const std::vector<uint8_t>* mode, int32_t folds,
+                              int32_t fold, uint64_t cv_seed, std::vector<float>& Qn, std::vector<float>& Fn, AdmixHeld& held) const {
+        const size_t N = (size_t)dims().second, Kr = (size_t)gpca_num_pca_snps(h_), k = (size_t)std::max<int32_t>(K, 1);
+        if (Q.size() != N * k || F.size() != Kr * k || (mode && mode->size() != N)) throw std::invalid_argument("admix_step_holdout: Q [N][K], F [Kr][K], mode [N]");
+        Qn.assign(std::max<size_t>(Q.size(), 1), 0.0f); Fn.assign(std::max<size_t>(F.size(), 1), 0.0f);
+        double ll = 0.0;
+        check(gpca_admix_step_holdout(h_, K, Q.data(), F.data(), mode ? mode->data() : nullptr, folds, fold, cv_seed, Qn.data(), Fn.data(), &ll,
+                                      &held.held_loglik, &held.n_held, &held.n_het_held));
+        Qn.resize(Q.size()); Fn.resize(F.size());
+        return ll;
+    }
+    // the cross-validation error of the fit (gpca.h section a22): per fold the fit with the fold's observed calls hidden, then their
+    // deviance; from the seed's init (params.init = 0) or from Q0 and F0 (1).  Returns cv_error; folds_out [folds].
+    double admix_cv(const gpca_admix_params& params, const std::vector<uint8_t>* mode, int32_t folds, uint64_t cv_seed, const std::vector<float>* Q0,
+                    const std::vector<float>* F0, std::vector<gpca_admix_cv_fold_info>& folds_out) const {
+        const size_t N = (size_t)dims().second, Kr = (size_t)gpca_num_pca_snps(h_), k = (size_t)std::max<int32_t>(params.K, 1);
+        if (mode && mode->size() != N) throw std::invalid_argument("admix_cv: mode needs one byte per sample");
+        if (params.init == 1 && (!Q0 || !F0 || Q0->size() != N * k || F0->size() != Kr * k)) throw std::invalid_argument("admix_cv: init = 1 needs Q0 [N][K] and F0 [Kr][K]");
+        folds_out.assign((size_t)std::min<int32_t>(std::max<int32_t>(folds, 1), GPCA_ADMIX_CV_MAX_FOLDS), gpca_admix_cv_fold_info{});
+        double cv = 0.0;
+        check(gpca_admix_cv(h_, &params, mode ? mode->data() : nullptr, folds, cv_seed, params.init == 1 ? Q0->data() : nullptr,
+                            params.init == 1 ? F0->data() : nullptr, folds_out.data(), &cv));
+        return cv;
+    }
     // the host rule on the records (gpca_roh_select; host only): keep [n] by length in bp and bp per SNP; pos [K] = the kept rows' positions
     static std::vector<uint8_t> roh_select(const std::vector<uint32_t>& segs, const std::vector<int64_t>& pos, int64_t min_bp, int64_t max_bp_per_snp) {
         const size_t n = segs.size() / 5;
