@@ -28,6 +28,7 @@ STORE_AUTO = 0         # 2-bit codes from 1 024 samples on, int8 below (decided 
 STORE_2BIT = 1
 STORE_INT8 = 2
 GROUPS_MAX = 64           # gpca_group_counts: most sample groups of one call (include/gpca.h)
+FSTAT_BLOCK_VARIANTS, FSTAT_BLOCK_BP = 0, 1   # gpca_fstat_blocks units (include/gpca.h)
 LDSCORE_UNBIASED = 1      # gpca_ld_score flag (include/gpca.h)
 ROH_WINDOW_MAX = 64       # gpca_roh: the widest window (include/gpca.h)
 ROH_DEN_MAX = 1 << 20     # gpca_roh: the largest denominator of the threshold
@@ -179,6 +180,9 @@ PROTOTYPES = {
     "gpca_group_counts": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p]),
     "gpca_fst_hudson": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gpca_fst_wc": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpca_f2_blocks": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpca_fstat_blocks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]),
+    "gpca_fstat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "gpca_sample_counts": (C.c_int, [_H, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gpca_het_weights": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
     "gpca_sample_het": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),

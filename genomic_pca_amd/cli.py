@@ -183,6 +183,15 @@ def build_parser() -> argparse.ArgumentParser:
                    help="--gpca-within: Fst between every pair of groups over the SNPs that pass the SNP QC, hudson (Bhatia et al. "
                         "2013) or wc (Weir and Cockerham 1984; with more than two groups also jointly) -> <out>.fst.summary")
     p.add_argument("--gpca-fst-variants", action="store_true", help="--gpca-fst: also the per-SNP terms -> <out>.fst.var")
+    p.add_argument("--gpca-f2", action="store_true",
+                   help="--gpca-within: the unbiased f2 of every pair of groups over the SNPs that pass the SNP QC, with its weighted "
+                        "block-jackknife standard error -> <out>.f2.summary")
+    p.add_argument("--gpca-fstats", default=None, metavar="FILE",
+                   help="--gpca-within: the statistics FILE lists, one per line: `f2 A B`, `f3 C A B` (C is the target) or `f4 A B C D` "
+                        "with group names -> <out>.fstats (estimate, jackknife SE, Z)")
+    p.add_argument("--gpca-fstat-block", default=None, metavar="SPEC",
+                   help="--gpca-f2 / --gpca-fstats: the jackknife blocks, a variant count such as 500 or a span such as 5000kb; a block "
+                        "ends at every change of chromosome [default: 5000kb]")
     p.add_argument("--gpca-sample-missing", action="store_true",
                    help="--eigensnp: the missing calls of every sample over the SNPs that pass the SNP QC -> <out>.smiss (#FID IID "
                         "MISSING_CT OBS_CT F_MISS)")
@@ -369,7 +378,7 @@ def run_eigensnp_workflow(a) -> int:
         raise SystemExit(PCRELATE_NEEDS_RESIDENT)
     if streamed and a.gpca_assoc_pheno is not None:
         raise SystemExit(ASSOC_NEEDS_RESIDENT)
-    if streamed and a.gpca_within is not None and (a.gpca_freq_strat or a.gpca_fst is not None):
+    if streamed and a.gpca_within is not None and _strat_asked(a):
         raise SystemExit(STRAT_NEEDS_RESIDENT)
     if streamed and _sample_qc_asked(a):
         raise SystemExit(SAMPLE_QC_NEEDS_RESIDENT)
@@ -451,7 +460,7 @@ def run_eigensnp_workflow(a) -> int:
         _admix(eng, a, fs, cols, sample_ids, rows, inset)
     if a.gpca_make_pcrelate is not None:
         _pcrelate(eng, a, fs, cols, sample_ids, np.asarray(scores, np.float64)[:, :a.gpca_make_pcrelate], inset, len(rows))
-    if a.gpca_within is not None and (a.gpca_freq_strat or a.gpca_fst is not None):
+    if a.gpca_within is not None and _strat_asked(a):
         _strat(eng, a, fs, cols, sample_ids, st)
     l2 = _ld_score(eng, a, fs, st) if a.gpca_ld_score is not None else None
     if a.gpca_assoc_pheno is not None:
@@ -740,6 +749,14 @@ STRAT_NEEDS_RESIDENT = ("error: --gpca-within needs the genotype matrix resident
                         "are not implemented")
 
 
+def _fstat_asked(a):
+    return a.gpca_f2 or a.gpca_fstats is not None
+
+
+def _strat_asked(a):
+    return a.gpca_freq_strat or a.gpca_fst is not None or _fstat_asked(a)
+
+
 def _within_table(a):
     """The table of --gpca-within, read once before any work on the device; refuses more than 64 groups, and fewer than 2 for --gpca-fst."""
     try:
@@ -752,8 +769,18 @@ def _within_table(a):
         raise SystemExit(f"error: --gpca-within: {len(t.names)} groups are more than {gio.GROUPS_MAX}")
     if a.gpca_fst is not None and len(t.names) < 2:
         raise SystemExit(f"error: --gpca-fst needs at least two groups, --gpca-within names {len(t.names)}")
+    if _fstat_asked(a) and len(t.names) < 2:
+        raise SystemExit(f"error: --gpca-f2 and --gpca-fstats need at least two groups, --gpca-within names {len(t.names)}")
     if len(t.names) < 1:
         raise SystemExit("error: --gpca-within names no group")
+    a.gpca_fstats_list = None
+    if a.gpca_fstats is not None:
+        try:
+            a.gpca_fstats_list = gio.read_fstats_list(a.gpca_fstats, t.names)
+        except OSError:
+            raise SystemExit(f"error: --gpca-fstats: cannot open {a.gpca_fstats}") from None
+        except ValueError as e:
+            raise SystemExit(f"error: --gpca-fstats: {e}") from None
     return t
 
 
@@ -765,7 +792,8 @@ def _strat(eng, a, fs, cols, sample_ids, st):
     """--gpca-freq-strat / --gpca-fst: the genotype counts of every SNP that passes the SNP QC inside every group of --gpca-within
     (gpca_group_counts), in row bands, into P.frq.strat, and Fst from them (gpca_fst_hudson / gpca_fst_wc) into P.fst.summary and
     P.fst.var.  Resets the keep mask to the QC mask (mu, sigma unchanged), which ends the fit's validity; every kept sample with a
-    group counts, the KING in-set or not."""
+    group counts, the KING in-set or not.  --gpca-f2 / --gpca-fstats: the same bands through gpca_f2_blocks, whose counts serve the files
+    above, the blocks from io.fstat_blocks over the same SNPs; gpca_fstat turns the summed blocks into P.f2.summary and P.fstats."""
     from . import _lib
     fids = fs.family_ids if cols is None else [fs.family_ids[i] for i in cols]
     labels, names = gio.align_within(a.gpca_within_table, fids, sample_ids)
@@ -774,9 +802,19 @@ def _strat(eng, a, fs, cols, sample_ids, st):
     rows = np.flatnonzero(st["keep"])
     pairs = gio.fst_pairs(P)
     hud, wcp, wcj = np.zeros((max(len(pairs), 1), 3)), np.zeros((max(len(pairs), 1), 3)), np.zeros(3)
+    fstat, need_counts = _fstat_asked(a), a.gpca_freq_strat or a.gpca_fst is not None
+    if fstat:
+        spec = a.gpca_fstat_block if a.gpca_fstat_block is not None else gio.FSTAT_BLOCK_DEFAULT
+        block, B = gio.fstat_blocks([fs.chromosomes[i] for i in rows], [int(fs.positions[i]) for i in rows], spec)
+        facc, fcnt = np.zeros((max(B, 1), len(pairs)), np.int64), np.zeros((max(B, 1), len(pairs)), np.int64)
     try:
-        for bi, (r0, r1) in enumerate(gio.group_count_bands(len(rows), P)):
-            c = eng.group_counts(labels, P, rows=(r0, r1))
+        for bi, (r0, r1) in enumerate(gio.group_count_bands(len(rows), P, max_rows=gio.F2_BAND_ROWS_MAX if fstat else None)):
+            if fstat:
+                res = eng.f2_blocks(labels, block[r0:r1], P, B, rows=(r0, r1), counts=need_counts)
+                facc += res[0]; fcnt += res[1]
+                c = res[2] if need_counts else None
+            else:
+                c = eng.group_counts(labels, P, rows=(r0, r1))
             meta = _snp_meta(fs, rows[r0:r1])
             if a.gpca_freq_strat:
                 gio.write_frq_strat(f"{a.output_prefix}.frq.strat", *meta, names, c, append=bi > 0)
@@ -806,6 +844,15 @@ def _strat(eng, a, fs, cols, sample_ids, st):
         sums = hud[:len(pairs)] if a.gpca_fst == "hudson" else (np.vstack([wcp[:len(pairs)], wcj[None]]) if P > 2 else wcp[:len(pairs)])
         gio.write_fst_summary(a.output_prefix, a.gpca_fst, names, sums)
         _log(f"{a.gpca_fst} Fst of {len(pairs)} pairs of groups over {len(rows)} SNPs, written to {a.output_prefix}.fst.summary")
+    if fstat and B >= 1:
+        if a.gpca_f2:
+            gio.write_f2_summary(a.output_prefix, names, GpcaEngine.fstat(facc, fcnt, [(j, i, j, i) for j, i in pairs]))
+            _log(f"f2 of {len(pairs)} pairs of groups over {len(rows)} SNPs in {B} jackknife blocks ({spec}), written to "
+                 f"{a.output_prefix}.f2.summary")
+        if a.gpca_fstats is not None:
+            lst = a.gpca_fstats_list
+            gio.write_fstats(a.output_prefix, names, lst, GpcaEngine.fstat(facc, fcnt, [gio.fstat_quad(k, g) for k, g in lst]))
+            _log(f"{len(lst)} f-statistics over {len(rows)} SNPs in {B} jackknife blocks ({spec}), written to {a.output_prefix}.fstats")
 
 
 def _cc_freq(eng, a, fs, rows, Yb, bnames, include):
@@ -1113,6 +1160,16 @@ def main(argv=None) -> int:
         raise SystemExit("error: --gpca-assoc-cc-freq needs --gpca-assoc-logistic")
     if a.gpca_within is None and (a.gpca_freq_strat or a.gpca_fst is not None):
         raise SystemExit("error: --gpca-freq-strat and --gpca-fst need --gpca-within")
+    if a.gpca_within is None and (_fstat_asked(a) or a.gpca_fstat_block is not None):
+        raise SystemExit("error: --gpca-f2, --gpca-fstats and --gpca-fstat-block need --gpca-within")
+    if a.gpca_fstat_block is not None and not _fstat_asked(a):
+        raise SystemExit("error: --gpca-fstat-block needs --gpca-f2 or --gpca-fstats")
+    if _fstat_asked(a):
+        try:
+            gio.parse_ld_window(a.gpca_fstat_block if a.gpca_fstat_block is not None else gio.FSTAT_BLOCK_DEFAULT)
+        except ValueError:
+            raise SystemExit(f"error: --gpca-fstat-block: '{a.gpca_fstat_block}' is neither a variant count such as 500 nor a span such as "
+                             "5000kb") from None
     if a.gpca_fst_variants and a.gpca_fst is None:
         raise SystemExit("error: --gpca-fst-variants needs --gpca-fst")
     if a.gpca_fst is not None and a.gpca_fst not in ("hudson", "wc"):
@@ -1120,9 +1177,9 @@ def main(argv=None) -> int:
     if a.gpca_within is not None:
         if not a.eigensnp:
             raise SystemExit("error: --gpca-within needs the --eigensnp workflow")
-        if not a.gpca_freq_strat and a.gpca_fst is None and not a.gpca_admixture_supervised:
+        if not _strat_asked(a) and not a.gpca_admixture_supervised:
             raise SystemExit("error: --gpca-within needs --gpca-freq-strat or --gpca-fst")
-        if a.gpca_stream == "on" and (a.gpca_freq_strat or a.gpca_fst is not None):
+        if a.gpca_stream == "on" and _strat_asked(a):
             raise SystemExit(STRAT_NEEDS_RESIDENT)
         a.gpca_within_table = _within_table(a)
     if _sample_qc_asked(a):

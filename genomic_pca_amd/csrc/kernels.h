@@ -413,6 +413,11 @@ void launch_gc_onehot(hipStream_t st, const int32_t* group, int64_t N, int P, ui
 int launch_group_counts(hipStream_t st, const void* G, int packed, int64_t ldr, const int64_t* krows, int64_t N, const uint8_t* O,
                         const unsigned* size, int P, int64_t row0, int64_t row1, unsigned* counts, unsigned long long* bad);
 
+// ---- f2 jackknife blocks (f2_blocks.hip): counts [rows][P][3] as launch_group_counts leaves them, block [rows] in -1 .. B - 1 (-1: the
+// row enters nothing); acc [B][pairs] i64 += rint(v 2^40) and cnt [B][pairs] i32 += 1 of every (row, pair) with both groups observed,
+// both zeroed by the caller.  Nonzero when P or rows is outside the kernel's limits (plan_math.h: fb_*).
+int launch_f2_blocks(hipStream_t st, const unsigned* counts, const int* block, int64_t rows, int P, long long* acc, int* cnt);
+
 // ---- per-sample genotype counts (sample_counts.hip): part [plan.splits][sc_npad(N)][3] u32 = missing, het, hom2 and (q given)
 // qpart [plan.splits][sc_npad(N)] u64 = the q of the missing calls, per row split of kept rows [row0, row1) (PCA-SNP order through
 // krows; q [row1 - row0]); *bad as in launch_assoc.  launch_sc_sum: counts [N][3] = n_obs, n_het, n_hom2 and qsum [N] = qtot - the

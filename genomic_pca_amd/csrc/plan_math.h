@@ -458,6 +458,41 @@ constexpr double gc_call_bytes(int64_t N, int64_t rows, int P) {
            4.0 * (double)gc_counts_capacity(rows, P) + 8.0;
 }
 
+// ---- f2 jackknife blocks from the counts workspace (f2_blocks.hip, gpca_f2_blocks.cpp) -----------------------------------------------
+// A workgroup of kFbThreads threads owns kFbRun consecutive band rows, in LDS tiles of kFbTile rows.  Per tile, thread t forms p and
+// h = (p (1 - p)) / (n - 1) of group t % kFbPitch of rows t / kFbPitch + (kFbThreads / kFbPitch) k (a wave per row: the row's validity
+// mask is one ballot); then thread t owns the pairs t, t + kFbThreads, ... (at most kFbSlots), whose i64 sums and i32 counts stay in
+// registers while the block id stays the same.
+constexpr int kFbThreads = 256, kFbTile = 32, kFbRun = 256, kFbPitch = 64, kFbSlots = 8;
+constexpr int64_t kFbMaxRows = (int64_t)1 << 21;     // rows of a call: |q| <= 1.5 x 2^40 < 2^41 per row, so a sum stays below 2^62
+constexpr double kFbScale = 1099511627776.0;         // 2^40
+static_assert(kFbPitch == kGcMaxGroups && kFbPitch == 64 && kFbThreads % kFbPitch == 0 && kFbRun % kFbTile == 0, "a wave stages one row's groups");
+static_assert(kFbTile % (kFbThreads / kFbPitch) == 0, "the staging loop covers a tile in whole passes");
+static_assert(kFbSlots * kFbThreads >= kGcMaxGroups * (kGcMaxGroups - 1) / 2, "every pair has a register slot");
+constexpr int fb_pairs(int P) { return P * (P - 1) / 2; }
+constexpr int fb_slots(int P) { return (fb_pairs(P) + kFbThreads - 1) / kFbThreads; }
+// the pair map: pair q = i (i - 1) / 2 + j with j < i; fb_pair_i walks i up from 1 (at most kGcMaxGroups steps, once per thread and slot)
+constexpr int fb_pair_index(int i, int j) { return i * (i - 1) / 2 + j; }
+constexpr int fb_pair_i(int q) { int i = 1; while ((i + 1) * i / 2 <= q) ++i; return i; }
+constexpr int fb_pair_j(int q) { return q - fb_pair_i(q) * (fb_pair_i(q) - 1) / 2; }
+constexpr int64_t fb_row_blocks(int64_t rows) { return (rows + kFbRun - 1) / kFbRun; }
+// the staging map: pass k of thread t stages (tile row, group); the LDS index of a (tile row, group) value
+constexpr int fb_stage_passes() { return kFbTile / (kFbThreads / kFbPitch); }
+constexpr int fb_stage_row(int t, int k) { return t / kFbPitch + (kFbThreads / kFbPitch) * k; }
+constexpr int fb_stage_group(int t) { return t % kFbPitch; }
+constexpr int fb_lds_index(int r, int g) { return r * kFbPitch + g; }
+constexpr int fb_lds_values() { return kFbTile * kFbPitch; }                  // doubles of each of the two LDS planes (p and h)
+constexpr int fb_lds_bytes() { return 2 * 8 * fb_lds_values() + 8 * kFbTile + 4 * kFbTile; }   // + the masks (u64) and the block ids (i32)
+// where the sum and the count of (block b, pair q) lie
+constexpr int64_t fb_out_index(int64_t b, int P, int q) { return b * fb_pairs(P) + q; }
+// elements of the call's own buffers: the block ids [rows] (i32), the sums [B][pairs] (i64), the counts [B][pairs] (i32)
+constexpr int64_t fb_block_capacity(int64_t rows) { return rows; }
+constexpr int64_t fb_out_capacity(int64_t B, int P) { return B * (int64_t)fb_pairs(P); }
+// The device bytes a call allocates (gpca_f2_blocks' GPCA_ERR_OOM sum, without the check's slack): the group-counts pass and the above
+constexpr double fb_call_bytes(int64_t N, int64_t rows, int P, int64_t B) {
+    return gc_call_bytes(N, rows, P) + 4.0 * (double)fb_block_capacity(rows) + (8.0 + 4.0) * (double)fb_out_capacity(B, P);
+}
+
 // ---- per-sample genotype counts (sample_counts.hip, gpca_sample_counts.cpp) ---------------------------------------------------------
 // A thread owns kScLane consecutive samples (one uint4 of an int8 row, one dword of a 2-bit row); a workgroup of kScThreads threads (one
 // wave) owns a chunk of kScChunk samples and one of the plan's row splits: the band's kept rows [split * per, (split + 1) * per).  The

@@ -746,6 +746,59 @@ class GpcaEngine:
         self._chk(self._lib.gpca_group_counts(self._h, _vp(gv), P, r0, r1, _vp(out)))
         return out[:n]
 
+    def f2_blocks(self, group, block, n_groups: Optional[int] = None, n_blocks: Optional[int] = None,
+                  rows: Optional[Tuple[int, int]] = None, counts: bool = False):
+        """f2 jackknife blocks (gpca_f2_blocks; gpca.h section a23): group and rows as in group_counts (n_groups = P, 2 .. 64); block =
+        one jackknife block id per row of the band, 0 .. B - 1, or -1 for a row that enters nothing; n_blocks = B (default: the largest
+        id + 1, at least 1).  Returns (acc, cnt), both int64 [B][P (P - 1) / 2]: per block and pair (i, j), j < i, at i (i - 1) / 2 + j,
+        the sum of rint(f2 2^40) over the block's rows on which both groups have a call, and the number of those rows; with counts=True
+        also group_counts' uint32 [rows][P][3] of the band, from the same genotype pass.  Exact integers, written per call: the caller
+        adds its bands."""
+        N = self.dims()[1]
+        gv = np.asarray(group)
+        if gv.shape != (N,) or gv.dtype.kind not in "iu":
+            raise ValueError("group must be an integer array with one label per sample")
+        gv = np.ascontiguousarray(np.clip(gv.astype(np.int64), -1, 1 << 30), np.int32)
+        P = int(n_groups) if n_groups is not None else max(int(gv.max(initial=-1)) + 1, 1)
+        K = int(self._lib.gpca_num_pca_snps(self._h))
+        r0, r1 = (0, K) if rows is None else (int(rows[0]), int(rows[1]))
+        n = max(r1 - r0, 0)
+        bv = np.asarray(block)
+        if bv.shape != (n,) or bv.dtype.kind not in "iu":
+            raise ValueError("block must be an integer array with one block id per row of the band")
+        bq = np.zeros(max(n, 1), np.int32)
+        bq[:n] = np.clip(bv.astype(np.int64), -(1 << 30), 1 << 30)
+        B = int(n_blocks) if n_blocks is not None else max(int(bv.max(initial=-1)) + 1, 1)
+        Pc = max(min(P, 64), 2)
+        pairs = Pc * (Pc - 1) // 2
+        acc = np.zeros((max(B, 1), pairs), np.int64)
+        cnt = np.zeros((max(B, 1), pairs), np.int64)
+        cv = np.zeros((max(n, 1), Pc, 3), np.uint32) if counts else None
+        self._chk(self._lib.gpca_f2_blocks(self._h, _vp(gv), P, r0, r1, _vp(bq), B, _vp(acc), _vp(cnt), _vp(cv)))
+        return (acc, cnt, cv[:n]) if counts else (acc, cnt)
+
+    @staticmethod
+    def fstat(acc, cnt, quads) -> np.ndarray:
+        """f2, f3 and f4 with their weighted block-jackknife standard errors (gpca_fstat; gpca.h section a23; host only).  acc and cnt
+        [B][pairs] = the bands of f2_blocks added up; quads [M][4] = (a, b, c, d) per statistic, read as f4(a, b; c, d), so that
+        f2(A, B) = (A, B, A, B) and f3(C; A, B) = (C, A, C, B).  Returns float64 [M][6] = theta, the jackknife estimate, se, z = theta /
+        se, the blocks used, the fewest SNPs behind one of its pairs."""
+        av, cv = np.ascontiguousarray(acc, np.int64), np.ascontiguousarray(cnt, np.int64)
+        if av.ndim != 2 or av.shape != cv.shape:
+            raise ValueError("acc and cnt must be [B][pairs] as f2_blocks returns them")
+        B, pairs = av.shape
+        P = int(round((1.0 + np.sqrt(1.0 + 8.0 * pairs)) / 2.0))
+        if P * (P - 1) // 2 != pairs:
+            raise ValueError(f"{pairs} is not a number of pairs P (P - 1) / 2")
+        qv = np.ascontiguousarray(quads, np.int32).reshape(-1, 4)
+        M = qv.shape[0]
+        out = np.zeros((max(M, 1), 6), np.float64)
+        lib = _lib.load()
+        rc = lib.gpca_fstat(_vp(av), _vp(cv), B, P, _vp(qv if M else np.zeros((1, 4), np.int32)), M, _vp(out))
+        if rc != _lib.GPCA_OK:
+            raise GpcaError(rc, "gpca_fstat: " + lib.gpca_status_string(rc).decode())
+        return out[:M]
+
     def sample_counts(self, weights=None, rows: Optional[Tuple[int, int]] = None) -> dict:
         """Genotype counts per sample (gpca_sample_counts; gpca.h section a18) over the kept rows [row0, row1) in PCA-SNP order
         (rows; default: all).  Returns {"counts": uint32 [N][3] = n_obs, n_het, n_hom2 (the rows on which the sample has an observed

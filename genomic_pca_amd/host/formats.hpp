@@ -1125,9 +1125,12 @@ inline std::vector<int32_t> align_within(const WithinTable& t, const std::vector
     }
     return out;
 }
-// [row0, row1) bands of the K kept rows whose counts (rows x P x 3) hold at most max_values entries (at least one row)
-inline std::vector<std::pair<int64_t, int64_t>> group_count_bands(int64_t K, int64_t P, int64_t max_values = (int64_t)1 << 26) {
-    const int64_t step = std::max<int64_t>(max_values / (3 * std::max<int64_t>(P, 1)), 1);
+// [row0, row1) bands of the K kept rows whose counts (rows x P x 3) hold at most max_values entries (at least one row); max_rows > 0: no
+// band holds more rows than that (kF2BandRowsMax for gpca_f2_blocks)
+constexpr int64_t kF2BandRowsMax = (int64_t)1 << 21;
+inline std::vector<std::pair<int64_t, int64_t>> group_count_bands(int64_t K, int64_t P, int64_t max_values = (int64_t)1 << 26, int64_t max_rows = 0) {
+    int64_t step = std::max<int64_t>(max_values / (3 * std::max<int64_t>(P, 1)), 1);
+    if (max_rows > 0) step = std::max<int64_t>(std::min(step, max_rows), 1);
     std::vector<std::pair<int64_t, int64_t>> out;
     for (int64_t r0 = 0; r0 < K; r0 += step) out.emplace_back(r0, std::min(r0 + step, K));
     return out;
@@ -1210,6 +1213,100 @@ private:
     bool wc_;
     std::vector<std::string> names_;
 };
+
+// ---- f-statistics: the twins of io.fstat_blocks, io.read_fstats_list, io.fstat_quad, io.write_f2_summary and io.write_fstats (same
+// rules, same error texts, byte-identical files) ----------------------------------------------------------------------------------------
+// block [K] and B: the jackknife block of every SNP of a list in genome order (gpca_fstat_blocks' rule; include/gpca.h section a23).  spec
+// has parse_ld_window's grammar: "500" = blocks of 500 variants, "5000kb" = a block ends before the first SNP 5 000 000 bp or more beyond
+// its first one; a new block starts at every change of chromosome.
+inline std::vector<int32_t> fstat_blocks(const std::vector<std::string>& chromosomes, const std::vector<int64_t>& positions, const std::string& spec,
+                                         int32_t& n_blocks) {
+    const LdWindow lw = parse_ld_window(spec);
+    const size_t K = chromosomes.size();
+    if (positions.size() != K) throw std::runtime_error("fstat_blocks: one position per chromosome entry");
+    std::vector<int32_t> block(K);
+    int64_t b = -1, held = 0, first = 0;
+    std::string prev;
+    for (size_t r = 0; r < K; ++r) {
+        const std::string c = normalize_chromosome_name(chromosomes[r]);
+        const bool start = r == 0 || c != prev || (lw.bp ? positions[r] - first >= lw.w : held >= lw.w);
+        if (start) { ++b; held = 0; first = positions[r]; }
+        block[r] = (int32_t)b;
+        ++held;
+        prev = c;
+    }
+    n_blocks = (int32_t)(b + 1);
+    return block;
+}
+struct FstatSpec { std::string kind; std::vector<int32_t> groups; };   // kind: f2, f3 or f4; groups: indices into the within file's names
+// The statistics of --gpca-fstats: one per line, `f2 A B`, `f3 C A B` (C is the target) or `f4 A B C D` with group names; '#' lines and
+// blank lines are skipped.
+inline std::vector<FstatSpec> read_fstats_list(const std::string& path, const std::vector<std::string>& names) {
+    std::ifstream in(path);
+    if (!in) throw std::runtime_error("cannot open " + path);
+    std::map<std::string, int32_t> index;
+    for (size_t p = 0; p < names.size(); ++p) index[names[p]] = (int32_t)p;
+    std::vector<FstatSpec> out;
+    std::string line;
+    for (int64_t ln = 1; std::getline(in, line); ++ln) {
+        const std::vector<std::string> p = split_ws(line);
+        if (p.empty() || p[0][0] == '#') continue;
+        const std::string at = path + ":" + std::to_string(ln) + ": ";
+        const size_t arity = p[0] == "f2" ? 2 : p[0] == "f3" ? 3 : p[0] == "f4" ? 4 : 0;
+        if (arity == 0) throw std::runtime_error(at + "'" + p[0] + "' is not f2, f3 or f4");
+        if (p.size() - 1 != arity) throw std::runtime_error(at + p[0] + " takes " + std::to_string(arity) + " groups, " + std::to_string(p.size() - 1) + " are given");
+        FstatSpec s;
+        s.kind = p[0];
+        for (size_t k = 1; k < p.size(); ++k) {
+            const auto it = index.find(p[k]);
+            if (it == index.end()) throw std::runtime_error(at + "no group '" + p[k] + "' in the within file");
+            s.groups.push_back(it->second);
+        }
+        out.push_back(s);
+    }
+    return out;
+}
+// gpca_fstat's quad (a, b, c, d), read as f4(a, b; c, d): f2(A, B) = (A, B, A, B), f3(C; A, B) = (C, A, C, B), f4 as it is
+inline void fstat_quad(const FstatSpec& s, int32_t (&q)[4]) {
+    const std::vector<int32_t>& g = s.groups;
+    if (s.kind == "f2" && g.size() == 2) { q[0] = g[0]; q[1] = g[1]; q[2] = g[0]; q[3] = g[1]; }
+    else if (s.kind == "f3" && g.size() == 3) { q[0] = g[0]; q[1] = g[1]; q[2] = g[0]; q[3] = g[2]; }
+    else if (s.kind == "f4" && g.size() == 4) { q[0] = g[0]; q[1] = g[1]; q[2] = g[2]; q[3] = g[3]; }
+    else throw std::runtime_error("fstat_quad: f2 takes 2 groups, f3 3 and f4 4");
+}
+inline void fmt_count_or_na(char (&b)[48], double v) { if (v != v) std::snprintf(b, sizeof b, "NA"); else std::snprintf(b, sizeof b, "%lld", (long long)v); }
+inline void write_fstat_tail(std::FILE* f, const double* s) {   // EST SE Z N_BLOCKS N_SNPS of one row of gpca_fstat
+    char b[5][48];
+    fmt_g6(b[0], s[0]); fmt_g6(b[1], s[2]); fmt_g6(b[2], s[3]); fmt_count_or_na(b[3], s[4]); fmt_count_or_na(b[4], s[5]);
+    std::fprintf(f, "\t%s\t%s\t%s\t%s\t%s\n", b[0], b[1], b[2], b[3], b[4]);
+}
+// P.f2.summary: `#POP1 POP2 F2 SE Z N_BLOCKS N_SNPS`, one line per pair (j < i at i (i - 1) / 2 + j, POP1 the earlier group) from stats
+// [pairs][6] = gpca_fstat's rows of the quads (j, i, j, i); %.6g, NaN as NA
+inline void write_f2_summary(const std::string& prefix, const std::vector<std::string>& names, const std::vector<double>& stats) {
+    const size_t P = names.size(), pairs = P * (P - 1) / 2;
+    if (stats.size() != pairs * 6) throw std::runtime_error("write_f2_summary: stats must be [pairs][6]");
+    OutFile o(prefix + ".f2.summary");
+    std::fputs("#POP1\tPOP2\tF2\tSE\tZ\tN_BLOCKS\tN_SNPS\n", o.f);
+    size_t q = 0;
+    for (size_t i = 1; i < P; ++i)
+        for (size_t j = 0; j < i; ++j, ++q) {
+            std::fprintf(o.f, "%s\t%s", names[j].c_str(), names[i].c_str());
+            write_fstat_tail(o.f, &stats[6 * q]);
+        }
+}
+// P.fstats: `#STAT POP1 POP2 POP3 POP4 EST SE Z N_BLOCKS N_SNPS`, one line per statistic of the list in its order, `.` for the columns a
+// statistic does not have; stats [M][6] = gpca_fstat's rows of fstat_quad of each
+inline void write_fstats(const std::string& prefix, const std::vector<std::string>& names, const std::vector<FstatSpec>& list,
+                         const std::vector<double>& stats) {
+    if (stats.size() != list.size() * 6) throw std::runtime_error("write_fstats: one row of stats per statistic");
+    OutFile o(prefix + ".fstats");
+    std::fputs("#STAT\tPOP1\tPOP2\tPOP3\tPOP4\tEST\tSE\tZ\tN_BLOCKS\tN_SNPS\n", o.f);
+    for (size_t m = 0; m < list.size(); ++m) {
+        std::fputs(list[m].kind.c_str(), o.f);
+        for (size_t k = 0; k < 4; ++k) std::fprintf(o.f, "\t%s", k < list[m].groups.size() ? names[(size_t)list[m].groups[k]].c_str() : ".");
+        write_fstat_tail(o.f, &stats[6 * m]);
+    }
+}
 
 // ---- genotype counts per sample, heterozygosity F and sample QC: the twins of io.sample_count_bands, io.write_smiss, io.write_het,
 // io.sample_qc_pass and io.write_sample_qc_ids (same rules, byte-identical files) --------------------------------------------------------

@@ -79,6 +79,13 @@ struct Args {
     bool have_fst = false, fst_variants = false;   // --gpca-fst hudson|wc: P.fst.summary; --gpca-fst-variants: P.fst.var
     std::string fst;
     gpca_host::WithinTable within_table;   // read in main, before any work on the device
+    bool f2 = false;                  // --gpca-f2: P.f2.summary
+    std::string fstats;               // --gpca-fstats FILE: P.fstats
+    bool have_fstat_block = false;
+    std::string fstat_block = "5000kb";   // --gpca-fstat-block SPEC: the jackknife blocks of --gpca-f2 and --gpca-fstats
+    std::vector<gpca_host::FstatSpec> fstats_list;   // read in main, before any work on the device
+    bool fstat_asked() const { return f2 || !fstats.empty(); }
+    bool strat_asked() const { return freq_strat || have_fst || fstat_asked(); }
     bool sample_missing = false, het = false;      // --gpca-sample-missing: P.smiss; --gpca-het: P.het
     bool have_mind = false, have_het_sd = false;   // --gpca-mind X, --gpca-het-sd K: the sample filters, P.sampleqc.in.id / .out.id
     double mind = 0.0, het_sd = 0.0;
@@ -241,6 +248,12 @@ void print_help() {
         "                                       (Bhatia et al. 2013) or wc (Weir and Cockerham 1984; with more than two groups also\n"
         "                                       jointly) -> <out>.fst.summary\n"
         "      --gpca-fst-variants              --gpca-fst: also the per-SNP terms -> <out>.fst.var\n"
+        "      --gpca-f2                        --gpca-within: the unbiased f2 of every pair of groups over the SNPs that pass the SNP QC,\n"
+        "                                       with its weighted block-jackknife standard error -> <out>.f2.summary\n"
+        "      --gpca-fstats <FILE>             --gpca-within: the statistics FILE lists, one per line: `f2 A B`, `f3 C A B` (C is the\n"
+        "                                       target) or `f4 A B C D` with group names -> <out>.fstats (estimate, jackknife SE, Z)\n"
+        "      --gpca-fstat-block <SPEC>        --gpca-f2 / --gpca-fstats: the jackknife blocks, a variant count such as 500 or a span\n"
+        "                                       such as 5000kb; a block ends at every change of chromosome [default: 5000kb]\n"
         "      --gpca-sample-missing            --eigensnp: the missing calls of every sample over the SNPs that pass the SNP QC ->\n"
         "                                       <out>.smiss (#FID IID MISSING_CT OBS_CT F_MISS)\n"
         "      --gpca-het                       --eigensnp: the observed and expected homozygous calls and the inbreeding coefficient F of\n"
@@ -373,6 +386,9 @@ Args parse(int argc, char** argv) {
         else if (f == "--gpca-freq-strat") a.freq_strat = true;
         else if (f == "--gpca-fst") { a.fst = val(); a.have_fst = true; }
         else if (f == "--gpca-fst-variants") a.fst_variants = true;
+        else if (f == "--gpca-f2") a.f2 = true;
+        else if (f == "--gpca-fstats") a.fstats = val();
+        else if (f == "--gpca-fstat-block") { a.fstat_block = val(); a.have_fstat_block = true; }
         else if (f == "--gpca-sample-missing") a.sample_missing = true;
         else if (f == "--gpca-het") a.het = true;
         else if (f == "--gpca-mind") { a.mind = to_f64(f, val()); a.have_mind = true; }
@@ -531,7 +547,8 @@ const char* const kStratNeedsResident =
 // --gpca-freq-strat / --gpca-fst: the genotype counts of every SNP that passes the SNP QC inside every group of --gpca-within
 // (gpca_group_counts), in row bands, into P.frq.strat, and Fst from them (gpca_fst_hudson / gpca_fst_wc) into P.fst.summary and
 // P.fst.var.  Resets the keep mask to the QC mask (mu, sigma unchanged), which ends the fit's validity; every kept sample with a group
-// counts, the KING in-set or not (cli.py:_strat).
+// counts, the KING in-set or not (cli.py:_strat).  --gpca-f2 / --gpca-fstats: the same bands through gpca_f2_blocks, whose counts serve the
+// files above, the blocks from fstat_blocks over the same SNPs; gpca_fstat turns the summed blocks into P.f2.summary and P.fstats.
 int run_strat(gpca::Engine& eng, const Args& a, const gpca_host::PlinkFileset& fs, const std::vector<std::string>& fids,
               const std::vector<std::string>& sample_ids, const gpca::SnpStats& st) {
     const std::vector<int32_t> labels = gpca_host::align_within(a.within_table, fids, sample_ids);
@@ -549,10 +566,28 @@ int run_strat(gpca::Engine& eng, const Args& a, const gpca_host::PlinkFileset& f
     std::unique_ptr<gpca_host::FstVarWriter> wv;
     if (a.freq_strat) wf.reset(new gpca_host::FrqStratWriter(a.output_prefix + ".frq.strat", names, gpca_hwe_chi_squared_p_value));
     if (a.have_fst && a.fst_variants) wv.reset(new gpca_host::FstVarWriter(a.output_prefix, wc, names));
+    const bool fstat = a.fstat_asked(), need_counts = a.freq_strat || a.have_fst;
+    std::vector<int32_t> block;
+    int32_t B = 0;
+    std::vector<int64_t> facc, fcnt;
+    if (fstat) {
+        std::vector<std::string> chrom;
+        std::vector<int64_t> pos;
+        for (int64_t o : rows) { chrom.push_back(fs.chromosomes[(size_t)o]); pos.push_back(fs.positions[(size_t)o]); }
+        block = gpca_host::fstat_blocks(chrom, pos, a.fstat_block, B);
+        facc.assign((size_t)std::max<int32_t>(B, 1) * pairs, 0); fcnt = facc;
+    }
     try {
-        for (const auto& b : gpca_host::group_count_bands((int64_t)rows.size(), P)) {
+        for (const auto& b : gpca_host::group_count_bands((int64_t)rows.size(), P, (int64_t)1 << 26, fstat ? gpca_host::kF2BandRowsMax : 0)) {
             std::vector<uint32_t> c;
-            eng.group_counts(labels, P, b.first, b.second, c);
+            if (fstat) {
+                std::vector<int64_t> bacc, bcnt;
+                eng.f2_blocks(labels, P, b.first, b.second, std::vector<int32_t>(block.begin() + b.first, block.begin() + b.second), B, bacc, bcnt,
+                              need_counts ? &c : nullptr);
+                for (size_t k = 0; k < facc.size(); ++k) { facc[k] += bacc[k]; fcnt[k] += bcnt[k]; }
+            } else {
+                eng.group_counts(labels, P, b.first, b.second, c);
+            }
             const size_t nr = (size_t)(b.second - b.first);
             if (wf)
                 for (size_t i = 0; i < nr; ++i) {
@@ -606,6 +641,25 @@ int run_strat(gpca::Engine& eng, const Args& a, const gpca_host::PlinkFileset& f
         std::snprintf(buf, sizeof buf, "%s Fst of %zu pairs of groups over %zu SNPs, written to %s.fst.summary", a.fst.c_str(), pairs, rows.size(),
                       a.output_prefix.c_str());
         logmsg(buf);
+    }
+    if (fstat && B >= 1) {
+        if (a.f2) {
+            std::vector<int32_t> quads;
+            for (int32_t i = 1; i < P; ++i)
+                for (int32_t j = 0; j < i; ++j) { const int32_t q[4] = {j, i, j, i}; quads.insert(quads.end(), q, q + 4); }
+            gpca_host::write_f2_summary(a.output_prefix, names, gpca::Engine::fstat(facc, fcnt, B, P, quads));
+            std::snprintf(buf, sizeof buf, "f2 of %zu pairs of groups over %zu SNPs in %d jackknife blocks (%s), written to %s.f2.summary", pairs, rows.size(),
+                          (int)B, a.fstat_block.c_str(), a.output_prefix.c_str());
+            logmsg(buf);
+        }
+        if (!a.fstats.empty()) {
+            std::vector<int32_t> quads;
+            for (const auto& s : a.fstats_list) { int32_t q[4]; gpca_host::fstat_quad(s, q); quads.insert(quads.end(), q, q + 4); }
+            gpca_host::write_fstats(a.output_prefix, names, a.fstats_list, gpca::Engine::fstat(facc, fcnt, B, P, quads));
+            std::snprintf(buf, sizeof buf, "%zu f-statistics over %zu SNPs in %d jackknife blocks (%s), written to %s.fstats", a.fstats_list.size(),
+                          rows.size(), (int)B, a.fstat_block.c_str(), a.output_prefix.c_str());
+            logmsg(buf);
+        }
     }
     return 0;
 }
@@ -1124,7 +1178,7 @@ int run_eigensnp_workflow(Args a) {
     const bool streamed = load_bed(eng, a, fs, use_kept ? &kept : nullptr);
     if (streamed && a.make_pcrelate) { std::fputs(kPcrelateNeedsResident, stderr); return 1; }
     if (streamed && !a.assoc_pheno.empty()) { std::fputs(kAssocNeedsResident, stderr); return 1; }
-    if (streamed && !a.within.empty() && (a.freq_strat || a.have_fst)) { std::fputs(kStratNeedsResident, stderr); return 1; }
+    if (streamed && !a.within.empty() && a.strat_asked()) { std::fputs(kStratNeedsResident, stderr); return 1; }
     if (streamed && a.sample_qc_asked()) { std::fputs(kSampleQcNeedsResident, stderr); return 1; }
     if (streamed && a.homozyg) { std::fputs(kHomozygNeedsResident, stderr); return 1; }
     if (streamed && !a.ld_score.empty()) { std::fputs(kLdScoreNeedsResident, stderr); return 1; }
@@ -1373,7 +1427,7 @@ int run_eigensnp_workflow(Args a) {
                       rows.size(), (int)P, a.output_prefix.c_str());
         logmsg(buf);
     }
-    if (!a.within.empty() && (a.freq_strat || a.have_fst)) {
+    if (!a.within.empty() && a.strat_asked()) {
         std::vector<std::string> fids = fs.family_ids;
         if (use_kept) { fids.clear(); for (int64_t c : kept.cols) fids.push_back(fs.family_ids[(size_t)c]); }
         const int rc = run_strat(eng, a, fs, fids, sample_ids, st);
@@ -1500,12 +1554,24 @@ int main(int argc, char** argv) {
         }
         if (a.assoc_cc_freq && !a.assoc_logistic) { std::fprintf(stderr, "error: --gpca-assoc-cc-freq needs --gpca-assoc-logistic\n"); return 2; }
         if (a.within.empty() && (a.freq_strat || a.have_fst)) { std::fprintf(stderr, "error: --gpca-freq-strat and --gpca-fst need --gpca-within\n"); return 2; }
+        if (a.within.empty() && (a.fstat_asked() || a.have_fstat_block)) {
+            std::fprintf(stderr, "error: --gpca-f2, --gpca-fstats and --gpca-fstat-block need --gpca-within\n");
+            return 2;
+        }
+        if (a.have_fstat_block && !a.fstat_asked()) { std::fprintf(stderr, "error: --gpca-fstat-block needs --gpca-f2 or --gpca-fstats\n"); return 2; }
+        if (a.fstat_asked()) {
+            try { gpca_host::parse_ld_window(a.fstat_block); }
+            catch (const std::runtime_error&) {
+                std::fprintf(stderr, "error: --gpca-fstat-block: '%s' is neither a variant count such as 500 nor a span such as 5000kb\n", a.fstat_block.c_str());
+                return 2;
+            }
+        }
         if (a.fst_variants && !a.have_fst) { std::fprintf(stderr, "error: --gpca-fst-variants needs --gpca-fst\n"); return 2; }
         if (a.have_fst && a.fst != "hudson" && a.fst != "wc") { std::fprintf(stderr, "error: --gpca-fst must be hudson or wc\n"); return 2; }
         if (!a.within.empty()) {
             if (!a.eigensnp) { std::fprintf(stderr, "error: --gpca-within needs the --eigensnp workflow\n"); return 2; }
-            if (!a.freq_strat && !a.have_fst && !a.admix_supervised) { std::fprintf(stderr, "error: --gpca-within needs --gpca-freq-strat or --gpca-fst\n"); return 2; }
-            if (a.stream == "on" && (a.freq_strat || a.have_fst)) { std::fputs(kStratNeedsResident, stderr); return 2; }
+            if (!a.strat_asked() && !a.admix_supervised) { std::fprintf(stderr, "error: --gpca-within needs --gpca-freq-strat or --gpca-fst\n"); return 2; }
+            if (a.stream == "on" && a.strat_asked()) { std::fputs(kStratNeedsResident, stderr); return 2; }
             try { a.within_table = gpca_host::read_within(a.within); }
             catch (const std::runtime_error& e) { std::fprintf(stderr, "error: --gpca-within: %s\n", e.what()); return 2; }
             const size_t ng = a.within_table.names.size();
@@ -1514,7 +1580,15 @@ int main(int argc, char** argv) {
                 return 2;
             }
             if (a.have_fst && ng < 2) { std::fprintf(stderr, "error: --gpca-fst needs at least two groups, --gpca-within names %zu\n", ng); return 2; }
+            if (a.fstat_asked() && ng < 2) {
+                std::fprintf(stderr, "error: --gpca-f2 and --gpca-fstats need at least two groups, --gpca-within names %zu\n", ng);
+                return 2;
+            }
             if (ng < 1) { std::fprintf(stderr, "error: --gpca-within names no group\n"); return 2; }
+            if (!a.fstats.empty()) {
+                try { a.fstats_list = gpca_host::read_fstats_list(a.fstats, a.within_table.names); }
+                catch (const std::runtime_error& e) { std::fprintf(stderr, "error: --gpca-fstats: %s\n", e.what()); return 2; }
+            }
         }
         if (a.sample_qc_asked()) {
             if (!a.eigensnp) { std::fprintf(stderr, "error: --gpca-sample-missing, --gpca-het, --gpca-mind and --gpca-het-sd need the --eigensnp workflow\n"); return 2; }

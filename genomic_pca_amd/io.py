@@ -1083,10 +1083,15 @@ def align_within(table: WithinTable, family_ids: Sequence[str], sample_ids: Sequ
     return out, list(table.names)
 
 
-def group_count_bands(K: int, P: int, max_values: int = 1 << 26):
+F2_BAND_ROWS_MAX = 1 << 21          # the rows gpca_f2_blocks takes in one call
+
+
+def group_count_bands(K: int, P: int, max_values: int = 1 << 26, max_rows: Optional[int] = None):
     """[row0, row1) bands of the K kept rows whose counts (rows x P x 3) hold at most max_values entries (at least one row): the bands
-    gpca_group_counts is asked for, one at a time."""
+    gpca_group_counts is asked for, one at a time.  max_rows: no band holds more rows than that (F2_BAND_ROWS_MAX for gpca_f2_blocks)."""
     step = max(max_values // (3 * max(P, 1)), 1)
+    if max_rows is not None:
+        step = max(min(step, int(max_rows)), 1)
     return [(r0, min(r0 + step, K)) for r0 in range(0, K, step)]
 
 
@@ -1186,6 +1191,108 @@ def write_fst_var(prefix: str, method: str, chromosomes: Sequence[str], position
                 v = vv[i, q]
                 den = v[1] if method == "hudson" else (v[0] + v[1]) + v[2]
                 f.write(head + f"{names[j]}\t{names[k]}\t" + "\t".join(_g6(x) for x in v) + f"\t{_ratio6(v[0], den)}\n")
+    return path
+
+
+# ---- f-statistics (gpca_f2_blocks, gpca_fstat_blocks, gpca_fstat; include/gpca.h section a23): twins in host/formats.hpp -------------------
+FSTAT_BLOCK_DEFAULT = "5000kb"
+
+
+def fstat_blocks(chromosomes: Sequence[str], positions: Sequence[int], spec: str = FSTAT_BLOCK_DEFAULT) -> Tuple[np.ndarray, int]:
+    """(block int32 [K], B): the jackknife block of every SNP of a list in genome order (gpca_fstat_blocks).  spec has parse_ld_window's
+    grammar: "500" = blocks of 500 variants, "5000kb" = a block ends before the first SNP 5 000 000 bp or more beyond its first one; a
+    new block starts at every change of chromosome."""
+    import ctypes
+    from . import _lib
+    kind, w = parse_ld_window(spec)
+    K = len(chromosomes)
+    pos = np.ascontiguousarray(positions, np.int64)
+    if pos.shape != (K,):
+        raise ValueError("fstat_blocks: one position per chromosome entry")
+    chrom = [normalize_chromosome_name(c) for c in chromosomes]
+    change = np.zeros(max(K, 1), np.uint8)
+    for r in range(1, K):
+        change[r] = chrom[r] != chrom[r - 1]
+    block = np.zeros(max(K, 1), np.int32)
+    nb = ctypes.c_int32(0)
+    rc = _lib.load().gpca_fstat_blocks(change.ctypes.data_as(ctypes.c_void_p), pos.ctypes.data_as(ctypes.c_void_p) if K else None, K, int(w),
+                                       _lib.FSTAT_BLOCK_VARIANTS if kind == "variants" else _lib.FSTAT_BLOCK_BP,
+                                       block.ctypes.data_as(ctypes.c_void_p), ctypes.byref(nb))
+    if rc != _lib.GPCA_OK:
+        raise ValueError(f"fstat_blocks: gpca_fstat_blocks refused the block size '{spec}'")
+    return block[:K], int(nb.value)
+
+
+def read_fstats_list(path: str, names: Sequence[str]) -> List[Tuple[str, Tuple[int, ...]]]:
+    """The statistics of --gpca-fstats: one per line, `f2 A B`, `f3 C A B` (C is the target) or `f4 A B C D` with group names; '#' lines
+    and blank lines are skipped.  Returns [(kind, the groups' indices in names)].  An unknown name, another keyword or a wrong number
+    of names is an error that names the line."""
+    arity = {"f2": 2, "f3": 3, "f4": 4}
+    index = {g: p for p, g in enumerate(names)}
+    out = []
+    with open(path) as f:
+        for ln, line in enumerate(f, 1):
+            p = line.split()
+            if not p or p[0].startswith("#"):
+                continue
+            if p[0] not in arity:
+                raise ValueError(f"{path}:{ln}: '{p[0]}' is not f2, f3 or f4")
+            if len(p) - 1 != arity[p[0]]:
+                raise ValueError(f"{path}:{ln}: {p[0]} takes {arity[p[0]]} groups, {len(p) - 1} are given")
+            for g in p[1:]:
+                if g not in index:
+                    raise ValueError(f"{path}:{ln}: no group '{g}' in the within file")
+            out.append((p[0], tuple(index[g] for g in p[1:])))
+    return out
+
+
+def fstat_quad(kind: str, groups: Sequence[int]) -> Tuple[int, int, int, int]:
+    """gpca_fstat's quad (a, b, c, d), read as f4(a, b; c, d): f2(A, B) = (A, B, A, B), f3(C; A, B) = (C, A, C, B), f4 as it is"""
+    g = [int(x) for x in groups]
+    if kind == "f2" and len(g) == 2:
+        return g[0], g[1], g[0], g[1]
+    if kind == "f3" and len(g) == 3:
+        return g[0], g[1], g[0], g[2]
+    if kind == "f4" and len(g) == 4:
+        return g[0], g[1], g[2], g[3]
+    raise ValueError("fstat_quad: f2 takes 2 groups, f3 3 and f4 4")
+
+
+def write_f2_summary(prefix: str, names: Sequence[str], stats) -> str:
+    """P.f2.summary: `#POP1 POP2 F2 SE Z N_BLOCKS N_SNPS`, tab-separated, one line per pair of groups with POP1 the earlier one, in the
+    order of fst_pairs; stats [pairs][6] = gpca_fstat's rows of the quads (j, i, j, i).  F2 = theta, SE and Z as %.6g, NaN as NA; the
+    blocks used and the SNPs of the pair as integers."""
+    pairs = fst_pairs(len(names))
+    sv = np.asarray(stats, np.float64)
+    if sv.shape != (len(pairs), 6):
+        raise ValueError("write_f2_summary: stats must be [pairs][6]")
+    path = f"{prefix}.f2.summary"
+    with _open_out(path, False) as f:
+        f.write("#POP1\tPOP2\tF2\tSE\tZ\tN_BLOCKS\tN_SNPS\n")
+        for q, (j, i) in enumerate(pairs):
+            s = sv[q]
+            f.write(f"{names[j]}\t{names[i]}\t{_g6(s[0])}\t{_g6(s[2])}\t{_g6(s[3])}\t{_count_or_na(s[4])}\t{_count_or_na(s[5])}\n")
+    return path
+
+
+def _count_or_na(x: float) -> str:
+    x = float(x)
+    return "NA" if x != x else str(int(x))
+
+
+def write_fstats(prefix: str, names: Sequence[str], stats_list, stats) -> str:
+    """P.fstats: `#STAT POP1 POP2 POP3 POP4 EST SE Z N_BLOCKS N_SNPS`, tab-separated, one line per statistic of stats_list
+    (read_fstats_list) in its order, the groups as the list gave them and `.` for the columns a statistic does not have; stats [M][6] =
+    gpca_fstat's rows of fstat_quad of each.  EST = theta; numbers as in write_f2_summary."""
+    sv = np.asarray(stats, np.float64).reshape(-1, 6)
+    if sv.shape[0] != len(stats_list):
+        raise ValueError("write_fstats: one row of stats per statistic")
+    path = f"{prefix}.fstats"
+    with _open_out(path, False) as f:
+        f.write("#STAT\tPOP1\tPOP2\tPOP3\tPOP4\tEST\tSE\tZ\tN_BLOCKS\tN_SNPS\n")
+        for (kind, groups), s in zip(stats_list, sv):
+            cols = [names[g] for g in groups] + ["."] * (4 - len(groups))
+            f.write(kind + "\t" + "\t".join(cols) + f"\t{_g6(s[0])}\t{_g6(s[2])}\t{_g6(s[3])}\t{_count_or_na(s[4])}\t{_count_or_na(s[5])}\n")
     return path
 
 

@@ -970,6 +970,69 @@ GPCA_API int gpca_admix_cv(gpca_handle* h, const gpca_admix_params* params, cons
                            uint64_t cv_seed, const float* Q0 /* [N][K], init = 1 */, const float* F0 /* [Kr][K], init = 1 */,
                            gpca_admix_cv_fold_info* out /* [folds] */, double* cv_error);
 
+/* ---- a23: f-statistics (Patterson et al. 2012; ADMIXTOOLS 2's "f2 blocks"): for every jackknife block of SNPs and every pair of a17's
+ * groups, the summed unbiased f2 and the number of SNPs behind it, on the device; f2, f3 and f4 with their weighted block-jackknife
+ * standard errors and Z scores are linear in those sums and are formed on the host.
+ * gpca_f2_blocks: group, P (2 .. GPCA_GROUPS_MAX here) and the kept rows [row0, row1) as in gpca_group_counts.  block [row1 - row0]:
+ *     block[r] = the jackknife block of kept row row0 + r, 0 <= block < B, or -1: the row enters nothing.  Any order of block ids is
+ *     legal and gives the same result; runs of equal ids are the fast case.  Pair (i, j), j < i, sits at i (i - 1) / 2 + j of
+ *     pairs = P (P - 1) / 2, as in gpca_fst_hudson.  For each row with block >= 0 and each pair whose two groups both have n_obs >= 1,
+ *     in f64 with no fused multiply-add, in exactly this order (a17's `num`):
+ *         n_i = 2 n_obs_i
+ *         p_i = (n_het_i + 2 n_hom2_i) / n_i
+ *         d   = p_i - p_j
+ *         v   = (d d - (p_i (1 - p_i)) / (n_i - 1)) - (p_j (1 - p_j)) / (n_j - 1)
+ *         q   = (int64) rint(v 2^40), half to even
+ *     acc[block][pair] += q and cnt[block][pair] += 1.  |v| <= 1.5 and the call refuses bands above 2^21 rows, so a call's sums stay
+ *     below 2^63.  acc and cnt [B][pairs] are WRITTEN: an untouched entry is 0; the caller adds its bands.  Every sum is an integer, so
+ *     any band split, int8 and 2-bit residency, a GPCA_PREC_F32_MFMA handle and any order of the atomics give the same bits.  counts
+ *     [rows][P][3], when given, carries the bits of gpca_group_counts for the band: one genotype pass serves a17's files and this.
+ *     The sample mask is ignored and no fitted result is touched.
+ *  Device: gpca_group_counts' pass as it is, then k_f2_blocks reads the counts workspace once (12 bytes per (row, group)): a workgroup
+ *     takes 256 rows in LDS tiles of 32; per tile it forms p_i and (p_i (1 - p_i)) / (n_i - 1) once per (row, group) and a 64-bit
+ *     validity mask per row; a thread owns the pairs t, t + 256, ... (at most 8) and keeps their i64 sums and i32 counts in registers
+ *     while the block id stays the same; at a block change and at the end of its rows it adds the non-zero counts with one 64-bit and
+ *     one 32-bit integer atomic.
+ *  Errors: everything on gpca_group_counts' list, and GPCA_ERR_BAD_ARG for a NULL block, acc or cnt, B < 1, a block id outside
+ *     -1 .. B - 1 (the message names the row), P < 2, a band above 2^21 rows.  rows = 0 writes zeros and returns GPCA_OK.  GPCA_ERR_OOM
+ *     is checked before any allocation and covers block, acc and cnt (B pairs 12 bytes) beside gpca_group_counts' buffers.
+ * The two host rules take no handle and work in f64 with no fused multiply-add.
+ *  gpca_fstat_blocks: the block of every row of a list of SNPs in genome order.  chrom_change[r] != 0: row r lies on another chromosome
+ *     than row r - 1.  A new block starts at row 0, at every chromosome change, and: unit = GPCA_FSTAT_BLOCK_VARIANTS: when the current
+ *     block holds `size` rows; unit = GPCA_FSTAT_BLOCK_BP: when pos[r] - (pos of the block's first row) >= size.  block[r] = the number
+ *     of blocks started before row r's; *n_blocks = B.  GPCA_ERR_BAD_ARG: rows < 0, size < 1, another unit, NULL n_blocks, and with
+ *     rows > 0 a NULL chrom_change or block, or a NULL pos with the bp unit.
+ *  gpca_fstat: acc and cnt [B][pairs] = the bands of gpca_f2_blocks added up; quads [M][4] = (a, b, c, d) per statistic, read as
+ *         f4(a, b; c, d) = 1/2 [f2(a, d) + f2(b, c) - f2(a, c) - f2(b, d)],  f2(x, x) = 0,
+ *     so that f2(A, B) = (A, B, A, B) and f3(C; A, B) = (C, A, C, B).  Per quad:
+ *     1. the four terms, each with coefficient +-1/2, are combined into coefficients c_q over distinct unordered pairs; the zero ones
+ *        are dropped; the rest are taken in ascending pair index in every sum below.
+ *     2. a block is used iff every such pair has cnt >= 1 in it; G = the number of used blocks, taken in ascending order.
+ *     3. S_q = sum of acc, C_q = sum of cnt over the used blocks, as integers, converted to f64 once:
+ *            theta      = sum_q c_q ((S_q 2^-40) / C_q)
+ *            theta_(-b) = sum_q c_q (((S_q - acc_bq) 2^-40) / (C_q - cnt_bq))          (the integer differences converted once)
+ *     4. the weighted jackknife (Busing et al. 1999): m_b = sum_q cnt_bq, n = sum_b m_b (integers), h_b = n / m_b,
+ *            theta_J = G theta - sum_b ((n - m_b) / n) theta_(-b)
+ *            tau_b   = h_b theta - (h_b - 1) theta_(-b)
+ *            var     = (1 / G) sum_b ((tau_b - theta_J) (tau_b - theta_J)) / (h_b - 1)
+ *     5. out [M][6] = theta, theta_J, se = sqrt(var), z = theta / se, G, min_q C_q.  G < 2: the first four are NaN.  A quad without a
+ *        non-zero coefficient, e.g. (A, A, A, A): all six are NaN.
+ *     GPCA_ERR_BAD_ARG: NULL acc, cnt or out, NULL quads with M > 0, M < 0, B < 1, P outside 2 .. GPCA_GROUPS_MAX, a quad entry outside
+ *     0 .. P - 1.
+ *  Where a group has no call on some SNPs, the pairs of one statistic average over different sets of SNPs (a pair counts a SNP iff its
+ *     own two groups are observed): the f3 and f4 identities then hold in expectation only, not SNP by SNP.
+ *  Not there: D statistics, f4-ratio, qpAdm and qpGraph, normalised f3, blocks in cM (no genetic map: 5 000 kb stands in for 5 cM),
+ *     ADMIXTOOLS' own digits, more than GPCA_GROUPS_MAX groups, streamed and row-sharded handles. */
+#define GPCA_FSTAT_BLOCK_VARIANTS 0
+#define GPCA_FSTAT_BLOCK_BP 1
+GPCA_API int gpca_f2_blocks(gpca_handle* h, const int32_t* group /* [N] */, int32_t P, int64_t row0, int64_t row1,
+                            const int32_t* block /* [row1 - row0] */, int32_t B, int64_t* acc /* [B][pairs], units of 2^-40, WRITTEN */,
+                            int64_t* cnt /* [B][pairs], WRITTEN */, uint32_t* counts /* [rows][P][3] or NULL */);
+GPCA_API int gpca_fstat_blocks(const uint8_t* chrom_change /* [rows] */, const int64_t* pos /* [rows]; may be NULL for variants */,
+                               int64_t rows, int64_t size, int32_t unit, int32_t* block /* [rows] */, int32_t* n_blocks);
+GPCA_API int gpca_fstat(const int64_t* acc, const int64_t* cnt, int32_t B, int32_t P, const int32_t* quads /* [M][4] */, int64_t M,
+                        double* out /* [M][6] */);
+
 /* ---- f3: the stages of EigenSNPCoreAlgorithm::compute_pca (main.rs:311-327, 359-366) ------------------------------------------
  * The algorithm lives in the un-vendored efficient_pca crate (Cargo.toml:30, branch "main", no pinned revision): what follows is
  * the stage structure of its published description -- per-LD-block local bases learnt on a sample subset, condensed features of

@@ -375,6 +375,33 @@ public:
         check(gpca_group_counts(h_, group.data(), P, row0, row1, counts.data()));
         counts.resize(rows * p * 3);
     }
+    // f2 jackknife blocks (gpca_f2_blocks; gpca.h section a23): group and the kept rows [row0, row1) as in group_counts, block [rows] =
+    // the block 0 .. B - 1 of every row of the band or -1; acc and cnt [B][P (P - 1) / 2] are WRITTEN (the caller adds its bands);
+    // counts, when asked for, = group_counts' [rows][P][3] of the band from the same genotype pass
+    void f2_blocks(const std::vector<int32_t>& group, int32_t P, int64_t row0, int64_t row1, const std::vector<int32_t>& block, int32_t B,
+                   std::vector<int64_t>& acc, std::vector<int64_t>& cnt, std::vector<uint32_t>* counts = nullptr) const {
+        const size_t rows = row1 > row0 ? (size_t)(row1 - row0) : 0, p = P > 1 && P <= GPCA_GROUPS_MAX ? (size_t)P : 2;
+        const size_t nout = (size_t)std::max<int32_t>(B, 1) * (p * (p - 1) / 2);
+        if (block.size() != rows) throw Error(GPCA_ERR_BAD_ARG, "gpca_f2_blocks: one block id per row of the band");
+        acc.assign(nout, 0); cnt.assign(nout, 0);
+        if (counts) counts->assign(std::max<size_t>(rows * p * 3, 1), 0u);
+        const int32_t none = 0;
+        check(gpca_f2_blocks(h_, group.data(), P, row0, row1, rows ? block.data() : &none, B, acc.data(), cnt.data(), counts ? counts->data() : nullptr));
+        if (counts) counts->resize(rows * p * 3);
+    }
+    // f2, f3 and f4 with their weighted block-jackknife standard errors (gpca_fstat; host only): acc and cnt [B][pairs] = the bands of
+    // f2_blocks added up, quads [M][4] = (a, b, c, d) read as f4(a, b; c, d); returns [M][6] = theta, theta_J, se, z, blocks used, min SNPs
+    static std::vector<double> fstat(const std::vector<int64_t>& acc, const std::vector<int64_t>& cnt, int32_t B, int32_t P,
+                                     const std::vector<int32_t>& quads) {
+        const size_t M = quads.size() / 4, pairs = P > 1 ? (size_t)P * (size_t)(P - 1) / 2 : 0;
+        std::vector<double> out(std::max<size_t>(6 * M, 1), 0.0);
+        int rc = quads.size() != 4 * M || B < 1 || acc.size() != (size_t)B * pairs || cnt.size() != acc.size() ? GPCA_ERR_BAD_ARG : GPCA_OK;
+        const int32_t none[4] = {0, 0, 0, 0};
+        if (rc == GPCA_OK) rc = gpca_fstat(acc.data(), cnt.data(), B, P, M ? quads.data() : none, (int64_t)M, out.data());
+        if (rc != GPCA_OK) throw Error(rc, std::string("gpca_fstat: ") + gpca_status_string(rc));
+        out.resize(6 * M);
+        return out;
+    }
     // Hudson's Fst of every pair of groups (gpca_fst_hudson; host only): sums [P (P - 1) / 2][3] is ADDED TO (zero it before the first
     // band); num / den [rows][pairs] when asked for
     static void fst_hudson(const std::vector<uint32_t>& counts, int32_t P, std::vector<double>& sums, std::vector<double>* num = nullptr,
