@@ -1,6 +1,7 @@
 """Tile-edge shapes shared by the gpca_grm, gpca_king and gpca_project modules: sample counts at and around the output tiles (64, 128),
 kSamplePad (256) and kSamplePad2bit (1 024), down to one sample; row counts at and around the 32-row block and the flush group of
-4 096 rows, down to one row."""
+4 096 rows, down to one row.  Each list walks one axis; tests/_combos.py crosses the axes (sample count x kept rows x keep pattern x
+band x storage x missing calls), pairwise, for the band kernels."""
 import numpy as np
 
 EDGE_N = [1, 2, 63, 64, 65, 127, 128, 129, 255, 256, 257, 1023, 1024, 1025]

@@ -65,12 +65,18 @@ def load(e, G, keep=None):
 
 
 def check(e, G, q, keep=None, rows=None, what=None):
-    """both forms of the call against the model; q: the weights of the kept rows"""
+    """both forms of the call against the model; q: the weights of the kept rows (of the band `rows` of them, where one is given), or
+    None for the form without weights alone"""
+    if rows is not None:                                      # the model of a band: the keep mask of its kept rows only
+        kr = np.flatnonzero(np.ones(G.shape[0], np.uint8) if keep is None else keep)[rows[0]:rows[1]]
+        keep = np.zeros(G.shape[0], np.uint8); keep[kr] = 1
     wc, wq = model(G, q, keep)
-    r = e.sample_counts(q)
-    assert r["counts"].dtype == np.uint32 and r["qsum"].dtype == np.uint64 and r["counts"].shape == (G.shape[1], 3)
-    assert np.array_equal(r["counts"], wc) and np.array_equal(r["qsum"], wq), what
-    r = e.sample_counts()
+    if q is not None:
+        r = e.sample_counts(q, rows=rows)
+        assert r["counts"].dtype == np.uint32 and r["qsum"].dtype == np.uint64 and r["counts"].shape == (G.shape[1], 3)
+        assert np.array_equal(r["counts"], wc) and np.array_equal(r["qsum"], wq), what
+    r = e.sample_counts(rows=rows)
+    assert r["counts"].dtype == np.uint32 and r["counts"].shape == (G.shape[1], 3)
     assert r["qsum"] is None and np.array_equal(r["counts"], wc), what
 
 
