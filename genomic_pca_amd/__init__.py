@@ -17,5 +17,7 @@ sample_het = GpcaEngine.sample_het
 roh_select = GpcaEngine.roh_select
 roh_threshold = GpcaEngine.roh_threshold
 admix_cv_fold = GpcaEngine.admix_cv_fold
+qtl_stats = GpcaEngine.qtl_stats
+qtl_t_min = GpcaEngine.qtl_t_min
 
 __version__ = "0.2.2"

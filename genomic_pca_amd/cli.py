@@ -249,6 +249,20 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--gpca-assoc-vif", type=float, default=None, metavar="X",
                    help="--gpca-assoc-pheno: a SNP whose variance inflation against the covariates exceeds X gets NA (plink's --vif) "
                         "[default: 50]")
+    p.add_argument("--gpca-qtl-pheno", default=None, metavar="FILE",
+                   help="EigenSNP workflow: after everything else is written, test every SNP that passes the SNP QC against every column "
+                        "of FILE (`FID IID name...`, up to 2^20 traits: a molecular QTL or PheWAS screen) in one wide pass on the GPU, "
+                        "and keep the pairs beyond the threshold in <out>.qtl.hits and the best SNP of every trait in <out>.qtl.best")
+    p.add_argument("--gpca-qtl-pcs", type=int, default=None, metavar="P",
+                   help="--gpca-qtl-pheno: the first P columns of the scores this run writes are covariates (0 <= P <= "
+                        "--eigensnp-k-global) [default: every column]")
+    p.add_argument("--gpca-qtl-covar", default=None, metavar="FILE",
+                   help="--gpca-qtl-pheno: further covariates, a table in the format of the phenotype file (at most 63 with the PCs)")
+    p.add_argument("--gpca-qtl-log10p", type=float, default=None, metavar="X",
+                   help="--gpca-qtl-pheno: keep the pairs with -log10 p >= X [default: 5]")
+    p.add_argument("--gpca-qtl-t", type=float, default=None, metavar="X", help="--gpca-qtl-pheno: keep the pairs with |t| >= X instead")
+    p.add_argument("--gpca-qtl-vif", type=float, default=None, metavar="X",
+                   help="--gpca-qtl-pheno: a SNP whose variance inflation against the covariates exceeds X is not tested [default: 50]")
     return p
 
 
@@ -378,6 +392,8 @@ def run_eigensnp_workflow(a) -> int:
         raise SystemExit(PCRELATE_NEEDS_RESIDENT)
     if streamed and a.gpca_assoc_pheno is not None:
         raise SystemExit(ASSOC_NEEDS_RESIDENT)
+    if streamed and a.gpca_qtl_pheno is not None:
+        raise SystemExit(QTL_NEEDS_RESIDENT)
     if streamed and a.gpca_within is not None and _strat_asked(a):
         raise SystemExit(STRAT_NEEDS_RESIDENT)
     if streamed and _sample_qc_asked(a):
@@ -439,6 +455,8 @@ def run_eigensnp_workflow(a) -> int:
         raise SystemExit(f"error: --gpca-make-pcrelate {a.gpca_make_pcrelate} asks for more PCs than the {k} this run computes")
     if a.gpca_assoc_pcs is not None and a.gpca_assoc_pcs > k:
         raise SystemExit(f"error: --gpca-assoc-pcs {a.gpca_assoc_pcs} asks for more PCs than the {k} this run computes")
+    if a.gpca_qtl_pcs is not None and a.gpca_qtl_pcs > k:
+        raise SystemExit(f"error: --gpca-qtl-pcs {a.gpca_qtl_pcs} asks for more PCs than the {k} this run computes")
     if inset is not None and not inset.all():
         eng.set_sample_mask(inset.astype(np.uint8))                                # the fit sees the in-set only
     out, _ = EigenSNPCoreAlgorithm(cfg).compute_pca(acc, specs, local_stage=a.gpca_eigensnp_local_stage, project_all=inset is not None)
@@ -465,6 +483,8 @@ def run_eigensnp_workflow(a) -> int:
     l2 = _ld_score(eng, a, fs, st) if a.gpca_ld_score is not None else None
     if a.gpca_assoc_pheno is not None:
         _assoc(eng, a, fs, cols, sample_ids, np.asarray(scores, np.float64), inset, st, l2)
+    if a.gpca_qtl_pheno is not None:
+        _qtl(eng, a, fs, cols, sample_ids, np.asarray(scores, np.float64), inset, st)
     eng.close()
     _log(f"EigenSNP workflow done in {time.time() - t0:.2f}s")
     return 0
@@ -1013,6 +1033,108 @@ def _assoc(eng, a, fs, cols, sample_ids, scores, inset, st, l2=None):
         _log(f"LD-score regression of {len(out)} traits over {len(rows)} SNPs, written to {a.output_prefix}.ldsc.summary")
 
 
+QTL_NEEDS_RESIDENT = ("error: --gpca-qtl-pheno needs the genotype matrix resident on the device: the scan of a matrix walked out of "
+                      "core is not implemented")
+QTL_MAX_COVARIATES = 63
+QTL_MAX_TRAITS = 1 << 20
+QTL_CAP = 1 << 20
+
+
+def _qtl_tables(a):
+    """The trait and covariate tables of --gpca-qtl-pheno / --gpca-qtl-covar, read once before any work on the device; refuses more than
+    2^20 traits and more than 63 covariates (PCs + columns).  Returns (pheno, covar or None)."""
+    def table(flag, path):
+        try:
+            return gio.read_pheno(path)
+        except OSError:
+            raise SystemExit(f"error: {flag}: cannot open {path}") from None
+        except ValueError as e:
+            raise SystemExit(f"error: {flag}: {e}") from None
+    pheno = table("--gpca-qtl-pheno", a.gpca_qtl_pheno)
+    covar = None if a.gpca_qtl_covar is None else table("--gpca-qtl-covar", a.gpca_qtl_covar)
+    t, c = len(pheno.names), 0 if covar is None else len(covar.names)
+    p = a.eigensnp_k_global if a.gpca_qtl_pcs is None else a.gpca_qtl_pcs
+    if t > QTL_MAX_TRAITS:
+        raise SystemExit(f"error: --gpca-qtl-pheno: {t} traits are more than {QTL_MAX_TRAITS}")
+    if p + c > QTL_MAX_COVARIATES:
+        raise SystemExit(f"error: --gpca-qtl-pheno: {p} PCs + {c} covariates are more than {QTL_MAX_COVARIATES} covariates")
+    return pheno, covar
+
+
+def _qtl(eng, a, fs, cols, sample_ids, scores, inset, st):
+    """--gpca-qtl-pheno FILE: the many-trait QTL scan (gpca_assoc_qtl) of every SNP that passes the SNP QC against every column of FILE,
+    in row bands, into P.qtl.hits (the pairs at or beyond the threshold, in (SNP, trait) order) and P.qtl.best (the best SNP of every
+    trait).  Runs last, after the association scan: it resets the keep mask to the QC mask.  Covariates and the include rule are the
+    association scan's.  The threshold on -log10 p becomes one on |t| once (gpca_qtl_t_min) and that one on r2.  The statistics of a hit
+    come from gpca_qtl_stats; those of a trait's best SNP from gpca_assoc_linear on that SNP, which gives the same bits."""
+    from . import _lib
+    pheno, covar = a.gpca_qtl_tables
+    fids = fs.family_ids if cols is None else [fs.family_ids[i] for i in cols]
+    n = len(sample_ids)
+    P = scores.shape[1] if a.gpca_qtl_pcs is None else a.gpca_qtl_pcs
+    Y = np.ascontiguousarray(gio.align_pheno(pheno, fids, sample_ids), np.float64)
+    C = scores[:, :P]
+    if covar is not None:
+        C = np.hstack([C, gio.align_pheno(covar, fids, sample_ids)])
+    C = np.ascontiguousarray(C, np.float64)
+    T, Pc = Y.shape[1], C.shape[1]
+    include = np.isfinite(Y).all(1) & np.isfinite(C).all(1)
+    if inset is not None:
+        include &= np.asarray(inset, bool)
+    n_inc = int(include.sum())
+    df = n_inc - Pc - 2
+    if df < 1:
+        raise SystemExit(f"error: --gpca-qtl-pheno: {n_inc} samples have every trait and covariate, which leaves no degree of freedom "
+                         f"beside {Pc} covariates")
+    vif = 50.0 if a.gpca_qtl_vif is None else a.gpca_qtl_vif
+    lib = _lib.load()
+    tmin = a.gpca_qtl_t if a.gpca_qtl_t is not None else float(lib.gpca_qtl_t_min(5.0 if a.gpca_qtl_log10p is None else a.gpca_qtl_log10p, float(df)))
+    if not tmin < float("inf"):
+        raise SystemExit(f"error: --gpca-qtl-log10p: no finite t reaches the threshold at {df} degrees of freedom")
+    r2_min = tmin * tmin / (tmin * tmin + df)
+    eng.set_standardization(st["mu"], st["sigma"], st["keep"])                       # every SNP that passes the SNP QC
+    rows = np.flatnonzero(st["keep"])
+    names = list(pheno.names)
+    b2, bw = np.full(T, np.nan), np.full(T, -1, np.int64)
+    n_tests, n_hits = 0, 0
+    log10p = lambda t: float("nan") if t != t else lib.gpca_student_t_log10p(float(t), float(df))
+    try:
+        for bi, (r0, r1) in enumerate(gio.assoc_qtl_bands(len(rows), T, n, QTL_CAP)):
+            q = eng.assoc_qtl(Y, C, include=include, max_vif=vif, r2_min=r2_min, cap=QTL_CAP, rows=(r0, r1))
+            if q["n_found"] > QTL_CAP:                                               # a band with more hits than the buffer: once more
+                q = eng.assoc_qtl(Y, C, include=include, max_vif=vif, r2_min=r2_min, cap=q["n_found"], rows=(r0, r1))
+            with np.errstate(invalid="ignore"):
+                n_tests += int((~((q["n_obs"] == 0) | ~(q["xx"] > 0.0) | (q["sxx"] * vif < q["xx"]))).sum())
+            hr, ht = q["rows"].astype(np.int64), q["traits"].astype(np.int64)
+            stt = GpcaEngine.qtl_stats(q["xb"], q["sxx"][hr - r0], q["yy"][ht], df)
+            o = rows[hr]
+            gio.write_qtl_hits(a.output_prefix, [fs.chromosomes[i] for i in o], [int(fs.positions[i]) for i in o], [fs.variant_ids[i] for i in o],
+                               [fs.allele1[i] for i in o], [names[t] for t in ht], q["n_obs"][hr - r0], q["a1_freq"][hr - r0], stt[:, 0], stt[:, 1],
+                               stt[:, 2], [log10p(t) for t in stt[:, 2]], append=bi > 0)
+            n_hits += q["n_found"]
+            gio.qtl_best_merge(b2, bw, q["best_r2"], q["best_row"])
+        if len(rows) == 0:
+            gio.write_qtl_hits(a.output_prefix, [], [], [], [], [], [], [], [], [], [], [])
+        # the best SNP of every trait: gpca_assoc_linear on that SNP, the traits that share a SNP in groups of 64 - Pc
+        beta, se, tt = np.full(T, np.nan), np.full(T, np.nan), np.full(T, np.nan)
+        for r in np.unique(bw[bw >= 0]):
+            ts = np.flatnonzero(bw == r)
+            for g0 in range(0, len(ts), 64 - Pc):
+                g = ts[g0:g0 + 64 - Pc]
+                res = eng.assoc_linear(np.ascontiguousarray(Y[:, g]), C, include=include, max_vif=vif, rows=(int(r), int(r) + 1))
+                beta[g], se[g], tt[g] = res["beta"][0], res["se"][0], res["t"][0]
+    except _lib.GpcaError as e:
+        if e.status == _lib.GPCA_ERR_STATE:
+            raise SystemExit(QTL_NEEDS_RESIDENT) from None
+        raise
+    ob = [None if r < 0 else int(rows[r]) for r in bw]
+    pick = lambda col: [None if i is None else col[i] for i in ob]
+    gio.write_qtl_best(a.output_prefix, names, pick(fs.chromosomes), [0 if i is None else int(fs.positions[i]) for i in ob], pick(fs.variant_ids),
+                       pick(fs.allele1), beta, se, tt, [log10p(t) for t in tt], [n_tests if i is not None else 0 for i in ob])
+    _log(f"QTL scan of {len(rows)} SNPs against {T} traits with {Pc} covariates ({P} PCs) on {n_inc} of {n} samples: {n_hits} pairs with "
+         f"|t| >= {tmin:.6g}, written to {a.output_prefix}.qtl.hits and {a.output_prefix}.qtl.best")
+
+
 def _assoc_sets(eng, a, fs, rows, a1_freq, Yb, bnames, C, Pc, include, vif):
     """--gpca-assoc-set-list FILE: the gene-level burden and SKAT tests (gpca_assoc_logistic_set, gpca_set_test) of every case / control
     trait, on the QC mask and the include set of the per-SNP scans, into P.<trait>.assoc.set; one row per set in file order."""
@@ -1264,6 +1386,27 @@ def main(argv=None) -> int:
                 raise SystemExit(f"error: --gpca-assoc-set-list: cannot open {a.gpca_assoc_set_list}") from None
             except ValueError as e:
                 raise SystemExit(f"error: --gpca-assoc-set-list: {e}") from None
+    if a.gpca_qtl_pheno is None and any(v is not None for v in (a.gpca_qtl_pcs, a.gpca_qtl_covar, a.gpca_qtl_log10p, a.gpca_qtl_t, a.gpca_qtl_vif)):
+        raise SystemExit("error: --gpca-qtl-pcs, --gpca-qtl-covar, --gpca-qtl-log10p, --gpca-qtl-t and --gpca-qtl-vif need --gpca-qtl-pheno")
+    if a.gpca_qtl_pheno is not None:
+        if not a.eigensnp:
+            raise SystemExit("error: --gpca-qtl-pheno needs the --eigensnp workflow")
+        if a.gpca_qtl_pcs is not None and not 0 <= a.gpca_qtl_pcs <= a.eigensnp_k_global:
+            raise SystemExit("error: --gpca-qtl-pcs P must lie in [0, --eigensnp-k-global]")
+        if a.gpca_qtl_vif is not None and not (1.0 <= a.gpca_qtl_vif < float("inf")):
+            raise SystemExit("error: --gpca-qtl-vif must be finite and at least 1")
+        if a.gpca_qtl_log10p is not None and a.gpca_qtl_t is not None:
+            raise SystemExit("error: --gpca-qtl-log10p and --gpca-qtl-t set the same threshold: give one")
+        if a.gpca_qtl_log10p is not None and not (0.0 <= a.gpca_qtl_log10p < float("inf")):
+            raise SystemExit("error: --gpca-qtl-log10p must be finite and at least 0")
+        if a.gpca_qtl_t is not None and not (0.0 <= a.gpca_qtl_t < float("inf")):
+            raise SystemExit("error: --gpca-qtl-t must be finite and at least 0")
+        if a.gpca_eigensnp_local_stage:
+            raise SystemExit("error: --gpca-qtl-pheno cannot be combined with --gpca-eigensnp-local-stage (that stage defines no "
+                             "all-sample scores)")
+        if a.gpca_stream == "on":
+            raise SystemExit(QTL_NEEDS_RESIDENT)
+        a.gpca_qtl_tables = _qtl_tables(a)
     if a.gpca_indep_pairwise:
         if not a.eigensnp:
             raise SystemExit("error: --gpca-indep-pairwise needs the --eigensnp workflow")

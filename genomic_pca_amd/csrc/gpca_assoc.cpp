@@ -134,36 +134,41 @@ struct AscWs {
     ~AscWs() { dfree(Bt); dfree(incw); dfree(sums); dfree(xb); dfree(yy); dfree(stats); dfree(info); dfree(bad); }
 };
 
+}  // namespace
+
 // Host step: S = the included samples; Q = an orthonormal basis of the columns of C centred over S (each scaled to unit norm, then
 // Q = C L^-T with C^T C = L L^T); Y~ = Y centred over S minus Q Q^T Y (taken out twice, so that what rounding leaves of the first pass
-// goes too); Bt [lpad][npad] = (float)[Y~ | Q]^T, zero outside S; yy [T] = |Y~_t|^2; incw = the mask as bits.
-int asc_design(gpca_handle* h, const double* Y, int T, const double* C, int Pc, const uint8_t* include, std::vector<float>& Bt,
-               std::vector<unsigned>& incw, std::vector<double>& yy, int64_t& n_inc) {
-    static const std::string f("gpca_assoc_linear");
-    const int64_t N = h->N, npad = asc_npad(N);
-    const int L = T + Pc;
-    std::vector<int64_t> S;
+// goes too); yy [T] = |Y~_t|^2; incw = the mask as bits.  A trait column is treated on its own: its Y~ and yy do not depend on T.
+int asc_design_host(gpca_handle* h, const std::string& f, const double* Y, int64_t T, const double* C, int Pc, const uint8_t* include,
+                    AscDesign& d, std::vector<unsigned>& incw, std::vector<double>& yy) {
+    const int64_t N = h->N;
+    std::vector<int64_t>& S = d.S;
     asc_sample_set(include, N, S, &incw);
-    const int64_t ns = n_inc = (int64_t)S.size();
+    const int64_t ns = (int64_t)S.size();
     if (ns - Pc - 2 < 1)
         return fail(h, GPCA_ERR_BAD_ARG, f + ": " + std::to_string(ns) + " included samples leave df = n - Pc - 2 < 1");
     // (sample-major: the first entry that is not finite in the order of the caller's rows, ahead of the column-major standardisation)
     for (int64_t n : S) {
-        for (int t = 0; t < T; ++t)
+        for (int64_t t = 0; t < T; ++t)
             if (!std::isfinite(Y[n * T + t])) return fail(h, GPCA_ERR_BAD_ARG, f + ": Y[" + std::to_string(n) + "][" + std::to_string(t) + "] is not finite");
         for (int j = 0; j < Pc; ++j)
             if (!std::isfinite(C[n * Pc + j])) return fail(h, GPCA_ERR_BAD_ARG, f + ": C[" + std::to_string(n) + "][" + std::to_string(j) + "] is not finite");
     }
     // the covariates over S, column-major, centred and scaled to unit norm; A = Cc^T Cc = L L^T (unit diagonal: a pivot that falls to
     // 1e-10 means the columns are collinear to working precision); Q L^T = Cc, in place
-    std::vector<double> Cc((size_t)Pc * (size_t)ns), Yc((size_t)T * (size_t)ns), A;
+    std::vector<double>& Cc = d.Q;
+    std::vector<double>& Yc = d.Yc;
+    Cc.assign((size_t)Pc * (size_t)ns, 0.0); Yc.assign((size_t)T * (size_t)ns, 0.0);
+    std::vector<double> A;
     std::string msg;
     int rc = asc_standardise(C, Pc, S, Cc.data(), msg);
     if (rc == GPCA_OK) rc = asc_cholesky(Cc.data(), Pc, ns, nullptr, [](double d, double) { return d > 1e-10; }, A, msg);
     if (rc != GPCA_OK) return fail(h, rc, f + ": " + msg);
     asc_solve_lt(A, Pc, ns, Cc.data(), nullptr, Cc.data());
     yy.assign((size_t)T, 0.0);
-    for (int t = 0; t < T; ++t) {
+    // one trait: false when it is constant once the covariates are taken out.  It reads and writes its own column only, so the traits
+    // of a wide call may go to several threads without moving a bit.
+    auto one = [&](int64_t t) {
         double* y = &Yc[(size_t)t * (size_t)ns];
         double sum = 0.0;
         for (int64_t i = 0; i < ns; ++i) { y[i] = Y[S[(size_t)i] * T + t]; sum += y[i]; }
@@ -178,16 +183,56 @@ int asc_design(gpca_handle* h, const double* Y, int T, const double* C, int Pc, 
             }
         double ss = 0.0;
         for (int64_t i = 0; i < ns; ++i) ss += y[i] * y[i];
-        if (!(ss > 0.0) || !std::isfinite(ss))
-            return fail(h, GPCA_ERR_BAD_ARG, f + ": trait " + std::to_string(t) + " is constant over the included samples once the covariates are taken out (yy = 0)");
+        if (!(ss > 0.0) || !std::isfinite(ss)) return false;
         yy[(size_t)t] = ss;
+        return true;
+    };
+    // (gpca_assoc_linear's at most 64 traits stay on the caller's thread; GPCA_DESIGN_THREADS, default 8, for kAscDesignPerThread
+    // traits per thread and more)
+    constexpr int64_t kAscDesignPerThread = 128;
+    int want = 8;
+    if (const char* e = std::getenv("GPCA_DESIGN_THREADS")) want = std::atoi(e);
+    const int64_t nthr = std::max<int64_t>(1, std::min<int64_t>({(int64_t)want, 64, (int64_t)std::max(1u, std::thread::hardware_concurrency()), T / kAscDesignPerThread}));
+    std::atomic<int64_t> bad(T);                                                      // the first trait that fails
+    auto walk = [&](int64_t k) {
+        for (int64_t t = k; t < T && t < bad.load(std::memory_order_relaxed); t += nthr)
+            if (!one(t)) {
+                int64_t cur = bad.load();
+                while (t < cur && !bad.compare_exchange_weak(cur, t)) {}
+            }
+    };
+    if (nthr == 1) walk(0);
+    else {
+        std::vector<std::thread> th;
+        for (int64_t k = 0; k < nthr; ++k) th.emplace_back(walk, k);
+        for (std::thread& x : th) x.join();
     }
-    Bt.assign((size_t)asc_b_capacity(N, L), 0.0f);
-    for (int64_t i = 0; i < ns; ++i) {
-        const int64_t n = S[(size_t)i];
-        for (int t = 0; t < T; ++t) Bt[(size_t)t * (size_t)npad + (size_t)n] = (float)Yc[(size_t)t * (size_t)ns + (size_t)i];
-        for (int j = 0; j < Pc; ++j) Bt[(size_t)(T + j) * (size_t)npad + (size_t)n] = (float)Cc[(size_t)j * (size_t)ns + (size_t)i];
+    if (bad.load() < T)
+        return fail(h, GPCA_ERR_BAD_ARG, f + ": trait " + std::to_string(bad.load()) + " is constant over the included samples once the covariates are taken out (yy = 0)");
+    return GPCA_OK;
+}
+
+void asc_design_rows(const AscDesign& d, const std::vector<double>& cols, int64_t ncols, int64_t npad, float* Bt) {
+    const int64_t ns = (int64_t)d.S.size();
+    for (int64_t t = 0; t < ncols; ++t) {
+        const double* y = &cols[(size_t)t * (size_t)ns];
+        float* o = Bt + (size_t)t * (size_t)npad;
+        for (int64_t i = 0; i < ns; ++i) o[(size_t)d.S[(size_t)i]] = (float)y[i];
     }
+}
+
+namespace {
+// gpca_assoc_linear's panel: Bt [lpad][npad] = (float)[Y~ | Q]^T, zero outside S
+int asc_design(gpca_handle* h, const double* Y, int T, const double* C, int Pc, const uint8_t* include, std::vector<float>& Bt,
+               std::vector<unsigned>& incw, std::vector<double>& yy, int64_t& n_inc) {
+    static const std::string f("gpca_assoc_linear");
+    const int64_t N = h->N, npad = asc_npad(N);
+    AscDesign d;
+    CHK(asc_design_host(h, f, Y, T, C, Pc, include, d, incw, yy));
+    n_inc = (int64_t)d.S.size();
+    Bt.assign((size_t)asc_b_capacity(N, T + Pc), 0.0f);
+    asc_design_rows(d, d.Yc, T, npad, Bt.data());
+    asc_design_rows(d, d.Q, Pc, npad, Bt.data() + (size_t)T * (size_t)npad);
     return GPCA_OK;
 }
 }  // namespace

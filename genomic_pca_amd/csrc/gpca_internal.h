@@ -403,6 +403,14 @@ int asc_cholesky(const double* X, int P, int64_t ns, const double* w, bool (*acc
                  std::string& msg);
 // out [P][ns] = diag(w) X L^-T (w = NULL: X L^-T), column by column: out_j = (w x_j - sum_{k < j} L_jk out_k) / L_jj; out may be X
 void asc_solve_lt(const std::vector<double>& A, int P, int64_t ns, const double* X, const double* w, double* out);
+// the host step of the linear scans (gpca_assoc_linear, gpca_assoc_qtl; gpca.h section a12, step 1) for an entry point f: S, Q [Pc][|S|]
+// and Y~ [T][|S|] column-major over S (f64), yy [T], incw; refuses df < 1, an entry of Y or C that is not finite, a constant or collinear
+// column of C and a trait with yy = 0.  A trait's Y~ and yy are functions of its own column, C and S alone.
+struct AscDesign { std::vector<int64_t> S; std::vector<double> Q, Yc; };
+int asc_design_host(gpca_handle* h, const std::string& f, const double* Y, int64_t T, const double* C, int Pc, const uint8_t* include,
+                    AscDesign& d, std::vector<unsigned>& incw, std::vector<double>& yy);
+// Bt [ncols][npad] (zeroed by the caller): row t = (float) of column t of cols [ncols][|S|] at the samples of S
+void asc_design_rows(const AscDesign& d, const std::vector<double>& cols, int64_t ncols, int64_t npad, float* Bt);
 // reads the kernels' invalid-genotype word back (the stream is synchronised) and refuses the call if a row was flagged
 int asc_check_genotypes(gpca_handle* h, const std::string& f, const unsigned long long* d_bad, hipStream_t st);
 // copies every requested output (host != NULL) from the workspace and waits for the copies

@@ -365,6 +365,21 @@ int launch_assoc(hipStream_t st, const void* G, int packed, int64_t ldr, const i
 void launch_assoc_finish(hipStream_t st, const double* xb, const unsigned* sums, const double* yy, int T, int L, double df, double max_vif,
                          int64_t rows, double* stats, double* info);
 
+// ---- many-trait QTL scan: kept rows x a strip of trait columns per workgroup, thresholded in the epilogue (assoc_qtl.hip) -------------
+// One launch covers the kept rows [row0, row1) of the band that starts at band0 (row0 - band0 a multiple of kAscRows, at most
+// qtl_chunk_blocks(T) row blocks).  Bt [qtl_tpad(T)][asc_npad(N)] f32 and yy [qtl_tpad(T)]; sums, info: launch_assoc's and
+// launch_assoc_finish's of the band on the covariate basis; tw: a legal strip width (qtl_clamp_tw).  hit_count [band rows] u32 and
+// *counter (u64) are added to (integer atomics); a hit's record goes to hit_index [cap][2] (kept row, trait) / hit_value [cap][2] (xb, r2)
+// at the counter's value, dropped at or past cap; ws_r2 / ws_row [row blocks of the launch][T] = the workgroups' best (r2, kept row) per
+// trait, (-1, -1) without a live row
+int launch_assoc_qtl(hipStream_t st, const void* G, int packed, int64_t ldr, const int64_t* krows, int64_t N, const float* Bt,
+                     const unsigned* incw, const double* yy, int64_t T, int tw, int64_t band0, int64_t row0, int64_t row1, const unsigned* sums,
+                     const double* info, double max_vif, double r2_min, unsigned* hit_count, unsigned* hit_index, double* hit_value, int64_t cap,
+                     unsigned long long* counter, double* ws_r2, long long* ws_row);
+// folds ws [blocks][T] into the running best [T] (r2 = -1, row = -1: none yet): blocks ascending, replaced on a strictly larger r2
+void launch_assoc_qtl_best(hipStream_t st, const double* ws_r2, const long long* ws_row, int64_t blocks, int64_t T, double* best_r2,
+                           long long* best_row);
+
 // ---- logistic score scan: kept rows x T (Pc + 3) panel columns over the samples, the operand coded by the minor allele (assoc_score.hip)
 // sums [row1 - row0][3] u32 = n_obs, sum g o, sum g^2 o; *bad as in launch_assoc
 int launch_assoc_score_count(hipStream_t st, const void* G, int packed, int64_t ldr, const int64_t* krows, int64_t N, const unsigned* incw,

@@ -645,4 +645,56 @@ constexpr double adm_cv_call_bytes(int64_t N, int64_t rows, int K, int sets, boo
            8.0 * (double)adm_cv_sums_capacity() + 8.0 * (double)adm_cv_count_capacity();
 }
 
+// ---- many-trait QTL scan (assoc_qtl.hip, gpca_assoc_qtl.cpp; include/gpca.h section a24) ----------------------------------------------
+// The tile, the stages and the flush groups are k_assoc's.  A workgroup owns kAscRows kept rows x a strip of tw trait columns, which it
+// walks in tiles of kQtlTile = kAscMaxCols columns, the whole sample loop per tile.  The trait panel is B^T [qtl_tpad(T)][asc_npad(N)]: a
+// tile's panel is asc_b_capacity(N, kQtlTile) floats at qtl_tile_offset, so what a tile stages is what k_assoc stages of a 64-column call.
+// A band goes in chunks of qtl_chunk_blocks(T) row blocks, so that the per-workgroup bests [row blocks][T] stay within kQtlBestBytes.
+constexpr int kQtlTile = kAscMaxCols, kQtlMinTw = kQtlTile, kQtlMaxTw = 1024, kQtlMaxPc = 63, kQtlReduceThreads = 256;
+constexpr int64_t kQtlMaxTraits = (int64_t)1 << 20, kQtlBestBytes = (int64_t)256 << 20, kQtlTargetGroups = 512;
+constexpr int64_t qtl_tpad(int64_t T) { return (T + kQtlTile - 1) / kQtlTile * kQtlTile; }
+constexpr int64_t qtl_tiles(int64_t T) { return qtl_tpad(T) / kQtlTile; }
+constexpr int64_t qtl_tile_offset(int64_t tile, int64_t N) { return tile * kQtlTile * asc_npad(N); }
+// a legal strip width: a power of two between kQtlMinTw and kQtlMaxTw (what GPCA_QTL_TW is clamped to: the largest one not above it)
+constexpr int qtl_clamp_tw(int64_t tw) {
+    int w = kQtlMinTw;
+    while (w < kQtlMaxTw && 2 * (int64_t)w <= tw) w *= 2;
+    return w;
+}
+constexpr int64_t qtl_strips(int64_t T, int tw) { return (qtl_tpad(T) + tw - 1) / tw; }
+// the widest strip that still leaves kQtlTargetGroups workgroups (two per CU) to a launch of `blocks` row blocks; forced > 0: that width
+constexpr int qtl_strip_width(int64_t blocks, int64_t T, int64_t forced = 0) {
+    if (forced > 0) return qtl_clamp_tw(forced);
+    int w = kQtlMaxTw;
+    while (w > kQtlMinTw && blocks * qtl_strips(T, w) < kQtlTargetGroups) w /= 2;
+    return w;
+}
+// the row blocks of one launch: the bests of a launch are [blocks][T] x 16 B (r2 f64, row i64)
+constexpr int64_t qtl_chunk_blocks(int64_t T) { return kQtlBestBytes / (16 * T) > 1 ? kQtlBestBytes / (16 * T) : 1; }
+static_assert(qtl_chunk_blocks(kQtlMaxTraits) * 16 * kQtlMaxTraits <= kQtlBestBytes && qtl_strips(kQtlMaxTraits, kQtlMinTw) <= 65535, "bests and grid.y at the widest call");
+// elements of the call's buffers: the trait panel (f32), yy padded to whole tiles (f64, 1 past T), the covariate panel of the per-row
+// pass (Pc = 0: one column of zeros), its xb, the per-row sums and rowinfo (asc_sums_capacity, asc_info_capacity), hit_count [rows] u32,
+// the records (index [cap][2] u32, value [cap][2] f64), the bests of a launch and the running bests [T] (r2 f64, row i64)
+constexpr int64_t qtl_b_capacity(int64_t N, int64_t T) { return qtl_tpad(T) * asc_npad(N); }
+constexpr int64_t qtl_yy_capacity(int64_t T) { return qtl_tpad(T); }
+constexpr int qtl_cov_cols(int Pc) { return Pc > 0 ? Pc : 1; }
+constexpr int64_t qtl_q_capacity(int64_t N, int Pc) { return asc_b_capacity(N, qtl_cov_cols(Pc)); }
+constexpr int64_t qtl_xbq_capacity(int64_t rows, int Pc) { return asc_xb_capacity(rows, qtl_cov_cols(Pc)); }
+constexpr int64_t qtl_hitcount_capacity(int64_t rows) { return rows; }
+constexpr int64_t qtl_rec_capacity(int64_t cap) { return 2 * cap; }
+constexpr int64_t qtl_wsbest_blocks(int64_t rows, int64_t T) { return asc_row_blocks(rows) < qtl_chunk_blocks(T) ? asc_row_blocks(rows) : qtl_chunk_blocks(T); }
+constexpr int64_t qtl_wsbest_capacity(int64_t rows, int64_t T) { return qtl_wsbest_blocks(rows, T) * T; }
+constexpr int64_t qtl_wsbest_index(int64_t block, int64_t T, int64_t t) { return block * T + t; }
+// the workgroup's static LDS: k_assoc's two stage buffers and sums at 64 columns, then per row mbar and sxx (f64), live and the hit
+// count (u32), then the four waves' bests of a tile (r2 f64, row i64)
+constexpr int64_t asc_lds_bytes(int nb, int ns) { return 2 * kAscRows * kAscGPitch + 2 * nb * 32 * kAscBPitch * 4 + kAscRows * ns * 4; }
+constexpr int64_t qtl_lds_bytes() { return asc_lds_bytes(kQtlTile / 32, 3) + 2 * 8 * kAscRows + 2 * 4 * kAscRows + 4 * kQtlTile * 16; }
+// The device bytes a call allocates (gpca_assoc_qtl's GPCA_ERR_OOM sum, without the check's slack)
+constexpr double qtl_call_bytes(int64_t N, int64_t rows, int64_t T, int Pc, int64_t cap) {
+    return 4.0 * (double)qtl_b_capacity(N, T) + 8.0 * (double)qtl_yy_capacity(T) + 4.0 * (double)qtl_q_capacity(N, Pc) + 4.0 * (double)asc_inc_capacity(N) +
+           8.0 * (double)qtl_xbq_capacity(rows, Pc) + 4.0 * (double)asc_sums_capacity(rows) + 8.0 * (double)asc_info_capacity(rows) +
+           4.0 * (double)qtl_hitcount_capacity(rows) + (4.0 + 8.0) * (double)qtl_rec_capacity(cap) + 16.0 * (double)qtl_wsbest_capacity(rows, T) +
+           16.0 * (double)T + 8.0 /* the counter */ + 8.0 /* the invalid-genotype word */;
+}
+
 }  // namespace gpca

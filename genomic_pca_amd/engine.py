@@ -608,6 +608,69 @@ class GpcaEngine:
         """-log10 of the two-sided p-value of a Student t statistic (gpca_student_t_log10p; host only, no underflow)."""
         return float(_lib.load().gpca_student_t_log10p(float(t), float(df)))
 
+    def assoc_qtl(self, Y, covar=None, include=None, max_vif: float = 50.0, r2_min: Optional[float] = None, t_min: Optional[float] = None,
+                  cap: Optional[int] = None, rows: Optional[Tuple[int, int]] = None, best: bool = True):
+        """Many-trait QTL scan (gpca_assoc_qtl; gpca.h section a24): assoc_linear's regression of the kept rows [row0, row1) (default:
+        all) against every column of Y [N][T], T up to 2^20, of which the pairs with r2 >= r2_min come back, and the best row of every
+        trait.  Exactly one of r2_min (in [0, 1]) and t_min (a cutoff on |t|, turned once into r2_min = t^2 / (t^2 + df)) is given.
+        cap: the record buffer; None = sized by a first call, filled by a second.  Returns a dict: n_obs, a1_freq, xx, sxx [rows]; yy
+        [T]; df; r2_min; hit_count uint32 [rows]; n_found; rows (absolute kept rows, uint32), traits (uint32), xb, r2 [n_found] in
+        ascending (row, trait) order, or None each when n_found > cap; with best=True best_r2 [T] and best_row int64 [T] (NaN and -1
+        for a trait without a live row).  xb of a hit is assoc_linear's, bit for bit; qtl_stats turns it into beta, se, t."""
+        Yv, Cv, inc, T, Pc, r0, r1, n = self._assoc_args(Y, covar, include, rows)
+        if (r2_min is None) == (t_min is None):
+            raise ValueError("exactly one of r2_min and t_min must be given")
+        N = self.dims()[1]
+        df = float((N if inc is None else int(inc.sum())) - Pc - 2)
+        if t_min is not None:
+            t2 = float(t_min) * float(t_min)
+            r2_min = t2 / (t2 + df)
+        info = np.zeros((max(n, 1), 4), np.float64)
+        yy = np.zeros(max(T, 1), np.float64)
+        hit_count = np.zeros(max(n, 1), np.uint32)
+        b2 = np.zeros(max(T, 1), np.float64) if best else None
+        bw = np.zeros(max(T, 1), np.int64) if best else None
+        found = C.c_int64(0)
+        size = 0 if cap is None else int(cap)
+        while True:
+            hi = np.zeros((max(size, 1), 2), np.uint32)
+            hv = np.zeros((max(size, 1), 2), np.float64)
+            self._chk(self._lib.gpca_assoc_qtl(self._h, _vp(Yv), T, _vp(Cv) if Pc else None, Pc, _vp(inc), float(max_vif), float(r2_min), r0, r1,
+                                               _vp(info), _vp(yy), _vp(hit_count), _vp(hi) if size > 0 else None, _vp(hv) if size > 0 else None,
+                                               size, C.byref(found), _vp(b2), _vp(bw)))
+            nf = int(found.value)
+            if nf <= size or cap is not None:
+                break
+            size = nf
+        res = {"n_obs": info[:n, 0], "a1_freq": info[:n, 1], "xx": info[:n, 2], "sxx": info[:n, 3], "yy": yy[:T], "df": df,
+               "r2_min": float(r2_min), "hit_count": hit_count[:n], "n_found": nf}
+        ok = nf <= size
+        res["rows"] = hi[:nf, 0].copy() if ok else None
+        res["traits"] = hi[:nf, 1].copy() if ok else None
+        res["xb"] = hv[:nf, 0].copy() if ok else None
+        res["r2"] = hv[:nf, 1].copy() if ok else None
+        if best:
+            res["best_r2"], res["best_row"] = b2[:T], bw[:T]
+        return res
+
+    @staticmethod
+    def qtl_t_min(log10p: float, df: float) -> float:
+        """The |t| cutoff of a threshold on -log10 p at df degrees of freedom (gpca_qtl_t_min: bisection on student_t_log10p)."""
+        return float(_lib.load().gpca_qtl_t_min(float(log10p), float(df)))
+
+    @staticmethod
+    def qtl_stats(xb, sxx, yy, df: float) -> np.ndarray:
+        """The host rule on the hits of assoc_qtl (gpca_qtl_stats): [n][3] = beta, se, t of the pairs with products xb, row sums sxx and
+        trait sums yy (arrays of one length, or scalars), by assoc_linear's formulas; NaN where rss <= 0."""
+        lib = _lib.load()
+        xv, sv, yv = np.broadcast_arrays(np.asarray(xb, np.float64), np.asarray(sxx, np.float64), np.asarray(yy, np.float64))
+        out = np.zeros((xv.size, 3), np.float64)
+        tmp = (C.c_double * 3)()
+        for i, (a, b, c) in enumerate(zip(xv.ravel(), sv.ravel(), yv.ravel())):
+            lib.gpca_qtl_stats(float(a), float(b), float(c), float(df), tmp)
+            out[i] = tmp[0], tmp[1], tmp[2]
+        return out
+
     def assoc_logistic_score(self, Y, covar=None, include=None, max_vif: float = 50.0, rows: Optional[Tuple[int, int]] = None, ua: bool = False):
         """Logistic score scan (gpca_assoc_logistic_score): the score test of every case / control trait (column of Y [N][T], 0 / 1 on
         the included samples) for the kept rows [row0, row1) in PCA-SNP order (default: all), the null model logit P(y = 1) = (1, covar)

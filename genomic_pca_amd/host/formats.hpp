@@ -916,6 +916,71 @@ private:
     OutFile o_;
 };
 
+// ---- many-trait QTL scan: the twins of io.assoc_qtl_bands, io.qtl_best_merge, io.write_qtl_hits and io.write_qtl_best ---------------
+constexpr int64_t kQtlHitsPerPairs = 4096;                   // the record buffer holds one pair in this many of a band
+constexpr int64_t kQtlBandWorkMax = (int64_t)1 << 47;        // rows x N x T of one call
+// [row0, row1) bands of the K kept rows for gpca_assoc_qtl with a record buffer of cap hits: whole blocks of 128 rows (at least one)
+// such that cap holds one pair in kQtlHitsPerPairs of the band's rows x T pairs and rows x N x T stays within kQtlBandWorkMax
+inline std::vector<std::pair<int64_t, int64_t>> assoc_qtl_bands(int64_t K, int64_t T, int64_t N, int64_t cap) {
+    T = std::max<int64_t>(T, 1); N = std::max<int64_t>(N, 1); cap = std::max<int64_t>(cap, 1);
+    int64_t step = std::min(cap * kQtlHitsPerPairs / T, kQtlBandWorkMax / (N * T));
+    step = std::max<int64_t>(step / 128 * 128, 128);
+    std::vector<std::pair<int64_t, int64_t>> out;
+    for (int64_t r0 = 0; r0 < K; r0 += step) out.emplace_back(r0, std::min(r0 + step, K));
+    return out;
+}
+
+// the running best over bands in ascending row order: a band's (r2, row) replaces a trait's entry when the trait has none yet (row < 0)
+// or the band's r2 is strictly larger, so a tie stays with the lower row
+inline void qtl_best_merge(std::vector<double>& best_r2, std::vector<int64_t>& best_row, const std::vector<double>& band_r2,
+                           const std::vector<int64_t>& band_row) {
+    for (size_t t = 0; t < best_r2.size(); ++t)
+        if (band_row[t] >= 0 && (best_row[t] < 0 || band_r2[t] > best_r2[t])) { best_r2[t] = band_r2[t]; best_row[t] = band_row[t]; }
+}
+
+// P.qtl.hits: one tab-separated line per hit in the order given (the scan's: ascending (row, trait)), `#CHROM POS ID A1 TRAIT OBS_CT
+// A1_FREQ BETA SE T_STAT LOG10P`; numbers as %.6g, NaN as NA, OBS_CT as an integer; hits are added band by band
+class QtlHitsWriter {
+public:
+    explicit QtlHitsWriter(const std::string& prefix) : o_(prefix + ".qtl.hits") {
+        std::fputs("#CHROM\tPOS\tID\tA1\tTRAIT\tOBS_CT\tA1_FREQ\tBETA\tSE\tT_STAT\tLOG10P\n", o_.f);
+    }
+    void add_hit(const std::string& chrom, int64_t pos, const std::string& id, const std::string& a1, const std::string& trait, double n_obs,
+                 double a1_freq, double beta, double se, double t, double log10p) {
+        char b[5][48];
+        const double v[5] = {a1_freq, beta, se, t, log10p};
+        for (int i = 0; i < 5; ++i) { if (v[i] != v[i]) std::snprintf(b[i], sizeof b[i], "NA"); else std::snprintf(b[i], sizeof b[i], "%.6g", v[i]); }
+        std::fprintf(o_.f, "%s\t%lld\t%s\t%s\t%s\t%lld\t%s\t%s\t%s\t%s\t%s\n", chrom.c_str(), (long long)pos, id.c_str(), a1.c_str(), trait.c_str(),
+                     (long long)n_obs, b[0], b[1], b[2], b[3], b[4]);
+    }
+
+private:
+    OutFile o_;
+};
+
+// P.qtl.best: one tab-separated line per trait, `#TRAIT CHROM POS ID A1 BETA SE T_STAT LOG10P N_TESTS`: the SNP with the largest r2 for
+// the trait over all bands and the number of live SNPs it was chosen from; add_none: a trait without a live SNP (NA in the SNP's columns)
+class QtlBestWriter {
+public:
+    explicit QtlBestWriter(const std::string& prefix) : o_(prefix + ".qtl.best") {
+        std::fputs("#TRAIT\tCHROM\tPOS\tID\tA1\tBETA\tSE\tT_STAT\tLOG10P\tN_TESTS\n", o_.f);
+    }
+    void add_trait(const std::string& trait, const std::string& chrom, int64_t pos, const std::string& id, const std::string& a1, double beta,
+                   double se, double t, double log10p, int64_t n_tests) {
+        char b[4][48];
+        const double v[4] = {beta, se, t, log10p};
+        for (int i = 0; i < 4; ++i) { if (v[i] != v[i]) std::snprintf(b[i], sizeof b[i], "NA"); else std::snprintf(b[i], sizeof b[i], "%.6g", v[i]); }
+        std::fprintf(o_.f, "%s\t%s\t%lld\t%s\t%s\t%s\t%s\t%s\t%s\t%lld\n", trait.c_str(), chrom.c_str(), (long long)pos, id.c_str(), a1.c_str(), b[0], b[1],
+                     b[2], b[3], (long long)n_tests);
+    }
+    void add_none(const std::string& trait, int64_t n_tests) {
+        std::fprintf(o_.f, "%s\tNA\tNA\tNA\tNA\tNA\tNA\tNA\tNA\t%lld\n", trait.c_str(), (long long)n_tests);
+    }
+
+private:
+    OutFile o_;
+};
+
 // ---- logistic score scan: the twins of io.binary_trait, io.assoc_score_groups, io.assoc_score_bands and io.write_assoc_logistic ------
 // true when column c of the table is binary: its present (non-NaN) values are exactly {0, 1} (1 = case) or exactly {1, 2} (plink's
 // coding, 2 = case); *shift = what to take off a value to reach the 0 / 1 coding.  A column with one class only is not binary.

@@ -72,6 +72,13 @@ struct Args {
     bool have_assoc_set_max_maf = false, have_assoc_set_weights = false;
     double assoc_set_max_maf = 0.01;  // --gpca-assoc-set-max-maf X
     std::string assoc_set_weights = "beta";   // --gpca-assoc-set-weights beta|flat
+    std::string qtl_pheno, qtl_covar;       // --gpca-qtl-pheno FILE (turns the many-trait QTL scan on), --gpca-qtl-covar FILE
+    bool have_qtl_pcs = false, have_qtl_vif = false, have_qtl_log10p = false, have_qtl_t = false;
+    int64_t qtl_pcs = 0;              // --gpca-qtl-pcs P [default: every column of the scores]
+    double qtl_vif = 50.0;            // --gpca-qtl-vif X
+    double qtl_log10p = 5.0;          // --gpca-qtl-log10p X
+    double qtl_t = 0.0;               // --gpca-qtl-t X
+    gpca_host::PhenoTable qtl_pheno_table, qtl_covar_table;       // read in main, before any work on the device
     gpca_host::PhenoTable assoc_pheno_table, assoc_covar_table;   // read in main, before any work on the device
     bool assoc_cc_freq = false;       // --gpca-assoc-cc-freq: P.<trait>.frq.cc beside every logistic scan
     std::string within;               // --gpca-within FILE: the sample groups of --gpca-freq-strat and --gpca-fst
@@ -296,6 +303,15 @@ void print_help() {
         "      --gpca-assoc-pcs <P>             --gpca-assoc-pheno: the first P columns of the scores this run writes are covariates\n"
         "                                       (0 <= P <= --eigensnp-k-global) [default: every column]\n"
         "      --gpca-assoc-covar <FILE>        --gpca-assoc-pheno: further covariates, a table in the format of the phenotype file\n"
+        "      --gpca-qtl-pheno <FILE>          EigenSNP workflow: after everything else is written, test every SNP that passes the SNP QC\n"
+        "                                       against every column of FILE (`FID IID name...`, up to 2^20 traits) in one wide pass on\n"
+        "                                       the GPU; the pairs beyond the threshold go to <out>.qtl.hits, the best SNP of every trait\n"
+        "                                       to <out>.qtl.best\n"
+        "      --gpca-qtl-pcs <P>               --gpca-qtl-pheno: the first P columns of the scores this run writes are covariates\n"
+        "      --gpca-qtl-covar <FILE>          --gpca-qtl-pheno: further covariates (at most 63 with the PCs)\n"
+        "      --gpca-qtl-log10p <X>            --gpca-qtl-pheno: keep the pairs with -log10 p >= X [default: 5]\n"
+        "      --gpca-qtl-t <X>                 --gpca-qtl-pheno: keep the pairs with |t| >= X instead\n"
+        "      --gpca-qtl-vif <X>               --gpca-qtl-pheno: a SNP whose variance inflation exceeds X is not tested [default: 50]\n"
         "      --gpca-assoc-vif <X>             --gpca-assoc-pheno: a SNP whose variance inflation against the covariates exceeds X gets\n"
         "                                       NA (plink's --vif) [default: 50]\n"
         "  -h, --help                           Print help");
@@ -416,6 +432,12 @@ Args parse(int argc, char** argv) {
         else if (f == "--gpca-homozyg-density") { a.hom_density = to_f64(f, val()); a.homozyg = true; }
         else if (f == "--gpca-homozyg-gap") { a.hom_gap = to_f64(f, val()); a.homozyg = true; }
         else if (f == "--gpca-homozyg-het") { a.hom_het = to_i64(f, val()); a.have_hom_het = true; a.homozyg = true; }
+        else if (f == "--gpca-qtl-pheno") a.qtl_pheno = val();
+        else if (f == "--gpca-qtl-covar") a.qtl_covar = val();
+        else if (f == "--gpca-qtl-pcs") { a.qtl_pcs = to_i64(f, val()); a.have_qtl_pcs = true; }
+        else if (f == "--gpca-qtl-vif") { a.qtl_vif = to_f64(f, val()); a.have_qtl_vif = true; }
+        else if (f == "--gpca-qtl-log10p") { a.qtl_log10p = to_f64(f, val()); a.have_qtl_log10p = true; }
+        else if (f == "--gpca-qtl-t") { a.qtl_t = to_f64(f, val()); a.have_qtl_t = true; }
         else if (f == "--gpca-assoc-pcs") { a.assoc_pcs = to_i64(f, val()); a.have_assoc_pcs = true; }
         else if (f == "--gpca-assoc-vif") { a.assoc_vif = to_f64(f, val()); a.have_assoc_vif = true; }
         else if (f == "--gpca-ld-score") a.ld_score = val();
@@ -788,6 +810,117 @@ void run_assoc_sets(gpca::Engine& eng, const Args& a, const gpca_host::PlinkFile
     std::snprintf(buf, sizeof buf, "set tests of %zu of %zu sets against %d case / control traits, written to %s.<trait>.assoc.set", run.size(), sets.size(),
                   (int)Tb, a.output_prefix.c_str());
     logmsg(buf);
+}
+
+const char* kQtlNeedsResident =
+    "error: --gpca-qtl-pheno needs the genotype matrix resident on the device: the scan of a matrix walked out of core is not implemented\n";
+constexpr int64_t kQtlMaxCovariates = 63, kQtlMaxTraits = (int64_t)1 << 20, kQtlCap = (int64_t)1 << 20;
+
+// --gpca-qtl-pheno FILE: the many-trait QTL scan (gpca_assoc_qtl) of every SNP that passes the SNP QC against every column of FILE, in
+// row bands, into P.qtl.hits and P.qtl.best.  Runs last, after the association scan: it resets the keep mask to the QC mask.  Covariates
+// and the include rule are the association scan's; the statistics of a hit come from gpca_qtl_stats, those of a trait's best SNP from
+// gpca_assoc_linear on that SNP (cli.py:_qtl).  scores is [n][kc].
+int run_qtl(gpca::Engine& eng, const Args& a, const gpca_host::PlinkFileset& fs, const std::vector<std::string>& fids,
+            const std::vector<std::string>& sample_ids, const std::vector<double>& scores, int kc, const std::vector<uint8_t>& inset,
+            const gpca::SnpStats& st) {
+    const int64_t n = (int64_t)sample_ids.size();
+    const int32_t P = a.have_qtl_pcs ? (int32_t)a.qtl_pcs : (int32_t)kc;
+    const int64_t T = (int64_t)a.qtl_pheno_table.names.size();
+    const int32_t nc = a.qtl_covar.empty() ? 0 : (int32_t)a.qtl_covar_table.names.size();
+    const int32_t Pc = P + nc;
+    const std::vector<double> Y = gpca_host::align_pheno(a.qtl_pheno_table, fids, sample_ids);
+    std::vector<double> cv;
+    if (nc) cv = gpca_host::align_pheno(a.qtl_covar_table, fids, sample_ids);
+    std::vector<double> C((size_t)n * (size_t)Pc + 1);
+    std::vector<uint8_t> include((size_t)n, 1);
+    int64_t n_inc = 0;
+    for (int64_t s = 0; s < n; ++s) {
+        bool ok = inset.empty() || inset[(size_t)s];
+        for (int32_t c = 0; c < P; ++c) C[(size_t)s * Pc + c] = scores[(size_t)s * kc + c];
+        for (int32_t c = 0; c < nc; ++c) C[(size_t)s * Pc + P + c] = cv[(size_t)s * nc + c];
+        for (int32_t c = 0; c < Pc; ++c) ok = ok && std::isfinite(C[(size_t)s * Pc + c]);
+        for (int64_t t = 0; t < T; ++t) ok = ok && std::isfinite(Y[(size_t)s * (size_t)T + (size_t)t]);
+        include[(size_t)s] = ok ? 1 : 0;
+        n_inc += ok;
+    }
+    const int64_t df = n_inc - Pc - 2;
+    if (df < 1) {
+        std::fprintf(stderr, "error: --gpca-qtl-pheno: %lld samples have every trait and covariate, which leaves no degree of freedom beside %d covariates\n",
+                     (long long)n_inc, (int)Pc);
+        return 1;
+    }
+    const double tmin = a.have_qtl_t ? a.qtl_t : gpca_qtl_t_min(a.qtl_log10p, (double)df);
+    if (!(tmin < INFINITY)) {
+        std::fprintf(stderr, "error: --gpca-qtl-log10p: no finite t reaches the threshold at %lld degrees of freedom\n", (long long)df);
+        return 1;
+    }
+    const double r2_min = tmin * tmin / (tmin * tmin + (double)df);
+    eng.set_standardization(st.mu, st.sigma, st.keep);                                // every SNP that passes the SNP QC
+    std::vector<int64_t> rows;
+    for (size_t i = 0; i < st.keep.size(); ++i) if (st.keep[i]) rows.push_back((int64_t)i);
+    gpca_host::ensure_parent(a.output_prefix);
+    const std::vector<std::string>& names = a.qtl_pheno_table.names;
+    const double nan = std::nan("");
+    std::vector<double> b2((size_t)T, nan), beta((size_t)T, nan), se((size_t)T, nan), tt((size_t)T, nan);
+    std::vector<int64_t> bw((size_t)T, -1);
+    int64_t n_tests = 0, n_hits = 0;
+    auto log10p = [&](double t) { return t != t ? nan : gpca_student_t_log10p(t, (double)df); };
+    try {
+        {
+            gpca_host::QtlHitsWriter w(a.output_prefix);
+            for (const auto& b : gpca_host::assoc_qtl_bands((int64_t)rows.size(), T, n, kQtlCap)) {
+                gpca::Engine::QtlResult q = eng.assoc_qtl(Y, T, C, Pc, &include, a.qtl_vif, r2_min, kQtlCap, b.first, b.second);
+                if (q.n_found > kQtlCap) q = eng.assoc_qtl(Y, T, C, Pc, &include, a.qtl_vif, r2_min, q.n_found, b.first, b.second);   // once more
+                for (int64_t r = b.first; r < b.second; ++r) {
+                    const double* o = &q.rowinfo[4 * (size_t)(r - b.first)];
+                    n_tests += !(o[0] == 0.0 || !(o[2] > 0.0) || o[3] * a.qtl_vif < o[2]);
+                }
+                for (int64_t i = 0; i < q.n_found; ++i) {
+                    const size_t r = (size_t)q.rows[(size_t)i], t = (size_t)q.traits[(size_t)i], o = (size_t)rows[r];
+                    const double* info = &q.rowinfo[4 * (r - (size_t)b.first)];
+                    double s3[3];
+                    gpca_qtl_stats(q.xb[(size_t)i], info[3], q.yy[t], (double)df, s3);
+                    w.add_hit(fs.chromosomes[o], fs.positions[o], fs.variant_ids[o], fs.allele1[o], names[t], info[0], info[1], s3[0], s3[1], s3[2], log10p(s3[2]));
+                }
+                n_hits += q.n_found;
+                gpca_host::qtl_best_merge(b2, bw, q.best_r2, q.best_row);
+            }
+        }
+        // the best SNP of every trait: gpca_assoc_linear on that SNP, the traits that share a SNP in groups of 64 - Pc
+        std::map<int64_t, std::vector<int64_t>> by_row;
+        for (int64_t t = 0; t < T; ++t) if (bw[(size_t)t] >= 0) by_row[bw[(size_t)t]].push_back(t);
+        const int64_t gmax = 64 - Pc;
+        for (const auto& kv : by_row)
+            for (size_t g0 = 0; g0 < kv.second.size(); g0 += (size_t)gmax) {
+                const size_t gn = std::min<size_t>((size_t)gmax, kv.second.size() - g0);
+                std::vector<double> Yg((size_t)n * gn), stats, info;
+                for (int64_t s = 0; s < n; ++s)
+                    for (size_t j = 0; j < gn; ++j) Yg[(size_t)s * gn + j] = Y[(size_t)s * (size_t)T + (size_t)kv.second[g0 + j]];
+                eng.assoc_linear(Yg, (int32_t)gn, C, Pc, &include, a.qtl_vif, kv.first, kv.first + 1, stats, info);
+                for (size_t j = 0; j < gn; ++j) {
+                    const size_t t = (size_t)kv.second[g0 + j];
+                    beta[t] = stats[3 * j]; se[t] = stats[3 * j + 1]; tt[t] = stats[3 * j + 2];
+                }
+            }
+    } catch (const gpca::Error& e) {
+        if (e.status() == GPCA_ERR_STATE) { std::fputs(kQtlNeedsResident, stderr); return 1; }
+        throw;
+    }
+    {
+        gpca_host::QtlBestWriter w(a.output_prefix);
+        for (int64_t t = 0; t < T; ++t) {
+            if (bw[(size_t)t] < 0) { w.add_none(names[(size_t)t], 0); continue; }
+            const size_t o = (size_t)rows[(size_t)bw[(size_t)t]];
+            w.add_trait(names[(size_t)t], fs.chromosomes[o], fs.positions[o], fs.variant_ids[o], fs.allele1[o], beta[(size_t)t], se[(size_t)t], tt[(size_t)t],
+                        log10p(tt[(size_t)t]), n_tests);
+        }
+    }
+    char buf[768];
+    std::snprintf(buf, sizeof buf, "QTL scan of %zu SNPs against %lld traits with %d covariates (%d PCs) on %lld of %lld samples: %lld pairs with |t| >= %.6g, "
+                  "written to %s.qtl.hits and %s.qtl.best", rows.size(), (long long)T, (int)Pc, (int)P, (long long)n_inc, (long long)n, (long long)n_hits, tmin,
+                  a.output_prefix.c_str(), a.output_prefix.c_str());
+    logmsg(buf);
+    return 0;
 }
 
 // --gpca-assoc-pheno FILE: the linear association scan (gpca_assoc_linear) of every SNP that passes the SNP QC, in row bands, into
@@ -1178,6 +1311,7 @@ int run_eigensnp_workflow(Args a) {
     const bool streamed = load_bed(eng, a, fs, use_kept ? &kept : nullptr);
     if (streamed && a.make_pcrelate) { std::fputs(kPcrelateNeedsResident, stderr); return 1; }
     if (streamed && !a.assoc_pheno.empty()) { std::fputs(kAssocNeedsResident, stderr); return 1; }
+    if (streamed && !a.qtl_pheno.empty()) { std::fputs(kQtlNeedsResident, stderr); return 1; }
     if (streamed && !a.within.empty() && a.strat_asked()) { std::fputs(kStratNeedsResident, stderr); return 1; }
     if (streamed && a.sample_qc_asked()) { std::fputs(kSampleQcNeedsResident, stderr); return 1; }
     if (streamed && a.homozyg) { std::fputs(kHomozygNeedsResident, stderr); return 1; }
@@ -1362,6 +1496,10 @@ int run_eigensnp_workflow(Args a) {
         std::fprintf(stderr, "error: --gpca-assoc-pcs %lld asks for more PCs than the %lld this run computes\n", (long long)a.assoc_pcs, (long long)k);
         return 1;
     }
+    if (a.have_qtl_pcs && a.qtl_pcs > k) {
+        std::fprintf(stderr, "error: --gpca-qtl-pcs %lld asks for more PCs than the %lld this run computes\n", (long long)a.qtl_pcs, (long long)k);
+        return 1;
+    }
     if (!inset.empty() && n_fit < (int64_t)inset.size()) eng.set_sample_mask(&inset);      // the fit sees the in-set only
     // with the cutoff every sample is projected onto the in-set's PCs (the relatives included), inside compute_pca while the fit is valid
     const gpca::EigenSNPCoreOutput out = gpca::EigenSNPCoreAlgorithm(cfg).compute_pca(acc, specs, a.local_stage, !inset.empty());
@@ -1444,6 +1582,14 @@ int run_eigensnp_workflow(Args a) {
         std::vector<double> scores = projected;
         if (inset.empty()) scores.assign(out.final_sample_principal_component_scores.begin(), out.final_sample_principal_component_scores.end());
         const int rc = run_assoc(eng, a, fs, fids, sample_ids, scores, kc, inset, st, l2);
+        if (rc) return rc;
+    }
+    if (!a.qtl_pheno.empty()) {
+        std::vector<std::string> fids = fs.family_ids;
+        if (use_kept) { fids.clear(); for (int64_t c : kept.cols) fids.push_back(fs.family_ids[(size_t)c]); }
+        std::vector<double> scores = projected;
+        if (inset.empty()) scores.assign(out.final_sample_principal_component_scores.begin(), out.final_sample_principal_component_scores.end());
+        const int rc = run_qtl(eng, a, fs, fids, sample_ids, scores, kc, inset, st);
         if (rc) return rc;
     }
     std::snprintf(buf, sizeof buf, "EigenSNP workflow done in %.2fs", seconds_since(t0));
@@ -1704,6 +1850,39 @@ int main(int argc, char** argv) {
             if (!a.assoc_set_list.empty()) {                                          // (its format, before any work on the device)
                 try { gpca_host::read_set_list(a.assoc_set_list, {}); }
                 catch (const std::runtime_error& e) { std::fprintf(stderr, "error: --gpca-assoc-set-list: %s\n", e.what()); return 2; }
+            }
+        }
+        if (a.qtl_pheno.empty() && (a.have_qtl_pcs || !a.qtl_covar.empty() || a.have_qtl_log10p || a.have_qtl_t || a.have_qtl_vif)) {
+            std::fprintf(stderr, "error: --gpca-qtl-pcs, --gpca-qtl-covar, --gpca-qtl-log10p, --gpca-qtl-t and --gpca-qtl-vif need --gpca-qtl-pheno\n");
+            return 2;
+        }
+        if (!a.qtl_pheno.empty()) {
+            if (!a.eigensnp) { std::fprintf(stderr, "error: --gpca-qtl-pheno needs the --eigensnp workflow\n"); return 2; }
+            if (a.have_qtl_pcs && !(a.qtl_pcs >= 0 && a.qtl_pcs <= a.k_global)) {
+                std::fprintf(stderr, "error: --gpca-qtl-pcs P must lie in [0, --eigensnp-k-global]\n");
+                return 2;
+            }
+            if (!(a.qtl_vif >= 1.0) || !std::isfinite(a.qtl_vif)) { std::fprintf(stderr, "error: --gpca-qtl-vif must be finite and at least 1\n"); return 2; }
+            if (a.have_qtl_log10p && a.have_qtl_t) { std::fprintf(stderr, "error: --gpca-qtl-log10p and --gpca-qtl-t set the same threshold: give one\n"); return 2; }
+            if (!(a.qtl_log10p >= 0.0) || !std::isfinite(a.qtl_log10p)) { std::fprintf(stderr, "error: --gpca-qtl-log10p must be finite and at least 0\n"); return 2; }
+            if (!(a.qtl_t >= 0.0) || !std::isfinite(a.qtl_t)) { std::fprintf(stderr, "error: --gpca-qtl-t must be finite and at least 0\n"); return 2; }
+            if (a.local_stage) {
+                std::fprintf(stderr, "error: --gpca-qtl-pheno cannot be combined with --gpca-eigensnp-local-stage (that stage defines no all-sample scores)\n");
+                return 2;
+            }
+            if (a.stream == "on") { std::fputs(kQtlNeedsResident, stderr); return 2; }
+            try { a.qtl_pheno_table = gpca_host::read_pheno(a.qtl_pheno); }
+            catch (const std::runtime_error& e) { std::fprintf(stderr, "error: --gpca-qtl-pheno: %s\n", e.what()); return 2; }
+            if (!a.qtl_covar.empty()) {
+                try { a.qtl_covar_table = gpca_host::read_pheno(a.qtl_covar); }
+                catch (const std::runtime_error& e) { std::fprintf(stderr, "error: --gpca-qtl-covar: %s\n", e.what()); return 2; }
+            }
+            const int64_t t = (int64_t)a.qtl_pheno_table.names.size(), c = (int64_t)a.qtl_covar_table.names.size(), p = a.have_qtl_pcs ? a.qtl_pcs : a.k_global;
+            if (t > kQtlMaxTraits) { std::fprintf(stderr, "error: --gpca-qtl-pheno: %lld traits are more than %lld\n", (long long)t, (long long)kQtlMaxTraits); return 2; }
+            if (p + c > kQtlMaxCovariates) {
+                std::fprintf(stderr, "error: --gpca-qtl-pheno: %lld PCs + %lld covariates are more than %lld covariates\n", (long long)p, (long long)c,
+                             (long long)kQtlMaxCovariates);
+                return 2;
             }
         }
         if (a.assoc_ldsc && (a.ld_score.empty() || a.assoc_pheno.empty())) {

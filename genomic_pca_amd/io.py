@@ -798,6 +798,78 @@ def write_assoc(prefix: str, trait: str, chromosomes: Sequence[str], positions: 
     return path
 
 
+# ---- many-trait QTL scan (gpca_assoc_qtl, gpca_qtl_stats, gpca_qtl_t_min; include/gpca.h section a24): twins in host/formats.hpp ------------
+QTL_HITS_PER_PAIRS = 4096         # assoc_qtl_bands: the record buffer holds one pair in this many of a band
+QTL_BAND_WORK_MAX = 1 << 47       # assoc_qtl_bands: rows x N x T of one call (a few seconds of the matrix cores)
+
+
+def assoc_qtl_bands(K: int, T: int, N: int, cap: int):
+    """[row0, row1) bands of the K kept rows for gpca_assoc_qtl with a record buffer of cap hits: whole blocks of 128 rows (at least
+    one block) such that cap holds one pair in QTL_HITS_PER_PAIRS of the band's rows x T pairs (a threshold scan keeps far fewer; a band
+    that finds more is asked for again with a buffer of n_found; every band repeats the call's host step on all T traits, so bands are
+    made long) and rows x N x T stays within QTL_BAND_WORK_MAX."""
+    K, T, N, cap = int(K), max(int(T), 1), max(int(N), 1), max(int(cap), 1)
+    step = min(cap * QTL_HITS_PER_PAIRS // T, QTL_BAND_WORK_MAX // (N * T))
+    step = max(step // 128 * 128, 128)
+    return [(r0, min(r0 + step, K)) for r0 in range(0, K, step)]
+
+
+def write_qtl_hits(prefix: str, chromosomes: Sequence[str], positions: Sequence[int], variant_ids: Sequence[str], allele1: Sequence[str],
+                   traits: Sequence[str], n_obs, a1_freq, beta, se, t, log10p, append: bool = False) -> str:
+    """P.qtl.hits: one tab-separated line per hit in the order given (the scan's: ascending (row, trait)), `#CHROM POS ID A1 TRAIT OBS_CT
+    A1_FREQ BETA SE T_STAT LOG10P`; every column holds one entry per hit (the SNP's columns repeated per hit); numbers as %.6g, NaN as
+    NA, OBS_CT as an integer.  append=True adds the hits of a further band (no header)."""
+    path = f"{prefix}.qtl.hits"
+    n = len(traits)
+    for a in (chromosomes, positions, variant_ids, allele1, n_obs, a1_freq, beta, se, t, log10p):
+        if len(a) != n:
+            raise ValueError("write_qtl_hits: one entry per hit in every column")
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    with open(path, "a" if append else "w") as f:
+        if not append:
+            f.write("#CHROM\tPOS\tID\tA1\tTRAIT\tOBS_CT\tA1_FREQ\tBETA\tSE\tT_STAT\tLOG10P\n")
+        f.writelines(f"{chromosomes[i]}\t{int(positions[i])}\t{variant_ids[i]}\t{allele1[i]}\t{traits[i]}\t{int(n_obs[i])}\t{_g6(a1_freq[i])}\t"
+                     f"{_g6(beta[i])}\t{_g6(se[i])}\t{_g6(t[i])}\t{_g6(log10p[i])}\n" for i in range(n))
+    return path
+
+
+def qtl_best_merge(best_r2, best_row, band_r2, band_row):
+    """The running best over bands in ascending row order, in place: a band's (r2, row) replaces a trait's entry when the trait has
+    none yet (row < 0) or the band's r2 is strictly larger, so a tie stays with the lower row.  Returns (best_r2, best_row)."""
+    b2, bw = np.asarray(band_r2, np.float64), np.asarray(band_row, np.int64)
+    with np.errstate(invalid="ignore"):
+        take = (bw >= 0) & ((best_row < 0) | (b2 > best_r2))
+    best_r2[take] = b2[take]
+    best_row[take] = bw[take]
+    return best_r2, best_row
+
+
+def write_qtl_best(prefix: str, traits: Sequence[str], chromosomes: Sequence[str], positions: Sequence[int], variant_ids: Sequence[str],
+                   allele1: Sequence[str], beta, se, t, log10p, n_tests) -> str:
+    """P.qtl.best: one tab-separated line per trait, `#TRAIT CHROM POS ID A1 BETA SE T_STAT LOG10P N_TESTS`: the SNP with the largest r2
+    for the trait over all bands (the lower row on a tie) and the number of live SNPs it was chosen from; a trait without a live SNP
+    has NA in the SNP's columns (an entry of variant_ids that is None); numbers as %.6g, NaN as NA."""
+    path = f"{prefix}.qtl.best"
+    n = len(traits)
+    for a in (chromosomes, positions, variant_ids, allele1, beta, se, t, log10p, n_tests):
+        if len(a) != n:
+            raise ValueError("write_qtl_best: one entry per trait in every column")
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    with open(path, "w") as f:
+        f.write("#TRAIT\tCHROM\tPOS\tID\tA1\tBETA\tSE\tT_STAT\tLOG10P\tN_TESTS\n")
+        for i in range(n):
+            if variant_ids[i] is None:
+                f.write(f"{traits[i]}\tNA\tNA\tNA\tNA\tNA\tNA\tNA\tNA\t{int(n_tests[i])}\n")
+            else:
+                f.write(f"{traits[i]}\t{chromosomes[i]}\t{int(positions[i])}\t{variant_ids[i]}\t{allele1[i]}\t{_g6(beta[i])}\t{_g6(se[i])}\t"
+                        f"{_g6(t[i])}\t{_g6(log10p[i])}\t{int(n_tests[i])}\n")
+    return path
+
+
 # ---- LD scores and LD-score regression (gpca_ld_score, gpca_ld_score_total, gpca_ldsc_fit; include/gpca.h section a19) -----------
 def ld_score_sum(K: int, bands):
     """(acc int64 [K], partners int64 [K]) = the bands of GpcaEngine.ld_score added up.  bands: ((row0, row1), score[, partners]) over

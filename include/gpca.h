@@ -1033,6 +1033,48 @@ GPCA_API int gpca_fstat_blocks(const uint8_t* chrom_change /* [rows] */, const i
 GPCA_API int gpca_fstat(const int64_t* acc, const int64_t* cnt, int32_t B, int32_t P, const int32_t* quads /* [M][4] */, int64_t M,
                         double* out /* [M][6] */);
 
+/* ---- a24: many-trait QTL scan: a12's regression of every kept row of the band against every one of T traits (1 <= T <= 2^20, 0 <= Pc <=
+ * 63; the same samples and covariates for all traits), of which only the pairs at or above a threshold and the best row of every trait
+ * come back (Matrix eQTL, tensorQTL's trans mode, PheWAS screens).  One wide device pass: no [rows][T] table exists anywhere.
+ *  1. host: a12's step 1 on the T columns (a trait column is treated on its own): B_t = (float) Y~_t, Q, yy_t, df = n - Pc - 2.
+ *  2. device: n_obs, s1, s2 exact; d_it and e_it with the operands, the sample order and the flush rule of a12's step 2 (a workgroup
+ *     owns 128 rows and a strip of trait columns, which it walks in tiles of 64; no split of the sample axis); xb_it = d_it + mbar e_it.
+ *     xb_it, xx, sxx and the covariate products behind sxx carry, bit for bit, what gpca_assoc_linear returns for the row and the trait
+ *     with the same C and include, whichever traits sit beside it.
+ *  3. device, f64, no fused multiply-add: a row is dead if n_obs = 0, xx <= 0 or sxx max_vif < xx; for a live row r2_it = (xb_it xb_it) /
+ *     (sxx yy_t); a pair is a hit iff its row is live and r2_it >= r2_min.  A pair with r2 >= 1 (a12's rss <= 0) is still a hit:
+ *     gpca_qtl_stats gives it NaN statistics.
+ * Outputs: rowinfo [rows][4] as a12 (or NULL); yy [T] (or NULL); hit_count [rows] = the hits of every row, always complete, and
+ * *n_found = their sum.  n_found <= cap: hit_index [n_found][2] = (kept row, absolute; trait) and hit_value [n_found][2] = (xb, r2) hold
+ * every hit in ascending (row, trait) order.  n_found > cap: the status is still GPCA_OK and the record buffers are unspecified; the
+ * caller comes back with a larger buffer or a shorter band (hit_index and hit_value may be NULL iff cap = 0).  best_r2 [t] = the largest
+ * r2 of trait t over the band's live rows, best_row [t] = the smallest kept row that attains it; NaN and -1 without a live row (both
+ * pointers or neither).  Every output is independent of the launch plan and of the order of any atomic (integer atomics count the hits
+ * and place the records, which are sorted before they are returned); a band gives the records of the full call restricted to its rows;
+ * int8 and 2-bit residency and a GPCA_PREC_F32_MFMA handle give the same bits; the sample mask is ignored and no fitted result is
+ * touched.  GPCA_QTL_TW in the environment (read per call, clamped to a legal strip width: a power of two from 64 to 1024) forces the
+ * strip width; it changes no output.  The host step of a call with 256 traits or more runs on GPCA_DESIGN_THREADS threads (default 8; a
+ * trait belongs to one thread, so no bit depends on the count).
+ * gpca_qtl_stats: the host rule for one hit, out [3] = beta, se, t by a12's step 3 (beta = xb / sxx, rss = yy_t - xb beta, se = sqrt(rss /
+ * df / sxx), t = beta / se), all NaN when rss <= 0; gpca_student_t_log10p gives the p-value.
+ * Errors: as a12 (GPCA_ERR_STATE: no standardisation, K = 0, a streamed or row-sharded handle; GPCA_ERR_BAD_ARG: T, Pc or the row range
+ * out of bounds, a non-finite entry of Y or C on an included sample, df < 1, a constant or collinear column of C, a trait with yy_t = 0
+ * (the message names it), max_vif < 1 or not finite; GPCA_ERR_INVALID_GENOTYPE names the row; GPCA_ERR_OOM is checked before any
+ * allocation), and GPCA_ERR_BAD_ARG for r2_min outside [0, 1] or NaN, cap < 0, NULL record buffers with cap > 0, NULL hit_count or
+ * n_found, only one of best_r2 / best_row.
+ * Not there: cis windows and per-trait row ranges, permutation or beta-approximated empirical p-values, per-trait sample sets and missing
+ * phenotypes, interaction terms, case / control traits, bf16 or other reduced-precision operands, streamed and row-sharded handles. */
+GPCA_API int gpca_assoc_qtl(gpca_handle* h, const double* Y /* [N][T] */, int64_t T, const double* C /* [N][Pc] or NULL */, int32_t Pc,
+                            const uint8_t* include /* [N] or NULL */, double max_vif, double r2_min, int64_t row0, int64_t row1,
+                            double* rowinfo /* [rows][4] or NULL */, double* yy /* [T] or NULL */, uint32_t* hit_count /* [rows] */,
+                            uint32_t* hit_index /* [cap][2]; NULL iff cap = 0 */, double* hit_value /* [cap][2] */, int64_t cap,
+                            int64_t* n_found, double* best_r2 /* [T] or NULL */, int64_t* best_row /* [T] or NULL */);
+GPCA_API void gpca_qtl_stats(double xb, double sxx, double yy_t, double df, double* out /* [3] */);
+/* the smallest t >= 0 whose two-sided -log10 p at df degrees of freedom (gpca_student_t_log10p) reaches log10p, by bisection down to
+ * neighbouring doubles: the cutoff a threshold on the p-value becomes (r2_min = t^2 / (t^2 + df)).  0 for log10p <= 0, NaN for NaN or
+ * df <= 0, +inf when no finite t reaches it.  Host only. */
+GPCA_API double gpca_qtl_t_min(double log10p, double df);
+
 /* ---- f3: the stages of EigenSNPCoreAlgorithm::compute_pca (main.rs:311-327, 359-366) ------------------------------------------
  * The algorithm lives in the un-vendored efficient_pca crate (Cargo.toml:30, branch "main", no pinned revision): what follows is
  * the stage structure of its published description -- per-LD-block local bases learnt on a sample subset, condensed features of

@@ -271,6 +271,38 @@ public:
         if (xb) xb->resize(rows * (size_t)(T + Pc));
     }
 
+    // many-trait QTL scan (gpca_assoc_qtl) of kept rows [row0, row1): Y [N][T], T up to 2^20, C [N][Pc] (may be empty when Pc = 0), include
+    // (may be null: everyone) [N]; the pairs of a live row with r2 >= r2_min.  cap = the record buffer; when n_found > cap the records are
+    // empty and the caller comes back with cap = n_found.  best = false leaves best_r2 / best_row empty.
+    struct QtlResult {
+        std::vector<double> rowinfo, yy, xb, r2, best_r2;     // rowinfo [rows][4] = n_obs, a1_freq, xx, sxx; yy [T]; xb, r2 [n_found]
+        std::vector<uint32_t> hit_count, rows, traits;        // hit_count [rows]; rows (absolute kept row), traits [n_found]
+        std::vector<int64_t> best_row;                        // [T], -1 = no live row
+        int64_t n_found = 0;
+    };
+    QtlResult assoc_qtl(const std::vector<double>& Y, int64_t T, const std::vector<double>& C, int32_t Pc, const std::vector<uint8_t>* include,
+                        double max_vif, double r2_min, int64_t cap, int64_t row0, int64_t row1, bool best = true) const {
+        const size_t rows = row1 > row0 ? (size_t)(row1 - row0) : 0, nt = T > 0 ? (size_t)T : 0, nc = cap > 0 ? (size_t)cap : 0;
+        QtlResult q;
+        q.rowinfo.assign(std::max<size_t>(rows * 4, 1), 0.0);
+        q.yy.assign(std::max<size_t>(nt, 1), 0.0);
+        q.hit_count.assign(std::max<size_t>(rows, 1), 0u);
+        std::vector<uint32_t> hi(std::max<size_t>(2 * nc, 1), 0u);
+        std::vector<double> hv(std::max<size_t>(2 * nc, 1), 0.0);
+        if (best) { q.best_r2.assign(std::max<size_t>(nt, 1), 0.0); q.best_row.assign(std::max<size_t>(nt, 1), -1); }
+        check(gpca_assoc_qtl(h_, Y.data(), T, Pc ? C.data() : nullptr, Pc, include ? include->data() : nullptr, max_vif, r2_min, row0, row1,
+                             q.rowinfo.data(), q.yy.data(), q.hit_count.data(), cap > 0 ? hi.data() : nullptr, cap > 0 ? hv.data() : nullptr, cap,
+                             &q.n_found, best ? q.best_r2.data() : nullptr, best ? q.best_row.data() : nullptr));
+        q.rowinfo.resize(rows * 4); q.yy.resize(nt); q.hit_count.resize(rows);
+        if (best) { q.best_r2.resize(nt); q.best_row.resize(nt); }
+        if (q.n_found <= cap)
+            for (int64_t i = 0; i < q.n_found; ++i) {
+                q.rows.push_back(hi[2 * (size_t)i]); q.traits.push_back(hi[2 * (size_t)i + 1]);
+                q.xb.push_back(hv[2 * (size_t)i]); q.r2.push_back(hv[2 * (size_t)i + 1]);
+            }
+        return q;
+    }
+
     // logistic score scan (gpca_assoc_logistic_score) of kept rows [row0, row1): Y [N][T] in {0, 1}, C [N][Pc] (may be empty when
     // Pc = 0), include (may be null: everyone) [N], T (Pc + 3) <= 64; stats [rows][T][5] = beta, se, z, vw, V; rowinfo [rows][5] = n_obs,
     // a1_freq, xx, flipped, 0; ua (may be null) [rows][T][Pc + 3] = U, gwg, a_0 .. a_Pc
