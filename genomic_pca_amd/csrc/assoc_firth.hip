@@ -4,7 +4,8 @@
 // of kAspListItems.  k_assoc_firth_flag (a thread per item) writes the item's normal value with status 0 and, where z is finite and
 // |z| >= firth_z, takes a slot of the range's list from an atomic counter: the slot decides only which workgroup computes the item, every
 // result goes to the item's own address.
-// k_assoc_firth: asp_slots(N) persistent workgroups of kAspThreads threads take the listed items in turn.  For an item the workgroup
+// k_assoc_firth: asp_slots(N) persistent workgroups of kAspThreads threads (fewer where GPCA_ASP_SLOTS forces it: asp_clamp_slots; no
+// result depends on the count) take the listed items in turn.  For an item the workgroup
 //  1. stages g~ into its slice of the workspace as k_assoc_spa does (asp_stage_gt, assoc_stage.h), taking max |g~| on the way (a max
 //     is exact and does not depend on the order);
 //  2. runs the root rule of spa_math.h (firth_item): every pass is one sweep over g~ and mu with five running sums K .. K''''.
@@ -127,9 +128,9 @@ void launch_assoc_firth_flag(hipStream_t st, const double* stats, int T, int64_t
 
 int launch_assoc_firth(hipStream_t st, const void* G, int packed, int64_t ldr, const int64_t* krows, int64_t N, const unsigned* incw,
                        const unsigned* sums, const double* dv, const double* Z, const double* mu, int T, int Pc, int64_t row0,
-                       int64_t item0, const int* list, const unsigned* count, double* gws, double* out) {
-    if (T < 1 || Pc < 0 || asr_cols(T, Pc) > kAsrMaxCols || N < 1) return (int)hipErrorInvalidValue;
-    const dim3 grid((unsigned)asp_slots(N)), blk(kAspThreads);
+                       int64_t item0, const int* list, const unsigned* count, double* gws, double* out, int64_t slots) {
+    if (T < 1 || Pc < 0 || asr_cols(T, Pc) > kAsrMaxCols || N < 1 || slots < 1 || slots > asp_slots(N)) return (int)hipErrorInvalidValue;
+    const dim3 grid((unsigned)slots), blk(kAspThreads);                         // (gws keeps asp_slots(N) slices: workgroup b writes slice b)
     const int64_t npad = asp_gpad(N);
     if (packed)
         hipLaunchKernelGGL((k_assoc_firth<true>), grid, blk, 0, st, G, ldr, krows, N, npad, incw, sums, dv, Z, mu, T, Pc, row0, item0, list,

@@ -3,7 +3,8 @@
 // After k_assoc_score_finish the band's (row, trait) items are walked in ranges of kAspListItems.  k_assoc_spa_flag (a thread per item)
 // writes the item's normal value with status 0 and, where z is finite, |z| >= spa_z and U != 0, takes a slot of the range's list from an
 // atomic counter: the slot decides only which workgroup computes the item, every result goes to the item's own address.
-// k_assoc_spa: asp_slots(N) persistent workgroups of kAspThreads threads take the listed items in turn.  For an item the workgroup
+// k_assoc_spa: asp_slots(N) persistent workgroups of kAspThreads threads (fewer where GPCA_ASP_SLOTS forces it: asp_clamp_slots; no
+// result depends on the count) take the listed items in turn.  For an item the workgroup
 //  1. (asp_stage_gt, assoc_stage.h, shared with k_assoc_firth) reads the row once, in chunks of kAspChunk samples: a thread fetches 32 samples (asc_fetch), masks and flips them as the score
 //     kernel does (asr_put) into an LDS buffer; then thread t owns the samples t + kAspThreads k: x~ = the operand, the operand's mean
 //     xbar on a missing call, 0 outside S; g~ = x~ - sum_j a_j Z_nj (j ascending, a_j from dv, Z = X L^-T in f64 from the host), written
@@ -121,9 +122,9 @@ void launch_assoc_spa_flag(hipStream_t st, const double* stats, const double* dv
 
 int launch_assoc_spa(hipStream_t st, const void* G, int packed, int64_t ldr, const int64_t* krows, int64_t N, const unsigned* incw,
                      const unsigned* sums, const double* dv, const double* Z, const double* mu, int T, int Pc, int64_t row0,
-                     int64_t item0, const int* list, const unsigned* count, double* gws, double* out) {
-    if (T < 1 || Pc < 0 || asr_cols(T, Pc) > kAsrMaxCols || N < 1) return (int)hipErrorInvalidValue;
-    const dim3 grid((unsigned)asp_slots(N)), blk(kAspThreads);
+                     int64_t item0, const int* list, const unsigned* count, double* gws, double* out, int64_t slots) {
+    if (T < 1 || Pc < 0 || asr_cols(T, Pc) > kAsrMaxCols || N < 1 || slots < 1 || slots > asp_slots(N)) return (int)hipErrorInvalidValue;
+    const dim3 grid((unsigned)slots), blk(kAspThreads);                         // (gws keeps asp_slots(N) slices: workgroup b writes slice b)
     const int64_t npad = asp_gpad(N);
     if (packed)
         hipLaunchKernelGGL((k_assoc_spa<true>), grid, blk, 0, st, G, ldr, krows, N, npad, incw, sums, dv, Z, mu, T, Pc, row0, item0, list,

@@ -371,6 +371,9 @@ int assoc_logistic(gpca_handle* h, const std::string& f, const double* Y, int32_
     if (with_corr) {
         ScopedTimer t(h, with_firth ? "assoc_firth" : "assoc_spa", 0.0, 0.0);
         const int64_t items = rows * (int64_t)T;
+        int64_t forced = 0;
+        if (const char* e = std::getenv("GPCA_ASP_SLOTS")) forced = std::strtoll(e, nullptr, 10);   // read per call: the tests' way to every walk edge
+        const int64_t slots = asp_clamp_slots(N, forced);
         for (int64_t item0 = 0; item0 < items; item0 += kAspListItems) {
             HIPCHK(hipMemsetAsync(ws.count, 0, 4, st));
             const int64_t nitems = std::min<int64_t>(kAspListItems, items - item0);
@@ -379,7 +382,7 @@ int assoc_logistic(gpca_handle* h, const std::string& f, const double* Y, int32_
             HIPCHK(hipGetLastError());
             if (!correct) continue;
             if ((with_firth ? launch_assoc_firth : launch_assoc_spa)(st, G, packed, ldr, krows, N, ws.incw, ws.sums, ws.dv, ws.Z, ws.mu, T, Pc,
-                                                                     row0, item0, ws.list, ws.count, ws.g, ws.corr) != 0)
+                                                                     row0, item0, ws.list, ws.count, ws.g, ws.corr, slots) != 0)
                 return fail(h, GPCA_ERR_BAD_ARG, f + ": the launch was refused");
             HIPCHK(hipGetLastError());
         }

@@ -399,10 +399,11 @@ void launch_assoc_score_finish(hipStream_t st, const double* dv, const unsigned*
 void launch_assoc_spa_flag(hipStream_t st, const double* stats, const double* dv, int T, int Pc, int64_t item0, int64_t nitems, double spa_z,
                            double* out, int* list, unsigned* count);
 // the listed items' out = -log10 p, status, zeta+, zeta-; Z [T][Pc + 1][asp_gpad(N)] and mu [T][asp_gpad(N)] f64, 0 outside the included
-// samples; gws: asp_g_capacity(N) doubles; row0: the band's first kept row
+// samples; gws: asp_g_capacity(N) doubles; row0: the band's first kept row; slots: the workgroups of the launch, 1 .. asp_slots(N) (refused
+// outside: asp_clamp_slots), which decide only which workgroup computes an item
 int launch_assoc_spa(hipStream_t st, const void* G, int packed, int64_t ldr, const int64_t* krows, int64_t N, const unsigned* incw,
                      const unsigned* sums, const double* dv, const double* Z, const double* mu, int T, int Pc, int64_t row0, int64_t item0,
-                     const int* list, const unsigned* count, double* gws, double* out);
+                     const int* list, const unsigned* count, double* gws, double* out, int64_t slots);
 
 // ---- Firth correction of the score scan (assoc_firth.hip): the same ranges, list and buffers as the saddle-point correction's
 // out [rows][T][kAfiWidth] = the normal -log10 p, status 0, NaN, NaN, NaN; list [*count] = the items with finite |z| >= firth_z
@@ -411,7 +412,7 @@ void launch_assoc_firth_flag(hipStream_t st, const double* stats, int T, int64_t
 // the listed items' out = -log10 p, status, beta of A1, se, D; the arguments are launch_assoc_spa's
 int launch_assoc_firth(hipStream_t st, const void* G, int packed, int64_t ldr, const int64_t* krows, int64_t N, const unsigned* incw,
                        const unsigned* sums, const double* dv, const double* Z, const double* mu, int T, int Pc, int64_t row0, int64_t item0,
-                       const int* list, const unsigned* count, double* gws, double* out);
+                       const int* list, const unsigned* count, double* gws, double* out, int64_t slots);
 
 // ---- gene-level set tests of the score scan (assoc_set.hip): lrows [listed] = the listed rows' original rows, sums and dv = what the
 // score scan's kernels left for them (band = the list), strips [n_strips] (plan_math.h: AsgStrip), phi [tri_total][T] as asg_phi_index

@@ -369,6 +369,12 @@ constexpr int64_t asp_slots(int64_t N) {
     const int64_t s = kAspWsBytes / (8 * asp_gpad(N > 0 ? N : 1));
     return s < 1 ? 1 : (s > kAspMaxSlots ? kAspMaxSlots : s);
 }
+// the workgroups a correction launches: asp_slots(N), or what GPCA_ASP_SLOTS forces (want > 0), clamped to [1, asp_slots(N)]; the
+// workspace keeps asp_slots(N) slices, so a forced count only leaves slices unused
+constexpr int64_t asp_clamp_slots(int64_t N, int64_t want) {
+    const int64_t s = asp_slots(N);
+    return want <= 0 || want > s ? s : want;
+}
 constexpr int64_t asp_ranges(int64_t rows, int T) { return (rows * (int64_t)T + kAspListItems - 1) / kAspListItems; }
 // elements of the call's own buffers: g~ [asp_slots][asp_gpad] (f64); Z [T][Pc + 1][asp_gpad] and mu [T][asp_gpad] (f64, 0 outside S and
 // past N); the list of a range's flagged items (i32, relative to the range) and out [rows][T][4] (f64)

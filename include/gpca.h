@@ -517,7 +517,9 @@ GPCA_API double gpca_normal_log10p(double z);
  * Device: the items are flagged and compacted after a13's finish kernel; a workgroup owns an item, reads its row once, keeps g~ in its
  * slice of a workspace bounded independently of the band, and every sum over the samples runs through a fixed tree that depends on N
  * alone (no atomics on sums), so a band is bit-identical to the same rows of the full call and int8, 2-bit and a GPCA_PREC_F32_MFMA
- * handle give the same bits.  Out of scope: the fast partially-normal variant of SAIGE for non-carriers, and
+ * handle give the same bits.  GPCA_ASP_SLOTS in the environment, read per call, forces the number of workgroups that walk the item
+ * list, clamped to 1 .. the default (at most 1024, fewer once a slice of g~ exceeds 256 KiB); the workspace keeps its size and no
+ * result depends on the count: a test hook.  Out of scope: the fast partially-normal variant of SAIGE for non-carriers, and
  * everything a13 leaves out.
  * Errors: those of gpca_assoc_logistic_score, and GPCA_ERR_BAD_ARG for a NULL spa or an spa_z below 0.5 or NaN.
  * gpca_spa_log10p: the same rules for one given vector g~ [n] with mu [n] (in [0, 1]; a sample with mu (1 - mu) = 0 adds nothing) and
@@ -569,7 +571,8 @@ GPCA_API int gpca_spa_log10p(const double* gt /* [n] */, const double* mu /* [n]
  * of the correction is built or allocated); 1.959964 is the two-sided 0.05 of regenie's --pThresh.
  * Device: a14's, with a kernel of its own (assoc_firth.hip): the same flagging and compaction, item ranges, workspace and fixed
  * summation tree, so a band is bit-identical to the same rows of the full call and int8, 2-bit and a GPCA_PREC_F32_MFMA handle give
- * the same bits.  Out of scope: the exact Firth test with the covariates refitted per SNP, a Firth-penalised null fit,
+ * the same bits; GPCA_ASP_SLOTS (a14: a test hook, read per call) forces this kernel's workgroup count too, and no result depends on
+ * it.  Out of scope: the exact Firth test with the covariates refitted per SNP, a Firth-penalised null fit,
  * profile-likelihood intervals, regenie's own numbers (its choices of offset and of genotype coding are not claimed), and everything
  * a13 leaves out (streamed and row-sharded handles: GPCA_ERR_STATE).
  * Errors: those of gpca_assoc_logistic_score, and GPCA_ERR_BAD_ARG for a NULL firth or a firth_z that is negative or NaN.

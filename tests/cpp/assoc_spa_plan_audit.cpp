@@ -59,6 +59,15 @@ static void audit_samples(int64_t N, bool walk) {
     EXPECT((slots - 1) * npad + (npad - 1) < asp_g_capacity(N), "g~ slices N=%lld", (long long)N);
     EXPECT(8 * asp_g_capacity(N) <= kAspWsBytes || slots == 1, "workspace bound N=%lld", (long long)N);
     EXPECT(slots == kAspMaxSlots || 8 * (slots + 1) * npad > kAspWsBytes, "slots not maximal N=%lld", (long long)N);
+    // a forced workgroup count (GPCA_ASP_SLOTS through asp_clamp_slots): in range, the identity on legal values, the default for unset
+    // or <= 0, and the slice of its last workgroup inside the workspace, which keeps the size asp_slots(N) gives it
+    for (int64_t want : {(int64_t)-7, (int64_t)0, (int64_t)1, (int64_t)2, (int64_t)3, slots - 1, slots, slots + 1, (int64_t)kAspMaxSlots,
+                         (int64_t)kAspMaxSlots + 1, (int64_t)1 << 40}) {
+        const int64_t got = asp_clamp_slots(N, want);
+        EXPECT(got >= 1 && got <= slots, "clamped slots N=%lld want=%lld", (long long)N, (long long)want);
+        EXPECT(got == (want >= 1 && want <= slots ? want : slots), "clamp N=%lld want=%lld got=%lld", (long long)N, (long long)want, (long long)got);
+        EXPECT((got - 1) * npad + (npad - 1) < asp_g_capacity(N), "forced slices N=%lld want=%lld", (long long)N, (long long)want);
+    }
     for (int Pc : {0, 1, 3, 29, 61}) {
         const int T = asr_max_traits(Pc), P = Pc + 1;
         EXPECT(((int64_t)(T - 1) * P + (P - 1)) * npad + (npad - 1) < asp_z_capacity(N, T, Pc), "Z N=%lld Pc=%d", (long long)N, Pc);
@@ -92,6 +101,11 @@ int main() {
     std::vector<int64_t> big = {500000, ((int64_t)1 << 25) - 1, (int64_t)1 << 25, ((int64_t)1 << 25) + 1, ((int64_t)1 << 30) - 1};
     for (int t = 0; t < 200; ++t) big.push_back(1 + (int64_t)(rng() % ((uint64_t)1 << 30)));
     for (int64_t N : big) audit_samples(N, false);
+    // the slot classes the lists above hold: all of kAspMaxSlots, fewer (from asp_gpad(N) > 32768 on), one
+    EXPECT(asp_slots(32768) == kAspMaxSlots && asp_slots(32769) == 1022 && asp_slots(65537) < kAspMaxSlots && asp_slots(500000) > 1, "slot classes");
+    EXPECT(asp_slots(((int64_t)1 << 24) + 1) == 1 && asp_slots((int64_t)1 << 25) == 1 && asp_slots(((int64_t)1 << 30) - 1) == 1, "one slot");
+    EXPECT(asp_clamp_slots(32769, 1023) == 1022 && asp_clamp_slots(32769, 3) == 3 && asp_clamp_slots((int64_t)1 << 25, 3) == 1, "clamp at the classes");
+    audit_samples(((int64_t)1 << 24) + 1, false);
     std::vector<int64_t> Ks = {1, 2, 127, 128, 129, 4097, kAspListItems - 1, kAspListItems, kAspListItems + 1, 3 * kAspListItems, 1000003, ((int64_t)1 << 31) - 1};
     for (int t = 0; t < 200; ++t) Ks.push_back(1 + (int64_t)(rng() % 30000000));
     for (int64_t K : Ks)

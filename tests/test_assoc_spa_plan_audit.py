@@ -5,7 +5,8 @@ k_assoc_spa's index arithmetic by brute force -- every thread of every chunk for
 slice edges among them), the first and last chunk for sample counts up to 2^30 - 1 -- checking that every 32-sample word and every
 sample below the padded count is taken once, that the fetches stay inside a row's pitch, that the LDS buffer, the slices of g~ (within
 their byte bound), Z and mu hold every index reached, and that the ranges of the item list cover a band's items once for kept rows up
-to 2^31 - 1."""
+to 2^31 - 1.  For every one of those sample counts (1024 slots, fewer, and one among them) a forced workgroup count (asp_clamp_slots,
+what GPCA_ASP_SLOTS goes through) stays in [1, asp_slots(N)], is the identity on legal values and keeps its slices inside the workspace."""
 import os
 import subprocess
 
