@@ -19,5 +19,8 @@ roh_threshold = GpcaEngine.roh_threshold
 admix_cv_fold = GpcaEngine.admix_cv_fold
 qtl_stats = GpcaEngine.qtl_stats
 qtl_t_min = GpcaEngine.qtl_t_min
+qtl_perm_table = GpcaEngine.qtl_perm_table
+qtl_perm_panel = GpcaEngine.qtl_perm_panel      # (engine, b, Q, perm): it runs on the engine's device
+qtl_beta_approx = GpcaEngine.qtl_beta_approx
 
 __version__ = "0.2.2"

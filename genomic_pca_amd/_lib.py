@@ -168,6 +168,11 @@ PROTOTYPES = {
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]),
     "gpca_qtl_stats": (None, [C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p]),
     "gpca_qtl_t_min": (C.c_double, [C.c_double, C.c_double]),
+    "gpca_assoc_qtl_cis": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_int32,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gpca_qtl_perm_panel": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]),
+    "gpca_qtl_perm_table": (C.c_int, [C.c_uint64, C.c_int64, C.c_int32, C.c_void_p]),
+    "gpca_qtl_beta_approx": (C.c_int, [C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_void_p, C.POINTER(C.c_int32)]),
     "gpca_logistic_null": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
     "gpca_assoc_logistic_score": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_int64, C.c_int64,
                                             C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -263,6 +263,15 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--gpca-qtl-t", type=float, default=None, metavar="X", help="--gpca-qtl-pheno: keep the pairs with |t| >= X instead")
     p.add_argument("--gpca-qtl-vif", type=float, default=None, metavar="X",
                    help="--gpca-qtl-pheno: a SNP whose variance inflation against the covariates exceeds X is not tested [default: 50]")
+    p.add_argument("--gpca-qtl-cis-pos", default=None, metavar="FILE",
+                   help="--gpca-qtl-pheno: cis-QTL mapping after the scan: FILE is a `TRAIT CHROM POS` table; every trait with a position is "
+                        "tested against the SNPs within the window around it, with a permutation null and its beta approximation, into "
+                        "<out>.qtl.cis")
+    p.add_argument("--gpca-qtl-cis-window", type=int, default=None, metavar="BP", help="--gpca-qtl-cis-pos: |SNP - POS| <= BP [default: 1000000]")
+    p.add_argument("--gpca-qtl-cis-perm", type=int, default=None, metavar="P",
+                   help="--gpca-qtl-cis-pos: permutations of the traits [default: 1000; 0 = nominal only, the beta columns are NA]")
+    p.add_argument("--gpca-qtl-cis-seed", type=int, default=None, metavar="S", help="--gpca-qtl-cis-pos: the seed of the permutation table [default: 0]")
+    p.add_argument("--gpca-qtl-cis-only", action="store_true", help="--gpca-qtl-cis-pos: skip the scan of every SNP against every trait")
     return p
 
 
@@ -1095,6 +1104,15 @@ def _qtl(eng, a, fs, cols, sample_ids, scores, inset, st):
     eng.set_standardization(st["mu"], st["sigma"], st["keep"])                       # every SNP that passes the SNP QC
     rows = np.flatnonzero(st["keep"])
     names = list(pheno.names)
+    if not a.gpca_qtl_cis_only:
+        _qtl_trans(eng, a, fs, lib, Y, C, include, vif, r2_min, tmin, rows, names, T, Pc, P, n, n_inc, df)
+    if a.gpca_qtl_cis_pos is not None:
+        _qtl_cis(eng, a, fs, Y, C, include, vif, rows, names, T, Pc, n, n_inc, df)
+
+
+def _qtl_trans(eng, a, fs, lib, Y, C, include, vif, r2_min, tmin, rows, names, T, Pc, P, n, n_inc, df):
+    """The scan of every SNP against every trait of _qtl, into P.qtl.hits and P.qtl.best."""
+    from . import _lib
     b2, bw = np.full(T, np.nan), np.full(T, -1, np.int64)
     n_tests, n_hits = 0, 0
     log10p = lambda t: float("nan") if t != t else lib.gpca_student_t_log10p(float(t), float(df))
@@ -1133,6 +1151,44 @@ def _qtl(eng, a, fs, cols, sample_ids, scores, inset, st):
                        pick(fs.allele1), beta, se, tt, [log10p(t) for t in tt], [n_tests if i is not None else 0 for i in ob])
     _log(f"QTL scan of {len(rows)} SNPs against {T} traits with {Pc} covariates ({P} PCs) on {n_inc} of {n} samples: {n_hits} pairs with "
          f"|t| >= {tmin:.6g}, written to {a.output_prefix}.qtl.hits and {a.output_prefix}.qtl.best")
+
+
+def _qtl_cis(eng, a, fs, Y, C, include, vif, rows, names, T, Pc, n, n_inc, df):
+    """--gpca-qtl-cis-pos FILE: cis-QTL mapping (gpca_assoc_qtl_cis) of every trait of --gpca-qtl-pheno that FILE gives a position,
+    against the SNPs that pass the SNP QC within --gpca-qtl-cis-window of it, with --gpca-qtl-cis-perm permutations from the table of
+    --gpca-qtl-cis-seed, in bands of traits, into P.qtl.cis.  Samples, covariates and refusals are the scan's."""
+    from . import _lib
+    window = 1000000 if a.gpca_qtl_cis_window is None else a.gpca_qtl_cis_window
+    nperm = 1000 if a.gpca_qtl_cis_perm is None else a.gpca_qtl_cis_perm
+    seed = 0 if a.gpca_qtl_cis_seed is None else a.gpca_qtl_cis_seed
+    tpos = [a.gpca_qtl_cis_table.get(t) for t in names]
+    chrom = [fs.chromosomes[i] for i in rows]
+    pos = [int(fs.positions[i]) for i in rows]
+    try:
+        win = gio.qtl_cis_windows(chrom, pos, ["" if p is None else p[0] for p in tpos], [0 if p is None else p[1] for p in tpos], window)
+    except ValueError as e:
+        raise SystemExit(f"error: --gpca-qtl-cis-pos: {e}") from None
+    for g, p in enumerate(tpos):
+        if p is None:
+            win[g] = 0
+    perm = GpcaEngine.qtl_perm_table(seed, n_inc, nperm)
+    parts = []
+    try:
+        # (no SNP passes the SNP QC: nothing to ask the device; every trait with a position gets its N_VAR = 0 line)
+        for g0, g1 in (gio.assoc_qtl_cis_bands(T, nperm) if len(rows) else []):
+            parts.append(eng.assoc_qtl_cis(np.ascontiguousarray(Y[:, g0:g1]), win[g0:g1], C, include=include, max_vif=vif, perm=perm))
+    except _lib.GpcaError as e:
+        if e.status == _lib.GPCA_ERR_STATE:
+            raise SystemExit(QTL_NEEDS_RESIDENT) from None
+        raise
+    res = {k: np.concatenate([q[k] for q in parts]) for k in ("n_var", "best_row", "best_r2", "best_stat", "perm_r2")} if parts else \
+        {"n_var": np.zeros(T, np.int64), "best_row": np.full(T, -1, np.int64), "best_r2": np.full(T, np.nan), "best_stat": np.full((T, 3), np.nan),
+         "perm_r2": np.full((T, nperm), np.nan)}
+    res["df"] = float(df)
+    gio.write_qtl_cis(a.output_prefix, names, tpos, res, [fs.variant_ids[i] for i in rows], pos, [fs.allele1[i] for i in rows])
+    n_pos = sum(p is not None for p in tpos)
+    _log(f"cis-QTL mapping of {n_pos} of {T} traits within {window} bp with {Pc} covariates on {n_inc} of {n} samples and {nperm} "
+         f"permutations (seed {seed}), written to {a.output_prefix}.qtl.cis")
 
 
 def _assoc_sets(eng, a, fs, rows, a1_freq, Yb, bnames, C, Pc, include, vif):
@@ -1407,6 +1463,23 @@ def main(argv=None) -> int:
         if a.gpca_stream == "on":
             raise SystemExit(QTL_NEEDS_RESIDENT)
         a.gpca_qtl_tables = _qtl_tables(a)
+    if a.gpca_qtl_cis_pos is None and (a.gpca_qtl_cis_only or any(v is not None for v in (a.gpca_qtl_cis_window, a.gpca_qtl_cis_perm, a.gpca_qtl_cis_seed))):
+        raise SystemExit("error: --gpca-qtl-cis-window, --gpca-qtl-cis-perm, --gpca-qtl-cis-seed and --gpca-qtl-cis-only need --gpca-qtl-cis-pos")
+    if a.gpca_qtl_cis_pos is not None:
+        if a.gpca_qtl_pheno is None:
+            raise SystemExit("error: --gpca-qtl-cis-pos needs --gpca-qtl-pheno")
+        if a.gpca_qtl_cis_window is not None and a.gpca_qtl_cis_window < 0:
+            raise SystemExit("error: --gpca-qtl-cis-window must be at least 0")
+        if a.gpca_qtl_cis_perm is not None and not 0 <= a.gpca_qtl_cis_perm <= 65535:
+            raise SystemExit("error: --gpca-qtl-cis-perm must lie in [0, 65535]")
+        if a.gpca_qtl_cis_seed is not None and a.gpca_qtl_cis_seed < 0:
+            raise SystemExit("error: --gpca-qtl-cis-seed must be at least 0")
+        try:
+            a.gpca_qtl_cis_table = gio.read_trait_pos(a.gpca_qtl_cis_pos)
+        except OSError:
+            raise SystemExit(f"error: --gpca-qtl-cis-pos: cannot open {a.gpca_qtl_cis_pos}") from None
+        except ValueError as e:
+            raise SystemExit(f"error: --gpca-qtl-cis-pos: {e}") from None
     if a.gpca_indep_pairwise:
         if not a.eigensnp:
             raise SystemExit("error: --gpca-indep-pairwise needs the --eigensnp workflow")

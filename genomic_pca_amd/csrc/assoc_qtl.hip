@@ -23,8 +23,8 @@
 // scratch and no VGPR spill (22 SGPRs go to VGPR lanes): one wave per SIMD.  LDS (static, qtl_lds_bytes): the two
 // stage buffers of AscSmem<2, 3> = 54 784 B, mbar and sxx 2 x 1 KiB, live and the hit counts 2 x 512 B, the waves' bests 4 x 64 x 16 B
 // = 4 KiB: 61 952 B of the 160 KiB.
-// Out of scope: cis windows, per-trait sample sets, permutations, interaction terms, case / control traits, reduced-precision operands,
-// streamed and row-sharded handles.
+// Out of scope (cis windows and permutations: assoc_qtl_cis.hip): per-trait sample sets, interaction terms, case / control traits,
+// reduced-precision operands, streamed and row-sharded handles.
 #include "assoc_tile.h"
 
 #pragma clang fp contract(off)

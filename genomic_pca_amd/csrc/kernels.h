@@ -380,6 +380,21 @@ int launch_assoc_qtl(hipStream_t st, const void* G, int packed, int64_t ldr, con
 void launch_assoc_qtl_best(hipStream_t st, const double* ws_r2, const long long* ws_row, int64_t blocks, int64_t T, double* best_r2,
                            long long* best_row);
 
+// ---- cis-QTL mapping: the permuted panel of one trait, its window scanned for the best row of every column (assoc_qtl_cis.hip) ---------
+// out [P + 1][npad] f32 (zeroed by the caller where no included sample sits): column 0 = (float) b, column p + 1 = (float) of b gathered
+// through perm [p] and taken back into the complement of Qt [Pc][n] (f64); b [n] f64; S [n] = the sample of i (NULL: i itself)
+void launch_qtl_perm_panel(hipStream_t st, const double* b, const double* Qt, int Pc, int64_t n, const uint32_t* perm, int64_t P, const int* S,
+                           int64_t npad, float* out);
+// One launch covers the kept rows [row0, row1) (at most qtl_chunk_blocks(T) row blocks from row0) of a window inside the band that starts
+// at band0; T = P + 1 columns of Bt [qtl_tpad(T)][asc_npad(N)], all with the trait's yy; sums, info as launch_assoc_qtl.  ws_r2 / ws_row
+// [row blocks][T] and ws_xb [row blocks] = the workgroups' best (r2, kept row) per column and xb of column 0's
+int launch_assoc_qtl_cis(hipStream_t st, const void* G, int packed, int64_t ldr, const int64_t* krows, int64_t N, const float* Bt,
+                         const unsigned* incw, double yy, int64_t T, int tw, int64_t band0, int64_t row0, int64_t row1, const unsigned* sums,
+                         const double* info, double max_vif, double* ws_r2, long long* ws_row, double* ws_xb);
+// folds the launch into the trait's running best (first: starts it); last: writes perm_r2 [g][T - 1] and best [g][3] = r2, xb, row
+void launch_assoc_qtl_cis_best(hipStream_t st, const double* ws_r2, const long long* ws_row, const double* ws_xb, int64_t blocks, int64_t T,
+                               int first, int last, double* run_r2, long long* run_row, double* run_xb, int64_t g, double* perm_r2, double* best);
+
 // ---- logistic score scan: kept rows x T (Pc + 3) panel columns over the samples, the operand coded by the minor allele (assoc_score.hip)
 // sums [row1 - row0][3] u32 = n_obs, sum g o, sum g^2 o; *bad as in launch_assoc
 int launch_assoc_score_count(hipStream_t st, const void* G, int packed, int64_t ldr, const int64_t* krows, int64_t N, const unsigned* incw,

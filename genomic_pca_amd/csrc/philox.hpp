@@ -5,6 +5,7 @@
 //   0x41444D51  admixture init of Q  counter = (sample_lo, sample_hi, column/4)
 //   0x41444D46  admixture init of F  counter = (kept_row_lo, kept_row_hi, column/4)
 //   0x41444D43  admixture CV folds   counter = (sample, kept_row/4, 0)
+//   0x51544C50  QTL permutations     counter = (step/4, table row, 0)
 // The fast panel generator (GPCA_PANEL_SYNTH16) uses SplitMix64 in counter mode instead (below): output (snp << 26) + sample / 4
 // of the stream seeded with `seed` = four 16-bit uniforms.
 #pragma once
@@ -41,6 +42,8 @@ GPCA_HD philox_out philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t
 #define GPCA_STREAM_ADMIX_F 0x41444D46u
 // the fold of a call in the admixture cross-validation (gpca.h section a22): counter = (sample, kept row / 4, 0), word = kept row & 3
 #define GPCA_STREAM_ADMIX_CV 0x41444D43u
+// the Fisher-Yates steps of a row of the cis-QTL permutation table (gpca.h section a25): counter = (step / 4, row, 0), word = step & 3
+#define GPCA_STREAM_QTL_PERM 0x51544C50u
 // SplitMix64 (Steele, Lea, Flood 2014; the generator that seeds xoshiro) in counter mode: output number i (0-based) of the stream
 // seeded with `seed` is mix(seed + (i + 1) * gamma) -- any i can be computed directly, consecutive i cost one 64-bit add.
 // Known answers (seed 1234567): 6457827717110365317, 3203168211198807973, 9817491932198370423, ...

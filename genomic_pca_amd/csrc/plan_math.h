@@ -703,4 +703,52 @@ constexpr double qtl_call_bytes(int64_t N, int64_t rows, int64_t T, int Pc, int6
            16.0 * (double)T + 8.0 /* the counter */ + 8.0 /* the invalid-genotype word */;
 }
 
+// ---- cis-QTL mapping (assoc_qtl_cis.hip, gpca_assoc_qtl_cis.cpp; include/gpca.h section a25) -------------------------------------------
+// One trait at a time: its panel is the a24 panel of T = P + 1 columns (column 0 the residual, column p + 1 permutation p), built on the
+// device by k_qtl_perm_panel, and its window [lo, hi) of kept rows goes through k_assoc_qtl_cis in launches of qtl_chunk_blocks(P + 1)
+// row blocks that start at lo.  The per-row pass runs once over the union [ulo, uhi) of the windows.
+constexpr int64_t kQtlCisMaxPerm = 65535;
+// k_qtl_perm_panel: a workgroup of kQtlPermThreads threads owns qtl_perm_group(Pc) columns of the panel; in the first step a thread owns
+// one (column, covariate) pair, in the second the threads walk the samples of one column after the other.  b_t sits in LDS up to
+// kQtlPermLdsSamples included samples and is gathered from global memory above that.  Step 1 takes Q through LDS in tiles of
+// kQtlPermQTile samples x Pc covariates.
+constexpr int kQtlPermThreads = 256, kQtlPermLdsSamples = 4096, kQtlPermQTile = 32, kQtlPermQPitch = kQtlPermQTile + 1;
+constexpr int qtl_perm_group(int Pc) { return Pc > 0 ? kQtlPermThreads / Pc : 16; }
+static_assert(qtl_perm_group(kQtlMaxPc) >= 1 && qtl_perm_group(1) * 1 <= kQtlPermThreads, "a thread per (column, covariate) pair");
+constexpr int64_t qtl_perm_grid(int64_t P, int Pc) { return (P + 1 + qtl_perm_group(Pc) - 1) / qtl_perm_group(Pc); }
+// static LDS of k_qtl_perm_panel: b_t (f64), the group's c [columns][Pc] (f64; at most kQtlPermThreads pairs) and the tile of Q
+// [kQtlMaxPc][kQtlPermQPitch] (f64) that step 1 reads
+constexpr int64_t qtl_perm_lds_bytes() { return 8 * (int64_t)kQtlPermLdsSamples + 8 * (int64_t)kQtlPermThreads + 8 * (int64_t)kQtlMaxPc * kQtlPermQPitch; }
+static_assert(qtl_perm_lds_bytes() <= 64 * 1024, "static LDS of k_qtl_perm_panel");
+// the panel of one trait and where column `col` (0 = the residual, p + 1 = permutation p) of sample n sits in it
+constexpr int64_t qtl_cis_panel_capacity(int64_t N, int64_t P) { return qtl_b_capacity(N, P + 1); }
+constexpr int64_t qtl_cis_panel_index(int64_t col, int64_t npad, int64_t n) { return col * npad + n; }
+// the call's resident inputs: the table [P][n] u32, Q [Pc][n] f64, the residuals of all traits [G][n] f64, S [n] i32
+constexpr int64_t qtl_cis_table_capacity(int64_t P, int64_t n) { return P * n; }
+constexpr int64_t qtl_cis_q_capacity(int Pc, int64_t n) { return (int64_t)Pc * n; }
+constexpr int64_t qtl_cis_resid_capacity(int64_t G, int64_t n) { return G * n; }
+constexpr int64_t qtl_cis_resid_index(int64_t g, int64_t n, int64_t i) { return g * n + i; }
+// the bests of a launch: ws [row blocks][P + 1] (r2 f64, row i64) as a24's, and xb of column 0's best row per row block (f64)
+constexpr int64_t qtl_cis_ws_blocks(int64_t rows, int64_t P) { return qtl_wsbest_blocks(rows, P + 1); }
+constexpr int64_t qtl_cis_ws_capacity(int64_t rows, int64_t P) { return qtl_wsbest_capacity(rows, P + 1); }
+constexpr int64_t qtl_cis_wsxb_capacity(int64_t rows, int64_t P) { return qtl_cis_ws_blocks(rows, P); }
+// the running best of the trait in flight [P + 1] (r2 f64, row i64) and the results: perm_r2 [G][P] f64, column 0's [G][3] f64 =
+// r2, xb, row (a kept row below 2^53 is exact in f64)
+constexpr int64_t qtl_cis_run_capacity(int64_t P) { return P + 1; }
+constexpr int64_t qtl_cis_result_capacity(int64_t G, int64_t P) { return G * P; }
+constexpr int64_t qtl_cis_result_index(int64_t g, int64_t P, int64_t p) { return g * P + p; }
+constexpr int64_t qtl_cis_best_capacity(int64_t G) { return 3 * G; }
+// static LDS of k_assoc_qtl_cis: k_assoc_qtl's without the hit counts, plus the four waves' xb of column 0
+constexpr int64_t qtl_cis_lds_bytes() { return asc_lds_bytes(kQtlTile / 32, 3) + 2 * 8 * kAscRows + 4 * kAscRows + 4 * kQtlTile * 16 + 4 * 8; }
+static_assert(qtl_cis_lds_bytes() <= 64 * 1024, "static LDS of k_assoc_qtl_cis");
+// The device bytes a call allocates (gpca_assoc_qtl_cis's GPCA_ERR_OOM sum, without the check's slack): rows = the union of the windows,
+// wrows = the longest window
+constexpr double qtl_cis_call_bytes(int64_t N, int64_t n, int64_t rows, int64_t wrows, int64_t G, int64_t P, int Pc) {
+    return 4.0 * (double)qtl_cis_panel_capacity(N, P) + 4.0 * (double)qtl_cis_table_capacity(P, n) + 8.0 * (double)qtl_cis_q_capacity(Pc, n) +
+           8.0 * (double)qtl_cis_resid_capacity(G, n) + 4.0 * (double)n + 4.0 * (double)qtl_q_capacity(N, Pc) + 4.0 * (double)asc_inc_capacity(N) +
+           8.0 * (double)qtl_xbq_capacity(rows, Pc) + 4.0 * (double)asc_sums_capacity(rows) + 8.0 * (double)asc_info_capacity(rows) +
+           16.0 * (double)qtl_cis_ws_capacity(wrows, P) + 8.0 * (double)qtl_cis_wsxb_capacity(wrows, P) + (16.0 + 8.0) * (double)qtl_cis_run_capacity(P) +
+           8.0 * (double)qtl_cis_result_capacity(G, P) + 8.0 * (double)qtl_cis_best_capacity(G) + 8.0 /* the invalid-genotype word */;
+}
+
 }  // namespace gpca

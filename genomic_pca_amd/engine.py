@@ -671,6 +671,73 @@ class GpcaEngine:
             out[i] = tmp[0], tmp[1], tmp[2]
         return out
 
+    def assoc_qtl_cis(self, Y, win, covar=None, include=None, max_vif: float = 50.0, perm=None, n_perm: int = 0, seed: int = 0):
+        """cis-QTL mapping (gpca_assoc_qtl_cis; gpca.h section a25): for every column of Y [N][G] the best kept row of its own window
+        win [G][2] = [lo, hi) and the best r2 of P permutations of the trait over the same window.  perm: uint32 [P][n], every row a
+        permutation of the n included samples; None with n_perm > 0: qtl_perm_table(seed, n, n_perm).  Returns a dict: n_var int64 [G],
+        best_row int64 [G], best_r2 [G], best_stat [G][3] = xb, sxx, yy (qtl_stats applies), perm_r2 [G][P], df, perm (the table used).  A
+        window without a live row gives n_var = 0, best_row = -1 and NaN elsewhere."""
+        Yv, Cv, inc, G, Pc, _, _, _ = self._assoc_args(Y, covar, include, None)
+        N = self.dims()[1]
+        n = N if inc is None else int(np.count_nonzero(inc))
+        wv = np.ascontiguousarray(win, np.int64)
+        if wv.shape != (G, 2):
+            raise ValueError("win must be [G][2]: a range [lo, hi) of kept rows per trait")
+        if perm is None:
+            perm = GpcaEngine.qtl_perm_table(seed, n, int(n_perm)) if n_perm else np.zeros((0, n), np.uint32)
+        pv = np.ascontiguousarray(perm, np.uint32)
+        if pv.ndim != 2 or pv.shape[1] != n:
+            raise ValueError("perm must be [P][n]: one permutation of the n included samples per row")
+        P = pv.shape[0]
+        n_var, best_row = np.zeros(max(G, 1), np.int64), np.zeros(max(G, 1), np.int64)
+        best_r2, best_stat = np.zeros(max(G, 1), np.float64), np.zeros((max(G, 1), 3), np.float64)
+        perm_r2 = np.zeros((max(G, 1), max(P, 1)), np.float64)
+        self._chk(self._lib.gpca_assoc_qtl_cis(self._h, _vp(Yv), G, _vp(Cv) if Pc else None, Pc, _vp(inc), float(max_vif), _vp(wv),
+                                               _vp(pv) if P else None, P, _vp(n_var), _vp(best_row), _vp(best_r2), _vp(best_stat),
+                                               _vp(perm_r2) if P else None))
+        return {"n_var": n_var[:G], "best_row": best_row[:G], "best_r2": best_r2[:G], "best_stat": best_stat[:G], "perm_r2": perm_r2[:G, :P],
+                "df": float(n - Pc - 2), "perm": pv}
+
+    def qtl_perm_panel(self, b, Q, perm) -> np.ndarray:
+        """The permuted columns of a25's panel (gpca_qtl_perm_panel) for the residual b [n], the basis Q [n][Pc] (None or [n][0]: no
+        covariates) and the table perm uint32 [P][n]: float32 [P][n]."""
+        bv = np.ascontiguousarray(b, np.float64).reshape(-1)
+        n = bv.shape[0]
+        Qv = np.zeros((n, 0), np.float64) if Q is None else np.ascontiguousarray(Q, np.float64).reshape(n, -1)
+        pv = np.ascontiguousarray(perm, np.uint32)
+        if pv.ndim != 2 or pv.shape[1] != n:
+            raise ValueError("perm must be [P][n]")
+        P, Pc = pv.shape[0], Qv.shape[1]
+        out = np.zeros((max(P, 1), max(n, 1)), np.float32)
+        self._chk(self._lib.gpca_qtl_perm_panel(self._h, _vp(bv), _vp(Qv) if Pc else None, Pc, n, _vp(pv) if P else None, P, _vp(out)))
+        return out[:P, :n]
+
+    @staticmethod
+    def qtl_perm_table(seed: int, n: int, P: int) -> np.ndarray:
+        """The permutation table of a25 (gpca_qtl_perm_table; host only): uint32 [P][n], row p a Fisher-Yates shuffle of 0 .. n - 1 driven
+        by philox4x32-10 keyed by (seed, p)."""
+        out = np.zeros((max(int(P), 0), max(int(n), 0)), np.uint32)
+        rc = _lib.load().gpca_qtl_perm_table(int(seed) & 0xFFFFFFFFFFFFFFFF, int(n), int(P), _vp(out) if out.size else None)
+        if rc != 0:
+            raise GpcaError(rc, "gpca_qtl_perm_table: n >= 0 and 0 <= P <= 65535 are required")
+        return out
+
+    @staticmethod
+    def qtl_beta_approx(perm_r2, r2_nominal: float, df: float) -> dict:
+        """FastQTL's beta approximation of the permutation p-value (gpca_qtl_beta_approx; host only): a dict of pval_perm, true_df,
+        shape1, shape2, log10p_nominal_true, log10p_beta, shape1_mom and status (bit 1: no root for true_df, df used; bit 2: the
+        maximum-likelihood fit failed, moment estimates returned)."""
+        pv = np.ascontiguousarray(perm_r2, np.float64).reshape(-1)
+        out = np.zeros(7, np.float64)
+        st = C.c_int32(0)
+        rc = _lib.load().gpca_qtl_beta_approx(_vp(pv) if pv.size else None, pv.size, float(r2_nominal), float(df), _vp(out), C.byref(st))
+        if rc != 0:
+            raise GpcaError(rc, "gpca_qtl_beta_approx: bad argument")
+        keys = ("pval_perm", "true_df", "shape1", "shape2", "log10p_nominal_true", "log10p_beta", "shape1_mom")
+        res = {k: float(v) for k, v in zip(keys, out)}
+        res["status"] = int(st.value)
+        return res
+
     def assoc_logistic_score(self, Y, covar=None, include=None, max_vif: float = 50.0, rows: Optional[Tuple[int, int]] = None, ua: bool = False):
         """Logistic score scan (gpca_assoc_logistic_score): the score test of every case / control trait (column of Y [N][T], 0 / 1 on
         the included samples) for the kept rows [row0, row1) in PCA-SNP order (default: all), the null model logit P(y = 1) = (1, covar)

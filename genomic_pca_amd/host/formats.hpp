@@ -981,6 +981,99 @@ private:
     OutFile o_;
 };
 
+// ---- cis-QTL mapping: the twins of io.qtl_cis_windows, io.read_trait_pos, io.assoc_qtl_cis_bands and io.write_qtl_cis -----------------
+constexpr int64_t kQtlCisResultBytesMax = (int64_t)256 << 20;      // perm_r2 [G][P] f64 of one call
+// win [G][2] for gpca_assoc_qtl_cis: [lo, hi) over the kept SNPs given (in their order) with |pos - trait_pos| <= window_bp on the trait's
+// chromosome; lo = hi where none qualifies, [0, 0) for a chromosome the SNPs do not have.  Ordered as ld_windows requires.
+inline std::vector<int64_t> qtl_cis_windows(const std::vector<std::string>& chromosomes, const std::vector<int64_t>& positions,
+                                            const std::vector<std::string>& trait_chrom, const std::vector<int64_t>& trait_pos, int64_t window_bp) {
+    const int64_t K = (int64_t)chromosomes.size();
+    if ((int64_t)positions.size() != K) throw std::runtime_error("qtl_cis_windows: one position per chromosome entry");
+    if (trait_chrom.size() != trait_pos.size()) throw std::runtime_error("qtl_cis_windows: one position per trait chromosome");
+    std::map<std::string, std::pair<int64_t, int64_t>> runs;
+    for (int64_t s = 0; s < K;) {
+        const std::string c = normalize_chromosome_name(chromosomes[(size_t)s]);
+        if (runs.count(c))
+            throw std::runtime_error("qtl_cis_windows: chromosome '" + chromosomes[(size_t)s] + "' reappears at variant " + std::to_string(s) +
+                                     " after another chromosome: sort the variants");
+        int64_t e = s + 1;
+        while (e < K && normalize_chromosome_name(chromosomes[(size_t)e]) == c) {
+            if (positions[(size_t)e] < positions[(size_t)e - 1])
+                throw std::runtime_error("qtl_cis_windows: the position of variant " + std::to_string(e) + " (" + std::to_string(positions[(size_t)e]) +
+                                         ") is below that of the variant before it on chromosome '" + chromosomes[(size_t)e] + "': sort the variants");
+            ++e;
+        }
+        runs[c] = {s, e};
+        s = e;
+    }
+    std::vector<int64_t> win(2 * trait_chrom.size(), 0);
+    for (size_t g = 0; g < trait_chrom.size(); ++g) {
+        const auto it = runs.find(normalize_chromosome_name(trait_chrom[g]));
+        if (it == runs.end()) continue;
+        const auto b = positions.begin() + it->second.first, e = positions.begin() + it->second.second;
+        win[2 * g] = it->second.first + (std::lower_bound(b, e, trait_pos[g] - window_bp) - b);
+        win[2 * g + 1] = it->second.first + (std::upper_bound(b, e, trait_pos[g] + window_bp) - b);
+    }
+    return win;
+}
+
+// A `TRAIT CHROM POS` table (that header; whitespace-separated): trait -> (chrom, pos); a later line of a trait replaces an earlier one
+inline std::map<std::string, std::pair<std::string, int64_t>> read_trait_pos(const std::string& path) {
+    std::ifstream in(path);
+    if (!in) throw std::runtime_error("cannot open " + path);
+    std::map<std::string, std::pair<std::string, int64_t>> out;
+    std::string line;
+    std::getline(in, line);
+    const std::vector<std::string> head = split_ws(line);
+    if (head != std::vector<std::string>{"TRAIT", "CHROM", "POS"}) throw std::runtime_error(path + ": the header must be 'TRAIT CHROM POS'");
+    for (int64_t ln = 2; std::getline(in, line); ++ln) {
+        const std::vector<std::string> t = split_ws(line);
+        if (t.empty()) continue;
+        if (t.size() != 3) throw std::runtime_error(path + ": line " + std::to_string(ln) + " does not hold TRAIT CHROM POS");
+        const std::string& p = t[2];
+        const size_t d0 = (p[0] == '+' || p[0] == '-') ? 1 : 0;
+        bool ok = p.size() > d0 && p.size() <= 18;
+        for (size_t i = d0; i < p.size(); ++i) ok = ok && p[i] >= '0' && p[i] <= '9';
+        if (!ok) throw std::runtime_error(path + ": line " + std::to_string(ln) + ": the position '" + p + "' is not an integer");
+        out[t[0]] = {t[1], std::stoll(p)};
+    }
+    return out;
+}
+
+// [g0, g1) bands of the G traits for gpca_assoc_qtl_cis such that perm_r2 [g1 - g0][P] (f64) stays within kQtlCisResultBytesMax (at
+// least one trait per band; one band when P = 0)
+inline std::vector<std::pair<int64_t, int64_t>> assoc_qtl_cis_bands(int64_t G, int64_t P) {
+    const int64_t step = P > 0 ? std::max<int64_t>(kQtlCisResultBytesMax / (8 * P), 1) : std::max<int64_t>(G, 1);
+    std::vector<std::pair<int64_t, int64_t>> out;
+    for (int64_t g0 = 0; g0 < G; g0 += step) out.emplace_back(g0, std::min(g0 + step, G));
+    return out;
+}
+
+// P.qtl.cis: one tab-separated line per trait in the order added, `#TRAIT CHROM POS N_VAR ID VAR_POS A1 BETA SE T_STAT LOG10P_NOMINAL
+// TRUE_DF SHAPE1 SHAPE2 PVAL_PERM LOG10P_BETA`; numbers as %.6g, NaN as NA.  add_no_pos: a trait without a position (NA in every column
+// after the name); add_empty: a trait whose window holds no live SNP (its position, N_VAR = 0, NA from ID on)
+class QtlCisWriter {
+public:
+    explicit QtlCisWriter(const std::string& prefix) : o_(prefix + ".qtl.cis") {
+        std::fputs("#TRAIT\tCHROM\tPOS\tN_VAR\tID\tVAR_POS\tA1\tBETA\tSE\tT_STAT\tLOG10P_NOMINAL\tTRUE_DF\tSHAPE1\tSHAPE2\tPVAL_PERM\tLOG10P_BETA\n", o_.f);
+    }
+    void add_no_pos(const std::string& trait) { std::fprintf(o_.f, "%s\tNA\tNA\tNA\tNA\tNA\tNA\tNA\tNA\tNA\tNA\tNA\tNA\tNA\tNA\tNA\n", trait.c_str()); }
+    void add_empty(const std::string& trait, const std::string& chrom, int64_t pos) {
+        std::fprintf(o_.f, "%s\t%s\t%lld\t0\tNA\tNA\tNA\tNA\tNA\tNA\tNA\tNA\tNA\tNA\tNA\tNA\n", trait.c_str(), chrom.c_str(), (long long)pos);
+    }
+    // v [9] = beta, se, t, log10p_nominal, true_df, shape1, shape2, pval_perm, log10p_beta
+    void add_trait(const std::string& trait, const std::string& chrom, int64_t pos, int64_t n_var, const std::string& id, int64_t var_pos,
+                   const std::string& a1, const double* v) {
+        std::fprintf(o_.f, "%s\t%s\t%lld\t%lld\t%s\t%lld\t%s", trait.c_str(), chrom.c_str(), (long long)pos, (long long)n_var, id.c_str(), (long long)var_pos,
+                     a1.c_str());
+        for (int i = 0; i < 9; ++i) { if (v[i] != v[i]) std::fputs("\tNA", o_.f); else std::fprintf(o_.f, "\t%.6g", v[i]); }
+        std::fputc('\n', o_.f);
+    }
+
+private:
+    OutFile o_;
+};
+
 // ---- logistic score scan: the twins of io.binary_trait, io.assoc_score_groups, io.assoc_score_bands and io.write_assoc_logistic ------
 // true when column c of the table is binary: its present (non-NaN) values are exactly {0, 1} (1 = case) or exactly {1, 2} (plink's
 // coding, 2 = case); *shift = what to take off a value to reach the 0 / 1 coding.  A column with one class only is not binary.

@@ -79,6 +79,12 @@ struct Args {
     double qtl_log10p = 5.0;          // --gpca-qtl-log10p X
     double qtl_t = 0.0;               // --gpca-qtl-t X
     gpca_host::PhenoTable qtl_pheno_table, qtl_covar_table;       // read in main, before any work on the device
+    std::string qtl_cis_pos;          // --gpca-qtl-cis-pos FILE (turns cis-QTL mapping on, after the scan)
+    bool have_qtl_cis_window = false, have_qtl_cis_perm = false, have_qtl_cis_seed = false, qtl_cis_only = false;
+    int64_t qtl_cis_window = 1000000; // --gpca-qtl-cis-window BP
+    int64_t qtl_cis_perm = 1000;      // --gpca-qtl-cis-perm P
+    int64_t qtl_cis_seed = 0;         // --gpca-qtl-cis-seed S
+    std::map<std::string, std::pair<std::string, int64_t>> qtl_cis_table;     // read in main
     gpca_host::PhenoTable assoc_pheno_table, assoc_covar_table;   // read in main, before any work on the device
     bool assoc_cc_freq = false;       // --gpca-assoc-cc-freq: P.<trait>.frq.cc beside every logistic scan
     std::string within;               // --gpca-within FILE: the sample groups of --gpca-freq-strat and --gpca-fst
@@ -312,6 +318,13 @@ void print_help() {
         "      --gpca-qtl-log10p <X>            --gpca-qtl-pheno: keep the pairs with -log10 p >= X [default: 5]\n"
         "      --gpca-qtl-t <X>                 --gpca-qtl-pheno: keep the pairs with |t| >= X instead\n"
         "      --gpca-qtl-vif <X>               --gpca-qtl-pheno: a SNP whose variance inflation exceeds X is not tested [default: 50]\n"
+        "      --gpca-qtl-cis-pos <FILE>        --gpca-qtl-pheno: cis-QTL mapping after the scan: FILE is a `TRAIT CHROM POS` table; every trait\n"
+        "                                       with a position is tested against the SNPs within the window around it, with a permutation\n"
+        "                                       null and its beta approximation, into <out>.qtl.cis\n"
+        "      --gpca-qtl-cis-window <BP>       --gpca-qtl-cis-pos: |SNP - POS| <= BP [default: 1000000]\n"
+        "      --gpca-qtl-cis-perm <P>          --gpca-qtl-cis-pos: permutations of the traits [default: 1000; 0 = nominal only]\n"
+        "      --gpca-qtl-cis-seed <S>          --gpca-qtl-cis-pos: the seed of the permutation table [default: 0]\n"
+        "      --gpca-qtl-cis-only              --gpca-qtl-cis-pos: skip the scan of every SNP against every trait\n"
         "      --gpca-assoc-vif <X>             --gpca-assoc-pheno: a SNP whose variance inflation against the covariates exceeds X gets\n"
         "                                       NA (plink's --vif) [default: 50]\n"
         "  -h, --help                           Print help");
@@ -438,6 +451,11 @@ Args parse(int argc, char** argv) {
         else if (f == "--gpca-qtl-vif") { a.qtl_vif = to_f64(f, val()); a.have_qtl_vif = true; }
         else if (f == "--gpca-qtl-log10p") { a.qtl_log10p = to_f64(f, val()); a.have_qtl_log10p = true; }
         else if (f == "--gpca-qtl-t") { a.qtl_t = to_f64(f, val()); a.have_qtl_t = true; }
+        else if (f == "--gpca-qtl-cis-pos") a.qtl_cis_pos = val();
+        else if (f == "--gpca-qtl-cis-window") { a.qtl_cis_window = to_i64(f, val()); a.have_qtl_cis_window = true; }
+        else if (f == "--gpca-qtl-cis-perm") { a.qtl_cis_perm = to_i64(f, val()); a.have_qtl_cis_perm = true; }
+        else if (f == "--gpca-qtl-cis-seed") { a.qtl_cis_seed = to_i64(f, val()); a.have_qtl_cis_seed = true; }
+        else if (f == "--gpca-qtl-cis-only") a.qtl_cis_only = true;
         else if (f == "--gpca-assoc-pcs") { a.assoc_pcs = to_i64(f, val()); a.have_assoc_pcs = true; }
         else if (f == "--gpca-assoc-vif") { a.assoc_vif = to_f64(f, val()); a.have_assoc_vif = true; }
         else if (f == "--gpca-ld-score") a.ld_score = val();
@@ -816,49 +834,83 @@ const char* kQtlNeedsResident =
     "error: --gpca-qtl-pheno needs the genotype matrix resident on the device: the scan of a matrix walked out of core is not implemented\n";
 constexpr int64_t kQtlMaxCovariates = 63, kQtlMaxTraits = (int64_t)1 << 20, kQtlCap = (int64_t)1 << 20;
 
-// --gpca-qtl-pheno FILE: the many-trait QTL scan (gpca_assoc_qtl) of every SNP that passes the SNP QC against every column of FILE, in
-// row bands, into P.qtl.hits and P.qtl.best.  Runs last, after the association scan: it resets the keep mask to the QC mask.  Covariates
-// and the include rule are the association scan's; the statistics of a hit come from gpca_qtl_stats, those of a trait's best SNP from
-// gpca_assoc_linear on that SNP (cli.py:_qtl).  scores is [n][kc].
-int run_qtl(gpca::Engine& eng, const Args& a, const gpca_host::PlinkFileset& fs, const std::vector<std::string>& fids,
-            const std::vector<std::string>& sample_ids, const std::vector<double>& scores, int kc, const std::vector<uint8_t>& inset,
-            const gpca::SnpStats& st) {
-    const int64_t n = (int64_t)sample_ids.size();
-    const int32_t P = a.have_qtl_pcs ? (int32_t)a.qtl_pcs : (int32_t)kc;
-    const int64_t T = (int64_t)a.qtl_pheno_table.names.size();
-    const int32_t nc = a.qtl_covar.empty() ? 0 : (int32_t)a.qtl_covar_table.names.size();
-    const int32_t Pc = P + nc;
-    const std::vector<double> Y = gpca_host::align_pheno(a.qtl_pheno_table, fids, sample_ids);
-    std::vector<double> cv;
-    if (nc) cv = gpca_host::align_pheno(a.qtl_covar_table, fids, sample_ids);
-    std::vector<double> C((size_t)n * (size_t)Pc + 1);
-    std::vector<uint8_t> include((size_t)n, 1);
-    int64_t n_inc = 0;
-    for (int64_t s = 0; s < n; ++s) {
-        bool ok = inset.empty() || inset[(size_t)s];
-        for (int32_t c = 0; c < P; ++c) C[(size_t)s * Pc + c] = scores[(size_t)s * kc + c];
-        for (int32_t c = 0; c < nc; ++c) C[(size_t)s * Pc + P + c] = cv[(size_t)s * nc + c];
-        for (int32_t c = 0; c < Pc; ++c) ok = ok && std::isfinite(C[(size_t)s * Pc + c]);
-        for (int64_t t = 0; t < T; ++t) ok = ok && std::isfinite(Y[(size_t)s * (size_t)T + (size_t)t]);
-        include[(size_t)s] = ok ? 1 : 0;
-        n_inc += ok;
+// --gpca-qtl-cis-pos FILE: cis-QTL mapping (gpca_assoc_qtl_cis) of every trait of --gpca-qtl-pheno that FILE gives a position, against the
+// SNPs that pass the SNP QC within --gpca-qtl-cis-window of it, with --gpca-qtl-cis-perm permutations from the table of
+// --gpca-qtl-cis-seed, in bands of traits, into P.qtl.cis (cli.py:_qtl_cis).  Y [n][T], C [n][Pc], include, rows: run_qtl's.
+int run_qtl_cis(gpca::Engine& eng, const Args& a, const gpca_host::PlinkFileset& fs, const std::vector<double>& Y, const std::vector<double>& C,
+                int32_t Pc, const std::vector<uint8_t>& include, const std::vector<int64_t>& rows, int64_t n, int64_t n_inc, int64_t df) {
+    const std::vector<std::string>& names = a.qtl_pheno_table.names;
+    const int64_t T = (int64_t)names.size(), P = a.qtl_cis_perm;
+    std::vector<std::string> chrom, tchrom((size_t)T);
+    std::vector<int64_t> pos, tpos((size_t)T, 0);
+    std::vector<uint8_t> have((size_t)T, 0);
+    for (int64_t r : rows) { chrom.push_back(fs.chromosomes[(size_t)r]); pos.push_back(fs.positions[(size_t)r]); }
+    int64_t n_pos = 0;
+    for (int64_t t = 0; t < T; ++t) {
+        const auto it = a.qtl_cis_table.find(names[(size_t)t]);
+        if (it == a.qtl_cis_table.end()) continue;
+        have[(size_t)t] = 1; tchrom[(size_t)t] = it->second.first; tpos[(size_t)t] = it->second.second; ++n_pos;
     }
-    const int64_t df = n_inc - Pc - 2;
-    if (df < 1) {
-        std::fprintf(stderr, "error: --gpca-qtl-pheno: %lld samples have every trait and covariate, which leaves no degree of freedom beside %d covariates\n",
-                     (long long)n_inc, (int)Pc);
+    std::vector<int64_t> win;
+    try { win = gpca_host::qtl_cis_windows(chrom, pos, tchrom, tpos, a.qtl_cis_window); }
+    catch (const std::runtime_error& e) { std::fprintf(stderr, "error: --gpca-qtl-cis-pos: %s\n", e.what()); return 1; }
+    for (int64_t t = 0; t < T; ++t) if (!have[(size_t)t]) win[2 * (size_t)t] = win[2 * (size_t)t + 1] = 0;
+    std::vector<uint32_t> perm((size_t)P * (size_t)n_inc + 1);
+    if (gpca_qtl_perm_table((uint64_t)a.qtl_cis_seed, n_inc, (int32_t)P, perm.data()) != GPCA_OK) {
+        std::fprintf(stderr, "error: --gpca-qtl-cis-perm: the permutation table was refused\n");
         return 1;
     }
-    const double tmin = a.have_qtl_t ? a.qtl_t : gpca_qtl_t_min(a.qtl_log10p, (double)df);
-    if (!(tmin < INFINITY)) {
-        std::fprintf(stderr, "error: --gpca-qtl-log10p: no finite t reaches the threshold at %lld degrees of freedom\n", (long long)df);
-        return 1;
+    std::vector<int64_t> n_var((size_t)T + 1), best_row((size_t)T + 1);
+    std::vector<double> best_r2((size_t)T + 1), best_stat(3 * (size_t)T + 1), perm_r2((size_t)T * (size_t)P + 1);
+    try {
+        // (no SNP passes the SNP QC: nothing to ask the device; every trait with a position gets its N_VAR = 0 line)
+        for (const auto& b : rows.empty() ? std::vector<std::pair<int64_t, int64_t>>() : gpca_host::assoc_qtl_cis_bands(T, P)) {
+            const size_t g0 = (size_t)b.first, gn = (size_t)(b.second - b.first);
+            std::vector<double> Yg((size_t)n * gn);
+            for (int64_t s = 0; s < n; ++s)
+                for (size_t j = 0; j < gn; ++j) Yg[(size_t)s * gn + j] = Y[(size_t)s * (size_t)T + g0 + j];
+            eng.check(gpca_assoc_qtl_cis(eng.handle(), Yg.data(), (int64_t)gn, Pc ? C.data() : nullptr, Pc, include.data(), a.qtl_vif, &win[2 * g0],
+                                         P ? perm.data() : nullptr, (int32_t)P, &n_var[g0], &best_row[g0], &best_r2[g0], &best_stat[3 * g0],
+                                         P ? &perm_r2[g0 * (size_t)P] : nullptr));
+        }
+    } catch (const gpca::Error& e) {
+        if (e.status() == GPCA_ERR_STATE) { std::fputs(kQtlNeedsResident, stderr); return 1; }
+        throw;
     }
-    const double r2_min = tmin * tmin / (tmin * tmin + (double)df);
-    eng.set_standardization(st.mu, st.sigma, st.keep);                                // every SNP that passes the SNP QC
-    std::vector<int64_t> rows;
-    for (size_t i = 0; i < st.keep.size(); ++i) if (st.keep[i]) rows.push_back((int64_t)i);
     gpca_host::ensure_parent(a.output_prefix);
+    {
+        gpca_host::QtlCisWriter w(a.output_prefix);
+        const double nan = std::nan("");
+        for (int64_t t = 0; t < T; ++t) {
+            const size_t g = (size_t)t;
+            if (!have[g]) { w.add_no_pos(names[g]); continue; }
+            if (n_var[g] == 0) { w.add_empty(names[g], tchrom[g], tpos[g]); continue; }
+            const size_t o = (size_t)rows[(size_t)best_row[g]];
+            double v[9] = {nan, nan, nan, nan, nan, nan, nan, nan, nan};
+            gpca_qtl_stats(best_stat[3 * g], best_stat[3 * g + 1], best_stat[3 * g + 2], (double)df, v);
+            v[3] = v[2] != v[2] ? nan : gpca_student_t_log10p(v[2], (double)df);
+            if (P > 0) {
+                double ba[7];
+                int32_t status = 0;
+                gpca_qtl_beta_approx(&perm_r2[g * (size_t)P], P, best_r2[g], (double)df, ba, &status);
+                v[4] = ba[1]; v[5] = ba[2]; v[6] = ba[3]; v[7] = ba[0]; v[8] = ba[5];
+            }
+            w.add_trait(names[g], tchrom[g], tpos[g], n_var[g], fs.variant_ids[o], fs.positions[o], fs.allele1[o], v);
+        }
+    }
+    char buf[768];
+    std::snprintf(buf, sizeof buf, "cis-QTL mapping of %lld of %lld traits within %lld bp with %d covariates on %lld of %lld samples and %lld permutations "
+                  "(seed %lld), written to %s.qtl.cis", (long long)n_pos, (long long)T, (long long)a.qtl_cis_window, (int)Pc, (long long)n_inc, (long long)n,
+                  (long long)P, (long long)a.qtl_cis_seed, a.output_prefix.c_str());
+    logmsg(buf);
+    return 0;
+}
+
+// The scan of every SNP against every trait of run_qtl, into P.qtl.hits and P.qtl.best (cli.py:_qtl_trans).  Y [n][T], C [n][Pc],
+// include, rows (the SNPs that pass the SNP QC), df, r2_min and tmin are run_qtl's.
+int run_qtl_trans(gpca::Engine& eng, const Args& a, const gpca_host::PlinkFileset& fs, const std::vector<double>& Y, const std::vector<double>& C,
+                  int32_t Pc, int32_t P, const std::vector<uint8_t>& include, const std::vector<int64_t>& rows, int64_t T, int64_t n, int64_t n_inc,
+                  int64_t df, double r2_min, double tmin) {
     const std::vector<std::string>& names = a.qtl_pheno_table.names;
     const double nan = std::nan("");
     std::vector<double> b2((size_t)T, nan), beta((size_t)T, nan), se((size_t)T, nan), tt((size_t)T, nan);
@@ -920,6 +972,57 @@ int run_qtl(gpca::Engine& eng, const Args& a, const gpca_host::PlinkFileset& fs,
                   "written to %s.qtl.hits and %s.qtl.best", rows.size(), (long long)T, (int)Pc, (int)P, (long long)n_inc, (long long)n, (long long)n_hits, tmin,
                   a.output_prefix.c_str(), a.output_prefix.c_str());
     logmsg(buf);
+    return 0;
+}
+
+// --gpca-qtl-pheno FILE: the many-trait QTL scan (gpca_assoc_qtl) of every SNP that passes the SNP QC against every column of FILE, in
+// row bands, into P.qtl.hits and P.qtl.best.  Runs last, after the association scan: it resets the keep mask to the QC mask.  Covariates
+// and the include rule are the association scan's; the statistics of a hit come from gpca_qtl_stats, those of a trait's best SNP from
+// gpca_assoc_linear on that SNP (cli.py:_qtl).  scores is [n][kc].
+int run_qtl(gpca::Engine& eng, const Args& a, const gpca_host::PlinkFileset& fs, const std::vector<std::string>& fids,
+            const std::vector<std::string>& sample_ids, const std::vector<double>& scores, int kc, const std::vector<uint8_t>& inset,
+            const gpca::SnpStats& st) {
+    const int64_t n = (int64_t)sample_ids.size();
+    const int32_t P = a.have_qtl_pcs ? (int32_t)a.qtl_pcs : (int32_t)kc;
+    const int64_t T = (int64_t)a.qtl_pheno_table.names.size();
+    const int32_t nc = a.qtl_covar.empty() ? 0 : (int32_t)a.qtl_covar_table.names.size();
+    const int32_t Pc = P + nc;
+    const std::vector<double> Y = gpca_host::align_pheno(a.qtl_pheno_table, fids, sample_ids);
+    std::vector<double> cv;
+    if (nc) cv = gpca_host::align_pheno(a.qtl_covar_table, fids, sample_ids);
+    std::vector<double> C((size_t)n * (size_t)Pc + 1);
+    std::vector<uint8_t> include((size_t)n, 1);
+    int64_t n_inc = 0;
+    for (int64_t s = 0; s < n; ++s) {
+        bool ok = inset.empty() || inset[(size_t)s];
+        for (int32_t c = 0; c < P; ++c) C[(size_t)s * Pc + c] = scores[(size_t)s * kc + c];
+        for (int32_t c = 0; c < nc; ++c) C[(size_t)s * Pc + P + c] = cv[(size_t)s * nc + c];
+        for (int32_t c = 0; c < Pc; ++c) ok = ok && std::isfinite(C[(size_t)s * Pc + c]);
+        for (int64_t t = 0; t < T; ++t) ok = ok && std::isfinite(Y[(size_t)s * (size_t)T + (size_t)t]);
+        include[(size_t)s] = ok ? 1 : 0;
+        n_inc += ok;
+    }
+    const int64_t df = n_inc - Pc - 2;
+    if (df < 1) {
+        std::fprintf(stderr, "error: --gpca-qtl-pheno: %lld samples have every trait and covariate, which leaves no degree of freedom beside %d covariates\n",
+                     (long long)n_inc, (int)Pc);
+        return 1;
+    }
+    const double tmin = a.have_qtl_t ? a.qtl_t : gpca_qtl_t_min(a.qtl_log10p, (double)df);
+    if (!(tmin < INFINITY)) {
+        std::fprintf(stderr, "error: --gpca-qtl-log10p: no finite t reaches the threshold at %lld degrees of freedom\n", (long long)df);
+        return 1;
+    }
+    const double r2_min = tmin * tmin / (tmin * tmin + (double)df);
+    eng.set_standardization(st.mu, st.sigma, st.keep);                                // every SNP that passes the SNP QC
+    std::vector<int64_t> rows;
+    for (size_t i = 0; i < st.keep.size(); ++i) if (st.keep[i]) rows.push_back((int64_t)i);
+    gpca_host::ensure_parent(a.output_prefix);
+    if (!a.qtl_cis_only) {
+        const int rc = run_qtl_trans(eng, a, fs, Y, C, Pc, P, include, rows, T, n, n_inc, df, r2_min, tmin);
+        if (rc) return rc;
+    }
+    if (!a.qtl_cis_pos.empty()) return run_qtl_cis(eng, a, fs, Y, C, Pc, include, rows, n, n_inc, df);
     return 0;
 }
 
@@ -1884,6 +1987,18 @@ int main(int argc, char** argv) {
                              (long long)kQtlMaxCovariates);
                 return 2;
             }
+        }
+        if (a.qtl_cis_pos.empty() && (a.qtl_cis_only || a.have_qtl_cis_window || a.have_qtl_cis_perm || a.have_qtl_cis_seed)) {
+            std::fprintf(stderr, "error: --gpca-qtl-cis-window, --gpca-qtl-cis-perm, --gpca-qtl-cis-seed and --gpca-qtl-cis-only need --gpca-qtl-cis-pos\n");
+            return 2;
+        }
+        if (!a.qtl_cis_pos.empty()) {
+            if (a.qtl_pheno.empty()) { std::fprintf(stderr, "error: --gpca-qtl-cis-pos needs --gpca-qtl-pheno\n"); return 2; }
+            if (a.qtl_cis_window < 0) { std::fprintf(stderr, "error: --gpca-qtl-cis-window must be at least 0\n"); return 2; }
+            if (a.qtl_cis_perm < 0 || a.qtl_cis_perm > 65535) { std::fprintf(stderr, "error: --gpca-qtl-cis-perm must lie in [0, 65535]\n"); return 2; }
+            if (a.qtl_cis_seed < 0) { std::fprintf(stderr, "error: --gpca-qtl-cis-seed must be at least 0\n"); return 2; }
+            try { a.qtl_cis_table = gpca_host::read_trait_pos(a.qtl_cis_pos); }
+            catch (const std::runtime_error& e) { std::fprintf(stderr, "error: --gpca-qtl-cis-pos: %s\n", e.what()); return 2; }
         }
         if (a.assoc_ldsc && (a.ld_score.empty() || a.assoc_pheno.empty())) {
             std::fprintf(stderr, "error: --gpca-assoc-ldsc needs --gpca-ld-score and --gpca-assoc-pheno\n");

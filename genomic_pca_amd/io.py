@@ -870,6 +870,118 @@ def write_qtl_best(prefix: str, traits: Sequence[str], chromosomes: Sequence[str
     return path
 
 
+# ---- cis-QTL mapping (gpca_assoc_qtl_cis, gpca_qtl_beta_approx; include/gpca.h section a25) ------------------------------------------------
+QTL_CIS_RESULT_BYTES_MAX = 256 << 20      # assoc_qtl_cis_bands: perm_r2 [G][P] f64 of one call
+
+
+def qtl_cis_windows(chromosomes: Sequence[str], positions: Sequence[int], trait_chrom: Sequence[str], trait_pos: Sequence[int],
+                    window_bp: int) -> np.ndarray:
+    """win [G][2] (int64) for gpca_assoc_qtl_cis: [lo, hi) over the kept SNPs given (in their order) with |pos - trait_pos| <= window_bp
+    on the trait's chromosome; lo = hi where none qualifies, [0, 0) for a chromosome the SNPs do not have.  The SNPs are ordered as
+    ld_windows requires, and refused in its words."""
+    K = len(chromosomes)
+    pos = np.asarray(positions, np.int64)
+    if pos.shape != (K,):
+        raise ValueError("qtl_cis_windows: one position per chromosome entry")
+    if len(trait_chrom) != len(trait_pos):
+        raise ValueError("qtl_cis_windows: one position per trait chromosome")
+    runs = {}
+    s = 0
+    while s < K:
+        c = normalize_chromosome_name(chromosomes[s])
+        if c in runs:
+            raise ValueError(f"qtl_cis_windows: chromosome '{chromosomes[s]}' reappears at variant {s} after another chromosome: sort the variants")
+        e = s + 1
+        while e < K and normalize_chromosome_name(chromosomes[e]) == c:
+            if pos[e] < pos[e - 1]:
+                raise ValueError(f"qtl_cis_windows: the position of variant {e} ({int(pos[e])}) is below that of the variant before it on chromosome "
+                                 f"'{chromosomes[e]}': sort the variants")
+            e += 1
+        runs[c] = (s, e)
+        s = e
+    w = int(window_bp)
+    win = np.zeros((len(trait_chrom), 2), np.int64)
+    for g, (tc, tp) in enumerate(zip(trait_chrom, trait_pos)):
+        run = runs.get(normalize_chromosome_name(tc))
+        if run is None:
+            continue
+        s, e = run
+        win[g, 0] = s + int(np.searchsorted(pos[s:e], int(tp) - w, side="left"))
+        win[g, 1] = s + int(np.searchsorted(pos[s:e], int(tp) + w, side="right"))
+    return win
+
+
+def read_trait_pos(path: str) -> dict:
+    """A `TRAIT CHROM POS` table (that header; whitespace-separated): {trait: (chrom, pos)}.  A later line of a trait replaces an
+    earlier one."""
+    out = {}
+    with open(path) as f:
+        head = f.readline().split()
+        if head != ["TRAIT", "CHROM", "POS"]:
+            raise ValueError(f"{path}: the header must be 'TRAIT CHROM POS'")
+        for ln, line in enumerate(f, 2):
+            t = line.split()
+            if not t:
+                continue
+            if len(t) != 3:
+                raise ValueError(f"{path}: line {ln} does not hold TRAIT CHROM POS")
+            digits = t[2][1:] if t[2][:1] in ("+", "-") else t[2]
+            if not (digits.isascii() and digits.isdigit() and len(t[2]) <= 18):
+                raise ValueError(f"{path}: line {ln}: the position '{t[2]}' is not an integer")
+            out[t[0]] = (t[1], int(t[2]))
+    return out
+
+
+def assoc_qtl_cis_bands(G: int, P: int):
+    """[g0, g1) bands of the G traits for gpca_assoc_qtl_cis such that perm_r2 [g1 - g0][P] (f64) stays within QTL_CIS_RESULT_BYTES_MAX
+    (at least one trait per band; one band when P = 0)."""
+    G, P = int(G), int(P)
+    step = max(QTL_CIS_RESULT_BYTES_MAX // (8 * P), 1) if P > 0 else max(G, 1)
+    return [(g0, min(g0 + step, G)) for g0 in range(0, G, step)]
+
+
+def write_qtl_cis(prefix: str, traits: Sequence[str], trait_pos, res: dict, ids: Sequence[str], var_pos: Sequence[int],
+                  a1: Sequence[str]) -> str:
+    """P.qtl.cis: one tab-separated line per trait in the order given, `#TRAIT CHROM POS N_VAR ID VAR_POS A1 BETA SE T_STAT LOG10P_NOMINAL
+    TRUE_DF SHAPE1 SHAPE2 PVAL_PERM LOG10P_BETA`.  trait_pos [G]: (chrom, pos) or None; res: assoc_qtl_cis's dict over the same traits
+    (bands concatenated); ids, var_pos, a1: per kept row.  The SNP is the window's best row; BETA, SE, T_STAT by qtl_stats, LOG10P_NOMINAL
+    at df = n - Pc - 2, the last five by qtl_beta_approx (NA without permutations).  A trait without a position is a row of NA; a
+    trait with N_VAR = 0 has NA from ID on.  Numbers as %.6g, NaN as NA."""
+    from .engine import GpcaEngine
+    path = f"{prefix}.qtl.cis"
+    G = len(traits)
+    if len(trait_pos) != G or any(len(res[k]) != G for k in ("n_var", "best_row", "best_r2", "best_stat", "perm_r2")):
+        raise ValueError("write_qtl_cis: one entry per trait in every column")
+    df = float(res["df"])
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    with open(path, "w") as f:
+        f.write("#TRAIT\tCHROM\tPOS\tN_VAR\tID\tVAR_POS\tA1\tBETA\tSE\tT_STAT\tLOG10P_NOMINAL\tTRUE_DF\tSHAPE1\tSHAPE2\tPVAL_PERM\tLOG10P_BETA\n")
+        for g in range(G):
+            if trait_pos[g] is None:
+                f.write(traits[g] + "\tNA" * 15 + "\n")
+                continue
+            chrom, tp = trait_pos[g]
+            nv = int(res["n_var"][g])
+            if nv == 0:
+                f.write(f"{traits[g]}\t{chrom}\t{int(tp)}\t0" + "\tNA" * 12 + "\n")
+                continue
+            row = int(res["best_row"][g])
+            xb, sxx, yy = (float(v) for v in res["best_stat"][g])
+            beta, se, t = GpcaEngine.qtl_stats(xb, sxx, yy, df)[0]
+            l10 = GpcaEngine.student_t_log10p(t, df) if not np.isnan(t) else float("nan")
+            pr = np.asarray(res["perm_r2"][g], np.float64)
+            if pr.size:
+                ba = GpcaEngine.qtl_beta_approx(pr, float(res["best_r2"][g]), df)
+                tail = [ba["true_df"], ba["shape1"], ba["shape2"], ba["pval_perm"], ba["log10p_beta"]]
+            else:
+                tail = [float("nan")] * 5
+            f.write(f"{traits[g]}\t{chrom}\t{int(tp)}\t{nv}\t{ids[row]}\t{int(var_pos[row])}\t{a1[row]}\t{_g6(beta)}\t{_g6(se)}\t{_g6(t)}\t"
+                    f"{_g6(l10)}\t" + "\t".join(_g6(v) for v in tail) + "\n")
+    return path
+
+
 # ---- LD scores and LD-score regression (gpca_ld_score, gpca_ld_score_total, gpca_ldsc_fit; include/gpca.h section a19) -----------
 def ld_score_sum(K: int, bands):
     """(acc int64 [K], partners int64 [K]) = the bands of GpcaEngine.ld_score added up.  bands: ((row0, row1), score[, partners]) over

@@ -1065,8 +1065,8 @@ GPCA_API int gpca_fstat(const int64_t* acc, const int64_t* cnt, int32_t B, int32
  * (the message names it), max_vif < 1 or not finite; GPCA_ERR_INVALID_GENOTYPE names the row; GPCA_ERR_OOM is checked before any
  * allocation), and GPCA_ERR_BAD_ARG for r2_min outside [0, 1] or NaN, cap < 0, NULL record buffers with cap > 0, NULL hit_count or
  * n_found, only one of best_r2 / best_row.
- * Not there: cis windows and per-trait row ranges, permutation or beta-approximated empirical p-values, per-trait sample sets and missing
- * phenotypes, interaction terms, case / control traits, bf16 or other reduced-precision operands, streamed and row-sharded handles. */
+ * Not there (cis windows and permutation p-values are section a25): per-trait sample sets and missing phenotypes, interaction terms,
+ * case / control traits, bf16 or other reduced-precision operands, streamed and row-sharded handles. */
 GPCA_API int gpca_assoc_qtl(gpca_handle* h, const double* Y /* [N][T] */, int64_t T, const double* C /* [N][Pc] or NULL */, int32_t Pc,
                             const uint8_t* include /* [N] or NULL */, double max_vif, double r2_min, int64_t row0, int64_t row1,
                             double* rowinfo /* [rows][4] or NULL */, double* yy /* [T] or NULL */, uint32_t* hit_count /* [rows] */,
@@ -1077,6 +1077,61 @@ GPCA_API void gpca_qtl_stats(double xb, double sxx, double yy_t, double df, doub
  * neighbouring doubles: the cutoff a threshold on the p-value becomes (r2_min = t^2 / (t^2 + df)).  0 for log10p <= 0, NaN for NaN or
  * df <= 0, +inf when no finite t reaches it.  Host only. */
 GPCA_API double gpca_qtl_t_min(double log10p, double df);
+
+/* ---- a25: cis-QTL mapping: for each of G traits the best kept row of its own window [lo, hi) and the null distribution of that best
+ * r2 under P permutations of the trait (FastQTL, tensorQTL's cis mode).  Inputs as a24 (Y [N][G], C [N][Pc], include, max_vif), plus
+ * win [G][2] = [lo, hi) in kept rows, 0 <= lo <= hi <= K, and perm [P][n] u32, 0 <= P <= 65 535, n = the included samples: every row a
+ * permutation of 0 .. n - 1 over the included samples in ascending sample order; one table serves every trait of the call.
+ *  1. host: a12's step 1 once on the G columns: the residuals b_t (f64, over the included samples), the orthonormal covariate basis Q,
+ *     yy_t, df = n - Pc - 2.
+ *  2. device: the per-row pass of a24 (sums, rowinfo) once over the union of the windows.
+ *  3. the panel of trait t, P + 1 columns in a24's layout.  Column 0 is (float) b_t: the bits a24 stages.  Column p + 1 is the permuted
+ *     residual taken back into the covariates' complement, on the device in f64 without fused multiply-add:
+ *       v_i = b_t[perm[p][i]];  c_j = sum_i Q_ij v_i, i ascending, one running sum;  s_i = sum_j Q_ij c_j, j ascending, one running
+ *       sum;  the value is (float)(v_i - s_i).  Q is the basis of step 1 as it stands (its columns are centred: there is no intercept
+ *     column).  With Pc = 0 the value is (float) v_i.  yy of every permuted column is yy_t (the unpermuted residual's norm: FastQTL's rule).
+ *  4. a24's steps 2 and 3 on the kept rows [lo, hi) and all P + 1 columns, with the same liveness rule: xb, xx, sxx carry
+ *     gpca_assoc_linear's bits, r2 = (xb xb) / (sxx yy_t) in f64; per column the largest r2 over the live rows, the smallest row on a tie.
+ * Outputs per trait: n_var = the live rows of the window; best_row, best_r2 and best_stat [3] = (xb, sxx, yy_t) of column 0's best row
+ * (gpca_qtl_stats applies directly); perm_r2 [P] = the best r2 of every permuted column.  A window without a live row: n_var = 0,
+ * best_row = -1, NaN everywhere else.  Every output of a trait is a function of that trait, its window, the table, C and include alone:
+ * not of the other traits of the call or their order, not of the launch plan (GPCA_QTL_TW is honoured as in a24), not of int8 / 2-bit
+ * residency or a GPCA_PREC_F32_MFMA handle.  No atomic anywhere.
+ * Errors: as a24, plus GPCA_ERR_BAD_ARG for a window outside [0, K] or with lo > hi (the message names the trait), for P out of range,
+ * for perm = NULL or perm_r2 = NULL with P > 0, and for a table row that is not a permutation (checked on the host; the message names the
+ * row); GPCA_ERR_STATE for streamed and row-sharded handles.
+ * gpca_qtl_perm_panel: step 3 alone on the caller's b [n] and Q [n][Pc] (row-major): out [P][n] = the columns 1 .. P.  Needs no genotypes.
+ * gpca_qtl_perm_table (host only, a pure function): row p starts as 0 .. n - 1; for step s = 0 .. n - 2, with i = n - 1 - s: r = word
+ *   s & 3 of philox4x32-10(counter = (s >> 2, p, 0, 0x51544C50), key = (seed low word, seed high word)); j = ((uint64) r (i + 1)) >> 32;
+ *   the entries i and j change places (Fisher-Yates with a multiply-shift index).
+ * gpca_qtl_beta_approx (host only): FastQTL's beta approximation.  With p(r2, d) = the two-sided Student p-value of t^2 = d r2 / (1 - r2)
+ *   at d degrees of freedom (gpca_student_t_log10p): NaN entries of perm_r2 drop out, P' are left.
+ *   (a) pval_perm = (1 + #{perm_r2 >= r2_nominal}) / (P' + 1).  With P' < 10 every other field is NaN.
+ *   (b) true_df = the root in d of log shape1_mom(d) = 0, where shape1_mom = m (m (1 - m) / v - 1) from the mean m and the variance v
+ *       (divisor P' - 1) of p(perm_r2, d): bisection on [1, 2 df] down to an interval of 1e-6 df, its midpoint.  No sign change: d = df
+ *       and status bit 1.
+ *   (c) shape1, shape2 = the maximum-likelihood Beta fit of p(perm_r2, true_df): Newton with step halving on psi(a) - psi(a + b) =
+ *       mean log p, psi(b) - psi(a + b) = mean log(1 - p), started at the moment estimates.  On failure: the moment estimates and status
+ *       bit 2.
+ *   (d) log10p_nominal_true = -log10 p(r2_nominal, true_df).
+ *   (e) log10p_beta = -log10 I_x(shape1, shape2) at x = p(r2_nominal, true_df): the continued fraction, assembled in log space from
+ *       log x, so it does not underflow.
+ *   out [7] = pval_perm, true_df, shape1, shape2, log10p_nominal_true, log10p_beta, the moment estimate of shape1.  All NaN for a NaN
+ *   r2_nominal or df < 1.
+ * The P.qtl.cis file of the command lines (io.write_qtl_cis, formats.hpp QtlCisWriter): one line per trait; a trait without a position
+ * is `TRAIT` and 15 `NA`; a trait with n_var = 0 keeps what is known of it, `TRAIT CHROM POS 0`, and has `NA` in the 12 columns from ID on.
+ * Not there: conditionally independent signals, q-values across traits, per-trait sample sets, interaction terms, adaptive permutation
+ * counts, grouped phenotypes, tensorQTL's or FastQTL's own digits, streamed and row-sharded handles. */
+GPCA_API int gpca_assoc_qtl_cis(gpca_handle* h, const double* Y /* [N][G] */, int64_t G, const double* C /* [N][Pc] or NULL */, int32_t Pc,
+                                const uint8_t* include /* [N] or NULL */, double max_vif, const int64_t* win /* [G][2] */,
+                                const uint32_t* perm /* [P][n]; NULL iff P = 0 */, int32_t P, int64_t* n_var /* [G] */,
+                                int64_t* best_row /* [G] */, double* best_r2 /* [G] */, double* best_stat /* [G][3] */,
+                                double* perm_r2 /* [G][P]; NULL iff P = 0 */);
+GPCA_API int gpca_qtl_perm_panel(gpca_handle* h, const double* b /* [n] */, const double* Q /* [n][Pc] */, int32_t Pc, int64_t n,
+                                 const uint32_t* perm /* [P][n] */, int32_t P, float* out /* [P][n] */);
+GPCA_API int gpca_qtl_perm_table(uint64_t seed, int64_t n, int32_t P, uint32_t* out /* [P][n] */);
+GPCA_API int gpca_qtl_beta_approx(const double* perm_r2 /* [P] */, int64_t P, double r2_nominal, double df, double* out /* [7] */,
+                                  int32_t* status /* or NULL */);
 
 /* ---- f3: the stages of EigenSNPCoreAlgorithm::compute_pca (main.rs:311-327, 359-366) ------------------------------------------
  * The algorithm lives in the un-vendored efficient_pca crate (Cargo.toml:30, branch "main", no pinned revision): what follows is
